@@ -91,7 +91,35 @@ def parse_args():
     ap.add_argument("--tp-steps", type=int, default=2000,
                     help="extra leg: steps with the trajectory predictor in the observation (algo.use_TP_net: 1, the reference's "
                          "default config), reported as `tp_mode`; 0 = skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the LAST step of the timed region returned to its caller (rank 0): every leaf of the stepped tensordict as "
+                         "DIR/<dotted key>.npy, float32 (float64 for integer / bool leaves), for comparing two builds output for output.  Whole "
+                         "batches up to 60 MB; beyond that a fixed seeded sample of envs (DIR/env_index.npy names them, in order)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 60_000_000     # --dump-outputs: all arrays together, headers aside (under 64 MB)
+
+
+def step_outputs(td):
+    """Every leaf of a stepped tensordict under its dotted key."""
+    return {k if isinstance(k, str) else ".".join(k): td[k] for k in td.keys(include_nested=True, leaves_only=True)}
+
+
+def dump_rows(leaves, E):
+    """Rows of every leaf (batch dimension E first) as float32 / float64 (integer and bool leaves as float64, exact): the whole batch when it fits
+    DUMP_BYTES, else a sorted sample of envs drawn with a fixed seed, named by the extra entry `env_index`."""
+    import numpy as np
+    import torch
+    dt = {k: torch.float32 if v.is_floating_point() and v.element_size() <= 4 else torch.float64 for k, v in leaves.items()}
+    for k, v in leaves.items():
+        assert isinstance(v, torch.Tensor) and v.shape[0] == E, f"--dump-outputs: {k} is not a [{E}, ...] tensor"
+    n = min(E, DUMP_BYTES // (8 + sum(v[0].numel() * dt[k].itemsize for k, v in leaves.items())))
+    dev = next(iter(leaves.values())).device
+    idx = torch.arange(E, device=dev) if n == E else torch.from_numpy(np.sort(np.random.default_rng(0).choice(E, n, replace=False))).to(dev)
+    out = {k: v.index_select(0, idx).to(dt[k]) for k, v in leaves.items()}
+    out["env_index"] = idx.to(torch.float64)
+    return out
 
 
 def self_launch(args):
@@ -329,6 +357,8 @@ def main():
     env.success_rate_fn = rate_hook
 
     coll_events, coll_host_us = [], []
+    # --dump-outputs: the step that ends the timed region is number warmup + steps of `run`; its outputs are views of buffers a reset rewrites
+    dump = {"last": args.warmup + args.steps, "out": None} if args.dump_outputs and rank == 0 else None
 
     def run(n):
         for _ in range(n):
@@ -336,6 +366,8 @@ def main():
             env.step(tds[i % R])
             progress["t"] = i + 1
             if (i + 1) % args.episode == 0:          # lock-step episodes: every env is done now
+                if dump is not None and i + 1 == dump["last"]:       # the region's last step ends an episode: copy its outputs before the reset
+                    dump["out"] = {k: v.clone() for k, v in step_outputs(tds[i % R]).items()}
                 reset_td.set("_reset", env._bufs["done"])
                 env.reset(reset_td)
             if dist is not None and (i + 1) % rollout == 0:
@@ -404,6 +436,8 @@ def main():
     closing_barrier_us = (time.perf_counter() - t0 - elapsed) * 1e6
     clock_probe_after = env.clock_probe()         # behind the region and its wall clock: not part of any timed quantity
     torch.cuda.synchronize(device)
+    if dump is not None:                          # (before the launches below step the env on)
+        dump["rows"] = dump_rows(dump["out"] or step_outputs(tds[(dump["last"] - 1) % R]), E)
     clock_mhz = {"before_region": env.clock_mhz(clock_probe_before), "after_region": env.clock_mhz(clock_probe_after)}
     env.enable_kernel_timing(0)
     region_ms = env.region_ms()
@@ -811,6 +845,11 @@ def main():
             "roofline": roofline, "cpu_baseline": cpu_baseline, "abi_rate": abi_rate, "configs": configs or None,
             "tp_mode": tp_mode, "stream_shards": streams_mode,
         }
+        if dump is not None:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, t in dump["rows"].items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), t.cpu().numpy())
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

@@ -36,6 +36,8 @@ Fixtures written (tests/golden/*.npz):
                on whole [E,T,A,1] tensors: what the data-parallel form (sharding.py) must reproduce from gathered moments
   g_episode_resetpid_*  the same loop with the controller's reset_pid = the root `done` of the stepped tensordict
                (transforms.py:449-454), across resets of the done envs (their deterministic effects restated, see the function)
+  g_task_hideandseek.json  cfg/task/HideAndSeek.yaml as parsed (values only): the reference's unedited task file for test_manifest.py /
+               test_motor_input.py
 """
 import ast
 import importlib.util
@@ -1500,3 +1502,19 @@ def gen_learner_moments(E=64, T=8, A=3, rollouts=3, seed=20261001):
 if __name__ == "__main__":
     gen_genbuffer()
     gen_learner_moments()
+
+
+# ---- the reference's task file as data: the values hydra / load_cfg read from cfg/task/HideAndSeek.yaml, for tests that check this build's task
+# file and the action-input rule against them without a reference checkout -------------------------------------------------------------------
+def gen_task_file():
+    import json
+    task = yaml.safe_load(open(os.path.join(REF, "cfg/task/HideAndSeek.yaml")))
+    text = json.dumps(task, indent=1, sort_keys=True) + "\n"
+    assert yaml.safe_load(text) == task                  # JSON read back as YAML (config.load_cfg) gives the same values
+    with open(os.path.join(OUT, "g_task_hideandseek.json"), "w") as f:
+        f.write(text)
+    print("wrote g_task_hideandseek.json")
+
+
+if __name__ == "__main__":
+    gen_task_file()

@@ -138,6 +138,34 @@ def test_bench_loop_with_two_hip_shards_reproduces_the_whole_batch():
 
 
 @pytest.mark.gpu
+def test_bench_dumps_the_outputs_of_its_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: what the last step of the timed region handed its caller, one float32 / float64 .npy per leaf of the stepped tensordict,
+    the same bytes from run to run.  Episodes of 20 steps: after 8 warm-up + 12 timed steps every env is done — those are the step's outputs, copied
+    before the boundary's reset rewrites them — and after 8 + 11 none is, so --steps sets the step that is dumped.  At 65 536 envs the whole tree
+    exceeds the 64 MB cap and a fixed sample of envs is written."""
+    import numpy as np
+    common = ["--gpus", "1", "--envs", "65536", "--warmup", "8", "--episode", "20", "--settle-steps", "100", "--no-cpu-baseline", "--tp-steps", "0",
+              "--config-steps", "0", "--abi-steps", "0", "--no-traffic-live"]
+    dumps = {}
+    for tag, steps in (("a", 12), ("b", 12), ("c", 11)):
+        d = tmp_path / tag
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--dump-outputs", str(d), *common],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])["steps"] == steps
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64e6
+        dumps[tag] = {f.name[:-4]: np.load(f) for f in d.iterdir()}
+    a, b, c = dumps["a"], dumps["b"], dumps["c"]
+    assert set(a) == set(b) == set(c) and {"next.agents.observation.state_self", "next.agents.reward", "next.done", "env_index"} <= set(a)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k], equal_nan=True), k
+    idx = a["env_index"]
+    assert 0 < len(idx) < 65536 and np.all(np.diff(idx) > 0) and idx[-1] < 65536 and all(v.shape[0] == len(idx) for v in a.values())
+    assert np.all(a["next.done"] == 1) and np.all(c["next.done"] == 0)
+    assert not np.array_equal(a["next.agents.observation.state_self"], c["next.agents.observation.state_self"])
+
+
+@pytest.mark.gpu
 def test_bench_under_torchrun_with_one_rccl_rank():
     """Multi-GPU day one: the driver launches `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`.  With ONE rank
     torchrun still sets WORLD_SIZE / RANK / MASTER_*, so bench.py runs its launched-by-torchrun branch; HNS_BENCH_FORCE_DIST=1 makes it initialise the

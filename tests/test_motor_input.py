@@ -50,9 +50,9 @@ def test_action_input_follows_the_key_train_py_decides_on(tmp_path):
     cfg = config.make_cfg({})
     assert cfg.task.action_input == "policy" and config.resolve_hns_cfg(cfg).action_input == abi.HNS_ACTION_POLICY
     assert config.resolve_hns_cfg(config.make_cfg({"action_input": "motor"})).action_input == abi.HNS_ACTION_MOTOR
-    if os.path.isfile("/root/reference/cfg/task/HideAndSeek.yaml"):  # authoring container only: the reference's file itself, verbatim
-        cfg = config.load_cfg("/root/reference/cfg/task/HideAndSeek.yaml")
-        assert str(cfg.task.action_transform) == "PIDrate" and config.resolve_hns_cfg(cfg).action_input == abi.HNS_ACTION_MOTOR
+    # the reference's task file itself, as parsed (golden/make_golden.py::gen_task_file)
+    cfg = config.load_cfg(os.path.join(ROOT, "tests", "golden", "g_task_hideandseek.json"))
+    assert str(cfg.task.action_transform) == "PIDrate" and config.resolve_hns_cfg(cfg).action_input == abi.HNS_ACTION_MOTOR
 
 
 # ---- against the reference: the commands of its own _inv_call --------------------------------------------------------------------------------

@@ -46,7 +46,7 @@ def _worker(rank, world, port, E_total, steps, q):
     success = torch.from_numpy(arrs["stats"][abi.STAT_NAMES.index("success")])
     norm, rate = sharding.normalise_advantages(adv, success)
     q.put((rank, offset, count, arrs["drone_state"], arrs["stats"], rew, norm.numpy(), rate))
-    dist.barrier()
+    dist.monitored_barrier()          # gloo's CPU barrier: dist.barrier() probes for an accelerator, which opens the GPU in every rank of a CPU job
     dist.destroy_process_group()
 
 
@@ -124,7 +124,7 @@ def _job8_worker(rank, world, port, E_total, steps, q):
     gb.insert_history(np.random.default_rng(200 + rank).random((n, gb.task_dim)).astype(np.float32))
     q.put((rank, offset, count, arrs["drone_state"], arrs["target_pos"], arrs["stats"], np.stack(rews), rates,
            np.array(gb.inner._history_buffer, copy=True), gb.buffer_share(count, offset, 0.3)))
-    dist.barrier()
+    dist.monitored_barrier()          # (CPU barrier, see _worker)
     dist.destroy_process_group()
 
 
@@ -204,7 +204,7 @@ def _genbuf_worker(rank, world, port, q):
     share = gb.buffer_share(100, 100 * rank, 0.3)
     mean = sharding.global_mean(torch.full((100,), float(rank)))
     q.put((rank, hists, share, mean))
-    dist.barrier()
+    dist.monitored_barrier()          # (CPU barrier, see _worker)
     dist.destroy_process_group()
 
 
@@ -436,7 +436,7 @@ def _learner_worker(rank, world, port, q):
         adv_n, _ = sharding.normalise_advantages(adv, returns=ret, value_normalizer=vn)
         outs.append((adv_n.numpy(), vn.normalize(ret).numpy(), vn.running_mean.numpy().copy(), vn.running_mean_sq.numpy().copy(), vn.debiasing_term.numpy().copy()))   # numpy: torch tensors travel as shared-memory handles the exiting worker takes with it
     q.put((rank, off, cnt, outs))
-    dist.barrier()
+    dist.monitored_barrier()          # (CPU barrier, see _worker)
     dist.destroy_process_group()
 
 

@@ -1,5 +1,5 @@
-import sys, time, ctypes as C
-sys.path.insert(0, "/root/repo")
+import os, sys, time, ctypes as C
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, hns_amd
 from hns_amd import abi
 lib = abi.load_library()

@@ -2,7 +2,7 @@
 """The 65 536-env batch as 1 / 2 / 4 independent shards on separate HIP streams of one GPU (no join between steps):
 per-step time and aggregate throughput."""
 import os, sys, time, ctypes as C
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, hns_amd
 from hns_amd import config
 from hns_amd.env import HideAndSeek

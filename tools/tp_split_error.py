@@ -1,6 +1,8 @@
 """Accuracy of the two-term fp16 split used by hns_tp_lstm_kernel, emulated in numpy on the reference golden weights/window: plain fp32 and the split against fp64."""
+import os
+
 import numpy as np
-g = np.load('/root/repo/tests/golden/g_tp_obs.npz')
+g = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests', 'golden', 'g_tp_obs.npz'))
 Wih, Whh = g['w_lstm_weight_ih_l0'].astype(np.float32), g['w_lstm_weight_hh_l0'].astype(np.float32)
 b = (g['w_lstm_bias_ih_l0'] + g['w_lstm_bias_hh_l0']).astype(np.float32)
 Wfc, bfc = g['w_fc_weight'].astype(np.float32), g['w_fc_bias'].astype(np.float32)
