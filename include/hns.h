@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define HNS_ABI_VERSION 5
+#define HNS_ABI_VERSION 6
 #define HNS_MAX_AGENTS 7    /* pursuers per env: a workgroup is 64 envs = A pursuer waves + one env wave (<= 512 threads) */
 #define HNS_MAX_CYLINDERS 16
 #define HNS_NUM_STATS 24    /* hideandseek.py:400-425 */
@@ -167,7 +167,35 @@ typedef struct hns_cfg {
                                   every env (reset or not) integrates one dt with no rotor force (gravity + damping), every evader moves one dt with
                                   the velocity it holds; then the observation of all envs is recomputed (isaac_env.py:221).  0 = no extra step */
     int32_t action_input;      /* hns_action_input: what `action` of hns_step holds (below) */
+    /* contact response (ABI 6; NOT the reference's PhysX contacts — an opt-in model, DESIGN.md §A5, described below) */
+    int32_t contact_response;  /* 0 = off (the default: bodies pass through cylinders and each other, as every earlier build); 1 = on */
+    float contact_drone_radius;   /* r_d: task.contact_drone_radius (0.05) */
+    float contact_target_radius;  /* r_t: task.contact_target_radius (0.05, the reference's evader sphere, hideandseek.py:544-551) */
+    float contact_dd;          /* D   = fp32(2 r_d): distance of two pursuers in contact */
+    float contact_dd2;         /* D2  = fp32(D*D) */
+    float contact_rd;          /* Rd  = fp32(cylinder_size + r_d): pursuer <-> cylinder axis in contact */
+    float contact_rd2;         /* Rd2 = fp32(Rd*Rd) */
+    float contact_rt;          /* Rt  = fp32(cylinder_size + r_t): evader <-> cylinder axis in contact */
+    float contact_rt2;         /* Rt2 = fp32(Rt*Rt) */
+    int32_t contact_pad[7];    /* zero: the nine contact words padded to one 64-byte line, so that every field the device parameter block
+                                  holds behind the config keeps its place within a scalar-cache line */
 } hns_cfg;
+
+/*
+ * Contact response (cfg.contact_response = 1; a documented model, not PhysX — DESIGN.md §A5).  Runs inside hns_step after the
+ * integrator (ground clamp included) and before anything reads S_{t+1}; inelastic, frictionless, cylinders of infinite mass,
+ * pursuers of equal mass, fp32 without FMA, correctly rounded sqrt and division.  p, v: integrated position / velocity.
+ *   1. pursuer <-> pursuer, one Jacobi pass: for pursuer a, peers j != a ascending: d = p_a - p_j, d2 = (dx*dx + dy*dy) + dz*dz;
+ *      if d2 < D2 && d2 > 0: r = sqrt(d2), inv = 1/r, n = d*inv, cp += ((D - r)*0.5f)*n,
+ *      vn = ((va.x-vj.x)*n.x + (va.y-vj.y)*n.y) + (va.z-vj.z)*n.z, if vn < 0: cv += (-(vn*0.5f))*n.  Then p_a += cp, v_a += cv (cp, cv from 0).
+ *   2. pursuer <-> cylinder, slots ascending, active slots (!(cz < 0)) with p.z < cylinder_height: dx = px - cx, dy = py - cy,
+ *      d2 = dx*dx + dy*dy; if d2 < Rd2 && d2 > 0: r = sqrt(d2), n = (dx, dy)*(1/r), px = cx + n.x*Rd, py = cy + n.y*Rd,
+ *      vn = vx*n.x + vy*n.y, if vn < 0: vx -= vn*n.x, vy -= vn*n.y.
+ *   3. the integrator's ground clamp again (cfg.ground_clamp).
+ *   4. evader <-> cylinder: stage 2 on the evader's new position with Rt / Rt2, position only (target_vel stays the policy's velocity).
+ * Not modelled: pursuer <-> evader (capture happens far earlier), arena walls and ceiling (no colliders in the reference), friction,
+ * restitution, the reset's extra physics step.  hns_create refuses it with num_targets = 2.
+ */
 
 /*
  * Two-evader extension (num_targets = 2; NOT in the reference — BASELINE config 5 "6-pursuer/2-evader"):

@@ -6,7 +6,7 @@ been built (`python -c "import __graft_entry__ as g; g.build()"`).
 import ctypes as C
 import os
 
-HNS_ABI_VERSION = 5
+HNS_ABI_VERSION = 6
 HNS_MAX_AGENTS = 7
 HNS_MAX_CYLINDERS = 16
 HNS_NUM_STATS = 24
@@ -57,6 +57,10 @@ class HnsCfg(C.Structure):
         ("fixed_drone_pos", (_f * 3) * (HNS_MAX_AGENTS + 1)), ("fixed_target_pos", _f * 3),
         ("fixed_cyl_pos", (_f * 3) * HNS_MAX_CYLINDERS), ("fixed_cyl_active", _i), ("tp_use_obstacles", _i),
         ("pid_reset_on_reset", _i), ("stats_stride", _i), ("reset_extra_step", _i), ("action_input", _i),
+        # contact response (include/hns.h; off by default): the switch, the two radii, the derived fp32 constants, padding to 64 bytes
+        ("contact_response", _i), ("contact_drone_radius", _f), ("contact_target_radius", _f),
+        ("contact_dd", _f), ("contact_dd2", _f), ("contact_rd", _f), ("contact_rd2", _f), ("contact_rt", _f), ("contact_rt2", _f),
+        ("contact_pad", _i * 7),
     ]
 
     def copy(self):

@@ -11,6 +11,7 @@ reference uses, so they round identically (e.g. `dt / tau` is `tau.reciprocal() 
 """
 import copy
 import math
+import struct
 
 import torch
 import yaml
@@ -65,6 +66,12 @@ DEFAULT_TASK = {
     # reset_extra_step: 1 = `_reset_idx` ends with one physics step of the whole scene, no rotor forces (hideandseek.py:722-723); 0 = none
     "reset_extra_step": 1,
     # action_input (NOT a default here: see `resolve_action_input`): "policy" | "motor" — what ("agents","action") of a stepped tensordict holds
+    # contact_response: 1 = pursuers stop at cylinders and at each other, the evader at cylinders (an opt-in model, NOT the reference's PhysX
+    #   contacts: include/hns.h); 0 = bodies pass through, as the reference's reward sees them.  The radii: contact spheres of a
+    #   pursuer and of the evader (the reference's evader sphere is 0.05, hideandseek.py:544-551)
+    "contact_response": 0,
+    "contact_drone_radius": 0.05,
+    "contact_target_radius": 0.05,
 }
 
 DEFAULT_ALGO = {"name": "mappo", "use_TP_net": 0, "train_every": 64}
@@ -176,6 +183,20 @@ def resolve_action_input(task):
     return "policy" if tr is None or str(tr).lower() == "none" else "motor"
 
 
+def check_contact(task):
+    """Validate the contact-response keys of a task mapping; returns (on, drone radius, evader radius)."""
+    on = task.get("contact_response", 0)
+    if on not in (0, 1, False, True):
+        raise ValueError("task.contact_response must be 0 (off, the default) or 1 (on)")
+    rd, rt = float(task.get("contact_drone_radius", 0.05)), float(task.get("contact_target_radius", 0.05))
+    if not (math.isfinite(rd) and rd > 0 and math.isfinite(rt) and rt > 0):
+        raise ValueError("task.contact_drone_radius and task.contact_target_radius must be finite and > 0")
+    if on and int(task.get("num_targets", 1)) == 2:
+        raise ValueError("task.contact_response: 1 is not built for the two-evader extension (task.num_targets: 2); "
+                         "the contact model covers the reference's one evader only")
+    return int(on), rd, rt
+
+
 def make_cfg(task=None, algo=None, headless=True, _from_yaml=False, **task_overrides):
     """Compose a train-style config {task, algo, env, sim, headless} from partial mappings.  Called directly (not through `load_cfg`) the env
     takes the raw policy action whatever `action_transform` says (`action_input: policy`, see `resolve_action_input`)."""
@@ -184,6 +205,7 @@ def make_cfg(task=None, algo=None, headless=True, _from_yaml=False, **task_overr
     _merge(t, task_overrides)
     if not _from_yaml:
         t.setdefault("action_input", "policy")
+    check_contact(t)
     a = copy.deepcopy(DEFAULT_ALGO)
     _merge(a, algo or {})
     cfg = {"task": t, "algo": a, "env": t["env"], "sim": t["sim"], "headless": headless,
@@ -338,6 +360,14 @@ def resolve_hns_cfg(cfg, num_envs=None, env_index_offset=0, drone_params=None, w
     c.arena_sq = float(t.arena_size) ** 2
     c.coll_drone_dist = 2.0 * float(t.collision_radius)
     c.boundary = float(t.arena_size) - 0.1
+    # contact response (include/hns.h): fp32 constants from the Python doubles, as coll_drone_dist / arena_sq above
+    on, rd, rt = check_contact(t)
+    f32 = lambda x: float(struct.unpack("f", struct.pack("f", x))[0])   # noqa: E731 (round to the nearest fp32, as the ctypes field does)
+    D, Rd, Rt = f32(2.0 * rd), f32(float(t.cylinder.size) + rd), f32(float(t.cylinder.size) + rt)
+    c.contact_response, c.contact_drone_radius, c.contact_target_radius = on, rd, rt
+    c.contact_dd, c.contact_dd2 = D, D * D          # (a product of two fp32 values is exact in a double: one rounding, = the fp32 product)
+    c.contact_rd, c.contact_rd2 = Rd, Rd * Rd
+    c.contact_rt, c.contact_rt2 = Rt, Rt * Rt
     # drone
     c.mass = float(p["mass"])
     c.inertia[:] = [float(p["inertia"]["xx"]), float(p["inertia"]["yy"]), float(p["inertia"]["zz"])]

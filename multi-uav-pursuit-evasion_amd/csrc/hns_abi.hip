@@ -351,6 +351,14 @@ int hns_create(const hns_cfg *cfg, hns_env **out) {
     if (cfg->num_targets < 0 || cfg->num_targets > hns::kMaxT) { set_error("hns_create: num_targets must be 0, 1 or 2"); return HNS_ERR_INVALID_ARG; }
     if (cfg->action_input != HNS_ACTION_POLICY && cfg->action_input != HNS_ACTION_MOTOR) { set_error("hns_create: action_input must be HNS_ACTION_POLICY or HNS_ACTION_MOTOR"); return HNS_ERR_INVALID_ARG; }
     if (cfg->grid_num < 1 || cfg->grid_num > 16) { set_error("hns_create: grid_num out of range"); return HNS_ERR_INVALID_ARG; }
+    if (cfg->contact_response != 0 && cfg->contact_response != 1) { set_error("hns_create: contact_response must be 0 or 1"); return HNS_ERR_INVALID_ARG; }
+    if (cfg->contact_response) {   // include/hns.h: the contact model (pursuers, one evader)
+        const float r[] = {cfg->contact_drone_radius, cfg->contact_target_radius, cfg->contact_dd, cfg->contact_dd2, cfg->contact_rd,
+                           cfg->contact_rd2, cfg->contact_rt, cfg->contact_rt2};
+        for (float x : r)
+            if (!(x > 0.0f) || !std::isfinite(x)) { set_error("hns_create: contact radii and their derived constants must be > 0 and finite"); return HNS_ERR_INVALID_ARG; }
+        if (cfg->num_targets == 2) { set_error("hns_create: contact_response is not built for the two-evader extension"); return HNS_ERR_INVALID_ARG; }
+    }
     if (cfg->init_mode != HNS_INIT_SCENARIO) {
         int half = cfg->grid_num / 2, free_cells = 0;
         for (int i = 0; i < cfg->grid_num; ++i)

@@ -22,7 +22,10 @@ enum { R_AERR = 0, R_TD, R_DIST, R_SPEED, R_CC, R_CD, R_CW, R_COLL,
        // so is the thrust vector handed to the downwash partners (3 consecutive slots)
        R_TWX = R_CD,
        // two-evader extension: the push on the second evader (slots 8..10)
-       R_F1X = 8 };
+       R_F1X = 8,
+       // contact response (one evader): the integrated position and velocity handed to the contact partners between the barrier in front of
+       // the contact stages and barrier 2 (slots 2..7: nothing else lives there then)
+       R_CPOS = R_DIST, R_CVEL = R_DIST + 3 };
 enum { F_CAP = 1, F_BLOCKED = 2, F_DET = 4, F_DET1 = 8 };
 constexpr int kGridStride = 516;   // bytes of reset scratch per env: 2 x 256 + 4 (an odd dword stride: lanes = envs hit different LDS banks)
 constexpr int kSmallWgPerCu = 2;   // the small-batch mapping (hns_step_small_kernel.h) serves grids of up to this many workgroups per CU (one with four and more pursuers; hns_inst.hip)

@@ -80,6 +80,17 @@ void HNS_CAT(hns_select_kernels_, HNS_INST_A)(hns_env *env) {
         }
         env->reset_fn = two ? hns_reset_kernel<A, 2> : hns_reset_kernel<A, 1>;
     }
+    const bool contact = c.contact_response != 0;   // include/hns.h; one evader (hns_create refuses the extension)
+    if (contact) {
+        // the same choice among the same mappings, with the contact stages (hns_step_kernel.h: hns_step_contact_kernel); no phase-stamped twin
+        env->step_args_prof_fn = nullptr;
+        if (motor) env->step_args_fn = wide ? hns_step_contact_kernel<A, 1, true, kWideK, 0, true> : hns_step_contact_kernel<A, 1, true, kMaxK, 0, true>;
+        else if (wide) env->step_args_fn = hns_step_contact_kernel<A, 1, true, kWideK, 0, false>;
+        else if (ragged) env->step_args_fn = hns_step_contact_kernel<A, 1, true, kMaxK, 0, false>;
+        else if (c.obs_max_cylinder == 3 && c.num_cylinders == 5) env->step_args_fn = hns_step_contact_kernel<A, 1, false, kMaxK, 5, false>;
+        else if (c.obs_max_cylinder == 3 && c.num_cylinders == 8) env->step_args_fn = hns_step_contact_kernel<A, 1, false, kMaxK, 8, false>;
+        else env->step_args_fn = hns_step_contact_kernel<A, 1, false, kMaxK, 0, false>;
+    }
     env->threads = Geo<A>::T;
     env->threads_step = Geo<A>::T;
     env->cyl_magic = (uint32_t)(0xFFFFFFFFull / (uint32_t)(3 * c.num_cylinders) + 1ull);
@@ -92,7 +103,8 @@ void HNS_CAT(hns_select_kernels_, HNS_INST_A)(hns_env *env) {
     // tiles, k <= 4, at most kSmallWgPerCu workgroups per CU.  HNS_STEP_MAPPING=tile|small overrides the choice where the shape allows both
     // (A/B runs, tests/test_hip_parity.py).
     const char *mp = std::getenv("HNS_STEP_MAPPING");
-    const bool eligible = !two && !wide && !ragged && !motor;
+    // (contact response: not eligible — the small-batch mapping has no contact stages; such envs take the tile mapping at every batch size)
+    const bool eligible = !two && !wide && !ragged && !motor && !contact;
     // (2 A + 1 waves per workgroup: with four and more pursuers two of them no longer share a CU — 32 768 envs measured 13.4 / 19.5 / 22.2 us
     //  with the tile mapping against 17.3 / 22.9 / 25.9 us for 4 / 6 / 7 pursuers, while one tile per CU is faster in the small mapping for every count)
     bool small = eligible && env->grid <= (A <= 3 ? kSmallWgPerCu : 1) * env->cus;
