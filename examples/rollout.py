@@ -6,6 +6,7 @@ storage, and the advantage normalisation runs in its data-parallel form (one all
 
     python examples/rollout.py --envs 65536 --tp            # one GPU
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/rollout.py
+    python examples/rollout.py --gae                         # GAE + normalised targets on the device (hns_amd.gae.rollout_targets)
 
 The policy is a fixed random linear map (there is no learner in this repository)."""
 import argparse
@@ -17,7 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import hns_amd  # noqa: E402,F401
-from hns_amd import config, sharding  # noqa: E402
+from hns_amd import config, gae, sharding  # noqa: E402
 from hns_amd.env import HideAndSeek  # noqa: E402
 
 
@@ -27,6 +28,7 @@ def main():
     ap.add_argument("--rollouts", type=int, default=5)
     ap.add_argument("--train-every", type=int, default=64)
     ap.add_argument("--tp", action="store_true", help="algo.use_TP_net: 1 (the reference's default)")
+    ap.add_argument("--gae", action="store_true", help="advantages by GAE (gamma 0.995, lambda 0.95: cfg/algo/mappo.yaml) on a linear value head")
     args = ap.parse_args()
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
@@ -43,6 +45,8 @@ def main():
     D = td[("agents", "observation", "state_self")].shape[-1]
     n_in = D + 3 * (A - 1) + 5 * env.obs_max_cylinder
     W = torch.randn(n_in, 4, device=env.device) * 0.3          # the stand-in policy
+    Wv = torch.randn(n_in, 1, device=env.device) * 0.1         # and its linear value head (--gae)
+    val_buf = torch.empty(T, E, A, 1, device=env.device)
     obs_buf = torch.empty(T, E, A, n_in, device=env.device)
     rew_buf = torch.empty(T, E, A, device=env.device)
     done_buf = torch.empty(T, E, dtype=torch.bool, device=env.device)
@@ -58,6 +62,8 @@ def main():
         for t in range(T):
             x = flat_obs(cur)
             obs_buf[t] = x
+            if args.gae:
+                val_buf[t] = x @ Wv
             step_td = env.rand_step_input(torch.tanh(x @ W))
             nxt = env.step(step_td)["next"]
             rew_buf[t] = nxt[("agents", "reward")].squeeze(-1)
@@ -68,8 +74,13 @@ def main():
                 cur = env.reset(rtd)
             else:
                 cur = nxt
-        adv = rew_buf - rew_buf.mean()                          # placeholder for GAE: what matters here is the global normalisation
-        adv_n, success = sharding.normalise_advantages(adv, env.stats["success"])
+        if args.gae:                                            # time-major storage: compute_gae_'s layout; one all-gather inside
+            adv_n, _, success = gae.rollout_targets(rew_buf.unsqueeze(-1), done_buf.view(T, E, 1, 1), val_buf, flat_obs(cur) @ Wv, 0.995, 0.95,
+                                                    success=env.stats["success"].reshape(-1).float(), time_major=True)
+            success = float(success)
+        else:
+            adv = rew_buf - rew_buf.mean()                      # placeholder for GAE: what matters here is the global normalisation
+            adv_n, success = sharding.normalise_advantages(adv, env.stats["success"])
         if rank == 0:
             print(f"rollout {r}: reward mean {float(rew_buf.mean()):+.3f}  |adv| mean {float(adv_n.abs().mean()):.3f}  "
                   f"global success {success:.3f}")

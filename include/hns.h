@@ -442,6 +442,28 @@ int hns_moments(const float *values, int64_t n, const float *success, int64_t m,
  * rollout's returns, mappo.py:398-399) — SURVEY §8(e)(3): out[0..7] = [sum adv, sum adv^2, n, sum success, m, sum ret, sum ret^2, n_returns]. */
 int hns_rollout_moments(const float *advantages, int64_t n, const float *success, int64_t m, const float *returns, int64_t n_returns, double *out, void *stream);
 
+/* The rollout boundary (learning/utils/gae.py:27-75 driven by learning/mappo.py:370-402), two launches in one stream:
+ * hns_gae: GAE over reward / value fp32 [n, t, k] (HNS_GAE_BATCH_MAJOR: compute_gae) or [t, n, k] (HNS_GAE_TIME_MAJOR: compute_gae_), done [.., kd] in the
+ * same layout with kd = 1 (broadcast over k) or k, as bytes (bool / uint8: HNS_GAE_DONE_U8) or fp32; next_value [n, k].  scale / shift: both NULL, or two
+ * device fp32 scalars every value read (next_value included) is first mapped through, v * scale + shift (ValueNorm1.denormalize: sqrt(var), mean).
+ * Writes advantages and returns (= advantages + value) in reward's layout, bit for bit the reference's fp32 statements.  With `moments` (device, 8 fp64)
+ * it also writes the rank's row of the moment table (sharding.MOMENT_DIM): [sum adv, sum adv^2, n t k, sum success, m, sum ret, sum ret^2, n t k]
+ * (success [m] fp32, m may be 0), deterministically, through `workspace` (device, HNS_GAE_WORKSPACE_DOUBLES fp64) and a second one-workgroup launch.
+ * No host synchronisation and no allocation: legal inside a stream capture. */
+#define HNS_GAE_BATCH_MAJOR 0
+#define HNS_GAE_TIME_MAJOR 1
+#define HNS_GAE_DONE_U8 0
+#define HNS_GAE_DONE_F32 1
+#define HNS_GAE_WORKSPACE_DOUBLES 20480
+int hns_gae(const float *reward, const float *value, const void *done, const float *next_value, int64_t n, int64_t t, int64_t k, int64_t kd,
+            int32_t layout, int32_t done_dtype, double gamma, double lambda, const float *scale, const float *shift, const float *success, int64_t m,
+            float *advantages, float *returns, double *moments, double *workspace, void *stream);
+/* In place, ONE launch: advantages[i] = (advantages[i] - *adv_mean) / *adv_den, returns[i] = (returns[i] - *ret_mean) / *ret_scale (device fp32
+ * scalars: mean.to(f32) and std.to(f32) + eps from the gathered table; ValueNorm1's mean and sqrt(var) after its update).  Either group (array, n,
+ * two scalars) may be left out with NULL scalars. */
+int hns_rollout_normalise(float *advantages, int64_t n_adv, const float *adv_mean, const float *adv_den, float *returns, int64_t n_ret,
+                          const float *ret_mean, const float *ret_scale, void *stream);
+
 int hns_abi_version(void);
 size_t hns_cfg_size(void);   /* sizeof(hns_cfg) the library was built with (binding self-check) */
 const char *hns_last_error(void);

@@ -146,6 +146,9 @@ def hover_buffer_shapes(E):
             "obs": ((E, 1, HNS_SELF_DIM), "float32"), "reward": ((E, 1), "float32"), "done": ((E,), "uint8")}
 
 
+HNS_GAE_BATCH_MAJOR, HNS_GAE_TIME_MAJOR = 0, 1        # hns_gae layouts: [N, T, K] (compute_gae) / [T, N, K] (compute_gae_)
+HNS_GAE_DONE_U8, HNS_GAE_DONE_F32 = 0, 1              # hns_gae done dtypes: bool / uint8 bytes, fp32
+HNS_GAE_WORKSPACE_DOUBLES = 20480                     # fp64 scratch hns_gae needs for its moment row
 HNS_OK, HNS_ERR_INVALID_ARG, HNS_ERR_NOT_BOUND, HNS_ERR_DEVICE, HNS_ERR_NO_DEVICE, HNS_ERR_CONFIG = 0, -1, -2, -3, -4, -5
 
 # ---- trajectory predictor (include/hns.h: hns_tp_buffers) ------------------------------------------------
@@ -238,6 +241,11 @@ def load_library():
     lib.hns_moments.restype = C.c_int
     lib.hns_rollout_moments.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.hns_rollout_moments.restype = C.c_int
+    lib.hns_gae.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                            C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hns_gae.restype = C.c_int
+    lib.hns_rollout_normalise.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hns_rollout_normalise.restype = C.c_int
     lib.hns_clock_probe.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     lib.hns_clock_probe.restype = C.c_int
     lib.hns_copy_f4.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -290,5 +298,5 @@ def load_library():
 EXPORTED_SYMBOLS = [
     "hns_create", "hns_destroy", "hns_bind", "hns_step", "hns_reset", "hns_reset_tasks", "hns_raycast", "hns_set_v_prey",
     "hns_set_smoothness_coef", "hns_set_reset_epoch", "hns_get_reset_epoch", "hns_enable_timing",
-    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
+    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_gae", "hns_rollout_normalise", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
 ]
