@@ -434,6 +434,14 @@ int hns_set_phase_profile(hns_env *env, unsigned long long *device_buf);
  * start at a raised issue priority, which hns_create decides from the shape and has no effect on any result). */
 int hns_step_mapping(const hns_env *env);
 
+/* Diagnostics: the kernel instantiations hns_create chose for this env, by name, in the form tools/kernel_resources.py prints them (argument
+ * list, return type and "hns::" stripped, e.g. "hns_step_v4_kernel<3, 1, false, 4, false, 8, false>"): `step` the step kernel, `step_prof` its
+ * phase-stamped twin (empty when the env has none), `reset` the reset kernel — each a host buffer of `cap` bytes; *prio_boost (may be NULL) =
+ * whether the tile mapping's pursuer waves start at a raised priority.  Returns 1 when the stamped twin serves the next step (a phase-profile
+ * buffer is attached and a twin exists), 0 when the plain step kernel does; HNS_ERR_INVALID_ARG when a name does not fit or a kernel handle is
+ * not an exported symbol of this library. */
+int hns_selected_kernels(const hns_env *env, char *step, char *step_prof, char *reset, int cap, int32_t *prio_boost);
+
 /* The per-rollout moments of the data-parallel advantage normalisation (learning/mappo.py:391-396 made data-parallel; sharding.py) in ONE launch:
  * out[0..4] = [sum v, sum v^2, n, sum s, m] in fp64 over `values` [n] fp32 and `success` [m] fp32 (m may be 0: success NULL) — device
  * pointers; one workgroup, fixed summation order (the same inputs give the same bits on every run). */

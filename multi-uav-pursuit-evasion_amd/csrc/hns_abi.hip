@@ -3,6 +3,8 @@
 // hns_step_kernel.h / hns_reset_kernel.h and are instantiated by hns_inst.hip, one translation unit per pursuer count.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <cxxabi.h>
+#include <dlfcn.h>
 
 #include <cmath>
 #include <cstdio>
@@ -753,6 +755,35 @@ int hns_set_phase_profile(hns_env *env, unsigned long long *device_buf) {
 }
 
 int hns_step_mapping(const hns_env *env) { return env ? env->small_mapping : HNS_ERR_INVALID_ARG; }
+
+int hns_selected_kernels(const hns_env *env, char *step, char *step_prof, char *reset, int cap, int32_t *prio_boost) {
+    if (!env || !step || !step_prof || !reset || cap < 1) { set_error("hns_selected_kernels: null argument"); return HNS_ERR_INVALID_ARG; }
+    // the host handle of a kernel is an exported symbol named after the kernel (nm -D libhns.so): its name, demangled, is the instantiation
+    auto name_of = [&](const void *fn, char *out, const char *what) -> int {
+        out[0] = '\0';
+        if (!fn) return HNS_OK;
+        Dl_info info;
+        if (!dladdr(fn, &info) || info.dli_saddr != fn || !info.dli_sname) {
+            set_error(std::string("hns_selected_kernels: the ") + what + " kernel's handle is not an exported symbol of this library");
+            return HNS_ERR_INVALID_ARG;
+        }
+        int status = 0;
+        char *d = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &status);
+        std::string s = status == 0 && d ? d : info.dli_sname;
+        std::free(d);
+        s = s.substr(0, s.find('('));                                  // the form tools/kernel_resources.py prints
+        for (const char *drop : {"void ", "hns::"})
+            for (size_t at; (at = s.find(drop)) != std::string::npos;) s.erase(at, std::strlen(drop));
+        if (s.size() + 1 > (size_t)cap) { set_error(std::string("hns_selected_kernels: the ") + what + " kernel's name does not fit in cap bytes"); return HNS_ERR_INVALID_ARG; }
+        std::memcpy(out, s.c_str(), s.size() + 1);
+        return HNS_OK;
+    };
+    if (const int rc = name_of(reinterpret_cast<const void *>(env->step_args_fn), step, "step")) return rc;
+    if (const int rc = name_of(reinterpret_cast<const void *>(env->step_args_prof_fn), step_prof, "stamped step")) return rc;
+    if (const int rc = name_of(reinterpret_cast<const void *>(env->reset_fn), reset, "reset")) return rc;
+    if (prio_boost) *prio_boost = env->prio_boost;
+    return (env->prof && env->step_args_prof_fn) ? 1 : 0;             // hns_step's choice (launch_step)
+}
 
 int hns_enable_timing(hns_env *env, int on) {
     if (!env) return HNS_ERR_INVALID_ARG;

@@ -318,6 +318,13 @@ HNS_DEV void cylinder_pass(const Cfg &c, int C, int K, const V3 &pos, const V3 &
     for (int i = 0; i < kTrack - 1; ++i)
         if (i < K) order_safe = order_safe && (bd[i + 1] > bd[i] * 1.0000152587890625f);   // 1 + 2^-16
     if (!order_safe) {                          // rare: exact (distance - size) keys, as the reference sorts
+        if (!(__builtin_isfinite(pos.x) && __builtin_isfinite(pos.y) && __builtin_isfinite(pos.z))) {
+            // a non-finite position (a NaN or infinite command in motor input): every key is +inf or NaN, none compares below, and the order
+            // is the index order, as the oracle's (was: no key ever passed `md < +inf`, and every slot kept cylinder 0)
+#pragma unroll
+            for (int i = 0; i < kTrack; ++i) bi[i] = i < C ? i : 0;
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < kTrack; ++i) { bd[i] = kInf; bi[i] = 0; }
         for (int k = 0; k < C; ++k) {

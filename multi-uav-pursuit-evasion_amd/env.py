@@ -783,6 +783,17 @@ class HideAndSeek(_EnvBase):
         """'tile' or 'small': which mapping of the step kernel serves this env (hns_step_mapping; csrc/hns_step_small_kernel.h)."""
         return "small" if self._lib.hns_step_mapping(self._env) == 1 else "tile"
 
+    def selected_kernels(self):
+        """The kernel instantiations serving this env (hns_selected_kernels), named as tools/kernel_resources.py names them:
+        {"step", "step_prof" (None without a phase-stamped twin), "reset", "prio_boost", "stamped" (the twin serves the next step)}."""
+        cap = 256
+        step, prof, reset, boost = C.create_string_buffer(cap), C.create_string_buffer(cap), C.create_string_buffer(cap), C.c_int32()
+        rc = self._lib.hns_selected_kernels(self._env, step, prof, reset, cap, C.byref(boost))
+        if rc < 0:
+            self._check(rc, "hns_selected_kernels")
+        return {"step": step.value.decode(), "step_prof": prof.value.decode() or None, "reset": reset.value.decode(),
+                "prio_boost": bool(boost.value), "stamped": rc == 1}
+
     def region_begin(self):
         """One start event on the stream the steps are launched on (hns_region_begin); `region_end` records the stop event,
         `region_ms` waits for it.  Nothing is added to the launches in between."""
