@@ -7,6 +7,7 @@ storage, and the advantage normalisation runs in its data-parallel form (one all
     python examples/rollout.py --envs 65536 --tp            # one GPU
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/rollout.py
     python examples/rollout.py --gae                         # GAE + normalised targets on the device (hns_amd.gae.rollout_targets)
+    python examples/rollout.py --tp --tp-train               # the predictor trained once per rollout on the device (hns_amd.tp_train.update_tp)
 
 The policy is a fixed random linear map (there is no learner in this repository)."""
 import argparse
@@ -18,7 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import hns_amd  # noqa: E402,F401
-from hns_amd import config, gae, sharding  # noqa: E402
+from hns_amd import config, gae, sharding, tp_train  # noqa: E402
 from hns_amd.env import HideAndSeek  # noqa: E402
 
 
@@ -29,7 +30,10 @@ def main():
     ap.add_argument("--train-every", type=int, default=64)
     ap.add_argument("--tp", action="store_true", help="algo.use_TP_net: 1 (the reference's default)")
     ap.add_argument("--gae", action="store_true", help="advantages by GAE (gamma 0.995, lambda 0.95: cfg/algo/mappo.yaml) on a linear value head")
+    ap.add_argument("--tp-train", action="store_true", help="with --tp: train the predictor on each rollout (mappo.py:405-441, 16 minibatches)")
     args = ap.parse_args()
+    if args.tp_train and not args.tp:
+        ap.error("--tp-train needs --tp")
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
     if world > 1:
@@ -50,6 +54,12 @@ def main():
     obs_buf = torch.empty(T, E, A, n_in, device=env.device)
     rew_buf = torch.empty(T, E, A, device=env.device)
     done_buf = torch.empty(T, E, dtype=torch.bool, device=env.device)
+    if args.tp_train:                                           # the rollout's ('next', 'agents', 'TP') entries, [E, T, ...] as the learner stacks them
+        hist = env._tp_bufs["history"]
+        tp_in = torch.empty(E, T, *hist.shape[1:], device=env.device)
+        tp_gt = torch.empty(E, T, 3, device=env.device)
+        tp_done = torch.empty(E, T, 1, dtype=torch.bool, device=env.device)
+        tp_opt = tp_train.TPAdam(env.TP.parameters(), lr=1e-4)
 
     def flat_obs(t):
         o = t[("agents", "observation")]
@@ -67,6 +77,8 @@ def main():
             step_td = env.rand_step_input(torch.tanh(x @ W))
             nxt = env.step(step_td)["next"]
             rew_buf[t] = nxt[("agents", "reward")].squeeze(-1)
+            if args.tp_train:
+                tp_in[:, t], tp_gt[:, t], tp_done[:, t] = (nxt[("agents", "TP", k)] for k in ("TP_input", "TP_groundtruth", "TP_done"))
             done_buf[t] = nxt["done"].squeeze(-1)
             if bool(done_buf[t].any()):                          # episodes are lock-step: reset exactly the done envs
                 rtd = env.rand_step_input()
@@ -81,9 +93,13 @@ def main():
         else:
             adv = rew_buf - rew_buf.mean()                      # placeholder for GAE: what matters here is the global normalisation
             adv_n, success = sharding.normalise_advantages(adv, env.stats["success"])
+        tp_msg = ""
+        if args.tp_train:                                       # the env re-packs the updated weights before its next step by itself
+            tp_loss = tp_train.update_tp(env.TP, tp_in, tp_gt, tp_done, env.tp_future_step, 1, 16, 1, tp_opt)
+            tp_msg = f"  TP loss {float(tp_loss):.4f}"
         if rank == 0:
             print(f"rollout {r}: reward mean {float(rew_buf.mean()):+.3f}  |adv| mean {float(adv_n.abs().mean()):.3f}  "
-                  f"global success {success:.3f}")
+                  f"global success {success:.3f}{tp_msg}")
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if rank == 0:

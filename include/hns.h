@@ -472,6 +472,38 @@ int hns_gae(const float *reward, const float *value, const void *done, const flo
 int hns_rollout_normalise(float *advantages, int64_t n_adv, const float *adv_mean, const float *adv_den, float *returns, int64_t n_ret,
                           const float *ret_mean, const float *ret_scale, void *stream);
 
+/*
+ * The trajectory predictor's training step (learning/mappo.py:252-268 driven by :405-441): loss and gradients of one minibatch
+ * and torch.optim.Adam's update, on the device, in PyTorch layouts.  No host synchronisation and no allocation: legal inside a stream capture.
+ */
+typedef struct hns_tp_params {             /* TP_net's parameters (hns_tp_buffers' first six fields) */
+    const float *w_ih, *w_hh, *b_ih, *b_hh, *w_fc, *b_fc;
+} hns_tp_params;
+typedef struct hns_tp_grads {              /* their gradients, same shapes; b_ih and b_hh receive the same values */
+    float *w_ih, *w_hh, *b_ih, *b_hh, *w_fc, *b_fc;
+} hns_tp_grads;
+/* Bytes of device workspace hns_tp_train_grad needs: a partial-gradient row per workgroup (at most 256 of them), independent of T and of B
+ * beyond 4 096 sequences; 0 for an invalid shape. */
+size_t hns_tp_train_workspace_bytes(int64_t batch, int32_t input_dim, int32_t future_step);
+/* loss = mean((tanh(W_fc h_T + b_fc) - y)^2) over [batch, 3F] (nn.MSELoss) for an LSTM(input_dim -> 64) from a zero state, and its gradients.
+ * x: [num_envs, num_steps, T, I] fp32 with element (e, s, t, i) at e stride_env + s stride_step + t I + i (each [T, I] block contiguous);
+ * y: [num_envs num_steps, 3F] fp32; index: [batch] int64 rows of the flattened [num_envs num_steps] (NULL: rows 0 .. batch - 1; an index
+ * outside the rows contributes nothing — callers check the range).  loss: one device fp32.  T in [1, 16], I in [1, 80], F in [1, 10],
+ * batch >= 1.  Two launches; deterministic (per-workgroup partials, fixed-order sums). */
+int hns_tp_train_grad(const hns_tp_params *params, const float *x, int64_t num_envs, int64_t num_steps, int64_t stride_env, int64_t stride_step,
+                      int32_t history_step, int32_t input_dim, const float *y, const int64_t *index, int64_t batch, int32_t future_step,
+                      const hns_tp_grads *grads, float *loss, void *workspace, size_t workspace_bytes, void *stream);
+typedef struct hns_tp_adam_tensor {
+    float *param;
+    const float *grad;
+    float *exp_avg, *exp_avg_sq;
+    int64_t numel;
+} hns_tp_adam_tensor;
+/* torch.optim.Adam (amsgrad off, weight decay 0) over 1 to 8 tensors in ONE launch, in the single-tensor statement order of torch's CPU kernels:
+ * step += 1; m = fma(1 - b1, g - m, m); v = fma((1 - b2) g, g, v b2); denom = sqrt(v) / f32(sqrt(1 - b2^step)) + f32(eps);
+ * p = p + (f32(-lr / (1 - b1^step)) m) / denom.  `step`: the device-resident fp32 step counter (torch's state['step']), read and bumped on the device. */
+int hns_tp_adam(const hns_tp_adam_tensor *tensors, int32_t count, float *step, double lr, double beta1, double beta2, double eps, void *stream);
+
 int hns_abi_version(void);
 size_t hns_cfg_size(void);   /* sizeof(hns_cfg) the library was built with (binding self-check) */
 const char *hns_last_error(void);

@@ -166,6 +166,14 @@ class HnsTpBuffers(C.Structure):
     _fields_ = [(name, _fp) for name in TP_BUFFER_FIELDS]
 
 
+class HnsTpParams(C.Structure):           # hns_tp_params / hns_tp_grads: the six weight pointers
+    _fields_ = [(name, _fp) for name in TP_WEIGHT_FIELDS]
+
+
+class HnsTpAdamTensor(C.Structure):
+    _fields_ = [("param", _fp), ("grad", _fp), ("exp_avg", _fp), ("exp_avg_sq", _fp), ("numel", C.c_int64)]
+
+
 def tp_frame_dim(A, C=0, use_obstacles=False):
     """Width of one predictor frame (hideandseek.py:808-820)."""
     return 7 + 3 * A + (3 * C if use_obstacles else 0)
@@ -269,6 +277,14 @@ def load_library():
     lib.hns_tp_packed_bytes.restype = C.c_size_t
     lib.hns_tp_observe.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     lib.hns_tp_observe.restype = C.c_int
+    lib.hns_tp_train_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    lib.hns_tp_train_workspace_bytes.restype = C.c_size_t
+    lib.hns_tp_train_grad.argtypes = [C.POINTER(HnsTpParams), C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(HnsTpParams), C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.c_void_p]
+    lib.hns_tp_train_grad.restype = C.c_int
+    lib.hns_tp_adam.argtypes = [C.POINTER(HnsTpAdamTensor), C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]
+    lib.hns_tp_adam.restype = C.c_int
     lib.hns_set_state.argtypes = [C.c_void_p, C.POINTER(HnsBuffers), C.c_void_p]
     lib.hns_set_state.restype = C.c_int
     lib.hns_get_state.argtypes = [C.c_void_p, C.POINTER(HnsBuffers), C.c_void_p]
@@ -300,5 +316,5 @@ def load_library():
 EXPORTED_SYMBOLS = [
     "hns_create", "hns_destroy", "hns_bind", "hns_step", "hns_reset", "hns_reset_tasks", "hns_raycast", "hns_set_v_prey",
     "hns_set_smoothness_coef", "hns_set_reset_epoch", "hns_get_reset_epoch", "hns_enable_timing",
-    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_gae", "hns_rollout_normalise", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_selected_kernels", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
+    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_gae", "hns_rollout_normalise", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_selected_kernels", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_tp_train_workspace_bytes", "hns_tp_train_grad", "hns_tp_adam", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
 ]
