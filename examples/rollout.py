@@ -8,8 +8,10 @@ storage, and the advantage normalisation runs in its data-parallel form (one all
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/rollout.py
     python examples/rollout.py --gae                         # GAE + normalised targets on the device (hns_amd.gae.rollout_targets)
     python examples/rollout.py --tp --tp-train               # the predictor trained once per rollout on the device (hns_amd.tp_train.update_tp)
+    python examples/rollout.py --tp --policy device          # the reference's actor / critic network (random init) on the device (hns_amd.policy)
 
-The policy is a fixed random linear map (there is no learner in this repository)."""
+The policy is a fixed random linear map by default (there is no learner in this repository); `--policy device` runs a randomly
+initialised network of the reference's architecture (PartialAttentionEncoder actor and critic, DiagGaussian) through hns_amd.policy."""
 import argparse
 import os
 import sys
@@ -19,7 +21,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import hns_amd  # noqa: E402,F401
-from hns_amd import config, gae, sharding, tp_train  # noqa: E402
+from hns_amd import config, gae, policy, sharding, tp_train  # noqa: E402
 from hns_amd.env import HideAndSeek  # noqa: E402
 
 
@@ -31,6 +33,8 @@ def main():
     ap.add_argument("--tp", action="store_true", help="algo.use_TP_net: 1 (the reference's default)")
     ap.add_argument("--gae", action="store_true", help="advantages by GAE (gamma 0.995, lambda 0.95: cfg/algo/mappo.yaml) on a linear value head")
     ap.add_argument("--tp-train", action="store_true", help="with --tp: train the predictor on each rollout (mappo.py:405-441, 16 minibatches)")
+    ap.add_argument("--policy", choices=("linear", "device"), default="linear",
+                    help="device: the reference's attention actor / critic (random init) in one HIP launch per step")
     args = ap.parse_args()
     if args.tp_train and not args.tp:
         ap.error("--tp-train needs --tp")
@@ -50,6 +54,9 @@ def main():
     n_in = D + 3 * (A - 1) + 5 * env.obs_max_cylinder
     W = torch.randn(n_in, 4, device=env.device) * 0.3          # the stand-in policy
     Wv = torch.randn(n_in, 1, device=env.device) * 0.1         # and its linear value head (--gae)
+    if args.policy == "device":
+        actor_p, critic_p = policy.random_parameters(D, A, seed=rank)
+        net = policy.DevicePolicy(actor_p, critic_p, device=env.device, seed=rank)
     val_buf = torch.empty(T, E, A, 1, device=env.device)
     obs_buf = torch.empty(T, E, A, n_in, device=env.device)
     rew_buf = torch.empty(T, E, A, device=env.device)
@@ -72,9 +79,16 @@ def main():
         for t in range(T):
             x = flat_obs(cur)
             obs_buf[t] = x
-            if args.gae:
-                val_buf[t] = x @ Wv
-            step_td = env.rand_step_input(torch.tanh(x @ W))
+            if args.policy == "device":
+                cur = net(cur)
+                action = cur[("agents", "action")]
+                if args.gae:
+                    val_buf[t] = cur["state_value"]
+            else:
+                action = torch.tanh(x @ W)
+                if args.gae:
+                    val_buf[t] = x @ Wv
+            step_td = env.rand_step_input(action)
             nxt = env.step(step_td)["next"]
             rew_buf[t] = nxt[("agents", "reward")].squeeze(-1)
             if args.tp_train:
@@ -87,7 +101,7 @@ def main():
             else:
                 cur = nxt
         if args.gae:                                            # time-major storage: compute_gae_'s layout; one all-gather inside
-            adv_n, _, success = gae.rollout_targets(rew_buf.unsqueeze(-1), done_buf.view(T, E, 1, 1), val_buf, flat_obs(cur) @ Wv, 0.995, 0.95,
+            adv_n, _, success = gae.rollout_targets(rew_buf.unsqueeze(-1), done_buf.view(T, E, 1, 1), val_buf, (net.value(cur) if args.policy == "device" else flat_obs(cur) @ Wv), 0.995, 0.95,
                                                     success=env.stats["success"].reshape(-1).float(), time_major=True)
             success = float(success)
         else:

@@ -504,6 +504,49 @@ typedef struct hns_tp_adam_tensor {
  * p = p + (f32(-lr / (1 - b1^step)) m) / denom.  `step`: the device-resident fp32 step counter (torch's state['step']), read and bumped on the device. */
 int hns_tp_adam(const hns_tp_adam_tensor *tensors, int32_t count, float *step, double lr, double beta1, double beta2, double eps, void *stream);
 
+/*
+ * The MAPPO policy's forward pass (learning/mappo.py:221-250 with cfg/algo/mappo.yaml's defaults: shared actor, critic on the observation, no rnn,
+ * no tanh): per (env, agent) row the actor's PartialAttentionEncoder + DiagGaussian (loc, a sample or the mode, its log_prob) and
+ * the critic's encoder + v_out.  embed_dim 128, one head, dim_feedforward 128.  No host synchronisation and no allocation: legal inside a stream
+ * capture.
+ */
+#define HNS_POLICY_MAX_SELF_DIM 96
+#define HNS_POLICY_DETERMINISTIC 1         /* action = loc (the distribution's mode) */
+#define HNS_POLICY_VALUE_ONLY 2            /* the critic alone: value (train_op's next_value) */
+typedef struct hns_policy_net {            /* one network's parameters, fp32 in PyTorch layouts (device) */
+    const float *embed_self_w, *embed_self_b;         /* [128, D], [128] */
+    const float *embed_others_w, *embed_others_b;     /* [128, 3], [128]; NULL with one pursuer (no state_others key) */
+    const float *embed_cyl_w, *embed_cyl_b;           /* [128, 5], [128] */
+    const float *ln_w, *ln_b;                         /* SplitEmbedding's LayerNorm(128) */
+    const float *in_proj_w, *in_proj_b;               /* [384, 128], [384]: q, k, v */
+    const float *out_proj_w, *out_proj_b;             /* [128, 128], [128] */
+    const float *linear1_w, *linear1_b, *linear2_w, *linear2_b;   /* [128, 128], [128] each */
+    const float *norm1_w, *norm1_b, *norm2_w, *norm2_b;
+    const float *head_w, *head_b;                     /* actor fc_mean [4, 128], [4]; critic v_out [1, 128], [1] */
+    const float *log_std;                             /* actor [4]; ignored for the critic */
+} hns_policy_net;
+typedef struct hns_policy_io {
+    const float *obs_self;                 /* [E, A, D]: element (e, a, i) at e s[0] + a s[1] + i */
+    const float *obs_others;               /* [E, A, A - 1, 3]: (e, a, j, i) at e s[0] + a s[1] + j s[2] + i; NULL when A = 1 */
+    const float *obs_cylinders;            /* [E, A, K, 5] likewise */
+    int64_t self_stride[2], others_stride[3], cyl_stride[3];
+    const float *eps;                      /* [E, A, 4] contiguous standard-normal noise, or NULL: Philox4x32-10 + Box-Muller in the kernel */
+    float *action;                         /* [E, A, 4] contiguous */
+    float *loc;                            /* [E, A, 4] contiguous, or NULL */
+    float *log_prob;                       /* [E, A] (Normal.log_prob summed over the 4 dims) */
+    float *value;                          /* [E, A] (the critic's normalised value) */
+} hns_policy_io;
+/* Bytes of the packed image of both networks (actor, then critic) for self_dim D in [1, 96]; 0 otherwise. */
+size_t hns_policy_packed_bytes(int32_t self_dim);
+/* Builds the packed image on the device from the parameter tensors (ONE launch): call it again after the parameters change. */
+int hns_policy_pack(const hns_policy_net *actor, const hns_policy_net *critic, int32_t self_dim, int32_t num_agents, void *packed, void *stream);
+/* The forward pass of num_envs x num_agents rows (num_agents in [1, 7], num_cylinders in [1, 16]).  flags: HNS_POLICY_DETERMINISTIC,
+ * HNS_POLICY_VALUE_ONLY (action / log_prob / loc untouched).  When the call samples without io->eps, the noise of row r is Philox4x32-10 with
+ * key `seed` and counter (*counter, r), and a second launch bumps the device uint64 *counter, so every call (and every replay of a captured
+ * graph) draws fresh noise.  Deterministic: the same inputs give the same bits. */
+int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
+                       int32_t flags, uint64_t seed, uint64_t *counter, void *stream);
+
 int hns_abi_version(void);
 size_t hns_cfg_size(void);   /* sizeof(hns_cfg) the library was built with (binding self-check) */
 const char *hns_last_error(void);

@@ -192,6 +192,23 @@ def tp_buffer_shapes(E, A, T, F, I=None, num_targets=1):
             "state_drones": ((E, A, D), "float32"), "groundtruth": ((U, 3), "float32"), "tp_done": ((U,), "uint8")}
 
 
+# the MAPPO policy's forward pass (include/hns.h: hns_policy_*; hns_amd.policy)
+HNS_POLICY_MAX_SELF_DIM = 96
+HNS_POLICY_DETERMINISTIC, HNS_POLICY_VALUE_ONLY = 1, 2
+POLICY_NET_FIELDS = ["embed_self_w", "embed_self_b", "embed_others_w", "embed_others_b", "embed_cyl_w", "embed_cyl_b", "ln_w", "ln_b",
+                     "in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "linear1_w", "linear1_b", "linear2_w", "linear2_b",
+                     "norm1_w", "norm1_b", "norm2_w", "norm2_b", "head_w", "head_b", "log_std"]
+
+
+class HnsPolicyNet(C.Structure):
+    _fields_ = [(f, _fp) for f in POLICY_NET_FIELDS]
+
+
+class HnsPolicyIo(C.Structure):
+    _fields_ = [("obs_self", _fp), ("obs_others", _fp), ("obs_cylinders", _fp), ("self_stride", C.c_int64 * 2), ("others_stride", C.c_int64 * 3),
+                ("cyl_stride", C.c_int64 * 3), ("eps", _fp), ("action", _fp), ("loc", _fp), ("log_prob", _fp), ("value", _fp)]
+
+
 _LIB = None
 LIB_NAME = "libhns.so"
 
@@ -285,6 +302,13 @@ def load_library():
     lib.hns_tp_train_grad.restype = C.c_int
     lib.hns_tp_adam.argtypes = [C.POINTER(HnsTpAdamTensor), C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]
     lib.hns_tp_adam.restype = C.c_int
+    lib.hns_policy_packed_bytes.argtypes = [C.c_int32]
+    lib.hns_policy_packed_bytes.restype = C.c_size_t
+    lib.hns_policy_pack.argtypes = [C.POINTER(HnsPolicyNet), C.POINTER(HnsPolicyNet), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.hns_policy_pack.restype = C.c_int
+    lib.hns_policy_forward.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(HnsPolicyIo), C.c_int32, C.c_uint64,
+                                       C.c_void_p, C.c_void_p]
+    lib.hns_policy_forward.restype = C.c_int
     lib.hns_set_state.argtypes = [C.c_void_p, C.POINTER(HnsBuffers), C.c_void_p]
     lib.hns_set_state.restype = C.c_int
     lib.hns_get_state.argtypes = [C.c_void_p, C.POINTER(HnsBuffers), C.c_void_p]
@@ -316,5 +340,5 @@ def load_library():
 EXPORTED_SYMBOLS = [
     "hns_create", "hns_destroy", "hns_bind", "hns_step", "hns_reset", "hns_reset_tasks", "hns_raycast", "hns_set_v_prey",
     "hns_set_smoothness_coef", "hns_set_reset_epoch", "hns_get_reset_epoch", "hns_enable_timing",
-    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_gae", "hns_rollout_normalise", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_selected_kernels", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_tp_train_workspace_bytes", "hns_tp_train_grad", "hns_tp_adam", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
+    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_gae", "hns_rollout_normalise", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_selected_kernels", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_tp_train_workspace_bytes", "hns_tp_train_grad", "hns_tp_adam", "hns_policy_packed_bytes", "hns_policy_pack", "hns_policy_forward", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
 ]

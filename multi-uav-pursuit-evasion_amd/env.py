@@ -863,10 +863,19 @@ class HideAndSeek(_EnvBase):
         return out
 
     # ---- checkpoint / resume of the env state (the reference checkpoints the policy only, train.py:288-292) ----
-    def load_policy_checkpoint(self, checkpoint):
+    def load_policy_checkpoint(self, checkpoint, policy=False, seed=0):
         """Take the trajectory predictor's parameters from a checkpoint of the reference's MAPPO policy
         (`MAPPOPolicy.state_dict()`, learning/mappo.py:477-484: {"TP", "critic", "actor_params", "value_normalizer"};
-        written by scripts/train.py:292,318 with torch.save).  `checkpoint` is that dict or a path to it."""
+        written by scripts/train.py:292,318 with torch.save).  `checkpoint` is that dict or a path to it.
+        `policy=True`: also return the actor and critic as a hns_amd.policy.DevicePolicy on this env's device (the predictor is loaded
+        as before when algo.use_TP_net is on; without it only the policy is read)."""
+        if policy:
+            from .policy import DevicePolicy
+            if not isinstance(checkpoint, dict):
+                checkpoint = torch.load(checkpoint, map_location="cpu", weights_only=False)
+            if self.use_TP_net:
+                self.TP.load_state_dict(checkpoint["TP"])
+            return DevicePolicy.from_checkpoint(checkpoint, device=self.device, seed=seed)
         if not self.use_TP_net:
             raise HnsError("load_policy_checkpoint: algo.use_TP_net is off, there is no predictor to load")
         if not isinstance(checkpoint, dict):

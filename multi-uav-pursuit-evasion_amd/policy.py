@@ -1,0 +1,382 @@
+"""The MAPPO policy's forward pass on the device: MAPPOPolicy.__call__ and value_op (learning/mappo.py:221-250) for HideAndSeek.
+
+The reference's network for this task, at cfg/algo/mappo.yaml's defaults (share_actor: True, critic_input: obs, no rnn, tanh: false), is a
+PartialAttentionEncoder per network (modules/networks.py:250-313: SplitEmbedding over state_self / state_others / cylinders, LayerNorm,
+single-query attention, a GELU feed-forward and two more LayerNorms; embed_dim 128), a DiagGaussian head for the actor (fc_mean 128 -> 4,
+scale = exp(log_std)) and v_out 128 -> 1 for the critic.  `DevicePolicy` runs both networks for every (env, agent) row in ONE call of
+`hns_policy_forward`: loc, an action (a sample, or the mode with deterministic=True), its log_prob and the critic's value.  The noise is the
+caller's eps, or Philox4x32-10 drawn in the kernel from (seed, device call counter, row) — a captured graph draws fresh noise on every replay.
+
+Parameters come from the reference's live objects (`actor_params`, a TensorDictParams of the shared actor, and the critic module) or from a
+checkpoint written by scripts/train.py (`MAPPOPolicy.state_dict()`: "actor_params", "critic").  Names are accepted with or without
+TensorDictModule's `module.` prefix.  The packed operand image is rebuilt on the device when a parameter's data_ptr or version counter moves,
+so the next call follows an optimiser step (as env.HideAndSeek._tp_sync_weights does for the predictor).
+
+CPU tensors run a torch restatement of the reference's statements (tests, gloo runs — not the hot path).  DESIGN.md §7.3."""
+import collections
+import ctypes as C
+import math
+
+import torch
+import torch.nn.functional as F
+
+from . import abi
+
+EMBED_DIM = 128
+ACTION_DIM = 4
+KEYS = ("state_self", "state_others", "cylinders")          # spec order of the observation CompositeSpec (env._set_specs)
+
+# reference parameter names (after `module.`) of one PartialAttentionEncoder -> hns_policy_net fields
+_ENCODER = {
+    "split_embed.embed.state_self.weight": "embed_self_w", "split_embed.embed.state_self.bias": "embed_self_b",
+    "split_embed.embed.state_others.weight": "embed_others_w", "split_embed.embed.state_others.bias": "embed_others_b",
+    "split_embed.embed.cylinders.weight": "embed_cyl_w", "split_embed.embed.cylinders.bias": "embed_cyl_b",
+    "split_embed.layer_norm.weight": "ln_w", "split_embed.layer_norm.bias": "ln_b",
+    "attn.in_proj_weight": "in_proj_w", "attn.in_proj_bias": "in_proj_b",
+    "attn.out_proj.weight": "out_proj_w", "attn.out_proj.bias": "out_proj_b",
+    "linear1.weight": "linear1_w", "linear1.bias": "linear1_b", "linear2.weight": "linear2_w", "linear2.bias": "linear2_b",
+    "norm1.weight": "norm1_w", "norm1.bias": "norm1_b", "norm2.weight": "norm2_w", "norm2.bias": "norm2_b",
+}
+ACTOR_NAMES = {**{"encoder." + k: v for k, v in _ENCODER.items()},
+               "act_dist.fc_mean.weight": "head_w", "act_dist.fc_mean.bias": "head_b", "act_dist.log_std": "log_std"}
+CRITIC_NAMES = {**{"base." + k: v for k, v in _ENCODER.items()}, "v_out.weight": "head_w", "v_out.bias": "head_b"}
+
+PolicyOutput = collections.namedtuple("PolicyOutput", ["action", "log_prob", "value", "loc"])
+
+
+class PolicyConfigError(ValueError):
+    """The network or configuration is one this forward pass does not implement."""
+
+
+def check_config(cfg):
+    """Refuse the algo configurations the device forward pass does not cover (cfg: the algo cfg mapping, or None)."""
+    if cfg is None:
+        return
+    get = cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
+    if not get("share_actor", True):
+        raise PolicyConfigError("share_actor: False (one actor per agent) is not supported; only the shared actor is")
+    if get("critic_input", "obs") != "obs":
+        raise PolicyConfigError(f"critic_input: {get('critic_input')} (the centralised critic) is not supported; only critic_input: obs is")
+    for part in ("actor", "critic"):
+        sub = get(part, None)
+        if sub is None:
+            continue
+        sget = sub.get if hasattr(sub, "get") else (lambda k, d=None, s=sub: getattr(s, k, d))
+        if sget("rnn", None):
+            raise PolicyConfigError(f"{part}.rnn is not supported")
+        if part == "actor" and sget("tanh", False):
+            raise PolicyConfigError("actor.tanh: true (TanhNormal) is not supported; only the DiagGaussian actor is")
+
+
+def _flatten(obj, prefix=""):
+    """name -> tensor from an nn.Module, a TensorDict-like (flatten_keys / items) or a (nested) mapping; `module.` prefixes dropped."""
+    if hasattr(obj, "named_parameters") and not hasattr(obj, "flatten_keys"):
+        items = list(obj.named_parameters())
+        if not items:
+            items = list(obj.state_dict(keep_vars=True).items())
+    elif hasattr(obj, "flatten_keys"):
+        flat = obj.flatten_keys(".")
+        items = list(flat.items())
+    elif hasattr(obj, "items"):
+        out = {}
+        for k, v in obj.items():
+            k = ".".join(k) if isinstance(k, tuple) else str(k)
+            if torch.is_tensor(v):
+                out[prefix + k] = v
+            else:
+                out.update(_flatten(v, prefix + k + "."))
+        return out
+    else:
+        raise TypeError(f"cannot read parameters from {type(obj).__name__}")
+    out = {}
+    for k, v in items:
+        k = ".".join(k) if isinstance(k, tuple) else str(k)
+        out[prefix + k] = v
+    return out
+
+
+def _strip(name):
+    while name.startswith("module."):
+        name = name[len("module."):]
+    return name
+
+
+def parse_parameters(params, names, what):
+    """The hns_policy_net fields of one network from reference parameter names; raises PolicyConfigError on anything it does not implement."""
+    flat = {_strip(k): v for k, v in _flatten(params).items()}
+    out, unknown = {}, []
+    for k, v in flat.items():
+        if k in names:
+            out[names[k]] = v
+        else:
+            unknown.append(k)
+    if any(".rnn." in "." + k or k.startswith("rnn.") for k in unknown):
+        raise PolicyConfigError(f"{what}: an rnn is not supported ({[k for k in unknown if 'rnn' in k][:3]})")
+    if unknown:
+        raise PolicyConfigError(f"{what}: parameters this network does not have: {sorted(unknown)[:6]} (centralised critic, tanh actor or another "
+                                "encoder?)")
+    required = set(names.values()) - {"embed_others_w", "embed_others_b"}
+    missing = sorted(required - set(out))
+    if missing:
+        raise PolicyConfigError(f"{what}: missing parameters {missing}")
+    E = EMBED_DIM
+    w = out["in_proj_w"]
+    if w.dim() != 2:
+        raise PolicyConfigError(f"{what}: parameters with a leading agent dimension (share_actor: False) are not supported")
+    if tuple(w.shape) != (3 * E, E) or tuple(out["linear1_w"].shape) != (E, E) or tuple(out["linear2_w"].shape) != (E, E):
+        raise PolicyConfigError(f"{what}: embed_dim and dim_feedforward must be 128 (in_proj_weight {tuple(w.shape)}, linear1 "
+                                f"{tuple(out['linear1_w'].shape)})")
+    heads = ACTION_DIM if "log_std" in names.values() else 1
+    if tuple(out["head_w"].shape) != (heads, E) or tuple(out["head_b"].shape) != (heads,):
+        raise PolicyConfigError(f"{what}: the head must be Linear(128, {heads}), not {tuple(out['head_w'].shape)}")
+    if heads == ACTION_DIM and tuple(out["log_std"].shape) != (ACTION_DIM,):
+        raise PolicyConfigError(f"{what}: log_std must have {ACTION_DIM} values")
+    if tuple(out["embed_cyl_w"].shape) != (E, 5):
+        raise PolicyConfigError(f"{what}: the cylinders embedding must be Linear(5, 128)")
+    if ("embed_others_w" in out) and tuple(out["embed_others_w"].shape) != (E, 3):
+        raise PolicyConfigError(f"{what}: the state_others embedding must be Linear(3, 128)")
+    sw = out["embed_self_w"]
+    if sw.dim() != 2 or sw.shape[0] != E or not 1 <= sw.shape[1] <= abi.HNS_POLICY_MAX_SELF_DIM:
+        raise PolicyConfigError(f"{what}: the state_self embedding must be Linear(D, 128) with D in [1, {abi.HNS_POLICY_MAX_SELF_DIM}]")
+    for k, v in out.items():
+        if v.dtype != torch.float32:
+            raise TypeError(f"{what}: parameter {k} must be float32, not {v.dtype}")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# torch restatement (CPU path): the reference's statements, modules/networks.py:125-163, :250-313, distributions.py:66-82, mappo.py:591-660
+def _encoder(p, xs, xo, xc):
+    toks = [F.linear(xs, p["embed_self_w"], p["embed_self_b"])]
+    if xo is not None:
+        toks.append(F.linear(xo, p["embed_others_w"], p["embed_others_b"]))
+    toks.append(F.linear(xc, p["embed_cyl_w"], p["embed_cyl_b"]))
+    x = F.layer_norm(torch.cat(toks, dim=-2), (EMBED_DIM,), p["ln_w"], p["ln_b"])
+    lead = x.shape[:-2]
+    x = x.reshape(-1, x.shape[-2], EMBED_DIM)
+    q = x[:, [0]]
+    attn = F.multi_head_attention_forward(q.transpose(0, 1), x.transpose(0, 1), x.transpose(0, 1), EMBED_DIM, 1, p["in_proj_w"], p["in_proj_b"],
+                                          None, None, False, 0.0, p["out_proj_w"], p["out_proj_b"], training=False, need_weights=False)[0]
+    x = F.layer_norm(q + attn.transpose(0, 1), (EMBED_DIM,), p["norm1_w"], p["norm1_b"])
+    x = F.layer_norm(x + F.linear(F.gelu(F.linear(x, p["linear1_w"], p["linear1_b"])), p["linear2_w"], p["linear2_b"]), (EMBED_DIM,),
+                     p["norm2_w"], p["norm2_b"])
+    return x.mean(-2).reshape(*lead, EMBED_DIM)
+
+
+def torch_forward(actor, critic, xs, xo, xc, eps=None, deterministic=False, value_only=False, generator=None):
+    """The CPU path: (action, log_prob, value, loc) from parameter dicts in hns_policy_net field names; xs [E, A, 1, D]."""
+    value = F.linear(_encoder(critic, xs, xo, xc), critic["head_w"], critic["head_b"])
+    if value_only:
+        return PolicyOutput(None, None, value, None)
+    loc = F.linear(_encoder(actor, xs, xo, xc), actor["head_w"], actor["head_b"])
+    scale = torch.broadcast_to(torch.exp(actor["log_std"]), loc.shape)
+    if deterministic:
+        action = loc
+    else:
+        if eps is None:
+            eps = torch.randn(loc.shape, dtype=loc.dtype, device=loc.device, generator=generator)
+        action = loc + scale * eps
+    log_prob = torch.distributions.Normal(loc, scale).log_prob(action).sum(-1, keepdim=True)
+    return PolicyOutput(action, log_prob, value, loc)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+class DevicePolicy:
+    """The actor's and critic's forward pass of MAPPOPolicy (shared actor, critic on the observation) in one HIP launch per call.
+
+    `DevicePolicy(actor_params, critic)`: actor_params a TensorDictParams / TensorDict / mapping / nn.Module of the actor's parameters,
+    critic the critic TensorDictModule / nn.Module / state_dict.  Live tensors are read in place (an optimiser step is followed); anything on
+    another device than `device` is copied once.  `cfg` (the algo cfg, optional) is checked for what this pass does not implement."""
+
+    def __init__(self, actor_params, critic, cfg=None, device=None, seed=0, agent_name="drone"):
+        check_config(cfg)
+        self.actor_p = parse_parameters(actor_params, ACTOR_NAMES, "actor")
+        self.critic_p = parse_parameters(critic, CRITIC_NAMES, "critic")
+        ds = {v.device for v in (*self.actor_p.values(), *self.critic_p.values())}
+        self.device = torch.device(device) if device is not None else next(iter(ds))
+        if ds != {self.device}:
+            self.actor_p = {k: v.detach().to(self.device).contiguous() for k, v in self.actor_p.items()}
+            self.critic_p = {k: v.detach().to(self.device).contiguous() for k, v in self.critic_p.items()}
+        self.self_dim = int(self.actor_p["embed_self_w"].shape[1])
+        if int(self.critic_p["embed_self_w"].shape[1]) != self.self_dim:
+            raise PolicyConfigError("actor and critic see state_self rows of different widths")
+        if ("embed_others_w" in self.actor_p) != ("embed_others_w" in self.critic_p):
+            raise PolicyConfigError("actor and critic disagree on the state_others key")
+        self.has_others = "embed_others_w" in self.actor_p
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.agent_name = agent_name
+        self._stamp = None
+        self._generator = None
+        if self.device.type == "cuda":
+            self._lib = abi.load_library()
+            nbytes = self._lib.hns_policy_packed_bytes(self.self_dim)
+            self.packed = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self.counter = torch.zeros(1, dtype=torch.int64, device=self.device)   # the Philox call counter (uint64 on the device)
+        else:
+            self._generator = torch.Generator(device="cpu").manual_seed(self.seed)
+
+    @classmethod
+    def from_checkpoint(cls, checkpoint, cfg=None, device=None, seed=0):
+        """From `MAPPOPolicy.state_dict()` (scripts/train.py:292,318) or a path to it: its "actor_params" and "critic" entries."""
+        if not isinstance(checkpoint, dict):
+            checkpoint = torch.load(checkpoint, map_location="cpu", weights_only=False)
+        for k in ("actor_params", "critic"):
+            if k not in checkpoint:
+                raise KeyError(f"checkpoint has no {k!r} entry (keys: {sorted(checkpoint)})")
+        return cls(checkpoint["actor_params"], checkpoint["critic"], cfg=cfg, device=device, seed=seed)
+
+    # ---- packed image
+    def _tensors(self):
+        return [*self.actor_p.values(), *self.critic_p.values()]
+
+    def _net(self, p):
+        n = abi.HnsPolicyNet()
+        for f in abi.POLICY_NET_FIELDS:
+            if f in p:
+                if not p[f].is_contiguous():
+                    raise ValueError(f"parameter {f} must be contiguous")
+                setattr(n, f, p[f].data_ptr())
+        return n
+
+    def refresh(self, force=False):
+        """Re-pack the operand image if a parameter's storage or version counter moved (or `force`)."""
+        stamp = tuple((t.data_ptr(), t._version) for t in self._tensors())
+        if not force and stamp == self._stamp:
+            return
+        a, c = self._net(self.actor_p), self._net(self.critic_p)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            rc = self._lib.hns_policy_pack(C.byref(a), C.byref(c), self.self_dim, 2 if self.has_others else 1, self.packed.data_ptr(), st)
+        self._check(rc, "hns_policy_pack")
+        self._stamp = stamp
+
+    @property
+    def scale(self):
+        """exp(log_std) as the kernel uses it (device: read from the packed image)."""
+        if self.device.type != "cuda":
+            return torch.exp(self.actor_p["log_std"].detach())
+        self.refresh()
+        img = self.packed.view(torch.float32)
+        off = 6 * EMBED_DIM * EMBED_DIM + 18 * EMBED_DIM + 4          # P_SCALE of hns_policy.hip
+        return img[off:off + ACTION_DIM]
+
+    def _check(self, rc, what):
+        if rc != abi.HNS_OK:
+            raise RuntimeError(f"{what} failed ({rc}): {self._lib.hns_last_error().decode()}")
+
+    # ---- forward
+    def _validate(self, xs, xo, xc):
+        if xs.dim() == 4:
+            if xs.shape[2] != 1:
+                raise ValueError(f"state_self must be [E, A, D] or [E, A, 1, D], not {tuple(xs.shape)}")
+            xs = xs.squeeze(2)
+        if xs.dim() != 3 or xs.shape[-1] != self.self_dim:
+            raise ValueError(f"state_self must be [E, A, {self.self_dim}], not {tuple(xs.shape)}")
+        E, A, _ = xs.shape
+        if (xo is not None) != self.has_others or (A > 1) != self.has_others:
+            raise ValueError(f"{A} agents: state_others is {'required' if A > 1 else 'absent'} for this network")
+        if xo is not None and (xo.dim() != 4 or tuple(xo.shape) != (E, A, A - 1, 3)):
+            raise ValueError(f"state_others must be [{E}, {A}, {A - 1}, 3], not {tuple(xo.shape)}")
+        if xc.dim() != 4 or tuple(xc.shape[:2]) != (E, A) or xc.shape[-1] != 5 or not 1 <= xc.shape[2] <= abi.HNS_MAX_CYLINDERS:
+            raise ValueError(f"cylinders must be [{E}, {A}, K, 5] with K in [1, {abi.HNS_MAX_CYLINDERS}], not {tuple(xc.shape)}")
+        for name, t in (("state_self", xs), ("state_others", xo), ("cylinders", xc)):
+            if t is None:
+                continue
+            if t.dtype != torch.float32:
+                raise TypeError(f"{name} must be float32, not {t.dtype}")
+            if t.device != self.device:
+                raise ValueError(f"{name} is on {t.device}, the policy on {self.device}")
+        return xs, xo, xc
+
+    def forward(self, obs_self, obs_others, obs_cylinders, eps=None, deterministic=False, value_only=False):
+        """PolicyOutput(action [E, A, 4], log_prob [E, A, 1], value [E, A, 1], loc [E, A, 4]); value_only: only value is set."""
+        xs, xo, xc = self._validate(obs_self, obs_others, obs_cylinders)
+        E, A, D = xs.shape
+        if eps is not None and (tuple(eps.shape) != (E, A, ACTION_DIM) or eps.dtype != torch.float32 or eps.device != self.device):
+            raise ValueError(f"eps must be float32 [{E}, {A}, {ACTION_DIM}] on {self.device}")
+        if self.device.type != "cuda":
+            with torch.no_grad():
+                return torch_forward(self.actor_p, self.critic_p, xs.unsqueeze(2), xo, xc, eps, deterministic, value_only, self._generator)
+        self.refresh()
+        xs, xc = (t if t.stride(-1) == 1 else t.contiguous() for t in (xs, xc))
+        if xo is not None and xo.stride(-1) != 1:
+            xo = xo.contiguous()
+        eps = eps.contiguous() if eps is not None else None
+        dev = self.device
+        value = torch.empty(E, A, 1, device=dev)
+        action = log_prob = loc = None
+        if not value_only:
+            action, log_prob, loc = torch.empty(E, A, ACTION_DIM, device=dev), torch.empty(E, A, 1, device=dev), torch.empty(E, A, ACTION_DIM, device=dev)
+        io = abi.HnsPolicyIo()
+        io.obs_self, io.obs_cylinders = xs.data_ptr(), xc.data_ptr()
+        io.obs_others = xo.data_ptr() if xo is not None else None
+        io.self_stride[:] = [xs.stride(0), xs.stride(1)]
+        io.others_stride[:] = [xo.stride(0), xo.stride(1), xo.stride(2)] if xo is not None else [0, 0, 0]
+        io.cyl_stride[:] = [xc.stride(0), xc.stride(1), xc.stride(2)]
+        io.eps = eps.data_ptr() if eps is not None else None
+        io.value = value.data_ptr()
+        if not value_only:
+            io.action, io.log_prob, io.loc = action.data_ptr(), log_prob.data_ptr(), loc.data_ptr()
+        flags = (abi.HNS_POLICY_DETERMINISTIC if deterministic else 0) | (abi.HNS_POLICY_VALUE_ONLY if value_only else 0)
+        with torch.cuda.device(dev):
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            rc = self._lib.hns_policy_forward(self.packed.data_ptr(), self.self_dim, E, A, xc.shape[2], C.byref(io), flags, self.seed,
+                                              self.counter.data_ptr(), st)
+        self._check(rc, "hns_policy_forward")
+        return PolicyOutput(action, log_prob, value, loc)
+
+    @staticmethod
+    def _obs(td):
+        obs = td[("agents", "observation")]
+        xo = obs.get("state_others", None) if hasattr(obs, "get") else None
+        return obs["state_self"], xo, obs["cylinders"]
+
+    def __call__(self, tensordict, deterministic=False):
+        """MAPPOPolicy.__call__: writes ("agents", "action"), "<agent>.action_logp" and "state_value" into the tensordict and returns it."""
+        out = self.forward(*self._obs(tensordict), deterministic=deterministic)
+        tensordict[("agents", "action")] = out.action
+        tensordict[f"{self.agent_name}.action_logp"] = out.log_prob
+        tensordict["state_value"] = out.value
+        return tensordict
+
+    def value(self, tensordict):
+        """value_op: the critic's state_value [E, A, 1] (train_op's next_value)."""
+        return self.forward(*self._obs(tensordict), value_only=True).value
+
+
+def random_parameters(self_dim, num_agents, seed=0):
+    """A randomly initialised network of the reference's architecture (PyTorch's default initialisers; DiagGaussian's xavier gain 0.01,
+    zero bias, log_std 0; v_out orthogonal): (actor, critic) parameter dicts in the reference's names, CPU fp32."""
+    g = torch.Generator().manual_seed(seed)
+    E = EMBED_DIM
+
+    def lin(o, i):
+        bound = 1.0 / math.sqrt(i)
+        return (torch.rand(o, i, generator=g) * 2 - 1) * bound, (torch.rand(o, generator=g) * 2 - 1) * bound
+
+    def encoder(prefix):
+        p = {}
+        keys = [("state_self", self_dim), ("state_others", 3), ("cylinders", 5)] if num_agents > 1 else [("state_self", self_dim), ("cylinders", 5)]
+        for k, i in keys:
+            p[f"{prefix}split_embed.embed.{k}.weight"], p[f"{prefix}split_embed.embed.{k}.bias"] = lin(E, i)
+        for n in ("split_embed.layer_norm", "norm1", "norm2"):
+            p[f"{prefix}{n}.weight"], p[f"{prefix}{n}.bias"] = torch.ones(E), torch.zeros(E)
+        bound = math.sqrt(6.0 / (E + E))
+        p[f"{prefix}attn.in_proj_weight"] = (torch.rand(3 * E, E, generator=g) * 2 - 1) * bound
+        p[f"{prefix}attn.in_proj_bias"] = torch.zeros(3 * E)
+        p[f"{prefix}attn.out_proj.weight"], _ = lin(E, E)
+        p[f"{prefix}attn.out_proj.bias"] = torch.zeros(E)
+        p[f"{prefix}linear1.weight"], p[f"{prefix}linear1.bias"] = lin(E, E)
+        p[f"{prefix}linear2.weight"], p[f"{prefix}linear2.bias"] = lin(E, E)
+        return p
+
+    actor = encoder("encoder.")
+    bound = 0.01 * math.sqrt(6.0 / (E + ACTION_DIM))
+    actor["act_dist.fc_mean.weight"] = (torch.rand(ACTION_DIM, E, generator=g) * 2 - 1) * bound
+    actor["act_dist.fc_mean.bias"] = torch.zeros(ACTION_DIM)
+    actor["act_dist.log_std"] = torch.zeros(ACTION_DIM)
+    critic = encoder("base.")
+    q, _ = torch.linalg.qr(torch.randn(E, 1, generator=g))
+    critic["v_out.weight"] = q.T.contiguous() * 0.01
+    _, critic["v_out.bias"] = lin(1, E)
+    return actor, critic
