@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define HNS_ABI_VERSION 6
+#define HNS_ABI_VERSION 7
 #define HNS_MAX_AGENTS 7    /* pursuers per env: a workgroup is 64 envs = A pursuer waves + one env wave (<= 512 threads) */
 #define HNS_MAX_CYLINDERS 16
 #define HNS_NUM_STATS 24    /* hideandseek.py:400-425 */
@@ -546,6 +546,52 @@ int hns_policy_pack(const hns_policy_net *actor, const hns_policy_net *critic, i
  * graph) draws fresh noise.  Deterministic: the same inputs give the same bits. */
 int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
                        int32_t flags, uint64_t seed, uint64_t *counter, void *stream);
+
+/*
+ * The MAPPO critic's update (learning/mappo.py:326-352 on make_critic's network at the defaults: critic_input obs, no rnn): value
+ * loss, explained variance and every parameter's gradient of one minibatch, then clip_grad_norm_ and torch.optim.Adam's update, on the device, in
+ * PyTorch layouts.  No host synchronisation and no allocation: legal inside a stream capture.  Deterministic: fixed-order sums, no float atomics.
+ */
+#define HNS_CRITIC_LOSS_HUBER 0            /* nn.HuberLoss(delta = huber_delta) */
+#define HNS_CRITIC_LOSS_MSE 1              /* nn.MSELoss() */
+typedef struct hns_policy_grads {          /* one network's gradients: hns_policy_net's fields and shapes, writable (log_std: unused by the critic) */
+    float *embed_self_w, *embed_self_b, *embed_others_w, *embed_others_b, *embed_cyl_w, *embed_cyl_b, *ln_w, *ln_b, *in_proj_w, *in_proj_b;
+    float *out_proj_w, *out_proj_b, *linear1_w, *linear1_b, *linear2_w, *linear2_b, *norm1_w, *norm1_b, *norm2_w, *norm2_b, *head_w, *head_b, *log_std;
+} hns_policy_grads;
+typedef struct hns_critic_batch {          /* a minibatch of make_dataset_naive (seq_len 1) read in place from the rollout */
+    const float *obs_self;                 /* [N, T, A, D]: element (n, t, a, i) at n s[0] + t s[1] + a s[2] + i */
+    const float *obs_others;               /* [N, T, A, A - 1, 3]: (n, t, a, j, i) at n s[0] + t s[1] + a s[2] + j s[3] + i; NULL when A = 1 */
+    const float *obs_cylinders;            /* [N, T, A, K, 5] likewise */
+    int64_t self_stride[3], others_stride[4], cyl_stride[4];
+    int64_t num_envs, num_steps;           /* N, T: env-step e of the flattened [N T] is (e / T, e % T) */
+    const int64_t *index;                  /* [batch] env-steps, or NULL: env-steps 0 .. batch - 1; an index outside [0, N T) contributes nothing */
+    int64_t batch;                         /* env-steps in the minibatch; each contributes its A agent rows */
+    const float *b_values, *b_returns;     /* [N T, A] contiguous */
+} hns_critic_batch;
+/* Bytes of device workspace for a minibatch of `rows` = batch x num_agents rows; 0 for an invalid shape.  Per row: the staged operand pairs of
+ * the six weight gradients, 12 x 512 bytes, and the row's share of its 32-row tile's two partial rows of LayerNorm / head / embedding
+ * gradients, (2 308 + 128 self_dim) x 4 / 16 bytes (1.7 KB at self_dim 35, 3.6 KB at 96); beside them the packed operand image (0.8 MB) and
+ * at most 48 x 6 weight-gradient partials (19 MB).  213 MB at 24 576 rows and self_dim 35 (151 + 42 + 20), 6.2 GB at 786 432 rows. */
+size_t hns_critic_train_workspace_bytes(int64_t rows, int32_t self_dim, int32_t num_agents, int32_t num_cylinders);
+/* values = critic(obs); value_loss = max(mean loss(b_returns, values), mean loss(b_returns, b_values + clamp(values - b_values, +-clip_param)))
+ * — the max of two means: one branch for the whole minibatch, both by halves at an exact tie, as torch's backward; explained_var =
+ * 1 - mse(values, b_returns) / var(b_returns) (unbiased); grads: d value_loss / d parameter for each of the critic's 22 tensors (`critic`: live
+ * fp32 tensors in PyTorch layouts, 16-byte aligned; in_proj_b's k third receives zeros: the softmax cancels it); grad_norm: their total 2-norm.
+ * value_loss, explained_var, grad_norm: one device fp32 each; values: [batch, A] or NULL; workspace: 256-byte aligned.  self_dim in [1, 96],
+ * num_agents in [1, 7], num_cylinders in [1, 16], batch >= 1.  Seven launches in one stream. */
+int hns_critic_train_grad(const hns_policy_net *critic, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                          float clip_param, int32_t loss_kind, float huber_delta, const hns_policy_grads *grads, float *value_loss,
+                          float *explained_var, float *grad_norm, float *values, void *workspace, size_t workspace_bytes, void *stream);
+typedef struct hns_adam_tensor {
+    float *param, *grad, *exp_avg, *exp_avg_sq;
+    int64_t numel;
+} hns_adam_tensor;
+/* clip_grad_norm_ and torch.optim.Adam over ANY number of tensors with ONE bump of the device step counter: every gradient is multiplied by
+ * min(max_norm / (*total_norm + 1e-6), 1) in place (torch's statements: the reciprocal, times max_norm, clamped), then Adam's statements in
+ * the order hns_tp_adam documents, with step = *step + 1; *step is bumped after the last tensor.  total_norm NULL or max_norm = +inf: no
+ * clipping (a data-parallel caller all-reduces the gradients and their norm between hns_critic_train_grad and this call). */
+int hns_adam_clipped(const hns_adam_tensor *tensors, int32_t count, float *step, const float *total_norm, double max_norm, double lr, double beta1,
+                     double beta2, double eps, void *stream);
 
 int hns_abi_version(void);
 size_t hns_cfg_size(void);   /* sizeof(hns_cfg) the library was built with (binding self-check) */

@@ -6,7 +6,7 @@ been built (`python -c "import __graft_entry__ as g; g.build()"`).
 import ctypes as C
 import os
 
-HNS_ABI_VERSION = 6
+HNS_ABI_VERSION = 7
 HNS_MAX_AGENTS = 7
 HNS_MAX_CYLINDERS = 16
 HNS_NUM_STATS = 24
@@ -209,6 +209,20 @@ class HnsPolicyIo(C.Structure):
                 ("cyl_stride", C.c_int64 * 3), ("eps", _fp), ("action", _fp), ("loc", _fp), ("log_prob", _fp), ("value", _fp)]
 
 
+# the MAPPO critic's update (include/hns.h: hns_critic_train_grad, hns_adam_clipped; hns_amd.critic_train)
+HNS_CRITIC_LOSS_HUBER, HNS_CRITIC_LOSS_MSE = 0, 1
+
+
+class HnsCriticBatch(C.Structure):
+    _fields_ = [("obs_self", _fp), ("obs_others", _fp), ("obs_cylinders", _fp), ("self_stride", C.c_int64 * 3), ("others_stride", C.c_int64 * 4),
+                ("cyl_stride", C.c_int64 * 4), ("num_envs", C.c_int64), ("num_steps", C.c_int64), ("index", _fp), ("batch", C.c_int64),
+                ("b_values", _fp), ("b_returns", _fp)]
+
+
+class HnsAdamTensor(C.Structure):
+    _fields_ = [("param", _fp), ("grad", _fp), ("exp_avg", _fp), ("exp_avg_sq", _fp), ("numel", C.c_int64)]
+
+
 _LIB = None
 LIB_NAME = "libhns.so"
 
@@ -309,6 +323,15 @@ def load_library():
     lib.hns_policy_forward.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(HnsPolicyIo), C.c_int32, C.c_uint64,
                                        C.c_void_p, C.c_void_p]
     lib.hns_policy_forward.restype = C.c_int
+    lib.hns_critic_train_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32]
+    lib.hns_critic_train_workspace_bytes.restype = C.c_size_t
+    lib.hns_critic_train_grad.argtypes = [C.POINTER(HnsPolicyNet), C.POINTER(HnsCriticBatch), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                          C.c_float, C.POINTER(HnsPolicyNet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.c_void_p]
+    lib.hns_critic_train_grad.restype = C.c_int
+    lib.hns_adam_clipped.argtypes = [C.POINTER(HnsAdamTensor), C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,
+                                     C.c_double, C.c_void_p]
+    lib.hns_adam_clipped.restype = C.c_int
     lib.hns_set_state.argtypes = [C.c_void_p, C.POINTER(HnsBuffers), C.c_void_p]
     lib.hns_set_state.restype = C.c_int
     lib.hns_get_state.argtypes = [C.c_void_p, C.POINTER(HnsBuffers), C.c_void_p]
@@ -340,5 +363,5 @@ def load_library():
 EXPORTED_SYMBOLS = [
     "hns_create", "hns_destroy", "hns_bind", "hns_step", "hns_reset", "hns_reset_tasks", "hns_raycast", "hns_set_v_prey",
     "hns_set_smoothness_coef", "hns_set_reset_epoch", "hns_get_reset_epoch", "hns_enable_timing",
-    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_gae", "hns_rollout_normalise", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_selected_kernels", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_tp_train_workspace_bytes", "hns_tp_train_grad", "hns_tp_adam", "hns_policy_packed_bytes", "hns_policy_pack", "hns_policy_forward", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
+    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_gae", "hns_rollout_normalise", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_selected_kernels", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_tp_train_workspace_bytes", "hns_tp_train_grad", "hns_tp_adam", "hns_policy_packed_bytes", "hns_policy_pack", "hns_policy_forward", "hns_critic_train_workspace_bytes", "hns_critic_train_grad", "hns_adam_clipped", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
 ]

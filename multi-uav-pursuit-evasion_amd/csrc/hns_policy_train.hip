@@ -1,0 +1,1049 @@
+// hns_policy_train.hip — the MAPPO critic's update on the device: value loss, backward pass of the PartialAttentionEncoder, gradient-norm clip, Adam.
+//
+// Reference: MAPPOPolicy.update_critic (omni_drones/learning/mappo.py:326-352) on make_critic's network at cfg/algo/mappo.yaml's defaults
+// (critic_input obs, no rnn): values = v_out(encoder(obs)); clipped = b_values + clamp(values - b_values, +-clip); value_loss = max(mean loss(ret,
+// clipped), mean loss(ret, values)) with nn.HuberLoss(delta) or nn.MSELoss; backward; clip_grad_norm_; torch.optim.Adam.  DESIGN.md §7.4.
+//
+// The network is the one of hns_policy.hip (single-query algebra): per row six 128 x 128 products forward (W_q, W_k^T, W_v, W_o, W_1,
+// W_2) and six against the transposes backward, on v_mfma_f32_16x16x4_f32 for 32 rows at a time, and two token passes on the VALU.
+//   hns_critic_pack_kernel   : the six matrices in both orientations in MFMA A-operand fragment order, the embedding weights transposed.
+//   hns_critic_kernel<false> : forward of the minibatch rows: values, per-tile fp64 partials of sum loss(v), sum loss(clipped), sum (v - ret)^2,
+//                              sum ret, sum ret^2.
+//   hns_critic_loss_kernel   : one workgroup sums the partials in a fixed order: value_loss, explained_var and the branch weights of the max
+//                              ((1, 0), (0, 1), or (1/2, 1/2) at an exact tie, as torch.maximum's backward).
+//   hns_critic_kernel<true>  : recomputes a tile's forward pass, forms dv from the branch weights and walks back to the embeddings.  The operand
+//                              pairs (dy, x) of the six weight gradients are staged in the workspace ([rows, 128] each); LayerNorm, head and
+//                              embedding gradients leave as two partial rows per tile (rows 0-15 and 16-31).
+//   hns_critic_wgrad_kernel  : dW = sum_rows dy (x) x, split over row ranges: per (split, matrix) a 128 x 128 partial and the bias partial
+//                              (column sums of dy).
+//   hns_critic_reduce_kernel : every gradient value = the fp64 sum of its partials in index order, written in the PyTorch layout; per-block sums
+//                              of squares;  hns_critic_norm_kernel adds those in order: the total gradient norm.
+//   hns_adam_clipped_kernel  : clip_grad_norm_'s scaling and torch.optim.Adam's single-tensor statements over any number of tensors; the device
+//                              step counter is bumped once by hns_adam_bump_kernel.
+// Determinism: every sum has a fixed order, no float atomics: the same inputs give the same bits.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <string>
+
+#include "hns_device.h"
+#include "hns_host.h"
+#include "../../include/hns.h"
+
+namespace hns {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kCtE = 128;
+constexpr int kCtRows = 32;                  // rows per tile (two 16-wide MFMA column blocks)
+constexpr int kCtLd = kCtRows + 16;          // LDS pitch of the [feature][row] activations (hns_policy.hip)
+constexpr int kCtThreads = 256;
+constexpr int kCtMat = kCtE * kCtE;
+constexpr int kCtRedLd = kCtE + 4;           // LDS pitch of the [row][feature] images the cross-row sums read
+constexpr int kCtMaxSplits = 48;             // row ranges of the weight-gradient kernel
+constexpr int kCtGemmLd = kCtE + 16;         // LDS pitch of the staged operand tiles: the four k rows of an operand read fall in distinct banks
+constexpr int kCtGemmOut = kCtMat + kCtE;    // a weight-gradient partial: dW, then the bias partial
+constexpr int kCtMaxBlocks = 4096;           // upper bound of the reduce kernel's grid (its per-block sums of squares)
+constexpr int kCtMaxSelf = HNS_POLICY_MAX_SELF_DIM;
+
+// image: 12 matrices in fragment order — forward Q, K^T, V, O, L1, L2, then their transposes — and the embedding weights transposed
+constexpr int I_EW = 12 * kCtMat;
+static __host__ __device__ __forceinline__ long long ct_img_floats(int D) { return I_EW + (long long)(D + 8) * kCtE; }
+
+// a tile's partial row (two per tile: rows 0-15 and 16-31)
+enum : int {
+    O_LNW = 0, O_LNB = 128, O_N1W = 256, O_N1B = 384, O_N2W = 512, O_N2B = 640, O_HW = 768, O_EBS = 896, O_EBO = 1024, O_EBC = 1152,
+    O_EWO = 1280,                            // [3][128]
+    O_EWC = O_EWO + 3 * kCtE,                // [5][128]
+    O_HB = O_EWC + 5 * kCtE,                 // 1 value (+ 3 of padding)
+    O_EWS = O_HB + 4,                        // [D][128]
+};
+static __host__ __device__ constexpr int ct_partial_floats(int D) { return O_EWS + D * kCtE; }
+static_assert((6 * kCtGemmOut + 31) / 32 + (ct_partial_floats(kCtMaxSelf) + 31) / 32 <= kCtMaxBlocks, "the reduce kernel's grid outgrew its per-block sums");
+
+struct CtNet {
+    const float *ew[3], *eb[3], *ln_w, *ln_b, *in_w, *in_b, *out_w, *out_b, *l1_w, *l1_b, *l2_w, *l2_b, *n1_w, *n1_b, *n2_w, *n2_b, *head_w, *head_b;
+};
+struct CtGrad {
+    float *ew[3], *eb[3], *ln_w, *ln_b, *in_w, *in_b, *out_w, *out_b, *l1_w, *l1_b, *l2_w, *l2_b, *n1_w, *n1_b, *n2_w, *n2_b, *head_w, *head_b;
+};
+
+__global__ __launch_bounds__(256) void hns_critic_pack_kernel(const CtNet s, int D, float *img) {
+    const long long n = ct_img_floats(D);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        float v;
+        if (i < I_EW) {
+            const int m = (int)(i / kCtMat), x = (int)(i % kCtMat);
+            const int u = x & 3, lane = (x >> 2) & 63, s4 = (x >> 8) & 7, rb = x >> 11;
+            const int row = rb * 16 + (lane & 15), k = 4 * (4 * s4 + u) + (lane >> 4);
+            const int a = m >= 6 ? k : row, b = m >= 6 ? row : k;        // element [a][b] of the forward-orientation matrix
+            switch (m % 6) {
+                case 0: v = s.in_w[a * kCtE + b]; break;
+                case 1: v = s.in_w[(kCtE + b) * kCtE + a]; break;       // W_k^T
+                case 2: v = s.in_w[(2 * kCtE + a) * kCtE + b]; break;
+                case 3: v = s.out_w[a * kCtE + b]; break;
+                case 4: v = s.l1_w[a * kCtE + b]; break;
+                default: v = s.l2_w[a * kCtE + b]; break;
+            }
+        } else {
+            const long long e = i - I_EW;
+            const int in = (int)(e / kCtE), f = (int)(e % kCtE);
+            if (in < D) v = s.ew[0][f * D + in];
+            else if (in < D + 3) v = s.ew[1] ? s.ew[1][f * 3 + (in - D)] : 0.0f;
+            else v = s.ew[2][f * 5 + (in - D - 3)];
+        }
+        img[i] = v;
+    }
+}
+
+struct CtArgs {
+    const float *img;
+    CtNet net;
+    const float *xs, *xo, *xc;               // element (n, t, a, [j,] i) at n s?[0] + t s?[1] + a s?[2] (+ j s?[3]) + i
+    long long ss[3], so[4], sc[4];
+    long long T, steps;                      // env-steps = num_envs T
+    const long long *index;                  // [batch] env-steps, or NULL
+    long long rows;                          // batch A
+    int A, K, D, tiles;
+    const float *bval, *bret;                // [steps, A]
+    float clip, delta, inv_n;
+    int mse;
+    float *values;                           // [rows] or NULL
+    double *losspart;                        // [tiles][5]
+    const float *ctl;                        // branch weights (written by hns_critic_loss_kernel)
+    float *tilepart;                         // [2 tiles][P]
+    int P;
+    float *stage;                            // 12 arrays [stage_rows][128]: dy, x of Q, K, V, O, L1, L2
+    long long stage_rows;
+};
+
+struct CtLds {
+    double dred[5 * kCtRows];
+    float a[kCtE * kCtLd], b[kCtE * kCtLd], c[kCtE * kCtLd];
+    float p[kCtE * kCtLd];                   // (from here on: the backward kernel only)
+    float red[kCtRows * kCtRedLd];
+    float sx[kCtMaxSelf * kCtRows];
+    float sc[kCtRows];
+};
+constexpr size_t kCtLdsFwd = offsetof(CtLds, p);
+
+HNS_DEV f32x4 cmfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+// OUT[128][R] = W[128][128] IN[128][R]; EPI 0: + bias; 1: gelu(. + bias); 2: times 1/sqrt(128); 3: nothing; 4: . + bias to out2, its gelu to out.
+// `stage` (or NULL): the tile's [32][128] block of a staging array, receives what `out` receives.
+template <int EPI>
+HNS_DEV void ct_matvec(const float *__restrict__ W, const float *__restrict__ bias, const float *in, float *out, float *out2, float *stage, int w, int lane) {
+    const int col = lane & 15, kq = lane >> 4;
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const f32x4 *A0 = reinterpret_cast<const f32x4 *>(W) + (2 * w) * 8 * 64 + lane;
+    const f32x4 *A1 = A0 + 8 * 64;
+#pragma unroll
+    for (int s4 = 0; s4 < 8; ++s4) {
+        const f32x4 a0 = A0[s4 * 64], a1 = A1[s4 * 64];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = 4 * (4 * s4 + u) + kq;
+            const float b0 = in[k * kCtLd + col], b1 = in[k * kCtLd + 16 + col];
+            acc[0][0] = cmfma(a0[u], b0, acc[0][0]);
+            acc[0][1] = cmfma(a0[u], b1, acc[0][1]);
+            acc[1][0] = cmfma(a1[u], b0, acc[1][0]);
+            acc[1][1] = cmfma(a1[u], b1, acc[1][1]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int f0 = (2 * w + i) * 16 + 4 * kq;
+            f32x4 o;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = acc[i][c][r];
+                if (EPI == 2) v = v * 0.08838834764831845f;        // 1 / sqrt(128)
+                else if (EPI != 3) v = v + bias[f0 + r];
+                if (EPI == 4) out2[(f0 + r) * kCtLd + c * 16 + col] = v;
+                if (EPI == 1 || EPI == 4) v = 0.5f * v * (1.0f + erff(v * 0.7071067811865476f));
+                out[(f0 + r) * kCtLd + c * 16 + col] = v;
+                o[r] = v;
+            }
+            if (stage) *reinterpret_cast<f32x4 *>(stage + (c * 16 + col) * kCtE + f0) = o;
+        }
+}
+
+// the thread's 16 features of a row: f = 4 g + 32 i + u (g = the lane in the row's group of eight)
+HNS_DEV int cfeat(int g, int i, int u) { return 4 * g + 32 * i + u; }
+
+HNS_DEV float crow_sum8(float v) {
+    v += __shfl_xor(v, 1, 64);
+    v += __shfl_xor(v, 2, 64);
+    v += __shfl_xor(v, 4, 64);
+    return v;
+}
+
+HNS_DEV void cvec_load(const float *p, int g, float (&x)[16]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(p + cfeat(g, i, 0));
+#pragma unroll
+        for (int u = 0; u < 4; ++u) x[4 * i + u] = v[u];
+    }
+}
+
+// LayerNorm(128), eps 1e-5 (the statements of hns_policy.hip's pol_layernorm): xh = the normalised vector, y = xh w + b; returns 1 / std
+HNS_DEV float ct_ln(const float (&x)[16], const float *w, const float *b, int g, float (&xh)[16], float (&y)[16]) {
+    float s = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s += x[i];
+    const float mean = crow_sum8(s) * (1.0f / kCtE);
+    float q = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        xh[i] = x[i] - mean;
+        q = __builtin_fmaf(xh[i], xh[i], q);
+    }
+    const float rstd = 1.0f / __builtin_sqrtf(crow_sum8(q) * (1.0f / kCtE) + 1e-5f);
+    float wv[16], bv[16];
+    cvec_load(w, g, wv);
+    cvec_load(b, g, bv);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        xh[i] = xh[i] * rstd;
+        y[i] = xh[i] * wv[i] + bv[i];
+    }
+    return rstd;
+}
+
+// LayerNorm backward: dx = rstd (g - mean(g) - xh mean(g xh)) with g = dy w; dw += dy xh, db += dy
+HNS_DEV void ct_ln_bwd(const float (&dy)[16], const float (&xh)[16], float rstd, const float *w, int g, float (&dx)[16], float (&dw)[16], float (&db)[16]) {
+    float wv[16], gi[16];
+    cvec_load(w, g, wv);
+    float s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        gi[i] = dy[i] * wv[i];
+        s1 += gi[i];
+        s2 = __builtin_fmaf(gi[i], xh[i], s2);
+        dw[i] = __builtin_fmaf(dy[i], xh[i], dw[i]);
+        db[i] += dy[i];
+    }
+    const float m1 = crow_sum8(s1) * (1.0f / kCtE), m2 = crow_sum8(s2) * (1.0f / kCtE);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) dx[i] = rstd * ((gi[i] - m1) - xh[i] * m2);
+}
+
+// token = LN(embedding of the n inputs at x (NULL: zeros) + bias): t, its normalised vector xh; returns 1 / std
+HNS_DEV float ct_token(const float *ewT, const float *eb, const float *x, int n, const float *lnw, const float *lnb, int g, float (&xh)[16], float (&t)[16]) {
+    asm volatile("" ::: "memory");                              // the embedding rows are loaded per token, not hoisted out of the token loops
+    float e[16], eb16[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) e[i] = 0.0f;
+    if (x) {
+        for (int k = 0; k < n; ++k) {
+            const float xv = x[k];
+            const float *wr = ewT + k * kCtE;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const f32x4 wv = *reinterpret_cast<const f32x4 *>(wr + cfeat(g, i, 0));
+#pragma unroll
+                for (int u = 0; u < 4; ++u) e[4 * i + u] = __builtin_fmaf(wv[u], xv, e[4 * i + u]);
+            }
+        }
+    }
+    cvec_load(eb, g, eb16);                                     // the bias last (one rounding at its magnitude, as F.linear: near-constant tokens)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) e[i] += eb16[i];
+    return ct_ln(e, lnw, lnb, g, xh, t);
+}
+
+HNS_DEV void clds_load(const float *buf, int r, int g, float (&x)[16]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) x[4 * i + u] = buf[cfeat(g, i, u) * kCtLd + r];
+}
+
+HNS_DEV void clds_store(float *buf, int r, int g, const float (&x)[16]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) buf[cfeat(g, i, u) * kCtLd + r] = x[4 * i + u];
+}
+
+// the row's vector into a [row][feature] image (LDS pitch kCtRedLd, or a staging block at pitch 128)
+HNS_DEV void crow_store(float *img, int pitch, int r, int g, const float (&x)[16]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        *reinterpret_cast<f32x4 *>(img + r * pitch + cfeat(g, i, 0)) = f32x4{x[4 * i], x[4 * i + 1], x[4 * i + 2], x[4 * i + 3]};
+}
+
+// sum of the vector over rows 0-15 and 16-31 of the tile, written to the tile's two partial rows at `off` (fixed order)
+HNS_DEV void ct_flush(CtLds &L, const float (&v)[16], float *part, int P, int off, int tid, int r, int g) {
+    crow_store(L.red, kCtRedLd, r, g, v);
+    __syncthreads();
+    const int f = tid & 127, half = tid >> 7;
+    float s = 0.0f;
+#pragma unroll
+    for (int rr = 0; rr < 16; ++rr) s += L.red[(half * 16 + rr) * kCtRedLd + f];
+    float *d = part + (long long)half * P + off + f;
+    *d = s;
+    __syncthreads();
+}
+
+HNS_DEV float ct_dloss(float x, float delta, int mse) {         // d loss / d x before the 1 / n of the mean
+    if (mse) return 2.0f * x;
+    return x <= -delta ? -delta : (x >= delta ? delta : x);
+}
+
+HNS_DEV double ct_loss64(double x, double delta, int mse) {
+    if (mse) return x * x;
+    const double ax = fabs(x);
+    return ax < delta ? 0.5 * x * x : delta * (ax - 0.5 * delta);
+}
+
+struct CtRow {
+    bool live;
+    long long e;                             // env-step
+    int ag;
+    const float *xs, *xo, *xc;
+};
+
+HNS_DEV CtRow ct_row(const CtArgs &a, long long row) {
+    CtRow R;
+    R.live = row < a.rows;
+    const long long q = R.live ? row / a.A : 0;
+    R.ag = R.live ? (int)(row % a.A) : 0;
+    R.e = R.live ? (a.index ? a.index[q] : q) : 0;
+    if (R.e < 0 || R.e >= a.steps) { R.live = false; R.e = 0; }   // an index outside the rollout contributes nothing (callers check the range)
+    const long long n = R.e / a.T, t = R.e % a.T;
+    R.xs = R.live ? a.xs + n * a.ss[0] + t * a.ss[1] + R.ag * a.ss[2] : nullptr;
+    R.xo = R.live && a.xo ? a.xo + n * a.so[0] + t * a.so[1] + R.ag * a.so[2] : nullptr;
+    R.xc = R.live ? a.xc + n * a.sc[0] + t * a.sc[1] + R.ag * a.sc[2] : nullptr;
+    return R;
+}
+
+// token j >= 1 of the row
+HNS_DEV float ct_token_j(const CtArgs &a, const CtRow &R, int j, int g, float (&xh)[16], float (&t)[16], const float *&x, int &n) {
+    const float *ewo = a.img + I_EW + a.D * kCtE;
+    if (j < a.A) {
+        x = R.xo ? R.xo + (j - 1) * a.so[3] : nullptr;
+        n = 3;
+        return ct_token(ewo, a.net.eb[1], x, 3, a.net.ln_w, a.net.ln_b, g, xh, t);
+    }
+    x = R.xc ? R.xc + (j - a.A) * a.sc[3] : nullptr;
+    n = 5;
+    return ct_token(ewo + 3 * kCtE, a.net.eb[2], x, 5, a.net.ln_w, a.net.ln_b, g, xh, t);
+}
+
+template <bool BWD>
+__global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(const CtArgs a) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    CtLds &L = *reinterpret_cast<CtLds *>(lds_raw);
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
+    const float *img = a.img;
+    const CtNet &N = a.net;
+    const int ntok = a.A + a.K;
+    float *part = BWD ? a.tilepart + (long long)blockIdx.x * 2 * a.P : nullptr;
+
+    {   // one tile per workgroup: its two partial rows are written, never accumulated
+        const int tile = blockIdx.x;
+        const long long row = (long long)tile * kCtRows + r;
+        const CtRow R = ct_row(a, row);
+        float *stg = BWD ? a.stage + (long long)tile * kCtRows * kCtE : nullptr;
+        const long long SA = a.stage_rows * kCtE;               // floats per staging array
+
+        // ---- forward
+        float t[16], xh[16];
+        ct_token(img + I_EW, N.eb[0], R.xs, a.D, N.ln_w, N.ln_b, g, xh, t);                 // token 0
+        clds_store(L.a, r, g, t);
+        if (BWD) crow_store(stg + 1 * SA, kCtE, r, g, t);
+        __syncthreads();
+        ct_matvec<0>(img + 0 * kCtMat, N.in_b, L.a, L.b, nullptr, BWD ? stg + 2 * SA : nullptr, w, lane);          // q
+        __syncthreads();
+        ct_matvec<2>(img + 1 * kCtMat, nullptr, L.b, L.c, nullptr, nullptr, w, lane);       // W_k^T q / sqrt(128)
+        __syncthreads();
+        float kq[16], z[16];
+        clds_load(L.c, r, g, kq);
+        float s = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s = __builtin_fmaf(kq[i], t[i], s);
+        float m = crow_sum8(s), l = 1.0f;
+        const float s0 = m;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) z[i] = t[i];
+        for (int j = 1; j < ntok; ++j) {
+            const float *x;
+            int n;
+            ct_token_j(a, R, j, g, xh, t, x, n);
+            s = 0.0f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) s = __builtin_fmaf(kq[i], t[i], s);
+            s = crow_sum8(s);
+            const float mn = s > m ? s : m;
+            const float c = expf(m - mn), p = expf(s - mn);
+            l = l * c + p;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) z[i] = __builtin_fmaf(p, t[i], z[i] * c);
+            m = mn;
+        }
+        const float il = 1.0f / l;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) z[i] *= il;
+        clds_store(L.b, r, g, z);
+        if (BWD) crow_store(stg + 5 * SA, kCtE, r, g, z);
+        __syncthreads();
+        ct_matvec<0>(img + 2 * kCtMat, N.in_b + 2 * kCtE, L.b, L.c, nullptr, BWD ? stg + 7 * SA : nullptr, w, lane);   // v = W_v z + b_v
+        __syncthreads();
+        ct_matvec<0>(img + 3 * kCtMat, N.out_b, L.c, L.b, nullptr, nullptr, w, lane);       // attn
+        __syncthreads();
+        float x1[16], xh1[16], u[16];
+        clds_load(L.a, r, g, u);
+        clds_load(L.b, r, g, t);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) u[i] += t[i];
+        const float rstd1 = ct_ln(u, N.n1_w, N.n1_b, g, xh1, x1);                           // x0' = LN1(x0 + attn)
+        clds_store(L.a, r, g, x1);
+        if (BWD) crow_store(stg + 9 * SA, kCtE, r, g, x1);
+        __syncthreads();
+        if (BWD) ct_matvec<4>(img + 4 * kCtMat, N.l1_b, L.a, L.b, L.p, stg + 11 * SA, w, lane);   // h = gelu(W_1 x0' + b_1), the pre-activation to p
+        else ct_matvec<1>(img + 4 * kCtMat, N.l1_b, L.a, L.b, nullptr, nullptr, w, lane);
+        __syncthreads();
+        ct_matvec<0>(img + 5 * kCtMat, N.l2_b, L.b, L.c, nullptr, nullptr, w, lane);        // W_2 h + b_2
+        __syncthreads();
+        float y[16], xh2[16];
+        clds_load(L.c, r, g, t);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) u[i] = x1[i] + t[i];
+        const float rstd2 = ct_ln(u, N.n2_w, N.n2_b, g, xh2, y);                            // y = LN2(x0' + ff)
+        float hw[16];
+        cvec_load(N.head_w, g, hw);
+        s = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s = __builtin_fmaf(hw[i], y[i], s);
+        const float v = crow_sum8(s) + N.head_b[0];
+        float ret = 0.0f, bv = 0.0f;
+        if (R.live) {
+            ret = a.bret[R.e * a.A + R.ag];
+            bv = a.bval[R.e * a.A + R.ag];
+        }
+        const float d = v - bv;
+        const float dcl = fminf(fmaxf(d, -a.clip), a.clip);
+        const float clipped = bv + dcl;
+
+        if (!BWD) {
+            if (g == 0) {
+                double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0, q4 = 0.0;
+                if (R.live) {
+                    if (a.values) a.values[row] = v;
+                    const double e0 = (double)v - (double)ret, e1 = (double)clipped - (double)ret;
+                    q0 = ct_loss64(e0, (double)a.delta, a.mse);
+                    q1 = ct_loss64(e1, (double)a.delta, a.mse);
+                    q2 = e0 * e0;
+                    q3 = (double)ret;
+                    q4 = (double)ret * (double)ret;
+                }
+                L.dred[0 * kCtRows + r] = q0; L.dred[1 * kCtRows + r] = q1; L.dred[2 * kCtRows + r] = q2;
+                L.dred[3 * kCtRows + r] = q3; L.dred[4 * kCtRows + r] = q4;
+            }
+            __syncthreads();
+            if (tid < 5) {
+                double acc = 0.0;
+                for (int rr = 0; rr < kCtRows; ++rr) acc += L.dred[tid * kCtRows + rr];
+                a.losspart[(long long)tile * 5 + tid] = acc;
+            }
+            return;
+        }
+
+        // ---- backward: dv from the branch weights of max(mean loss(v), mean loss(clipped))
+        float dv = 0.0f;
+        if (R.live) {
+            const float g0 = ct_dloss(v - ret, a.delta, a.mse);
+            const float g1 = (d >= -a.clip && d <= a.clip) ? ct_dloss(clipped - ret, a.delta, a.mse) : 0.0f;   // clamp's backward: inside, bounds included
+            dv = (a.ctl[0] * g0 + a.ctl[1] * g1) * a.inv_n;
+        }
+        float dy[16], dw[16], db[16], dx[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            dy[i] = dv * hw[i];
+            u[i] = dv * y[i];                                   // d head_w
+            dw[i] = 0.0f;
+            db[i] = 0.0f;
+        }
+        ct_ln_bwd(dy, xh2, rstd2, N.n2_w, g, dx, dw, db);       // dx = d(x0' + ff)
+        clds_store(L.b, r, g, dx);
+        crow_store(stg + 10 * SA, kCtE, r, g, dx);
+        if (g == 0) L.sc[r] = dv;
+        ct_flush(L, u, part, a.P, O_HW, tid, r, g);
+        ct_flush(L, dw, part, a.P, O_N2W, tid, r, g);
+        ct_flush(L, db, part, a.P, O_N2B, tid, r, g);
+        if ((tid & 127) == 0) {                                 // d head_b: the two halves' sums of dv
+            const int half = tid >> 7;
+            float sb = 0.0f;
+            for (int rr = 0; rr < 16; ++rr) sb += L.sc[half * 16 + rr];
+            float *dst = part + (long long)half * a.P + O_HB;
+            *dst = sb;
+        }
+        ct_matvec<3>(img + 11 * kCtMat, nullptr, L.b, L.c, nullptr, nullptr, w, lane);      // dh = W_2^T dff
+        __syncthreads();
+        clds_load(L.c, r, g, t);
+        clds_load(L.p, r, g, u);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {                          // gelu'(x) = Phi(x) + x phi(x)
+            const float xx = u[i];
+            const float dg = 0.5f * (1.0f + erff(xx * 0.7071067811865476f)) + xx * (0.3989422804014327f * expf(-0.5f * xx * xx));
+            t[i] = t[i] * dg;
+        }
+        clds_store(L.c, r, g, t);
+        crow_store(stg + 8 * SA, kCtE, r, g, t);
+        __syncthreads();
+        ct_matvec<3>(img + 10 * kCtMat, nullptr, L.c, L.p, nullptr, nullptr, w, lane);      // W_1^T dh'
+        __syncthreads();
+        clds_load(L.b, r, g, dy);
+        clds_load(L.p, r, g, t);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            dy[i] += t[i];                                      // d x0'
+            dw[i] = 0.0f;
+            db[i] = 0.0f;
+        }
+        ct_ln_bwd(dy, xh1, rstd1, N.n1_w, g, dx, dw, db);       // dx = d(x0 + attn)
+        clds_store(L.a, r, g, dx);
+        crow_store(stg + 6 * SA, kCtE, r, g, dx);
+        ct_flush(L, dw, part, a.P, O_N1W, tid, r, g);
+        ct_flush(L, db, part, a.P, O_N1B, tid, r, g);
+        ct_matvec<3>(img + 9 * kCtMat, nullptr, L.a, L.b, nullptr, stg + 4 * SA, w, lane);  // dv = W_o^T dattn
+        __syncthreads();
+        ct_matvec<3>(img + 8 * kCtMat, nullptr, L.b, L.c, nullptr, nullptr, w, lane);       // dz = W_v^T dv
+        __syncthreads();
+
+        // ---- token pass backward: alpha_j = exp(s_j - m) / l, ds_j = alpha_j (dz.t_j - dz.z), dt_j = alpha_j dz + ds_j kq
+        float dz[16], dkq[16], dt0[16];
+        clds_load(L.c, r, g, dz);
+        s = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s = __builtin_fmaf(dz[i], z[i], s);
+        const float dzz = crow_sum8(s);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            dw[i] = 0.0f;                                       // d ln_w, d ln_b over every token of the row
+            db[i] = 0.0f;
+        }
+        {
+            // token 0: its LayerNorm backward waits for W_q^T dq
+            ct_token(img + I_EW, N.eb[0], R.xs, a.D, N.ln_w, N.ln_b, g, xh, t);
+            s = 0.0f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) s = __builtin_fmaf(dz[i], t[i], s);
+            const float al = expf(s0 - m) * il, ds = al * (crow_sum8(s) - dzz);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                dt0[i] = __builtin_fmaf(ds, kq[i], al * dz[i]);
+                dkq[i] = ds * t[i];
+            }
+        }
+        float eo[4] = {0.f, 0.f, 0.f, 0.f}, ec[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // the thread's (feature, half) sums: bias, then the inputs
+        const int ef = tid & 127, eh = tid >> 7;
+        for (int j = 1; j < ntok; ++j) {
+            const float *x;
+            int n;
+            const float rs = ct_token_j(a, R, j, g, xh, t, x, n);
+            float sa = 0.0f, sd = 0.0f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                sa = __builtin_fmaf(kq[i], t[i], sa);
+                sd = __builtin_fmaf(dz[i], t[i], sd);
+            }
+            const float al = expf(crow_sum8(sa) - m) * il, ds = al * (crow_sum8(sd) - dzz);
+            float dt[16], de[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                dt[i] = __builtin_fmaf(ds, kq[i], al * dz[i]);
+                dkq[i] = __builtin_fmaf(ds, t[i], dkq[i]);
+            }
+            ct_ln_bwd(dt, xh, rs, N.ln_w, g, de, dw, db);
+            crow_store(L.red, kCtRedLd, r, g, de);
+            if (g < n) L.sx[g * kCtRows + r] = x ? x[g] : 0.0f;
+            __syncthreads();
+            if (j < a.A) {
+#pragma unroll
+                for (int rr = 0; rr < 16; ++rr) {
+                    const int q = eh * 16 + rr;
+                    const float dd = L.red[q * kCtRedLd + ef];
+                    eo[0] += dd;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) eo[1 + k] = __builtin_fmaf(dd, L.sx[k * kCtRows + q], eo[1 + k]);
+                }
+            } else {
+#pragma unroll
+                for (int rr = 0; rr < 16; ++rr) {
+                    const int q = eh * 16 + rr;
+                    const float dd = L.red[q * kCtRedLd + ef];
+                    ec[0] += dd;
+#pragma unroll
+                    for (int k = 0; k < 5; ++k) ec[1 + k] = __builtin_fmaf(dd, L.sx[k * kCtRows + q], ec[1 + k]);
+                }
+            }
+            __syncthreads();
+        }
+        {
+            float *ph = part + (long long)eh * a.P;
+            ph[O_EBO + ef] = eo[0];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) ph[O_EWO + k * kCtE + ef] = eo[1 + k];
+            ph[O_EBC + ef] = ec[0];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) ph[O_EWC + k * kCtE + ef] = ec[1 + k];
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) dkq[i] *= 0.08838834764831845f;          // d(W_k^T q) = dkq / sqrt(128)
+        clds_store(L.b, r, g, dkq);
+        crow_store(stg + 3 * SA, kCtE, r, g, dkq);
+        __syncthreads();
+        ct_matvec<3>(img + 7 * kCtMat, nullptr, L.b, L.c, nullptr, stg + 0 * SA, w, lane);  // dq = W_k d(W_k^T q)
+        __syncthreads();
+        ct_matvec<3>(img + 6 * kCtMat, nullptr, L.c, L.b, nullptr, nullptr, w, lane);       // W_q^T dq
+        __syncthreads();
+        {
+            float de[16];
+            clds_load(L.a, r, g, u);
+            clds_load(L.b, r, g, y);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) dt0[i] = (dt0[i] + u[i]) + y[i];
+            const float rs = ct_token(img + I_EW, N.eb[0], R.xs, a.D, N.ln_w, N.ln_b, g, xh, t);
+            ct_ln_bwd(dt0, xh, rs, N.ln_w, g, de, dw, db);
+            crow_store(L.red, kCtRedLd, r, g, de);
+            for (int k = g; k < a.D; k += 8) L.sx[k * kCtRows + r] = R.xs ? R.xs[k] : 0.0f;
+            __syncthreads();
+            float *ph = part + (long long)eh * a.P;
+            float sb = 0.0f;
+#pragma unroll
+            for (int rr = 0; rr < 16; ++rr) sb += L.red[(eh * 16 + rr) * kCtRedLd + ef];
+            ph[O_EBS + ef] = sb;
+            for (int k = 0; k < a.D; ++k) {
+                float sw = 0.0f;
+#pragma unroll
+                for (int rr = 0; rr < 16; ++rr) sw = __builtin_fmaf(L.red[(eh * 16 + rr) * kCtRedLd + ef], L.sx[k * kCtRows + eh * 16 + rr], sw);
+                ph[O_EWS + k * kCtE + ef] = sw;
+            }
+            __syncthreads();
+        }
+        ct_flush(L, dw, part, a.P, O_LNW, tid, r, g);
+        ct_flush(L, db, part, a.P, O_LNB, tid, r, g);
+    }
+}
+
+// sums the per-tile loss partials in a fixed order; value_loss, explained_var, branch weights
+__global__ __launch_bounds__(256) void hns_critic_loss_kernel(const double *part, int tiles, double n, float *ctl, float *value_loss, float *explained_var) {
+    __shared__ double sm[5][256];
+    const int tid = threadIdx.x;
+    double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = tid; i < tiles; i += 256)
+#pragma unroll
+        for (int q = 0; q < 5; ++q) acc[q] += part[(long long)i * 5 + q];
+#pragma unroll
+    for (int q = 0; q < 5; ++q) sm[q][tid] = acc[q];
+    __syncthreads();
+    if (tid == 0) {
+        double S[5];
+        for (int q = 0; q < 5; ++q) {
+            double s = 0.0;
+            for (int i = 0; i < 256; ++i) s += sm[q][i];
+            S[q] = s;
+        }
+        const double lo = S[0] / n, lc = S[1] / n;
+        ctl[0] = lo > lc ? 1.0f : (lo < lc ? 0.0f : 0.5f);
+        ctl[1] = lo > lc ? 0.0f : (lo < lc ? 1.0f : 0.5f);
+        value_loss[0] = (float)(lo > lc ? lo : lc);
+        const double var = (S[4] - S[3] * S[3] / n) / (n - 1.0);             // unbiased, as Tensor.var()
+        explained_var[0] = (float)(1.0 - (S[2] / n) / var);
+    }
+}
+
+// dW partials: per (row range, matrix) the 128 x 128 product dy^T x over the range's rows, and the column sums of dy
+__global__ __launch_bounds__(256, 2) void hns_critic_wgrad_kernel(const float *stage, long long stage_rows, int tiles, int tps, float *part) {
+    __shared__ __align__(16) float sdy[kCtRows * kCtGemmLd];
+    __shared__ __align__(16) float sxx[kCtRows * kCtGemmLd];
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, col = lane & 15, kq = lane >> 4;
+    const int m = blockIdx.y, split = blockIdx.x;
+    const float *dy = stage + (long long)(2 * m) * stage_rows * kCtE, *x = stage + (long long)(2 * m + 1) * stage_rows * kCtE;
+    const int t0 = split * tps, t1 = t0 + tps < tiles ? t0 + tps : tiles;
+    f32x4 acc[2][8];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float bs0 = 0.0f, bs1 = 0.0f;
+    for (int t = t0; t < t1; ++t) {
+        const long long base = (long long)t * kCtRows * kCtE;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int idx = tid + 256 * i, rr = idx >> 5, c4 = idx & 31;
+            *reinterpret_cast<f32x4 *>(&sdy[rr * kCtGemmLd + 4 * c4]) = *reinterpret_cast<const f32x4 *>(dy + base + rr * kCtE + 4 * c4);
+            *reinterpret_cast<f32x4 *>(&sxx[rr * kCtGemmLd + 4 * c4]) = *reinterpret_cast<const f32x4 *>(x + base + rr * kCtE + 4 * c4);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const int k = 4 * s + kq;
+            const float a0 = sdy[k * kCtGemmLd + (2 * w) * 16 + col], a1 = sdy[k * kCtGemmLd + (2 * w + 1) * 16 + col];
+            bs0 += a0;
+            bs1 += a1;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const float b = sxx[k * kCtGemmLd + c * 16 + col];
+                acc[0][c] = cmfma(a0, b, acc[0][c]);
+                acc[1][c] = cmfma(a1, b, acc[1][c]);
+            }
+        }
+        __syncthreads();
+    }
+    float *out = part + ((long long)split * 6 + m) * kCtGemmOut;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) out[((2 * w + i) * 16 + 4 * kq + r) * kCtE + c * 16 + col] = acc[i][c][r];
+    bs0 += __shfl_xor(bs0, 16, 64);
+    bs0 += __shfl_xor(bs0, 32, 64);
+    bs1 += __shfl_xor(bs1, 16, 64);
+    bs1 += __shfl_xor(bs1, 32, 64);
+    if (kq == 0) {
+        out[kCtMat + (2 * w) * 16 + col] = bs0;
+        out[kCtMat + (2 * w + 1) * 16 + col] = bs1;
+    }
+}
+
+// where gradient value e of the weight-gradient partials goes (zero: in_proj_bias' k third, whose gradient is identically 0)
+HNS_DEV float *ct_dst_gemm(const CtGrad &g, int e, bool &zero) {
+    const int m = e / kCtGemmOut, x = e % kCtGemmOut;
+    zero = false;
+    if (x < kCtMat) {
+        switch (m) {
+            case 0: case 1: case 2: return g.in_w + m * kCtMat + x;
+            case 3: return g.out_w + x;
+            case 4: return g.l1_w + x;
+            default: return g.l2_w + x;
+        }
+    }
+    const int f = x - kCtMat;
+    switch (m) {
+        case 0: return g.in_b + f;
+        case 1: zero = true; return g.in_b + kCtE + f;
+        case 2: return g.in_b + 2 * kCtE + f;
+        case 3: return g.out_b + f;
+        case 4: return g.l1_b + f;
+        default: return g.l2_b + f;
+    }
+}
+
+HNS_DEV float *ct_dst_tile(const CtGrad &g, int D, int e) {
+    if (e < O_EWO) {
+        const int f = e & 127;
+        switch (e >> 7) {
+            case 0: return g.ln_w + f;
+            case 1: return g.ln_b + f;
+            case 2: return g.n1_w + f;
+            case 3: return g.n1_b + f;
+            case 4: return g.n2_w + f;
+            case 5: return g.n2_b + f;
+            case 6: return g.head_w + f;
+            case 7: return g.eb[0] + f;
+            case 8: return g.eb[1] ? g.eb[1] + f : nullptr;
+            default: return g.eb[2] + f;
+        }
+    }
+    if (e < O_EWC) return g.ew[1] ? g.ew[1] + ((e - O_EWO) & 127) * 3 + ((e - O_EWO) >> 7) : nullptr;
+    if (e < O_HB) return g.ew[2] + ((e - O_EWC) & 127) * 5 + ((e - O_EWC) >> 7);
+    if (e < O_EWS) return e == O_HB ? g.head_b : nullptr;
+    return g.ew[0] + ((e - O_EWS) & 127) * D + ((e - O_EWS) >> 7);
+}
+
+// 32 gradient values per block, 8 threads each: slice s sums its range of the partials in fp64, the slices add up in order
+__global__ __launch_bounds__(256) void hns_critic_reduce_kernel(const float *gpart, int splits, const float *tpart, int nt, int P, int gblocks, const CtGrad g,
+                                                                int D, double *blockpart) {
+    __shared__ double sm[8][32];
+    __shared__ double sq[32];
+    const int tid = threadIdx.x, el = tid & 31, sl = tid >> 5;
+    const bool gemm = (int)blockIdx.x < gblocks;
+    const int e = (gemm ? blockIdx.x : blockIdx.x - gblocks) * 32 + el;
+    const int n = gemm ? splits : nt;
+    const long long stride = gemm ? 6LL * kCtGemmOut : P;
+    const float *src = gemm ? gpart : tpart;
+    float *dst = nullptr;
+    bool zero = false;
+    if (e < stride) dst = gemm ? ct_dst_gemm(g, e, zero) : ct_dst_tile(g, D, e);
+    double acc = 0.0;
+    if (dst && !zero) {
+        const int lo = (int)((long long)n * sl / 8), hi = (int)((long long)n * (sl + 1) / 8);
+        for (int b = lo; b < hi; ++b) acc += (double)src[(long long)b * stride + e];
+    }
+    sm[sl][el] = acc;
+    __syncthreads();
+    if (tid < 32) {
+        double tot = 0.0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) tot += sm[q][el];
+        const float s = (float)tot;
+        if (dst) dst[0] = s;
+        sq[el] = dst ? (double)s * (double)s : 0.0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double tot = 0.0;
+        for (int q = 0; q < 32; ++q) tot += sq[q];
+        blockpart[blockIdx.x] = tot;
+    }
+}
+
+__global__ __launch_bounds__(256) void hns_critic_norm_kernel(const double *blockpart, int nb, float *grad_norm) {
+    __shared__ double sm[256];
+    const int tid = threadIdx.x;
+    double acc = 0.0;
+    for (int i = tid; i < nb; i += 256) acc += blockpart[i];
+    sm[tid] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0;
+        for (int i = 0; i < 256; ++i) s += sm[i];
+        grad_norm[0] = (float)sqrt(s);
+    }
+}
+
+constexpr int kCAdamMax = 64;                // tensors per launch (the descriptors travel in the kernel arguments)
+struct CAdamArgs {
+    float *p[kCAdamMax], *g[kCAdamMax], *m[kCAdamMax], *v[kCAdamMax];
+    long long n[kCAdamMax];
+    int count, clip;
+    const float *step, *norm;
+    float max_norm;
+    double lr, beta1, beta2, eps;
+};
+
+// clip_grad_norm_: g *= min(max_norm / (norm + 1e-6), 1) (torch: reciprocal, then times max_norm), then hns_tp_adam_kernel's statements with
+// step = *step + 1 (the counter itself is bumped by hns_adam_bump_kernel after every tensor is done)
+__global__ __launch_bounds__(256) void hns_adam_clipped_kernel(const CAdamArgs a) {
+    const float step = a.step[0] + 1.0f;
+    float coef = 1.0f;
+    if (a.clip) {
+        coef = (1.0f / (a.norm[0] + 1e-6f)) * a.max_norm;
+        coef = coef > 1.0f ? 1.0f : coef;                       // (a NaN norm stays NaN, as torch's clamp)
+    }
+    const double bc1 = 1.0 - pow(a.beta1, (double)step), bc2 = 1.0 - pow(a.beta2, (double)step);
+    const float w1 = (float)(1.0 - a.beta1), b2 = (float)a.beta2, w2 = (float)(1.0 - a.beta2);
+    const float ss = (float)(-(a.lr / bc1)), bc2s = (float)sqrt(bc2), eps = (float)a.eps;
+    for (int k = 0; k < a.count; ++k) {
+        float *p = a.p[k], *m = a.m[k], *v = a.v[k], *g = a.g[k];
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.n[k]; i += (long long)gridDim.x * 256) {
+            float gi = g[i];
+            if (a.clip) {
+                gi = gi * coef;
+                g[i] = gi;
+            }
+            const float mi = __builtin_fmaf(w1, gi - m[i], m[i]);
+            const float vi = __builtin_fmaf(w2 * gi, gi, v[i] * b2);
+            const float den = __builtin_sqrtf(vi) / bc2s + eps;
+            m[i] = mi;
+            v[i] = vi;
+            p[i] = p[i] + (ss * mi) / den;
+        }
+    }
+}
+
+__global__ void hns_adam_bump_kernel(float *step) { step[0] = step[0] + 1.0f; }
+
+}  // namespace hns
+
+namespace {
+
+int ct_fail(const char *fn, const std::string &m) {
+    hns_set_error(std::string(fn) + ": " + m);
+    return HNS_ERR_INVALID_ARG;
+}
+
+bool ct_aligned(const void *p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
+
+size_t ct_up(size_t v) { return (v + 255) & ~(size_t)255; }
+
+struct CtPlan {
+    long long tiles, tps, splits, stage_rows;
+    int P, gblocks, tblocks;
+    size_t o_ctl, o_loss, o_block, o_img, o_tile, o_gemm, o_stage, total;
+};
+
+bool ct_plan(int64_t rows, int32_t D, int32_t A, int32_t K, CtPlan &p) {
+    if (rows < 1 || rows > ((int64_t)1 << 31) - 64 || D < 1 || D > hns::kCtMaxSelf || A < 1 || A > HNS_MAX_AGENTS || K < 1 || K > HNS_MAX_CYLINDERS) return false;
+    p.tiles = (rows + hns::kCtRows - 1) / hns::kCtRows;
+    p.tps = (p.tiles + hns::kCtMaxSplits - 1) / hns::kCtMaxSplits;
+    p.splits = (p.tiles + p.tps - 1) / p.tps;
+    p.stage_rows = p.tiles * hns::kCtRows;
+    p.P = hns::ct_partial_floats(D);
+    p.gblocks = (6 * hns::kCtGemmOut + 31) / 32;
+    p.tblocks = (p.P + 31) / 32;
+    size_t o = 0;
+    p.o_ctl = o; o += ct_up(64 * sizeof(float));
+    p.o_loss = o; o += ct_up((size_t)p.tiles * 5 * sizeof(double));
+    p.o_block = o; o += ct_up((size_t)hns::kCtMaxBlocks * sizeof(double));
+    p.o_img = o; o += ct_up((size_t)hns::ct_img_floats(D) * sizeof(float));
+    p.o_tile = o; o += ct_up((size_t)p.tiles * 2 * p.P * sizeof(float));
+    p.o_gemm = o; o += ct_up((size_t)p.splits * 6 * hns::kCtGemmOut * sizeof(float));
+    p.o_stage = o; o += ct_up((size_t)12 * p.stage_rows * hns::kCtE * sizeof(float));
+    p.total = o;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t hns_critic_train_workspace_bytes(int64_t rows, int32_t self_dim, int32_t num_agents, int32_t num_cylinders) {
+    CtPlan p;
+    return ct_plan(rows, self_dim, num_agents, num_cylinders, p) ? p.total : 0;
+}
+
+int hns_critic_train_grad(const hns_policy_net *critic, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                          float clip_param, int32_t loss_kind, float huber_delta, const hns_policy_grads *grads, float *value_loss,
+                          float *explained_var, float *grad_norm, float *values, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "hns_critic_train_grad";
+    if (!critic || !batch || !grads || !value_loss || !explained_var || !grad_norm || !workspace) return ct_fail(fn, "null pointer");
+    if (self_dim < 1 || self_dim > hns::kCtMaxSelf) return ct_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kCtMaxSelf) + "]");
+    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return ct_fail(fn, "num_agents must be in [1, 7]");
+    if (num_cylinders < 1 || num_cylinders > HNS_MAX_CYLINDERS) return ct_fail(fn, "num_cylinders must be in [1, 16]");
+    if (batch->batch < 1) return ct_fail(fn, "batch must be >= 1 (the mean over an empty minibatch is NaN)");
+    if (batch->num_envs < 1 || batch->num_steps < 1 || batch->num_envs > ((int64_t)1 << 40) / batch->num_steps) return ct_fail(fn, "num_envs, num_steps must be >= 1");
+    const int64_t steps = batch->num_envs * batch->num_steps;
+    if (batch->batch > ((int64_t)1 << 31) / HNS_MAX_AGENTS) return ct_fail(fn, "batch too large");
+    if (!batch->index && batch->batch > steps) return ct_fail(fn, "batch exceeds the env-steps of the rollout (no index)");
+    if (loss_kind != HNS_CRITIC_LOSS_HUBER && loss_kind != HNS_CRITIC_LOSS_MSE) return ct_fail(fn, "loss_kind must be HNS_CRITIC_LOSS_HUBER or HNS_CRITIC_LOSS_MSE");
+    if (!(clip_param >= 0.0f) || (loss_kind == HNS_CRITIC_LOSS_HUBER && !(huber_delta > 0.0f))) return ct_fail(fn, "clip_param >= 0, huber_delta > 0");
+    const bool others = num_agents > 1;
+    const float *pr[] = {critic->embed_self_w, critic->embed_self_b, critic->embed_cyl_w, critic->embed_cyl_b, critic->ln_w, critic->ln_b, critic->in_proj_w,
+                         critic->in_proj_b, critic->out_proj_w, critic->out_proj_b, critic->linear1_w, critic->linear1_b, critic->linear2_w, critic->linear2_b,
+                         critic->norm1_w, critic->norm1_b, critic->norm2_w, critic->norm2_b, critic->head_w, critic->head_b};
+    float *gr[] = {grads->embed_self_w, grads->embed_self_b, grads->embed_cyl_w, grads->embed_cyl_b, grads->ln_w, grads->ln_b, grads->in_proj_w,
+                   grads->in_proj_b, grads->out_proj_w, grads->out_proj_b, grads->linear1_w, grads->linear1_b, grads->linear2_w, grads->linear2_b,
+                   grads->norm1_w, grads->norm1_b, grads->norm2_w, grads->norm2_b, grads->head_w, grads->head_b};
+    for (int k = 0; k < 20; ++k)
+        if (!pr[k] || !gr[k] || !ct_aligned(pr[k], 16) || !ct_aligned(gr[k], 4)) return ct_fail(fn, "every parameter must be a non-NULL 16-byte aligned fp32 array, every gradient a non-NULL fp32 array");
+    if (others && (!critic->embed_others_w || !critic->embed_others_b || !grads->embed_others_w || !grads->embed_others_b || !ct_aligned(critic->embed_others_b, 16)))
+        return ct_fail(fn, "state_others embedding (parameter or gradient) missing or misaligned (num_agents > 1)");
+    if (!batch->obs_self || !batch->obs_cylinders || (others && !batch->obs_others)) return ct_fail(fn, "observation pointer missing");
+    if (!ct_aligned(batch->obs_self, 4) || !ct_aligned(batch->obs_cylinders, 4) || (batch->obs_others && !ct_aligned(batch->obs_others, 4)))
+        return ct_fail(fn, "misaligned observation");
+    for (int k = 0; k < 3; ++k)
+        if (batch->self_stride[k] < 0) return ct_fail(fn, "negative stride");
+    for (int k = 0; k < 4; ++k)
+        if (batch->others_stride[k] < 0 || batch->cyl_stride[k] < 0) return ct_fail(fn, "negative stride");
+    if (!batch->b_values || !batch->b_returns || !ct_aligned(batch->b_values, 4) || !ct_aligned(batch->b_returns, 4)) return ct_fail(fn, "b_values / b_returns missing or misaligned");
+    if (batch->index && !ct_aligned(batch->index, 8)) return ct_fail(fn, "misaligned index");
+    if (!ct_aligned(value_loss, 4) || !ct_aligned(explained_var, 4) || !ct_aligned(grad_norm, 4) || (values && !ct_aligned(values, 4)) || !ct_aligned(workspace, 256))
+        return ct_fail(fn, "misaligned output (scalars 4 bytes, workspace 256)");
+    CtPlan p;
+    const int64_t rows = batch->batch * num_agents;
+    if (!ct_plan(rows, self_dim, num_agents, num_cylinders, p)) return ct_fail(fn, "invalid shape");
+    if (workspace_bytes < p.total) return ct_fail(fn, "workspace too small (hns_critic_train_workspace_bytes)");
+
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    hns::CtArgs a{};
+    hns::CtNet &n = a.net;
+    n.ew[0] = critic->embed_self_w; n.eb[0] = critic->embed_self_b;
+    n.ew[1] = others ? critic->embed_others_w : nullptr; n.eb[1] = others ? critic->embed_others_b : nullptr;
+    n.ew[2] = critic->embed_cyl_w; n.eb[2] = critic->embed_cyl_b;
+    n.ln_w = critic->ln_w; n.ln_b = critic->ln_b; n.in_w = critic->in_proj_w; n.in_b = critic->in_proj_b; n.out_w = critic->out_proj_w; n.out_b = critic->out_proj_b;
+    n.l1_w = critic->linear1_w; n.l1_b = critic->linear1_b; n.l2_w = critic->linear2_w; n.l2_b = critic->linear2_b;
+    n.n1_w = critic->norm1_w; n.n1_b = critic->norm1_b; n.n2_w = critic->norm2_w; n.n2_b = critic->norm2_b; n.head_w = critic->head_w; n.head_b = critic->head_b;
+    hns::CtGrad G{};
+    G.ew[0] = grads->embed_self_w; G.eb[0] = grads->embed_self_b;
+    G.ew[1] = others ? grads->embed_others_w : nullptr; G.eb[1] = others ? grads->embed_others_b : nullptr;
+    G.ew[2] = grads->embed_cyl_w; G.eb[2] = grads->embed_cyl_b;
+    G.ln_w = grads->ln_w; G.ln_b = grads->ln_b; G.in_w = grads->in_proj_w; G.in_b = grads->in_proj_b; G.out_w = grads->out_proj_w; G.out_b = grads->out_proj_b;
+    G.l1_w = grads->linear1_w; G.l1_b = grads->linear1_b; G.l2_w = grads->linear2_w; G.l2_b = grads->linear2_b;
+    G.n1_w = grads->norm1_w; G.n1_b = grads->norm1_b; G.n2_w = grads->norm2_w; G.n2_b = grads->norm2_b; G.head_w = grads->head_w; G.head_b = grads->head_b;
+
+    float *img = reinterpret_cast<float *>(ws + p.o_img);
+    float *ctl = reinterpret_cast<float *>(ws + p.o_ctl);
+    a.img = img;
+    a.xs = batch->obs_self; a.xo = others ? batch->obs_others : nullptr; a.xc = batch->obs_cylinders;
+    for (int k = 0; k < 3; ++k) a.ss[k] = batch->self_stride[k];
+    for (int k = 0; k < 4; ++k) { a.so[k] = batch->others_stride[k]; a.sc[k] = batch->cyl_stride[k]; }
+    a.T = batch->num_steps; a.steps = steps;
+    a.index = reinterpret_cast<const long long *>(batch->index);
+    a.rows = rows; a.A = num_agents; a.K = num_cylinders; a.D = self_dim; a.tiles = (int)p.tiles;
+    a.bval = batch->b_values; a.bret = batch->b_returns;
+    a.clip = clip_param; a.delta = huber_delta; a.inv_n = (float)(1.0 / (double)rows); a.mse = loss_kind == HNS_CRITIC_LOSS_MSE;
+    a.values = values;
+    a.losspart = reinterpret_cast<double *>(ws + p.o_loss);
+    a.ctl = ctl;
+    a.tilepart = reinterpret_cast<float *>(ws + p.o_tile);
+    a.P = p.P;
+    a.stage = reinterpret_cast<float *>(ws + p.o_stage);
+    a.stage_rows = p.stage_rows;
+
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    static const hipError_t attr_f = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<false>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)hns::kCtLdsFwd);
+    static const hipError_t attr_b = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<true>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::CtLds));
+    HNS_CHECK_HIP(attr_f);
+    HNS_CHECK_HIP(attr_b);
+    hipLaunchKernelGGL(hns::hns_critic_pack_kernel, dim3(256), dim3(256), 0, st, n, (int)self_dim, img);
+    HNS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hns::hns_critic_kernel<false>, dim3((unsigned)p.tiles), dim3(hns::kCtThreads), hns::kCtLdsFwd, st, a);
+    HNS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hns::hns_critic_loss_kernel, dim3(1), dim3(256), 0, st, a.losspart, (int)p.tiles, (double)rows, ctl, value_loss, explained_var);
+    HNS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hns::hns_critic_kernel<true>, dim3((unsigned)p.tiles), dim3(hns::kCtThreads), sizeof(hns::CtLds), st, a);
+    HNS_CHECK_HIP(hipGetLastError());
+    float *gpart = reinterpret_cast<float *>(ws + p.o_gemm);
+    hipLaunchKernelGGL(hns::hns_critic_wgrad_kernel, dim3((unsigned)p.splits, 6), dim3(256), 0, st, a.stage, a.stage_rows, (int)p.tiles, (int)p.tps, gpart);
+    HNS_CHECK_HIP(hipGetLastError());
+    double *blockpart = reinterpret_cast<double *>(ws + p.o_block);
+    const int nb = p.gblocks + p.tblocks;
+    hipLaunchKernelGGL(hns::hns_critic_reduce_kernel, dim3(nb), dim3(256), 0, st, gpart, (int)p.splits, a.tilepart, (int)(2 * p.tiles), p.P, p.gblocks, G,
+                       (int)self_dim, blockpart);
+    HNS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hns::hns_critic_norm_kernel, dim3(1), dim3(256), 0, st, blockpart, nb, grad_norm);
+    HNS_CHECK_HIP(hipGetLastError());
+    return HNS_OK;
+}
+
+int hns_adam_clipped(const hns_adam_tensor *tensors, int32_t count, float *step, const float *total_norm, double max_norm, double lr, double beta1,
+                     double beta2, double eps, void *stream) {
+    const char *fn = "hns_adam_clipped";
+    if (!tensors || !step || count < 1) return ct_fail(fn, "at least one tensor and a device step counter");
+    if (!ct_aligned(step, 4) || (total_norm && !ct_aligned(total_norm, 4))) return ct_fail(fn, "misaligned step counter / norm");
+    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(max_norm >= 0.0))
+        return ct_fail(fn, "lr >= 0, 0 <= beta < 1, eps >= 0, max_norm >= 0");
+    for (int k = 0; k < count; ++k) {
+        const hns_adam_tensor &t = tensors[k];
+        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq || t.numel < 0) return ct_fail(fn, "tensor with a NULL array or numel < 0");
+        if (!ct_aligned(t.param, 4) || !ct_aligned(t.grad, 4) || !ct_aligned(t.exp_avg, 4) || !ct_aligned(t.exp_avg_sq, 4)) return ct_fail(fn, "misaligned fp32 array");
+    }
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    for (int k0 = 0; k0 < count; k0 += hns::kCAdamMax) {
+        hns::CAdamArgs a{};
+        a.count = std::min<int>(hns::kCAdamMax, count - k0);
+        a.clip = total_norm != nullptr && std::isfinite(max_norm);
+        a.step = step; a.norm = total_norm; a.max_norm = (float)max_norm;
+        a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+        long long most = 1;
+        for (int k = 0; k < a.count; ++k) {
+            const hns_adam_tensor &t = tensors[k0 + k];
+            a.p[k] = t.param; a.g[k] = t.grad; a.m[k] = t.exp_avg; a.v[k] = t.exp_avg_sq; a.n[k] = t.numel;
+            most = std::max<long long>(most, t.numel);
+        }
+        const int grid = (int)std::min<long long>((most + 255) / 256, 256);
+        hipLaunchKernelGGL(hns::hns_adam_clipped_kernel, dim3(grid), dim3(256), 0, st, a);
+        HNS_CHECK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(hns::hns_adam_bump_kernel, dim3(1), dim3(1), 0, st, step);
+    HNS_CHECK_HIP(hipGetLastError());
+    return HNS_OK;
+}
+
+}  // extern "C"
