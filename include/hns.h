@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define HNS_ABI_VERSION 7
+#define HNS_ABI_VERSION 8
 #define HNS_MAX_AGENTS 7    /* pursuers per env: a workgroup is 64 envs = A pursuer waves + one env wave (<= 512 threads) */
 #define HNS_MAX_CYLINDERS 16
 #define HNS_NUM_STATS 24    /* hideandseek.py:400-425 */
@@ -554,7 +554,7 @@ int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, i
  */
 #define HNS_CRITIC_LOSS_HUBER 0            /* nn.HuberLoss(delta = huber_delta) */
 #define HNS_CRITIC_LOSS_MSE 1              /* nn.MSELoss() */
-typedef struct hns_policy_grads {          /* one network's gradients: hns_policy_net's fields and shapes, writable (log_std: unused by the critic) */
+typedef struct hns_policy_grads {          /* one network's gradients: hns_policy_net's fields and shapes, writable (log_std: the actor's; unused by the critic) */
     float *embed_self_w, *embed_self_b, *embed_others_w, *embed_others_b, *embed_cyl_w, *embed_cyl_b, *ln_w, *ln_b, *in_proj_w, *in_proj_b;
     float *out_proj_w, *out_proj_b, *linear1_w, *linear1_b, *linear2_w, *linear2_b, *norm1_w, *norm1_b, *norm2_w, *norm2_b, *head_w, *head_b, *log_std;
 } hns_policy_grads;
@@ -592,6 +592,37 @@ typedef struct hns_adam_tensor {
  * clipping (a data-parallel caller all-reduces the gradients and their norm between hns_critic_train_grad and this call). */
 int hns_adam_clipped(const hns_adam_tensor *tensors, int32_t count, float *step, const float *total_norm, double max_norm, double lr, double beta1,
                      double beta2, double eps, void *stream);
+
+/*
+ * The MAPPO actor's update (learning/mappo.py:271-324 on make_ppo_actor's network at the defaults: share_actor, no tanh, no rnn, DiagGaussian over
+ * a 4-dim action): the clipped PPO surrogate, the entropy bonus and every parameter's gradient of one minibatch; the step itself is
+ * hns_adam_clipped over the 23 tensors.  Same properties as the critic's call: one stream, no host synchronisation, no allocation, capturable,
+ * fixed-order sums and no float atomics.
+ */
+typedef struct hns_actor_batch {           /* hns_critic_batch's observation / index part, then the actor's per-row data */
+    const float *obs_self, *obs_others, *obs_cylinders;
+    int64_t self_stride[3], others_stride[4], cyl_stride[4];
+    int64_t num_envs, num_steps;
+    const int64_t *index;
+    int64_t batch;
+    const float *action;                   /* [N T, A, 4] contiguous: the stored actions */
+    const float *log_probs_old;            /* [N T, A] contiguous */
+    const float *advantages;               /* [N T, A] contiguous */
+} hns_actor_batch;
+/* Bytes of device workspace for a minibatch of `rows` = batch x num_agents rows; 0 for an invalid shape.  The critic's workspace with a tile's
+ * partial rows 388 floats longer (three more head rows, log_std) and 22 fp64 loss partials per tile instead of 5. */
+size_t hns_actor_train_workspace_bytes(int64_t rows, int32_t self_dim, int32_t num_agents, int32_t num_cylinders);
+/* Per row: mu = fc_mean(encoder(obs)), logp = sum_i Normal(mu_i, exp(log_std_i)).log_prob(action_i), r = exp(logp - log_probs_old);
+ * policy_loss = -mean(min(r adv, clamp(r, 1 - clip_param, 1 + clip_param) adv) 4); entropy: the mean of the distribution's entropy (the same for
+ * every row); grads: d (policy_loss - entropy_coef entropy) / d parameter for each of the actor's 23 tensors (16-byte aligned live fp32 tensors in
+ * PyTorch layouts; in_proj_b's k third receives zeros) — the backward weight of min and clamp is per row: 1 inside the clip (bounds included),
+ * outside 1 where the unclipped surrogate is the smaller and 0 otherwise; ess = mean over agents of exp(2 logsumexp_batch(r) - logsumexp_batch(2 r))
+ * / batch (of the ratio itself, as the reference writes it); grad_norm: the total 2-norm.  policy_loss, entropy, ess, grad_norm: one device fp32
+ * each; log_probs: [batch, A] or NULL, receives logp.  Six launches in one stream: pack, ONE pass over the tiles (forward, loss partials,
+ * backward), the scalars, weight gradients, reduce, norm. */
+int hns_actor_train_grad(const hns_policy_net *actor, const hns_actor_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                         double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
+                         float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream);
 
 int hns_abi_version(void);
 size_t hns_cfg_size(void);   /* sizeof(hns_cfg) the library was built with (binding self-check) */

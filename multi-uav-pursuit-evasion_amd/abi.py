@@ -6,7 +6,7 @@ been built (`python -c "import __graft_entry__ as g; g.build()"`).
 import ctypes as C
 import os
 
-HNS_ABI_VERSION = 7
+HNS_ABI_VERSION = 8
 HNS_MAX_AGENTS = 7
 HNS_MAX_CYLINDERS = 16
 HNS_NUM_STATS = 24
@@ -219,6 +219,12 @@ class HnsCriticBatch(C.Structure):
                 ("b_values", _fp), ("b_returns", _fp)]
 
 
+class HnsActorBatch(C.Structure):         # the MAPPO actor's update (include/hns.h: hns_actor_train_grad; hns_amd.actor_train)
+    _fields_ = [("obs_self", _fp), ("obs_others", _fp), ("obs_cylinders", _fp), ("self_stride", C.c_int64 * 3), ("others_stride", C.c_int64 * 4),
+                ("cyl_stride", C.c_int64 * 4), ("num_envs", C.c_int64), ("num_steps", C.c_int64), ("index", _fp), ("batch", C.c_int64),
+                ("action", _fp), ("log_probs_old", _fp), ("advantages", _fp)]
+
+
 class HnsAdamTensor(C.Structure):
     _fields_ = [("param", _fp), ("grad", _fp), ("exp_avg", _fp), ("exp_avg_sq", _fp), ("numel", C.c_int64)]
 
@@ -329,6 +335,12 @@ def load_library():
                                           C.c_float, C.POINTER(HnsPolicyNet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                           C.c_void_p]
     lib.hns_critic_train_grad.restype = C.c_int
+    lib.hns_actor_train_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32]
+    lib.hns_actor_train_workspace_bytes.restype = C.c_size_t
+    lib.hns_actor_train_grad.argtypes = [C.POINTER(HnsPolicyNet), C.POINTER(HnsActorBatch), C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                         C.POINTER(HnsPolicyNet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.c_void_p]
+    lib.hns_actor_train_grad.restype = C.c_int
     lib.hns_adam_clipped.argtypes = [C.POINTER(HnsAdamTensor), C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,
                                      C.c_double, C.c_void_p]
     lib.hns_adam_clipped.restype = C.c_int
@@ -363,5 +375,5 @@ def load_library():
 EXPORTED_SYMBOLS = [
     "hns_create", "hns_destroy", "hns_bind", "hns_step", "hns_reset", "hns_reset_tasks", "hns_raycast", "hns_set_v_prey",
     "hns_set_smoothness_coef", "hns_set_reset_epoch", "hns_get_reset_epoch", "hns_enable_timing",
-    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_gae", "hns_rollout_normalise", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_selected_kernels", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_tp_train_workspace_bytes", "hns_tp_train_grad", "hns_tp_adam", "hns_policy_packed_bytes", "hns_policy_pack", "hns_policy_forward", "hns_critic_train_workspace_bytes", "hns_critic_train_grad", "hns_adam_clipped", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
+    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_gae", "hns_rollout_normalise", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_selected_kernels", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_tp_train_workspace_bytes", "hns_tp_train_grad", "hns_tp_adam", "hns_policy_packed_bytes", "hns_policy_pack", "hns_policy_forward", "hns_critic_train_workspace_bytes", "hns_critic_train_grad", "hns_actor_train_workspace_bytes", "hns_actor_train_grad", "hns_adam_clipped", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
 ]

@@ -1,4 +1,5 @@
-// hns_policy_train.hip — the MAPPO critic's update on the device: value loss, backward pass of the PartialAttentionEncoder, gradient-norm clip, Adam.
+// hns_policy_train.hip — the MAPPO critic's and actor's updates on the device: value loss / PPO surrogate, backward pass of the
+// PartialAttentionEncoder, gradient-norm clip, Adam.
 //
 // Reference: MAPPOPolicy.update_critic (omni_drones/learning/mappo.py:326-352) on make_critic's network at cfg/algo/mappo.yaml's defaults
 // (critic_input obs, no rnn): values = v_out(encoder(obs)); clipped = b_values + clamp(values - b_values, +-clip); value_loss = max(mean loss(ret,
@@ -20,6 +21,14 @@
 //                              of squares;  hns_critic_norm_kernel adds those in order: the total gradient norm.
 //   hns_adam_clipped_kernel  : clip_grad_norm_'s scaling and torch.optim.Adam's single-tensor statements over any number of tensors; the device
 //                              step counter is bumped once by hns_adam_bump_kernel.
+// The actor (MAPPOPolicy.update_actor, mappo.py:271-324; DiagGaussian head fc_mean 128 -> 4 and a free log_std[4]) is the same
+// encoder with a four-output head, selected by the tile kernel's HEAD template parameter.  The clipped surrogate's backward weight is per row, so
+// ONE pass over the tiles gives the loss partials and the gradients:
+//   hns_critic_kernel<true, 4> : forward, log-probability, ratio, surrogate and its d mu per row, then the encoder's backward pass as above; per
+//                                tile the fp64 partials of sum min(surr1, surr2) and, per agent, (max, sum exp(r - max), sum exp(2 (r - max)))
+//                                of the ratios; head_w [4][128], head_b [4] and log_std [4] leave in the tile's partial rows.
+//   hns_actor_loss_kernel      : one workgroup adds the partials in a fixed order: policy_loss, entropy, ESS.
+//   pack, wgrad, reduce (which adds -entropy_coef to d log_std, once) and norm kernels: the critic's.
 // Determinism: every sum has a fixed order, no float atomics: the same inputs give the same bits.
 #include <hip/hip_runtime.h>
 
@@ -60,14 +69,19 @@ enum : int {
     O_HB = O_EWC + 5 * kCtE,                 // 1 value (+ 3 of padding)
     O_EWS = O_HB + 4,                        // [D][128]
 };
-static __host__ __device__ constexpr int ct_partial_floats(int D) { return O_EWS + D * kCtE; }
-static_assert((6 * kCtGemmOut + 31) / 32 + (ct_partial_floats(kCtMaxSelf) + 31) / 32 <= kCtMaxBlocks, "the reduce kernel's grid outgrew its per-block sums");
+// the actor's head (heads = 4): head_b's four values at O_HB, head_w row 0 at O_HW, and behind the state_self embedding rows 1-3 of head_w
+// [3][128] and log_std [4]; the critic's layout (heads = 1) ends at the embedding
+constexpr int kActDim = 4;                   // DiagGaussian's action dimension (fc_mean's rows)
+constexpr int kActLossSlots = 1 + 3 * HNS_MAX_AGENTS;   // a tile's fp64 partials: sum of the surrogate, then (max, s1, s2) of the ratios per agent
+static __host__ __device__ constexpr int ct_partial_floats(int D, int heads = 1) { return O_EWS + D * kCtE + (heads > 1 ? (heads - 1) * kCtE + heads : 0); }
+static_assert((6 * kCtGemmOut + 31) / 32 + (ct_partial_floats(kCtMaxSelf, kActDim) + 31) / 32 <= kCtMaxBlocks, "the reduce kernel's grid outgrew its per-block sums");
 
 struct CtNet {
     const float *ew[3], *eb[3], *ln_w, *ln_b, *in_w, *in_b, *out_w, *out_b, *l1_w, *l1_b, *l2_w, *l2_b, *n1_w, *n1_b, *n2_w, *n2_b, *head_w, *head_b;
 };
 struct CtGrad {
     float *ew[3], *eb[3], *ln_w, *ln_b, *in_w, *in_b, *out_w, *out_b, *l1_w, *l1_b, *l2_w, *l2_b, *n1_w, *n1_b, *n2_w, *n2_b, *head_w, *head_b;
+    float *log_std;                          // the actor's; NULL for the critic
 };
 
 __global__ __launch_bounds__(256) void hns_critic_pack_kernel(const CtNet s, int D, float *img) {
@@ -107,16 +121,21 @@ struct CtArgs {
     const long long *index;                  // [batch] env-steps, or NULL
     long long rows;                          // batch A
     int A, K, D, tiles;
-    const float *bval, *bret;                // [steps, A]
+    union { const float *bval; const float *logp_old; };       // [steps, A]: the critic's old values / the actor's old log-probabilities
+    union { const float *bret; const float *adv; };            // [steps, A]: the critic's returns / the actor's advantages
     float clip, delta, inv_n;
     int mse;
-    float *values;                           // [rows] or NULL
-    double *losspart;                        // [tiles][5]
+    union { float *values; float *logp_new; };                 // [rows] or NULL: the critic's values / the actor's new log-probabilities
+    double *losspart;                        // [tiles][5]; the actor: [tiles][kActLossSlots]
     const float *ctl;                        // branch weights (written by hns_critic_loss_kernel)
     float *tilepart;                         // [2 tiles][P]
     int P;
     float *stage;                            // 12 arrays [stage_rows][128]: dy, x of Q, K, V, O, L1, L2
     long long stage_rows;
+    // the actor (HEAD = 4) alone
+    const float *action;                     // [steps, A, 4]
+    const float *log_std;                    // [4]
+    float clip_lo, clip_hi;                  // f32(1 - clip_param), f32(1 + clip_param): torch.clamp's bounds on a float tensor
 };
 
 struct CtLds {
@@ -340,8 +359,9 @@ HNS_DEV float ct_token_j(const CtArgs &a, const CtRow &R, int j, int g, float (&
     return ct_token(ewo + 3 * kCtE, a.net.eb[2], x, 5, a.net.ln_w, a.net.ln_b, g, xh, t);
 }
 
-template <bool BWD>
+template <bool BWD, int HEAD = 1>
 __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(const CtArgs a) {
+    static_assert(HEAD == 1 || (HEAD == kActDim && BWD), "the actor's head runs in the one-pass kernel");
     extern __shared__ __align__(16) unsigned char lds_raw[];
     CtLds &L = *reinterpret_cast<CtLds *>(lds_raw);
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
@@ -420,73 +440,175 @@ __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(con
 #pragma unroll
         for (int i = 0; i < 16; ++i) u[i] = x1[i] + t[i];
         const float rstd2 = ct_ln(u, N.n2_w, N.n2_b, g, xh2, y);                            // y = LN2(x0' + ff)
-        float hw[16];
-        cvec_load(N.head_w, g, hw);
-        s = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s = __builtin_fmaf(hw[i], y[i], s);
-        const float v = crow_sum8(s) + N.head_b[0];
-        float ret = 0.0f, bv = 0.0f;
-        if (R.live) {
-            ret = a.bret[R.e * a.A + R.ag];
-            bv = a.bval[R.e * a.A + R.ag];
-        }
-        const float d = v - bv;
-        const float dcl = fminf(fmaxf(d, -a.clip), a.clip);
-        const float clipped = bv + dcl;
-
-        if (!BWD) {
-            if (g == 0) {
-                double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0, q4 = 0.0;
-                if (R.live) {
-                    if (a.values) a.values[row] = v;
-                    const double e0 = (double)v - (double)ret, e1 = (double)clipped - (double)ret;
-                    q0 = ct_loss64(e0, (double)a.delta, a.mse);
-                    q1 = ct_loss64(e1, (double)a.delta, a.mse);
-                    q2 = e0 * e0;
-                    q3 = (double)ret;
-                    q4 = (double)ret * (double)ret;
-                }
-                L.dred[0 * kCtRows + r] = q0; L.dred[1 * kCtRows + r] = q1; L.dred[2 * kCtRows + r] = q2;
-                L.dred[3 * kCtRows + r] = q3; L.dred[4 * kCtRows + r] = q4;
-            }
-            __syncthreads();
-            if (tid < 5) {
-                double acc = 0.0;
-                for (int rr = 0; rr < kCtRows; ++rr) acc += L.dred[tid * kCtRows + rr];
-                a.losspart[(long long)tile * 5 + tid] = acc;
-            }
-            return;
-        }
-
-        // ---- backward: dv from the branch weights of max(mean loss(v), mean loss(clipped))
-        float dv = 0.0f;
-        if (R.live) {
-            const float g0 = ct_dloss(v - ret, a.delta, a.mse);
-            const float g1 = (d >= -a.clip && d <= a.clip) ? ct_dloss(clipped - ret, a.delta, a.mse) : 0.0f;   // clamp's backward: inside, bounds included
-            dv = (a.ctl[0] * g0 + a.ctl[1] * g1) * a.inv_n;
-        }
+        float dv = 0.0f, dmu[HEAD];
         float dy[16], dw[16], db[16], dx[16];
+        if constexpr (HEAD == 1) {
+            float hw[16];
+            cvec_load(N.head_w, g, hw);
+            s = 0.0f;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            dy[i] = dv * hw[i];
-            u[i] = dv * y[i];                                   // d head_w
-            dw[i] = 0.0f;
-            db[i] = 0.0f;
+            for (int i = 0; i < 16; ++i) s = __builtin_fmaf(hw[i], y[i], s);
+            const float v = crow_sum8(s) + N.head_b[0];
+            float ret = 0.0f, bv = 0.0f;
+            if (R.live) {
+                ret = a.bret[R.e * a.A + R.ag];
+                bv = a.bval[R.e * a.A + R.ag];
+            }
+            const float d = v - bv;
+            const float dcl = fminf(fmaxf(d, -a.clip), a.clip);
+            const float clipped = bv + dcl;
+
+            if (!BWD) {
+                if (g == 0) {
+                    double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0, q4 = 0.0;
+                    if (R.live) {
+                        if (a.values) a.values[row] = v;
+                        const double e0 = (double)v - (double)ret, e1 = (double)clipped - (double)ret;
+                        q0 = ct_loss64(e0, (double)a.delta, a.mse);
+                        q1 = ct_loss64(e1, (double)a.delta, a.mse);
+                        q2 = e0 * e0;
+                        q3 = (double)ret;
+                        q4 = (double)ret * (double)ret;
+                    }
+                    L.dred[0 * kCtRows + r] = q0; L.dred[1 * kCtRows + r] = q1; L.dred[2 * kCtRows + r] = q2;
+                    L.dred[3 * kCtRows + r] = q3; L.dred[4 * kCtRows + r] = q4;
+                }
+                __syncthreads();
+                if (tid < 5) {
+                    double acc = 0.0;
+                    for (int rr = 0; rr < kCtRows; ++rr) acc += L.dred[tid * kCtRows + rr];
+                    a.losspart[(long long)tile * 5 + tid] = acc;
+                }
+                return;
+            }
+
+            // ---- backward: dv from the branch weights of max(mean loss(v), mean loss(clipped))
+            if (R.live) {
+                const float g0 = ct_dloss(v - ret, a.delta, a.mse);
+                const float g1 = (d >= -a.clip && d <= a.clip) ? ct_dloss(clipped - ret, a.delta, a.mse) : 0.0f;   // clamp's backward: inside, bounds included
+                dv = (a.ctl[0] * g0 + a.ctl[1] * g1) * a.inv_n;
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                dy[i] = dv * hw[i];
+                u[i] = dv * y[i];                                   // d head_w
+                dw[i] = 0.0f;
+                db[i] = 0.0f;
+            }
+        } else {
+            // ---- the actor's head: mu = fc_mean(y), Normal(mu, exp(log_std)).log_prob(action) summed, the ratio and the clipped surrogate;
+            // d logp = -k adv r w / n with w per row (1 inside the clip, bounds included; outside 1 where the unclipped surrogate is the smaller)
+            // logp sums four terms of order 1 to a number of order 10 whose ROUNDING is the ratio's relative error (r = exp(logp - logp_old)): the terms
+            // and their sum are formed in fp64 from the fp32 mean, so the ratio carries the mean's error only
+            float am[HEAD], dls[HEAD], hr[16];
+            double lp = 0.0;
+#pragma unroll
+            for (int i = 0; i < HEAD; ++i) {
+                cvec_load(N.head_w + i * kCtE, g, hr);              // fc_mean.weight's row, read again in the backward pass (not kept)
+                s = 0.0f;
+#pragma unroll
+                for (int q = 0; q < 16; ++q) s = __builtin_fmaf(hr[q], y[q], s);
+                const float mu = crow_sum8(s) + N.head_b[i];
+                const float ls = a.log_std[i];
+                const double iv = exp(-2.0 * (double)ls);                          // 1 / sigma^2
+                const float act = R.live ? a.action[(R.e * a.A + R.ag) * HEAD + i] : mu;
+                const double dm = (double)act - (double)mu, z2 = dm * dm * iv;
+                am[i] = (float)(dm * iv);                                          // (a - mu) / sigma^2
+                dls[i] = (float)z2;                                                // (a - mu)^2 / sigma^2
+                lp += (-0.5 * z2 - (double)ls) - 0.9189385332046727;               // log sqrt(2 pi)
+            }
+            const float logp = (float)lp;
+            float ratio = -1.0f, dlogp = 0.0f;
+            double q0 = 0.0;
+            if (R.live) {
+                const float adv = a.adv[R.e * a.A + R.ag];
+                ratio = expf((float)(lp - (double)a.logp_old[R.e * a.A + R.ag]));
+                const float rc = fminf(fmaxf(ratio, a.clip_lo), a.clip_hi);
+                const float s1 = ratio * adv, s2 = rc * adv;
+                const bool inside = ratio >= a.clip_lo && ratio <= a.clip_hi;
+                const float wgt = (inside || s1 < s2) ? 1.0f : 0.0f;
+                const double d1 = (double)ratio * (double)adv, d2 = (double)rc * (double)adv;
+                q0 = d1 < d2 ? d1 : d2;
+                dlogp = -(float)HEAD * adv * ratio * wgt * a.inv_n;
+            }
+#pragma unroll
+            for (int i = 0; i < HEAD; ++i) {
+                dmu[i] = dlogp * am[i];
+                dls[i] = dlogp * (dls[i] - 1.0f);
+            }
+            if (g == 0) {
+                if (R.live && a.logp_new) a.logp_new[row] = logp;
+                L.dred[0 * kCtRows + r] = q0;
+                L.dred[1 * kCtRows + r] = (double)ratio;            // -1: the row is not part of the minibatch
+#pragma unroll
+                for (int i = 0; i < HEAD; ++i) {
+                    L.sx[i * kCtRows + r] = dmu[i];
+                    L.sx[(HEAD + i) * kCtRows + r] = dls[i];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                dy[i] = 0.0f;
+                dw[i] = 0.0f;
+                db[i] = 0.0f;
+            }
+#pragma unroll
+            for (int i = 0; i < HEAD; ++i) {
+                cvec_load(N.head_w + i * kCtE, g, hr);
+#pragma unroll
+                for (int q = 0; q < 16; ++q) dy[q] = __builtin_fmaf(dmu[i], hr[q], dy[q]);
+            }
         }
         ct_ln_bwd(dy, xh2, rstd2, N.n2_w, g, dx, dw, db);       // dx = d(x0' + ff)
         clds_store(L.b, r, g, dx);
         crow_store(stg + 10 * SA, kCtE, r, g, dx);
-        if (g == 0) L.sc[r] = dv;
-        ct_flush(L, u, part, a.P, O_HW, tid, r, g);
+        if constexpr (HEAD == 1) {
+            if (g == 0) L.sc[r] = dv;
+            ct_flush(L, u, part, a.P, O_HW, tid, r, g);
+        } else {
+#pragma unroll
+            for (int i = 0; i < HEAD; ++i) {                        // d fc_mean.weight[i] = sum_rows d mu_i y
+#pragma unroll
+                for (int q = 0; q < 16; ++q) u[q] = dmu[i] * y[q];
+                ct_flush(L, u, part, a.P, i == 0 ? O_HW : O_EWS + a.D * kCtE + (i - 1) * kCtE, tid, r, g);
+            }
+            if (tid < 4 * HEAD) {                                   // d fc_mean.bias and the rows' part of d log_std: the two halves' sums
+                const int half = tid & 1, q = tid >> 1;
+                float sb = 0.0f;
+                for (int rr = 0; rr < 16; ++rr) sb += L.sx[q * kCtRows + half * 16 + rr];
+                float *dst = part + (long long)half * a.P + (q < HEAD ? O_HB + q : O_EWS + a.D * kCtE + (HEAD - 1) * kCtE + (q - HEAD));
+                *dst = sb;
+            } else if (tid >= 32 && tid < 32 + a.A) {               // the ratios of agent tid - 32: max, sum exp(r - max), sum exp(2 (r - max))
+                const int ag = tid - 32;
+                const int first = (int)((ag + a.A - (long long)tile * kCtRows % a.A) % a.A);
+                double mx = -1.0, e1 = 0.0, e2 = 0.0;
+                for (int rr = first; rr < kCtRows; rr += a.A) mx = L.dred[kCtRows + rr] > mx ? L.dred[kCtRows + rr] : mx;
+                for (int rr = first; rr < kCtRows; rr += a.A) {
+                    const double x = L.dred[kCtRows + rr];
+                    if (x >= 0.0 || x != x) {
+                        const double ex = exp(x - mx);
+                        e1 += ex;
+                        e2 += ex * ex;
+                    }
+                }
+                double *dst = a.losspart + (long long)tile * kActLossSlots + 1 + 3 * ag;
+                dst[0] = mx; dst[1] = e1; dst[2] = e2;
+            } else if (tid == 64) {
+                double acc = 0.0;
+                for (int rr = 0; rr < kCtRows; ++rr) acc += L.dred[rr];
+                a.losspart[(long long)tile * kActLossSlots] = acc;
+            }
+        }
         ct_flush(L, dw, part, a.P, O_N2W, tid, r, g);
         ct_flush(L, db, part, a.P, O_N2B, tid, r, g);
-        if ((tid & 127) == 0) {                                 // d head_b: the two halves' sums of dv
-            const int half = tid >> 7;
-            float sb = 0.0f;
-            for (int rr = 0; rr < 16; ++rr) sb += L.sc[half * 16 + rr];
-            float *dst = part + (long long)half * a.P + O_HB;
-            *dst = sb;
+        if constexpr (HEAD == 1) {
+            if ((tid & 127) == 0) {                                 // d head_b: the two halves' sums of dv
+                const int half = tid >> 7;
+                float sb = 0.0f;
+                for (int rr = 0; rr < 16; ++rr) sb += L.sc[half * 16 + rr];
+                float *dst = part + (long long)half * a.P + O_HB;
+                *dst = sb;
+            }
         }
         ct_matvec<3>(img + 11 * kCtMat, nullptr, L.b, L.c, nullptr, nullptr, w, lane);      // dh = W_2^T dff
         __syncthreads();
@@ -664,6 +786,59 @@ __global__ __launch_bounds__(256) void hns_critic_loss_kernel(const double *part
     }
 }
 
+// the actor's scalars from the per-tile partials, in a fixed order: policy_loss = -k mean(min(surr1, surr2)); entropy of DiagGaussian (the same for
+// every row); ESS = mean over agents of exp(2 logsumexp_batch(r) - logsumexp_batch(2 r)) / batch — of the ratio itself, as the reference writes it
+__global__ __launch_bounds__(64) void hns_actor_loss_kernel(const double *part, int tiles, int A, double n, double batch, const float *log_std, float *policy_loss,
+                                                            float *entropy, float *ess) {
+    __shared__ double sm[kActLossSlots][64];
+    const int tid = threadIdx.x;
+    double acc = 0.0, mx[HNS_MAX_AGENTS], s1[HNS_MAX_AGENTS], s2[HNS_MAX_AGENTS];
+#pragma unroll
+    for (int q = 0; q < HNS_MAX_AGENTS; ++q) { mx[q] = -1.0; s1[q] = 0.0; s2[q] = 0.0; }
+    for (int i = tid; i < tiles; i += 64) {
+        const double *t = part + (long long)i * kActLossSlots;
+        acc += t[0];
+#pragma unroll
+        for (int q = 0; q < HNS_MAX_AGENTS; ++q) {
+            if (q >= A) continue;
+            const double m = t[1 + 3 * q], e1 = t[2 + 3 * q], e2 = t[3 + 3 * q];
+            if (e1 == 0.0) continue;                            // no row of this agent in the tile
+            const double M = m > mx[q] ? m : mx[q];
+            const double c0 = s1[q] == 0.0 ? 0.0 : exp(mx[q] - M), c1 = exp(m - M);
+            s1[q] = s1[q] * c0 + e1 * c1;
+            s2[q] = s2[q] * (c0 * c0) + e2 * (c1 * c1);
+            mx[q] = M;
+        }
+    }
+    sm[0][tid] = acc;
+#pragma unroll
+    for (int q = 0; q < HNS_MAX_AGENTS; ++q) { sm[1 + 3 * q][tid] = mx[q]; sm[2 + 3 * q][tid] = s1[q]; sm[3 + 3 * q][tid] = s2[q]; }
+    __syncthreads();
+    if (tid == 0) {
+        double tot = 0.0;
+        for (int i = 0; i < 64; ++i) tot += sm[0][i];
+        policy_loss[0] = (float)(-(double)kActDim * tot / n);
+        double ent = 0.0;
+        for (int i = 0; i < kActDim; ++i) ent += 0.5 + 0.9189385332046727 + (double)log_std[i];
+        entropy[0] = (float)ent;
+        double es = 0.0;
+        for (int q = 0; q < A; ++q) {
+            double M = -1.0, a1 = 0.0, a2 = 0.0;
+            for (int i = 0; i < 64; ++i) {
+                const double m = sm[1 + 3 * q][i], e1 = sm[2 + 3 * q][i], e2 = sm[3 + 3 * q][i];
+                if (e1 == 0.0) continue;
+                const double Mn = m > M ? m : M;
+                const double c0 = a1 == 0.0 ? 0.0 : exp(M - Mn), c1 = exp(m - Mn);
+                a1 = a1 * c0 + e1 * c1;
+                a2 = a2 * (c0 * c0) + e2 * (c1 * c1);
+                M = Mn;
+            }
+            es += a1 * a1 / a2;                                 // exp(2 (M + log a1) - (2 M + log a2))
+        }
+        ess[0] = (float)(es / (double)A / batch);
+    }
+}
+
 // dW partials: per (row range, matrix) the 128 x 128 product dy^T x over the range's rows, and the column sums of dy
 __global__ __launch_bounds__(256, 2) void hns_critic_wgrad_kernel(const float *stage, long long stage_rows, int tiles, int tps, float *part) {
     __shared__ __align__(16) float sdy[kCtRows * kCtGemmLd];
@@ -742,7 +917,7 @@ HNS_DEV float *ct_dst_gemm(const CtGrad &g, int e, bool &zero) {
     }
 }
 
-HNS_DEV float *ct_dst_tile(const CtGrad &g, int D, int e) {
+HNS_DEV float *ct_dst_tile(const CtGrad &g, int D, int heads, int e) {
     if (e < O_EWO) {
         const int f = e & 127;
         switch (e >> 7) {
@@ -760,13 +935,16 @@ HNS_DEV float *ct_dst_tile(const CtGrad &g, int D, int e) {
     }
     if (e < O_EWC) return g.ew[1] ? g.ew[1] + ((e - O_EWO) & 127) * 3 + ((e - O_EWO) >> 7) : nullptr;
     if (e < O_HB) return g.ew[2] + ((e - O_EWC) & 127) * 5 + ((e - O_EWC) >> 7);
-    if (e < O_EWS) return e == O_HB ? g.head_b : nullptr;
-    return g.ew[0] + ((e - O_EWS) & 127) * D + ((e - O_EWS) >> 7);
+    if (e < O_EWS) return e - O_HB < heads ? g.head_b + (e - O_HB) : nullptr;
+    if (e < O_EWS + D * kCtE) return g.ew[0] + ((e - O_EWS) & 127) * D + ((e - O_EWS) >> 7);
+    const int x = e - (O_EWS + D * kCtE);                       // the actor's head: rows 1 .. heads - 1 of head_w, then log_std
+    return x < (heads - 1) * kCtE ? g.head_w + kCtE + x : g.log_std + (x - (heads - 1) * kCtE);
 }
 
-// 32 gradient values per block, 8 threads each: slice s sums its range of the partials in fp64, the slices add up in order
+// 32 gradient values per block, 8 threads each: slice s sums its range of the partials in fp64, the slices add up in order.  `ls_add` joins
+// every log_std value's sum once (the actor's -entropy_coef: the entropy term's gradient is the same constant whatever the rows)
 __global__ __launch_bounds__(256) void hns_critic_reduce_kernel(const float *gpart, int splits, const float *tpart, int nt, int P, int gblocks, const CtGrad g,
-                                                                int D, double *blockpart) {
+                                                                int D, double *blockpart, int heads, double ls_add) {
     __shared__ double sm[8][32];
     __shared__ double sq[32];
     const int tid = threadIdx.x, el = tid & 31, sl = tid >> 5;
@@ -777,7 +955,7 @@ __global__ __launch_bounds__(256) void hns_critic_reduce_kernel(const float *gpa
     const float *src = gemm ? gpart : tpart;
     float *dst = nullptr;
     bool zero = false;
-    if (e < stride) dst = gemm ? ct_dst_gemm(g, e, zero) : ct_dst_tile(g, D, e);
+    if (e < stride) dst = gemm ? ct_dst_gemm(g, e, zero) : ct_dst_tile(g, D, heads, e);
     double acc = 0.0;
     if (dst && !zero) {
         const int lo = (int)((long long)n * sl / 8), hi = (int)((long long)n * (sl + 1) / 8);
@@ -789,6 +967,7 @@ __global__ __launch_bounds__(256) void hns_critic_reduce_kernel(const float *gpa
         double tot = 0.0;
 #pragma unroll
         for (int q = 0; q < 8; ++q) tot += sm[q][el];
+        if (heads > 1 && !gemm && e >= P - heads && e < P) tot += ls_add;
         const float s = (float)tot;
         if (dst) dst[0] = s;
         sq[el] = dst ? (double)s * (double)s : 0.0;
@@ -876,18 +1055,18 @@ struct CtPlan {
     size_t o_ctl, o_loss, o_block, o_img, o_tile, o_gemm, o_stage, total;
 };
 
-bool ct_plan(int64_t rows, int32_t D, int32_t A, int32_t K, CtPlan &p) {
+bool ct_plan(int64_t rows, int32_t D, int32_t A, int32_t K, CtPlan &p, int heads = 1) {
     if (rows < 1 || rows > ((int64_t)1 << 31) - 64 || D < 1 || D > hns::kCtMaxSelf || A < 1 || A > HNS_MAX_AGENTS || K < 1 || K > HNS_MAX_CYLINDERS) return false;
     p.tiles = (rows + hns::kCtRows - 1) / hns::kCtRows;
     p.tps = (p.tiles + hns::kCtMaxSplits - 1) / hns::kCtMaxSplits;
     p.splits = (p.tiles + p.tps - 1) / p.tps;
     p.stage_rows = p.tiles * hns::kCtRows;
-    p.P = hns::ct_partial_floats(D);
+    p.P = hns::ct_partial_floats(D, heads);
     p.gblocks = (6 * hns::kCtGemmOut + 31) / 32;
     p.tblocks = (p.P + 31) / 32;
     size_t o = 0;
     p.o_ctl = o; o += ct_up(64 * sizeof(float));
-    p.o_loss = o; o += ct_up((size_t)p.tiles * 5 * sizeof(double));
+    p.o_loss = o; o += ct_up((size_t)p.tiles * (heads > 1 ? hns::kActLossSlots : 5) * sizeof(double));
     p.o_block = o; o += ct_up((size_t)hns::kCtMaxBlocks * sizeof(double));
     p.o_img = o; o += ct_up((size_t)hns::ct_img_floats(D) * sizeof(float));
     p.o_tile = o; o += ct_up((size_t)p.tiles * 2 * p.P * sizeof(float));
@@ -1005,7 +1184,116 @@ int hns_critic_train_grad(const hns_policy_net *critic, const hns_critic_batch *
     double *blockpart = reinterpret_cast<double *>(ws + p.o_block);
     const int nb = p.gblocks + p.tblocks;
     hipLaunchKernelGGL(hns::hns_critic_reduce_kernel, dim3(nb), dim3(256), 0, st, gpart, (int)p.splits, a.tilepart, (int)(2 * p.tiles), p.P, p.gblocks, G,
-                       (int)self_dim, blockpart);
+                       (int)self_dim, blockpart, 1, 0.0);
+    HNS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hns::hns_critic_norm_kernel, dim3(1), dim3(256), 0, st, blockpart, nb, grad_norm);
+    HNS_CHECK_HIP(hipGetLastError());
+    return HNS_OK;
+}
+
+size_t hns_actor_train_workspace_bytes(int64_t rows, int32_t self_dim, int32_t num_agents, int32_t num_cylinders) {
+    CtPlan p;
+    return ct_plan(rows, self_dim, num_agents, num_cylinders, p, hns::kActDim) ? p.total : 0;
+}
+
+int hns_actor_train_grad(const hns_policy_net *actor, const hns_actor_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                         double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
+                         float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "hns_actor_train_grad";
+    if (!actor || !batch || !grads || !policy_loss || !entropy || !ess || !grad_norm || !workspace) return ct_fail(fn, "null pointer");
+    if (self_dim < 1 || self_dim > hns::kCtMaxSelf) return ct_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kCtMaxSelf) + "]");
+    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return ct_fail(fn, "num_agents must be in [1, 7]");
+    if (num_cylinders < 1 || num_cylinders > HNS_MAX_CYLINDERS) return ct_fail(fn, "num_cylinders must be in [1, 16]");
+    if (batch->batch < 1) return ct_fail(fn, "batch must be >= 1 (the mean over an empty minibatch is NaN)");
+    if (batch->num_envs < 1 || batch->num_steps < 1 || batch->num_envs > ((int64_t)1 << 40) / batch->num_steps) return ct_fail(fn, "num_envs, num_steps must be >= 1");
+    const int64_t steps = batch->num_envs * batch->num_steps;
+    if (batch->batch > ((int64_t)1 << 31) / HNS_MAX_AGENTS) return ct_fail(fn, "batch too large");
+    if (!batch->index && batch->batch > steps) return ct_fail(fn, "batch exceeds the env-steps of the rollout (no index)");
+    if (!(clip_param >= 0.0) || !std::isfinite(clip_param) || !std::isfinite(entropy_coef)) return ct_fail(fn, "clip_param >= 0 and a finite entropy_coef");
+    const bool others = num_agents > 1;
+    const float *pr[] = {actor->embed_self_w, actor->embed_self_b, actor->embed_cyl_w, actor->embed_cyl_b, actor->ln_w, actor->ln_b, actor->in_proj_w,
+                         actor->in_proj_b, actor->out_proj_w, actor->out_proj_b, actor->linear1_w, actor->linear1_b, actor->linear2_w, actor->linear2_b,
+                         actor->norm1_w, actor->norm1_b, actor->norm2_w, actor->norm2_b, actor->head_w, actor->head_b, actor->log_std};
+    float *gr[] = {grads->embed_self_w, grads->embed_self_b, grads->embed_cyl_w, grads->embed_cyl_b, grads->ln_w, grads->ln_b, grads->in_proj_w,
+                   grads->in_proj_b, grads->out_proj_w, grads->out_proj_b, grads->linear1_w, grads->linear1_b, grads->linear2_w, grads->linear2_b,
+                   grads->norm1_w, grads->norm1_b, grads->norm2_w, grads->norm2_b, grads->head_w, grads->head_b, grads->log_std};
+    for (int k = 0; k < 21; ++k)
+        if (!pr[k] || !gr[k] || !ct_aligned(pr[k], 16) || !ct_aligned(gr[k], 4)) return ct_fail(fn, "every parameter must be a non-NULL 16-byte aligned fp32 array, every gradient a non-NULL fp32 array");
+    if (others && (!actor->embed_others_w || !actor->embed_others_b || !grads->embed_others_w || !grads->embed_others_b || !ct_aligned(actor->embed_others_b, 16)))
+        return ct_fail(fn, "state_others embedding (parameter or gradient) missing or misaligned (num_agents > 1)");
+    if (!batch->obs_self || !batch->obs_cylinders || (others && !batch->obs_others)) return ct_fail(fn, "observation pointer missing");
+    if (!ct_aligned(batch->obs_self, 4) || !ct_aligned(batch->obs_cylinders, 4) || (batch->obs_others && !ct_aligned(batch->obs_others, 4)))
+        return ct_fail(fn, "misaligned observation");
+    for (int k = 0; k < 3; ++k)
+        if (batch->self_stride[k] < 0) return ct_fail(fn, "negative stride");
+    for (int k = 0; k < 4; ++k)
+        if (batch->others_stride[k] < 0 || batch->cyl_stride[k] < 0) return ct_fail(fn, "negative stride");
+    if (!batch->action || !batch->log_probs_old || !batch->advantages || !ct_aligned(batch->action, 4) || !ct_aligned(batch->log_probs_old, 4) ||
+        !ct_aligned(batch->advantages, 4))
+        return ct_fail(fn, "action / log_probs_old / advantages missing or misaligned");
+    if (batch->index && !ct_aligned(batch->index, 8)) return ct_fail(fn, "misaligned index");
+    if (!ct_aligned(policy_loss, 4) || !ct_aligned(entropy, 4) || !ct_aligned(ess, 4) || !ct_aligned(grad_norm, 4) || (log_probs && !ct_aligned(log_probs, 4)) ||
+        !ct_aligned(workspace, 256))
+        return ct_fail(fn, "misaligned output (scalars 4 bytes, workspace 256)");
+    CtPlan p;
+    const int64_t rows = batch->batch * num_agents;
+    if (!ct_plan(rows, self_dim, num_agents, num_cylinders, p, hns::kActDim)) return ct_fail(fn, "invalid shape");
+    if (workspace_bytes < p.total) return ct_fail(fn, "workspace too small (hns_actor_train_workspace_bytes)");
+
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    hns::CtArgs a{};
+    hns::CtNet &n = a.net;
+    n.ew[0] = actor->embed_self_w; n.eb[0] = actor->embed_self_b;
+    n.ew[1] = others ? actor->embed_others_w : nullptr; n.eb[1] = others ? actor->embed_others_b : nullptr;
+    n.ew[2] = actor->embed_cyl_w; n.eb[2] = actor->embed_cyl_b;
+    n.ln_w = actor->ln_w; n.ln_b = actor->ln_b; n.in_w = actor->in_proj_w; n.in_b = actor->in_proj_b; n.out_w = actor->out_proj_w; n.out_b = actor->out_proj_b;
+    n.l1_w = actor->linear1_w; n.l1_b = actor->linear1_b; n.l2_w = actor->linear2_w; n.l2_b = actor->linear2_b;
+    n.n1_w = actor->norm1_w; n.n1_b = actor->norm1_b; n.n2_w = actor->norm2_w; n.n2_b = actor->norm2_b; n.head_w = actor->head_w; n.head_b = actor->head_b;
+    hns::CtGrad G{};
+    G.ew[0] = grads->embed_self_w; G.eb[0] = grads->embed_self_b;
+    G.ew[1] = others ? grads->embed_others_w : nullptr; G.eb[1] = others ? grads->embed_others_b : nullptr;
+    G.ew[2] = grads->embed_cyl_w; G.eb[2] = grads->embed_cyl_b;
+    G.ln_w = grads->ln_w; G.ln_b = grads->ln_b; G.in_w = grads->in_proj_w; G.in_b = grads->in_proj_b; G.out_w = grads->out_proj_w; G.out_b = grads->out_proj_b;
+    G.l1_w = grads->linear1_w; G.l1_b = grads->linear1_b; G.l2_w = grads->linear2_w; G.l2_b = grads->linear2_b;
+    G.n1_w = grads->norm1_w; G.n1_b = grads->norm1_b; G.n2_w = grads->norm2_w; G.n2_b = grads->norm2_b; G.head_w = grads->head_w; G.head_b = grads->head_b;
+    G.log_std = grads->log_std;
+
+    float *img = reinterpret_cast<float *>(ws + p.o_img);
+    a.img = img;
+    a.xs = batch->obs_self; a.xo = others ? batch->obs_others : nullptr; a.xc = batch->obs_cylinders;
+    for (int k = 0; k < 3; ++k) a.ss[k] = batch->self_stride[k];
+    for (int k = 0; k < 4; ++k) { a.so[k] = batch->others_stride[k]; a.sc[k] = batch->cyl_stride[k]; }
+    a.T = batch->num_steps; a.steps = steps;
+    a.index = reinterpret_cast<const long long *>(batch->index);
+    a.rows = rows; a.A = num_agents; a.K = num_cylinders; a.D = self_dim; a.tiles = (int)p.tiles;
+    a.logp_old = batch->log_probs_old; a.adv = batch->advantages; a.action = batch->action; a.log_std = actor->log_std;
+    a.clip_lo = (float)(1.0 - clip_param); a.clip_hi = (float)(1.0 + clip_param);
+    a.inv_n = (float)(1.0 / (double)rows);
+    a.logp_new = log_probs;
+    a.losspart = reinterpret_cast<double *>(ws + p.o_loss);
+    a.tilepart = reinterpret_cast<float *>(ws + p.o_tile);
+    a.P = p.P;
+    a.stage = reinterpret_cast<float *>(ws + p.o_stage);
+    a.stage_rows = p.stage_rows;
+
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<true, hns::kActDim>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::CtLds));
+    HNS_CHECK_HIP(attr);
+    hipLaunchKernelGGL(hns::hns_critic_pack_kernel, dim3(256), dim3(256), 0, st, n, (int)self_dim, img);
+    HNS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL((hns::hns_critic_kernel<true, hns::kActDim>), dim3((unsigned)p.tiles), dim3(hns::kCtThreads), sizeof(hns::CtLds), st, a);
+    HNS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hns::hns_actor_loss_kernel, dim3(1), dim3(64), 0, st, a.losspart, (int)p.tiles, (int)num_agents, (double)rows, (double)batch->batch,
+                       actor->log_std, policy_loss, entropy, ess);
+    HNS_CHECK_HIP(hipGetLastError());
+    float *gpart = reinterpret_cast<float *>(ws + p.o_gemm);
+    hipLaunchKernelGGL(hns::hns_critic_wgrad_kernel, dim3((unsigned)p.splits, 6), dim3(256), 0, st, a.stage, a.stage_rows, (int)p.tiles, (int)p.tps, gpart);
+    HNS_CHECK_HIP(hipGetLastError());
+    double *blockpart = reinterpret_cast<double *>(ws + p.o_block);
+    const int nb = p.gblocks + p.tblocks;
+    hipLaunchKernelGGL(hns::hns_critic_reduce_kernel, dim3(nb), dim3(256), 0, st, gpart, (int)p.splits, a.tilepart, (int)(2 * p.tiles), p.P, p.gblocks, G,
+                       (int)self_dim, blockpart, hns::kActDim, -entropy_coef);
     HNS_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(hns::hns_critic_norm_kernel, dim3(1), dim3(256), 0, st, blockpart, nb, grad_norm);
     HNS_CHECK_HIP(hipGetLastError());
