@@ -624,8 +624,23 @@ int hns_actor_train_grad(const hns_policy_net *actor, const hns_actor_batch *bat
                          double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
                          float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * The info row of MAPPOPolicy.train_op (learning/mappo.py:463-472): the means over the minibatches of the scalars the updates wrote
+ * into `table` ([minibatches, columns] fp32, contiguous; hns_amd.learner hands the two *_train_grad calls pointers into its rows), then
+ * action_norm = mean over the rows of sqrt(sum_i a_i^2), row r's element i at action[r action_stride[0] + i action_stride[1]] (strides in
+ * elements, >= 0; float4 loads where act_dim is 4, the element stride 1 and every row 16-byte aligned).  out [columns + 1]: column c's fp64 sum in
+ * row order divided by `minibatches` and rounded once to fp32, then action_norm: per-workgroup fp64 partials in `workspace`, summed in index
+ * order by one workgroup, divided by `rows`, rounded once.  Two launches in one stream; no allocation, no host synchronisation, no float
+ * atomics, capturable; the same inputs give the same bits.  Refused before any launch: a NULL or misaligned pointer (fp32 arrays 4-byte,
+ * workspace 8-byte aligned), rows < 1, act_dim outside [1, 8], minibatches < 1, columns outside [1, 16], a negative stride, a workspace
+ * shorter than the size function's bytes (rows < 1: 0).
+ */
+size_t hns_learner_info_workspace_bytes(long long rows);
+int hns_learner_info(const float *action, const int64_t action_stride[2], long long rows, int act_dim, const float *table, int minibatches,
+                     int columns, float *out, void *workspace, size_t workspace_bytes, void *stream);
+
 int hns_abi_version(void);
-size_t hns_cfg_size(void);   /* sizeof(hns_cfg) the library was built with (binding self-check) */
+size_t hns_cfg_size(void);  /* sizeof(hns_cfg) the library was built with (binding self-check) */
 const char *hns_last_error(void);
 
 #ifdef __cplusplus

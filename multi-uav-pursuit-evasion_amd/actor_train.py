@@ -23,7 +23,7 @@ import torch.nn.functional as F
 
 from . import abi
 from . import policy as P
-from .critic_train import ClippedAdam, _as_rollout, _check, _encoder, _getter
+from .critic_train import ClippedAdam, _as_rollout, _check, _check_out, _check_workspace, _encoder, _getter
 
 ActorLoss = collections.namedtuple("ActorLoss", ["policy_loss", "entropy", "ess", "grad_norm", "log_probs"])
 
@@ -113,14 +113,17 @@ def _torch_loss_and_grad(p, xs, xo, xc, action, log_probs_old, advantages, index
 
 
 def policy_loss_and_grad(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index=None, clip_param=0.1,
-                         entropy_coef=0.001, check_index=True):
+                         entropy_coef=0.001, check_index=True, workspace=None, out=None):
     """The clipped PPO surrogate of the actor on a minibatch (plus entropy_coef times the entropy loss) and every parameter's .grad (as
     zero_grad() + backward() leave them, before clip_grad_norm_).  Returns ActorLoss(policy_loss, entropy, ess, grad_norm: 0-dim tensors;
     log_probs [B, A, 1]: the new log-probabilities of the stored actions).
 
     obs_*: the rollout's [N, T, A, ...] observations or a flat [R, A, ...] batch, read in place (critic_train.value_loss_and_grad's
     layouts); action [N, T, A, 4], log_probs_old, advantages [N, T, A, 1] (any shape of that many values); index: int64 [B] env-steps of
-    the flattened [N T] (None: all).  `check_index` range-checks the index (one host synchronisation; skipped inside a graph capture)."""
+    the flattened [N T] (None: all).  `check_index` range-checks the index (one host synchronisation; skipped inside a graph capture).
+    `workspace`: a uint8 device tensor of at least hns_actor_train_workspace_bytes bytes, 256-byte aligned, instead of one allocated per call;
+    `out`: four fp32 device values that receive policy_loss, entropy, ess and grad_norm (the returned scalars are views of it) instead of a
+    tensor of the call's own.  Both are ignored on the CPU."""
     if not clip_param >= 0:
         raise ValueError("clip_param must be >= 0")
     p = actor_parameters(actor)
@@ -144,6 +147,8 @@ def policy_loss_and_grad(actor, obs_self, obs_others, obs_cylinders, action, log
     nbytes = lib.hns_actor_train_workspace_bytes(B * A, D_, A, K)
     if nbytes == 0:
         raise ValueError(f"shape outside the kernel's limits: {B * A} rows, self_dim {D_}, {A} agents, {K} cylinders")
+    ws = _check_workspace(workspace, nbytes, dev) if workspace is not None else None
+    scal = _check_out(out, 4, dev) if out is not None else None
     for f, t in p.items():
         if t.grad is None:
             t.grad = torch.empty_like(t)
@@ -158,8 +163,10 @@ def policy_loss_and_grad(actor, obs_self, obs_others, obs_cylinders, action, log
     b.num_envs, b.num_steps, b.batch = N, T, B
     b.index = index.data_ptr() if index is not None else None
     b.action, b.log_probs_old, b.advantages = act.data_ptr(), lpo.data_ptr(), adv.data_ptr()
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    scal = torch.empty(4, dtype=torch.float32, device=dev)
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if scal is None:
+        scal = torch.empty(4, dtype=torch.float32, device=dev)
     log_probs = torch.empty(B, A, 1, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -187,11 +194,12 @@ def make_optimizer(actor, cfg=None):
                        weight_decay=float(sget("weight_decay", 0.0) or 0.0))
 
 
-def update_actor(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, optimizer, index=None, cfg=None, check_index=False):
+def update_actor(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, optimizer, index=None, cfg=None, check_index=False,
+                 workspace=None, out=None):
     """MAPPOPolicy.update_actor on one minibatch: loss, backward, clip_grad_norm_, Adam.  cfg: the algo cfg (clip_param, entropy_coef; the
     reference's defaults when None).  Returns {"policy_loss", "actor_grad_norm", "entropy", "ESS"} as 0-dim tensors on the parameters' device
     — the caller decides when to .item().  `optimizer`: a ClippedAdam (make_optimizer).  The index is NOT range-checked by default, as in
-    critic_train.update_critic."""
+    critic_train.update_critic.  `workspace`, `out`: policy_loss_and_grad's."""
     if not isinstance(optimizer, ClippedAdam):
         raise TypeError(f"update_actor takes a ClippedAdam (actor_train.make_optimizer), not {type(optimizer).__name__}: the clip and the "
                         "step are one launch that needs the gradient norm")
@@ -199,8 +207,9 @@ def update_actor(actor, obs_self, obs_others, obs_cylinders, action, log_probs_o
     for group in optimizer.param_groups:
         if group.get("weight_decay", 0) != 0:
             raise NotImplementedError("weight_decay != 0 is not supported")
-    out = policy_loss_and_grad(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index,
-                               clip_param=float(get("clip_param", 0.1)), entropy_coef=float(get("entropy_coef", 0.001)), check_index=check_index)
-    optimizer.step(grad_norm=out.grad_norm)
-    norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else out.grad_norm
-    return {"policy_loss": out.policy_loss, "actor_grad_norm": norm, "entropy": out.entropy, "ESS": out.ess}
+    res = policy_loss_and_grad(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index,
+                               clip_param=float(get("clip_param", 0.1)), entropy_coef=float(get("entropy_coef", 0.001)), check_index=check_index,
+                               workspace=workspace, out=out)
+    optimizer.step(grad_norm=res.grad_norm)
+    norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else res.grad_norm
+    return {"policy_loss": res.policy_loss, "actor_grad_norm": norm, "entropy": res.entropy, "ESS": res.ess}

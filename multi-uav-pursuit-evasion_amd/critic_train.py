@@ -41,6 +41,24 @@ def _getter(cfg):
     return cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
 
 
+def _check_workspace(workspace, nbytes, dev):
+    """The caller's workspace (a uint8 device tensor of at least `nbytes` bytes, 256-byte aligned) as the kernels take it."""
+    if not torch.is_tensor(workspace) or workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError(f"workspace must be a contiguous uint8 tensor on {dev}")
+    if workspace.numel() < nbytes:
+        raise ValueError(f"workspace holds {workspace.numel()} bytes, the minibatch needs {nbytes}")
+    if workspace.data_ptr() % 256:
+        raise ValueError("workspace must be 256-byte aligned")
+    return workspace
+
+
+def _check_out(out, n, dev):
+    """The caller's `n` fp32 result slots (a view into a table row) as the kernels write them."""
+    if not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != dev or out.dim() != 1 or out.numel() != n or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 tensor of {n} values on {dev}")
+    return out
+
+
 def critic_parameters(critic):
     """The critic's tensors by hns_policy_net field, in the order the module registers them (clip_grad_norm_'s order)."""
     return P.parse_parameters(critic, P.CRITIC_NAMES, "critic")
@@ -153,13 +171,16 @@ def _torch_loss_and_grad(p, xs, xo, xc, b_values, b_returns, index, clip_param, 
 
 
 def value_loss_and_grad(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, index=None, clip_param=0.1, loss="huber",
-                        huber_delta=10.0, check_index=True):
+                        huber_delta=10.0, check_index=True, workspace=None, out=None):
     """The clipped value loss of the critic on a minibatch and every parameter's .grad (as zero_grad() + backward() leave them, before
     clip_grad_norm_).  Returns CriticLoss(value_loss, explained_var, grad_norm: 0-dim tensors; values [B, A, 1]).
 
     obs_*: the rollout's [N, T, A, ...] observations (state_self [N, T, A, D] or [N, T, A, 1, D]; state_others None with one agent) or a
     flat [R, A, ...] batch, read in place; b_values, b_returns: [N, T, A, 1] (any shape of N T A values); index: int64 [B] env-steps of the
-    flattened [N T] (None: all).  `check_index` range-checks the index (one host synchronisation; skipped inside a graph capture)."""
+    flattened [N T] (None: all).  `check_index` range-checks the index (one host synchronisation; skipped inside a graph capture).
+    `workspace`: a uint8 device tensor of at least hns_critic_train_workspace_bytes bytes, 256-byte aligned, instead of one allocated per call;
+    `out`: three fp32 device values that receive value_loss, explained_var and grad_norm (the returned scalars are views of it) instead of a
+    tensor of the call's own.  Both are ignored on the CPU."""
     if loss not in LOSSES:
         raise ValueError(f"loss must be 'huber' or 'mse', not {loss!r}")
     if not clip_param >= 0 or (loss == "huber" and not huber_delta > 0):
@@ -185,6 +206,8 @@ def value_loss_and_grad(critic, obs_self, obs_others, obs_cylinders, b_values, b
     nbytes = lib.hns_critic_train_workspace_bytes(B * A, D, A, K)
     if nbytes == 0:
         raise ValueError(f"shape outside the kernel's limits: {B * A} rows, self_dim {D}, {A} agents, {K} cylinders")
+    ws = _check_workspace(workspace, nbytes, dev) if workspace is not None else None
+    scal = _check_out(out, 3, dev) if out is not None else None
     for f, t in p.items():
         if t.grad is None:
             t.grad = torch.empty_like(t)
@@ -199,8 +222,10 @@ def value_loss_and_grad(critic, obs_self, obs_others, obs_cylinders, b_values, b
     b.num_envs, b.num_steps, b.batch = N, T, B
     b.index = index.data_ptr() if index is not None else None
     b.b_values, b.b_returns = bv.data_ptr(), ret.data_ptr()
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    scal = torch.empty(3, dtype=torch.float32, device=dev)
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if scal is None:
+        scal = torch.empty(3, dtype=torch.float32, device=dev)
     values = torch.empty(B, A, 1, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -287,12 +312,14 @@ def make_optimizer(critic, cfg=None):
                        weight_decay=float(sget("weight_decay", 0.0) or 0.0))
 
 
-def update_critic(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, optimizer, index=None, cfg=None, check_index=False):
+def update_critic(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, optimizer, index=None, cfg=None, check_index=False,
+                  workspace=None, out=None):
     """MAPPOPolicy.update_critic on one minibatch: loss, backward, clip_grad_norm_, Adam.  cfg: the algo cfg (clip_param, critic.use_huber_loss,
     critic.huber_delta; the reference's defaults when None).  Returns {"value_loss", "critic_grad_norm", "explained_var"} as 0-dim tensors on the
     parameters' device — the caller decides when to .item().  `optimizer`: a ClippedAdam (make_optimizer).  The index is NOT range-checked
     by default (make_dataset_naive's permutations are in range by construction; the check is a host synchronisation per minibatch, and the
-    kernel skips an env-step outside the rollout): pass check_index=True for an index of another origin."""
+    kernel skips an env-step outside the rollout): pass check_index=True for an index of another origin.  `workspace`, `out`:
+    value_loss_and_grad's."""
     if not isinstance(optimizer, ClippedAdam):
         raise TypeError(f"update_critic takes a ClippedAdam (critic_train.make_optimizer), not {type(optimizer).__name__}: the clip and the "
                         "step are one launch that needs the gradient norm")
@@ -305,9 +332,9 @@ def update_critic(critic, obs_self, obs_others, obs_cylinders, b_values, b_retur
     for group in optimizer.param_groups:
         if group.get("weight_decay", 0) != 0:
             raise NotImplementedError("weight_decay != 0 is not supported")
-    out = value_loss_and_grad(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, index, clip_param=float(get("clip_param", 0.1)),
+    res = value_loss_and_grad(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, index, clip_param=float(get("clip_param", 0.1)),
                               loss="huber" if sget("use_huber_loss", True) else "mse", huber_delta=float(sget("huber_delta", 10.0)),
-                              check_index=check_index)
-    optimizer.step(grad_norm=out.grad_norm)
-    norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else out.grad_norm
-    return {"value_loss": out.value_loss, "critic_grad_norm": norm, "explained_var": out.explained_var}
+                              check_index=check_index, workspace=workspace, out=out)
+    optimizer.step(grad_norm=res.grad_norm)
+    norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else res.grad_norm
+    return {"value_loss": res.value_loss, "critic_grad_norm": norm, "explained_var": res.explained_var}

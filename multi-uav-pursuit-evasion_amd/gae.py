@@ -146,13 +146,15 @@ def rollout_normalise(advantages, returns, adv_mean=None, adv_den=None, ret_mean
 
 
 def rollout_targets(reward, done, value, next_value, gamma, lmbda, value_normalizer=None, success=None, normalize_advantages=True, eps=1e-8,
-                    time_major=False):
+                    time_major=False, return_moments=False):
     """MAPPOPolicy.train_op's targets (learning/mappo.py:370-402) for this rank's share of a data-parallel rollout.
 
     reward [N, T, *k, r] (summed over its last dim when r != 1, mappo.py:370-371), value [N, T, *k, 1] (critic output, normalised when a
     `value_normalizer` — the reference's ValueNorm1 — is given), done [N, T, ...] of the same rank (1 or k trailing), next_value [N, *k, 1];
     [T, N, ...] with `time_major`.  Returns (advantages, returns, success_rate): the normalised targets in reward's layout and the global success
-    rate as a 0-dim device tensor (None without `success`).  `value_normalizer` is updated in place with the global batch moments of the returns."""
+    rate as a 0-dim device tensor (None without `success`).  `value_normalizer` is updated in place with the global batch moments of the returns.
+    With `return_moments` a fourth value follows: (advantages_mean, advantages_std) of the advantages BEFORE the normalisation (mappo.py:391-392,
+    train_info's entries; torch.std: unbiased) as 0-dim fp32 tensors, from the same gathered table."""
     if reward.shape[-1] != 1:
         reward = reward.sum(-1, keepdim=True)
     scale = shift = None
@@ -169,10 +171,12 @@ def rollout_targets(reward, done, value, next_value, gamma, lmbda, value_normali
     table = sharding.allgather_moments(row)
     if value_normalizer is not None:
         sharding.valuenorm1_update(value_normalizer, table)
-    adv_mean = adv_den = ret_mean = ret_scale = None
-    if normalize_advantages:
+    adv_mean = adv_den = ret_mean = ret_scale = moments = None
+    if normalize_advantages or return_moments:
         mean, std = sharding.global_mean_std(table)
-        adv_mean, adv_den = mean.to(adv.dtype), std.to(adv.dtype) + eps
+        moments = (mean.to(adv.dtype), std.to(adv.dtype))
+    if normalize_advantages:
+        adv_mean, adv_den = moments[0], moments[1] + eps
     if value_normalizer is not None:
         mean, var = value_normalizer.running_mean_var()
         ret_mean, ret_scale = mean, torch.sqrt(var)
@@ -182,4 +186,6 @@ def rollout_targets(reward, done, value, next_value, gamma, lmbda, value_normali
     if success is not None:
         tot = table.sum(0)
         rate = tot[3] / tot[4]
+    if return_moments:
+        return adv, ret, rate, moments
     return adv, ret, rate

@@ -1,0 +1,269 @@
+"""The MAPPO learner on the device: MAPPOPolicy.train_op (learning/mappo.py:363-475) over the update paths of this package.
+
+`DeviceLearner(actor, critic, cfg, tp_net, value_normalizer)` holds what the reference's policy object holds for training — the two Adam
+optimisers as `ClippedAdam`s, the predictor's `TPAdam(lr=1e-4)` (mappo.py:94), the ValueNorm1 instance, a `DevicePolicy` for the bootstrap
+value — and `train_op(tensordict)` drives the five blocks in the reference's order:
+
+    next_value  DevicePolicy.forward(value_only=True) on the last step's next observation          mappo.py:365-367, §7.3
+    targets     gae.rollout_targets: denormalise, GAE, the moments, ValueNorm1, both normalisations  mappo.py:369-402, §7.1
+    predictor   tp_train.update_tp over TP_epochs                                                    mappo.py:407-443, §7.2
+    PPO loop    per epoch ONE randperm (tp_train.minibatches: make_dataset_naive's), per minibatch   mappo.py:446-461
+                actor_train.update_actor, then critic_train.update_critic, both through index=       §7.5, §7.4
+    info row    hns_learner_info: the column means of the per-minibatch table and action_norm         mappo.py:463-472
+
+One RNG stream serves the call (the predictor's epochs draw first): `generator` goes to every randperm.  On the device the loop makes no host
+synchronisation (the updates write their scalars into the rows of one table; no `.item()`, no index check); update_tp's selected-count read
+stays, and the finished info row crosses to the host in one copy.  The two update workspaces and the info workspace are allocated once per
+shape and reused by all ppo_epochs x num_minibatches calls.  CPU tensors run the same driver over the modules' CPU paths (CPU tests, gloo
+runs — not the hot path).  DESIGN.md §7.6."""
+import ctypes as C
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import abi, actor_train, critic_train, gae, tp_train
+from . import policy as P
+from .critic_train import _getter
+
+ACTOR_COLUMNS = ("policy_loss", "entropy", "ESS", "actor_grad_norm")           # hns_actor_train_grad's four scalars, in its order
+CRITIC_COLUMNS = ("value_loss", "explained_var", "critic_grad_norm")           # hns_critic_train_grad's three
+COLUMNS = ACTOR_COLUMNS + CRITIC_COLUMNS
+# train_info's keys in the reference's order of insertion (mappo.py:319-324, :348-352, :463-472)
+INFO_KEYS = ("policy_loss", "actor_grad_norm", "entropy", "ESS", "value_loss", "critic_grad_norm", "explained_var", "TP_loss", "advantages_mean",
+             "advantages_std", "action_norm", "value_running_mean")
+
+
+class ValueNorm1(nn.Module):
+    """The state of the reference's ValueNorm1 (learning/utils/valuenorm.py:41-103) under its buffer names, for a learner built without the
+    reference's package: gae.rollout_targets updates it and reads `running_mean_var()`; its state_dict is the reference's."""
+
+    def __init__(self, input_shape=(1,), beta=0.995, epsilon=1e-5):
+        super().__init__()
+        self.beta, self.epsilon = beta, epsilon
+        self.register_buffer("running_mean", torch.zeros(input_shape))
+        self.register_buffer("running_mean_sq", torch.zeros(input_shape))
+        self.register_buffer("debiasing_term", torch.tensor(0.0))
+
+    def running_mean_var(self):
+        d = self.debiasing_term.clamp(min=self.epsilon)
+        mean, mean_sq = self.running_mean / d, self.running_mean_sq / d
+        return mean, (mean_sq - mean ** 2).clamp(min=1e-2)
+
+
+def check_learner_config(cfg):
+    """Every configuration policy.check_config, actor_train._actor_cfg and critic_train's make_optimizer / update_critic refuse, with their
+    exception types, before anything is built."""
+    actor_train._actor_cfg(cfg)                                  # check_config; actor.lr_scheduler, actor.weight_decay
+    sget = _getter(_getter(cfg)("critic", None))
+    if sget("lr_scheduler", None):
+        raise P.PolicyConfigError("critic.lr_scheduler is not supported")
+    if float(sget("weight_decay", 0.0) or 0.0) != 0:
+        raise NotImplementedError("critic.weight_decay != 0 is not supported")
+    if int(sget("num_critics", 1) or 1) != 1:
+        raise P.PolicyConfigError("critic.num_critics > 1 is not supported")
+
+
+def _named(obj):
+    """name -> tensor of a network (module, TensorDict-like or mapping) under the reference's names, `module.` prefixes dropped."""
+    return {P._strip(k): v for k, v in P._flatten(obj).items()}
+
+
+def _mean_row(table):
+    """The CPU path's column means: hns_learner_info's statement (the fp64 sum in row order, divided once, rounded once to fp32)."""
+    out = []
+    for c in range(table.shape[1]):
+        s = 0.0
+        for v in table[:, c].tolist():
+            s += v
+        out.append(float(np.float32(s / table.shape[0])))
+    return out
+
+
+class DeviceLearner:
+    """MAPPOPolicy's training half.  actor: the shared actor's parameters (TensorDictParams / TensorDict / mapping / nn.Module), critic: the
+    critic module or its parameters — live tensors, updated in place; cfg: the algo cfg (dict or attribute object); tp_net: the predictor
+    (tp_net.TPNet or the reference's TP_net) or None; value_normalizer: a ValueNorm1 (the reference's or this module's) or None; generator:
+    the torch.Generator of every randperm (None: the global one); device_policy: a DevicePolicy over the same tensors (built when None)."""
+
+    def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, agent_name="drone", generator=None, device_policy=None):
+        check_learner_config(cfg)
+        get = _getter(cfg)
+        self.cfg, self.agent_name, self.generator = cfg, agent_name, generator
+        self.actor, self.critic, self.tp_net, self.value_normalizer = actor, critic, tp_net, value_normalizer
+        self.ppo_epochs, self.tp_epochs = int(get("ppo_epochs", 4)), int(get("TP_epochs", 1))
+        self.num_minibatches = int(get("num_minibatches", 16))
+        self.normalize_advantages = bool(get("normalize_advantages", True))
+        self.gamma, self.gae_lambda = float(get("gamma", 0.995)), float(get("gae_lambda", 0.95))
+        self.use_tp = tp_net is not None and bool(get("use_TP_net", 1))
+        if self.ppo_epochs < 1 or self.num_minibatches < 1 or (self.use_tp and self.tp_epochs < 1):
+            raise ValueError("ppo_epochs, num_minibatches and TP_epochs must be >= 1")
+        self.actor_opt = actor_train.make_optimizer(actor, cfg)
+        self.critic_opt = critic_train.make_optimizer(critic, cfg)
+        self.tp_opt = tp_train.TPAdam(tp_train.parameters(tp_net), lr=1e-4) if tp_net is not None else None
+        self.policy = device_policy if device_policy is not None else P.DevicePolicy(actor, critic, cfg, agent_name=agent_name)
+        self.n_updates = 0
+        self._ws = {}
+
+    # ---- workspaces
+    def _workspace(self, name, nbytes, device):
+        """The cached buffer of `name`, reallocated only when the shape grows (or the device changes)."""
+        ws = self._ws.get(name)
+        if ws is None or ws.numel() < nbytes or ws.device != device:
+            ws = self._ws[name] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return ws
+
+    def release(self):
+        """Drop the cached workspaces (the next train_op allocates them again)."""
+        self._ws = {}
+
+    # ---- the reference's entry point
+    def train_op(self, tensordict):
+        """MAPPOPolicy.train_op on the collector's [N, T] tensordict; returns {"<agent>/policy_loss": float, ...}."""
+        td = tensordict
+        obs = td[("agents", "observation")]
+        nxt = td["next"]
+        last = nxt[("agents", "observation")]
+        pick = lambda o, k: o.get(k, None) if hasattr(o, "get") else o[k]          # noqa: E731
+        agent_done = nxt.get(f"{self.agent_name}.done", None) if hasattr(nxt, "get") else None
+        tp = None
+        if self.use_tp:
+            t = nxt[("agents", "TP")]
+            tp = (t["TP_input"], t["TP_groundtruth"], t["TP_done"])
+        xo_last = pick(last, "state_others")
+        return self.train_rollout(
+            obs_self=obs["state_self"], obs_others=pick(obs, "state_others"), obs_cylinders=obs["cylinders"], action=td[("agents", "action")],
+            log_probs=td[f"{self.agent_name}.action_logp"], state_value=td["state_value"],
+            next_obs_last=(last["state_self"][:, -1], xo_last[:, -1] if xo_last is not None else None, last["cylinders"][:, -1]),
+            reward=nxt[("agents", "reward")], done=nxt["done"], agent_done=agent_done, tp=tp)
+
+    def train_rollout(self, *, obs_self, obs_others, obs_cylinders, action, log_probs, state_value, next_obs_last, reward, done, agent_done=None,
+                      tp=None):
+        """train_op on tensors: observations [N, T, A, ...], action [N, T, A, 4], log_probs / state_value [N, T, A, 1], next_obs_last: the
+        (state_self, state_others, cylinders) of the last step's next observation [N, A, ...], reward [N, T, A, r], done [N, T, 1] (the env's),
+        agent_done [N, T, A, 1] or None, tp: (TP_input, TP_groundtruth, TP_done) with the predictor."""
+        if self.use_tp and tp is None:
+            raise ValueError("use_TP_net: the rollout's TP_input, TP_groundtruth and TP_done are needed (tp=)")
+        xs, xo, xc = critic_train._as_rollout(obs_self, obs_others, obs_cylinders)
+        N, T, A, _ = xs.shape
+        dev = xs.device
+        # mappo.py:354-361: done = agent_done | env_done (an absent agent_done is env_done, which rollout_targets broadcasts over the agents)
+        dones = done.unsqueeze(-1)
+        if agent_done is not None:
+            dones = agent_done | dones
+        with torch.no_grad():
+            next_value = self.policy.forward(*next_obs_last, value_only=True).value
+        adv, ret, _, (adv_mean, adv_std) = gae.rollout_targets(reward, dones, state_value, next_value, self.gamma, self.gae_lambda,
+                                                               value_normalizer=self.value_normalizer, normalize_advantages=self.normalize_advantages,
+                                                               return_moments=True)
+        tp_loss = None
+        if self.use_tp:
+            tp_loss = tp_train.update_tp(self.tp_net, *tp, self.tp_net.future_predcition_step, self.tp_net.window_step, self.num_minibatches,
+                                         self.tp_epochs, self.tp_opt, generator=self.generator)
+        M = self.ppo_epochs * self.num_minibatches
+        table = torch.empty(M, len(COLUMNS), dtype=torch.float32, device=dev)
+        self._ppo_loop(xs, xo, xc, action, log_probs, adv, state_value, ret, table)
+        extras = [t.reshape(()).to(torch.float32) for t in ([tp_loss] if self.use_tp else []) + [adv_mean, adv_std]]
+        if self.value_normalizer is not None:
+            extras.append(self.value_normalizer.running_mean.mean().to(torch.float32))
+        if dev.type == "cuda":
+            row = torch.cat([self._info_row(action, table), torch.stack(extras)]).tolist()          # the call's one copy to the host
+        else:
+            a = action.reshape(-1, action.shape[-1]).double()
+            norm = float(np.float32(a.square().sum(-1).sqrt().sum().item() / a.shape[0]))
+            row = _mean_row(table) + [norm] + [float(t) for t in extras]
+        info = dict(zip(COLUMNS + ("action_norm",), row))
+        rest = iter(row[len(COLUMNS) + 1:])
+        if self.use_tp:
+            info["TP_loss"] = next(rest)
+        info["advantages_mean"], info["advantages_std"] = next(rest), next(rest)
+        if self.value_normalizer is not None:
+            info["value_running_mean"] = next(rest)
+        self.n_updates += 1
+        return {f"{self.agent_name}/{k}": info[k] for k in INFO_KEYS if k in info}
+
+    def _ppo_loop(self, xs, xo, xc, action, log_probs, adv, state_value, ret, table):
+        """mappo.py:446-461: per epoch one permutation, per minibatch the actor's update and then the critic's.  On the device: no host
+        synchronisation — cached workspaces, scalars written into `table`'s rows, no index check."""
+        N, T, A, D = xs.shape
+        dev, K = xs.device, int(xc.shape[3])
+        ws_a = ws_c = None
+        if dev.type == "cuda":
+            lib = abi.load_library()
+            rows = (N * T // self.num_minibatches) * A
+            na, nc = lib.hns_actor_train_workspace_bytes(rows, D, A, K), lib.hns_critic_train_workspace_bytes(rows, D, A, K)
+            if rows < 1 or na == 0 or nc == 0:
+                raise ValueError(f"shape outside the kernels' limits: {rows} rows per minibatch, self_dim {D}, {A} agents, {K} cylinders")
+            ws_a, ws_c = self._workspace("actor", na, dev), self._workspace("critic", nc, dev)
+        m = 0
+        for _ in range(self.ppo_epochs):
+            for idx in tp_train.minibatches(N * T, self.num_minibatches, dev, self.generator):
+                out_a = table[m, :len(ACTOR_COLUMNS)] if ws_a is not None else None
+                out_c = table[m, len(ACTOR_COLUMNS):] if ws_c is not None else None
+                sa = actor_train.update_actor(self.actor, xs, xo, xc, action, log_probs, adv, self.actor_opt, index=idx, cfg=self.cfg,
+                                              workspace=ws_a, out=out_a)
+                sc = critic_train.update_critic(self.critic, xs, xo, xc, state_value, ret, self.critic_opt, index=idx, cfg=self.cfg,
+                                                workspace=ws_c, out=out_c)
+                if ws_a is None:                                 # CPU: the updates return their scalars
+                    table[m] = torch.stack([(sa | sc)[k].reshape(()).to(torch.float32) for k in COLUMNS])
+                m += 1
+
+    def _info_row(self, action, table):
+        """hns_learner_info: [column means, action_norm] as a device tensor (two launches, no synchronisation)."""
+        a = action.reshape(-1, action.shape[-1])
+        if a.dtype != torch.float32:
+            raise TypeError(f"action must be float32, not {a.dtype}")
+        dev, lib = a.device, abi.load_library()
+        nbytes = lib.hns_learner_info_workspace_bytes(a.shape[0])
+        ws = self._workspace("info", nbytes, dev)
+        out = torch.empty(table.shape[1] + 1, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.hns_learner_info(a.data_ptr(), (C.c_int64 * 2)(a.stride(0), a.stride(1)), a.shape[0], a.shape[1], table.data_ptr(),
+                                      table.shape[0], table.shape[1], out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        critic_train._check(rc, "hns_learner_info")
+        return out
+
+    # ---- checkpoints
+    def state_dict(self):
+        """MAPPOPolicy.state_dict()'s entries (mappo.py:477-484: "TP", "critic", "actor_params", "value_normalizer"; an absent part is left
+        out) and the three optimisers in torch.optim.Adam's format ("actor_opt", "critic_opt", "TP_opt"), which the reference drops."""
+        sd = {}
+        if self.tp_net is not None:
+            sd["TP"] = self.tp_net.state_dict()
+        sd["critic"] = self.critic.state_dict() if isinstance(self.critic, nn.Module) else {k: v.detach() for k, v in P._flatten(self.critic).items()}
+        sd["actor_params"] = self.actor if hasattr(self.actor, "flatten_keys") else {k: v.detach() for k, v in P._flatten(self.actor).items()}
+        if self.value_normalizer is not None:
+            sd["value_normalizer"] = self.value_normalizer.state_dict() if hasattr(self.value_normalizer, "state_dict") else \
+                {k: getattr(self.value_normalizer, k) for k in ("running_mean", "running_mean_sq", "debiasing_term")}
+        sd["actor_opt"], sd["critic_opt"] = self.actor_opt.state_dict(), self.critic_opt.state_dict()
+        if self.tp_opt is not None:
+            sd["TP_opt"] = self.tp_opt.state_dict()
+        return sd
+
+    def load_state_dict(self, sd):
+        """A checkpoint of state_dict() or of the reference (no optimiser keys: fresh optimisers, as mappo.py:486-491 leaves them).  Every
+        tensor is copied into the live parameter, so its version counter moves and DevicePolicy and the env's predictor re-pack."""
+        with torch.no_grad():
+            for mine, theirs, what in ((self.actor, sd["actor_params"], "actor_params"), (self.critic, sd["critic"], "critic")):
+                dst, src = _named(mine), _named(theirs)
+                if set(dst) != set(src):
+                    raise KeyError(f"{what}: parameter names differ: {sorted(set(dst) ^ set(src))[:6]}")
+                for k, v in dst.items():
+                    v.copy_(src[k])
+            if self.tp_net is not None and "TP" in sd:
+                self.tp_net.load_state_dict(sd["TP"])
+            if self.value_normalizer is not None and "value_normalizer" in sd:
+                if hasattr(self.value_normalizer, "load_state_dict"):
+                    self.value_normalizer.load_state_dict(sd["value_normalizer"])
+                else:
+                    for k, v in sd["value_normalizer"].items():
+                        getattr(self.value_normalizer, k).copy_(v)
+        for name, key, make in (("actor_opt", "actor_opt", lambda: actor_train.make_optimizer(self.actor, self.cfg)),
+                                ("critic_opt", "critic_opt", lambda: critic_train.make_optimizer(self.critic, self.cfg)),
+                                ("tp_opt", "TP_opt", lambda: tp_train.TPAdam(tp_train.parameters(self.tp_net), lr=1e-4))):
+            if getattr(self, name) is None:
+                continue
+            setattr(self, name, make())
+            if key in sd:
+                getattr(self, name).load_state_dict(sd[key])

@@ -260,19 +260,21 @@ def select_windows(tp_input, tp_groundtruth, tp_done, future_step, window_step):
     return tp_input[:, :n_sel], selected.reshape(batch * n_sel, fs * pos_dim)
 
 
-def minibatches(rows, num_minibatches, device):
-    """make_dataset_naive's permutation (mappo.py:506-513, seq_len 1): [num_minibatches, rows // num_minibatches] int64, same generator calls."""
-    return torch.randperm((rows // num_minibatches) * num_minibatches, device=device).reshape(num_minibatches, -1)
+def minibatches(rows, num_minibatches, device, generator=None):
+    """make_dataset_naive's permutation (mappo.py:506-513, seq_len 1): [num_minibatches, rows // num_minibatches] int64, same generator calls
+    (`generator`: a torch.Generator on `device` instead of the global one)."""
+    return torch.randperm((rows // num_minibatches) * num_minibatches, device=device, generator=generator).reshape(num_minibatches, -1)
 
 
-def update_tp(tp, tp_input, tp_groundtruth, tp_done, future_step, window_step, num_minibatches, epochs, optimizer):
+def update_tp(tp, tp_input, tp_groundtruth, tp_done, future_step, window_step, num_minibatches, epochs, optimizer, generator=None):
     """MAPPOPolicy.train_op's predictor block (mappo.py:405-441) with update_TP (:252-268): tp_input [E, steps, T, I], tp_groundtruth
-    [E, steps, 3], tp_done [E, steps, 1] (the rollout's ('next', 'agents', 'TP') entries).  Returns the mean minibatch loss as a 0-dim tensor."""
+    [E, steps, 3], tp_done [E, steps, 1] (the rollout's ('next', 'agents', 'TP') entries).  Returns the mean minibatch loss as a 0-dim tensor.
+    `generator`: the torch.Generator every epoch's permutation is drawn from (None: the global one)."""
     x, y = select_windows(tp_input, tp_groundtruth, tp_done, future_step, window_step)
     rows = x.shape[0] * x.shape[1]
     losses = []
     for _ in range(epochs):
-        for idx in minibatches(rows, num_minibatches, x.device):
+        for idx in minibatches(rows, num_minibatches, x.device, generator):
             losses.append(loss_and_grad(tp, x, y, idx, check_index=False))
             optimizer.step()
     return torch.stack(losses).mean()
