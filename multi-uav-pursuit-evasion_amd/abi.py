@@ -213,16 +213,17 @@ class HnsPolicyIo(C.Structure):
 HNS_CRITIC_LOSS_HUBER, HNS_CRITIC_LOSS_MSE = 0, 1
 
 
+# hns_critic_batch's and hns_actor_batch's observation / index part (hns_amd.policy_train fills it), in front of each update's per-row pointers
+TRAIN_BATCH_FIELDS = [("obs_self", _fp), ("obs_others", _fp), ("obs_cylinders", _fp), ("self_stride", C.c_int64 * 3), ("others_stride", C.c_int64 * 4),
+                      ("cyl_stride", C.c_int64 * 4), ("num_envs", C.c_int64), ("num_steps", C.c_int64), ("index", _fp), ("batch", C.c_int64)]
+
+
 class HnsCriticBatch(C.Structure):
-    _fields_ = [("obs_self", _fp), ("obs_others", _fp), ("obs_cylinders", _fp), ("self_stride", C.c_int64 * 3), ("others_stride", C.c_int64 * 4),
-                ("cyl_stride", C.c_int64 * 4), ("num_envs", C.c_int64), ("num_steps", C.c_int64), ("index", _fp), ("batch", C.c_int64),
-                ("b_values", _fp), ("b_returns", _fp)]
+    _fields_ = TRAIN_BATCH_FIELDS + [("b_values", _fp), ("b_returns", _fp)]
 
 
 class HnsActorBatch(C.Structure):         # the MAPPO actor's update (include/hns.h: hns_actor_train_grad; hns_amd.actor_train)
-    _fields_ = [("obs_self", _fp), ("obs_others", _fp), ("obs_cylinders", _fp), ("self_stride", C.c_int64 * 3), ("others_stride", C.c_int64 * 4),
-                ("cyl_stride", C.c_int64 * 4), ("num_envs", C.c_int64), ("num_steps", C.c_int64), ("index", _fp), ("batch", C.c_int64),
-                ("action", _fp), ("log_probs_old", _fp), ("advantages", _fp)]
+    _fields_ = TRAIN_BATCH_FIELDS + [("action", _fp), ("log_probs_old", _fp), ("advantages", _fp)]
 
 
 class HnsAdamTensor(C.Structure):

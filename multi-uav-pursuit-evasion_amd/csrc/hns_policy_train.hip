@@ -1076,6 +1076,116 @@ bool ct_plan(int64_t rows, int32_t D, int32_t A, int32_t K, CtPlan &p, int heads
     return true;
 }
 
+// What the critic's and the actor's entry points share.  hns_critic_batch and hns_actor_batch carry the same leading fields under the same names:
+// the templates over the batch type read them from either.  Every refusal keeps the entry point's order: ct_check_shape, the entry's hyper-parameters,
+// ct_bind_net, ct_check_obs, the entry's per-row pointers, ct_plan_call.
+
+template <typename Batch>
+int ct_check_shape(const char *fn, const Batch &b, int32_t self_dim, int32_t num_agents, int32_t num_cylinders) {
+    if (self_dim < 1 || self_dim > hns::kCtMaxSelf) return ct_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kCtMaxSelf) + "]");
+    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return ct_fail(fn, "num_agents must be in [1, 7]");
+    if (num_cylinders < 1 || num_cylinders > HNS_MAX_CYLINDERS) return ct_fail(fn, "num_cylinders must be in [1, 16]");
+    if (b.batch < 1) return ct_fail(fn, "batch must be >= 1 (the mean over an empty minibatch is NaN)");
+    if (b.num_envs < 1 || b.num_steps < 1 || b.num_envs > ((int64_t)1 << 40) / b.num_steps) return ct_fail(fn, "num_envs, num_steps must be >= 1");
+    if (b.batch > ((int64_t)1 << 31) / HNS_MAX_AGENTS) return ct_fail(fn, "batch too large");
+    if (!b.index && b.batch > b.num_envs * b.num_steps) return ct_fail(fn, "batch exceeds the env-steps of the rollout (no index)");
+    return HNS_OK;
+}
+
+// X(field of hns_policy_net and hns_policy_grads, member of CtNet and CtGrad): every tensor both networks always have.  The state_others embedding
+// (absent with one agent) and log_std (the actor's) follow by hand in ct_bind_net.
+#define HNS_CT_FIELDS(X)                                                                                                                       \
+    X(embed_self_w, ew[0]) X(embed_self_b, eb[0]) X(embed_cyl_w, ew[2]) X(embed_cyl_b, eb[2]) X(ln_w, ln_w) X(ln_b, ln_b) X(in_proj_w, in_w)   \
+    X(in_proj_b, in_b) X(out_proj_w, out_w) X(out_proj_b, out_b) X(linear1_w, l1_w) X(linear1_b, l1_b) X(linear2_w, l2_w) X(linear2_b, l2_b)   \
+    X(norm1_w, n1_w) X(norm1_b, n1_b) X(norm2_w, n2_w) X(norm2_b, n2_b) X(head_w, head_w) X(head_b, head_b)
+
+// the parameter and gradient tables, checked and copied by ONE field list (heads > 1: the actor, whose log_std joins both)
+int ct_bind_net(const char *fn, const hns_policy_net &net, const hns_policy_grads &grads, bool others, int heads, hns::CtNet &n, hns::CtGrad &g) {
+    bool ok = true;
+#define X(f, m)                                                                                      \
+    ok = ok && net.f && grads.f && ct_aligned(net.f, 16) && ct_aligned(grads.f, 4);                  \
+    n.m = net.f;                                                                                     \
+    g.m = grads.f;
+    HNS_CT_FIELDS(X)
+#undef X
+    if (heads > 1) {
+        ok = ok && net.log_std && grads.log_std && ct_aligned(net.log_std, 16) && ct_aligned(grads.log_std, 4);
+        g.log_std = grads.log_std;
+    }
+    if (!ok) return ct_fail(fn, "every parameter must be a non-NULL 16-byte aligned fp32 array, every gradient a non-NULL fp32 array");
+    if (others && (!net.embed_others_w || !net.embed_others_b || !grads.embed_others_w || !grads.embed_others_b || !ct_aligned(net.embed_others_b, 16)))
+        return ct_fail(fn, "state_others embedding (parameter or gradient) missing or misaligned (num_agents > 1)");
+    n.ew[1] = others ? net.embed_others_w : nullptr; n.eb[1] = others ? net.embed_others_b : nullptr;
+    g.ew[1] = others ? grads.embed_others_w : nullptr; g.eb[1] = others ? grads.embed_others_b : nullptr;
+    return HNS_OK;
+}
+
+template <typename Batch>
+int ct_check_obs(const char *fn, const Batch &b, bool others) {
+    if (!b.obs_self || !b.obs_cylinders || (others && !b.obs_others)) return ct_fail(fn, "observation pointer missing");
+    if (!ct_aligned(b.obs_self, 4) || !ct_aligned(b.obs_cylinders, 4) || (b.obs_others && !ct_aligned(b.obs_others, 4))) return ct_fail(fn, "misaligned observation");
+    for (int k = 0; k < 3; ++k)
+        if (b.self_stride[k] < 0) return ct_fail(fn, "negative stride");
+    for (int k = 0; k < 4; ++k)
+        if (b.others_stride[k] < 0 || b.cyl_stride[k] < 0) return ct_fail(fn, "negative stride");
+    return HNS_OK;
+}
+
+// the last refusals (index, `outs`: the entry's fp32 outputs, a NULL optional one among them; the plan and the workspace), then the part of the
+// kernel arguments that is the same for both networks: observations, index, shape, the workspace's arrays
+template <typename Batch>
+int ct_plan_call(const char *fn, const Batch &b, std::initializer_list<const float *> outs, void *workspace, size_t workspace_bytes, int32_t self_dim,
+                 int32_t num_agents, int32_t num_cylinders, int heads, CtPlan &p, hns::CtArgs &a) {
+    if (b.index && !ct_aligned(b.index, 8)) return ct_fail(fn, "misaligned index");
+    bool ok = ct_aligned(workspace, 256);
+    for (const float *o : outs) ok = ok && ct_aligned(o, 4);
+    if (!ok) return ct_fail(fn, "misaligned output (scalars 4 bytes, workspace 256)");
+    const int64_t rows = b.batch * num_agents;
+    if (!ct_plan(rows, self_dim, num_agents, num_cylinders, p, heads)) return ct_fail(fn, "invalid shape");
+    if (workspace_bytes < p.total)
+        return ct_fail(fn, heads > 1 ? "workspace too small (hns_actor_train_workspace_bytes)" : "workspace too small (hns_critic_train_workspace_bytes)");
+
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    a.img = reinterpret_cast<float *>(ws + p.o_img);
+    a.xs = b.obs_self; a.xo = num_agents > 1 ? b.obs_others : nullptr; a.xc = b.obs_cylinders;
+    for (int k = 0; k < 3; ++k) a.ss[k] = b.self_stride[k];
+    for (int k = 0; k < 4; ++k) { a.so[k] = b.others_stride[k]; a.sc[k] = b.cyl_stride[k]; }
+    a.T = b.num_steps; a.steps = b.num_envs * b.num_steps;
+    a.index = reinterpret_cast<const long long *>(b.index);
+    a.rows = rows; a.A = num_agents; a.K = num_cylinders; a.D = self_dim; a.tiles = (int)p.tiles;
+    a.inv_n = (float)(1.0 / (double)rows);
+    a.losspart = reinterpret_cast<double *>(ws + p.o_loss);
+    a.tilepart = reinterpret_cast<float *>(ws + p.o_tile);
+    a.P = p.P;
+    a.stage = reinterpret_cast<float *>(ws + p.o_stage);
+    a.stage_rows = p.stage_rows;
+    return HNS_OK;
+}
+
+// the launch in front of an entry's own: the packed operand image
+int ct_launch_pack(hipStream_t st, const hns::CtArgs &a, const CtPlan &p, void *workspace) {
+    float *img = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + p.o_img);
+    hipLaunchKernelGGL(hns::hns_critic_pack_kernel, dim3(256), dim3(256), 0, st, a.net, a.D, img);
+    HNS_CHECK_HIP(hipGetLastError());
+    return HNS_OK;
+}
+
+// the launches behind them: weight gradients, the fixed-order sums into the PyTorch layouts (`ls_add`: hns_critic_reduce_kernel's), the total norm
+int ct_launch_tail(hipStream_t st, const hns::CtArgs &a, const CtPlan &p, const hns::CtGrad &g, void *workspace, int heads, double ls_add, float *grad_norm) {
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    float *gpart = reinterpret_cast<float *>(ws + p.o_gemm);
+    hipLaunchKernelGGL(hns::hns_critic_wgrad_kernel, dim3((unsigned)p.splits, 6), dim3(256), 0, st, a.stage, a.stage_rows, (int)p.tiles, (int)p.tps, gpart);
+    HNS_CHECK_HIP(hipGetLastError());
+    double *blockpart = reinterpret_cast<double *>(ws + p.o_block);
+    const int nb = p.gblocks + p.tblocks;
+    hipLaunchKernelGGL(hns::hns_critic_reduce_kernel, dim3(nb), dim3(256), 0, st, gpart, (int)p.splits, a.tilepart, (int)(2 * p.tiles), p.P, p.gblocks, g, a.D,
+                       blockpart, heads, ls_add);
+    HNS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hns::hns_critic_norm_kernel, dim3(1), dim3(256), 0, st, blockpart, nb, grad_norm);
+    HNS_CHECK_HIP(hipGetLastError());
+    return HNS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1090,78 +1200,21 @@ int hns_critic_train_grad(const hns_policy_net *critic, const hns_critic_batch *
                           float *explained_var, float *grad_norm, float *values, void *workspace, size_t workspace_bytes, void *stream) {
     const char *fn = "hns_critic_train_grad";
     if (!critic || !batch || !grads || !value_loss || !explained_var || !grad_norm || !workspace) return ct_fail(fn, "null pointer");
-    if (self_dim < 1 || self_dim > hns::kCtMaxSelf) return ct_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kCtMaxSelf) + "]");
-    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return ct_fail(fn, "num_agents must be in [1, 7]");
-    if (num_cylinders < 1 || num_cylinders > HNS_MAX_CYLINDERS) return ct_fail(fn, "num_cylinders must be in [1, 16]");
-    if (batch->batch < 1) return ct_fail(fn, "batch must be >= 1 (the mean over an empty minibatch is NaN)");
-    if (batch->num_envs < 1 || batch->num_steps < 1 || batch->num_envs > ((int64_t)1 << 40) / batch->num_steps) return ct_fail(fn, "num_envs, num_steps must be >= 1");
-    const int64_t steps = batch->num_envs * batch->num_steps;
-    if (batch->batch > ((int64_t)1 << 31) / HNS_MAX_AGENTS) return ct_fail(fn, "batch too large");
-    if (!batch->index && batch->batch > steps) return ct_fail(fn, "batch exceeds the env-steps of the rollout (no index)");
+    if (int rc = ct_check_shape(fn, *batch, self_dim, num_agents, num_cylinders)) return rc;
     if (loss_kind != HNS_CRITIC_LOSS_HUBER && loss_kind != HNS_CRITIC_LOSS_MSE) return ct_fail(fn, "loss_kind must be HNS_CRITIC_LOSS_HUBER or HNS_CRITIC_LOSS_MSE");
     if (!(clip_param >= 0.0f) || (loss_kind == HNS_CRITIC_LOSS_HUBER && !(huber_delta > 0.0f))) return ct_fail(fn, "clip_param >= 0, huber_delta > 0");
-    const bool others = num_agents > 1;
-    const float *pr[] = {critic->embed_self_w, critic->embed_self_b, critic->embed_cyl_w, critic->embed_cyl_b, critic->ln_w, critic->ln_b, critic->in_proj_w,
-                         critic->in_proj_b, critic->out_proj_w, critic->out_proj_b, critic->linear1_w, critic->linear1_b, critic->linear2_w, critic->linear2_b,
-                         critic->norm1_w, critic->norm1_b, critic->norm2_w, critic->norm2_b, critic->head_w, critic->head_b};
-    float *gr[] = {grads->embed_self_w, grads->embed_self_b, grads->embed_cyl_w, grads->embed_cyl_b, grads->ln_w, grads->ln_b, grads->in_proj_w,
-                   grads->in_proj_b, grads->out_proj_w, grads->out_proj_b, grads->linear1_w, grads->linear1_b, grads->linear2_w, grads->linear2_b,
-                   grads->norm1_w, grads->norm1_b, grads->norm2_w, grads->norm2_b, grads->head_w, grads->head_b};
-    for (int k = 0; k < 20; ++k)
-        if (!pr[k] || !gr[k] || !ct_aligned(pr[k], 16) || !ct_aligned(gr[k], 4)) return ct_fail(fn, "every parameter must be a non-NULL 16-byte aligned fp32 array, every gradient a non-NULL fp32 array");
-    if (others && (!critic->embed_others_w || !critic->embed_others_b || !grads->embed_others_w || !grads->embed_others_b || !ct_aligned(critic->embed_others_b, 16)))
-        return ct_fail(fn, "state_others embedding (parameter or gradient) missing or misaligned (num_agents > 1)");
-    if (!batch->obs_self || !batch->obs_cylinders || (others && !batch->obs_others)) return ct_fail(fn, "observation pointer missing");
-    if (!ct_aligned(batch->obs_self, 4) || !ct_aligned(batch->obs_cylinders, 4) || (batch->obs_others && !ct_aligned(batch->obs_others, 4)))
-        return ct_fail(fn, "misaligned observation");
-    for (int k = 0; k < 3; ++k)
-        if (batch->self_stride[k] < 0) return ct_fail(fn, "negative stride");
-    for (int k = 0; k < 4; ++k)
-        if (batch->others_stride[k] < 0 || batch->cyl_stride[k] < 0) return ct_fail(fn, "negative stride");
-    if (!batch->b_values || !batch->b_returns || !ct_aligned(batch->b_values, 4) || !ct_aligned(batch->b_returns, 4)) return ct_fail(fn, "b_values / b_returns missing or misaligned");
-    if (batch->index && !ct_aligned(batch->index, 8)) return ct_fail(fn, "misaligned index");
-    if (!ct_aligned(value_loss, 4) || !ct_aligned(explained_var, 4) || !ct_aligned(grad_norm, 4) || (values && !ct_aligned(values, 4)) || !ct_aligned(workspace, 256))
-        return ct_fail(fn, "misaligned output (scalars 4 bytes, workspace 256)");
-    CtPlan p;
-    const int64_t rows = batch->batch * num_agents;
-    if (!ct_plan(rows, self_dim, num_agents, num_cylinders, p)) return ct_fail(fn, "invalid shape");
-    if (workspace_bytes < p.total) return ct_fail(fn, "workspace too small (hns_critic_train_workspace_bytes)");
-
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
     hns::CtArgs a{};
-    hns::CtNet &n = a.net;
-    n.ew[0] = critic->embed_self_w; n.eb[0] = critic->embed_self_b;
-    n.ew[1] = others ? critic->embed_others_w : nullptr; n.eb[1] = others ? critic->embed_others_b : nullptr;
-    n.ew[2] = critic->embed_cyl_w; n.eb[2] = critic->embed_cyl_b;
-    n.ln_w = critic->ln_w; n.ln_b = critic->ln_b; n.in_w = critic->in_proj_w; n.in_b = critic->in_proj_b; n.out_w = critic->out_proj_w; n.out_b = critic->out_proj_b;
-    n.l1_w = critic->linear1_w; n.l1_b = critic->linear1_b; n.l2_w = critic->linear2_w; n.l2_b = critic->linear2_b;
-    n.n1_w = critic->norm1_w; n.n1_b = critic->norm1_b; n.n2_w = critic->norm2_w; n.n2_b = critic->norm2_b; n.head_w = critic->head_w; n.head_b = critic->head_b;
-    hns::CtGrad G{};
-    G.ew[0] = grads->embed_self_w; G.eb[0] = grads->embed_self_b;
-    G.ew[1] = others ? grads->embed_others_w : nullptr; G.eb[1] = others ? grads->embed_others_b : nullptr;
-    G.ew[2] = grads->embed_cyl_w; G.eb[2] = grads->embed_cyl_b;
-    G.ln_w = grads->ln_w; G.ln_b = grads->ln_b; G.in_w = grads->in_proj_w; G.in_b = grads->in_proj_b; G.out_w = grads->out_proj_w; G.out_b = grads->out_proj_b;
-    G.l1_w = grads->linear1_w; G.l1_b = grads->linear1_b; G.l2_w = grads->linear2_w; G.l2_b = grads->linear2_b;
-    G.n1_w = grads->norm1_w; G.n1_b = grads->norm1_b; G.n2_w = grads->norm2_w; G.n2_b = grads->norm2_b; G.head_w = grads->head_w; G.head_b = grads->head_b;
-
-    float *img = reinterpret_cast<float *>(ws + p.o_img);
-    float *ctl = reinterpret_cast<float *>(ws + p.o_ctl);
-    a.img = img;
-    a.xs = batch->obs_self; a.xo = others ? batch->obs_others : nullptr; a.xc = batch->obs_cylinders;
-    for (int k = 0; k < 3; ++k) a.ss[k] = batch->self_stride[k];
-    for (int k = 0; k < 4; ++k) { a.so[k] = batch->others_stride[k]; a.sc[k] = batch->cyl_stride[k]; }
-    a.T = batch->num_steps; a.steps = steps;
-    a.index = reinterpret_cast<const long long *>(batch->index);
-    a.rows = rows; a.A = num_agents; a.K = num_cylinders; a.D = self_dim; a.tiles = (int)p.tiles;
+    hns::CtGrad g{};
+    CtPlan p;
+    if (int rc = ct_bind_net(fn, *critic, *grads, num_agents > 1, 1, a.net, g)) return rc;
+    if (int rc = ct_check_obs(fn, *batch, num_agents > 1)) return rc;
+    if (!batch->b_values || !batch->b_returns || !ct_aligned(batch->b_values, 4) || !ct_aligned(batch->b_returns, 4)) return ct_fail(fn, "b_values / b_returns missing or misaligned");
+    if (int rc = ct_plan_call(fn, *batch, {value_loss, explained_var, grad_norm, values}, workspace, workspace_bytes, self_dim, num_agents, num_cylinders, 1, p, a)) return rc;
+    float *ctl = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + p.o_ctl);
     a.bval = batch->b_values; a.bret = batch->b_returns;
-    a.clip = clip_param; a.delta = huber_delta; a.inv_n = (float)(1.0 / (double)rows); a.mse = loss_kind == HNS_CRITIC_LOSS_MSE;
+    a.clip = clip_param; a.delta = huber_delta; a.mse = loss_kind == HNS_CRITIC_LOSS_MSE;
     a.values = values;
-    a.losspart = reinterpret_cast<double *>(ws + p.o_loss);
     a.ctl = ctl;
-    a.tilepart = reinterpret_cast<float *>(ws + p.o_tile);
-    a.P = p.P;
-    a.stage = reinterpret_cast<float *>(ws + p.o_stage);
-    a.stage_rows = p.stage_rows;
 
     const hipStream_t st = static_cast<hipStream_t>(stream);
     static const hipError_t attr_f = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<false>),
@@ -1170,25 +1223,14 @@ int hns_critic_train_grad(const hns_policy_net *critic, const hns_critic_batch *
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::CtLds));
     HNS_CHECK_HIP(attr_f);
     HNS_CHECK_HIP(attr_b);
-    hipLaunchKernelGGL(hns::hns_critic_pack_kernel, dim3(256), dim3(256), 0, st, n, (int)self_dim, img);
-    HNS_CHECK_HIP(hipGetLastError());
+    if (int rc = ct_launch_pack(st, a, p, workspace)) return rc;
     hipLaunchKernelGGL(hns::hns_critic_kernel<false>, dim3((unsigned)p.tiles), dim3(hns::kCtThreads), hns::kCtLdsFwd, st, a);
     HNS_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hns::hns_critic_loss_kernel, dim3(1), dim3(256), 0, st, a.losspart, (int)p.tiles, (double)rows, ctl, value_loss, explained_var);
+    hipLaunchKernelGGL(hns::hns_critic_loss_kernel, dim3(1), dim3(256), 0, st, a.losspart, (int)p.tiles, (double)a.rows, ctl, value_loss, explained_var);
     HNS_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(hns::hns_critic_kernel<true>, dim3((unsigned)p.tiles), dim3(hns::kCtThreads), sizeof(hns::CtLds), st, a);
     HNS_CHECK_HIP(hipGetLastError());
-    float *gpart = reinterpret_cast<float *>(ws + p.o_gemm);
-    hipLaunchKernelGGL(hns::hns_critic_wgrad_kernel, dim3((unsigned)p.splits, 6), dim3(256), 0, st, a.stage, a.stage_rows, (int)p.tiles, (int)p.tps, gpart);
-    HNS_CHECK_HIP(hipGetLastError());
-    double *blockpart = reinterpret_cast<double *>(ws + p.o_block);
-    const int nb = p.gblocks + p.tblocks;
-    hipLaunchKernelGGL(hns::hns_critic_reduce_kernel, dim3(nb), dim3(256), 0, st, gpart, (int)p.splits, a.tilepart, (int)(2 * p.tiles), p.P, p.gblocks, G,
-                       (int)self_dim, blockpart, 1, 0.0);
-    HNS_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hns::hns_critic_norm_kernel, dim3(1), dim3(256), 0, st, blockpart, nb, grad_norm);
-    HNS_CHECK_HIP(hipGetLastError());
-    return HNS_OK;
+    return ct_launch_tail(st, a, p, g, workspace, 1, 0.0, grad_norm);
 }
 
 size_t hns_actor_train_workspace_bytes(int64_t rows, int32_t self_dim, int32_t num_agents, int32_t num_cylinders) {
@@ -1201,103 +1243,34 @@ int hns_actor_train_grad(const hns_policy_net *actor, const hns_actor_batch *bat
                          float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream) {
     const char *fn = "hns_actor_train_grad";
     if (!actor || !batch || !grads || !policy_loss || !entropy || !ess || !grad_norm || !workspace) return ct_fail(fn, "null pointer");
-    if (self_dim < 1 || self_dim > hns::kCtMaxSelf) return ct_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kCtMaxSelf) + "]");
-    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return ct_fail(fn, "num_agents must be in [1, 7]");
-    if (num_cylinders < 1 || num_cylinders > HNS_MAX_CYLINDERS) return ct_fail(fn, "num_cylinders must be in [1, 16]");
-    if (batch->batch < 1) return ct_fail(fn, "batch must be >= 1 (the mean over an empty minibatch is NaN)");
-    if (batch->num_envs < 1 || batch->num_steps < 1 || batch->num_envs > ((int64_t)1 << 40) / batch->num_steps) return ct_fail(fn, "num_envs, num_steps must be >= 1");
-    const int64_t steps = batch->num_envs * batch->num_steps;
-    if (batch->batch > ((int64_t)1 << 31) / HNS_MAX_AGENTS) return ct_fail(fn, "batch too large");
-    if (!batch->index && batch->batch > steps) return ct_fail(fn, "batch exceeds the env-steps of the rollout (no index)");
+    if (int rc = ct_check_shape(fn, *batch, self_dim, num_agents, num_cylinders)) return rc;
     if (!(clip_param >= 0.0) || !std::isfinite(clip_param) || !std::isfinite(entropy_coef)) return ct_fail(fn, "clip_param >= 0 and a finite entropy_coef");
-    const bool others = num_agents > 1;
-    const float *pr[] = {actor->embed_self_w, actor->embed_self_b, actor->embed_cyl_w, actor->embed_cyl_b, actor->ln_w, actor->ln_b, actor->in_proj_w,
-                         actor->in_proj_b, actor->out_proj_w, actor->out_proj_b, actor->linear1_w, actor->linear1_b, actor->linear2_w, actor->linear2_b,
-                         actor->norm1_w, actor->norm1_b, actor->norm2_w, actor->norm2_b, actor->head_w, actor->head_b, actor->log_std};
-    float *gr[] = {grads->embed_self_w, grads->embed_self_b, grads->embed_cyl_w, grads->embed_cyl_b, grads->ln_w, grads->ln_b, grads->in_proj_w,
-                   grads->in_proj_b, grads->out_proj_w, grads->out_proj_b, grads->linear1_w, grads->linear1_b, grads->linear2_w, grads->linear2_b,
-                   grads->norm1_w, grads->norm1_b, grads->norm2_w, grads->norm2_b, grads->head_w, grads->head_b, grads->log_std};
-    for (int k = 0; k < 21; ++k)
-        if (!pr[k] || !gr[k] || !ct_aligned(pr[k], 16) || !ct_aligned(gr[k], 4)) return ct_fail(fn, "every parameter must be a non-NULL 16-byte aligned fp32 array, every gradient a non-NULL fp32 array");
-    if (others && (!actor->embed_others_w || !actor->embed_others_b || !grads->embed_others_w || !grads->embed_others_b || !ct_aligned(actor->embed_others_b, 16)))
-        return ct_fail(fn, "state_others embedding (parameter or gradient) missing or misaligned (num_agents > 1)");
-    if (!batch->obs_self || !batch->obs_cylinders || (others && !batch->obs_others)) return ct_fail(fn, "observation pointer missing");
-    if (!ct_aligned(batch->obs_self, 4) || !ct_aligned(batch->obs_cylinders, 4) || (batch->obs_others && !ct_aligned(batch->obs_others, 4)))
-        return ct_fail(fn, "misaligned observation");
-    for (int k = 0; k < 3; ++k)
-        if (batch->self_stride[k] < 0) return ct_fail(fn, "negative stride");
-    for (int k = 0; k < 4; ++k)
-        if (batch->others_stride[k] < 0 || batch->cyl_stride[k] < 0) return ct_fail(fn, "negative stride");
+    hns::CtArgs a{};
+    hns::CtGrad g{};
+    CtPlan p;
+    if (int rc = ct_bind_net(fn, *actor, *grads, num_agents > 1, hns::kActDim, a.net, g)) return rc;
+    if (int rc = ct_check_obs(fn, *batch, num_agents > 1)) return rc;
     if (!batch->action || !batch->log_probs_old || !batch->advantages || !ct_aligned(batch->action, 4) || !ct_aligned(batch->log_probs_old, 4) ||
         !ct_aligned(batch->advantages, 4))
         return ct_fail(fn, "action / log_probs_old / advantages missing or misaligned");
-    if (batch->index && !ct_aligned(batch->index, 8)) return ct_fail(fn, "misaligned index");
-    if (!ct_aligned(policy_loss, 4) || !ct_aligned(entropy, 4) || !ct_aligned(ess, 4) || !ct_aligned(grad_norm, 4) || (log_probs && !ct_aligned(log_probs, 4)) ||
-        !ct_aligned(workspace, 256))
-        return ct_fail(fn, "misaligned output (scalars 4 bytes, workspace 256)");
-    CtPlan p;
-    const int64_t rows = batch->batch * num_agents;
-    if (!ct_plan(rows, self_dim, num_agents, num_cylinders, p, hns::kActDim)) return ct_fail(fn, "invalid shape");
-    if (workspace_bytes < p.total) return ct_fail(fn, "workspace too small (hns_actor_train_workspace_bytes)");
-
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    hns::CtArgs a{};
-    hns::CtNet &n = a.net;
-    n.ew[0] = actor->embed_self_w; n.eb[0] = actor->embed_self_b;
-    n.ew[1] = others ? actor->embed_others_w : nullptr; n.eb[1] = others ? actor->embed_others_b : nullptr;
-    n.ew[2] = actor->embed_cyl_w; n.eb[2] = actor->embed_cyl_b;
-    n.ln_w = actor->ln_w; n.ln_b = actor->ln_b; n.in_w = actor->in_proj_w; n.in_b = actor->in_proj_b; n.out_w = actor->out_proj_w; n.out_b = actor->out_proj_b;
-    n.l1_w = actor->linear1_w; n.l1_b = actor->linear1_b; n.l2_w = actor->linear2_w; n.l2_b = actor->linear2_b;
-    n.n1_w = actor->norm1_w; n.n1_b = actor->norm1_b; n.n2_w = actor->norm2_w; n.n2_b = actor->norm2_b; n.head_w = actor->head_w; n.head_b = actor->head_b;
-    hns::CtGrad G{};
-    G.ew[0] = grads->embed_self_w; G.eb[0] = grads->embed_self_b;
-    G.ew[1] = others ? grads->embed_others_w : nullptr; G.eb[1] = others ? grads->embed_others_b : nullptr;
-    G.ew[2] = grads->embed_cyl_w; G.eb[2] = grads->embed_cyl_b;
-    G.ln_w = grads->ln_w; G.ln_b = grads->ln_b; G.in_w = grads->in_proj_w; G.in_b = grads->in_proj_b; G.out_w = grads->out_proj_w; G.out_b = grads->out_proj_b;
-    G.l1_w = grads->linear1_w; G.l1_b = grads->linear1_b; G.l2_w = grads->linear2_w; G.l2_b = grads->linear2_b;
-    G.n1_w = grads->norm1_w; G.n1_b = grads->norm1_b; G.n2_w = grads->norm2_w; G.n2_b = grads->norm2_b; G.head_w = grads->head_w; G.head_b = grads->head_b;
-    G.log_std = grads->log_std;
-
-    float *img = reinterpret_cast<float *>(ws + p.o_img);
-    a.img = img;
-    a.xs = batch->obs_self; a.xo = others ? batch->obs_others : nullptr; a.xc = batch->obs_cylinders;
-    for (int k = 0; k < 3; ++k) a.ss[k] = batch->self_stride[k];
-    for (int k = 0; k < 4; ++k) { a.so[k] = batch->others_stride[k]; a.sc[k] = batch->cyl_stride[k]; }
-    a.T = batch->num_steps; a.steps = steps;
-    a.index = reinterpret_cast<const long long *>(batch->index);
-    a.rows = rows; a.A = num_agents; a.K = num_cylinders; a.D = self_dim; a.tiles = (int)p.tiles;
+    if (int rc = ct_plan_call(fn, *batch, {policy_loss, entropy, ess, grad_norm, log_probs}, workspace, workspace_bytes, self_dim, num_agents, num_cylinders,
+                              hns::kActDim, p, a))
+        return rc;
     a.logp_old = batch->log_probs_old; a.adv = batch->advantages; a.action = batch->action; a.log_std = actor->log_std;
     a.clip_lo = (float)(1.0 - clip_param); a.clip_hi = (float)(1.0 + clip_param);
-    a.inv_n = (float)(1.0 / (double)rows);
     a.logp_new = log_probs;
-    a.losspart = reinterpret_cast<double *>(ws + p.o_loss);
-    a.tilepart = reinterpret_cast<float *>(ws + p.o_tile);
-    a.P = p.P;
-    a.stage = reinterpret_cast<float *>(ws + p.o_stage);
-    a.stage_rows = p.stage_rows;
 
     const hipStream_t st = static_cast<hipStream_t>(stream);
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<true, hns::kActDim>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::CtLds));
     HNS_CHECK_HIP(attr);
-    hipLaunchKernelGGL(hns::hns_critic_pack_kernel, dim3(256), dim3(256), 0, st, n, (int)self_dim, img);
-    HNS_CHECK_HIP(hipGetLastError());
+    if (int rc = ct_launch_pack(st, a, p, workspace)) return rc;
     hipLaunchKernelGGL((hns::hns_critic_kernel<true, hns::kActDim>), dim3((unsigned)p.tiles), dim3(hns::kCtThreads), sizeof(hns::CtLds), st, a);
     HNS_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hns::hns_actor_loss_kernel, dim3(1), dim3(64), 0, st, a.losspart, (int)p.tiles, (int)num_agents, (double)rows, (double)batch->batch,
+    hipLaunchKernelGGL(hns::hns_actor_loss_kernel, dim3(1), dim3(64), 0, st, a.losspart, (int)p.tiles, (int)num_agents, (double)a.rows, (double)batch->batch,
                        actor->log_std, policy_loss, entropy, ess);
     HNS_CHECK_HIP(hipGetLastError());
-    float *gpart = reinterpret_cast<float *>(ws + p.o_gemm);
-    hipLaunchKernelGGL(hns::hns_critic_wgrad_kernel, dim3((unsigned)p.splits, 6), dim3(256), 0, st, a.stage, a.stage_rows, (int)p.tiles, (int)p.tps, gpart);
-    HNS_CHECK_HIP(hipGetLastError());
-    double *blockpart = reinterpret_cast<double *>(ws + p.o_block);
-    const int nb = p.gblocks + p.tblocks;
-    hipLaunchKernelGGL(hns::hns_critic_reduce_kernel, dim3(nb), dim3(256), 0, st, gpart, (int)p.splits, a.tilepart, (int)(2 * p.tiles), p.P, p.gblocks, G,
-                       (int)self_dim, blockpart, hns::kActDim, -entropy_coef);
-    HNS_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hns::hns_critic_norm_kernel, dim3(1), dim3(256), 0, st, blockpart, nb, grad_norm);
-    HNS_CHECK_HIP(hipGetLastError());
-    return HNS_OK;
+    return ct_launch_tail(st, a, p, g, workspace, hns::kActDim, -entropy_coef, grad_norm);
 }
 
 int hns_adam_clipped(const hns_adam_tensor *tensors, int32_t count, float *step, const float *total_norm, double max_norm, double lr, double beta1,

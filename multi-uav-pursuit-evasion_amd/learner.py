@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import abi, actor_train, critic_train, gae, tp_train
 from . import policy as P
-from .critic_train import _getter
+from . import policy_train as PT
 
 ACTOR_COLUMNS = ("policy_loss", "entropy", "ESS", "actor_grad_norm")           # hns_actor_train_grad's four scalars, in its order
 CRITIC_COLUMNS = ("value_loss", "explained_var", "critic_grad_norm")           # hns_critic_train_grad's three
@@ -52,16 +52,10 @@ class ValueNorm1(nn.Module):
 
 
 def check_learner_config(cfg):
-    """Every configuration policy.check_config, actor_train._actor_cfg and critic_train's make_optimizer / update_critic refuse, with their
-    exception types, before anything is built."""
-    actor_train._actor_cfg(cfg)                                  # check_config; actor.lr_scheduler, actor.weight_decay
-    sget = _getter(_getter(cfg)("critic", None))
-    if sget("lr_scheduler", None):
-        raise P.PolicyConfigError("critic.lr_scheduler is not supported")
-    if float(sget("weight_decay", 0.0) or 0.0) != 0:
-        raise NotImplementedError("critic.weight_decay != 0 is not supported")
-    if int(sget("num_critics", 1) or 1) != 1:
-        raise P.PolicyConfigError("critic.num_critics > 1 is not supported")
+    """Every configuration actor_train.actor_cfg and critic_train.critic_cfg refuse (policy.check_config's among them), with their exception
+    types, before anything is built."""
+    actor_train.actor_cfg(cfg)
+    critic_train.critic_cfg(cfg)
 
 
 def _named(obj):
@@ -88,7 +82,7 @@ class DeviceLearner:
 
     def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, agent_name="drone", generator=None, device_policy=None):
         check_learner_config(cfg)
-        get = _getter(cfg)
+        get = PT.getter(cfg)
         self.cfg, self.agent_name, self.generator = cfg, agent_name, generator
         self.actor, self.critic, self.tp_net, self.value_normalizer = actor, critic, tp_net, value_normalizer
         self.ppo_epochs, self.tp_epochs = int(get("ppo_epochs", 4)), int(get("TP_epochs", 1))
@@ -144,7 +138,7 @@ class DeviceLearner:
         agent_done [N, T, A, 1] or None, tp: (TP_input, TP_groundtruth, TP_done) with the predictor."""
         if self.use_tp and tp is None:
             raise ValueError("use_TP_net: the rollout's TP_input, TP_groundtruth and TP_done are needed (tp=)")
-        xs, xo, xc = critic_train._as_rollout(obs_self, obs_others, obs_cylinders)
+        xs, xo, xc = PT.as_rollout(obs_self, obs_others, obs_cylinders)
         N, T, A, _ = xs.shape
         dev = xs.device
         # mappo.py:354-361: done = agent_done | env_done (an absent agent_done is env_done, which rollout_targets broadcasts over the agents)
@@ -221,7 +215,7 @@ class DeviceLearner:
             rc = lib.hns_learner_info(a.data_ptr(), (C.c_int64 * 2)(a.stride(0), a.stride(1)), a.shape[0], a.shape[1], table.data_ptr(),
                                       table.shape[0], table.shape[1], out.data_ptr(), ws.data_ptr(), ws.numel(),
                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        critic_train._check(rc, "hns_learner_info")
+        PT.check(rc, "hns_learner_info")
         return out
 
     # ---- checkpoints

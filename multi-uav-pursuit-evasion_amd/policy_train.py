@@ -1,0 +1,246 @@
+"""What the MAPPO critic's and actor's updates share on the host side of csrc/hns_policy_train.hip: the checks of a minibatch read in place from
+the rollout, the preparation of a `hns_*_train_grad` call, the training restatement of the encoder and `ClippedAdam`.
+
+`critic_train` and `actor_train` keep what is their own — the reference's loss statements, their C call, their part of the cfg — and
+`learner` drives both.  `validate` and `prepare_call` take the network's word ("critic" / "actor") and its per-row tensors, so a refusal
+reads the same whichever update raised it.
+
+`ClippedAdam` is clip_grad_norm_ + torch.optim.Adam (amsgrad off, weight decay 0) in ONE launch of `hns_adam_clipped` over all tensors and a
+device-resident step counter; its state_dict is Adam's, both ways.  Every step bumps the parameters' version counters, so
+`policy.DevicePolicy` re-packs its operand image before the next forward pass.  A data-parallel caller all-reduces the `.grad` tensors and
+recomputes the norm between the two calls.  DESIGN.md §7.4-7.5."""
+import ctypes as C
+import math
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import abi
+from . import policy as P
+from .tp_train import TPAdam
+
+
+def check(rc, what):
+    if rc != abi.HNS_OK:
+        raise RuntimeError(f"{what} failed ({rc}): {abi.load_library().hns_last_error().decode()}")
+
+
+def getter(cfg):
+    if cfg is None:
+        return lambda k, d=None: d
+    return cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
+
+
+def check_workspace(workspace, nbytes, dev):
+    """The caller's workspace (a uint8 device tensor of at least `nbytes` bytes, 256-byte aligned) as the kernels take it."""
+    if not torch.is_tensor(workspace) or workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError(f"workspace must be a contiguous uint8 tensor on {dev}")
+    if workspace.numel() < nbytes:
+        raise ValueError(f"workspace holds {workspace.numel()} bytes, the minibatch needs {nbytes}")
+    if workspace.data_ptr() % 256:
+        raise ValueError("workspace must be 256-byte aligned")
+    return workspace
+
+
+def check_out(out, n, dev):
+    """The caller's `n` fp32 result slots (a view into a table row) as the kernels write them."""
+    if not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != dev or out.dim() != 1 or out.numel() != n or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 tensor of {n} values on {dev}")
+    return out
+
+
+def as_rollout(obs_self, obs_others, obs_cylinders):
+    """The observations as [N, T, A, ...] views (a flat [R, A, ...] batch is [R, 1, A, ...]) — never a copy."""
+    xs = obs_self
+    if xs.dim() == obs_cylinders.dim() and xs.dim() in (4, 5) and xs.shape[-2] == 1:
+        xs = xs.squeeze(-2)                                          # [.., A, 1, D] as the env writes state_self
+    if xs.dim() == 3:
+        xs = xs.unsqueeze(1)
+        obs_others = obs_others.unsqueeze(1) if obs_others is not None else None
+        obs_cylinders = obs_cylinders.unsqueeze(1)
+    if xs.dim() != 4:
+        raise ValueError(f"state_self must be [N, T, A, D] or [R, A, D] (optionally with a 1 before D), not {tuple(obs_self.shape)}")
+    return xs, obs_others, obs_cylinders
+
+
+def validate(word, p, xs, xo, xc, per_row, index, check_index):
+    """Every refusal of hns_critic_train_grad / hns_actor_train_grad, raised here before anything is launched.  word: "critic" / "actor";
+    per_row: (name, tensor, values per agent row) of the update's own [N T, A(, values)] tensors, in the order they are named."""
+    for k, t in p.items():
+        if not t.is_contiguous():
+            raise ValueError(f"{word} parameter {k} must be contiguous")
+    D = int(p["embed_self_w"].shape[1])
+    N, T, A, Dx = xs.shape
+    if Dx != D:
+        raise ValueError(f"state_self rows have {Dx} values, the {word} takes {D}")
+    if not 1 <= A <= abi.HNS_MAX_AGENTS:
+        raise ValueError(f"{A} agents outside [1, {abi.HNS_MAX_AGENTS}]")
+    has_others = "embed_others_w" in p
+    if (xo is not None) != has_others or (A > 1) != has_others:
+        raise ValueError(f"{A} agents: state_others is {'required' if A > 1 else 'absent'} for this network")
+    if xo is not None and tuple(xo.shape) != (N, T, A, A - 1, 3):
+        raise ValueError(f"state_others must be [{N}, {T}, {A}, {A - 1}, 3], not {tuple(xo.shape)}")
+    if xc.dim() != 5 or tuple(xc.shape[:3]) != (N, T, A) or xc.shape[-1] != 5 or not 1 <= xc.shape[3] <= abi.HNS_MAX_CYLINDERS:
+        raise ValueError(f"cylinders must be [{N}, {T}, {A}, K, 5] with K in [1, {abi.HNS_MAX_CYLINDERS}], not {tuple(xc.shape)}")
+    for name, t in (("state_self", xs), ("state_others", xo), ("cylinders", xc), *((name, t) for name, t, _ in per_row)):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, not {t.dtype}")
+    steps = N * T
+    if steps == 0:
+        raise ValueError("the rollout holds no env-step")
+    for name, t, width in per_row:
+        if width == 1:
+            if t.numel() != steps * A:
+                raise ValueError(f"{name} must hold [N * T, A] = [{steps}, {A}] values, not {tuple(t.shape)}")
+        elif t.numel() != steps * A * width or t.shape[-1] != width:
+            raise ValueError(f"{name} must hold [N * T, A, {width}] = [{steps}, {A}, {width}] values, not {tuple(t.shape)}")
+    if index is not None:
+        if index.dtype != torch.int64 or index.dim() != 1:
+            raise TypeError("index must be a 1-d int64 tensor")
+        if index.numel() < 1:
+            raise ValueError("empty minibatch: the mean over zero rows is NaN")
+        if not index.is_contiguous():
+            raise ValueError("index must be contiguous (the kernel reads it in place as consecutive int64): pass index.contiguous()")
+        if check_index and not (xs.is_cuda and torch.cuda.is_current_stream_capturing()):
+            lo, hi = torch.stack([index.min(), index.max()]).tolist()     # one host synchronisation
+            if lo < 0 or hi >= steps:
+                raise IndexError(f"index values [{lo}, {hi}] outside the {steps} env-steps of the rollout")
+    devs = {t.device for t in (*p.values(), xs, xc, *(t for _, t, _ in per_row))} | ({xo.device} if xo is not None else set()) | \
+        ({index.device} if index is not None else set())
+    if len(devs) != 1:
+        raise ValueError(f"parameters, observations, {', '.join(name for name, _, _ in per_row)} and index must share one device, not {devs}")
+    return N, T, A, D, int(xc.shape[3])
+
+
+def prepare_call(word, p, xs, xo, xc, index, shape, workspace_bytes, workspace, out, n_out, batch_type):
+    """The arguments of a hns_*_train_grad call on validated device tensors: (net, grd, batch, ws, nbytes, scal, B, stream) — the filled
+    hns_policy_net of the parameters and of their .grad tensors (created where absent), a `batch_type` with its observation / index part
+    filled (the per-row pointers are the caller's), the workspace and its size by `workspace_bytes`, the `n_out` fp32 result slots, the
+    env-steps of the minibatch and the current stream.  Every refusal comes first: nothing is allocated for a call that is refused."""
+    N, T, A, D, K = shape
+    dev = xs.device
+    xs, xc = (t if t.stride(-1) == 1 else t.contiguous() for t in (xs, xc))
+    if xo is not None and xo.stride(-1) != 1:
+        xo = xo.contiguous()
+    B = index.numel() if index is not None else N * T
+    for f, t in p.items():
+        if t.data_ptr() % 16:
+            raise ValueError(f"{word} parameter {f} must be 16-byte aligned")
+        if t.grad is not None and (t.grad.dtype != torch.float32 or not t.grad.is_contiguous() or t.grad.shape != t.shape or t.grad.device != dev):
+            raise ValueError("existing .grad tensors must be contiguous float32 of the parameter's shape on its device")
+    nbytes = workspace_bytes(B * A, D, A, K)
+    if nbytes == 0:
+        raise ValueError(f"shape outside the kernel's limits: {B * A} rows, self_dim {D}, {A} agents, {K} cylinders")
+    ws = check_workspace(workspace, nbytes, dev) if workspace is not None else None
+    scal = check_out(out, n_out, dev) if out is not None else None
+    net, grd = abi.HnsPolicyNet(), abi.HnsPolicyNet()
+    for f, t in p.items():
+        if t.grad is None:
+            t.grad = torch.empty_like(t)
+        setattr(net, f, t.data_ptr())
+        setattr(grd, f, t.grad.data_ptr())
+    b = batch_type()
+    b.obs_self, b.obs_cylinders = xs.data_ptr(), xc.data_ptr()
+    b.obs_others = xo.data_ptr() if xo is not None else None
+    b.self_stride[:] = [xs.stride(0), xs.stride(1), xs.stride(2)]
+    b.others_stride[:] = [xo.stride(0), xo.stride(1), xo.stride(2), xo.stride(3)] if xo is not None else [0, 0, 0, 0]
+    b.cyl_stride[:] = [xc.stride(0), xc.stride(1), xc.stride(2), xc.stride(3)]
+    b.num_envs, b.num_steps, b.batch = N, T, B
+    b.index = index.data_ptr() if index is not None else None
+    b._keep = (xs, xo, xc)                                       # a fix-up copy lives as long as the struct that points at it
+    if ws is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if scal is None:
+        scal = torch.empty(n_out, dtype=torch.float32, device=dev)
+    return net, grd, b, ws, nbytes, scal, B, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def encoder(p, xs, xo, xc):
+    """PartialAttentionEncoder.forward as nn.MultiheadAttention(batch_first=True) runs it with key IS value (modules/networks.py:283-313):
+    ONE transposed tensor serves as key and value, so torch projects k and v with one packed product — policy._encoder hands over two
+    transposes, which gives the same forward bits but sums the token gradients in another order than the reference's backward."""
+    E = P.EMBED_DIM
+    toks = [F.linear(xs, p["embed_self_w"], p["embed_self_b"])]
+    if xo is not None:
+        toks.append(F.linear(xo, p["embed_others_w"], p["embed_others_b"]))
+    toks.append(F.linear(xc, p["embed_cyl_w"], p["embed_cyl_b"]))
+    x = F.layer_norm(torch.cat(toks, dim=-2), (E,), p["ln_w"], p["ln_b"])
+    lead = x.shape[:-2]
+    x = x.reshape(-1, x.shape[-2], E)
+    res = x[:, [0]]                                              # (the reference's order of creation: autograd sums x's three uses in it)
+    q, kv = x[:, [0]].transpose(1, 0), x.transpose(1, 0)
+    attn = F.multi_head_attention_forward(q, kv, kv, E, 1, p["in_proj_w"], p["in_proj_b"], None, None, False, 0.0, p["out_proj_w"],
+                                          p["out_proj_b"], training=True, need_weights=False)[0].transpose(1, 0)
+    x = F.layer_norm(res + attn, (E,), p["norm1_w"], p["norm1_b"])
+    x = F.layer_norm(x + F.linear(F.gelu(F.linear(x, p["linear1_w"], p["linear1_b"])), p["linear2_w"], p["linear2_b"]), (E,),
+                     p["norm2_w"], p["norm2_b"])
+    return x.mean(-2).reshape(*lead, E)
+
+
+class ClippedAdam(TPAdam):
+    """clip_grad_norm_(params, max_grad_norm) followed by torch.optim.Adam's step, as update_critic runs them: one launch of
+    hns_adam_clipped per step for all tensors on the device (device-resident step counter, capturable), the reference's torch statements on
+    the CPU.  `step(grad_norm=...)` takes the total gradient norm value_loss_and_grad returned (a 0-dim device tensor; required on the device
+    unless max_grad_norm is inf or None).  state_dict() / load_state_dict() use Adam's format.  `last_grad_norm`: the unclipped norm of the
+    last step (what clip_grad_norm_ returns)."""
+
+    def __init__(self, params, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=10.0, weight_decay=0.0):
+        if weight_decay != 0:
+            raise NotImplementedError("ClippedAdam implements Adam with weight_decay 0")
+        super().__init__(params, lr=lr, betas=betas, eps=eps)
+        self.max_grad_norm = float("inf") if max_grad_norm is None else float(max_grad_norm)
+        if not self.max_grad_norm >= 0:
+            raise ValueError("max_grad_norm must be >= 0")
+        self.last_grad_norm = None
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_norm=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            self._check_group(group)
+            ps = [p for p in group["params"] if p.grad is not None]
+            cpu = [p for p in ps if not p.is_cuda]
+            dev = [p for p in ps if p.is_cuda]
+            if cpu:
+                self.last_grad_norm = nn.utils.clip_grad_norm_(cpu, self.max_grad_norm)
+                for p in cpu:
+                    self._cpu_step(p, self._state(p, None), group)
+            if dev:
+                self._device_step(dev, group, grad_norm)
+        return loss
+
+    def _device_step(self, ps, group, grad_norm=None):
+        devs = {p.device for p in ps}
+        if len(devs) != 1:
+            raise ValueError(f"ClippedAdam: the parameters of a group live on one device, not {devs}")
+        dev = ps[0].device
+        clip = math.isfinite(self.max_grad_norm)
+        if clip:
+            if grad_norm is None:
+                raise ValueError("ClippedAdam.step on the device needs grad_norm= (value_loss_and_grad's) unless max_grad_norm is inf")
+            if not torch.is_tensor(grad_norm) or grad_norm.device != dev or grad_norm.dtype != torch.float32 or grad_norm.numel() != 1:
+                raise ValueError("grad_norm must be a one-element float32 tensor on the parameters' device")
+        shared = next((self.state[p]["step"] for p in ps if len(self.state[p]) and self.state[p]["step"].device == dev), None)
+        if shared is None:
+            shared = torch.zeros((), dtype=torch.float32, device=dev)
+        arr = (abi.HnsAdamTensor * len(ps))()
+        for j, p in enumerate(ps):
+            st = self._state(p, shared)
+            if st["step"] is not shared:
+                raise RuntimeError("ClippedAdam: the parameters of a group on one device step together (one step counter)")
+            if p.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous() or p.grad.dtype != torch.float32:
+                raise ValueError("ClippedAdam on the device takes contiguous float32 parameters and gradients")
+            arr[j] = abi.HnsAdamTensor(p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel())
+        beta1, beta2 = group["betas"]
+        with torch.cuda.device(dev):
+            rc = abi.load_library().hns_adam_clipped(arr, len(ps), shared.data_ptr(), grad_norm.data_ptr() if clip else None,
+                                                     self.max_grad_norm, float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
+                                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        check(rc, "hns_adam_clipped")
+        self.last_grad_norm = grad_norm
+        for p in ps:
+            torch.autograd.graph.increment_version(p)

@@ -19,13 +19,13 @@ import torch.nn.functional as F  # noqa: E402
 
 import hns_amd  # noqa: E402,F401
 from hns_amd import actor_train as AT  # noqa: E402
-from hns_amd import critic_train as CT  # noqa: E402
 from hns_amd import policy as P  # noqa: E402
+from hns_amd import policy_train as PT  # noqa: E402
 
 
 def torch_update(p, opt, xs, xo, xc, act, lpo, adv, idx):
     """update_actor's statements on the gathered minibatch (mappo.py:271-324; actor_train._torch_loss_and_grad's, with backward() into .grad)."""
-    mean = F.linear(CT._encoder(p, xs[idx], xo[idx], xc[idx]), p["head_w"], p["head_b"])
+    mean = F.linear(PT.encoder(p, xs[idx], xo[idx], xc[idx]), p["head_w"], p["head_b"])
     dist = D.Independent(D.Normal(mean, torch.broadcast_to(torch.exp(p["log_std"]), mean.shape), validate_args=False), 1, validate_args=False)
     logp = dist.log_prob(act[idx]).unsqueeze(-1)
     ent = dist.entropy().unsqueeze(-1)

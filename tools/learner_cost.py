@@ -24,6 +24,7 @@ from hns_amd import actor_train as AT  # noqa: E402
 from hns_amd import critic_train as CT  # noqa: E402
 from hns_amd import gae, learner, tp_train  # noqa: E402
 from hns_amd import policy as P  # noqa: E402
+from hns_amd import policy_train as PT  # noqa: E402
 from hns_amd.tp_net import TPNet  # noqa: E402
 
 A, K, D, HIST, FUTURE = 3, 5, 35, 10, 5
@@ -84,7 +85,7 @@ def torch_arm(state, cfg):
 
     def run(ro):
         N, T = ro["action"].shape[:2]
-        xs, xo, xc = CT._as_rollout(ro["obs_self"], ro["obs_others"], ro["obs_cylinders"])
+        xs, xo, xc = PT.as_rollout(ro["obs_self"], ro["obs_others"], ro["obs_cylinders"])
         with torch.no_grad():
             l = ro["next_obs_last"]
             next_value = P.torch_forward(pa, pc, l[0], l[1], l[2], value_only=True).value
