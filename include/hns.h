@@ -499,9 +499,8 @@ typedef struct hns_tp_adam_tensor {
     float *exp_avg, *exp_avg_sq;
     int64_t numel;
 } hns_tp_adam_tensor;
-/* torch.optim.Adam (amsgrad off, weight decay 0) over 1 to 8 tensors in ONE launch, in the single-tensor statement order of torch's CPU kernels:
- * step += 1; m = fma(1 - b1, g - m, m); v = fma((1 - b2) g, g, v b2); denom = sqrt(v) / f32(sqrt(1 - b2^step)) + f32(eps);
- * p = p + (f32(-lr / (1 - b1^step)) m) / denom.  `step`: the device-resident fp32 step counter (torch's state['step']), read and bumped on the device. */
+/* torch.optim.Adam (amsgrad off, weight decay 0) over 1 to 8 tensors: hns_adam_clipped (below) without a norm, so one Adam launch and the bump
+ * of the counter, in one stream.  `step`: the device-resident fp32 step counter (torch's state['step']), read and bumped on the device. */
 int hns_tp_adam(const hns_tp_adam_tensor *tensors, int32_t count, float *step, double lr, double beta1, double beta2, double eps, void *stream);
 
 /*
@@ -587,9 +586,11 @@ typedef struct hns_adam_tensor {
     int64_t numel;
 } hns_adam_tensor;
 /* clip_grad_norm_ and torch.optim.Adam over ANY number of tensors with ONE bump of the device step counter: every gradient is multiplied by
- * min(max_norm / (*total_norm + 1e-6), 1) in place (torch's statements: the reciprocal, times max_norm, clamped), then Adam's statements in
- * the order hns_tp_adam documents, with step = *step + 1; *step is bumped after the last tensor.  total_norm NULL or max_norm = +inf: no
- * clipping (a data-parallel caller all-reduces the gradients and their norm between hns_critic_train_grad and this call). */
+ * min(max_norm / (*total_norm + 1e-6), 1) in place (torch's statements: the reciprocal, times max_norm, clamped), then Adam (amsgrad off, weight
+ * decay 0) in the single-tensor statement order of torch's CPU kernels with step = *step + 1: m = fma(1 - b1, g - m, m); v = fma((1 - b2) g, g, v b2);
+ * denom = sqrt(v) / f32(sqrt(1 - b2^step)) + f32(eps); p = p + (f32(-lr / (1 - b1^step)) m) / denom.  *step is bumped after the last tensor (one
+ * launch per 64 tensors, then the bump).  total_norm NULL or max_norm = +inf: no clipping (a data-parallel caller all-reduces the gradients and
+ * their norm between hns_critic_train_grad and this call). */
 int hns_adam_clipped(const hns_adam_tensor *tensors, int32_t count, float *step, const float *total_norm, double max_norm, double lr, double beta1,
                      double beta2, double eps, void *stream);
 

@@ -170,10 +170,6 @@ class HnsTpParams(C.Structure):           # hns_tp_params / hns_tp_grads: the si
     _fields_ = [(name, _fp) for name in TP_WEIGHT_FIELDS]
 
 
-class HnsTpAdamTensor(C.Structure):
-    _fields_ = [("param", _fp), ("grad", _fp), ("exp_avg", _fp), ("exp_avg_sq", _fp), ("numel", C.c_int64)]
-
-
 def tp_frame_dim(A, C=0, use_obstacles=False):
     """Width of one predictor frame (hideandseek.py:808-820)."""
     return 7 + 3 * A + (3 * C if use_obstacles else 0)
@@ -226,8 +222,11 @@ class HnsActorBatch(C.Structure):         # the MAPPO actor's update (include/hn
     _fields_ = TRAIN_BATCH_FIELDS + [("action", _fp), ("log_probs_old", _fp), ("advantages", _fp)]
 
 
-class HnsAdamTensor(C.Structure):
+class HnsAdamTensor(C.Structure):          # hns_adam_tensor, and hns_tp_adam_tensor (the same layout: csrc/hns_adam.hip asserts it)
     _fields_ = [("param", _fp), ("grad", _fp), ("exp_avg", _fp), ("exp_avg_sq", _fp), ("numel", C.c_int64)]
+
+
+HnsTpAdamTensor = HnsAdamTensor
 
 
 _LIB = None
@@ -376,6 +375,12 @@ def load_library():
         raise RuntimeError("hns_cfg layout mismatch between include/hns.h and abi.py")
     _LIB = lib
     return lib
+
+
+def check(rc, what):
+    """Raise with hns_last_error's text unless `rc` is HNS_OK."""
+    if rc != HNS_OK:
+        raise RuntimeError(f"{what} failed ({rc}): {load_library().hns_last_error().decode()}")
 
 
 EXPORTED_SYMBOLS = [

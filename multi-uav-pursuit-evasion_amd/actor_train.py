@@ -8,7 +8,7 @@ every parameter's `.grad` in its PyTorch layout and returns policy_loss, entropy
 no autograd graph, no host synchronisation.  `index` reads a minibatch of `make_dataset_naive` in place from the rollout's [N, T, A, ...]
 tensors, as critic_train does.
 
-The step is policy_train's `ClippedAdam` (clip_grad_norm_ + torch.optim.Adam in one launch) over the actor's 23 tensors; it bumps the
+The step is optim's `ClippedAdam` (clip_grad_norm_ + torch.optim.Adam in one call of `hns_adam_clipped`) over the actor's 23 tensors; it bumps the
 parameters' version counters, so `policy.DevicePolicy` re-packs its operand image before the next forward pass.
 
 `update_actor` is the reference's function.  CPU tensors run the reference's torch statements throughout (CPU tests, gloo runs — not the
@@ -95,7 +95,7 @@ def policy_loss_and_grad(actor, obs_self, obs_others, obs_cylinders, action, log
     with torch.cuda.device(xs.device):
         rc = lib.hns_actor_train_grad(C.byref(net), C.byref(b), D_, A, K, float(clip_param), float(entropy_coef), C.byref(grd), scal[0:].data_ptr(),
                                       scal[1:].data_ptr(), scal[2:].data_ptr(), scal[3:].data_ptr(), log_probs.data_ptr(), ws.data_ptr(), nbytes, st)
-    PT.check(rc, "hns_actor_train_grad")
+    abi.check(rc, "hns_actor_train_grad")
     return ActorLoss(scal[0], scal[1], scal[2], scal[3], log_probs)
 
 

@@ -7,7 +7,7 @@ encoder's backward pass, the weight-gradient products, fixed-order sums) that fi
 returns value_loss, explained_var and the total gradient norm as 0-dim device tensors — no autograd graph, no host synchronisation.  `index`
 reads a minibatch of `make_dataset_naive` (mappo.py:493-513, seq_len 1) in place from the rollout's [N, T, A, ...] observations.
 
-`ClippedAdam` (policy_train's, re-exported here) is clip_grad_norm_ + torch.optim.Adam in ONE launch of `hns_adam_clipped`.  What this update
+`ClippedAdam` (optim's, re-exported here) is clip_grad_norm_ + torch.optim.Adam in one call of `hns_adam_clipped`.  What this update
 shares with the actor's — the batch checks, the preparation of the C call, the encoder's restatement — lives in `policy_train`.
 
 `update_critic` is the reference's function.  CPU tensors run the reference's torch statements throughout (CPU tests, gloo runs — not the
@@ -88,7 +88,7 @@ def value_loss_and_grad(critic, obs_self, obs_others, obs_cylinders, b_values, b
     with torch.cuda.device(xs.device):
         rc = lib.hns_critic_train_grad(C.byref(net), C.byref(b), D, A, K, float(clip_param), LOSSES[loss], float(huber_delta), C.byref(grd),
                                        scal[0:].data_ptr(), scal[1:].data_ptr(), scal[2:].data_ptr(), values.data_ptr(), ws.data_ptr(), nbytes, st)
-    PT.check(rc, "hns_critic_train_grad")
+    abi.check(rc, "hns_critic_train_grad")
     return CriticLoss(scal[0], scal[1], scal[2], values)
 
 

@@ -262,11 +262,6 @@ __global__ __launch_bounds__(kGaeThreads) void hns_rollout_normalise_kernel(Norm
 
 namespace {
 
-int gae_fail(const std::string &m) {
-    hns_set_error("hns_gae: " + m);
-    return HNS_ERR_INVALID_ARG;
-}
-
 template <bool D, bool M>
 void launch_gae(bool staged, int grid, const hns::GaeArgs &a, hipStream_t st) {
     if (staged) hipLaunchKernelGGL((hns::hns_gae_staged_kernel<D, M>), dim3(grid), dim3(hns::kGaeThreads), 0, st, a);
@@ -282,17 +277,18 @@ extern "C" {
 int hns_gae(const float *reward, const float *value, const void *done, const float *next_value, int64_t n, int64_t t, int64_t k, int64_t kd,
             int32_t layout, int32_t done_dtype, double gamma, double lambda, const float *scale, const float *shift, const float *success, int64_t m,
             float *advantages, float *returns, double *moments, double *workspace, void *stream) {
-    if (!reward || !value || !done || !next_value || !advantages || !returns) return gae_fail("null array pointer");
-    if (n < 1 || t < 1 || k < 1) return gae_fail("n, t and k must be >= 1");
-    if (kd != 1 && kd != k) return gae_fail("kd (done's trailing size) must be 1 or k");
+    const char *fn = "hns_gae";
+    if (!reward || !value || !done || !next_value || !advantages || !returns) return hns_fail(fn, "null array pointer");
+    if (n < 1 || t < 1 || k < 1) return hns_fail(fn, "n, t and k must be >= 1");
+    if (kd != 1 && kd != k) return hns_fail(fn, "kd (done's trailing size) must be 1 or k");
     if (n > (int64_t)1 << 31 || t > (int64_t)1 << 31 || k > (int64_t)1 << 31 || n * k > ((int64_t)1 << 31) || n * t * k > ((int64_t)1 << 40))
-        return gae_fail("shape too large");
-    if (layout != HNS_GAE_BATCH_MAJOR && layout != HNS_GAE_TIME_MAJOR) return gae_fail("layout must be HNS_GAE_BATCH_MAJOR or HNS_GAE_TIME_MAJOR");
-    if (done_dtype != HNS_GAE_DONE_U8 && done_dtype != HNS_GAE_DONE_F32) return gae_fail("done_dtype must be HNS_GAE_DONE_U8 or HNS_GAE_DONE_F32");
-    if (!scale != !shift) return gae_fail("scale and shift go together (both NULL or both device scalars)");
-    if (m < 0 || (m > 0 && !success)) return gae_fail("success: m >= 0 values, non-NULL when m > 0");
-    if (moments && !workspace) return gae_fail("moments need a workspace of HNS_GAE_WORKSPACE_DOUBLES doubles");
-    if (!(gamma == gamma) || !(lambda == lambda)) return gae_fail("gamma and lambda must be numbers");
+        return hns_fail(fn, "shape too large");
+    if (layout != HNS_GAE_BATCH_MAJOR && layout != HNS_GAE_TIME_MAJOR) return hns_fail(fn, "layout must be HNS_GAE_BATCH_MAJOR or HNS_GAE_TIME_MAJOR");
+    if (done_dtype != HNS_GAE_DONE_U8 && done_dtype != HNS_GAE_DONE_F32) return hns_fail(fn, "done_dtype must be HNS_GAE_DONE_U8 or HNS_GAE_DONE_F32");
+    if (!scale != !shift) return hns_fail(fn, "scale and shift go together (both NULL or both device scalars)");
+    if (m < 0 || (m > 0 && !success)) return hns_fail(fn, "success: m >= 0 values, non-NULL when m > 0");
+    if (moments && !workspace) return hns_fail(fn, "moments need a workspace of HNS_GAE_WORKSPACE_DOUBLES doubles");
+    if (!(gamma == gamma) || !(lambda == lambda)) return hns_fail(fn, "gamma and lambda must be numbers");
     hns::GaeArgs a{};
     a.reward = reward; a.value = value; a.next_value = next_value; a.done = done; a.scale = scale; a.shift = shift;
     a.adv = advantages; a.ret = returns; a.partial = workspace; a.success = success; a.m = m;

@@ -17,6 +17,15 @@ typedef void (*hns_step_fn)(const hns::Params *, const float *, float *, float *
 
 void hns_set_error(const std::string &m);
 
+// an entry point's refusal: "<fn>: <msg>" as hns_last_error, HNS_ERR_INVALID_ARG as its return value
+inline int hns_fail(const char *fn, const std::string &m) {
+    hns_set_error(std::string(fn) + ": " + m);
+    return HNS_ERR_INVALID_ARG;
+}
+
+// true iff `p` is a multiple of `n` bytes (n a power of two)
+inline bool hns_aligned(const void *p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
+
 // trajectory-predictor binding (hns_tp.hip)
 struct hns_tp_state {
     hns_tp_buffers buf;

@@ -84,17 +84,6 @@ inline int info_groups(long long rows) {
 
 }  // namespace hns
 
-namespace {
-
-int info_fail(const std::string &m) {
-    hns_set_error("hns_learner_info: " + m);
-    return HNS_ERR_INVALID_ARG;
-}
-
-bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-}  // namespace
-
 extern "C" {
 
 size_t hns_learner_info_workspace_bytes(long long rows) {
@@ -104,18 +93,19 @@ size_t hns_learner_info_workspace_bytes(long long rows) {
 
 int hns_learner_info(const float *action, const int64_t action_stride[2], long long rows, int act_dim, const float *table, int minibatches,
                      int columns, float *out, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!action || !action_stride || !table || !out || !workspace) return info_fail("null pointer (action, action_stride, table, out, workspace)");
-    if (!aligned(action, 4) || !aligned(table, 4) || !aligned(out, 4)) return info_fail("misaligned pointer: action, table and out hold fp32 values");
-    if (!aligned(workspace, 8)) return info_fail("misaligned pointer: the workspace holds fp64 partials (8-byte aligned)");
-    if (rows < 1) return info_fail("rows must be >= 1");
-    if (act_dim < 1 || act_dim > hns::kInfoMaxActDim) return info_fail("act_dim outside [1, 8]");
-    if (minibatches < 1) return info_fail("minibatches must be >= 1");
-    if (columns < 1 || columns > hns::kInfoMaxColumns) return info_fail("columns outside [1, 16]");
-    if (action_stride[0] < 0 || action_stride[1] < 0) return info_fail("action strides must be >= 0");
-    if (workspace_bytes < hns_learner_info_workspace_bytes(rows)) return info_fail("workspace shorter than hns_learner_info_workspace_bytes(rows)");
+    const char *fn = "hns_learner_info";
+    if (!action || !action_stride || !table || !out || !workspace) return hns_fail(fn, "null pointer (action, action_stride, table, out, workspace)");
+    if (!hns_aligned(action, 4) || !hns_aligned(table, 4) || !hns_aligned(out, 4)) return hns_fail(fn, "misaligned pointer: action, table and out hold fp32 values");
+    if (!hns_aligned(workspace, 8)) return hns_fail(fn, "misaligned pointer: the workspace holds fp64 partials (8-byte aligned)");
+    if (rows < 1) return hns_fail(fn, "rows must be >= 1");
+    if (act_dim < 1 || act_dim > hns::kInfoMaxActDim) return hns_fail(fn, "act_dim outside [1, 8]");
+    if (minibatches < 1) return hns_fail(fn, "minibatches must be >= 1");
+    if (columns < 1 || columns > hns::kInfoMaxColumns) return hns_fail(fn, "columns outside [1, 16]");
+    if (action_stride[0] < 0 || action_stride[1] < 0) return hns_fail(fn, "action strides must be >= 0");
+    if (workspace_bytes < hns_learner_info_workspace_bytes(rows)) return hns_fail(fn, "workspace shorter than hns_learner_info_workspace_bytes(rows)");
     const int groups = hns::info_groups(rows);
     const long long s0 = action_stride[0], s1 = action_stride[1];
-    const bool vec4 = act_dim == 4 && s1 == 1 && s0 % 4 == 0 && aligned(action, 16);
+    const bool vec4 = act_dim == 4 && s1 == 1 && s0 % 4 == 0 && hns_aligned(action, 16);
     const hipStream_t st = static_cast<hipStream_t>(stream);
     double *partial = static_cast<double *>(workspace);
     if (vec4) hipLaunchKernelGGL(hns::hns_learner_norm_kernel<true>, dim3(groups), dim3(hns::kInfoThreads), 0, st, action, s0, s1, rows, act_dim, partial);

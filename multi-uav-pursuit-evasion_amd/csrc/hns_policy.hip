@@ -391,22 +391,15 @@ __global__ void hns_policy_bump_kernel(unsigned long long *counter) { counter[0]
 
 namespace {
 
-int pol_fail(const char *fn, const std::string &m) {
-    hns_set_error(std::string(fn) + ": " + m);
-    return HNS_ERR_INVALID_ARG;
-}
-
-bool pol_aligned(const void *p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
 int pol_net(const char *fn, const hns_policy_net *n, int D, int has_others, bool actor, hns::PolNetSrc &s) {
-    if (!n) return pol_fail(fn, "null network");
+    if (!n) return hns_fail(fn, "null network");
     const float *req[] = {n->embed_self_w, n->embed_self_b, n->embed_cyl_w, n->embed_cyl_b, n->ln_w, n->ln_b, n->in_proj_w, n->in_proj_b,
                           n->out_proj_w, n->out_proj_b, n->linear1_w, n->linear1_b, n->linear2_w, n->linear2_b, n->norm1_w, n->norm1_b,
                           n->norm2_w, n->norm2_b, n->head_w, n->head_b};
     for (const float *p : req)
-        if (!p || !pol_aligned(p, 4)) return pol_fail(fn, "every parameter pointer must be a non-NULL fp32 array");
-    if (has_others && (!n->embed_others_w || !n->embed_others_b)) return pol_fail(fn, "state_others embedding missing (num_agents > 1)");
-    if (actor && !n->log_std) return pol_fail(fn, "the actor needs log_std");
+        if (!p || !hns_aligned(p, 4)) return hns_fail(fn, "every parameter pointer must be a non-NULL fp32 array");
+    if (has_others && (!n->embed_others_w || !n->embed_others_b)) return hns_fail(fn, "state_others embedding missing (num_agents > 1)");
+    if (actor && !n->log_std) return hns_fail(fn, "the actor needs log_std");
     s.ew[0] = n->embed_self_w; s.eb[0] = n->embed_self_b;
     s.ew[1] = has_others ? n->embed_others_w : nullptr; s.eb[1] = has_others ? n->embed_others_b : nullptr;
     s.ew[2] = n->embed_cyl_w; s.eb[2] = n->embed_cyl_b;
@@ -429,9 +422,9 @@ size_t hns_policy_packed_bytes(int32_t self_dim) {
 
 int hns_policy_pack(const hns_policy_net *actor, const hns_policy_net *critic, int32_t self_dim, int32_t num_agents, void *packed, void *stream) {
     const char *fn = "hns_policy_pack";
-    if (self_dim < 1 || self_dim > hns::kPolMaxSelf) return pol_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kPolMaxSelf) + "]");
-    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return pol_fail(fn, "num_agents must be in [1, 7]");
-    if (!packed || !pol_aligned(packed, 16)) return pol_fail(fn, "packed image must be a 16-byte aligned device array");
+    if (self_dim < 1 || self_dim > hns::kPolMaxSelf) return hns_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kPolMaxSelf) + "]");
+    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return hns_fail(fn, "num_agents must be in [1, 7]");
+    if (!packed || !hns_aligned(packed, 16)) return hns_fail(fn, "packed image must be a 16-byte aligned device array");
     hns::PolNetSrc sa{}, sc{};
     int rc = pol_net(fn, actor, self_dim, num_agents > 1, true, sa);
     if (rc != HNS_OK) return rc;
@@ -446,26 +439,26 @@ int hns_policy_pack(const hns_policy_net *actor, const hns_policy_net *critic, i
 int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
                        int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
     const char *fn = "hns_policy_forward";
-    if (!packed || !io || !pol_aligned(packed, 16)) return pol_fail(fn, "null or misaligned packed image / io");
-    if (self_dim < 1 || self_dim > hns::kPolMaxSelf) return pol_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kPolMaxSelf) + "]");
-    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return pol_fail(fn, "num_agents must be in [1, 7]");
-    if (num_cylinders < 1 || num_cylinders > HNS_MAX_CYLINDERS) return pol_fail(fn, "num_cylinders must be in [1, 16]");
-    if (num_envs < 1 || num_envs > ((int64_t)1 << 31) / HNS_MAX_AGENTS) return pol_fail(fn, "num_envs must be in [1, 2^31 / 7]");
-    if (flags & ~(HNS_POLICY_DETERMINISTIC | HNS_POLICY_VALUE_ONLY)) return pol_fail(fn, "unknown flag");
+    if (!packed || !io || !hns_aligned(packed, 16)) return hns_fail(fn, "null or misaligned packed image / io");
+    if (self_dim < 1 || self_dim > hns::kPolMaxSelf) return hns_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kPolMaxSelf) + "]");
+    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return hns_fail(fn, "num_agents must be in [1, 7]");
+    if (num_cylinders < 1 || num_cylinders > HNS_MAX_CYLINDERS) return hns_fail(fn, "num_cylinders must be in [1, 16]");
+    if (num_envs < 1 || num_envs > ((int64_t)1 << 31) / HNS_MAX_AGENTS) return hns_fail(fn, "num_envs must be in [1, 2^31 / 7]");
+    if (flags & ~(HNS_POLICY_DETERMINISTIC | HNS_POLICY_VALUE_ONLY)) return hns_fail(fn, "unknown flag");
     const bool value_only = flags & HNS_POLICY_VALUE_ONLY, det = flags & HNS_POLICY_DETERMINISTIC;
-    if (!io->obs_self || !io->obs_cylinders || (num_agents > 1 && !io->obs_others)) return pol_fail(fn, "observation pointer missing");
-    if (!pol_aligned(io->obs_self, 4) || !pol_aligned(io->obs_cylinders, 4) || (io->obs_others && !pol_aligned(io->obs_others, 4)))
-        return pol_fail(fn, "misaligned observation");
+    if (!io->obs_self || !io->obs_cylinders || (num_agents > 1 && !io->obs_others)) return hns_fail(fn, "observation pointer missing");
+    if (!hns_aligned(io->obs_self, 4) || !hns_aligned(io->obs_cylinders, 4) || (io->obs_others && !hns_aligned(io->obs_others, 4)))
+        return hns_fail(fn, "misaligned observation");
     for (int k = 0; k < 2; ++k)
-        if (io->self_stride[k] < 0) return pol_fail(fn, "negative stride");
+        if (io->self_stride[k] < 0) return hns_fail(fn, "negative stride");
     for (int k = 0; k < 3; ++k)
-        if (io->others_stride[k] < 0 || io->cyl_stride[k] < 0) return pol_fail(fn, "negative stride");
-    if (!io->value || !pol_aligned(io->value, 4)) return pol_fail(fn, "value output missing or misaligned");
+        if (io->others_stride[k] < 0 || io->cyl_stride[k] < 0) return hns_fail(fn, "negative stride");
+    if (!io->value || !hns_aligned(io->value, 4)) return hns_fail(fn, "value output missing or misaligned");
     if (!value_only) {
-        if (!io->action || !io->log_prob || !pol_aligned(io->action, 4) || !pol_aligned(io->log_prob, 4) || (io->loc && !pol_aligned(io->loc, 4)))
-            return pol_fail(fn, "action / log_prob outputs missing or misaligned");
-        if (!det && !io->eps && (!counter || !pol_aligned(counter, 8))) return pol_fail(fn, "sampling without eps needs the device call counter");
-        if (io->eps && !pol_aligned(io->eps, 4)) return pol_fail(fn, "misaligned eps");
+        if (!io->action || !io->log_prob || !hns_aligned(io->action, 4) || !hns_aligned(io->log_prob, 4) || (io->loc && !hns_aligned(io->loc, 4)))
+            return hns_fail(fn, "action / log_prob outputs missing or misaligned");
+        if (!det && !io->eps && (!counter || !hns_aligned(counter, 8))) return hns_fail(fn, "sampling without eps needs the device call counter");
+        if (io->eps && !hns_aligned(io->eps, 4)) return hns_fail(fn, "misaligned eps");
     }
     hns::PolArgs a{};
     a.img = static_cast<const float *>(packed);

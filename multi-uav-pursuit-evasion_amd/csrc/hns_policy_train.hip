@@ -1,5 +1,5 @@
 // hns_policy_train.hip — the MAPPO critic's and actor's updates on the device: value loss / PPO surrogate, backward pass of the
-// PartialAttentionEncoder, gradient-norm clip, Adam.
+// PartialAttentionEncoder, total gradient norm.
 //
 // Reference: MAPPOPolicy.update_critic (omni_drones/learning/mappo.py:326-352) on make_critic's network at cfg/algo/mappo.yaml's defaults
 // (critic_input obs, no rnn): values = v_out(encoder(obs)); clipped = b_values + clamp(values - b_values, +-clip); value_loss = max(mean loss(ret,
@@ -19,8 +19,7 @@
 //                              (column sums of dy).
 //   hns_critic_reduce_kernel : every gradient value = the fp64 sum of its partials in index order, written in the PyTorch layout; per-block sums
 //                              of squares;  hns_critic_norm_kernel adds those in order: the total gradient norm.
-//   hns_adam_clipped_kernel  : clip_grad_norm_'s scaling and torch.optim.Adam's single-tensor statements over any number of tensors; the device
-//                              step counter is bumped once by hns_adam_bump_kernel.
+// The clip and the Adam step that follow are hns_adam.hip's.
 // The actor (MAPPOPolicy.update_actor, mappo.py:271-324; DiagGaussian head fc_mean 128 -> 4 and a free log_std[4]) is the same
 // encoder with a four-output head, selected by the tile kernel's HEAD template parameter.  The clipped surrogate's backward weight is per row, so
 // ONE pass over the tiles gives the loss partials and the gradients:
@@ -994,58 +993,9 @@ __global__ __launch_bounds__(256) void hns_critic_norm_kernel(const double *bloc
     }
 }
 
-constexpr int kCAdamMax = 64;                // tensors per launch (the descriptors travel in the kernel arguments)
-struct CAdamArgs {
-    float *p[kCAdamMax], *g[kCAdamMax], *m[kCAdamMax], *v[kCAdamMax];
-    long long n[kCAdamMax];
-    int count, clip;
-    const float *step, *norm;
-    float max_norm;
-    double lr, beta1, beta2, eps;
-};
-
-// clip_grad_norm_: g *= min(max_norm / (norm + 1e-6), 1) (torch: reciprocal, then times max_norm), then hns_tp_adam_kernel's statements with
-// step = *step + 1 (the counter itself is bumped by hns_adam_bump_kernel after every tensor is done)
-__global__ __launch_bounds__(256) void hns_adam_clipped_kernel(const CAdamArgs a) {
-    const float step = a.step[0] + 1.0f;
-    float coef = 1.0f;
-    if (a.clip) {
-        coef = (1.0f / (a.norm[0] + 1e-6f)) * a.max_norm;
-        coef = coef > 1.0f ? 1.0f : coef;                       // (a NaN norm stays NaN, as torch's clamp)
-    }
-    const double bc1 = 1.0 - pow(a.beta1, (double)step), bc2 = 1.0 - pow(a.beta2, (double)step);
-    const float w1 = (float)(1.0 - a.beta1), b2 = (float)a.beta2, w2 = (float)(1.0 - a.beta2);
-    const float ss = (float)(-(a.lr / bc1)), bc2s = (float)sqrt(bc2), eps = (float)a.eps;
-    for (int k = 0; k < a.count; ++k) {
-        float *p = a.p[k], *m = a.m[k], *v = a.v[k], *g = a.g[k];
-        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.n[k]; i += (long long)gridDim.x * 256) {
-            float gi = g[i];
-            if (a.clip) {
-                gi = gi * coef;
-                g[i] = gi;
-            }
-            const float mi = __builtin_fmaf(w1, gi - m[i], m[i]);
-            const float vi = __builtin_fmaf(w2 * gi, gi, v[i] * b2);
-            const float den = __builtin_sqrtf(vi) / bc2s + eps;
-            m[i] = mi;
-            v[i] = vi;
-            p[i] = p[i] + (ss * mi) / den;
-        }
-    }
-}
-
-__global__ void hns_adam_bump_kernel(float *step) { step[0] = step[0] + 1.0f; }
-
 }  // namespace hns
 
 namespace {
-
-int ct_fail(const char *fn, const std::string &m) {
-    hns_set_error(std::string(fn) + ": " + m);
-    return HNS_ERR_INVALID_ARG;
-}
-
-bool ct_aligned(const void *p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
 
 size_t ct_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -1082,13 +1032,13 @@ bool ct_plan(int64_t rows, int32_t D, int32_t A, int32_t K, CtPlan &p, int heads
 
 template <typename Batch>
 int ct_check_shape(const char *fn, const Batch &b, int32_t self_dim, int32_t num_agents, int32_t num_cylinders) {
-    if (self_dim < 1 || self_dim > hns::kCtMaxSelf) return ct_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kCtMaxSelf) + "]");
-    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return ct_fail(fn, "num_agents must be in [1, 7]");
-    if (num_cylinders < 1 || num_cylinders > HNS_MAX_CYLINDERS) return ct_fail(fn, "num_cylinders must be in [1, 16]");
-    if (b.batch < 1) return ct_fail(fn, "batch must be >= 1 (the mean over an empty minibatch is NaN)");
-    if (b.num_envs < 1 || b.num_steps < 1 || b.num_envs > ((int64_t)1 << 40) / b.num_steps) return ct_fail(fn, "num_envs, num_steps must be >= 1");
-    if (b.batch > ((int64_t)1 << 31) / HNS_MAX_AGENTS) return ct_fail(fn, "batch too large");
-    if (!b.index && b.batch > b.num_envs * b.num_steps) return ct_fail(fn, "batch exceeds the env-steps of the rollout (no index)");
+    if (self_dim < 1 || self_dim > hns::kCtMaxSelf) return hns_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kCtMaxSelf) + "]");
+    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return hns_fail(fn, "num_agents must be in [1, 7]");
+    if (num_cylinders < 1 || num_cylinders > HNS_MAX_CYLINDERS) return hns_fail(fn, "num_cylinders must be in [1, 16]");
+    if (b.batch < 1) return hns_fail(fn, "batch must be >= 1 (the mean over an empty minibatch is NaN)");
+    if (b.num_envs < 1 || b.num_steps < 1 || b.num_envs > ((int64_t)1 << 40) / b.num_steps) return hns_fail(fn, "num_envs, num_steps must be >= 1");
+    if (b.batch > ((int64_t)1 << 31) / HNS_MAX_AGENTS) return hns_fail(fn, "batch too large");
+    if (!b.index && b.batch > b.num_envs * b.num_steps) return hns_fail(fn, "batch exceeds the env-steps of the rollout (no index)");
     return HNS_OK;
 }
 
@@ -1103,18 +1053,18 @@ int ct_check_shape(const char *fn, const Batch &b, int32_t self_dim, int32_t num
 int ct_bind_net(const char *fn, const hns_policy_net &net, const hns_policy_grads &grads, bool others, int heads, hns::CtNet &n, hns::CtGrad &g) {
     bool ok = true;
 #define X(f, m)                                                                                      \
-    ok = ok && net.f && grads.f && ct_aligned(net.f, 16) && ct_aligned(grads.f, 4);                  \
+    ok = ok && net.f && grads.f && hns_aligned(net.f, 16) && hns_aligned(grads.f, 4);                  \
     n.m = net.f;                                                                                     \
     g.m = grads.f;
     HNS_CT_FIELDS(X)
 #undef X
     if (heads > 1) {
-        ok = ok && net.log_std && grads.log_std && ct_aligned(net.log_std, 16) && ct_aligned(grads.log_std, 4);
+        ok = ok && net.log_std && grads.log_std && hns_aligned(net.log_std, 16) && hns_aligned(grads.log_std, 4);
         g.log_std = grads.log_std;
     }
-    if (!ok) return ct_fail(fn, "every parameter must be a non-NULL 16-byte aligned fp32 array, every gradient a non-NULL fp32 array");
-    if (others && (!net.embed_others_w || !net.embed_others_b || !grads.embed_others_w || !grads.embed_others_b || !ct_aligned(net.embed_others_b, 16)))
-        return ct_fail(fn, "state_others embedding (parameter or gradient) missing or misaligned (num_agents > 1)");
+    if (!ok) return hns_fail(fn, "every parameter must be a non-NULL 16-byte aligned fp32 array, every gradient a non-NULL fp32 array");
+    if (others && (!net.embed_others_w || !net.embed_others_b || !grads.embed_others_w || !grads.embed_others_b || !hns_aligned(net.embed_others_b, 16)))
+        return hns_fail(fn, "state_others embedding (parameter or gradient) missing or misaligned (num_agents > 1)");
     n.ew[1] = others ? net.embed_others_w : nullptr; n.eb[1] = others ? net.embed_others_b : nullptr;
     g.ew[1] = others ? grads.embed_others_w : nullptr; g.eb[1] = others ? grads.embed_others_b : nullptr;
     return HNS_OK;
@@ -1122,12 +1072,12 @@ int ct_bind_net(const char *fn, const hns_policy_net &net, const hns_policy_grad
 
 template <typename Batch>
 int ct_check_obs(const char *fn, const Batch &b, bool others) {
-    if (!b.obs_self || !b.obs_cylinders || (others && !b.obs_others)) return ct_fail(fn, "observation pointer missing");
-    if (!ct_aligned(b.obs_self, 4) || !ct_aligned(b.obs_cylinders, 4) || (b.obs_others && !ct_aligned(b.obs_others, 4))) return ct_fail(fn, "misaligned observation");
+    if (!b.obs_self || !b.obs_cylinders || (others && !b.obs_others)) return hns_fail(fn, "observation pointer missing");
+    if (!hns_aligned(b.obs_self, 4) || !hns_aligned(b.obs_cylinders, 4) || (b.obs_others && !hns_aligned(b.obs_others, 4))) return hns_fail(fn, "misaligned observation");
     for (int k = 0; k < 3; ++k)
-        if (b.self_stride[k] < 0) return ct_fail(fn, "negative stride");
+        if (b.self_stride[k] < 0) return hns_fail(fn, "negative stride");
     for (int k = 0; k < 4; ++k)
-        if (b.others_stride[k] < 0 || b.cyl_stride[k] < 0) return ct_fail(fn, "negative stride");
+        if (b.others_stride[k] < 0 || b.cyl_stride[k] < 0) return hns_fail(fn, "negative stride");
     return HNS_OK;
 }
 
@@ -1136,14 +1086,14 @@ int ct_check_obs(const char *fn, const Batch &b, bool others) {
 template <typename Batch>
 int ct_plan_call(const char *fn, const Batch &b, std::initializer_list<const float *> outs, void *workspace, size_t workspace_bytes, int32_t self_dim,
                  int32_t num_agents, int32_t num_cylinders, int heads, CtPlan &p, hns::CtArgs &a) {
-    if (b.index && !ct_aligned(b.index, 8)) return ct_fail(fn, "misaligned index");
-    bool ok = ct_aligned(workspace, 256);
-    for (const float *o : outs) ok = ok && ct_aligned(o, 4);
-    if (!ok) return ct_fail(fn, "misaligned output (scalars 4 bytes, workspace 256)");
+    if (b.index && !hns_aligned(b.index, 8)) return hns_fail(fn, "misaligned index");
+    bool ok = hns_aligned(workspace, 256);
+    for (const float *o : outs) ok = ok && hns_aligned(o, 4);
+    if (!ok) return hns_fail(fn, "misaligned output (scalars 4 bytes, workspace 256)");
     const int64_t rows = b.batch * num_agents;
-    if (!ct_plan(rows, self_dim, num_agents, num_cylinders, p, heads)) return ct_fail(fn, "invalid shape");
+    if (!ct_plan(rows, self_dim, num_agents, num_cylinders, p, heads)) return hns_fail(fn, "invalid shape");
     if (workspace_bytes < p.total)
-        return ct_fail(fn, heads > 1 ? "workspace too small (hns_actor_train_workspace_bytes)" : "workspace too small (hns_critic_train_workspace_bytes)");
+        return hns_fail(fn, heads > 1 ? "workspace too small (hns_actor_train_workspace_bytes)" : "workspace too small (hns_critic_train_workspace_bytes)");
 
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     a.img = reinterpret_cast<float *>(ws + p.o_img);
@@ -1199,16 +1149,16 @@ int hns_critic_train_grad(const hns_policy_net *critic, const hns_critic_batch *
                           float clip_param, int32_t loss_kind, float huber_delta, const hns_policy_grads *grads, float *value_loss,
                           float *explained_var, float *grad_norm, float *values, void *workspace, size_t workspace_bytes, void *stream) {
     const char *fn = "hns_critic_train_grad";
-    if (!critic || !batch || !grads || !value_loss || !explained_var || !grad_norm || !workspace) return ct_fail(fn, "null pointer");
+    if (!critic || !batch || !grads || !value_loss || !explained_var || !grad_norm || !workspace) return hns_fail(fn, "null pointer");
     if (int rc = ct_check_shape(fn, *batch, self_dim, num_agents, num_cylinders)) return rc;
-    if (loss_kind != HNS_CRITIC_LOSS_HUBER && loss_kind != HNS_CRITIC_LOSS_MSE) return ct_fail(fn, "loss_kind must be HNS_CRITIC_LOSS_HUBER or HNS_CRITIC_LOSS_MSE");
-    if (!(clip_param >= 0.0f) || (loss_kind == HNS_CRITIC_LOSS_HUBER && !(huber_delta > 0.0f))) return ct_fail(fn, "clip_param >= 0, huber_delta > 0");
+    if (loss_kind != HNS_CRITIC_LOSS_HUBER && loss_kind != HNS_CRITIC_LOSS_MSE) return hns_fail(fn, "loss_kind must be HNS_CRITIC_LOSS_HUBER or HNS_CRITIC_LOSS_MSE");
+    if (!(clip_param >= 0.0f) || (loss_kind == HNS_CRITIC_LOSS_HUBER && !(huber_delta > 0.0f))) return hns_fail(fn, "clip_param >= 0, huber_delta > 0");
     hns::CtArgs a{};
     hns::CtGrad g{};
     CtPlan p;
     if (int rc = ct_bind_net(fn, *critic, *grads, num_agents > 1, 1, a.net, g)) return rc;
     if (int rc = ct_check_obs(fn, *batch, num_agents > 1)) return rc;
-    if (!batch->b_values || !batch->b_returns || !ct_aligned(batch->b_values, 4) || !ct_aligned(batch->b_returns, 4)) return ct_fail(fn, "b_values / b_returns missing or misaligned");
+    if (!batch->b_values || !batch->b_returns || !hns_aligned(batch->b_values, 4) || !hns_aligned(batch->b_returns, 4)) return hns_fail(fn, "b_values / b_returns missing or misaligned");
     if (int rc = ct_plan_call(fn, *batch, {value_loss, explained_var, grad_norm, values}, workspace, workspace_bytes, self_dim, num_agents, num_cylinders, 1, p, a)) return rc;
     float *ctl = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + p.o_ctl);
     a.bval = batch->b_values; a.bret = batch->b_returns;
@@ -1242,17 +1192,17 @@ int hns_actor_train_grad(const hns_policy_net *actor, const hns_actor_batch *bat
                          double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
                          float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream) {
     const char *fn = "hns_actor_train_grad";
-    if (!actor || !batch || !grads || !policy_loss || !entropy || !ess || !grad_norm || !workspace) return ct_fail(fn, "null pointer");
+    if (!actor || !batch || !grads || !policy_loss || !entropy || !ess || !grad_norm || !workspace) return hns_fail(fn, "null pointer");
     if (int rc = ct_check_shape(fn, *batch, self_dim, num_agents, num_cylinders)) return rc;
-    if (!(clip_param >= 0.0) || !std::isfinite(clip_param) || !std::isfinite(entropy_coef)) return ct_fail(fn, "clip_param >= 0 and a finite entropy_coef");
+    if (!(clip_param >= 0.0) || !std::isfinite(clip_param) || !std::isfinite(entropy_coef)) return hns_fail(fn, "clip_param >= 0 and a finite entropy_coef");
     hns::CtArgs a{};
     hns::CtGrad g{};
     CtPlan p;
     if (int rc = ct_bind_net(fn, *actor, *grads, num_agents > 1, hns::kActDim, a.net, g)) return rc;
     if (int rc = ct_check_obs(fn, *batch, num_agents > 1)) return rc;
-    if (!batch->action || !batch->log_probs_old || !batch->advantages || !ct_aligned(batch->action, 4) || !ct_aligned(batch->log_probs_old, 4) ||
-        !ct_aligned(batch->advantages, 4))
-        return ct_fail(fn, "action / log_probs_old / advantages missing or misaligned");
+    if (!batch->action || !batch->log_probs_old || !batch->advantages || !hns_aligned(batch->action, 4) || !hns_aligned(batch->log_probs_old, 4) ||
+        !hns_aligned(batch->advantages, 4))
+        return hns_fail(fn, "action / log_probs_old / advantages missing or misaligned");
     if (int rc = ct_plan_call(fn, *batch, {policy_loss, entropy, ess, grad_norm, log_probs}, workspace, workspace_bytes, self_dim, num_agents, num_cylinders,
                               hns::kActDim, p, a))
         return rc;
@@ -1271,40 +1221,6 @@ int hns_actor_train_grad(const hns_policy_net *actor, const hns_actor_batch *bat
                        actor->log_std, policy_loss, entropy, ess);
     HNS_CHECK_HIP(hipGetLastError());
     return ct_launch_tail(st, a, p, g, workspace, hns::kActDim, -entropy_coef, grad_norm);
-}
-
-int hns_adam_clipped(const hns_adam_tensor *tensors, int32_t count, float *step, const float *total_norm, double max_norm, double lr, double beta1,
-                     double beta2, double eps, void *stream) {
-    const char *fn = "hns_adam_clipped";
-    if (!tensors || !step || count < 1) return ct_fail(fn, "at least one tensor and a device step counter");
-    if (!ct_aligned(step, 4) || (total_norm && !ct_aligned(total_norm, 4))) return ct_fail(fn, "misaligned step counter / norm");
-    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(max_norm >= 0.0))
-        return ct_fail(fn, "lr >= 0, 0 <= beta < 1, eps >= 0, max_norm >= 0");
-    for (int k = 0; k < count; ++k) {
-        const hns_adam_tensor &t = tensors[k];
-        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq || t.numel < 0) return ct_fail(fn, "tensor with a NULL array or numel < 0");
-        if (!ct_aligned(t.param, 4) || !ct_aligned(t.grad, 4) || !ct_aligned(t.exp_avg, 4) || !ct_aligned(t.exp_avg_sq, 4)) return ct_fail(fn, "misaligned fp32 array");
-    }
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    for (int k0 = 0; k0 < count; k0 += hns::kCAdamMax) {
-        hns::CAdamArgs a{};
-        a.count = std::min<int>(hns::kCAdamMax, count - k0);
-        a.clip = total_norm != nullptr && std::isfinite(max_norm);
-        a.step = step; a.norm = total_norm; a.max_norm = (float)max_norm;
-        a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-        long long most = 1;
-        for (int k = 0; k < a.count; ++k) {
-            const hns_adam_tensor &t = tensors[k0 + k];
-            a.p[k] = t.param; a.g[k] = t.grad; a.m[k] = t.exp_avg; a.v[k] = t.exp_avg_sq; a.n[k] = t.numel;
-            most = std::max<long long>(most, t.numel);
-        }
-        const int grid = (int)std::min<long long>((most + 255) / 256, 256);
-        hipLaunchKernelGGL(hns::hns_adam_clipped_kernel, dim3(grid), dim3(256), 0, st, a);
-        HNS_CHECK_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(hns::hns_adam_bump_kernel, dim3(1), dim3(1), 0, st, step);
-    HNS_CHECK_HIP(hipGetLastError());
-    return HNS_OK;
 }
 
 }  // extern "C"

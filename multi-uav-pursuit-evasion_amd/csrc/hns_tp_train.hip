@@ -1,4 +1,4 @@
-// hns_tp_train.hip — the trajectory predictor's training step on the device: loss and gradients of one minibatch, and the Adam update.
+// hns_tp_train.hip — the trajectory predictor's training step on the device: loss and gradients of one minibatch (the Adam step is hns_adam.hip's).
 //
 // Reference: MAPPOPolicy.update_TP (omni_drones/learning/mappo.py:252-268) driven by train_op (:405-441): TP_net (:572-589: LSTM(I -> 64, one
 // layer, zero initial state, gate order i, f, g, o) + Linear(64 -> 3F) + tanh) on a [B, T, I] minibatch, nn.MSELoss against [B, 3F], autograd
@@ -10,8 +10,6 @@
 //                          (unit, sequence) pairs in the same lanes, so the cell runs in registers.  dh_{t-1} = W_hh^T dA_t is summed over the
 //                          four waves' partial products in LDS in a fixed order.  Each workgroup writes its partial gradients to the workspace.
 //   hns_tp_grad_sum_kernel : one thread per gradient value sums the workgroups' partials in index order in fp64, writes b_ih and b_hh from the same sum.
-//   hns_tp_adam_kernel   : torch.optim.Adam's single-tensor statements over up to eight tensors in one workgroup (the device step counter is read
-//                          before a barrier and written after it, so the launch needs no host value and can be captured).
 // Arithmetic: every matrix product is v_mfma_f32_16x16x4_f32 (exact f32 products, one rounding per accumulation step); the activations use
 // the library's expf / tanhf.  Determinism: tiles go to workgroups by index, every sum has a fixed order, no float atomics — the same inputs
 // give the same bits on every run.  Workspace: kTrainMaxGroups partial-gradient rows at most, whatever B and T are.
@@ -34,7 +32,6 @@ constexpr int kTrainMaxGroups = 256;         // one workgroup per CU of an MI355
 constexpr int kTrainH = HNS_TP_HIDDEN;
 constexpr int kTrainG = 4 * kTrainH;         // gate rows
 constexpr int kTrainMaxT = 16, kTrainMaxI = 80, kTrainMaxF3 = 30;
-constexpr int kAdamThreads = 1024;
 
 struct TrainArgs {
     const float *x;                          // row r of the flattened [E, S]: x + (r / S) sE + (r % S) sS, a contiguous [T, I] block
@@ -332,53 +329,12 @@ __global__ __launch_bounds__(256) void hns_tp_grad_sum_kernel(const float *part,
     else o.loss[0] = (float)(acc * inv_n);
 }
 
-struct AdamArgs {
-    float *p[8];
-    const float *g[8];
-    float *m[8], *v[8];
-    long long n[8];
-    int count;
-    float *step;
-    double lr, beta1, beta2, eps;
-};
-
-// torch.optim.Adam, single-tensor path (amsgrad off, weight decay 0, maximize off), statement for statement with torch's CPU kernels:
-//   step += 1;  m = lerp(m, g, 1 - beta1) = fma(1 - beta1, g - m, m);  v = fma((1 - beta2) g, g, v beta2)
-//   bc1 = 1 - beta1^step, bc2 = 1 - beta2^step (double);  denom = sqrt(v) / f32(sqrt(bc2)) + f32(eps);  p = p + (f32(-lr / bc1) m) / denom
-__global__ __launch_bounds__(kAdamThreads) void hns_tp_adam_kernel(const AdamArgs a) {
-    const float step = a.step[0] + 1.0f;
-    __syncthreads();                                            // every thread has read the counter before it is written
-    if (threadIdx.x == 0) a.step[0] = step;
-    const double bc1 = 1.0 - pow(a.beta1, (double)step), bc2 = 1.0 - pow(a.beta2, (double)step);
-    const float w1 = (float)(1.0 - a.beta1), b2 = (float)a.beta2, w2 = (float)(1.0 - a.beta2);
-    const float ss = (float)(-(a.lr / bc1)), bc2s = (float)sqrt(bc2), eps = (float)a.eps;
-    for (int k = 0; k < a.count; ++k) {
-        float *p = a.p[k], *m = a.m[k], *v = a.v[k];
-        const float *g = a.g[k];
-        for (long long i = threadIdx.x; i < a.n[k]; i += kAdamThreads) {
-            const float gi = g[i];
-            const float mi = __builtin_fmaf(w1, gi - m[i], m[i]);
-            const float vi = __builtin_fmaf(w2 * gi, gi, v[i] * b2);
-            const float den = __builtin_sqrtf(vi) / bc2s + eps;
-            m[i] = mi;
-            v[i] = vi;
-            p[i] = p[i] + (ss * mi) / den;
-        }
-    }
-}
-
 }  // namespace hns
 
 namespace {
 
-int train_fail(const char *fn, const std::string &m) {
-    hns_set_error(std::string(fn) + ": " + m);
-    return HNS_ERR_INVALID_ARG;
-}
-
 long long train_groups(long long B) { return std::min<long long>((B + hns::kTrainTile - 1) / hns::kTrainTile, hns::kTrainMaxGroups); }
 long long train_partial(int I, int F3) { return (long long)hns::kTrainG * (I + hns::kTrainH + 1) + (long long)F3 * (hns::kTrainH + 1) + 1; }
-bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
 template <int NXC>
 hipError_t launch_grad(int grid, const hns::TrainArgs &a, hipStream_t st) {
@@ -402,23 +358,23 @@ int hns_tp_train_grad(const hns_tp_params *params, const float *x, int64_t num_e
                       int32_t history_step, int32_t input_dim, const float *y, const int64_t *index, int64_t batch, int32_t future_step,
                       const hns_tp_grads *grads, float *loss, void *workspace, size_t workspace_bytes, void *stream) {
     const char *fn = "hns_tp_train_grad";
-    if (!params || !grads || !x || !y || !loss || !workspace) return train_fail(fn, "null pointer");
+    if (!params || !grads || !x || !y || !loss || !workspace) return hns_fail(fn, "null pointer");
     const float *pw[6] = {params->w_ih, params->w_hh, params->b_ih, params->b_hh, params->w_fc, params->b_fc};
     float *gw[6] = {grads->w_ih, grads->w_hh, grads->b_ih, grads->b_hh, grads->w_fc, grads->b_fc};
     for (int k = 0; k < 6; ++k)
-        if (!pw[k] || !gw[k] || !aligned4(pw[k]) || !aligned4(gw[k])) return train_fail(fn, "parameter / gradient pointers must be non-NULL fp32 arrays");
-    if (!aligned4(x) || !aligned4(y) || !aligned4(loss) || (reinterpret_cast<uintptr_t>(workspace) & 15) ||
+        if (!pw[k] || !gw[k] || !hns_aligned(pw[k], 4) || !hns_aligned(gw[k], 4)) return hns_fail(fn, "parameter / gradient pointers must be non-NULL fp32 arrays");
+    if (!hns_aligned(x, 4) || !hns_aligned(y, 4) || !hns_aligned(loss, 4) || (reinterpret_cast<uintptr_t>(workspace) & 15) ||
         (index && (reinterpret_cast<uintptr_t>(index) & 7)))
-        return train_fail(fn, "misaligned array (x / y / loss 4 bytes, index 8, workspace 16)");
-    if (history_step < 1 || history_step > hns::kTrainMaxT) return train_fail(fn, "history_step must be in [1, 16]");
-    if (input_dim < 1 || input_dim > hns::kTrainMaxI) return train_fail(fn, "input_dim must be in [1, 80]");
-    if (future_step < 1 || 3 * future_step > hns::kTrainMaxF3) return train_fail(fn, "future_step must be in [1, 10]");
-    if (batch < 1) return train_fail(fn, "batch must be >= 1 (the mean over an empty batch is NaN)");
-    if (num_envs < 1 || num_steps < 1 || num_envs * num_steps >= ((int64_t)1 << 40)) return train_fail(fn, "num_envs, num_steps must be >= 1");
+        return hns_fail(fn, "misaligned array (x / y / loss 4 bytes, index 8, workspace 16)");
+    if (history_step < 1 || history_step > hns::kTrainMaxT) return hns_fail(fn, "history_step must be in [1, 16]");
+    if (input_dim < 1 || input_dim > hns::kTrainMaxI) return hns_fail(fn, "input_dim must be in [1, 80]");
+    if (future_step < 1 || 3 * future_step > hns::kTrainMaxF3) return hns_fail(fn, "future_step must be in [1, 10]");
+    if (batch < 1) return hns_fail(fn, "batch must be >= 1 (the mean over an empty batch is NaN)");
+    if (num_envs < 1 || num_steps < 1 || num_envs * num_steps >= ((int64_t)1 << 40)) return hns_fail(fn, "num_envs, num_steps must be >= 1");
     if (stride_step < (int64_t)history_step * input_dim || stride_env < stride_step * num_steps)
-        return train_fail(fn, "strides must keep the [T, I] blocks apart: stride_step >= T I, stride_env >= stride_step S");
-    if (!index && batch > num_envs * num_steps) return train_fail(fn, "batch exceeds the rows of x (no index)");
-    if (workspace_bytes < hns_tp_train_workspace_bytes(batch, input_dim, future_step)) return train_fail(fn, "workspace too small");
+        return hns_fail(fn, "strides must keep the [T, I] blocks apart: stride_step >= T I, stride_env >= stride_step S");
+    if (!index && batch > num_envs * num_steps) return hns_fail(fn, "batch exceeds the rows of x (no index)");
+    if (workspace_bytes < hns_tp_train_workspace_bytes(batch, input_dim, future_step)) return hns_fail(fn, "workspace too small");
     hns::TrainArgs a{};
     a.x = x; a.sE = stride_env; a.sS = stride_step; a.S = num_steps; a.rows = num_envs * num_steps;
     a.y = y; a.index = reinterpret_cast<const long long *>(index); a.B = batch;
@@ -441,25 +397,6 @@ int hns_tp_train_grad(const hns_tp_params *params, const float *x, int64_t num_e
     const hns::GradOut o{gw[0], gw[1], gw[2], gw[3], gw[4], gw[5], loss};
     hipLaunchKernelGGL(hns::hns_tp_grad_sum_kernel, dim3((a.P + 255) / 256), dim3(256), 0, st, static_cast<const float *>(workspace), grid, a.P,
                        input_dim, a.F3, 1.0 / n, o);
-    HNS_CHECK_HIP(hipGetLastError());
-    return HNS_OK;
-}
-
-int hns_tp_adam(const hns_tp_adam_tensor *tensors, int32_t count, float *step, double lr, double beta1, double beta2, double eps, void *stream) {
-    const char *fn = "hns_tp_adam";
-    if (!tensors || !step || count < 1 || count > 8) return train_fail(fn, "1 to 8 tensors and a device step counter");
-    if (!aligned4(step)) return train_fail(fn, "misaligned step counter");
-    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
-        return train_fail(fn, "lr >= 0, 0 <= beta < 1, eps >= 0");
-    hns::AdamArgs a{};
-    a.count = count; a.step = step; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-    for (int k = 0; k < count; ++k) {
-        const hns_tp_adam_tensor &t = tensors[k];
-        if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq || t.numel < 0) return train_fail(fn, "tensor with a NULL array or numel < 0");
-        if (!aligned4(t.param) || !aligned4(t.grad) || !aligned4(t.exp_avg) || !aligned4(t.exp_avg_sq)) return train_fail(fn, "misaligned fp32 array");
-        a.p[k] = t.param; a.g[k] = t.grad; a.m[k] = t.exp_avg; a.v[k] = t.exp_avg_sq; a.n[k] = t.numel;
-    }
-    hipLaunchKernelGGL(hns::hns_tp_adam_kernel, dim3(1), dim3(hns::kAdamThreads), 0, static_cast<hipStream_t>(stream), a);
     HNS_CHECK_HIP(hipGetLastError());
     return HNS_OK;
 }

@@ -215,7 +215,7 @@ class DeviceLearner:
             rc = lib.hns_learner_info(a.data_ptr(), (C.c_int64 * 2)(a.stride(0), a.stride(1)), a.shape[0], a.shape[1], table.data_ptr(),
                                       table.shape[0], table.shape[1], out.data_ptr(), ws.data_ptr(), ws.numel(),
                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        PT.check(rc, "hns_learner_info")
+        abi.check(rc, "hns_learner_info")
         return out
 
     # ---- checkpoints

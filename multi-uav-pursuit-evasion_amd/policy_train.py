@@ -1,16 +1,14 @@
 """What the MAPPO critic's and actor's updates share on the host side of csrc/hns_policy_train.hip: the checks of a minibatch read in place from
-the rollout, the preparation of a `hns_*_train_grad` call, the training restatement of the encoder and `ClippedAdam`.
+the rollout, the preparation of a `hns_*_train_grad` call, and the training restatement of the encoder.
 
 `critic_train` and `actor_train` keep what is their own — the reference's loss statements, their C call, their part of the cfg — and
 `learner` drives both.  `validate` and `prepare_call` take the network's word ("critic" / "actor") and its per-row tensors, so a refusal
 reads the same whichever update raised it.
 
-`ClippedAdam` is clip_grad_norm_ + torch.optim.Adam (amsgrad off, weight decay 0) in ONE launch of `hns_adam_clipped` over all tensors and a
-device-resident step counter; its state_dict is Adam's, both ways.  Every step bumps the parameters' version counters, so
-`policy.DevicePolicy` re-packs its operand image before the next forward pass.  A data-parallel caller all-reduces the `.grad` tensors and
-recomputes the norm between the two calls.  DESIGN.md §7.4-7.5."""
+`ClippedAdam` (optim's, re-exported here) is clip_grad_norm_ + torch.optim.Adam (amsgrad off, weight decay 0) with the device step every update
+shares.  Every step bumps the parameters' version counters, so `policy.DevicePolicy` re-packs its operand image before the next forward pass.  A
+data-parallel caller all-reduces the `.grad` tensors and recomputes the norm between the two calls.  DESIGN.md §7.4-7.5."""
 import ctypes as C
-import math
 
 import torch
 import torch.nn as nn
@@ -18,12 +16,7 @@ import torch.nn.functional as F
 
 from . import abi
 from . import policy as P
-from .tp_train import TPAdam
-
-
-def check(rc, what):
-    if rc != abi.HNS_OK:
-        raise RuntimeError(f"{what} failed ({rc}): {abi.load_library().hns_last_error().decode()}")
+from .optim import ClippedAdam  # noqa: F401  (the two updates' optimiser, public here)
 
 
 def getter(cfg):
@@ -176,71 +169,3 @@ def encoder(p, xs, xo, xc):
     x = F.layer_norm(x + F.linear(F.gelu(F.linear(x, p["linear1_w"], p["linear1_b"])), p["linear2_w"], p["linear2_b"]), (E,),
                      p["norm2_w"], p["norm2_b"])
     return x.mean(-2).reshape(*lead, E)
-
-
-class ClippedAdam(TPAdam):
-    """clip_grad_norm_(params, max_grad_norm) followed by torch.optim.Adam's step, as update_critic runs them: one launch of
-    hns_adam_clipped per step for all tensors on the device (device-resident step counter, capturable), the reference's torch statements on
-    the CPU.  `step(grad_norm=...)` takes the total gradient norm value_loss_and_grad returned (a 0-dim device tensor; required on the device
-    unless max_grad_norm is inf or None).  state_dict() / load_state_dict() use Adam's format.  `last_grad_norm`: the unclipped norm of the
-    last step (what clip_grad_norm_ returns)."""
-
-    def __init__(self, params, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=10.0, weight_decay=0.0):
-        if weight_decay != 0:
-            raise NotImplementedError("ClippedAdam implements Adam with weight_decay 0")
-        super().__init__(params, lr=lr, betas=betas, eps=eps)
-        self.max_grad_norm = float("inf") if max_grad_norm is None else float(max_grad_norm)
-        if not self.max_grad_norm >= 0:
-            raise ValueError("max_grad_norm must be >= 0")
-        self.last_grad_norm = None
-
-    @torch.no_grad()
-    def step(self, closure=None, grad_norm=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        for group in self.param_groups:
-            self._check_group(group)
-            ps = [p for p in group["params"] if p.grad is not None]
-            cpu = [p for p in ps if not p.is_cuda]
-            dev = [p for p in ps if p.is_cuda]
-            if cpu:
-                self.last_grad_norm = nn.utils.clip_grad_norm_(cpu, self.max_grad_norm)
-                for p in cpu:
-                    self._cpu_step(p, self._state(p, None), group)
-            if dev:
-                self._device_step(dev, group, grad_norm)
-        return loss
-
-    def _device_step(self, ps, group, grad_norm=None):
-        devs = {p.device for p in ps}
-        if len(devs) != 1:
-            raise ValueError(f"ClippedAdam: the parameters of a group live on one device, not {devs}")
-        dev = ps[0].device
-        clip = math.isfinite(self.max_grad_norm)
-        if clip:
-            if grad_norm is None:
-                raise ValueError("ClippedAdam.step on the device needs grad_norm= (value_loss_and_grad's) unless max_grad_norm is inf")
-            if not torch.is_tensor(grad_norm) or grad_norm.device != dev or grad_norm.dtype != torch.float32 or grad_norm.numel() != 1:
-                raise ValueError("grad_norm must be a one-element float32 tensor on the parameters' device")
-        shared = next((self.state[p]["step"] for p in ps if len(self.state[p]) and self.state[p]["step"].device == dev), None)
-        if shared is None:
-            shared = torch.zeros((), dtype=torch.float32, device=dev)
-        arr = (abi.HnsAdamTensor * len(ps))()
-        for j, p in enumerate(ps):
-            st = self._state(p, shared)
-            if st["step"] is not shared:
-                raise RuntimeError("ClippedAdam: the parameters of a group on one device step together (one step counter)")
-            if p.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous() or p.grad.dtype != torch.float32:
-                raise ValueError("ClippedAdam on the device takes contiguous float32 parameters and gradients")
-            arr[j] = abi.HnsAdamTensor(p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel())
-        beta1, beta2 = group["betas"]
-        with torch.cuda.device(dev):
-            rc = abi.load_library().hns_adam_clipped(arr, len(ps), shared.data_ptr(), grad_norm.data_ptr() if clip else None,
-                                                     self.max_grad_norm, float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
-                                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        check(rc, "hns_adam_clipped")
-        self.last_grad_norm = grad_norm
-        for p in ps:
-            torch.autograd.graph.increment_version(p)

@@ -5,9 +5,9 @@ of `hns_tp_train_grad` (two launches: per-workgroup partial gradients on the mat
 `.grad` in its PyTorch layout and returns the loss as a 0-dim device tensor — no autograd graph, no host synchronisation.  `index` reads a
 minibatch of `make_dataset_naive` (mappo.py:493-513) in place.  A data-parallel caller can all_reduce the `.grad` tensors before the step.
 
-`TPAdam` is torch.optim.Adam (amsgrad off, weight decay 0) with its step in ONE launch of `hns_tp_adam` over the six tensors and a
-device-resident step counter; its state_dict is Adam's, both ways.  Every step bumps the parameters' version counters, so the env re-packs its
-operand image before the next `hns_tp_observe` (env.HideAndSeek._tp_sync_weights).
+`TPAdam` (optim's, re-exported here) is torch.optim.Adam (amsgrad off, weight decay 0, lr 1e-4) with the device step every update shares.  Every
+step bumps the parameters' version counters, so the env re-packs its operand image before the next `hns_tp_observe`
+(env.HideAndSeek._tp_sync_weights).
 
 `update_tp` is mappo.py:405-441 end to end.  CPU tensors run the reference's torch statements throughout (CPU tests, gloo runs — not the hot
 path).  DESIGN.md §7.2."""
@@ -17,13 +17,9 @@ import torch
 import torch.nn as nn
 
 from . import abi
+from .optim import TPAdam  # noqa: F401  (the predictor's optimiser, public here)
 
 MAX_HISTORY, MAX_INPUT, MAX_FUTURE = 16, 80, 10
-
-
-def _check(rc, what):
-    if rc != abi.HNS_OK:
-        raise RuntimeError(f"{what} failed ({rc}): {abi.load_library().hns_last_error().decode()}")
 
 
 def parameters(tp):
@@ -135,118 +131,8 @@ def loss_and_grad(tp, x, y, index=None, check_index=True):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         rc = lib.hns_tp_train_grad(C.byref(pw), x.data_ptr(), E, S, x.stride(0), x.stride(1), T, I, y.data_ptr(),
                                    index.data_ptr() if index is not None else None, B, F, C.byref(gw), loss.data_ptr(), ws.data_ptr(), nbytes, st)
-    _check(rc, "hns_tp_train_grad")
+    abi.check(rc, "hns_tp_train_grad")
     return loss
-
-
-class TPAdam(torch.optim.Optimizer):
-    """torch.optim.Adam for TP_net's parameters: one launch of hns_tp_adam per step on the device (device-resident step counter, capturable),
-    the reference's torch statements on the CPU.  state_dict() / load_state_dict() use Adam's format (per-parameter 'step' on the CPU,
-    'exp_avg', 'exp_avg_sq'; Adam's param_group keys)."""
-
-    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8):
-        params = list(params)
-        defaults = dict(torch.optim.Adam([torch.zeros(1, requires_grad=True)], lr=lr, betas=betas, eps=eps).defaults)
-        super().__init__(params, defaults)
-
-    @staticmethod
-    def _check_group(group):
-        if group.get("weight_decay", 0) != 0 or group.get("amsgrad", False) or group.get("maximize", False):
-            raise NotImplementedError("TPAdam implements Adam with weight_decay 0, amsgrad and maximize off")
-
-    def _state(self, p, shared_step):
-        st = self.state[p]
-        if len(st) == 0:
-            st["step"] = shared_step if shared_step is not None else torch.tensor(0.0, dtype=torch.float32)
-            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-        return st
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        for group in self.param_groups:
-            self._check_group(group)
-            ps = [p for p in group["params"] if p.grad is not None]
-            dev = [p for p in ps if p.is_cuda]
-            for p in ps:
-                if not p.is_cuda:
-                    self._cpu_step(p, self._state(p, None), group)
-            if dev:
-                self._device_step(dev, group)
-        return loss
-
-    @staticmethod
-    def _cpu_step(param, st, group):
-        """torch.optim.adam._single_tensor_adam's statements (capturable off)."""
-        beta1, beta2 = group["betas"]
-        lr, eps = group["lr"], group["eps"]
-        grad, exp_avg, exp_avg_sq, step_t = param.grad, st["exp_avg"], st["exp_avg_sq"], st["step"]
-        step_t += 1
-        exp_avg.lerp_(grad, 1 - beta1)
-        exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
-        step = step_t.item()
-        bias_correction1 = 1 - beta1 ** step
-        bias_correction2 = 1 - beta2 ** step
-        step_size = lr / bias_correction1
-        bias_correction2_sqrt = bias_correction2 ** 0.5
-        denom = (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
-        param.addcdiv_(exp_avg, denom, value=-step_size)
-
-    def _device_step(self, ps, group):
-        by_dev = {}
-        for p in ps:
-            by_dev.setdefault(p.device, []).append(p)
-        lib = abi.load_library()
-        beta1, beta2 = group["betas"]
-        for dev, plist in by_dev.items():
-            shared = next((self.state[p]["step"] for p in plist if len(self.state[p]) and self.state[p]["step"].device == dev), None)
-            if shared is None:
-                shared = torch.zeros((), dtype=torch.float32, device=dev)
-            for k in range(0, len(plist), 8):
-                chunk = plist[k:k + 8]
-                arr = (abi.HnsTpAdamTensor * len(chunk))()
-                for j, p in enumerate(chunk):
-                    st = self._state(p, shared)
-                    if st["step"] is not shared:
-                        raise RuntimeError("TPAdam: the parameters of a group on one device step together (one step counter)")
-                    if p.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous() or p.grad.dtype != torch.float32:
-                        raise ValueError("TPAdam on the device takes contiguous float32 parameters and gradients")
-                    arr[j] = abi.HnsTpAdamTensor(p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel())
-                if k > 0:
-                    raise NotImplementedError("TPAdam: at most 8 parameters per group on one device")
-                with torch.cuda.device(dev):
-                    rc = lib.hns_tp_adam(arr, len(chunk), shared.data_ptr(), float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
-                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-                _check(rc, "hns_tp_adam")
-            for p in plist:
-                torch.autograd.graph.increment_version(p)
-
-    def state_dict(self):
-        sd = super().state_dict()
-        sd["state"] = {k: {n: (v.detach().to("cpu", copy=True) if n == "step" else v) for n, v in s.items()} for k, s in sd["state"].items()}
-        return sd
-
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        for group in self.param_groups:
-            shared = {}
-            for p in group["params"]:
-                st = self.state.get(p)
-                if not st or "step" not in st:
-                    continue
-                step = torch.as_tensor(st["step"], dtype=torch.float32).detach()
-                if not p.is_cuda:
-                    st["step"] = step.to("cpu", copy=True)
-                    continue
-                if p.device not in shared:
-                    shared[p.device] = step.to(p.device, copy=True)
-                elif float(shared[p.device]) != float(step):
-                    raise ValueError("TPAdam: the parameters of a group on one device must share one step count")
-                st["step"] = shared[p.device]
 
 
 def select_windows(tp_input, tp_groundtruth, tp_done, future_step, window_step):

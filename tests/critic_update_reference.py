@@ -1,12 +1,12 @@
 """Test-side restatement of MAPPOPolicy.update_critic (learning/mappo.py:326-352) in any float dtype, on top of tests/policy_reference.py (the
 full attention over all tokens, written out from the equations, independent of hns_amd): value loss, explained variance, the gradients by
 torch autograd, clip_grad_norm_ and Adam.  fp64 autograd is the accuracy gate's yardstick, fp32 the CPU error it is measured against.
-`clip_np` / `clip_adam_np` restate clip_grad_norm_'s scaling and torch.optim.Adam's single-tensor statements in numpy fp32: what
-hns_adam_clipped is held to, bit for bit."""
+`clip_np` / `adam_np` / `clip_adam_np`, the numpy fp32 restatement hns_adam_clipped is held to bit for bit, are tests/adam_reference.py's, re-exported."""
 import numpy as np
 import torch
 
 import policy_reference as R
+from adam_reference import adam_np, clip_adam_np, clip_np  # noqa: F401
 
 
 def _strip(d):
@@ -79,39 +79,3 @@ def golden_case(zc, zp, tag):
     obs = {k: zc[f"{tag}:obs:{k}"] for k in ("state_self", "state_others", "cylinders") if f"{tag}:obs:{k}" in zc.files}
     rec = {k[len(tag) + 1:]: zc[k] for k in zc.files if k.startswith(tag + ":")}
     return critic, obs, zc[f"{tag}:b_values"], zc[f"{tag}:b_returns"], zc[f"{tag}:index"], str(zc[f"{tag}:loss"]), rec
-
-
-def _fma32(a, b, c):
-    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
-
-
-def clip_np(grads, total_norm, max_norm):
-    """clip_grad_norm_'s scaling in fp32: coef = min((1 / (norm + 1e-6)) * max_norm, 1) (torch forms max_norm / x as reciprocal(x) * max_norm),
-    every gradient times coef — always, also when coef is 1."""
-    f32 = np.float32
-    coef = f32(f32(f32(1.0) / f32(f32(total_norm) + f32(1e-6))) * f32(max_norm))
-    coef = f32(min(coef, f32(1.0)))
-    return [(g * coef).astype(f32) for g in grads], coef
-
-
-def adam_np(p, g, m, v, step, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, sqrt=np.sqrt):
-    """torch.optim.Adam's single-tensor statements in numpy fp32 with `step` already bumped (tests/test_tp_train.py's adam_np, which bumps it
-    itself): returns p, m, v.  `sqrt`: IEEE (the kernel's); torch's CPU sqrt is not correctly rounded, so a CPU self-check passes torch's in."""
-    b1, b2 = betas
-    f32 = np.float32
-    m = _fma32(f32(1 - b1), (g - m).astype(f32), m)
-    v = _fma32((f32(1 - b2) * g).astype(f32), g, (v * f32(b2)).astype(f32))
-    bc1 = 1 - b1 ** float(step)
-    bc2 = 1 - b2 ** float(step)
-    den = (sqrt(v) / f32(bc2 ** 0.5)).astype(f32) + f32(eps)
-    p = (p + (f32(-(lr / bc1)) * m).astype(f32) / den).astype(f32)
-    return p, m, v
-
-
-def clip_adam_np(params, grads, ms, vs, step, total_norm, max_norm, **kw):
-    """One ClippedAdam step over lists of arrays: (params, clipped grads, ms, vs, step + 1)."""
-    if max_norm is not None and np.isfinite(max_norm):
-        grads, _ = clip_np(grads, total_norm, max_norm)
-    step = np.float32(np.float32(step) + np.float32(1.0))
-    out = [adam_np(p, g, m, v, step, **kw) for p, g, m, v in zip(params, grads, ms, vs)]
-    return [o[0] for o in out], grads, [o[1] for o in out], [o[2] for o in out], step

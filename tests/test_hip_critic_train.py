@@ -298,6 +298,34 @@ def test_adam_clipped_matches_the_numpy_restatement_bit_for_bit(max_norm):
         assert float(opt.state[dev[0]]["step"]) == it + 1 == float(step)
 
 
+@pytest.mark.parametrize("max_norm", [1.0, float("inf")])
+def test_adam_clipped_over_65_tensors_steps_both_launches_with_one_count(max_norm):
+    """65 tensors of 3 to 40 values: one past the 64 descriptors a launch carries, so the second launch of a step runs while the counter is
+    still unbumped.  Two steps, bit for bit against the restatement (which uses ONE step + 1 for all tensors), with the clip active (the norm
+    is ~ 4 to 40 > 1) and off; the counter reads 2.0."""
+    g = np.random.default_rng(65)
+    sizes = [3 + (7 * k) % 38 for k in range(65)]
+    assert min(sizes) == 3 and max(sizes) == 40 and len(sizes) == 65
+    ps = [g.standard_normal(n).astype(np.float32) for n in sizes]
+    ms, vs, step = [np.zeros(n, np.float32) for n in sizes], [np.zeros(n, np.float32) for n in sizes], np.float32(0)
+    dev = [torch.nn.Parameter(torch.as_tensor(p).cuda()) for p in ps]
+    opt = CT.ClippedAdam(dev, lr=5e-4, max_grad_norm=max_norm)
+    for it in range(2):
+        gs = [(g.standard_normal(n) * 10.0 ** (it - 1)).astype(np.float32) for n in sizes]
+        norm = np.float32(math.sqrt(sum(float((x.astype(np.float64) ** 2).sum()) for x in gs)))
+        assert norm > 1.0
+        for p, x in zip(dev, gs):
+            p.grad = torch.as_tensor(x).cuda()
+        opt.step(grad_norm=torch.tensor(norm, device="cuda"))
+        ps, cg, ms, vs, step = U.clip_adam_np(ps, gs, ms, vs, step, norm, max_norm)
+        for k, (p, x) in enumerate(zip(dev, ps)):
+            assert np.array_equal(p.detach().cpu().numpy(), x), (it, k)
+            assert np.array_equal(p.grad.cpu().numpy(), cg[k]), (it, k)
+            assert np.array_equal(opt.state[p]["exp_avg"].cpu().numpy(), ms[k]) and np.array_equal(opt.state[p]["exp_avg_sq"].cpu().numpy(), vs[k]), (it, k)
+    assert all(opt.state[p]["step"] is opt.state[dev[0]]["step"] for p in dev)
+    assert float(opt.state[dev[0]]["step"]) == 2.0 == float(step)
+
+
 def test_update_critic_end_to_end_and_the_policy_follows():
     """Four epochs x 16 minibatches from the same start and the same permutations on the device and in CPU torch.  Bound: Adam moves a
     parameter by at most ~lr per step whatever the gradient's size, and a gradient error of relative size r near |g| ~ sqrt(v) moves the step

@@ -246,7 +246,7 @@ FORWARD_REFUSALS = [
 
 @pytest.mark.parametrize("row", FORWARD_REFUSALS, ids=[r[0].replace(" ", "_") for r in FORWARD_REFUSALS])
 def test_every_refusal_branch_of_hns_policy_forward(row):
-    """Each pol_fail of hns_policy_forward, one wrong argument at a time on an otherwise valid call.  The refusals return before any launch and
+    """Each refusal of hns_policy_forward, one wrong argument at a time on an otherwise valid call.  The refusals return before any launch and
     do not depend on the machine: every pointer here is made up, so a row that were NOT refused must never be committed."""
     _, fragment, call, fields = row
     L = abi.load_library()
@@ -291,7 +291,7 @@ PACK_REFUSALS = [
 
 @pytest.mark.parametrize("row", PACK_REFUSALS, ids=[r[0].replace(" ", "_") for r in PACK_REFUSALS])
 def test_every_refusal_branch_of_hns_policy_pack(row):
-    """Each pol_fail of hns_policy_pack and of its per-network check, on made-up pointers (refused before the launch)."""
+    """Each refusal of hns_policy_pack and of its per-network check, on made-up pointers (refused before the launch)."""
     _, fragment, call, actor, critic = row
     L = abi.load_library()
     a = dict(actor=_net(**actor), critic=_net(**critic), D=35, A=3, packed=FAKE + (1 << 19))

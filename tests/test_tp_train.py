@@ -7,8 +7,8 @@ raises before anything is launched, and the C entry points refuse bad arguments 
 
 GPU part: the accuracy gate e_hip <= C * max(e_32, 2^-24 * max|g64|) for the loss and each gradient, with e_hip / e_32 the kernel's and CPU
 torch fp32 autograd's largest errors against fp64 autograd of the same network (C = 8; the worst measured ratio is recorded below), over stress
-cases; bit identity across calls, index vs gather, strided vs contiguous x, graph replay vs eager; hns_tp_adam bit for bit against the numpy
-restatement and, step by step from the same state, within 4 ulp (of max(|p|, lr)) of torch's Adam on the device; update_tp end to end on the golden rollout; the env picking up TPAdam's steps.
+cases; bit identity across calls, index vs gather, strided vs contiguous x, graph replay vs eager; the Adam step (TPAdam, and raw hns_tp_adam /
+hns_adam_clipped calls from the same state) bit for bit against the numpy restatement of tests/adam_reference.py and, step by step from the same state, within 4 ulp (of max(|p|, lr)) of torch's Adam on the device; update_tp end to end on the golden rollout; the env picking up TPAdam's steps.
 
 Worst measured gate ratio on an MI355X: WORST_RATIO below (C = 8 leaves 1.75x headroom).
 """
@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 
+from adam_reference import _fma32, adam_np, bump
 from hns_amd import abi
 from hns_amd import tp_train as TT
 from hns_amd.tp_net import TPNet
@@ -57,25 +58,6 @@ def _grad_digest(grads):
 
 def _golden_net(g):
     return _net(16, 5, {k: g["init_" + k] for k in KEYS})
-
-
-def _fma32(a, b, c):
-    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
-
-
-def adam_np(p, g, m, v, step, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, sqrt=np.sqrt):
-    """The statement order hns_tp_adam implements (torch's single-tensor Adam on its CPU kernels), in numpy fp32: returns p, m, v, step.
-    `sqrt`: IEEE (the kernel's); torch's CPU sqrt is not correctly rounded (about 0.6 % of values 1 ulp off), so the CPU self-check passes it in."""
-    b1, b2 = betas
-    f32 = np.float32
-    step = f32(f32(step) + f32(1.0))
-    m = _fma32(f32(1 - b1), (g - m).astype(f32), m)                      # lerp_(g, 1 - b1): fused on both the vector body and the tail
-    v = _fma32((f32(1 - b2) * g).astype(f32), g, (v * f32(b2)).astype(f32))   # mul_(b2).addcmul_(g, g, value=1 - b2)
-    bc1 = 1 - b1 ** float(step)
-    bc2 = 1 - b2 ** float(step)
-    den = (sqrt(v) / f32(bc2 ** 0.5)).astype(f32) + f32(eps)
-    p = (p + (f32(-(lr / bc1)) * m).astype(f32) / den).astype(f32)
-    return p, m, v, step
 
 
 # ---- CPU -----------------------------------------------------------------------------------------------------------------------------------
@@ -172,13 +154,32 @@ def test_numpy_adam_restatement_matches_torch_adam_on_cpu():
             grad = torch.randn(n, generator=gen) * (10.0 ** (it % 5 - 3))
             q.grad = grad.clone()
             opt.step()
-            pn, m, v, step = adam_np(pn, grad.numpy(), m, v, step, sqrt=torch_sqrt)
+            step = bump(step)
+            pn, m, v = adam_np(pn, grad.numpy(), m, v, step, 1e-4, sqrt=torch_sqrt)
             assert np.array_equal(pn, q.detach().numpy()), (n, it)
             assert np.array_equal(m, opt.state[q]["exp_avg"].numpy()) and np.array_equal(v, opt.state[q]["exp_avg_sq"].numpy())
     # the checker's power: the unfused lerp or an unfused addcmul is caught
     g = np.random.default_rng(0).standard_normal(100000).astype(np.float32)
     m0 = np.random.default_rng(1).standard_normal(100000).astype(np.float32)
     assert not np.array_equal(_fma32(np.float32(0.1), g - m0, m0), m0 + np.float32(0.1) * (g - m0))
+
+
+def test_tpadam_steps_nine_parameters_on_the_cpu_as_torch_adam():
+    """More tensors than hns_tp_adam's cap of 8: TPAdam has no cap of its own (on the device it goes through hns_adam_clipped)."""
+    gen = torch.Generator().manual_seed(9)
+    ps = [torch.randn(n, generator=gen).requires_grad_(True) for n in range(1, 10)]
+    qs = [p.detach().clone().requires_grad_(True) for p in ps]
+    opt, ref = TT.TPAdam(ps), torch.optim.Adam(qs, lr=1e-4, foreach=False)
+    for it in range(3):
+        for p, q in zip(ps, qs):
+            p.grad = torch.randn(p.shape, generator=gen)
+            q.grad = p.grad.clone()
+        opt.step()
+        ref.step()
+    for p, q in zip(ps, qs):
+        assert torch.equal(p, q) and torch.equal(opt.state[p]["exp_avg_sq"], ref.state[q]["exp_avg_sq"]) and float(opt.state[p]["step"]) == 3.0
+    with pytest.raises(TypeError):
+        opt.step(grad_norm=torch.tensor(1.0))                    # the predictor's step does not clip and takes no norm
 
 
 def _refusal_inputs():
@@ -426,11 +427,9 @@ def test_adam_kernel_matches_numpy_restatement_and_torch_adam(golden):
             p.grad, q.grad = gr.to(dev), gr.to(dev)
         opt.step()
         topt.step()
+        step = bump(step)
         for k, gr in zip(KEYS, grads):
-            pn, m, v = host[k]
-            pn, m, v, s = adam_np(pn, gr.numpy(), m, v, step)
-            host[k] = (pn, m, v)
-        step = s
+            host[k] = adam_np(host[k][0], gr.numpy(), *host[k][1:], step, 1e-4)
         for k, p in zip(KEYS, TT.parameters(net)):
             assert np.array_equal(p.detach().cpu().numpy(), host[k][0]), (it, k)
             assert np.array_equal(opt.state[p]["exp_avg"].cpu().numpy(), host[k][1]), (it, k)
@@ -444,6 +443,85 @@ def test_adam_kernel_matches_numpy_restatement_and_torch_adam(golden):
     print(f"adam: worst {worst:.1f} ulp against torch.optim.Adam(foreach=False) on the device")
     assert worst <= 4, worst
     assert float(opt.state[TT.parameters(net)[0]]["step"]) == 20.0
+
+
+DOOR_SIZES = (0, 1, 255, 256, 257, 65537)    # nothing, one thread, around one workgroup, and one value past 256 workgroups x 256 threads (a second grid-stride trip)
+
+
+def _descriptors(tensors, spare):
+    """hns_adam_tensor descriptors of (param, grad, exp_avg, exp_avg_sq) tuples.  An empty tensor has no address; the entry points want a
+    non-NULL one and read nothing through it: `spare`."""
+    arr = (abi.HnsAdamTensor * len(tensors))()
+    for j, ts in enumerate(tensors):
+        arr[j] = abi.HnsAdamTensor(*(t.data_ptr() or spare for t in ts), ts[0].numel())
+    return arr
+
+
+def _adam_np_steps(p0, grads, lr):
+    """p0 after one adam_np step per entry of grads, from zero moments: ([p...], [m...], [v...], step)."""
+    host, step = [(p.numpy().copy(), np.zeros(p.shape, np.float32), np.zeros(p.shape, np.float32)) for p in p0], np.float32(0)
+    for gs in grads:
+        step = bump(step)
+        host = [adam_np(*h, step, lr) for h in ((h[0], g.numpy(), h[1], h[2]) for h, g in zip(host, gs))]
+    return [h[0] for h in host], [h[1] for h in host], [h[2] for h in host], step
+
+
+def _tpadam_steps(p0, grads, lr):
+    ps = [torch.nn.Parameter(p.cuda()) for p in p0]
+    opt = TT.TPAdam(ps, lr=lr)
+    for gs in grads:
+        for p, g in zip(ps, gs):
+            p.grad = g.cuda()
+        opt.step()
+    torch.cuda.synchronize()
+    st = [opt.state[p] for p in ps]
+    assert all(s["step"] is st[0]["step"] for s in st)
+    return ([p.detach().cpu().numpy() for p in ps], [s["exp_avg"].cpu().numpy() for s in st], [s["exp_avg_sq"].cpu().numpy() for s in st],
+            np.float32(st[0]["step"].item()))
+
+
+@pytest.mark.gpu
+def test_one_adam_step_behind_hns_tp_adam_hns_adam_clipped_and_tpadam():
+    """The same parameters, moments, counter and gradients through a raw hns_tp_adam call, a raw hns_adam_clipped call without a norm and
+    TPAdam.step(): three steps with gradients at 1e-3, 1 and 1e3, every array and the counter identical and equal to adam_np's."""
+    lib = abi.load_library()
+    gen = torch.Generator().manual_seed(9)
+    p0 = [torch.randn(n, generator=gen) for n in DOOR_SIZES]
+    grads = [[torch.randn(n, generator=gen) * s for n in DOOR_SIZES] for s in (1e-3, 1.0, 1e3)]
+    got = {"TPAdam": _tpadam_steps(p0, grads, 1e-4)}
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for door in ("hns_tp_adam", "hns_adam_clipped"):
+        ps, ms, vs = [p.cuda() for p in p0], [torch.zeros_like(p).cuda() for p in p0], [torch.zeros_like(p).cuda() for p in p0]
+        step = torch.zeros((), device="cuda")
+        for gs in grads:
+            gd = [g.cuda() for g in gs]
+            arr = _descriptors(list(zip(ps, gd, ms, vs)), step.data_ptr())
+            if door == "hns_tp_adam":
+                rc = lib.hns_tp_adam(arr, len(ps), step.data_ptr(), 1e-4, 0.9, 0.999, 1e-8, stream)
+            else:
+                rc = lib.hns_adam_clipped(arr, len(ps), step.data_ptr(), None, 10.0, 1e-4, 0.9, 0.999, 1e-8, stream)
+            assert rc == abi.HNS_OK, lib.hns_last_error()
+            torch.cuda.synchronize()
+        got[door] = ([p.cpu().numpy() for p in ps], [m.cpu().numpy() for m in ms], [v.cpu().numpy() for v in vs], np.float32(step.item()))
+    want = _adam_np_steps(p0, grads, 1e-4)
+    assert float(want[3]) == 3.0
+    for door, (ps, ms, vs, step) in got.items():
+        assert step == want[3], door
+        for k, n in enumerate(DOOR_SIZES):
+            assert ps[k].shape == (n,) and np.array_equal(ps[k], want[0][k]), (door, n)
+            assert np.array_equal(ms[k], want[1][k]) and np.array_equal(vs[k], want[2][k]), (door, n)
+
+
+@pytest.mark.gpu
+def test_tpadam_steps_nine_tensors_on_the_device():
+    """One more than hns_tp_adam takes: TPAdam steps them in one call of hns_adam_clipped, bit for bit with adam_np."""
+    gen = torch.Generator().manual_seed(10)
+    p0 = [torch.randn(n, generator=gen) for n in (5, 64, 1, 300, 17, 2, 129, 33, 8)]
+    grads = [[torch.randn(p.shape, generator=gen) * s for p in p0] for s in (1.0, 1e-2)]
+    got, want = _tpadam_steps(p0, grads, 1e-4), _adam_np_steps(p0, grads, 1e-4)
+    assert got[3] == want[3] == 2.0
+    for k in range(9):
+        assert all(np.array_equal(got[j][k], want[j][k]) for j in range(3)), k
 
 
 @pytest.mark.gpu
