@@ -9,12 +9,17 @@
 // Single-query algebra: with q = W_q t_0 + b_q the score of token j is q.(W_k t_j + b_k) / sqrt(128) = (W_k^T q / sqrt(128)).t_j
 // plus a term that is the same for every j and cancels in the softmax, and sum_j a_j (W_v t_j + b_v) = W_v (sum_j a_j t_j) + b_v.  Per row and
 // network that leaves six 128 x 128 matrix-vector products (W_q, W_k^T, W_v, W_o, W_1, W_2), which run on v_mfma_f32_16x16x4_f32 for a tile of
-// kPolRows rows at a time, and a token pass on the VALU (embedding, LayerNorm, score, online softmax, weighted sum) that never stores a token.
+// kEncRows rows at a time, and a token pass on the VALU (embedding, LayerNorm, score, online softmax, weighted sum) that never stores a token.
+//
+// The encoder's shared pieces — tile shape, matrix-vector product, LayerNorm, token embedding, online-softmax step, the parameter table and the
+// matrices' fragment order — are hns_encoder.h's, which hns_policy_train.hip uses too.  Here: the packed image's vector sections, the head,
+// sampling, the log-probability, the entry points.
 //
 //   hns_policy_pack_kernel    : parameter tensors (PyTorch layouts) -> the packed image: the six matrices in MFMA A-operand fragment order (one
 //                               float4 per lane per four k-steps), the vectors, the head, the embedding weights transposed.
-//   hns_policy_forward_kernel : one workgroup of four waves per kPolRows rows.  Activations live in LDS as [128 features][kPolRows rows]; wave w
-//                               owns output row blocks 2w, 2w + 1 of every product, so each weight element is read once per workgroup.
+//   hns_policy_forward_kernel : one workgroup of four waves per kEncRows rows.  Activations live in LDS as [128 features][kEncRows rows]; wave w
+//                               owns output row blocks 2w, 2w + 1 of every product, so each weight element is read once per workgroup.  The
+//                               embedding starts its fma chain from the bias (enc_token<true>; the updates add it last: DESIGN §7.3).
 //   hns_policy_bump_kernel    : the device call counter += 1 after a sampling call (Philox counter; a captured graph draws fresh noise per replay).
 // Determinism: fixed reduction orders (butterflies over the eight lanes of a row), no atomics.
 #include <hip/hip_runtime.h>
@@ -22,61 +27,37 @@
 #include <string>
 
 #include "hns_device.h"
+#include "hns_encoder.h"
 #include "hns_host.h"
 #include "../../include/hns.h"
 
 namespace hns {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kPolE = 128;                   // embed_dim = dim_feedforward
-constexpr int kPolRows = 32;                 // rows per workgroup (two 16-wide MFMA column blocks)
-constexpr int kPolLd = kPolRows + 16;        // LDS row pitch in floats: the four k-quads of a B-operand read fall in distinct bank groups
-constexpr int kPolThreads = 256;
-constexpr int kPolMat = kPolE * kPolE;
 constexpr int kPolMaxSelf = HNS_POLICY_MAX_SELF_DIM;
 
 // packed network image, in floats (every section a multiple of 4 floats: float4 loads)
 enum : int {
     P_MAT = 0,                               // 6 matrices: Q, K^T, V, O, L1, L2 (fragment order)
-    P_BQ = 6 * kPolMat, P_BV = P_BQ + kPolE, P_BO = P_BV + kPolE, P_B1 = P_BO + kPolE, P_B2 = P_B1 + kPolE,
-    P_LNW = P_B2 + kPolE, P_LNB = P_LNW + kPolE, P_N1W = P_LNB + kPolE, P_N1B = P_N1W + kPolE, P_N2W = P_N1B + kPolE, P_N2B = P_N2W + kPolE,
-    P_EB = P_N2B + kPolE,                    // embedding biases [3][128]: self, others, cylinders
-    P_HW = P_EB + 3 * kPolE,                 // head weight [4][128] (the critic: row 0)
-    P_HB = P_HW + 4 * kPolE,                 // head bias [4]
+    P_BQ = 6 * kEncMat, P_BV = P_BQ + kEncE, P_BO = P_BV + kEncE, P_B1 = P_BO + kEncE, P_B2 = P_B1 + kEncE,
+    P_LNW = P_B2 + kEncE, P_LNB = P_LNW + kEncE, P_N1W = P_LNB + kEncE, P_N1B = P_N1W + kEncE, P_N2W = P_N1B + kEncE, P_N2B = P_N2W + kEncE,
+    P_EB = P_N2B + kEncE,                    // embedding biases [3][128]: self, others, cylinders
+    P_HW = P_EB + 3 * kEncE,                 // head weight [4][128] (the critic: row 0)
+    P_HB = P_HW + 4 * kEncE,                 // head bias [4]
     P_SCALE = P_HB + 4,                      // exp(log_std) [4]
     P_LOGSCALE = P_SCALE + 4,                // log(scale) [4]
     P_EW = P_LOGSCALE + 4,                   // embedding weights transposed: self [D][128], others [3][128], cylinders [5][128]
 };
-static __host__ __device__ __forceinline__ long long pol_net_floats(int D) { return P_EW + (long long)(D + 8) * kPolE; }
-
-struct PolNetSrc {                           // one network's parameters (PyTorch layouts)
-    const float *ew[3], *eb[3], *ln_w, *ln_b, *in_w, *in_b, *out_w, *out_b, *l1_w, *l1_b, *l2_w, *l2_b, *n1_w, *n1_b, *n2_w, *n2_b;
-    const float *head_w, *head_b, *log_std;  // log_std: the actor only
-    int head_n;                              // 4 (actor) / 1 (critic)
-};
+static __host__ __device__ __forceinline__ long long pol_net_floats(int D) { return P_EW + (long long)(D + 8) * kEncE; }
 
 // source value of image float i of one network
-HNS_DEV float pol_src(const PolNetSrc &s, int D, long long i) {
-    if (i < P_BQ) {
-        const int m = (int)(i / kPolMat), x = (int)(i % kPolMat);
-        const int u = x & 3, lane = (x >> 2) & 63, s4 = (x >> 8) & 7, rb = x >> 11;
-        const int row = rb * 16 + (lane & 15), k = 4 * (4 * s4 + u) + (lane >> 4);
-        switch (m) {
-            case 0: return s.in_w[row * kPolE + k];
-            case 1: return s.in_w[(kPolE + k) * kPolE + row];      // W_k^T
-            case 2: return s.in_w[(2 * kPolE + row) * kPolE + k];
-            case 3: return s.out_w[row * kPolE + k];
-            case 4: return s.l1_w[row * kPolE + k];
-            default: return s.l2_w[row * kPolE + k];
-        }
-    }
+HNS_DEV float pol_src(const EncNet &s, int D, long long i) {
+    if (i < P_BQ) return enc_mat_src(s, (int)(i / kEncMat), (int)(i % kEncMat));
     const int j = (int)(i - P_BQ);
     if (i < P_EB) {
-        const int sec = j / kPolE, f = j % kPolE;
+        const int sec = j / kEncE, f = j % kEncE;
         switch (sec) {
             case 0: return s.in_b[f];
-            case 1: return s.in_b[2 * kPolE + f];
+            case 1: return s.in_b[2 * kEncE + f];
             case 2: return s.out_b[f];
             case 3: return s.l1_b[f];
             case 4: return s.l2_b[f];
@@ -89,24 +70,24 @@ HNS_DEV float pol_src(const PolNetSrc &s, int D, long long i) {
         }
     }
     if (i < P_HW) {
-        const int key = (int)((i - P_EB) / kPolE), f = (int)((i - P_EB) % kPolE);
+        const int key = (int)((i - P_EB) / kEncE), f = (int)((i - P_EB) % kEncE);
         return s.eb[key] ? s.eb[key][f] : 0.0f;
     }
     if (i < P_HB) {
-        const int o = (int)((i - P_HW) / kPolE), f = (int)((i - P_HW) % kPolE);
-        return o < s.head_n ? s.head_w[o * kPolE + f] : 0.0f;
+        const int o = (int)((i - P_HW) / kEncE), f = (int)((i - P_HW) % kEncE);
+        return o < s.head_n ? s.head_w[o * kEncE + f] : 0.0f;
     }
     if (i < P_SCALE) return (int)(i - P_HB) < s.head_n ? s.head_b[i - P_HB] : 0.0f;
     if (i < P_LOGSCALE) return s.log_std ? expf(s.log_std[i - P_SCALE]) : 1.0f;
     if (i < P_EW) return s.log_std ? logf(expf(s.log_std[i - P_LOGSCALE])) : 0.0f;   // torch Normal: scale.log()
     const long long e = i - P_EW;
-    const int in = (int)(e / kPolE), f = (int)(e % kPolE);
+    const int in = (int)(e / kEncE), f = (int)(e % kEncE);
     if (in < D) return s.ew[0][f * D + in];
     if (in < D + 3) return s.ew[1] ? s.ew[1][f * 3 + (in - D)] : 0.0f;
     return s.ew[2][f * 5 + (in - D - 3)];
 }
 
-__global__ __launch_bounds__(256) void hns_policy_pack_kernel(const PolNetSrc actor, const PolNetSrc critic, int D, float *img) {
+__global__ __launch_bounds__(256) void hns_policy_pack_kernel(const EncNet actor, const EncNet critic, int D, float *img) {
     const long long n = pol_net_floats(D);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < 2 * n; i += (long long)gridDim.x * 256)
         img[i] = i < n ? pol_src(actor, D, i) : pol_src(critic, D, i - n);
@@ -126,210 +107,88 @@ struct PolArgs {
 };
 
 struct PolLds {
-    float x0[kPolE * kPolLd];                // token 0 / LN1 output
-    float t1[kPolE * kPolLd];
-    float t2[kPolE * kPolLd];
+    float x0[kEncE * kEncLd];                // token 0 / LN1 output
+    float t1[kEncE * kEncLd];
+    float t2[kEncE * kEncLd];
 };
-
-HNS_DEV f32x4 pmfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// OUT[128][R] = W[128][128] IN[128][R] + bias, then epilogue: 0 none, 1 exact gelu, 2 times 1/sqrt(128) (no bias)
-template <int EPI>
-HNS_DEV void pol_matvec(const float *__restrict__ W, const float *__restrict__ bias, const float *in, float *out, int w, int lane) {
-    const int col = lane & 15, kq = lane >> 4;
-    f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const f32x4 *A0 = reinterpret_cast<const f32x4 *>(W) + (2 * w) * 8 * 64 + lane;
-    const f32x4 *A1 = A0 + 8 * 64;
-#pragma unroll
-    for (int s4 = 0; s4 < 8; ++s4) {
-        const f32x4 a0 = A0[s4 * 64], a1 = A1[s4 * 64];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int k = 4 * (4 * s4 + u) + kq;
-            const float b0 = in[k * kPolLd + col], b1 = in[k * kPolLd + 16 + col];
-            acc[0][0] = pmfma(a0[u], b0, acc[0][0]);
-            acc[0][1] = pmfma(a0[u], b1, acc[0][1]);
-            acc[1][0] = pmfma(a1[u], b0, acc[1][0]);
-            acc[1][1] = pmfma(a1[u], b1, acc[1][1]);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int f = (2 * w + i) * 16 + 4 * kq + r;
-            const float b = EPI == 2 ? 0.0f : bias[f];
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                float v = acc[i][c][r];
-                if (EPI == 2) v = v * 0.08838834764831845f;        // 1 / sqrt(128)
-                else v = v + b;
-                if (EPI == 1) v = 0.5f * v * (1.0f + erff(v * 0.7071067811865476f));
-                out[f * kPolLd + c * 16 + col] = v;
-            }
-        }
-}
-
-// the thread's 16 features of a row: f = 4 g + 32 i + u (g = the lane in the row's group of eight)
-HNS_DEV int pfeat(int g, int i, int u) { return 4 * g + 32 * i + u; }
-
-HNS_DEV float row_sum8(float v) {
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    return v;
-}
-
-// LayerNorm(128) of the row's vector (16 values per thread), eps 1e-5, affine w / b from the image
-HNS_DEV void pol_layernorm(float (&x)[16], const float *w, const float *b, int g) {
-    float s = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s += x[i];
-    const float mean = row_sum8(s) * (1.0f / kPolE);
-    float q = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        x[i] -= mean;
-        q = __builtin_fmaf(x[i], x[i], q);
-    }
-    const float rstd = 1.0f / __builtin_sqrtf(row_sum8(q) * (1.0f / kPolE) + 1e-5f);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f32x4 wv = *reinterpret_cast<const f32x4 *>(w + pfeat(g, i, 0)), bv = *reinterpret_cast<const f32x4 *>(b + pfeat(g, i, 0));
-#pragma unroll
-        for (int u = 0; u < 4; ++u) x[4 * i + u] = (x[4 * i + u] * rstd) * wv[u] + bv[u];
-    }
-}
-
-// token = LN(E^T-packed embedding of the n inputs at x (NULL: a padding row, zeros) + bias)
-HNS_DEV void pol_token(const float *net, int key_off, int bias_off, const float *x, int n, int g, float (&t)[16]) {
-    const float *eb = net + bias_off;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f32x4 b = *reinterpret_cast<const f32x4 *>(eb + pfeat(g, i, 0));
-#pragma unroll
-        for (int u = 0; u < 4; ++u) t[4 * i + u] = b[u];
-    }
-    if (x) {
-        for (int k = 0; k < n; ++k) {
-            const float xv = x[k];
-            const float *wr = net + key_off + k * kPolE;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const f32x4 wv = *reinterpret_cast<const f32x4 *>(wr + pfeat(g, i, 0));
-#pragma unroll
-                for (int u = 0; u < 4; ++u) t[4 * i + u] = __builtin_fmaf(wv[u], xv, t[4 * i + u]);
-            }
-        }
-    }
-    pol_layernorm(t, net + P_LNW, net + P_LNB, g);
-}
-
-HNS_DEV void lds_row_load(const float *buf, int r, int g, float (&x)[16]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) x[4 * i + u] = buf[pfeat(g, i, u) * kPolLd + r];
-}
-
-HNS_DEV void lds_row_store(float *buf, int r, int g, const float (&x)[16]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) buf[pfeat(g, i, u) * kPolLd + r] = x[4 * i + u];
-}
 
 // one network on the workgroup's rows; leaves the encoder output y (the thread's 16 features of row r) in `y`
 HNS_DEV void pol_encoder(const PolArgs &a, const float *net, PolLds &L, int w, int lane, int r, int g, long long row, float (&y)[16]) {
     const bool live = row < a.rows;
     const long long e = live ? row / a.A : 0;
     const int ag = live ? (int)(row % a.A) : 0;
-    const int D = a.D, eo = P_EW + D * kPolE, ec = eo + 3 * kPolE;
+    const int D = a.D, eo = P_EW + D * kEncE, ec = eo + 3 * kEncE;
     const float *xs = live ? a.xs + e * a.sse + ag * a.ssa : nullptr;
     const float *xo = live && a.xo ? a.xo + e * a.soe + ag * a.soa : nullptr;
     const float *xc = live ? a.xc + e * a.sce + ag * a.sca : nullptr;
 
-    float t[16];
-    pol_token(net, P_EW, P_EB, xs, D, g, t);                      // token 0
-    lds_row_store(L.x0, r, g, t);
+    // the image's sections are `net + offset` at each call: pointers formed once in front of the token loop made the kernel 5 % slower
+    // (profiles/r15_encoder_fold.txt)
+    float t[16], xh[16];                                          // xh: the normalised vectors, which only a backward pass reads
+    enc_token<true>(net + P_EW, net + P_EB, xs, D, net + P_LNW, net + P_LNB, g, xh, t);          // token 0
+    enc_lds_store(L.x0, r, g, t);
     __syncthreads();
-    pol_matvec<0>(net + P_MAT + 0 * kPolMat, net + P_BQ, L.x0, L.t1, w, lane);       // q
+    enc_matvec<0>(net + P_MAT + 0 * kEncMat, net + P_BQ, L.x0, L.t1, nullptr, nullptr, w, lane);     // q
     __syncthreads();
-    pol_matvec<2>(net + P_MAT + 1 * kPolMat, nullptr, L.t1, L.t2, w, lane);          // W_k^T q / sqrt(128)
+    enc_matvec<2>(net + P_MAT + 1 * kEncMat, nullptr, L.t1, L.t2, nullptr, nullptr, w, lane);        // W_k^T q / sqrt(128)
     __syncthreads();
 
     // token pass: scores and online softmax, z = sum_j a_j t_j
     float kq[16], z[16];
-    lds_row_load(L.t2, r, g, kq);
-    float s = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s = __builtin_fmaf(kq[i], t[i], s);
-    float m = row_sum8(s), l = 1.0f;
+    enc_lds_load(L.t2, r, g, kq);
+    float m = enc_score(kq, t), l = 1.0f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) z[i] = t[i];
     const int N = a.A + a.K;
     for (int j = 1; j < N; ++j) {
-        if (j < a.A) pol_token(net, eo, P_EB + kPolE, xo ? xo + (j - 1) * a.sot : nullptr, 3, g, t);
-        else pol_token(net, ec, P_EB + 2 * kPolE, xc ? xc + (j - a.A) * a.sct : nullptr, 5, g, t);
-        s = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s = __builtin_fmaf(kq[i], t[i], s);
-        s = row_sum8(s);
-        const float mn = s > m ? s : m;
-        const float c = expf(m - mn), p = expf(s - mn);
-        l = l * c + p;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) z[i] = __builtin_fmaf(p, t[i], z[i] * c);
-        m = mn;
+        if (j < a.A) enc_token<true>(net + eo, net + P_EB + kEncE, xo ? xo + (j - 1) * a.sot : nullptr, 3, net + P_LNW, net + P_LNB, g, xh, t);
+        else enc_token<true>(net + ec, net + P_EB + 2 * kEncE, xc ? xc + (j - a.A) * a.sct : nullptr, 5, net + P_LNW, net + P_LNB, g, xh, t);
+        enc_softmax_step(kq, t, m, l, z);
     }
     const float il = 1.0f / l;
 #pragma unroll
     for (int i = 0; i < 16; ++i) z[i] *= il;
-    lds_row_store(L.t1, r, g, z);
+    enc_lds_store(L.t1, r, g, z);
     __syncthreads();
-    pol_matvec<0>(net + P_MAT + 2 * kPolMat, net + P_BV, L.t1, L.t2, w, lane);       // v = W_v z + b_v
+    enc_matvec<0>(net + P_MAT + 2 * kEncMat, net + P_BV, L.t1, L.t2, nullptr, nullptr, w, lane);     // v = W_v z + b_v
     __syncthreads();
-    pol_matvec<0>(net + P_MAT + 3 * kPolMat, net + P_BO, L.t2, L.t1, w, lane);       // attn = W_o v + b_o
+    enc_matvec<0>(net + P_MAT + 3 * kEncMat, net + P_BO, L.t2, L.t1, nullptr, nullptr, w, lane);     // attn = W_o v + b_o
     __syncthreads();
-    float x[16];
-    lds_row_load(L.x0, r, g, x);
-    lds_row_load(L.t1, r, g, t);
+    float x[16], u[16];
+    enc_lds_load(L.x0, r, g, u);
+    enc_lds_load(L.t1, r, g, t);
 #pragma unroll
-    for (int i = 0; i < 16; ++i) x[i] += t[i];
-    pol_layernorm(x, net + P_N1W, net + P_N1B, g);                // x0' = LN1(x0 + attn)
-    lds_row_store(L.x0, r, g, x);
+    for (int i = 0; i < 16; ++i) u[i] += t[i];
+    enc_layernorm(u, net + P_N1W, net + P_N1B, g, xh, x);         // x0' = LN1(x0 + attn)
+    enc_lds_store(L.x0, r, g, x);
     __syncthreads();
-    pol_matvec<1>(net + P_MAT + 4 * kPolMat, net + P_B1, L.x0, L.t1, w, lane);       // gelu(W_1 x0' + b_1)
+    enc_matvec<1>(net + P_MAT + 4 * kEncMat, net + P_B1, L.x0, L.t1, nullptr, nullptr, w, lane);     // gelu(W_1 x0' + b_1)
     __syncthreads();
-    pol_matvec<0>(net + P_MAT + 5 * kPolMat, net + P_B2, L.t1, L.t2, w, lane);       // W_2 h + b_2
+    enc_matvec<0>(net + P_MAT + 5 * kEncMat, net + P_B2, L.t1, L.t2, nullptr, nullptr, w, lane);     // W_2 h + b_2
     __syncthreads();
-    lds_row_load(L.t2, r, g, t);
+    enc_lds_load(L.t2, r, g, t);
 #pragma unroll
-    for (int i = 0; i < 16; ++i) y[i] = x[i] + t[i];
-    pol_layernorm(y, net + P_N2W, net + P_N2B, g);                // y = LN2(x0' + ff)
+    for (int i = 0; i < 16; ++i) u[i] = x[i] + t[i];
+    enc_layernorm(u, net + P_N2W, net + P_N2B, g, xh, y);         // y = LN2(x0' + ff)
 }
 
 HNS_DEV float pol_head(const float *net, int o, const float (&y)[16], int g) {
-    const float *hw = net + P_HW + o * kPolE;
+    const float *hw = net + P_HW + o * kEncE;
     float s = 0.0f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const f32x4 wv = *reinterpret_cast<const f32x4 *>(hw + pfeat(g, i, 0));
+        const f32x4 wv = *reinterpret_cast<const f32x4 *>(hw + enc_feat(g, i, 0));
 #pragma unroll
         for (int u = 0; u < 4; ++u) s = __builtin_fmaf(wv[u], y[4 * i + u], s);
     }
     return row_sum8(s) + net[P_HB + o];
 }
 
-__global__ __launch_bounds__(kPolThreads, 2) void hns_policy_forward_kernel(const PolArgs a) {
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_kernel(const PolArgs a) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
-    const long long row = (long long)blockIdx.x * kPolRows + r;
+    const long long row = (long long)blockIdx.x * kEncRows + r;
     const bool live = row < a.rows;
     float y[16];
 
@@ -391,23 +250,20 @@ __global__ void hns_policy_bump_kernel(unsigned long long *counter) { counter[0]
 
 namespace {
 
-int pol_net(const char *fn, const hns_policy_net *n, int D, int has_others, bool actor, hns::PolNetSrc &s) {
+// one network's table from hns_encoder.h's field list (ct_bind_net of hns_policy_train.hip fills the same struct)
+int pol_net(const char *fn, const hns_policy_net *n, int has_others, bool actor, hns::EncNet &s) {
     if (!n) return hns_fail(fn, "null network");
-    const float *req[] = {n->embed_self_w, n->embed_self_b, n->embed_cyl_w, n->embed_cyl_b, n->ln_w, n->ln_b, n->in_proj_w, n->in_proj_b,
-                          n->out_proj_w, n->out_proj_b, n->linear1_w, n->linear1_b, n->linear2_w, n->linear2_b, n->norm1_w, n->norm1_b,
-                          n->norm2_w, n->norm2_b, n->head_w, n->head_b};
-    for (const float *p : req)
-        if (!p || !hns_aligned(p, 4)) return hns_fail(fn, "every parameter pointer must be a non-NULL fp32 array");
+    bool ok = true;
+#define X(f, m)                                \
+    ok = ok && n->f && hns_aligned(n->f, 4); \
+    s.m = n->f;
+    HNS_CT_FIELDS(X)
+#undef X
+    if (!ok) return hns_fail(fn, "every parameter pointer must be a non-NULL fp32 array");
     if (has_others && (!n->embed_others_w || !n->embed_others_b)) return hns_fail(fn, "state_others embedding missing (num_agents > 1)");
     if (actor && !n->log_std) return hns_fail(fn, "the actor needs log_std");
-    s.ew[0] = n->embed_self_w; s.eb[0] = n->embed_self_b;
     s.ew[1] = has_others ? n->embed_others_w : nullptr; s.eb[1] = has_others ? n->embed_others_b : nullptr;
-    s.ew[2] = n->embed_cyl_w; s.eb[2] = n->embed_cyl_b;
-    s.ln_w = n->ln_w; s.ln_b = n->ln_b; s.in_w = n->in_proj_w; s.in_b = n->in_proj_b; s.out_w = n->out_proj_w; s.out_b = n->out_proj_b;
-    s.l1_w = n->linear1_w; s.l1_b = n->linear1_b; s.l2_w = n->linear2_w; s.l2_b = n->linear2_b;
-    s.n1_w = n->norm1_w; s.n1_b = n->norm1_b; s.n2_w = n->norm2_w; s.n2_b = n->norm2_b;
-    s.head_w = n->head_w; s.head_b = n->head_b; s.log_std = actor ? n->log_std : nullptr; s.head_n = actor ? 4 : 1;
-    (void)D;
+    s.log_std = actor ? n->log_std : nullptr; s.head_n = actor ? 4 : 1;
     return HNS_OK;
 }
 
@@ -425,10 +281,10 @@ int hns_policy_pack(const hns_policy_net *actor, const hns_policy_net *critic, i
     if (self_dim < 1 || self_dim > hns::kPolMaxSelf) return hns_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kPolMaxSelf) + "]");
     if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return hns_fail(fn, "num_agents must be in [1, 7]");
     if (!packed || !hns_aligned(packed, 16)) return hns_fail(fn, "packed image must be a 16-byte aligned device array");
-    hns::PolNetSrc sa{}, sc{};
-    int rc = pol_net(fn, actor, self_dim, num_agents > 1, true, sa);
+    hns::EncNet sa{}, sc{};
+    int rc = pol_net(fn, actor, num_agents > 1, true, sa);
     if (rc != HNS_OK) return rc;
-    rc = pol_net(fn, critic, self_dim, num_agents > 1, false, sc);
+    rc = pol_net(fn, critic, num_agents > 1, false, sc);
     if (rc != HNS_OK) return rc;
     hipLaunchKernelGGL(hns::hns_policy_pack_kernel, dim3(512), dim3(256), 0, static_cast<hipStream_t>(stream), sa, sc, (int)self_dim,
                        static_cast<float *>(packed));
@@ -475,8 +331,8 @@ int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, i
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_forward_kernel),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));   // 72 KB: above the default cap
     HNS_CHECK_HIP(attr);
-    const long long grid = (a.rows + hns::kPolRows - 1) / hns::kPolRows;
-    hipLaunchKernelGGL(hns::hns_policy_forward_kernel, dim3((unsigned)grid), dim3(hns::kPolThreads), sizeof(hns::PolLds), st, a);
+    const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
+    hipLaunchKernelGGL(hns::hns_policy_forward_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), st, a);
     HNS_CHECK_HIP(hipGetLastError());
     if (!value_only && !det && !io->eps) {
         hipLaunchKernelGGL(hns::hns_policy_bump_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<unsigned long long *>(counter));

@@ -6,7 +6,9 @@
 // clipped), mean loss(ret, values)) with nn.HuberLoss(delta) or nn.MSELoss; backward; clip_grad_norm_; torch.optim.Adam.  DESIGN.md §7.4.
 //
 // The network is the one of hns_policy.hip (single-query algebra): per row six 128 x 128 products forward (W_q, W_k^T, W_v, W_o, W_1,
-// W_2) and six against the transposes backward, on v_mfma_f32_16x16x4_f32 for 32 rows at a time, and two token passes on the VALU.
+// W_2) and six against the transposes backward, on v_mfma_f32_16x16x4_f32 for 32 rows at a time, and two token passes on the VALU.  The forward
+// pass' pieces (tile shape, matrix-vector product, LayerNorm, token embedding, online-softmax step, parameter table, fragment order) are
+// hns_encoder.h's, shared with hns_policy.hip; from the loss onwards everything is here.
 //   hns_critic_pack_kernel   : the six matrices in both orientations in MFMA A-operand fragment order, the embedding weights transposed.
 //   hns_critic_kernel<false> : forward of the minibatch rows: values, per-tile fp64 partials of sum loss(v), sum loss(clipped), sum (v - ret)^2,
 //                              sum ret, sum ret^2.
@@ -37,18 +39,14 @@
 #include <string>
 
 #include "hns_device.h"
+#include "hns_encoder.h"
 #include "hns_host.h"
 #include "../../include/hns.h"
 
 namespace hns {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kCtE = 128;
-constexpr int kCtRows = 32;                  // rows per tile (two 16-wide MFMA column blocks)
-constexpr int kCtLd = kCtRows + 16;          // LDS pitch of the [feature][row] activations (hns_policy.hip)
-constexpr int kCtThreads = 256;
-constexpr int kCtMat = kCtE * kCtE;
+// hns_encoder.h's tile under this file's names (the backward pass, the wgrad kernel and the host section use them throughout)
+constexpr int kCtE = kEncE, kCtRows = kEncRows, kCtLd = kEncLd, kCtThreads = kEncThreads, kCtMat = kEncMat;
 constexpr int kCtRedLd = kCtE + 4;           // LDS pitch of the [row][feature] images the cross-row sums read
 constexpr int kCtMaxSplits = 48;             // row ranges of the weight-gradient kernel
 constexpr int kCtGemmLd = kCtE + 16;         // LDS pitch of the staged operand tiles: the four k rows of an operand read fall in distinct banks
@@ -75,32 +73,17 @@ constexpr int kActLossSlots = 1 + 3 * HNS_MAX_AGENTS;   // a tile's fp64 partial
 static __host__ __device__ constexpr int ct_partial_floats(int D, int heads = 1) { return O_EWS + D * kCtE + (heads > 1 ? (heads - 1) * kCtE + heads : 0); }
 static_assert((6 * kCtGemmOut + 31) / 32 + (ct_partial_floats(kCtMaxSelf, kActDim) + 31) / 32 <= kCtMaxBlocks, "the reduce kernel's grid outgrew its per-block sums");
 
-struct CtNet {
-    const float *ew[3], *eb[3], *ln_w, *ln_b, *in_w, *in_b, *out_w, *out_b, *l1_w, *l1_b, *l2_w, *l2_b, *n1_w, *n1_b, *n2_w, *n2_b, *head_w, *head_b;
-};
 struct CtGrad {
     float *ew[3], *eb[3], *ln_w, *ln_b, *in_w, *in_b, *out_w, *out_b, *l1_w, *l1_b, *l2_w, *l2_b, *n1_w, *n1_b, *n2_w, *n2_b, *head_w, *head_b;
     float *log_std;                          // the actor's; NULL for the critic
 };
 
-__global__ __launch_bounds__(256) void hns_critic_pack_kernel(const CtNet s, int D, float *img) {
+__global__ __launch_bounds__(256) void hns_critic_pack_kernel(const EncNet s, int D, float *img) {
     const long long n = ct_img_floats(D);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         float v;
-        if (i < I_EW) {
-            const int m = (int)(i / kCtMat), x = (int)(i % kCtMat);
-            const int u = x & 3, lane = (x >> 2) & 63, s4 = (x >> 8) & 7, rb = x >> 11;
-            const int row = rb * 16 + (lane & 15), k = 4 * (4 * s4 + u) + (lane >> 4);
-            const int a = m >= 6 ? k : row, b = m >= 6 ? row : k;        // element [a][b] of the forward-orientation matrix
-            switch (m % 6) {
-                case 0: v = s.in_w[a * kCtE + b]; break;
-                case 1: v = s.in_w[(kCtE + b) * kCtE + a]; break;       // W_k^T
-                case 2: v = s.in_w[(2 * kCtE + a) * kCtE + b]; break;
-                case 3: v = s.out_w[a * kCtE + b]; break;
-                case 4: v = s.l1_w[a * kCtE + b]; break;
-                default: v = s.l2_w[a * kCtE + b]; break;
-            }
-        } else {
+        if (i < I_EW) v = enc_mat_src(s, (int)(i / kCtMat), (int)(i % kCtMat));
+        else {
             const long long e = i - I_EW;
             const int in = (int)(e / kCtE), f = (int)(e % kCtE);
             if (in < D) v = s.ew[0][f * D + in];
@@ -113,7 +96,7 @@ __global__ __launch_bounds__(256) void hns_critic_pack_kernel(const CtNet s, int
 
 struct CtArgs {
     const float *img;
-    CtNet net;
+    EncNet net;
     const float *xs, *xo, *xc;               // element (n, t, a, [j,] i) at n s?[0] + t s?[1] + a s?[2] (+ j s?[3]) + i
     long long ss[3], so[4], sc[4];
     long long T, steps;                      // env-steps = num_envs T
@@ -133,7 +116,6 @@ struct CtArgs {
     long long stage_rows;
     // the actor (HEAD = 4) alone
     const float *action;                     // [steps, A, 4]
-    const float *log_std;                    // [4]
     float clip_lo, clip_hi;                  // f32(1 - clip_param), f32(1 + clip_param): torch.clamp's bounds on a float tensor
 };
 
@@ -147,100 +129,10 @@ struct CtLds {
 };
 constexpr size_t kCtLdsFwd = offsetof(CtLds, p);
 
-HNS_DEV f32x4 cmfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// OUT[128][R] = W[128][128] IN[128][R]; EPI 0: + bias; 1: gelu(. + bias); 2: times 1/sqrt(128); 3: nothing; 4: . + bias to out2, its gelu to out.
-// `stage` (or NULL): the tile's [32][128] block of a staging array, receives what `out` receives.
-template <int EPI>
-HNS_DEV void ct_matvec(const float *__restrict__ W, const float *__restrict__ bias, const float *in, float *out, float *out2, float *stage, int w, int lane) {
-    const int col = lane & 15, kq = lane >> 4;
-    f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const f32x4 *A0 = reinterpret_cast<const f32x4 *>(W) + (2 * w) * 8 * 64 + lane;
-    const f32x4 *A1 = A0 + 8 * 64;
-#pragma unroll
-    for (int s4 = 0; s4 < 8; ++s4) {
-        const f32x4 a0 = A0[s4 * 64], a1 = A1[s4 * 64];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int k = 4 * (4 * s4 + u) + kq;
-            const float b0 = in[k * kCtLd + col], b1 = in[k * kCtLd + 16 + col];
-            acc[0][0] = cmfma(a0[u], b0, acc[0][0]);
-            acc[0][1] = cmfma(a0[u], b1, acc[0][1]);
-            acc[1][0] = cmfma(a1[u], b0, acc[1][0]);
-            acc[1][1] = cmfma(a1[u], b1, acc[1][1]);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int f0 = (2 * w + i) * 16 + 4 * kq;
-            f32x4 o;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float v = acc[i][c][r];
-                if (EPI == 2) v = v * 0.08838834764831845f;        // 1 / sqrt(128)
-                else if (EPI != 3) v = v + bias[f0 + r];
-                if (EPI == 4) out2[(f0 + r) * kCtLd + c * 16 + col] = v;
-                if (EPI == 1 || EPI == 4) v = 0.5f * v * (1.0f + erff(v * 0.7071067811865476f));
-                out[(f0 + r) * kCtLd + c * 16 + col] = v;
-                o[r] = v;
-            }
-            if (stage) *reinterpret_cast<f32x4 *>(stage + (c * 16 + col) * kCtE + f0) = o;
-        }
-}
-
-// the thread's 16 features of a row: f = 4 g + 32 i + u (g = the lane in the row's group of eight)
-HNS_DEV int cfeat(int g, int i, int u) { return 4 * g + 32 * i + u; }
-
-HNS_DEV float crow_sum8(float v) {
-    v += __shfl_xor(v, 1, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 4, 64);
-    return v;
-}
-
-HNS_DEV void cvec_load(const float *p, int g, float (&x)[16]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(p + cfeat(g, i, 0));
-#pragma unroll
-        for (int u = 0; u < 4; ++u) x[4 * i + u] = v[u];
-    }
-}
-
-// LayerNorm(128), eps 1e-5 (the statements of hns_policy.hip's pol_layernorm): xh = the normalised vector, y = xh w + b; returns 1 / std
-HNS_DEV float ct_ln(const float (&x)[16], const float *w, const float *b, int g, float (&xh)[16], float (&y)[16]) {
-    float s = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s += x[i];
-    const float mean = crow_sum8(s) * (1.0f / kCtE);
-    float q = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        xh[i] = x[i] - mean;
-        q = __builtin_fmaf(xh[i], xh[i], q);
-    }
-    const float rstd = 1.0f / __builtin_sqrtf(crow_sum8(q) * (1.0f / kCtE) + 1e-5f);
-    float wv[16], bv[16];
-    cvec_load(w, g, wv);
-    cvec_load(b, g, bv);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        xh[i] = xh[i] * rstd;
-        y[i] = xh[i] * wv[i] + bv[i];
-    }
-    return rstd;
-}
-
 // LayerNorm backward: dx = rstd (g - mean(g) - xh mean(g xh)) with g = dy w; dw += dy xh, db += dy
 HNS_DEV void ct_ln_bwd(const float (&dy)[16], const float (&xh)[16], float rstd, const float *w, int g, float (&dx)[16], float (&dw)[16], float (&db)[16]) {
     float wv[16], gi[16];
-    cvec_load(w, g, wv);
+    enc_vec_load(w, g, wv);
     float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -250,54 +142,22 @@ HNS_DEV void ct_ln_bwd(const float (&dy)[16], const float (&xh)[16], float rstd,
         dw[i] = __builtin_fmaf(dy[i], xh[i], dw[i]);
         db[i] += dy[i];
     }
-    const float m1 = crow_sum8(s1) * (1.0f / kCtE), m2 = crow_sum8(s2) * (1.0f / kCtE);
+    const float m1 = row_sum8(s1) * (1.0f / kCtE), m2 = row_sum8(s2) * (1.0f / kCtE);
 #pragma unroll
     for (int i = 0; i < 16; ++i) dx[i] = rstd * ((gi[i] - m1) - xh[i] * m2);
 }
 
-// token = LN(embedding of the n inputs at x (NULL: zeros) + bias): t, its normalised vector xh; returns 1 / std
-HNS_DEV float ct_token(const float *ewT, const float *eb, const float *x, int n, const float *lnw, const float *lnb, int g, float (&xh)[16], float (&t)[16]) {
+// a token of the updates: the bias joins last
+HNS_DEV float ct_token(const float *ewT, const float *eb, const float *x, int n, const EncNet &N, int g, float (&xh)[16], float (&t)[16]) {
     asm volatile("" ::: "memory");                              // the embedding rows are loaded per token, not hoisted out of the token loops
-    float e[16], eb16[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) e[i] = 0.0f;
-    if (x) {
-        for (int k = 0; k < n; ++k) {
-            const float xv = x[k];
-            const float *wr = ewT + k * kCtE;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const f32x4 wv = *reinterpret_cast<const f32x4 *>(wr + cfeat(g, i, 0));
-#pragma unroll
-                for (int u = 0; u < 4; ++u) e[4 * i + u] = __builtin_fmaf(wv[u], xv, e[4 * i + u]);
-            }
-        }
-    }
-    cvec_load(eb, g, eb16);                                     // the bias last (one rounding at its magnitude, as F.linear: near-constant tokens)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) e[i] += eb16[i];
-    return ct_ln(e, lnw, lnb, g, xh, t);
-}
-
-HNS_DEV void clds_load(const float *buf, int r, int g, float (&x)[16]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) x[4 * i + u] = buf[cfeat(g, i, u) * kCtLd + r];
-}
-
-HNS_DEV void clds_store(float *buf, int r, int g, const float (&x)[16]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int u = 0; u < 4; ++u) buf[cfeat(g, i, u) * kCtLd + r] = x[4 * i + u];
+    return enc_token<false>(ewT, eb, x, n, N.ln_w, N.ln_b, g, xh, t);
 }
 
 // the row's vector into a [row][feature] image (LDS pitch kCtRedLd, or a staging block at pitch 128)
 HNS_DEV void crow_store(float *img, int pitch, int r, int g, const float (&x)[16]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-        *reinterpret_cast<f32x4 *>(img + r * pitch + cfeat(g, i, 0)) = f32x4{x[4 * i], x[4 * i + 1], x[4 * i + 2], x[4 * i + 3]};
+        *reinterpret_cast<f32x4 *>(img + r * pitch + enc_feat(g, i, 0)) = f32x4{x[4 * i], x[4 * i + 1], x[4 * i + 2], x[4 * i + 3]};
 }
 
 // sum of the vector over rows 0-15 and 16-31 of the tile, written to the tile's two partial rows at `off` (fixed order)
@@ -351,11 +211,11 @@ HNS_DEV float ct_token_j(const CtArgs &a, const CtRow &R, int j, int g, float (&
     if (j < a.A) {
         x = R.xo ? R.xo + (j - 1) * a.so[3] : nullptr;
         n = 3;
-        return ct_token(ewo, a.net.eb[1], x, 3, a.net.ln_w, a.net.ln_b, g, xh, t);
+        return ct_token(ewo, a.net.eb[1], x, 3, a.net, g, xh, t);
     }
     x = R.xc ? R.xc + (j - a.A) * a.sc[3] : nullptr;
     n = 5;
-    return ct_token(ewo + 3 * kCtE, a.net.eb[2], x, 5, a.net.ln_w, a.net.ln_b, g, xh, t);
+    return ct_token(ewo + 3 * kCtE, a.net.eb[2], x, 5, a.net, g, xh, t);
 }
 
 template <bool BWD, int HEAD = 1>
@@ -365,7 +225,7 @@ __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(con
     CtLds &L = *reinterpret_cast<CtLds *>(lds_raw);
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
     const float *img = a.img;
-    const CtNet &N = a.net;
+    const EncNet &N = a.net;
     const int ntok = a.A + a.K;
     float *part = BWD ? a.tilepart + (long long)blockIdx.x * 2 * a.P : nullptr;
 
@@ -378,20 +238,17 @@ __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(con
 
         // ---- forward
         float t[16], xh[16];
-        ct_token(img + I_EW, N.eb[0], R.xs, a.D, N.ln_w, N.ln_b, g, xh, t);                 // token 0
-        clds_store(L.a, r, g, t);
+        ct_token(img + I_EW, N.eb[0], R.xs, a.D, N, g, xh, t);                 // token 0
+        enc_lds_store(L.a, r, g, t);
         if (BWD) crow_store(stg + 1 * SA, kCtE, r, g, t);
         __syncthreads();
-        ct_matvec<0>(img + 0 * kCtMat, N.in_b, L.a, L.b, nullptr, BWD ? stg + 2 * SA : nullptr, w, lane);          // q
+        enc_matvec<0>(img + 0 * kCtMat, N.in_b, L.a, L.b, nullptr, BWD ? stg + 2 * SA : nullptr, w, lane);          // q
         __syncthreads();
-        ct_matvec<2>(img + 1 * kCtMat, nullptr, L.b, L.c, nullptr, nullptr, w, lane);       // W_k^T q / sqrt(128)
+        enc_matvec<2>(img + 1 * kCtMat, nullptr, L.b, L.c, nullptr, nullptr, w, lane);       // W_k^T q / sqrt(128)
         __syncthreads();
         float kq[16], z[16];
-        clds_load(L.c, r, g, kq);
-        float s = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s = __builtin_fmaf(kq[i], t[i], s);
-        float m = crow_sum8(s), l = 1.0f;
+        enc_lds_load(L.c, r, g, kq);
+        float s, m = enc_score(kq, t), l = 1.0f;
         const float s0 = m;
 #pragma unroll
         for (int i = 0; i < 16; ++i) z[i] = t[i];
@@ -399,55 +256,46 @@ __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(con
             const float *x;
             int n;
             ct_token_j(a, R, j, g, xh, t, x, n);
-            s = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) s = __builtin_fmaf(kq[i], t[i], s);
-            s = crow_sum8(s);
-            const float mn = s > m ? s : m;
-            const float c = expf(m - mn), p = expf(s - mn);
-            l = l * c + p;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) z[i] = __builtin_fmaf(p, t[i], z[i] * c);
-            m = mn;
+            enc_softmax_step(kq, t, m, l, z);
         }
         const float il = 1.0f / l;
 #pragma unroll
         for (int i = 0; i < 16; ++i) z[i] *= il;
-        clds_store(L.b, r, g, z);
+        enc_lds_store(L.b, r, g, z);
         if (BWD) crow_store(stg + 5 * SA, kCtE, r, g, z);
         __syncthreads();
-        ct_matvec<0>(img + 2 * kCtMat, N.in_b + 2 * kCtE, L.b, L.c, nullptr, BWD ? stg + 7 * SA : nullptr, w, lane);   // v = W_v z + b_v
+        enc_matvec<0>(img + 2 * kCtMat, N.in_b + 2 * kCtE, L.b, L.c, nullptr, BWD ? stg + 7 * SA : nullptr, w, lane);   // v = W_v z + b_v
         __syncthreads();
-        ct_matvec<0>(img + 3 * kCtMat, N.out_b, L.c, L.b, nullptr, nullptr, w, lane);       // attn
+        enc_matvec<0>(img + 3 * kCtMat, N.out_b, L.c, L.b, nullptr, nullptr, w, lane);       // attn
         __syncthreads();
         float x1[16], xh1[16], u[16];
-        clds_load(L.a, r, g, u);
-        clds_load(L.b, r, g, t);
+        enc_lds_load(L.a, r, g, u);
+        enc_lds_load(L.b, r, g, t);
 #pragma unroll
         for (int i = 0; i < 16; ++i) u[i] += t[i];
-        const float rstd1 = ct_ln(u, N.n1_w, N.n1_b, g, xh1, x1);                           // x0' = LN1(x0 + attn)
-        clds_store(L.a, r, g, x1);
+        const float rstd1 = enc_layernorm(u, N.n1_w, N.n1_b, g, xh1, x1);                           // x0' = LN1(x0 + attn)
+        enc_lds_store(L.a, r, g, x1);
         if (BWD) crow_store(stg + 9 * SA, kCtE, r, g, x1);
         __syncthreads();
-        if (BWD) ct_matvec<4>(img + 4 * kCtMat, N.l1_b, L.a, L.b, L.p, stg + 11 * SA, w, lane);   // h = gelu(W_1 x0' + b_1), the pre-activation to p
-        else ct_matvec<1>(img + 4 * kCtMat, N.l1_b, L.a, L.b, nullptr, nullptr, w, lane);
+        if (BWD) enc_matvec<4>(img + 4 * kCtMat, N.l1_b, L.a, L.b, L.p, stg + 11 * SA, w, lane);   // h = gelu(W_1 x0' + b_1), the pre-activation to p
+        else enc_matvec<1>(img + 4 * kCtMat, N.l1_b, L.a, L.b, nullptr, nullptr, w, lane);
         __syncthreads();
-        ct_matvec<0>(img + 5 * kCtMat, N.l2_b, L.b, L.c, nullptr, nullptr, w, lane);        // W_2 h + b_2
+        enc_matvec<0>(img + 5 * kCtMat, N.l2_b, L.b, L.c, nullptr, nullptr, w, lane);        // W_2 h + b_2
         __syncthreads();
         float y[16], xh2[16];
-        clds_load(L.c, r, g, t);
+        enc_lds_load(L.c, r, g, t);
 #pragma unroll
         for (int i = 0; i < 16; ++i) u[i] = x1[i] + t[i];
-        const float rstd2 = ct_ln(u, N.n2_w, N.n2_b, g, xh2, y);                            // y = LN2(x0' + ff)
+        const float rstd2 = enc_layernorm(u, N.n2_w, N.n2_b, g, xh2, y);                            // y = LN2(x0' + ff)
         float dv = 0.0f, dmu[HEAD];
         float dy[16], dw[16], db[16], dx[16];
         if constexpr (HEAD == 1) {
             float hw[16];
-            cvec_load(N.head_w, g, hw);
+            enc_vec_load(N.head_w, g, hw);
             s = 0.0f;
 #pragma unroll
             for (int i = 0; i < 16; ++i) s = __builtin_fmaf(hw[i], y[i], s);
-            const float v = crow_sum8(s) + N.head_b[0];
+            const float v = row_sum8(s) + N.head_b[0];
             float ret = 0.0f, bv = 0.0f;
             if (R.live) {
                 ret = a.bret[R.e * a.A + R.ag];
@@ -503,12 +351,12 @@ __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(con
             double lp = 0.0;
 #pragma unroll
             for (int i = 0; i < HEAD; ++i) {
-                cvec_load(N.head_w + i * kCtE, g, hr);              // fc_mean.weight's row, read again in the backward pass (not kept)
+                enc_vec_load(N.head_w + i * kCtE, g, hr);              // fc_mean.weight's row, read again in the backward pass (not kept)
                 s = 0.0f;
 #pragma unroll
                 for (int q = 0; q < 16; ++q) s = __builtin_fmaf(hr[q], y[q], s);
-                const float mu = crow_sum8(s) + N.head_b[i];
-                const float ls = a.log_std[i];
+                const float mu = row_sum8(s) + N.head_b[i];
+                const float ls = N.log_std[i];
                 const double iv = exp(-2.0 * (double)ls);                          // 1 / sigma^2
                 const float act = R.live ? a.action[(R.e * a.A + R.ag) * HEAD + i] : mu;
                 const double dm = (double)act - (double)mu, z2 = dm * dm * iv;
@@ -553,13 +401,13 @@ __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(con
             }
 #pragma unroll
             for (int i = 0; i < HEAD; ++i) {
-                cvec_load(N.head_w + i * kCtE, g, hr);
+                enc_vec_load(N.head_w + i * kCtE, g, hr);
 #pragma unroll
                 for (int q = 0; q < 16; ++q) dy[q] = __builtin_fmaf(dmu[i], hr[q], dy[q]);
             }
         }
         ct_ln_bwd(dy, xh2, rstd2, N.n2_w, g, dx, dw, db);       // dx = d(x0' + ff)
-        clds_store(L.b, r, g, dx);
+        enc_lds_store(L.b, r, g, dx);
         crow_store(stg + 10 * SA, kCtE, r, g, dx);
         if constexpr (HEAD == 1) {
             if (g == 0) L.sc[r] = dv;
@@ -609,23 +457,23 @@ __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(con
                 *dst = sb;
             }
         }
-        ct_matvec<3>(img + 11 * kCtMat, nullptr, L.b, L.c, nullptr, nullptr, w, lane);      // dh = W_2^T dff
+        enc_matvec<3>(img + 11 * kCtMat, nullptr, L.b, L.c, nullptr, nullptr, w, lane);      // dh = W_2^T dff
         __syncthreads();
-        clds_load(L.c, r, g, t);
-        clds_load(L.p, r, g, u);
+        enc_lds_load(L.c, r, g, t);
+        enc_lds_load(L.p, r, g, u);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {                          // gelu'(x) = Phi(x) + x phi(x)
             const float xx = u[i];
             const float dg = 0.5f * (1.0f + erff(xx * 0.7071067811865476f)) + xx * (0.3989422804014327f * expf(-0.5f * xx * xx));
             t[i] = t[i] * dg;
         }
-        clds_store(L.c, r, g, t);
+        enc_lds_store(L.c, r, g, t);
         crow_store(stg + 8 * SA, kCtE, r, g, t);
         __syncthreads();
-        ct_matvec<3>(img + 10 * kCtMat, nullptr, L.c, L.p, nullptr, nullptr, w, lane);      // W_1^T dh'
+        enc_matvec<3>(img + 10 * kCtMat, nullptr, L.c, L.p, nullptr, nullptr, w, lane);      // W_1^T dh'
         __syncthreads();
-        clds_load(L.b, r, g, dy);
-        clds_load(L.p, r, g, t);
+        enc_lds_load(L.b, r, g, dy);
+        enc_lds_load(L.p, r, g, t);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             dy[i] += t[i];                                      // d x0'
@@ -633,22 +481,22 @@ __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(con
             db[i] = 0.0f;
         }
         ct_ln_bwd(dy, xh1, rstd1, N.n1_w, g, dx, dw, db);       // dx = d(x0 + attn)
-        clds_store(L.a, r, g, dx);
+        enc_lds_store(L.a, r, g, dx);
         crow_store(stg + 6 * SA, kCtE, r, g, dx);
         ct_flush(L, dw, part, a.P, O_N1W, tid, r, g);
         ct_flush(L, db, part, a.P, O_N1B, tid, r, g);
-        ct_matvec<3>(img + 9 * kCtMat, nullptr, L.a, L.b, nullptr, stg + 4 * SA, w, lane);  // dv = W_o^T dattn
+        enc_matvec<3>(img + 9 * kCtMat, nullptr, L.a, L.b, nullptr, stg + 4 * SA, w, lane);  // dv = W_o^T dattn
         __syncthreads();
-        ct_matvec<3>(img + 8 * kCtMat, nullptr, L.b, L.c, nullptr, nullptr, w, lane);       // dz = W_v^T dv
+        enc_matvec<3>(img + 8 * kCtMat, nullptr, L.b, L.c, nullptr, nullptr, w, lane);       // dz = W_v^T dv
         __syncthreads();
 
         // ---- token pass backward: alpha_j = exp(s_j - m) / l, ds_j = alpha_j (dz.t_j - dz.z), dt_j = alpha_j dz + ds_j kq
         float dz[16], dkq[16], dt0[16];
-        clds_load(L.c, r, g, dz);
+        enc_lds_load(L.c, r, g, dz);
         s = 0.0f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) s = __builtin_fmaf(dz[i], z[i], s);
-        const float dzz = crow_sum8(s);
+        const float dzz = row_sum8(s);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             dw[i] = 0.0f;                                       // d ln_w, d ln_b over every token of the row
@@ -656,11 +504,11 @@ __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(con
         }
         {
             // token 0: its LayerNorm backward waits for W_q^T dq
-            ct_token(img + I_EW, N.eb[0], R.xs, a.D, N.ln_w, N.ln_b, g, xh, t);
+            ct_token(img + I_EW, N.eb[0], R.xs, a.D, N, g, xh, t);
             s = 0.0f;
 #pragma unroll
             for (int i = 0; i < 16; ++i) s = __builtin_fmaf(dz[i], t[i], s);
-            const float al = expf(s0 - m) * il, ds = al * (crow_sum8(s) - dzz);
+            const float al = expf(s0 - m) * il, ds = al * (row_sum8(s) - dzz);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 dt0[i] = __builtin_fmaf(ds, kq[i], al * dz[i]);
@@ -679,7 +527,7 @@ __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(con
                 sa = __builtin_fmaf(kq[i], t[i], sa);
                 sd = __builtin_fmaf(dz[i], t[i], sd);
             }
-            const float al = expf(crow_sum8(sa) - m) * il, ds = al * (crow_sum8(sd) - dzz);
+            const float al = expf(row_sum8(sa) - m) * il, ds = al * (row_sum8(sd) - dzz);
             float dt[16], de[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
@@ -722,20 +570,20 @@ __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(con
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) dkq[i] *= 0.08838834764831845f;          // d(W_k^T q) = dkq / sqrt(128)
-        clds_store(L.b, r, g, dkq);
+        enc_lds_store(L.b, r, g, dkq);
         crow_store(stg + 3 * SA, kCtE, r, g, dkq);
         __syncthreads();
-        ct_matvec<3>(img + 7 * kCtMat, nullptr, L.b, L.c, nullptr, stg + 0 * SA, w, lane);  // dq = W_k d(W_k^T q)
+        enc_matvec<3>(img + 7 * kCtMat, nullptr, L.b, L.c, nullptr, stg + 0 * SA, w, lane);  // dq = W_k d(W_k^T q)
         __syncthreads();
-        ct_matvec<3>(img + 6 * kCtMat, nullptr, L.c, L.b, nullptr, nullptr, w, lane);       // W_q^T dq
+        enc_matvec<3>(img + 6 * kCtMat, nullptr, L.c, L.b, nullptr, nullptr, w, lane);       // W_q^T dq
         __syncthreads();
         {
             float de[16];
-            clds_load(L.a, r, g, u);
-            clds_load(L.b, r, g, y);
+            enc_lds_load(L.a, r, g, u);
+            enc_lds_load(L.b, r, g, y);
 #pragma unroll
             for (int i = 0; i < 16; ++i) dt0[i] = (dt0[i] + u[i]) + y[i];
-            const float rs = ct_token(img + I_EW, N.eb[0], R.xs, a.D, N.ln_w, N.ln_b, g, xh, t);
+            const float rs = ct_token(img + I_EW, N.eb[0], R.xs, a.D, N, g, xh, t);
             ct_ln_bwd(dt0, xh, rs, N.ln_w, g, de, dw, db);
             crow_store(L.red, kCtRedLd, r, g, de);
             for (int k = g; k < a.D; k += 8) L.sx[k * kCtRows + r] = R.xs ? R.xs[k] : 0.0f;
@@ -870,8 +718,8 @@ __global__ __launch_bounds__(256, 2) void hns_critic_wgrad_kernel(const float *s
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
                 const float b = sxx[k * kCtGemmLd + c * 16 + col];
-                acc[0][c] = cmfma(a0, b, acc[0][c]);
-                acc[1][c] = cmfma(a1, b, acc[1][c]);
+                acc[0][c] = enc_mfma(a0, b, acc[0][c]);
+                acc[1][c] = enc_mfma(a1, b, acc[1][c]);
             }
         }
         __syncthreads();
@@ -1042,15 +890,8 @@ int ct_check_shape(const char *fn, const Batch &b, int32_t self_dim, int32_t num
     return HNS_OK;
 }
 
-// X(field of hns_policy_net and hns_policy_grads, member of CtNet and CtGrad): every tensor both networks always have.  The state_others embedding
-// (absent with one agent) and log_std (the actor's) follow by hand in ct_bind_net.
-#define HNS_CT_FIELDS(X)                                                                                                                       \
-    X(embed_self_w, ew[0]) X(embed_self_b, eb[0]) X(embed_cyl_w, ew[2]) X(embed_cyl_b, eb[2]) X(ln_w, ln_w) X(ln_b, ln_b) X(in_proj_w, in_w)   \
-    X(in_proj_b, in_b) X(out_proj_w, out_w) X(out_proj_b, out_b) X(linear1_w, l1_w) X(linear1_b, l1_b) X(linear2_w, l2_w) X(linear2_b, l2_b)   \
-    X(norm1_w, n1_w) X(norm1_b, n1_b) X(norm2_w, n2_w) X(norm2_b, n2_b) X(head_w, head_w) X(head_b, head_b)
-
 // the parameter and gradient tables, checked and copied by ONE field list (heads > 1: the actor, whose log_std joins both)
-int ct_bind_net(const char *fn, const hns_policy_net &net, const hns_policy_grads &grads, bool others, int heads, hns::CtNet &n, hns::CtGrad &g) {
+int ct_bind_net(const char *fn, const hns_policy_net &net, const hns_policy_grads &grads, bool others, int heads, hns::EncNet &n, hns::CtGrad &g) {
     bool ok = true;
 #define X(f, m)                                                                                      \
     ok = ok && net.f && grads.f && hns_aligned(net.f, 16) && hns_aligned(grads.f, 4);                  \
@@ -1058,10 +899,9 @@ int ct_bind_net(const char *fn, const hns_policy_net &net, const hns_policy_grad
     g.m = grads.f;
     HNS_CT_FIELDS(X)
 #undef X
-    if (heads > 1) {
-        ok = ok && net.log_std && grads.log_std && hns_aligned(net.log_std, 16) && hns_aligned(grads.log_std, 4);
-        g.log_std = grads.log_std;
-    }
+    if (heads > 1) ok = ok && net.log_std && grads.log_std && hns_aligned(net.log_std, 16) && hns_aligned(grads.log_std, 4);
+    n.log_std = heads > 1 ? net.log_std : nullptr;
+    g.log_std = heads > 1 ? grads.log_std : nullptr;
     if (!ok) return hns_fail(fn, "every parameter must be a non-NULL 16-byte aligned fp32 array, every gradient a non-NULL fp32 array");
     if (others && (!net.embed_others_w || !net.embed_others_b || !grads.embed_others_w || !grads.embed_others_b || !hns_aligned(net.embed_others_b, 16)))
         return hns_fail(fn, "state_others embedding (parameter or gradient) missing or misaligned (num_agents > 1)");
@@ -1206,7 +1046,7 @@ int hns_actor_train_grad(const hns_policy_net *actor, const hns_actor_batch *bat
     if (int rc = ct_plan_call(fn, *batch, {policy_loss, entropy, ess, grad_norm, log_probs}, workspace, workspace_bytes, self_dim, num_agents, num_cylinders,
                               hns::kActDim, p, a))
         return rc;
-    a.logp_old = batch->log_probs_old; a.adv = batch->advantages; a.action = batch->action; a.log_std = actor->log_std;
+    a.logp_old = batch->log_probs_old; a.adv = batch->advantages; a.action = batch->action;
     a.clip_lo = (float)(1.0 - clip_param); a.clip_hi = (float)(1.0 + clip_param);
     a.logp_new = log_probs;
 

@@ -38,7 +38,7 @@ BAR = R.BAR
 RATIOS = {}
 SEEDS = list(range(int(os.environ.get("HNS_FUZZ_POLICY_SEEDS", 40))))      # HNS_FUZZ_POLICY_SEEDS=2000: the occasional deep run
 DEFAULT_SEEDS = 40
-TILE = 32                                                                   # kPolRows of csrc/hns_policy.hip
+TILE = 32                                                                   # kEncRows of csrc/hns_encoder.h
 
 
 def _dev(d):
