@@ -10,7 +10,8 @@ storage, and the advantage normalisation runs in its data-parallel form (one all
     python examples/rollout.py --tp --tp-train               # the predictor trained once per rollout on the device (hns_amd.tp_train.update_tp)
     python examples/rollout.py --tp --policy device          # the reference's actor / critic network (random init) on the device (hns_amd.policy)
 
-The policy is a fixed random linear map by default (there is no learner in this repository); `--policy device` runs a randomly
+The policy is a fixed random linear map by default (this loop measures the env and the rollout boundary, it does not train; the training
+loop — hns_amd.collector.DeviceCollector into hns_amd.learner.DeviceLearner — is examples/train_device.py); `--policy device` runs a randomly
 initialised network of the reference's architecture (PartialAttentionEncoder actor and critic, DiagGaussian) through hns_amd.policy."""
 import argparse
 import os

@@ -640,6 +640,24 @@ size_t hns_learner_info_workspace_bytes(long long rows);
 int hns_learner_info(const float *action, const int64_t action_stride[2], long long rows, int act_dim, const float *table, int minibatches,
                      int columns, float *out, void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * The rollout collector's per-step store (hns_amd.collector): ONE launch copies up to 16 per-env rows into time slot `slot` of
+ * their batch-major storage — segment s takes env e's row_bytes contiguous bytes at src + e src_stride and writes them at
+ * dst + e dst_stride + slot row_bytes, for e in [0, num_envs).  A tensor without a slot axis (the last step's next observation) is stored with
+ * num_slots = 1, slot = 0.  The segments travel by value in the kernel arguments (no device-side table, no allocation); each is copied in
+ * the widest of 16-, 4- and 1-byte units that src, dst, both strides and row_bytes are all multiples of.  Nothing outside the target rows
+ * is written.  One launch in one stream; no host synchronisation, capturable.  Refused before any launch: NULL segments, count outside
+ * [1, 16], num_envs < 1, num_slots < 1, slot outside [0, num_slots), a NULL src or dst, row_bytes outside [1, 2^20], src_stride < row_bytes,
+ * dst_stride < num_slots row_bytes, num_envs dst_stride (or num_envs src_stride) past int64.  Sources and destinations must not overlap.
+ */
+#define HNS_ROLLOUT_MAX_SEGMENTS 16
+typedef struct hns_rollout_segment {
+    const void *src;   /* env e's row: row_bytes contiguous bytes at src + e * src_stride */
+    void *dst;         /* storage base: env e, slot t at dst + e * dst_stride + t * row_bytes */
+    int64_t src_stride, dst_stride, row_bytes;   /* in bytes */
+} hns_rollout_segment;
+int hns_rollout_store(const hns_rollout_segment *segments, int32_t count, int64_t num_envs, int64_t slot, int64_t num_slots, void *stream);
+
 int hns_abi_version(void);
 size_t hns_cfg_size(void);  /* sizeof(hns_cfg) the library was built with (binding self-check) */
 const char *hns_last_error(void);
