@@ -545,6 +545,13 @@ int hns_policy_pack(const hns_policy_net *actor, const hns_policy_net *critic, i
  * graph) draws fresh noise.  Deterministic: the same inputs give the same bits. */
 int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
                        int32_t flags, uint64_t seed, uint64_t *counter, void *stream);
+/* The actor alone, the mode of the distribution (evaluation): ONE encoder pass over the actor image (the first half of
+ * `packed`), io->action[row * 4 + o] = loc[o] for every row and nothing else.  The critic image, io->eps and the Philox call counter are never
+ * read, io->log_prob / io->value / io->loc are ignored (NULL is fine; non-NULL is left untouched).  `action` is bit for bit what
+ * hns_policy_forward with HNS_POLICY_DETERMINISTIC writes there.  Refused before any launch, as the forward refuses them: a NULL or misaligned
+ * packed image / io, a shape out of range, a missing or misaligned observation, a negative stride, a missing or misaligned action. */
+int hns_policy_act(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
+                   void *stream);
 
 /*
  * The MAPPO critic's update (learning/mappo.py:326-352 on make_critic's network at the defaults: critic_input obs, no rnn): value
@@ -657,6 +664,23 @@ typedef struct hns_rollout_segment {
     int64_t src_stride, dst_stride, row_bytes;   /* in bytes */
 } hns_rollout_segment;
 int hns_rollout_store(const hns_rollout_segment *segments, int32_t count, int64_t num_envs, int64_t slot, int64_t num_slots, void *stream);
+
+/*
+ * The evaluator's statistic means (hns_amd.evaluator): for each of `count` rows the mean, over the envs e in [0, num_envs) with
+ * mask[e] != 0 (every env when mask is NULL), of the values src[e * stride] that are not NaN — torch.nanmean restricted to the mask.
+ * used[i]: the values that entered row i's mean; used[count]: the masked envs.  A row with no value entering gives NaN; +-inf propagates as in
+ * IEEE addition.  The rows travel by value in the kernel arguments; one 256-thread workgroup per row sums its elements tid, tid + 256, ... in
+ * fp64 in that order, joins the partials in a fixed-order tree, divides once and rounds once to fp32: no atomics, the same inputs give the same
+ * bits.  For num_envs <= 2^20: |mean - exact| <= 2^-24 |exact| + 2^-33 mean|x|.  One launch in one stream; no allocation, no host
+ * synchronisation, capturable.  Refused before the launch: NULL rows, mean or used, count outside [1, 64], num_envs < 1, a NULL src, a
+ * misaligned src / mean (4 bytes) or used (8 bytes), a stride < 1 (or one with num_envs * stride * 4 past int64).
+ */
+#define HNS_EVAL_MAX_ROWS 64
+typedef struct hns_eval_row {
+    const float *src;   /* element e of the row is src[e * stride] */
+    int64_t stride;     /* in elements, >= 1 */
+} hns_eval_row;
+int hns_eval_means(const hns_eval_row *rows, int32_t count, int64_t num_envs, const uint8_t *mask, float *mean, int64_t *used, void *stream);
 
 int hns_abi_version(void);
 size_t hns_cfg_size(void);  /* sizeof(hns_cfg) the library was built with (binding self-check) */

@@ -235,6 +235,13 @@ class HnsRolloutSegment(C.Structure):      # hns_rollout_segment (hns_rollout_st
     _fields_ = [("src", _fp), ("dst", _fp), ("src_stride", C.c_int64), ("dst_stride", C.c_int64), ("row_bytes", C.c_int64)]
 
 
+HNS_EVAL_MAX_ROWS = 64
+
+
+class HnsEvalRow(C.Structure):             # hns_eval_row (hns_eval_means; hns_amd.evaluator): the stride in elements
+    _fields_ = [("src", _fp), ("stride", C.c_int64)]
+
+
 _LIB = None
 LIB_NAME = "libhns.so"
 
@@ -335,6 +342,8 @@ def load_library():
     lib.hns_policy_forward.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(HnsPolicyIo), C.c_int32, C.c_uint64,
                                        C.c_void_p, C.c_void_p]
     lib.hns_policy_forward.restype = C.c_int
+    lib.hns_policy_act.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(HnsPolicyIo), C.c_void_p]
+    lib.hns_policy_act.restype = C.c_int
     lib.hns_critic_train_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32]
     lib.hns_critic_train_workspace_bytes.restype = C.c_size_t
     lib.hns_critic_train_grad.argtypes = [C.POINTER(HnsPolicyNet), C.POINTER(HnsCriticBatch), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
@@ -357,6 +366,8 @@ def load_library():
     lib.hns_learner_info.restype = C.c_int
     lib.hns_rollout_store.argtypes = [C.POINTER(HnsRolloutSegment), C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]
     lib.hns_rollout_store.restype = C.c_int
+    lib.hns_eval_means.argtypes = [C.POINTER(HnsEvalRow), C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hns_eval_means.restype = C.c_int
     lib.hns_set_state.argtypes = [C.c_void_p, C.POINTER(HnsBuffers), C.c_void_p]
     lib.hns_set_state.restype = C.c_int
     lib.hns_get_state.argtypes = [C.c_void_p, C.POINTER(HnsBuffers), C.c_void_p]
@@ -394,5 +405,5 @@ def check(rc, what):
 EXPORTED_SYMBOLS = [
     "hns_create", "hns_destroy", "hns_bind", "hns_step", "hns_reset", "hns_reset_tasks", "hns_raycast", "hns_set_v_prey",
     "hns_set_smoothness_coef", "hns_set_reset_epoch", "hns_get_reset_epoch", "hns_enable_timing",
-    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_gae", "hns_rollout_normalise", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_selected_kernels", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_tp_train_workspace_bytes", "hns_tp_train_grad", "hns_tp_adam", "hns_policy_packed_bytes", "hns_policy_pack", "hns_policy_forward", "hns_critic_train_workspace_bytes", "hns_critic_train_grad", "hns_actor_train_workspace_bytes", "hns_actor_train_grad", "hns_adam_clipped", "hns_learner_info_workspace_bytes", "hns_learner_info", "hns_rollout_store", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
+    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_gae", "hns_rollout_normalise", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_selected_kernels", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_tp_train_workspace_bytes", "hns_tp_train_grad", "hns_tp_adam", "hns_policy_packed_bytes", "hns_policy_pack", "hns_policy_forward", "hns_policy_act", "hns_critic_train_workspace_bytes", "hns_critic_train_grad", "hns_actor_train_workspace_bytes", "hns_actor_train_grad", "hns_adam_clipped", "hns_learner_info_workspace_bytes", "hns_learner_info", "hns_rollout_store", "hns_eval_means", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
 ]

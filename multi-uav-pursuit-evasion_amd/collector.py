@@ -150,7 +150,8 @@ class DeviceCollector:
 
     The read-back rule rests on the collector's own step count, so two things must hold of the env: (1) an env is done only by reaching
     max_episode_length steps since its reset (pure truncation, as HideAndSeek's step decides it: no early termination), and (2) between
-    collect() calls nobody else steps, resets or loads a state into the env.  An env that can end an episode early, or that is driven from
+    collect() calls nobody else steps, resets or loads a state into the env — or, where somebody did (an evaluation on the same env:
+    hns_amd.evaluator), `restart()` is called before the next collect().  An env that can end an episode early, or that is driven from
     outside as well, needs a loop that reads `done` on every step."""
 
     def __init__(self, env, policy, num_steps):
@@ -165,6 +166,10 @@ class DeviceCollector:
         self.done_reads = 0                                      # host read-backs of `done` so far
         self._stat_keys = self._stat_sum = None
         self._episodes = 0
+
+    def restart(self):
+        """Drop the carried observation: the next collect() begins with a full reset, as the first one did (after somebody else drove the env)."""
+        self._cur = None
 
     @staticmethod
     def _obs(td):

@@ -20,6 +20,8 @@
 //   hns_policy_forward_kernel : one workgroup of four waves per kEncRows rows.  Activations live in LDS as [128 features][kEncRows rows]; wave w
 //                               owns output row blocks 2w, 2w + 1 of every product, so each weight element is read once per workgroup.  The
 //                               embedding starts its fma chain from the bias (enc_token<true>; the updates add it last: DESIGN §7.3).
+//   hns_policy_act_kernel     : the same tile, LDS and launch bounds for ONE encoder pass, the actor's: action = loc and nothing else (evaluation
+//                               reads neither the value nor the log-probability).  Bit for bit the forward's deterministic action.
 //   hns_policy_bump_kernel    : the device call counter += 1 after a sampling call (Philox counter; a captured graph draws fresh noise per replay).
 // Determinism: fixed reduction orders (butterflies over the eight lanes of a row), no atomics.
 #include <hip/hip_runtime.h>
@@ -244,6 +246,24 @@ __global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_kernel(cons
     if (live && g == 0) a.value[row] = v;
 }
 
+// the actor alone, the mode of the distribution (evaluation): the forward kernel's first encoder pass and head, nothing else read or written
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_kernel(const PolArgs a) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
+    const long long row = (long long)blockIdx.x * kEncRows + r;
+    const float *net = a.img;
+    float y[16];
+    pol_encoder(a, net, L, w, lane, r, g, row, y);
+    float loc[4];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
+    if (row < a.rows && g == 0) {
+#pragma unroll
+        for (int o = 0; o < 4; ++o) a.action[row * 4 + o] = loc[o];
+    }
+}
+
 __global__ void hns_policy_bump_kernel(unsigned long long *counter) { counter[0] += 1ull; }
 
 }  // namespace hns
@@ -265,6 +285,42 @@ int pol_net(const char *fn, const hns_policy_net *n, int has_others, bool actor,
     s.ew[1] = has_others ? n->embed_others_w : nullptr; s.eb[1] = has_others ? n->embed_others_b : nullptr;
     s.log_std = actor ? n->log_std : nullptr; s.head_n = actor ? 4 : 1;
     return HNS_OK;
+}
+
+// the checks hns_policy_forward and hns_policy_act share, in the forward's order: image / io / shape, then the observation
+int pol_check_shape(const char *fn, const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                    const hns_policy_io *io) {
+    if (!packed || !io || !hns_aligned(packed, 16)) return hns_fail(fn, "null or misaligned packed image / io");
+    if (self_dim < 1 || self_dim > hns::kPolMaxSelf) return hns_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kPolMaxSelf) + "]");
+    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return hns_fail(fn, "num_agents must be in [1, 7]");
+    if (num_cylinders < 1 || num_cylinders > HNS_MAX_CYLINDERS) return hns_fail(fn, "num_cylinders must be in [1, 16]");
+    if (num_envs < 1 || num_envs > ((int64_t)1 << 31) / HNS_MAX_AGENTS) return hns_fail(fn, "num_envs must be in [1, 2^31 / 7]");
+    return HNS_OK;
+}
+
+int pol_check_obs(const char *fn, int32_t num_agents, const hns_policy_io *io) {
+    if (!io->obs_self || !io->obs_cylinders || (num_agents > 1 && !io->obs_others)) return hns_fail(fn, "observation pointer missing");
+    if (!hns_aligned(io->obs_self, 4) || !hns_aligned(io->obs_cylinders, 4) || (io->obs_others && !hns_aligned(io->obs_others, 4)))
+        return hns_fail(fn, "misaligned observation");
+    for (int k = 0; k < 2; ++k)
+        if (io->self_stride[k] < 0) return hns_fail(fn, "negative stride");
+    for (int k = 0; k < 3; ++k)
+        if (io->others_stride[k] < 0 || io->cyl_stride[k] < 0) return hns_fail(fn, "negative stride");
+    return HNS_OK;
+}
+
+// the image, the observation and the shape; `action` the only output (the forward adds its own)
+hns::PolArgs pol_args(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io) {
+    hns::PolArgs a{};
+    a.img = static_cast<const float *>(packed);
+    a.net_floats = hns::pol_net_floats(self_dim);
+    a.xs = io->obs_self; a.xo = io->obs_others; a.xc = io->obs_cylinders;
+    a.sse = io->self_stride[0]; a.ssa = io->self_stride[1];
+    a.soe = io->others_stride[0]; a.soa = io->others_stride[1]; a.sot = io->others_stride[2];
+    a.sce = io->cyl_stride[0]; a.sca = io->cyl_stride[1]; a.sct = io->cyl_stride[2];
+    a.action = io->action;
+    a.rows = num_envs * num_agents; a.A = num_agents; a.K = num_cylinders; a.D = self_dim;
+    return a;
 }
 
 }  // namespace
@@ -295,20 +351,12 @@ int hns_policy_pack(const hns_policy_net *actor, const hns_policy_net *critic, i
 int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
                        int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
     const char *fn = "hns_policy_forward";
-    if (!packed || !io || !hns_aligned(packed, 16)) return hns_fail(fn, "null or misaligned packed image / io");
-    if (self_dim < 1 || self_dim > hns::kPolMaxSelf) return hns_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kPolMaxSelf) + "]");
-    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return hns_fail(fn, "num_agents must be in [1, 7]");
-    if (num_cylinders < 1 || num_cylinders > HNS_MAX_CYLINDERS) return hns_fail(fn, "num_cylinders must be in [1, 16]");
-    if (num_envs < 1 || num_envs > ((int64_t)1 << 31) / HNS_MAX_AGENTS) return hns_fail(fn, "num_envs must be in [1, 2^31 / 7]");
+    int rc = pol_check_shape(fn, packed, self_dim, num_envs, num_agents, num_cylinders, io);
+    if (rc != HNS_OK) return rc;
     if (flags & ~(HNS_POLICY_DETERMINISTIC | HNS_POLICY_VALUE_ONLY)) return hns_fail(fn, "unknown flag");
     const bool value_only = flags & HNS_POLICY_VALUE_ONLY, det = flags & HNS_POLICY_DETERMINISTIC;
-    if (!io->obs_self || !io->obs_cylinders || (num_agents > 1 && !io->obs_others)) return hns_fail(fn, "observation pointer missing");
-    if (!hns_aligned(io->obs_self, 4) || !hns_aligned(io->obs_cylinders, 4) || (io->obs_others && !hns_aligned(io->obs_others, 4)))
-        return hns_fail(fn, "misaligned observation");
-    for (int k = 0; k < 2; ++k)
-        if (io->self_stride[k] < 0) return hns_fail(fn, "negative stride");
-    for (int k = 0; k < 3; ++k)
-        if (io->others_stride[k] < 0 || io->cyl_stride[k] < 0) return hns_fail(fn, "negative stride");
+    rc = pol_check_obs(fn, num_agents, io);
+    if (rc != HNS_OK) return rc;
     if (!io->value || !hns_aligned(io->value, 4)) return hns_fail(fn, "value output missing or misaligned");
     if (!value_only) {
         if (!io->action || !io->log_prob || !hns_aligned(io->action, 4) || !hns_aligned(io->log_prob, 4) || (io->loc && !hns_aligned(io->loc, 4)))
@@ -316,16 +364,9 @@ int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, i
         if (!det && !io->eps && (!counter || !hns_aligned(counter, 8))) return hns_fail(fn, "sampling without eps needs the device call counter");
         if (io->eps && !hns_aligned(io->eps, 4)) return hns_fail(fn, "misaligned eps");
     }
-    hns::PolArgs a{};
-    a.img = static_cast<const float *>(packed);
-    a.net_floats = hns::pol_net_floats(self_dim);
-    a.xs = io->obs_self; a.xo = io->obs_others; a.xc = io->obs_cylinders;
-    a.sse = io->self_stride[0]; a.ssa = io->self_stride[1];
-    a.soe = io->others_stride[0]; a.soa = io->others_stride[1]; a.sot = io->others_stride[2];
-    a.sce = io->cyl_stride[0]; a.sca = io->cyl_stride[1]; a.sct = io->cyl_stride[2];
+    hns::PolArgs a = pol_args(packed, self_dim, num_envs, num_agents, num_cylinders, io);
     a.eps = io->eps; a.counter = reinterpret_cast<const unsigned long long *>(counter); a.seed = seed;
-    a.action = io->action; a.loc = io->loc; a.logp = io->log_prob; a.value = io->value;
-    a.rows = num_envs * num_agents; a.A = num_agents; a.K = num_cylinders; a.D = self_dim;
+    a.loc = io->loc; a.logp = io->log_prob; a.value = io->value;
     a.deterministic = det; a.value_only = value_only;
     const hipStream_t st = static_cast<hipStream_t>(stream);
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_forward_kernel),
@@ -338,6 +379,24 @@ int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, i
         hipLaunchKernelGGL(hns::hns_policy_bump_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<unsigned long long *>(counter));
         HNS_CHECK_HIP(hipGetLastError());
     }
+    return HNS_OK;
+}
+
+int hns_policy_act(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
+                   void *stream) {
+    const char *fn = "hns_policy_act";
+    int rc = pol_check_shape(fn, packed, self_dim, num_envs, num_agents, num_cylinders, io);
+    if (rc != HNS_OK) return rc;
+    rc = pol_check_obs(fn, num_agents, io);
+    if (rc != HNS_OK) return rc;
+    if (!io->action || !hns_aligned(io->action, 4)) return hns_fail(fn, "action output missing or misaligned");
+    const hns::PolArgs a = pol_args(packed, self_dim, num_envs, num_agents, num_cylinders, io);   // eps, counter, loc, log_prob, value stay NULL: never touched
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_act_kernel),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
+    HNS_CHECK_HIP(attr);
+    const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
+    hipLaunchKernelGGL(hns::hns_policy_act_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), static_cast<hipStream_t>(stream), a);
+    HNS_CHECK_HIP(hipGetLastError());
     return HNS_OK;
 }
 

@@ -421,6 +421,27 @@ class HideAndSeek(_EnvBase):
     def reset_epoch(self):
         return int(self._lib.hns_get_reset_epoch(self._env))
 
+    def set_reset_epoch(self, epoch):
+        """Put the reset counter back (the second word of the reset Philox stream's key, beside the seed): what `set_seed` clears and every
+        reset advances.  hns_amd.evaluator restores it after a run on a training env; `load_state` does the same from a snapshot."""
+        self._check(self._lib.hns_set_reset_epoch(self._env, C.c_uint32(int(epoch))), "hns_set_reset_epoch")
+
+    def clear_carried_state(self):
+        """Zero every state buffer, as a new env holds them.  A reset leaves some of them alone, as the reference's `_reset_idx` does: the
+        body-rate controller's integrator and last rate (task.pid_reset: reference), the first three components of `prev_action`, the
+        predictor's frame window (hideandseek.py:825-830) — so an episode's first steps depend on what ran before it.  After this call the
+        next full `reset()` starts the episodes a freshly built env of the same seed would (hns_amd.evaluator: a run is a function of its
+        seed and the networks alone).  The sticky non-finite word and the predictor's operand image stay as they are."""
+        for k, t in self._bufs.items():
+            if k != "nonfinite":
+                t.zero_()
+        if self.use_TP_net:
+            for k, t in self._tp_bufs.items():
+                if k != "packed":
+                    t.zero_()
+            self._tp_filled = False
+        self._state_version += 1
+
     def enable_render(self, enable=True):
         if not isinstance(enable, bool) and not callable(enable):                   # isaac_env.py:321-327: a bool or a callable(substep)
             raise TypeError("enable_render must be a bool or callable.")

@@ -4,7 +4,8 @@ The reference's network for this task, at cfg/algo/mappo.yaml's defaults (share_
 PartialAttentionEncoder per network (modules/networks.py:250-313: SplitEmbedding over state_self / state_others / cylinders, LayerNorm,
 single-query attention, a GELU feed-forward and two more LayerNorms; embed_dim 128), a DiagGaussian head for the actor (fc_mean 128 -> 4,
 scale = exp(log_std)) and v_out 128 -> 1 for the critic.  `DevicePolicy` runs both networks for every (env, agent) row in ONE call of
-`hns_policy_forward`: loc, an action (a sample, or the mode with deterministic=True), its log_prob and the critic's value.  The noise is the
+`hns_policy_forward`: loc, an action (a sample, or the mode with deterministic=True), its log_prob and the critic's value.  `act` runs the
+actor alone for the mode (`hns_policy_act`: evaluation).  The noise is the
 caller's eps, or Philox4x32-10 drawn in the kernel from (seed, device call counter, row) — a captured graph draws fresh noise on every replay.
 
 Parameters come from the reference's live objects (`actor_params`, a TensorDictParams of the shared actor, and the critic module) or from a
@@ -288,6 +289,20 @@ class DevicePolicy:
                 raise ValueError(f"{name} is on {t.device}, the policy on {self.device}")
         return xs, xo, xc
 
+    @staticmethod
+    def _io(xs, xo, xc):
+        """The observation part of an hns_policy_io: the tensors (made contiguous in their last axis only) with their strides."""
+        xs, xc = (t if t.stride(-1) == 1 else t.contiguous() for t in (xs, xc))
+        if xo is not None and xo.stride(-1) != 1:
+            xo = xo.contiguous()
+        io = abi.HnsPolicyIo()
+        io.obs_self, io.obs_cylinders = xs.data_ptr(), xc.data_ptr()
+        io.obs_others = xo.data_ptr() if xo is not None else None
+        io.self_stride[:] = [xs.stride(0), xs.stride(1)]
+        io.others_stride[:] = [xo.stride(0), xo.stride(1), xo.stride(2)] if xo is not None else [0, 0, 0]
+        io.cyl_stride[:] = [xc.stride(0), xc.stride(1), xc.stride(2)]
+        return xs, xo, xc, io
+
     def forward(self, obs_self, obs_others, obs_cylinders, eps=None, deterministic=False, value_only=False):
         """PolicyOutput(action [E, A, 4], log_prob [E, A, 1], value [E, A, 1], loc [E, A, 4]); value_only: only value is set."""
         xs, xo, xc = self._validate(obs_self, obs_others, obs_cylinders)
@@ -298,21 +313,13 @@ class DevicePolicy:
             with torch.no_grad():
                 return torch_forward(self.actor_p, self.critic_p, xs.unsqueeze(2), xo, xc, eps, deterministic, value_only, self._generator)
         self.refresh()
-        xs, xc = (t if t.stride(-1) == 1 else t.contiguous() for t in (xs, xc))
-        if xo is not None and xo.stride(-1) != 1:
-            xo = xo.contiguous()
+        xs, xo, xc, io = self._io(xs, xo, xc)
         eps = eps.contiguous() if eps is not None else None
         dev = self.device
         value = torch.empty(E, A, 1, device=dev)
         action = log_prob = loc = None
         if not value_only:
             action, log_prob, loc = torch.empty(E, A, ACTION_DIM, device=dev), torch.empty(E, A, 1, device=dev), torch.empty(E, A, ACTION_DIM, device=dev)
-        io = abi.HnsPolicyIo()
-        io.obs_self, io.obs_cylinders = xs.data_ptr(), xc.data_ptr()
-        io.obs_others = xo.data_ptr() if xo is not None else None
-        io.self_stride[:] = [xs.stride(0), xs.stride(1)]
-        io.others_stride[:] = [xo.stride(0), xo.stride(1), xo.stride(2)] if xo is not None else [0, 0, 0]
-        io.cyl_stride[:] = [xc.stride(0), xc.stride(1), xc.stride(2)]
         io.eps = eps.data_ptr() if eps is not None else None
         io.value = value.data_ptr()
         if not value_only:
@@ -324,6 +331,29 @@ class DevicePolicy:
                                               self.counter.data_ptr(), st)
         self._check(rc, "hns_policy_forward")
         return PolicyOutput(action, log_prob, value, loc)
+
+    def act(self, obs_self, obs_others, obs_cylinders, out=None):
+        """The mode of the actor's distribution, action [E, A, 4], from the actor alone (hns_policy_act: one encoder pass, no critic, no
+        log-prob, no noise, the call counter untouched) — bit for bit `forward(..., deterministic=True).action`.  `out`: a contiguous fp32
+        [E, A, 4] tensor on the policy's device, written in place and returned (an evaluation loop's one action tensor)."""
+        xs, xo, xc = self._validate(obs_self, obs_others, obs_cylinders)
+        E, A, _ = xs.shape
+        if out is not None and (tuple(out.shape) != (E, A, ACTION_DIM) or out.dtype != torch.float32 or out.device != self.device
+                                or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 [{E}, {A}, {ACTION_DIM}] tensor on {self.device}")
+        if self.device.type != "cuda":
+            with torch.no_grad():
+                action = torch_forward(self.actor_p, self.critic_p, xs.unsqueeze(2), xo, xc, deterministic=True).action
+            return action if out is None else out.copy_(action)
+        self.refresh()
+        xs, xo, xc, io = self._io(xs, xo, xc)
+        action = out if out is not None else torch.empty(E, A, ACTION_DIM, device=self.device)
+        io.action = action.data_ptr()
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            rc = self._lib.hns_policy_act(self.packed.data_ptr(), self.self_dim, E, A, xc.shape[2], C.byref(io), st)
+        self._check(rc, "hns_policy_act")
+        return action
 
     @staticmethod
     def _obs(td):
