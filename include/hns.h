@@ -596,8 +596,8 @@ typedef struct hns_adam_tensor {
  * min(max_norm / (*total_norm + 1e-6), 1) in place (torch's statements: the reciprocal, times max_norm, clamped), then Adam (amsgrad off, weight
  * decay 0) in the single-tensor statement order of torch's CPU kernels with step = *step + 1: m = fma(1 - b1, g - m, m); v = fma((1 - b2) g, g, v b2);
  * denom = sqrt(v) / f32(sqrt(1 - b2^step)) + f32(eps); p = p + (f32(-lr / (1 - b1^step)) m) / denom.  *step is bumped after the last tensor (one
- * launch per 64 tensors, then the bump).  total_norm NULL or max_norm = +inf: no clipping (a data-parallel caller all-reduces the gradients and
- * their norm between hns_critic_train_grad and this call). */
+ * launch per 64 tensors, then the bump).  total_norm NULL or max_norm = +inf: no clipping.  A data-parallel caller all-reduces the gradient
+ * buckets that the *_train_grad_global entries (below) filled and hands this call hns_grad_norm's device scalar over the summed bucket. */
 int hns_adam_clipped(const hns_adam_tensor *tensors, int32_t count, float *step, const float *total_norm, double max_norm, double lr, double beta1,
                      double beta2, double eps, void *stream);
 
@@ -631,6 +631,53 @@ size_t hns_actor_train_workspace_bytes(int64_t rows, int32_t self_dim, int32_t n
 int hns_actor_train_grad(const hns_policy_net *actor, const hns_actor_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
                          double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
                          float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The data-parallel learner's entries (hns_amd.learner.DeviceLearner(group=)): W ranks, each holding a part of a minibatch,
+ * perform ONE update on the union.  Per minibatch the critic runs hns_critic_train_sums, an all-reduce (SUM) of the five fp64 values,
+ * hns_critic_train_grad_global, an all-reduce (SUM) of the gradient bucket, hns_grad_norm, hns_adam_clipped; the actor runs
+ * hns_actor_train_grad_global, the bucket's all-reduce, hns_grad_norm, hns_adam_clipped.  The kernels, workspaces, refusals and properties (one
+ * stream, no host synchronisation, no allocation, capturable, fixed-order sums) are those of hns_critic_train_grad / hns_actor_train_grad;
+ * with one rank (global_rows = batch x num_agents, entropy_share 1) every output has the bits of those calls.
+ *
+ * hns_critic_train_sums: pack, forward, and the SUMMING half of the loss launch — values as hns_critic_train_grad writes them and
+ * sums[0 .. 5) = sum loss(v - ret), sum loss(clipped - ret), sum (v - ret)^2, sum ret, sum ret^2 over this rank's rows, fp64, added in exactly
+ * the order hns_critic_train_grad adds its tile partials.  sums: device, 8-byte aligned.  No gradients.  Three launches.
+ */
+int hns_critic_train_sums(const hns_policy_net *critic, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                          float clip_param, int32_t loss_kind, float huber_delta, double *sums, float *values, void *workspace, size_t workspace_bytes,
+                          void *stream);
+/* hns_critic_train_grad's arguments, then `sums` (the five values of ALL ranks' rows: the all-reduced output of hns_critic_train_sums) and
+ * `global_rows` (their row count, >= batch x num_agents).  The DECIDING half of the loss launch forms value_loss, explained_var and the branch
+ * weights of the max from `sums` with n = global_rows — one decision for the union, the same on every rank — and the backward pass scales each
+ * row by f32(1 / global_rows), so the ranks' gradients ADD UP to the union's.  It packs the operand image again (the call stands alone: the
+ * workspace need not be the one hns_critic_train_sums used) and does not run the forward launch: `values` is not written (it is
+ * hns_critic_train_sums' output; the parameter keeps the two argument lists parallel).  grad_norm may be NULL: the norm of one rank's part
+ * means nothing, and the launch is skipped.  Refused as hns_critic_train_grad refuses, plus NULL or misaligned sums, global_rows < rows. */
+int hns_critic_train_grad_global(const hns_policy_net *critic, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                                 float clip_param, int32_t loss_kind, float huber_delta, const hns_policy_grads *grads, float *value_loss,
+                                 float *explained_var, float *grad_norm, float *values, void *workspace, size_t workspace_bytes, void *stream,
+                                 const double *sums, int64_t global_rows);
+/* hns_actor_train_grad's arguments, then `global_rows` (all ranks' rows of the minibatch, >= batch x num_agents) and `entropy_share`.  Each row's
+ * backward weight is scaled by f32(1 / global_rows); policy_loss = -4 sum_local min(..) / global_rows is this rank's SHARE (the shares add up to
+ * the union's loss); the entropy term's constant gradient joins d log_std as -entropy_coef x entropy_share (1 / world, so a SUM over the ranks
+ * counts it once); entropy is the same on every rank; ess stays this rank's own (a diagnostic).  grad_norm may be NULL (launch skipped).
+ * Refused as hns_actor_train_grad refuses, plus global_rows < rows and a non-finite entropy_share. */
+int hns_actor_train_grad_global(const hns_policy_net *actor, const hns_actor_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                                double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
+                                float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream, int64_t global_rows,
+                                double entropy_share);
+/* The 2-norm of one flat fp32 gradient bucket: norm[0] = f32(sqrt(sum_i flat[i]^2)), in this order (tests/dp_reference.py restates it in numpy):
+ * the bucket is cut into quads of four consecutive floats, the last one short by numel % 4 values that count as 0 (nothing past numel is
+ * read); G = clamp(ceil(quads / 1024), 1, 64) workgroups of 256 threads, T = 256 G; thread t of the grid adds, for q = t, t + T, t + 2 T, ...,
+ * ((x x + y y) + z z) + w w of quad q in fp64 (each product exact) to its sum; within a workgroup each wave of 64 runs the butterfly
+ * s += s[lane ^ o] for o = 32, 16, 8, 4, 2, 1 and the four waves add in index order to the workgroup's partial (fp64, in `workspace`); a second
+ * launch adds the G partials in index order and rounds the fp64 square root once.  An entry of 3e19 squares to 9e38 without overflow.  Two
+ * launches in one stream; no atomics, no allocation, no host synchronisation, capturable; the same inputs give the same bits.  Refused before
+ * any launch: a NULL or misaligned pointer (flat 16 bytes, norm 4, workspace 8), numel < 1, a workspace shorter than the size function's
+ * bytes (numel < 1: 0). */
+size_t hns_grad_norm_workspace_bytes(long long numel);
+int hns_grad_norm(const float *flat, long long numel, float *norm, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * The info row of MAPPOPolicy.train_op (learning/mappo.py:463-472): the means over the minibatches of the scalars the updates wrote

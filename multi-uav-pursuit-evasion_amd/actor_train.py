@@ -11,6 +11,10 @@ tensors, as critic_train does.
 The step is optim's `ClippedAdam` (clip_grad_norm_ + torch.optim.Adam in one call of `hns_adam_clipped`) over the actor's 23 tensors; it bumps the
 parameters' version counters, so `policy.DevicePolicy` re-packs its operand image before the next forward pass.
 
+With `global_rows=` the same calls are one rank's part of a data-parallel update: `hns_actor_train_grad_global` scales the rows
+by 1 / global_rows and the entropy term by `entropy_share`, the gradients land in a `policy_train.GradBucket`, and with `group=` the bucket is
+all-reduced and its norm taken before the step.
+
 `update_actor` is the reference's function.  CPU tensors run the reference's torch statements throughout (CPU tests, gloo runs — not the
 hot path).  DESIGN.md §7.5."""
 import collections
@@ -34,7 +38,8 @@ def actor_parameters(actor):
     return P.parse_parameters(actor, P.ACTOR_NAMES, "actor")
 
 
-def _torch_loss_and_grad(p, xs, xo, xc, action, log_probs_old, advantages, index, clip_param, entropy_coef):
+def _torch_loss_and_grad(p, xs, xo, xc, action, log_probs_old, advantages, index, clip_param, entropy_coef, global_rows=None, entropy_share=1.0,
+                         group=None, bucket=None):
     """update_actor's statements (mappo.py:293-318) on the gathered minibatch, Actor.forward(eval_action=True) and DiagGaussian.forward
     (mappo.py:612-624, distributions.py:78-82) in front of them; autograd through policy_train's encoder."""
     N, T, A, D_ = xs.shape
@@ -54,19 +59,29 @@ def _torch_loss_and_grad(p, xs, xo, xc, action, log_probs_old, advantages, index
     ratio = torch.exp(log_probs_new - log_probs_old)
     surr1 = ratio * advantages
     surr2 = torch.clamp(ratio, 1.0 - clip_param, 1.0 + clip_param) * advantages
-    policy_loss = - torch.mean(torch.min(surr1, surr2) * P.ACTION_DIM)
     entropy_loss = - torch.mean(dist_entropy)
-    grads = torch.autograd.grad(policy_loss + entropy_loss * entropy_coef, list(leaves.values()))
+    if global_rows is None:
+        policy_loss = - torch.mean(torch.min(surr1, surr2) * P.ACTION_DIM)
+        total = policy_loss + entropy_loss * entropy_coef
+    else:                                                        # this rank's share of the union's mean; the entropy term counted once over the ranks
+        policy_loss = - torch.sum(torch.min(surr1, surr2) * P.ACTION_DIM) / float(global_rows)
+        total = policy_loss + entropy_loss * (entropy_coef * entropy_share)
+    grads = torch.autograd.grad(total, list(leaves.values()))
     for t, g in zip(p.values(), grads):
         t.grad = g
     with torch.no_grad():
-        grad_norm = nn.utils.clip_grad_norm_(list(p.values()), float("inf"))      # the total norm as clip_grad_norm_ forms it; scales by 1
+        if global_rows is None:
+            grad_norm = nn.utils.clip_grad_norm_(list(p.values()), float("inf"))      # the total norm as clip_grad_norm_ forms it; scales by 1
+        else:
+            if bucket is not None:
+                bucket.adopt()
+            grad_norm = PT.finish_global(bucket, group)
         ess = (2 * ratio.logsumexp(0) - (2 * ratio).logsumexp(0)).exp().mean() / ratio.shape[0]
     return ActorLoss(policy_loss.detach(), -entropy_loss.detach(), ess, grad_norm, log_probs_new.detach())
 
 
 def policy_loss_and_grad(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index=None, clip_param=0.1,
-                         entropy_coef=0.001, check_index=True, workspace=None, out=None):
+                         entropy_coef=0.001, check_index=True, workspace=None, out=None, global_rows=None, entropy_share=1.0, group=None, bucket=None):
     """The clipped PPO surrogate of the actor on a minibatch (plus entropy_coef times the entropy loss) and every parameter's .grad (as
     zero_grad() + backward() leave them, before clip_grad_norm_).  Returns ActorLoss(policy_loss, entropy, ess, grad_norm: 0-dim tensors;
     log_probs [B, A, 1]: the new log-probabilities of the stored actions).
@@ -76,15 +91,24 @@ def policy_loss_and_grad(actor, obs_self, obs_others, obs_cylinders, action, log
     the flattened [N T] (None: all).  `check_index` range-checks the index (one host synchronisation; skipped inside a graph capture).
     `workspace`: a uint8 device tensor of at least hns_actor_train_workspace_bytes bytes, 256-byte aligned, instead of one allocated per call;
     `out`: four fp32 device values that receive policy_loss, entropy, ess and grad_norm (the returned scalars are views of it) instead of a
-    tensor of the call's own.  Both are ignored on the CPU."""
+    tensor of the call's own.  Both are ignored on the CPU.
+
+    `global_rows` (None: the call above, untouched): this minibatch is one rank's part of a union of `global_rows` agent rows
+    (hns_actor_train_grad_global).  policy_loss is then this rank's SHARE, -4 sum_local / global_rows, and the gradients are the share's: over
+    the ranks both add up to the union's.  `entropy_share`: the part of the entropy term's gradient this rank adds (1 / world).  ess stays
+    this rank's own.  `bucket`: the actor's `policy_train.GradBucket`; grad_norm is then the norm of the bucket (None without one).
+    `group`: the bucket is all-reduced (SUM) over it first, so the gradients and grad_norm are the union's, the same on every rank."""
     if not clip_param >= 0:
         raise ValueError("clip_param must be >= 0")
     p = actor_parameters(actor)
     xs, xo, xc = PT.as_rollout(obs_self, obs_others, obs_cylinders)
     shape = PT.validate("actor", p, xs, xo, xc, (("action", action, P.ACTION_DIM), ("log_probs_old", log_probs_old, 1),
                                                  ("advantages", advantages, 1)), index, check_index)
+    B = index.numel() if index is not None else shape[0] * shape[1]
+    PT.check_global("actor", p, global_rows, B * shape[2], group, bucket)
     if not xs.is_cuda:
-        return _torch_loss_and_grad(p, xs, xo, xc, action, log_probs_old, advantages, index, float(clip_param), float(entropy_coef))
+        return _torch_loss_and_grad(p, xs, xo, xc, action, log_probs_old, advantages, index, float(clip_param), float(entropy_coef), global_rows,
+                                    float(entropy_share), group, bucket)
     lib = abi.load_library()
     act, lpo, adv = action.contiguous(), log_probs_old.contiguous(), advantages.contiguous()
     net, grd, b, ws, nbytes, scal, B, st = PT.prepare_call("actor", p, xs, xo, xc, index, shape, lib.hns_actor_train_workspace_bytes, workspace,
@@ -92,6 +116,14 @@ def policy_loss_and_grad(actor, obs_self, obs_others, obs_cylinders, action, log
     _, _, A, D_, K = shape
     b.action, b.log_probs_old, b.advantages = act.data_ptr(), lpo.data_ptr(), adv.data_ptr()
     log_probs = torch.empty(B, A, 1, dtype=torch.float32, device=xs.device)
+    if global_rows is not None:
+        with torch.cuda.device(xs.device):
+            rc = lib.hns_actor_train_grad_global(C.byref(net), C.byref(b), D_, A, K, float(clip_param), float(entropy_coef), C.byref(grd),
+                                                 scal[0:].data_ptr(), scal[1:].data_ptr(), scal[2:].data_ptr(), None, log_probs.data_ptr(), ws.data_ptr(),
+                                                 nbytes, st, int(global_rows), float(entropy_share))
+        abi.check(rc, "hns_actor_train_grad_global")
+        norm = PT.finish_global(bucket, group, scal[3:4])
+        return ActorLoss(scal[0], scal[1], scal[2], scal[3] if norm is not None else None, log_probs)
     with torch.cuda.device(xs.device):
         rc = lib.hns_actor_train_grad(C.byref(net), C.byref(b), D_, A, K, float(clip_param), float(entropy_coef), C.byref(grd), scal[0:].data_ptr(),
                                       scal[1:].data_ptr(), scal[2:].data_ptr(), scal[3:].data_ptr(), log_probs.data_ptr(), ws.data_ptr(), nbytes, st)
@@ -119,21 +151,25 @@ def make_optimizer(actor, cfg=None):
 
 
 def update_actor(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, optimizer, index=None, cfg=None, check_index=False,
-                 workspace=None, out=None):
+                 workspace=None, out=None, global_rows=None, entropy_share=1.0, group=None, bucket=None):
     """MAPPOPolicy.update_actor on one minibatch: loss, backward, clip_grad_norm_, Adam.  cfg: the algo cfg (clip_param, entropy_coef; the
     reference's defaults when None).  Returns {"policy_loss", "actor_grad_norm", "entropy", "ESS"} as 0-dim tensors on the parameters' device
     — the caller decides when to .item().  `optimizer`: a ClippedAdam (make_optimizer).  The index is NOT range-checked by default, as in
-    critic_train.update_critic.  `workspace`, `out`: policy_loss_and_grad's."""
+    critic_train.update_critic.  `workspace`, `out`: policy_loss_and_grad's.  `global_rows`, `entropy_share`, `group`, `bucket`:
+    policy_loss_and_grad's — one rank's part of a data-parallel update; the step needs the union's gradients, so all four travel together
+    (group may be None where the caller summed the buckets itself)."""
+    if global_rows is not None and bucket is None:
+        raise ValueError("update_actor with global_rows= steps on the bucket's norm: pass bucket=")
     if not isinstance(optimizer, ClippedAdam):
         raise TypeError(f"update_actor takes a ClippedAdam (actor_train.make_optimizer), not {type(optimizer).__name__}: the clip and the "
                         "step are one launch that needs the gradient norm")
     get, _ = actor_cfg(cfg)
-    for group in optimizer.param_groups:
-        if group.get("weight_decay", 0) != 0:
+    for pg in optimizer.param_groups:
+        if pg.get("weight_decay", 0) != 0:
             raise NotImplementedError("weight_decay != 0 is not supported")
     res = policy_loss_and_grad(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index,
                                clip_param=float(get("clip_param", 0.1)), entropy_coef=float(get("entropy_coef", 0.001)), check_index=check_index,
-                               workspace=workspace, out=out)
+                               workspace=workspace, out=out, global_rows=global_rows, entropy_share=entropy_share, group=group, bucket=bucket)
     optimizer.step(grad_norm=res.grad_norm)
     norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else res.grad_norm
     return {"policy_loss": res.policy_loss, "actor_grad_norm": norm, "entropy": res.entropy, "ESS": res.ess}

@@ -10,6 +10,11 @@ reads a minibatch of `make_dataset_naive` (mappo.py:493-513, seq_len 1) in place
 `ClippedAdam` (optim's, re-exported here) is clip_grad_norm_ + torch.optim.Adam in one call of `hns_adam_clipped`.  What this update
 shares with the actor's — the batch checks, the preparation of the C call, the encoder's restatement — lives in `policy_train`.
 
+The data-parallel form splits the call where the branch of the max is decided: `value_loss_sums` is the forward pass and the
+five fp64 sums of this rank's rows (`hns_critic_train_sums`); the caller adds the ranks' sums; `value_loss_and_grad(sums=, global_rows=)`
+decides on the union's sums and scales the rows by 1 / global_rows (`hns_critic_train_grad_global`), so the ranks' gradients add up to the
+union's in a `policy_train.GradBucket`.  `update_critic(group=)` runs the whole sequence.
+
 `update_critic` is the reference's function.  CPU tensors run the reference's torch statements throughout (CPU tests, gloo runs — not the
 hot path).  DESIGN.md §7.4."""
 import collections
@@ -25,12 +30,68 @@ from . import policy_train as PT
 from .policy_train import ClippedAdam
 
 CriticLoss = collections.namedtuple("CriticLoss", ["value_loss", "explained_var", "grad_norm", "values"])
+CriticSums = collections.namedtuple("CriticSums", ["sums", "values"])
 LOSSES = {"huber": abi.HNS_CRITIC_LOSS_HUBER, "mse": abi.HNS_CRITIC_LOSS_MSE}
 
 
 def critic_parameters(critic):
     """The critic's tensors by hns_policy_net field, in the order the module registers them (clip_grad_norm_'s order)."""
     return P.parse_parameters(critic, P.CRITIC_NAMES, "critic")
+
+
+def _gather(xs, xo, xc, b_values, b_returns, index):
+    N, T, A, D = xs.shape
+    xs, xc = xs.reshape(N * T, A, 1, D), xc.reshape(N * T, A, xc.shape[3], 5)
+    xo = xo.reshape(N * T, A, A - 1, 3) if xo is not None else None
+    bv, ret = b_values.reshape(N * T, A, 1), b_returns.reshape(N * T, A, 1)
+    if index is not None:
+        xs, xc, bv, ret = xs[index], xc[index], bv[index], ret[index]
+        xo = xo[index] if xo is not None else None
+    return xs, xo, xc, bv, ret
+
+
+def _sum_loss64(x, loss, huber_delta):
+    """sum loss(x) in fp64 from fp32 differences' operands, as hns_critic_kernel<false> forms its partials."""
+    ax = x.abs()
+    return (x * x).sum() if loss == "mse" else torch.where(ax < huber_delta, 0.5 * x * x, huber_delta * (ax - 0.5 * huber_delta)).sum()
+
+
+def _torch_sums(p, xs, xo, xc, b_values, b_returns, index, clip_param, loss, huber_delta):
+    """value_loss_sums on the CPU: the five sums of hns_critic_train_sums, fp64 from the fp32 values."""
+    xs, xo, xc, bv, ret = _gather(xs, xo, xc, b_values, b_returns, index)
+    with torch.no_grad():
+        values = F.linear(PT.encoder(p, xs, xo, xc), p["head_w"], p["head_b"])
+        clipped = bv + (values - bv).clamp(-clip_param, clip_param)
+        v, c, r = values.double(), clipped.double(), ret.double()
+        sums = torch.stack([_sum_loss64(v - r, loss, huber_delta), _sum_loss64(c - r, loss, huber_delta), ((v - r) ** 2).sum(), r.sum(), (r * r).sum()])
+    return CriticSums(sums, values)
+
+
+def _torch_loss_and_grad_global(p, xs, xo, xc, b_values, b_returns, index, clip_param, loss, huber_delta, sums, global_rows, group, bucket):
+    """hns_critic_train_grad_global on the CPU: the branch, value_loss and explained_var from the union's `sums`, the gradient of this rank's
+    rows of the chosen branch's sum over global_rows."""
+    xs, xo, xc, bv, ret = _gather(xs, xo, xc, b_values, b_returns, index)
+    n = float(global_rows)
+    S = sums.double().tolist()
+    lo, lc = S[0] / n, S[1] / n
+    w0, w1 = (1.0, 0.0) if lo > lc else ((0.0, 1.0) if lo < lc else (0.5, 0.5))
+    leaves = {k: v.detach().requires_grad_(True) for k, v in p.items()}
+    values = F.linear(PT.encoder(leaves, xs, xo, xc), leaves["head_w"], leaves["head_b"])
+    # the loss and its per-row derivative in fp64 from the fp32 values, as the kernel forms its loss partials: v - ret is not rounded to fp32
+    # before the 1 / n, so a rank's part carries the rounding of its fp32 backward pass alone
+    v64, bv64, ret64 = values.double(), bv.double(), ret.double()
+    clipped = bv64 + (v64 - bv64).clamp(-clip_param, clip_param)
+    loss_fn = nn.HuberLoss(delta=huber_delta, reduction="sum") if loss == "huber" else nn.MSELoss(reduction="sum")
+    total = (w0 * loss_fn(ret64, v64) + w1 * loss_fn(ret64, clipped)) / n
+    grads = torch.autograd.grad(total, list(leaves.values()))
+    for t, g in zip(p.values(), grads):
+        t.grad = g
+    if bucket is not None:
+        bucket.adopt()
+    grad_norm = PT.finish_global(bucket, group)
+    value_loss = torch.tensor(max(lo, lc), dtype=torch.float32)
+    explained_var = torch.tensor(1.0 - (S[2] / n) / ((S[4] - S[3] * S[3] / n) / (n - 1.0)), dtype=torch.float32)
+    return CriticLoss(value_loss, explained_var, grad_norm, values.detach())
 
 
 def _torch_loss_and_grad(p, xs, xo, xc, b_values, b_returns, index, clip_param, loss, huber_delta):
@@ -58,17 +119,12 @@ def _torch_loss_and_grad(p, xs, xo, xc, b_values, b_returns, index, clip_param, 
     return CriticLoss(value_loss.detach(), explained_var, grad_norm, values.detach())
 
 
-def value_loss_and_grad(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, index=None, clip_param=0.1, loss="huber",
-                        huber_delta=10.0, check_index=True, workspace=None, out=None):
-    """The clipped value loss of the critic on a minibatch and every parameter's .grad (as zero_grad() + backward() leave them, before
-    clip_grad_norm_).  Returns CriticLoss(value_loss, explained_var, grad_norm: 0-dim tensors; values [B, A, 1]).
-
-    obs_*: the rollout's [N, T, A, ...] observations (state_self [N, T, A, D] or [N, T, A, 1, D]; state_others None with one agent) or a
-    flat [R, A, ...] batch, read in place; b_values, b_returns: [N, T, A, 1] (any shape of N T A values); index: int64 [B] env-steps of the
-    flattened [N T] (None: all).  `check_index` range-checks the index (one host synchronisation; skipped inside a graph capture).
-    `workspace`: a uint8 device tensor of at least hns_critic_train_workspace_bytes bytes, 256-byte aligned, instead of one allocated per call;
-    `out`: three fp32 device values that receive value_loss, explained_var and grad_norm (the returned scalars are views of it) instead of a
-    tensor of the call's own.  Both are ignored on the CPU."""
+def value_loss_sums(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, index=None, clip_param=0.1, loss="huber", huber_delta=10.0,
+                    check_index=True, workspace=None):
+    """The forward half of a data-parallel value_loss_and_grad: CriticSums(sums, values) with sums the five fp64 device values of
+    hns_critic_train_sums over THIS rank's rows (sum loss(v - ret), sum loss(clipped - ret), sum (v - ret)^2, sum ret, sum ret^2) and values
+    [B, A, 1].  No gradient is touched.  The caller adds the ranks' sums (one SUM all-reduce) and passes the result to
+    value_loss_and_grad(sums=, global_rows=).  Arguments and refusals: value_loss_and_grad's."""
     if loss not in LOSSES:
         raise ValueError(f"loss must be 'huber' or 'mse', not {loss!r}")
     if not clip_param >= 0 or (loss == "huber" and not huber_delta > 0):
@@ -77,6 +133,67 @@ def value_loss_and_grad(critic, obs_self, obs_others, obs_cylinders, b_values, b
     xs, xo, xc = PT.as_rollout(obs_self, obs_others, obs_cylinders)
     shape = PT.validate("critic", p, xs, xo, xc, (("b_values", b_values, 1), ("b_returns", b_returns, 1)), index, check_index)
     if not xs.is_cuda:
+        return _torch_sums(p, xs, xo, xc, b_values, b_returns, index, float(clip_param), loss, float(huber_delta))
+    lib = abi.load_library()
+    bv, ret = b_values.contiguous(), b_returns.contiguous()
+    _, _, A, D, K = shape
+    dev = xs.device
+    B = index.numel() if index is not None else shape[0] * shape[1]
+    for f, t in p.items():
+        if t.data_ptr() % 16:
+            raise ValueError(f"critic parameter {f} must be 16-byte aligned")
+    nbytes = lib.hns_critic_train_workspace_bytes(B * A, D, A, K)
+    if nbytes == 0:
+        raise ValueError(f"shape outside the kernel's limits: {B * A} rows, self_dim {D}, {A} agents, {K} cylinders")
+    ws = PT.check_workspace(workspace, nbytes, dev) if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    net = abi.HnsPolicyNet()
+    for f, t in p.items():
+        setattr(net, f, t.data_ptr())
+    b = PT.fill_batch(abi.HnsCriticBatch, xs, xo, xc, index, shape)
+    b.b_values, b.b_returns = bv.data_ptr(), ret.data_ptr()
+    sums = torch.empty(5, dtype=torch.float64, device=dev)
+    values = torch.empty(B, A, 1, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.hns_critic_train_sums(C.byref(net), C.byref(b), D, A, K, float(clip_param), LOSSES[loss], float(huber_delta), sums.data_ptr(),
+                                       values.data_ptr(), ws.data_ptr(), nbytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    abi.check(rc, "hns_critic_train_sums")
+    return CriticSums(sums, values)
+
+
+def value_loss_and_grad(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, index=None, clip_param=0.1, loss="huber",
+                        huber_delta=10.0, check_index=True, workspace=None, out=None, sums=None, global_rows=None, group=None, bucket=None):
+    """The clipped value loss of the critic on a minibatch and every parameter's .grad (as zero_grad() + backward() leave them, before
+    clip_grad_norm_).  Returns CriticLoss(value_loss, explained_var, grad_norm: 0-dim tensors; values [B, A, 1]).
+
+    obs_*: the rollout's [N, T, A, ...] observations (state_self [N, T, A, D] or [N, T, A, 1, D]; state_others None with one agent) or a
+    flat [R, A, ...] batch, read in place; b_values, b_returns: [N, T, A, 1] (any shape of N T A values); index: int64 [B] env-steps of the
+    flattened [N T] (None: all).  `check_index` range-checks the index (one host synchronisation; skipped inside a graph capture).
+    `workspace`: a uint8 device tensor of at least hns_critic_train_workspace_bytes bytes, 256-byte aligned, instead of one allocated per call;
+    `out`: three fp32 device values that receive value_loss, explained_var and grad_norm (the returned scalars are views of it) instead of a
+    tensor of the call's own.  Both are ignored on the CPU.
+
+    `sums`, `global_rows` (both None: the call above, untouched): this minibatch is one rank's part of a union of `global_rows` agent rows
+    whose five fp64 sums are `sums` (value_loss_sums' over all ranks, added): hns_critic_train_grad_global takes the branch, value_loss and
+    explained_var from them — the same on every rank — and the gradients are this rank's part, which adds up over the ranks to the union's.
+    `values` is None on the device (value_loss_sums returned them).  `bucket`: the critic's `policy_train.GradBucket`; grad_norm is then the
+    bucket's norm (None without one).  `group`: the bucket is all-reduced (SUM) over it first."""
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be 'huber' or 'mse', not {loss!r}")
+    if not clip_param >= 0 or (loss == "huber" and not huber_delta > 0):
+        raise ValueError("clip_param must be >= 0 and huber_delta > 0")
+    if (sums is None) != (global_rows is None):
+        raise ValueError("sums= and global_rows= travel together: the union's five sums and its row count")
+    p = critic_parameters(critic)
+    xs, xo, xc = PT.as_rollout(obs_self, obs_others, obs_cylinders)
+    shape = PT.validate("critic", p, xs, xo, xc, (("b_values", b_values, 1), ("b_returns", b_returns, 1)), index, check_index)
+    PT.check_global("critic", p, global_rows, (index.numel() if index is not None else shape[0] * shape[1]) * shape[2], group, bucket)
+    if sums is not None and (not torch.is_tensor(sums) or sums.dtype != torch.float64 or sums.numel() != 5 or sums.device != xs.device or
+                             not sums.is_contiguous()):
+        raise ValueError(f"sums must be five contiguous float64 values on {xs.device}")
+    if not xs.is_cuda:
+        if sums is not None:
+            return _torch_loss_and_grad_global(p, xs, xo, xc, b_values, b_returns, index, float(clip_param), loss, float(huber_delta), sums,
+                                               global_rows, group, bucket)
         return _torch_loss_and_grad(p, xs, xo, xc, b_values, b_returns, index, float(clip_param), loss, float(huber_delta))
     lib = abi.load_library()
     bv, ret = b_values.contiguous(), b_returns.contiguous()
@@ -84,6 +201,14 @@ def value_loss_and_grad(critic, obs_self, obs_others, obs_cylinders, b_values, b
                                                            out, 3, abi.HnsCriticBatch)
     _, _, A, D, K = shape
     b.b_values, b.b_returns = bv.data_ptr(), ret.data_ptr()
+    if sums is not None:
+        with torch.cuda.device(xs.device):
+            rc = lib.hns_critic_train_grad_global(C.byref(net), C.byref(b), D, A, K, float(clip_param), LOSSES[loss], float(huber_delta), C.byref(grd),
+                                                  scal[0:].data_ptr(), scal[1:].data_ptr(), None, None, ws.data_ptr(), nbytes, st, sums.data_ptr(),
+                                                  int(global_rows))
+        abi.check(rc, "hns_critic_train_grad_global")
+        norm = PT.finish_global(bucket, group, scal[2:3])
+        return CriticLoss(scal[0], scal[1], scal[2] if norm is not None else None, None)
     values = torch.empty(B, A, 1, dtype=torch.float32, device=xs.device)
     with torch.cuda.device(xs.device):
         rc = lib.hns_critic_train_grad(C.byref(net), C.byref(b), D, A, K, float(clip_param), LOSSES[loss], float(huber_delta), C.byref(grd),
@@ -114,23 +239,33 @@ def make_optimizer(critic, cfg=None):
 
 
 def update_critic(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, optimizer, index=None, cfg=None, check_index=False,
-                  workspace=None, out=None):
+                  workspace=None, out=None, sums=None, global_rows=None, group=None, bucket=None):
     """MAPPOPolicy.update_critic on one minibatch: loss, backward, clip_grad_norm_, Adam.  cfg: the algo cfg (clip_param, critic.use_huber_loss,
     critic.huber_delta; the reference's defaults when None).  Returns {"value_loss", "critic_grad_norm", "explained_var"} as 0-dim tensors on the
     parameters' device — the caller decides when to .item().  `optimizer`: a ClippedAdam (make_optimizer).  The index is NOT range-checked
     by default (make_dataset_naive's permutations are in range by construction; the check is a host synchronisation per minibatch, and the
     kernel skips an env-step outside the rollout): pass check_index=True for an index of another origin.  `workspace`, `out`:
-    value_loss_and_grad's."""
+    value_loss_and_grad's.  `global_rows`, `bucket`: one rank's part of a data-parallel update over a union of `global_rows` rows.  With
+    `group` the call runs value_loss_sums, the SUM all-reduce of the five values, value_loss_and_grad(sums=, group=) and the step; `sums`
+    given instead: the caller added the ranks' sums itself."""
+    if global_rows is not None and bucket is None:
+        raise ValueError("update_critic with global_rows= steps on the bucket's norm: pass bucket=")
+    if global_rows is not None and sums is None and group is None:
+        raise ValueError("update_critic with global_rows= needs the union's sums= or the group= to add them over")
     if not isinstance(optimizer, ClippedAdam):
         raise TypeError(f"update_critic takes a ClippedAdam (critic_train.make_optimizer), not {type(optimizer).__name__}: the clip and the "
                         "step are one launch that needs the gradient norm")
     get, sget = critic_cfg(cfg)
-    for group in optimizer.param_groups:
-        if group.get("weight_decay", 0) != 0:
+    for pg in optimizer.param_groups:
+        if pg.get("weight_decay", 0) != 0:
             raise NotImplementedError("weight_decay != 0 is not supported")
-    res = value_loss_and_grad(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, index, clip_param=float(get("clip_param", 0.1)),
-                              loss="huber" if sget("use_huber_loss", True) else "mse", huber_delta=float(sget("huber_delta", 10.0)),
-                              check_index=check_index, workspace=workspace, out=out)
+    kw = dict(clip_param=float(get("clip_param", 0.1)), loss="huber" if sget("use_huber_loss", True) else "mse",
+              huber_delta=float(sget("huber_delta", 10.0)), check_index=check_index, workspace=workspace)
+    if global_rows is not None and sums is None:
+        from . import sharding
+        sums = sharding.all_reduce_sum(value_loss_sums(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, index, **kw).sums, group)
+    res = value_loss_and_grad(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, index, out=out, sums=sums, global_rows=global_rows,
+                              group=group, bucket=bucket, **kw)
     optimizer.step(grad_norm=res.grad_norm)
     norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else res.grad_norm
     return {"value_loss": res.value_loss, "critic_grad_norm": norm, "explained_var": res.explained_var}

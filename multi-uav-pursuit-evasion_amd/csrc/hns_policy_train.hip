@@ -13,7 +13,9 @@
 //   hns_critic_kernel<false> : forward of the minibatch rows: values, per-tile fp64 partials of sum loss(v), sum loss(clipped), sum (v - ret)^2,
 //                              sum ret, sum ret^2.
 //   hns_critic_loss_kernel   : one workgroup sums the partials in a fixed order: value_loss, explained_var and the branch weights of the max
-//                              ((1, 0), (0, 1), or (1/2, 1/2) at an exact tie, as torch.maximum's backward).
+//                              ((1, 0), (0, 1), or (1/2, 1/2) at an exact tie, as torch.maximum's backward).  Its two halves alone are
+//                              hns_critic_sums_kernel (the five sums) and hns_critic_decide_kernel (the scalars and weights from given sums):
+//                              the data-parallel entries' (DESIGN §7.9), which add the ranks' sums between them.
 //   hns_critic_kernel<true>  : recomputes a tile's forward pass, forms dv from the branch weights and walks back to the embeddings.  The operand
 //                              pairs (dy, x) of the six weight gradients are staged in the workspace ([rows, 128] each); LayerNorm, head and
 //                              embedding gradients leave as two partial rows per tile (rows 0-15 and 16-31).
@@ -606,10 +608,9 @@ __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(con
     }
 }
 
-// sums the per-tile loss partials in a fixed order; value_loss, explained_var, branch weights
-__global__ __launch_bounds__(256) void hns_critic_loss_kernel(const double *part, int tiles, double n, float *ctl, float *value_loss, float *explained_var) {
-    __shared__ double sm[5][256];
-    const int tid = threadIdx.x;
+// The critic's scalars in two halves that hns_critic_loss_kernel runs back to back and the data-parallel entries run apart.
+// Summing half: thread t adds the five partials of tiles t, t + 256, ... in that order; thread 0 then adds the 256 thread sums in index order.
+HNS_DEV void ct_loss_thread_sums(const double *part, int tiles, double (&sm)[5][256], int tid) {
     double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     for (int i = tid; i < tiles; i += 256)
 #pragma unroll
@@ -617,19 +618,54 @@ __global__ __launch_bounds__(256) void hns_critic_loss_kernel(const double *part
 #pragma unroll
     for (int q = 0; q < 5; ++q) sm[q][tid] = acc[q];
     __syncthreads();
-    if (tid == 0) {
+}
+
+HNS_DEV void ct_loss_total(const double (&sm)[5][256], double (&S)[5]) {
+    for (int q = 0; q < 5; ++q) {
+        double s = 0.0;
+        for (int i = 0; i < 256; ++i) s += sm[q][i];
+        S[q] = s;
+    }
+}
+
+// Deciding half: value_loss, explained_var and the branch weights from the five sums over n rows
+HNS_DEV void ct_loss_decide(const double (&S)[5], double n, float *ctl, float *value_loss, float *explained_var) {
+    const double lo = S[0] / n, lc = S[1] / n;
+    ctl[0] = lo > lc ? 1.0f : (lo < lc ? 0.0f : 0.5f);
+    ctl[1] = lo > lc ? 0.0f : (lo < lc ? 1.0f : 0.5f);
+    value_loss[0] = (float)(lo > lc ? lo : lc);
+    const double var = (S[4] - S[3] * S[3] / n) / (n - 1.0);             // unbiased, as Tensor.var()
+    explained_var[0] = (float)(1.0 - (S[2] / n) / var);
+}
+
+// sums the per-tile loss partials in a fixed order; value_loss, explained_var, branch weights
+__global__ __launch_bounds__(256) void hns_critic_loss_kernel(const double *part, int tiles, double n, float *ctl, float *value_loss, float *explained_var) {
+    __shared__ double sm[5][256];
+    ct_loss_thread_sums(part, tiles, sm, threadIdx.x);
+    if (threadIdx.x == 0) {
         double S[5];
-        for (int q = 0; q < 5; ++q) {
-            double s = 0.0;
-            for (int i = 0; i < 256; ++i) s += sm[q][i];
-            S[q] = s;
-        }
-        const double lo = S[0] / n, lc = S[1] / n;
-        ctl[0] = lo > lc ? 1.0f : (lo < lc ? 0.0f : 0.5f);
-        ctl[1] = lo > lc ? 0.0f : (lo < lc ? 1.0f : 0.5f);
-        value_loss[0] = (float)(lo > lc ? lo : lc);
-        const double var = (S[4] - S[3] * S[3] / n) / (n - 1.0);             // unbiased, as Tensor.var()
-        explained_var[0] = (float)(1.0 - (S[2] / n) / var);
+        ct_loss_total(sm, S);
+        ct_loss_decide(S, n, ctl, value_loss, explained_var);
+    }
+}
+
+// the summing half alone: the five sums of this rank's rows, for the caller to add to the other ranks'
+__global__ __launch_bounds__(256) void hns_critic_sums_kernel(const double *part, int tiles, double *sums) {
+    __shared__ double sm[5][256];
+    ct_loss_thread_sums(part, tiles, sm, threadIdx.x);
+    if (threadIdx.x == 0) {
+        double S[5];
+        ct_loss_total(sm, S);
+        for (int q = 0; q < 5; ++q) sums[q] = S[q];
+    }
+}
+
+// the deciding half alone, on sums over all ranks' n rows
+__global__ __launch_bounds__(64) void hns_critic_decide_kernel(const double *sums, double n, float *ctl, float *value_loss, float *explained_var) {
+    if (threadIdx.x == 0) {
+        double S[5];
+        for (int q = 0; q < 5; ++q) S[q] = sums[q];
+        ct_loss_decide(S, n, ctl, value_loss, explained_var);
     }
 }
 
@@ -890,23 +926,25 @@ int ct_check_shape(const char *fn, const Batch &b, int32_t self_dim, int32_t num
     return HNS_OK;
 }
 
-// the parameter and gradient tables, checked and copied by ONE field list (heads > 1: the actor, whose log_std joins both)
-int ct_bind_net(const char *fn, const hns_policy_net &net, const hns_policy_grads &grads, bool others, int heads, hns::EncNet &n, hns::CtGrad &g) {
+// the parameter and gradient tables, checked and copied by ONE field list (heads > 1: the actor, whose log_std joins both).  grads NULL: a
+// forward-only entry (hns_critic_train_sums) binds the parameters alone and `g` stays empty
+int ct_bind_net(const char *fn, const hns_policy_net &net, const hns_policy_grads *grads, bool others, int heads, hns::EncNet &n, hns::CtGrad &g) {
     bool ok = true;
 #define X(f, m)                                                                                      \
-    ok = ok && net.f && grads.f && hns_aligned(net.f, 16) && hns_aligned(grads.f, 4);                  \
+    ok = ok && net.f && hns_aligned(net.f, 16) && (!grads || (grads->f && hns_aligned(grads->f, 4)));  \
     n.m = net.f;                                                                                     \
-    g.m = grads.f;
+    g.m = grads ? grads->f : nullptr;
     HNS_CT_FIELDS(X)
 #undef X
-    if (heads > 1) ok = ok && net.log_std && grads.log_std && hns_aligned(net.log_std, 16) && hns_aligned(grads.log_std, 4);
+    if (heads > 1) ok = ok && net.log_std && hns_aligned(net.log_std, 16) && (!grads || (grads->log_std && hns_aligned(grads->log_std, 4)));
     n.log_std = heads > 1 ? net.log_std : nullptr;
-    g.log_std = heads > 1 ? grads.log_std : nullptr;
+    g.log_std = heads > 1 && grads ? grads->log_std : nullptr;
     if (!ok) return hns_fail(fn, "every parameter must be a non-NULL 16-byte aligned fp32 array, every gradient a non-NULL fp32 array");
-    if (others && (!net.embed_others_w || !net.embed_others_b || !grads.embed_others_w || !grads.embed_others_b || !hns_aligned(net.embed_others_b, 16)))
+    if (others && (!net.embed_others_w || !net.embed_others_b || !hns_aligned(net.embed_others_b, 16) ||
+                   (grads && (!grads->embed_others_w || !grads->embed_others_b))))
         return hns_fail(fn, "state_others embedding (parameter or gradient) missing or misaligned (num_agents > 1)");
     n.ew[1] = others ? net.embed_others_w : nullptr; n.eb[1] = others ? net.embed_others_b : nullptr;
-    g.ew[1] = others ? grads.embed_others_w : nullptr; g.eb[1] = others ? grads.embed_others_b : nullptr;
+    g.ew[1] = others && grads ? grads->embed_others_w : nullptr; g.eb[1] = others && grads ? grads->embed_others_b : nullptr;
     return HNS_OK;
 }
 
@@ -961,6 +999,7 @@ int ct_launch_pack(hipStream_t st, const hns::CtArgs &a, const CtPlan &p, void *
 }
 
 // the launches behind them: weight gradients, the fixed-order sums into the PyTorch layouts (`ls_add`: hns_critic_reduce_kernel's), the total norm
+// (grad_norm NULL: not launched)
 int ct_launch_tail(hipStream_t st, const hns::CtArgs &a, const CtPlan &p, const hns::CtGrad &g, void *workspace, int heads, double ls_add, float *grad_norm) {
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     float *gpart = reinterpret_cast<float *>(ws + p.o_gemm);
@@ -971,9 +1010,96 @@ int ct_launch_tail(hipStream_t st, const hns::CtArgs &a, const CtPlan &p, const 
     hipLaunchKernelGGL(hns::hns_critic_reduce_kernel, dim3(nb), dim3(256), 0, st, gpart, (int)p.splits, a.tilepart, (int)(2 * p.tiles), p.P, p.gblocks, g, a.D,
                        blockpart, heads, ls_add);
     HNS_CHECK_HIP(hipGetLastError());
+    if (!grad_norm) return HNS_OK;                              // the data-parallel entries: the local norm means nothing (hns_grad_norm after the all-reduce)
     hipLaunchKernelGGL(hns::hns_critic_norm_kernel, dim3(1), dim3(256), 0, st, blockpart, nb, grad_norm);
     HNS_CHECK_HIP(hipGetLastError());
     return HNS_OK;
+}
+
+// The critic's three entries over one body.  kCtLocal: hns_critic_train_grad — the minibatch is the whole batch.  kCtSums: pack, forward, the
+// summing half (`sums` out).  kCtGlobal: pack, the deciding half on the given `sums` over `global_rows`, backward scaled by 1 / global_rows, the tail.
+enum CtMode { kCtLocal, kCtSums, kCtGlobal };
+
+int ct_critic_call(const char *fn, CtMode mode, const hns_policy_net *critic, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents,
+                   int32_t num_cylinders, float clip_param, int32_t loss_kind, float huber_delta, const hns_policy_grads *grads, float *value_loss,
+                   float *explained_var, float *grad_norm, float *values, double *sums, int64_t global_rows, void *workspace, size_t workspace_bytes,
+                   void *stream) {
+    if (int rc = ct_check_shape(fn, *batch, self_dim, num_agents, num_cylinders)) return rc;
+    if (loss_kind != HNS_CRITIC_LOSS_HUBER && loss_kind != HNS_CRITIC_LOSS_MSE) return hns_fail(fn, "loss_kind must be HNS_CRITIC_LOSS_HUBER or HNS_CRITIC_LOSS_MSE");
+    if (!(clip_param >= 0.0f) || (loss_kind == HNS_CRITIC_LOSS_HUBER && !(huber_delta > 0.0f))) return hns_fail(fn, "clip_param >= 0, huber_delta > 0");
+    if (mode == kCtGlobal && global_rows < batch->batch * num_agents) return hns_fail(fn, "global_rows must be >= this rank's rows (batch x num_agents)");
+    hns::CtArgs a{};
+    hns::CtGrad g{};
+    CtPlan p;
+    if (int rc = ct_bind_net(fn, *critic, grads, num_agents > 1, 1, a.net, g)) return rc;
+    if (int rc = ct_check_obs(fn, *batch, num_agents > 1)) return rc;
+    if (!batch->b_values || !batch->b_returns || !hns_aligned(batch->b_values, 4) || !hns_aligned(batch->b_returns, 4)) return hns_fail(fn, "b_values / b_returns missing or misaligned");
+    if (int rc = ct_plan_call(fn, *batch, {value_loss, explained_var, grad_norm, values}, workspace, workspace_bytes, self_dim, num_agents, num_cylinders, 1, p, a)) return rc;
+    float *ctl = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + p.o_ctl);
+    a.bval = batch->b_values; a.bret = batch->b_returns;
+    a.clip = clip_param; a.delta = huber_delta; a.mse = loss_kind == HNS_CRITIC_LOSS_MSE;
+    a.values = values;
+    a.ctl = ctl;
+    if (mode == kCtGlobal) a.inv_n = (float)(1.0 / (double)global_rows);
+
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    static const hipError_t attr_f = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<false>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)hns::kCtLdsFwd);
+    static const hipError_t attr_b = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<true>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::CtLds));
+    HNS_CHECK_HIP(attr_f);
+    HNS_CHECK_HIP(attr_b);
+    if (int rc = ct_launch_pack(st, a, p, workspace)) return rc;
+    if (mode != kCtGlobal) {
+        hipLaunchKernelGGL(hns::hns_critic_kernel<false>, dim3((unsigned)p.tiles), dim3(hns::kCtThreads), hns::kCtLdsFwd, st, a);
+        HNS_CHECK_HIP(hipGetLastError());
+    }
+    if (mode == kCtLocal) hipLaunchKernelGGL(hns::hns_critic_loss_kernel, dim3(1), dim3(256), 0, st, a.losspart, (int)p.tiles, (double)a.rows, ctl, value_loss, explained_var);
+    else if (mode == kCtSums) hipLaunchKernelGGL(hns::hns_critic_sums_kernel, dim3(1), dim3(256), 0, st, a.losspart, (int)p.tiles, sums);
+    else hipLaunchKernelGGL(hns::hns_critic_decide_kernel, dim3(1), dim3(64), 0, st, sums, (double)global_rows, ctl, value_loss, explained_var);
+    HNS_CHECK_HIP(hipGetLastError());
+    if (mode == kCtSums) return HNS_OK;
+    hipLaunchKernelGGL(hns::hns_critic_kernel<true>, dim3((unsigned)p.tiles), dim3(hns::kCtThreads), sizeof(hns::CtLds), st, a);
+    HNS_CHECK_HIP(hipGetLastError());
+    return ct_launch_tail(st, a, p, g, workspace, 1, 0.0, grad_norm);
+}
+
+// The actor's two entries over one body.  global: the rows' backward weight and policy_loss are scaled by 1 / global_rows instead of 1 / rows (this
+// rank's share of the loss and of the gradient: the ranks' shares add up), the entropy term's constant gradient joins by `entropy_share` of it.
+int ct_actor_call(const char *fn, bool global, const hns_policy_net *actor, const hns_actor_batch *batch, int32_t self_dim, int32_t num_agents,
+                  int32_t num_cylinders, double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
+                  float *grad_norm, float *log_probs, int64_t global_rows, double entropy_share, void *workspace, size_t workspace_bytes, void *stream) {
+    if (int rc = ct_check_shape(fn, *batch, self_dim, num_agents, num_cylinders)) return rc;
+    if (!(clip_param >= 0.0) || !std::isfinite(clip_param) || !std::isfinite(entropy_coef)) return hns_fail(fn, "clip_param >= 0 and a finite entropy_coef");
+    if (global && global_rows < batch->batch * num_agents) return hns_fail(fn, "global_rows must be >= this rank's rows (batch x num_agents)");
+    if (global && !std::isfinite(entropy_share)) return hns_fail(fn, "entropy_share must be finite (1 / world)");
+    hns::CtArgs a{};
+    hns::CtGrad g{};
+    CtPlan p;
+    if (int rc = ct_bind_net(fn, *actor, grads, num_agents > 1, hns::kActDim, a.net, g)) return rc;
+    if (int rc = ct_check_obs(fn, *batch, num_agents > 1)) return rc;
+    if (!batch->action || !batch->log_probs_old || !batch->advantages || !hns_aligned(batch->action, 4) || !hns_aligned(batch->log_probs_old, 4) ||
+        !hns_aligned(batch->advantages, 4))
+        return hns_fail(fn, "action / log_probs_old / advantages missing or misaligned");
+    if (int rc = ct_plan_call(fn, *batch, {policy_loss, entropy, ess, grad_norm, log_probs}, workspace, workspace_bytes, self_dim, num_agents, num_cylinders,
+                              hns::kActDim, p, a))
+        return rc;
+    a.logp_old = batch->log_probs_old; a.adv = batch->advantages; a.action = batch->action;
+    a.clip_lo = (float)(1.0 - clip_param); a.clip_hi = (float)(1.0 + clip_param);
+    a.logp_new = log_probs;
+    if (global) a.inv_n = (float)(1.0 / (double)global_rows);
+
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<true, hns::kActDim>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::CtLds));
+    HNS_CHECK_HIP(attr);
+    if (int rc = ct_launch_pack(st, a, p, workspace)) return rc;
+    hipLaunchKernelGGL((hns::hns_critic_kernel<true, hns::kActDim>), dim3((unsigned)p.tiles), dim3(hns::kCtThreads), sizeof(hns::CtLds), st, a);
+    HNS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hns::hns_actor_loss_kernel, dim3(1), dim3(64), 0, st, a.losspart, (int)p.tiles, (int)num_agents, (double)(global ? global_rows : a.rows),
+                       (double)batch->batch, actor->log_std, policy_loss, entropy, ess);
+    HNS_CHECK_HIP(hipGetLastError());
+    return ct_launch_tail(st, a, p, g, workspace, hns::kActDim, global ? -entropy_coef * entropy_share : -entropy_coef, grad_norm);
 }
 
 }  // namespace
@@ -990,37 +1116,29 @@ int hns_critic_train_grad(const hns_policy_net *critic, const hns_critic_batch *
                           float *explained_var, float *grad_norm, float *values, void *workspace, size_t workspace_bytes, void *stream) {
     const char *fn = "hns_critic_train_grad";
     if (!critic || !batch || !grads || !value_loss || !explained_var || !grad_norm || !workspace) return hns_fail(fn, "null pointer");
-    if (int rc = ct_check_shape(fn, *batch, self_dim, num_agents, num_cylinders)) return rc;
-    if (loss_kind != HNS_CRITIC_LOSS_HUBER && loss_kind != HNS_CRITIC_LOSS_MSE) return hns_fail(fn, "loss_kind must be HNS_CRITIC_LOSS_HUBER or HNS_CRITIC_LOSS_MSE");
-    if (!(clip_param >= 0.0f) || (loss_kind == HNS_CRITIC_LOSS_HUBER && !(huber_delta > 0.0f))) return hns_fail(fn, "clip_param >= 0, huber_delta > 0");
-    hns::CtArgs a{};
-    hns::CtGrad g{};
-    CtPlan p;
-    if (int rc = ct_bind_net(fn, *critic, *grads, num_agents > 1, 1, a.net, g)) return rc;
-    if (int rc = ct_check_obs(fn, *batch, num_agents > 1)) return rc;
-    if (!batch->b_values || !batch->b_returns || !hns_aligned(batch->b_values, 4) || !hns_aligned(batch->b_returns, 4)) return hns_fail(fn, "b_values / b_returns missing or misaligned");
-    if (int rc = ct_plan_call(fn, *batch, {value_loss, explained_var, grad_norm, values}, workspace, workspace_bytes, self_dim, num_agents, num_cylinders, 1, p, a)) return rc;
-    float *ctl = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + p.o_ctl);
-    a.bval = batch->b_values; a.bret = batch->b_returns;
-    a.clip = clip_param; a.delta = huber_delta; a.mse = loss_kind == HNS_CRITIC_LOSS_MSE;
-    a.values = values;
-    a.ctl = ctl;
+    return ct_critic_call(fn, kCtLocal, critic, batch, self_dim, num_agents, num_cylinders, clip_param, loss_kind, huber_delta, grads, value_loss, explained_var,
+                          grad_norm, values, nullptr, 0, workspace, workspace_bytes, stream);
+}
 
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    static const hipError_t attr_f = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<false>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)hns::kCtLdsFwd);
-    static const hipError_t attr_b = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<true>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::CtLds));
-    HNS_CHECK_HIP(attr_f);
-    HNS_CHECK_HIP(attr_b);
-    if (int rc = ct_launch_pack(st, a, p, workspace)) return rc;
-    hipLaunchKernelGGL(hns::hns_critic_kernel<false>, dim3((unsigned)p.tiles), dim3(hns::kCtThreads), hns::kCtLdsFwd, st, a);
-    HNS_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hns::hns_critic_loss_kernel, dim3(1), dim3(256), 0, st, a.losspart, (int)p.tiles, (double)a.rows, ctl, value_loss, explained_var);
-    HNS_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hns::hns_critic_kernel<true>, dim3((unsigned)p.tiles), dim3(hns::kCtThreads), sizeof(hns::CtLds), st, a);
-    HNS_CHECK_HIP(hipGetLastError());
-    return ct_launch_tail(st, a, p, g, workspace, 1, 0.0, grad_norm);
+int hns_critic_train_sums(const hns_policy_net *critic, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                          float clip_param, int32_t loss_kind, float huber_delta, double *sums, float *values, void *workspace, size_t workspace_bytes,
+                          void *stream) {
+    const char *fn = "hns_critic_train_sums";
+    if (!critic || !batch || !sums || !workspace) return hns_fail(fn, "null pointer");
+    if (!hns_aligned(sums, 8)) return hns_fail(fn, "misaligned sums (five fp64 values, 8-byte aligned)");
+    return ct_critic_call(fn, kCtSums, critic, batch, self_dim, num_agents, num_cylinders, clip_param, loss_kind, huber_delta, nullptr, nullptr, nullptr, nullptr,
+                          values, sums, 0, workspace, workspace_bytes, stream);
+}
+
+int hns_critic_train_grad_global(const hns_policy_net *critic, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                                 float clip_param, int32_t loss_kind, float huber_delta, const hns_policy_grads *grads, float *value_loss,
+                                 float *explained_var, float *grad_norm, float *values, void *workspace, size_t workspace_bytes, void *stream,
+                                 const double *sums, int64_t global_rows) {
+    const char *fn = "hns_critic_train_grad_global";
+    if (!critic || !batch || !grads || !value_loss || !explained_var || !workspace || !sums) return hns_fail(fn, "null pointer");
+    if (!hns_aligned(sums, 8)) return hns_fail(fn, "misaligned sums (five fp64 values, 8-byte aligned)");
+    return ct_critic_call(fn, kCtGlobal, critic, batch, self_dim, num_agents, num_cylinders, clip_param, loss_kind, huber_delta, grads, value_loss, explained_var,
+                          grad_norm, values, const_cast<double *>(sums), global_rows, workspace, workspace_bytes, stream);
 }
 
 size_t hns_actor_train_workspace_bytes(int64_t rows, int32_t self_dim, int32_t num_agents, int32_t num_cylinders) {
@@ -1033,34 +1151,18 @@ int hns_actor_train_grad(const hns_policy_net *actor, const hns_actor_batch *bat
                          float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream) {
     const char *fn = "hns_actor_train_grad";
     if (!actor || !batch || !grads || !policy_loss || !entropy || !ess || !grad_norm || !workspace) return hns_fail(fn, "null pointer");
-    if (int rc = ct_check_shape(fn, *batch, self_dim, num_agents, num_cylinders)) return rc;
-    if (!(clip_param >= 0.0) || !std::isfinite(clip_param) || !std::isfinite(entropy_coef)) return hns_fail(fn, "clip_param >= 0 and a finite entropy_coef");
-    hns::CtArgs a{};
-    hns::CtGrad g{};
-    CtPlan p;
-    if (int rc = ct_bind_net(fn, *actor, *grads, num_agents > 1, hns::kActDim, a.net, g)) return rc;
-    if (int rc = ct_check_obs(fn, *batch, num_agents > 1)) return rc;
-    if (!batch->action || !batch->log_probs_old || !batch->advantages || !hns_aligned(batch->action, 4) || !hns_aligned(batch->log_probs_old, 4) ||
-        !hns_aligned(batch->advantages, 4))
-        return hns_fail(fn, "action / log_probs_old / advantages missing or misaligned");
-    if (int rc = ct_plan_call(fn, *batch, {policy_loss, entropy, ess, grad_norm, log_probs}, workspace, workspace_bytes, self_dim, num_agents, num_cylinders,
-                              hns::kActDim, p, a))
-        return rc;
-    a.logp_old = batch->log_probs_old; a.adv = batch->advantages; a.action = batch->action;
-    a.clip_lo = (float)(1.0 - clip_param); a.clip_hi = (float)(1.0 + clip_param);
-    a.logp_new = log_probs;
+    return ct_actor_call(fn, false, actor, batch, self_dim, num_agents, num_cylinders, clip_param, entropy_coef, grads, policy_loss, entropy, ess, grad_norm,
+                         log_probs, 0, 1.0, workspace, workspace_bytes, stream);
+}
 
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<true, hns::kActDim>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::CtLds));
-    HNS_CHECK_HIP(attr);
-    if (int rc = ct_launch_pack(st, a, p, workspace)) return rc;
-    hipLaunchKernelGGL((hns::hns_critic_kernel<true, hns::kActDim>), dim3((unsigned)p.tiles), dim3(hns::kCtThreads), sizeof(hns::CtLds), st, a);
-    HNS_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hns::hns_actor_loss_kernel, dim3(1), dim3(64), 0, st, a.losspart, (int)p.tiles, (int)num_agents, (double)a.rows, (double)batch->batch,
-                       actor->log_std, policy_loss, entropy, ess);
-    HNS_CHECK_HIP(hipGetLastError());
-    return ct_launch_tail(st, a, p, g, workspace, hns::kActDim, -entropy_coef, grad_norm);
+int hns_actor_train_grad_global(const hns_policy_net *actor, const hns_actor_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                                double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
+                                float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream, int64_t global_rows,
+                                double entropy_share) {
+    const char *fn = "hns_actor_train_grad_global";
+    if (!actor || !batch || !grads || !policy_loss || !entropy || !ess || !workspace) return hns_fail(fn, "null pointer");
+    return ct_actor_call(fn, true, actor, batch, self_dim, num_agents, num_cylinders, clip_param, entropy_coef, grads, policy_loss, entropy, ess, grad_norm,
+                         log_probs, global_rows, entropy_share, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

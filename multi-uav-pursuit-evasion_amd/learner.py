@@ -15,14 +15,18 @@ One RNG stream serves the call (the predictor's epochs draw first): `generator` 
 synchronisation (the updates write their scalars into the rows of one table; no `.item()`, no index check); update_tp's selected-count read
 stays, and the finished info row crosses to the host in one copy.  The two update workspaces and the info workspace are allocated once per
 shape and reused by all ppo_epochs x num_minibatches calls.  CPU tensors run the same driver over the modules' CPU paths (CPU tests, gloo
-runs — not the hot path).  DESIGN.md §7.6."""
+runs — not the hot path).  DESIGN.md §7.6.
+
+`DeviceLearner(..., group=)` is the data-parallel learner: W ranks, each with the rollout of its own env slice, perform ONE
+PPO update per minibatch on the union of their minibatches — the critic's branch decided on the union's sums, every mean over the union's
+rows, the norm taken from the summed gradient, the predictor's ranks weighted by their selected windows."""
 import ctypes as C
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import abi, actor_train, critic_train, gae, tp_train
+from . import abi, actor_train, critic_train, gae, sharding, tp_train
 from . import policy as P
 from . import policy_train as PT
 
@@ -78,9 +82,24 @@ class DeviceLearner:
     """MAPPOPolicy's training half.  actor: the shared actor's parameters (TensorDictParams / TensorDict / mapping / nn.Module), critic: the
     critic module or its parameters — live tensors, updated in place; cfg: the algo cfg (dict or attribute object); tp_net: the predictor
     (tp_net.TPNet or the reference's TP_net) or None; value_normalizer: a ValueNorm1 (the reference's or this module's) or None; generator:
-    the torch.Generator of every randperm (None: the global one); device_policy: a DevicePolicy over the same tensors (built when None)."""
+    the torch.Generator of every randperm (None: the global one); device_policy: a DevicePolicy over the same tensors (built when None).
 
-    def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, agent_name="drone", generator=None, device_policy=None):
+    group: None — one process, the path above exactly — or a torch.distributed process group ("world": the default one): the ranks of the
+    group train ONE set of networks from the rollouts of their env slices.  At construction and after load_state_dict the group's rank 0
+    broadcasts the actor, the critic, the predictor, ValueNorm1's buffers and the three Adam states.  Per train_rollout one gather carries
+    every rank's (num_minibatches, ppo_epochs, TP_epochs, predictor on, env-steps, agents): the settings must agree and every rank needs at
+    least one env-step per minibatch, else ValueError on every rank before any further collective; global_rows per minibatch follows from
+    it.  Each rank draws its own permutations of its own env-steps from its own `generator`.  Per minibatch: the actor's
+    hns_actor_train_grad_global, SUM all-reduce of its bucket, hns_grad_norm, the step; the critic's hns_critic_train_sums, SUM all-reduce of
+    five fp64 values, hns_critic_train_grad_global, SUM all-reduce of its bucket, hns_grad_norm, the step — three collectives per minibatch
+    pair.  rollout_targets' gather is the existing one; the host adds no synchronisation of its own (gloo moves
+    host copies: a correctness backend).
+    Info row: every entry is the same on all ranks (one more all-reduce of three values per call).  value_loss, explained_var, entropy, the two gradient norms and the rollout moments are
+    the union's by construction; policy_loss is the SUM of the ranks' shares (the union's loss); ESS is the MEAN of the ranks' own values —
+    an approximation of a diagnostic (the effective sample size of the union is not the mean of the parts'), not used by the update;
+    action_norm is the mean over all ranks' rows."""
+
+    def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, agent_name="drone", generator=None, device_policy=None, group=None):
         check_learner_config(cfg)
         get = PT.getter(cfg)
         self.cfg, self.agent_name, self.generator = cfg, agent_name, generator
@@ -98,6 +117,72 @@ class DeviceLearner:
         self.policy = device_policy if device_policy is not None else P.DevicePolicy(actor, critic, cfg, agent_name=agent_name)
         self.n_updates = 0
         self._ws = {}
+        self.group = sharding.resolve_group(group)
+        self.actor_bucket = self.critic_bucket = self.tp_bucket = None
+        if self.group is not None:
+            self.world = torch.distributed.get_world_size(self.group)
+            self._make_buckets()
+            self._broadcast_state()
+
+    # ---- the data-parallel path's state
+    def _optimizer_makers(self):
+        return (("actor_opt", "actor_opt", lambda: actor_train.make_optimizer(self.actor, self.cfg)),
+                ("critic_opt", "critic_opt", lambda: critic_train.make_optimizer(self.critic, self.cfg)),
+                ("tp_opt", "TP_opt", lambda: tp_train.TPAdam(tp_train.parameters(self.tp_net), lr=1e-4)))
+
+    def _make_buckets(self):
+        self.actor_bucket = PT.GradBucket(actor_train.actor_parameters(self.actor))
+        self.critic_bucket = PT.GradBucket(critic_train.critic_parameters(self.critic))
+        self.tp_bucket = PT.GradBucket(tp_train.parameters(self.tp_net)) if self.tp_net is not None else None
+
+    def _broadcast_state(self):
+        """Rank 0 of the group hands every rank its networks, ValueNorm1 buffers and Adam states (tensor by tensor: construction and checkpoint
+        loading only)."""
+        dist = torch.distributed
+        tensors = list(actor_train.actor_parameters(self.actor).values()) + list(critic_train.critic_parameters(self.critic).values())
+        if self.tp_net is not None:
+            tensors += tp_train.parameters(self.tp_net)
+        if self.value_normalizer is not None:
+            tensors += [getattr(self.value_normalizer, k) for k in ("running_mean", "running_mean_sq", "debiasing_term")]
+        for t in tensors:
+            sharding.broadcast_from_first(t, self.group)
+        first = dist.get_rank(self.group) == 0
+        to_cpu = lambda o: (o.detach().cpu() if torch.is_tensor(o) else {k: to_cpu(v) for k, v in o.items()} if isinstance(o, dict) else   # noqa: E731
+                            [to_cpu(v) for v in o] if isinstance(o, list) else o)
+        box = [{name: to_cpu(getattr(self, name).state_dict()) for name, _, _ in self._optimizer_makers() if getattr(self, name) is not None} if first else None]
+        dist.broadcast_object_list(box, src=dist.get_global_rank(self.group, 0), group=self.group)
+        if not first:
+            for name, _, make in self._optimizer_makers():
+                if getattr(self, name) is None:
+                    continue
+                setattr(self, name, make())
+                if box[0][name]["state"]:
+                    getattr(self, name).load_state_dict(box[0][name])
+
+    def _global_counts(self, steps, agents):
+        """The rollout's one gather of settings and counts -> (rows of a minibatch over all ranks).  Every rank sees the same table, so a
+        refusal is raised by all of them, before any collective whose shape or count depends on what disagrees."""
+        table = sharding.all_gather_rows([self.num_minibatches, self.ppo_epochs, self.tp_epochs if self.use_tp else 0, int(self.use_tp), steps, agents],
+                                         self.group)
+        for c, what in ((0, "num_minibatches"), (1, "ppo_epochs"), (2, "TP_epochs"), (3, "use_TP_net"), (5, "the number of agents")):
+            if len(set(table[:, c].tolist())) != 1:
+                raise ValueError(f"{what} differs across the ranks of the group: {table[:, c].tolist()}")
+        short = [r for r, n in enumerate(table[:, 4].tolist()) if n < self.num_minibatches]
+        if short:
+            raise ValueError(f"ranks {short} hold fewer env-steps than num_minibatches {self.num_minibatches}: {table[:, 4].tolist()}")
+        return sum(n // self.num_minibatches for n in table[:, 4].tolist()) * agents, sum(table[:, 4].tolist()) * agents
+
+    def _reduce_info(self, head, rows, total_rows):
+        """The three entries of [column means, action_norm] that differ from rank to rank, in ONE all-reduce of three fp64 values: policy_loss
+        becomes the sum of the ranks' shares, ESS the mean of the ranks' values, action_norm the mean over all ranks' rows (each rank's mean
+        times its row count, exact in fp64, over the total).  With one rank every value keeps its bits."""
+        cols = [COLUMNS.index("policy_loss"), COLUMNS.index("ESS"), len(COLUMNS)]
+        v = head[cols].double()
+        v[2] *= rows
+        sharding.all_reduce_sum(v, self.group)
+        head = head.clone()
+        head[cols[0]], head[cols[1]], head[cols[2]] = v[0].float(), (v[1] / self.world).float(), (v[2] / total_rows).float()
+        return head
 
     # ---- workspaces
     def _workspace(self, name, nbytes, device):
@@ -141,6 +226,7 @@ class DeviceLearner:
         xs, xo, xc = PT.as_rollout(obs_self, obs_others, obs_cylinders)
         N, T, A, _ = xs.shape
         dev = xs.device
+        global_rows, total_rows = self._global_counts(N * T, A) if self.group is not None else (None, None)
         # mappo.py:354-361: done = agent_done | env_done (an absent agent_done is env_done, which rollout_targets broadcasts over the agents)
         dones = done.unsqueeze(-1)
         if agent_done is not None:
@@ -153,19 +239,26 @@ class DeviceLearner:
         tp_loss = None
         if self.use_tp:
             tp_loss = tp_train.update_tp(self.tp_net, *tp, self.tp_net.future_predcition_step, self.tp_net.window_step, self.num_minibatches,
-                                         self.tp_epochs, self.tp_opt, generator=self.generator)
+                                         self.tp_epochs, self.tp_opt, generator=self.generator,
+                                         **(dict(group=self.group, bucket=self.tp_bucket) if self.group is not None else {}))
         M = self.ppo_epochs * self.num_minibatches
         table = torch.empty(M, len(COLUMNS), dtype=torch.float32, device=dev)
-        self._ppo_loop(xs, xo, xc, action, log_probs, adv, state_value, ret, table)
+        self._ppo_loop(xs, xo, xc, action, log_probs, adv, state_value, ret, table, global_rows)
         extras = [t.reshape(()).to(torch.float32) for t in ([tp_loss] if self.use_tp else []) + [adv_mean, adv_std]]
         if self.value_normalizer is not None:
             extras.append(self.value_normalizer.running_mean.mean().to(torch.float32))
         if dev.type == "cuda":
-            row = torch.cat([self._info_row(action, table), torch.stack(extras)]).tolist()          # the call's one copy to the host
+            head = self._info_row(action, table)
         else:
             a = action.reshape(-1, action.shape[-1]).double()
             norm = float(np.float32(a.square().sum(-1).sqrt().sum().item() / a.shape[0]))
-            row = _mean_row(table) + [norm] + [float(t) for t in extras]
+            head = torch.tensor(_mean_row(table) + [norm], dtype=torch.float32)
+        if self.group is not None:
+            head = self._reduce_info(head, N * T * A, total_rows)
+        if dev.type == "cuda":
+            row = torch.cat([head, torch.stack(extras)]).tolist()                                   # the call's one copy to the host
+        else:
+            row = head.tolist() + [float(t) for t in extras]
         info = dict(zip(COLUMNS + ("action_norm",), row))
         rest = iter(row[len(COLUMNS) + 1:])
         if self.use_tp:
@@ -176,9 +269,12 @@ class DeviceLearner:
         self.n_updates += 1
         return {f"{self.agent_name}/{k}": info[k] for k in INFO_KEYS if k in info}
 
-    def _ppo_loop(self, xs, xo, xc, action, log_probs, adv, state_value, ret, table):
+    def _ppo_loop(self, xs, xo, xc, action, log_probs, adv, state_value, ret, table, global_rows=None):
         """mappo.py:446-461: per epoch one permutation, per minibatch the actor's update and then the critic's.  On the device: no host
-        synchronisation — cached workspaces, scalars written into `table`'s rows, no index check."""
+        synchronisation — cached workspaces, scalars written into `table`'s rows, no index check.  `global_rows` (the data-parallel path):
+        the updates' global forms over the group, their gradients in the two buckets."""
+        kw_a = dict(global_rows=global_rows, entropy_share=1.0 / self.world, group=self.group, bucket=self.actor_bucket) if global_rows is not None else {}
+        kw_c = dict(global_rows=global_rows, group=self.group, bucket=self.critic_bucket) if global_rows is not None else {}
         N, T, A, D = xs.shape
         dev, K = xs.device, int(xc.shape[3])
         ws_a = ws_c = None
@@ -195,9 +291,9 @@ class DeviceLearner:
                 out_a = table[m, :len(ACTOR_COLUMNS)] if ws_a is not None else None
                 out_c = table[m, len(ACTOR_COLUMNS):] if ws_c is not None else None
                 sa = actor_train.update_actor(self.actor, xs, xo, xc, action, log_probs, adv, self.actor_opt, index=idx, cfg=self.cfg,
-                                              workspace=ws_a, out=out_a)
+                                              workspace=ws_a, out=out_a, **kw_a)
                 sc = critic_train.update_critic(self.critic, xs, xo, xc, state_value, ret, self.critic_opt, index=idx, cfg=self.cfg,
-                                                workspace=ws_c, out=out_c)
+                                                workspace=ws_c, out=out_c, **kw_c)
                 if ws_a is None:                                 # CPU: the updates return their scalars
                     table[m] = torch.stack([(sa | sc)[k].reshape(()).to(torch.float32) for k in COLUMNS])
                 m += 1
@@ -253,11 +349,11 @@ class DeviceLearner:
                 else:
                     for k, v in sd["value_normalizer"].items():
                         getattr(self.value_normalizer, k).copy_(v)
-        for name, key, make in (("actor_opt", "actor_opt", lambda: actor_train.make_optimizer(self.actor, self.cfg)),
-                                ("critic_opt", "critic_opt", lambda: critic_train.make_optimizer(self.critic, self.cfg)),
-                                ("tp_opt", "TP_opt", lambda: tp_train.TPAdam(tp_train.parameters(self.tp_net), lr=1e-4))):
+        for name, key, make in self._optimizer_makers():
             if getattr(self, name) is None:
                 continue
             setattr(self, name, make())
             if key in sd:
                 getattr(self, name).load_state_dict(sd[key])
+        if self.group is not None:                               # one state on every rank: rank 0's
+            self._broadcast_state()

@@ -6,8 +6,11 @@ the rollout, the preparation of a `hns_*_train_grad` call, and the training rest
 reads the same whichever update raised it.
 
 `ClippedAdam` (optim's, re-exported here) is clip_grad_norm_ + torch.optim.Adam (amsgrad off, weight decay 0) with the device step every update
-shares.  Every step bumps the parameters' version counters, so `policy.DevicePolicy` re-packs its operand image before the next forward pass.  A
-data-parallel caller all-reduces the `.grad` tensors and recomputes the norm between the two calls.  DESIGN.md §7.4-7.5."""
+shares.  Every step bumps the parameters' version counters, so `policy.DevicePolicy` re-packs its operand image before the next forward pass.
+
+`GradBucket` is the data-parallel caller's part (learner.DeviceLearner(group=)): one flat buffer behind a network's `.grad`
+tensors, so the `*_train_grad_global` entries write straight into what ONE all-reduce sums and ONE `hns_grad_norm` call measures, between the
+gradient call and the step.  DESIGN.md §7.4-7.5."""
 import ctypes as C
 
 import torch
@@ -16,6 +19,7 @@ import torch.nn.functional as F
 
 from . import abi
 from . import policy as P
+from . import sharding
 from .optim import ClippedAdam  # noqa: F401  (the two updates' optimiser, public here)
 
 
@@ -106,6 +110,29 @@ def validate(word, p, xs, xo, xc, per_row, index, check_index):
     return N, T, A, D, int(xc.shape[3])
 
 
+def _batch(batch_type, xs, xo, xc, index, N, T, B):
+    """The observation / index part of a `batch_type` (hns_critic_batch / hns_actor_batch) over tensors whose last stride is 1."""
+    b = batch_type()
+    b.obs_self, b.obs_cylinders = xs.data_ptr(), xc.data_ptr()
+    b.obs_others = xo.data_ptr() if xo is not None else None
+    b.self_stride[:] = [xs.stride(0), xs.stride(1), xs.stride(2)]
+    b.others_stride[:] = [xo.stride(0), xo.stride(1), xo.stride(2), xo.stride(3)] if xo is not None else [0, 0, 0, 0]
+    b.cyl_stride[:] = [xc.stride(0), xc.stride(1), xc.stride(2), xc.stride(3)]
+    b.num_envs, b.num_steps, b.batch = N, T, B
+    b.index = index.data_ptr() if index is not None else None
+    b._keep = (xs, xo, xc)                                       # a fix-up copy lives as long as the struct that points at it
+    return b
+
+
+def fill_batch(batch_type, xs, xo, xc, index, shape):
+    """`_batch` for a forward-only call (critic_train.value_loss_sums) on validated tensors; the per-row pointers are the caller's."""
+    N, T = shape[:2]
+    xs, xc = (t if t.stride(-1) == 1 else t.contiguous() for t in (xs, xc))
+    if xo is not None and xo.stride(-1) != 1:
+        xo = xo.contiguous()
+    return _batch(batch_type, xs, xo, xc, index, N, T, index.numel() if index is not None else N * T)
+
+
 def prepare_call(word, p, xs, xo, xc, index, shape, workspace_bytes, workspace, out, n_out, batch_type):
     """The arguments of a hns_*_train_grad call on validated device tensors: (net, grd, batch, ws, nbytes, scal, B, stream) — the filled
     hns_policy_net of the parameters and of their .grad tensors (created where absent), a `batch_type` with its observation / index part
@@ -133,20 +160,108 @@ def prepare_call(word, p, xs, xo, xc, index, shape, workspace_bytes, workspace, 
             t.grad = torch.empty_like(t)
         setattr(net, f, t.data_ptr())
         setattr(grd, f, t.grad.data_ptr())
-    b = batch_type()
-    b.obs_self, b.obs_cylinders = xs.data_ptr(), xc.data_ptr()
-    b.obs_others = xo.data_ptr() if xo is not None else None
-    b.self_stride[:] = [xs.stride(0), xs.stride(1), xs.stride(2)]
-    b.others_stride[:] = [xo.stride(0), xo.stride(1), xo.stride(2), xo.stride(3)] if xo is not None else [0, 0, 0, 0]
-    b.cyl_stride[:] = [xc.stride(0), xc.stride(1), xc.stride(2), xc.stride(3)]
-    b.num_envs, b.num_steps, b.batch = N, T, B
-    b.index = index.data_ptr() if index is not None else None
-    b._keep = (xs, xo, xc)                                       # a fix-up copy lives as long as the struct that points at it
+    b = _batch(batch_type, xs, xo, xc, index, N, T, B)
     if ws is None:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     if scal is None:
         scal = torch.empty(n_out, dtype=torch.float32, device=dev)
     return net, grd, b, ws, nbytes, scal, B, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+class GradBucket:
+    """One flat fp32 buffer behind the `.grad` tensors of a network: every parameter's gradient is a contiguous view of `flat`, in the order
+    given (registration order: the optimiser's), each view starting on a 16-byte boundary; the padding between them and behind the last one is
+    zero and stays zero (nothing writes it), so it adds nothing to a sum or to the norm.  `prepare_call` and tp_train accept existing contiguous
+    `.grad` tensors, so the device kernels write straight into the bucket.
+
+    flat: the buffer ([numel padded to a multiple of 4]); all_reduce(group): SUM over the group, in place; norm(out=None): the 2-norm of
+    `flat` as a one-element fp32 tensor (`out`: where to write it) — hns_grad_norm on the device, the fp64 sum of squares rounded once on the CPU;
+    adopt(): after a CPU backward that REPLACED the `.grad` tensors, copies them into the views and puts the views back."""
+
+    def __init__(self, parameters):
+        self.params = list(parameters.values() if hasattr(parameters, "values") else parameters)
+        if not self.params:
+            raise ValueError("GradBucket needs at least one parameter")
+        dev = self.params[0].device
+        self.offsets, n = [], 0
+        for p in self.params:
+            if p.dtype != torch.float32 or p.device != dev:
+                raise ValueError("GradBucket takes float32 parameters on one device")
+            self.offsets.append(n)
+            n += (p.numel() + 3) // 4 * 4
+        self.flat = torch.zeros(max(n, 4), dtype=torch.float32, device=dev)
+        if self.flat.data_ptr() % 16:
+            raise RuntimeError("the allocator returned a buffer that is not 16-byte aligned")
+        self.views = [self.flat[o:o + p.numel()].view(p.shape) for o, p in zip(self.offsets, self.params)]
+        for p, v in zip(self.params, self.views):
+            p.grad = v
+        self._ws = None
+
+    def owns(self, parameters):
+        """True when exactly these parameters, in this order, have their `.grad` in the bucket."""
+        ps = list(parameters)
+        return len(ps) == len(self.params) and all(a is b and a.grad is not None and a.grad.data_ptr() == v.data_ptr() and a.grad.shape == v.shape
+                                                   for a, b, v in zip(ps, self.params, self.views))
+
+    def adopt(self):
+        with torch.no_grad():
+            for p, v in zip(self.params, self.views):
+                if p.grad is not v:
+                    if p.grad is None:
+                        v.zero_()
+                    else:
+                        v.copy_(p.grad)
+                    p.grad = v
+
+    def all_reduce(self, group):
+        sharding.all_reduce_sum(self.flat, group)
+        return self.flat
+
+    def norm(self, out=None):
+        dev = self.flat.device
+        if out is None:
+            out = torch.empty(1, dtype=torch.float32, device=dev)
+        elif not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != dev or out.numel() != 1 or not out.is_contiguous():
+            raise ValueError(f"out must be one float32 value on {dev}")
+        if not self.flat.is_cuda:
+            with torch.no_grad():
+                out.copy_(self.flat.double().square().sum().sqrt().to(torch.float32).reshape(out.shape))
+            return out
+        lib = abi.load_library()
+        n = self.flat.numel()
+        nbytes = lib.hns_grad_norm_workspace_bytes(n)
+        if self._ws is None:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.hns_grad_norm(self.flat.data_ptr(), n, out.data_ptr(), self._ws.data_ptr(), nbytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        abi.check(rc, "hns_grad_norm")
+        return out
+
+
+def check_global(word, p, global_rows, rows, group, bucket):
+    """The refusals of an update's data-parallel arguments: `global_rows` (all ranks' rows of the minibatch) covers this rank's; a `group`
+    needs `global_rows` and a `bucket` that holds exactly this network's gradients."""
+    if global_rows is None:
+        if group is not None or bucket is not None:
+            raise ValueError(f"{word}: group= and bucket= belong to the data-parallel call: pass global_rows= as well")
+        return
+    if int(global_rows) < rows:
+        raise ValueError(f"{word}: global_rows {global_rows} is less than this rank's {rows} rows")
+    if group is not None and bucket is None:
+        raise ValueError(f"{word}: group= needs the GradBucket that is all-reduced (bucket=)")
+    if bucket is not None and (len(bucket.params) != len(p) or any(a is not b for a, b in zip(bucket.params, p.values()))):
+        raise ValueError(f"{word}: bucket= must be the GradBucket of this network's parameters, in their order")
+    if bucket is not None and bucket.flat.is_cuda and not bucket.owns(p.values()):      # (a CPU backward replaces .grad; adopt() takes it in)
+        raise ValueError(f"{word}: a parameter's .grad no longer lies in bucket=")
+
+
+def finish_global(bucket, group, out=None):
+    """What follows a `*_train_grad_global` call: the bucket's all-reduce over `group` (when given) and the norm of the result."""
+    if bucket is None:
+        return None
+    if group is not None:
+        bucket.all_reduce(group)
+    return bucket.norm(out)
 
 
 def encoder(p, xs, xo, xc):

@@ -138,6 +138,57 @@ def _coll_tensor(t):
     return t.contiguous() if dist.get_backend() == "nccl" else t.cpu().contiguous()
 
 
+# ---- the data-parallel learner's collectives (learner.DeviceLearner(group=)) ------------------------------------------------
+def resolve_group(group):
+    """None (no data parallelism), "world" (the default process group) or a torch.distributed process group -> the group object or None."""
+    if group is None:
+        return None
+    if not (dist.is_available() and dist.is_initialized()):
+        raise RuntimeError("group= needs an initialised torch.distributed process group")
+    return dist.group.WORLD if isinstance(group, str) and group == "world" else group
+
+
+def _on_host(t, group):
+    """True where the group's backend moves host tensors only (gloo: CPU tests and the one-card correctness runs)."""
+    return t.is_cuda and dist.get_backend(group) != "nccl"
+
+
+def all_reduce_sum(t, group):
+    """SUM all-reduce of a contiguous tensor IN PLACE over `group`.  RCCL reduces device tensors in the stream; gloo takes a host copy and
+    writes the result back (a host synchronisation that is gloo's, not the learner's)."""
+    if not t.is_contiguous():
+        raise ValueError("all_reduce_sum takes a contiguous tensor")
+    if _on_host(t, group):
+        h = t.cpu()
+        dist.all_reduce(h, group=group)
+        t.copy_(h)
+    else:
+        dist.all_reduce(t, group=group)
+    return t
+
+
+def all_gather_rows(row, group):
+    """[world, len(row)] int64 on the host from one small int64 row per rank (counts and settings: the values are needed on the host)."""
+    src = torch.as_tensor(row, dtype=torch.int64).reshape(-1)
+    if dist.get_backend(group) == "nccl":
+        src = src.cuda()
+    parts = [torch.empty_like(src) for _ in range(dist.get_world_size(group))]
+    dist.all_gather(parts, src, group=group)
+    return torch.stack(parts).cpu()
+
+
+def broadcast_from_first(t, group):
+    """The group's rank 0's values into every rank's `t` through copy_, so the tensor's version counter moves and its consumers re-pack."""
+    src = dist.get_global_rank(group, 0)
+    buf = t.detach().clone().contiguous()
+    if _on_host(buf, group):
+        buf = buf.cpu()
+    dist.broadcast(buf, src=src, group=group)
+    if dist.get_rank(group) != 0:
+        with torch.no_grad():
+            t.copy_(buf)
+
+
 def global_mean(values):
     """Mean over the WHOLE sharded batch (one all-reduce of [sum, count])."""
     v = values.reshape(-1).double()

@@ -3,7 +3,8 @@
 `loss_and_grad(tp, x, y, index)` is update_TP's first four statements (forward, nn.MSELoss, zero_grad, backward): device tensors go to ONE call
 of `hns_tp_train_grad` (two launches: per-workgroup partial gradients on the matrix cores, then a fixed-order sum) that fills every parameter's
 `.grad` in its PyTorch layout and returns the loss as a 0-dim device tensor — no autograd graph, no host synchronisation.  `index` reads a
-minibatch of `make_dataset_naive` (mappo.py:493-513) in place.  A data-parallel caller can all_reduce the `.grad` tensors before the step.
+minibatch of `make_dataset_naive` (mappo.py:493-513) in place.  `update_tp(group=)` is the data-parallel caller: the ranks' gradients, weighted
+by their minibatch sizes, are summed in one bucket before the step.
 
 `TPAdam` (optim's, re-exported here) is torch.optim.Adam (amsgrad off, weight decay 0, lr 1e-4) with the device step every update shares.  Every
 step bumps the parameters' version counters, so the env re-packs its operand image before the next `hns_tp_observe`
@@ -141,8 +142,9 @@ def select_windows(tp_input, tp_groundtruth, tp_done, future_step, window_step):
     windows = tp_groundtruth.unfold(dimension=1, size=future_step + 1, step=window_step).transpose(2, 3)[:, :, 1:]
     batch, _, fs, pos_dim = windows.shape
     mask = tp_done[:, :windows.shape[1]].squeeze(-1).unsqueeze(-1).unsqueeze(-1).expand_as(windows).bool()
-    selected = torch.masked_select(windows, mask).view(batch, -1, fs, pos_dim)
-    n_sel = selected.shape[1]
+    selected = torch.masked_select(windows, mask)
+    n_sel = selected.numel() // max(batch * fs * pos_dim, 1)     # (view(batch, -1, ..) cannot infer the count of an empty selection)
+    selected = selected.view(batch, n_sel, fs, pos_dim)
     return tp_input[:, :n_sel], selected.reshape(batch * n_sel, fs * pos_dim)
 
 
@@ -152,15 +154,57 @@ def minibatches(rows, num_minibatches, device, generator=None):
     return torch.randperm((rows // num_minibatches) * num_minibatches, device=device, generator=generator).reshape(num_minibatches, -1)
 
 
-def update_tp(tp, tp_input, tp_groundtruth, tp_done, future_step, window_step, num_minibatches, epochs, optimizer, generator=None):
+def update_tp(tp, tp_input, tp_groundtruth, tp_done, future_step, window_step, num_minibatches, epochs, optimizer, generator=None, group=None,
+              bucket=None):
     """MAPPOPolicy.train_op's predictor block (mappo.py:405-441) with update_TP (:252-268): tp_input [E, steps, T, I], tp_groundtruth
     [E, steps, 3], tp_done [E, steps, 1] (the rollout's ('next', 'agents', 'TP') entries).  Returns the mean minibatch loss as a 0-dim tensor.
-    `generator`: the torch.Generator every epoch's permutation is drawn from (None: the global one)."""
+    `generator`: the torch.Generator every epoch's permutation is drawn from (None: the global one).
+
+    `group` (a torch.distributed process group; None: the call above, untouched): every rank holds the windows its own TP_done selects, and
+    the ranks step together on the union of their minibatches.  The selected-window counts are gathered ONCE; minibatch k of a rank has
+    n_r = rows_r // num_minibatches windows, its gradient (a mean over n_r) is weighted by n_r / sum n before the SUM all-reduce of `bucket`
+    (a policy_train.GradBucket over `parameters(tp)`; made here when None), and TP_loss is the same weighted mean (one all-reduce of the loss
+    vector at the end).  A rank with n_r = 0 contributes zeros and still joins every collective; sum n = 0 skips the epochs on ALL ranks (the
+    decision is the gathered counts', never a local one) and returns 0."""
     x, y = select_windows(tp_input, tp_groundtruth, tp_done, future_step, window_step)
     rows = x.shape[0] * x.shape[1]
+    if group is not None:
+        return _update_tp_group(tp, x, y, rows, num_minibatches, epochs, optimizer, generator, group, bucket)
     losses = []
     for _ in range(epochs):
         for idx in minibatches(rows, num_minibatches, x.device, generator):
             losses.append(loss_and_grad(tp, x, y, idx, check_index=False))
             optimizer.step()
     return torch.stack(losses).mean()
+
+
+def _update_tp_group(tp, x, y, rows, num_minibatches, epochs, optimizer, generator, group, bucket):
+    from . import policy_train as PT
+    from . import sharding
+    dev = x.device
+    params = parameters(tp)
+    if bucket is None:
+        bucket = PT.GradBucket(params)
+    elif len(bucket.params) != len(params) or any(a is not b for a, b in zip(bucket.params, params)):
+        raise ValueError("bucket= must be the GradBucket of parameters(tp)")
+    counts = sharding.all_gather_rows([rows // num_minibatches], group)[:, 0].tolist()       # the call's one gather: n_r of every rank
+    n_mine, n_all = rows // num_minibatches, sum(counts)
+    if n_all == 0:
+        return torch.zeros((), dtype=torch.float32, device=dev)
+    weight = n_mine / n_all
+    losses = torch.zeros(epochs * num_minibatches, dtype=torch.float32, device=dev)
+    k = 0
+    for _ in range(epochs):
+        batches = minibatches(rows, num_minibatches, dev, generator) if n_mine else [None] * num_minibatches
+        for idx in batches:
+            if idx is None:
+                bucket.flat.zero_()
+            else:
+                loss = loss_and_grad(tp, x, y, idx, check_index=False)
+                bucket.adopt()                                   # (the CPU backward replaces .grad; on the device the kernels wrote the views)
+                bucket.flat.mul_(weight)
+                losses[k] = loss * weight
+            bucket.all_reduce(group)
+            optimizer.step()
+            k += 1
+    return sharding.all_reduce_sum(losses, group).mean()
