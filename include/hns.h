@@ -667,6 +667,31 @@ int hns_actor_train_grad_global(const hns_policy_net *actor, const hns_actor_bat
                                 double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
                                 float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream, int64_t global_rows,
                                 double entropy_share);
+/*
+ * The PartialAttentionEncoder alone as a differentiable op (hns_amd.encoder): the forward pass gives the 128 features of every
+ * (env-step, agent) row of a minibatch, the backward pass takes d features and gives the gradients of the encoder's 20 parameter tensors, so any
+ * head, loss, optimiser or schedule can be written on top of it (torch.autograd, or any other caller).  The kernels are the updates' tile kernel
+ * without a head and without a loss; the backward pass recomputes its tile's forward pass, so nothing is kept between the two calls.  `net`:
+ * hns_policy_net, whose head_w, head_b and log_std are ignored (NULL is fine); `batch`: hns_critic_batch, whose b_values and b_returns are ignored
+ * (NULL is fine).  features / dfeatures: fp32 [batch x num_agents, 128] row-major, 16-byte aligned, row = minibatch position x num_agents + agent
+ * (the row order of hns_critic_train_grad's `values`).  A row whose index lies outside [0, N T) contributes nothing: its feature row is not
+ * written, its dfeatures row is not read.  Properties of both calls: one stream, no host synchronisation, no allocation, fixed-order sums, no
+ * float atomics, the same inputs give the same bits.  Refused before any launch, in hns_critic_train_grad's order: shape, NULL or misaligned
+ * parameters (and gradients), observation pointers, strides, a NULL or misaligned features / dfeatures, index, workspace.
+ *
+ * hns_encoder_workspace_bytes: bytes of device workspace for `rows` = batch x num_agents rows (backward != 0: hns_encoder_backward's); 0 for an
+ * invalid shape.  Forward: the packed operand image alone (0.8 MB).  Backward: hns_critic_train_workspace_bytes without the branch weights and
+ * the loss partials.
+ * hns_encoder_forward: two launches (pack, tiles).
+ * hns_encoder_backward: each of the 20 encoder tensors of `grads` is WRITTEN (not accumulated) in its PyTorch layout with the gradient of
+ * sum(features x dfeatures): dfeatures is used as given, no 1 / n.  in_proj_b's k third receives zeros; the state_others embedding is written only
+ * when num_agents > 1; the head fields of `grads` are ignored.  Four launches (pack, tiles, weight gradients, reduce); no gradient norm.
+ */
+size_t hns_encoder_workspace_bytes(int64_t rows, int32_t self_dim, int32_t num_agents, int32_t num_cylinders, int32_t backward);
+int hns_encoder_forward(const hns_policy_net *net, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                        float *features, void *workspace, size_t workspace_bytes, void *stream);
+int hns_encoder_backward(const hns_policy_net *net, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                         const float *dfeatures, const hns_policy_grads *grads, void *workspace, size_t workspace_bytes, void *stream);
 /* The 2-norm of one flat fp32 gradient bucket: norm[0] = f32(sqrt(sum_i flat[i]^2)), in this order (tests/dp_reference.py restates it in numpy):
  * the bucket is cut into quads of four consecutive floats, the last one short by numel % 4 values that count as 0 (nothing past numel is
  * read); G = clamp(ceil(quads / 1024), 1, 64) workgroups of 256 threads, T = 256 G; thread t of the grid adds, for q = t, t + T, t + 2 T, ...,

@@ -32,6 +32,12 @@
 //                                of the ratios; head_w [4][128], head_b [4] and log_std [4] leave in the tile's partial rows.
 //   hns_actor_loss_kernel      : one workgroup adds the partials in a fixed order: policy_loss, entropy, ESS.
 //   pack, wgrad, reduce (which adds -entropy_coef to d log_std, once) and norm kernels: the critic's.
+// The encoder alone as a differentiable op (hns_encoder_forward / hns_encoder_backward; hns_amd.encoder) is the tile kernel
+// with HEAD = 0 — no head, no loss:
+//   hns_critic_kernel<false, 0> : forward up to y = LN2(x0' + ff); y leaves as fp32 [rows, 128], row = minibatch position x A + agent.
+//   hns_critic_kernel<true, 0>  : recomputes the tile's forward pass, reads the row's dy from a [rows, 128] array (as given: no 1 / n) and runs the
+//                                 backward pass above; a tile's partial rows carry no head entries.
+//   wgrad as above; hns_encoder_reduce_kernel is the reduce kernel's body without the head's destinations; no norm launch.
 // Determinism: every sum has a fixed order, no float atomics: the same inputs give the same bits.
 #include <hip/hip_runtime.h>
 
@@ -72,6 +78,7 @@ enum : int {
 // [3][128] and log_std [4]; the critic's layout (heads = 1) ends at the embedding
 constexpr int kActDim = 4;                   // DiagGaussian's action dimension (fc_mean's rows)
 constexpr int kActLossSlots = 1 + 3 * HNS_MAX_AGENTS;   // a tile's fp64 partials: sum of the surrogate, then (max, s1, s2) of the ratios per agent
+// (heads = 0, the encoder op: the critic's layout, its O_HW and O_HB slots never written and never read)
 static __host__ __device__ constexpr int ct_partial_floats(int D, int heads = 1) { return O_EWS + D * kCtE + (heads > 1 ? (heads - 1) * kCtE + heads : 0); }
 static_assert((6 * kCtGemmOut + 31) / 32 + (ct_partial_floats(kCtMaxSelf, kActDim) + 31) / 32 <= kCtMaxBlocks, "the reduce kernel's grid outgrew its per-block sums");
 
@@ -105,11 +112,13 @@ struct CtArgs {
     const long long *index;                  // [batch] env-steps, or NULL
     long long rows;                          // batch A
     int A, K, D, tiles;
-    union { const float *bval; const float *logp_old; };       // [steps, A]: the critic's old values / the actor's old log-probabilities
+    // [steps, A]: the critic's old values / the actor's old log-probabilities; the encoder op's d features [rows, 128]
+    union { const float *bval; const float *logp_old; const float *dfeat; };
     union { const float *bret; const float *adv; };            // [steps, A]: the critic's returns / the actor's advantages
     float clip, delta, inv_n;
     int mse;
-    union { float *values; float *logp_new; };                 // [rows] or NULL: the critic's values / the actor's new log-probabilities
+    // [rows] or NULL: the critic's values / the actor's new log-probabilities; the encoder op's features [rows, 128]
+    union { float *values; float *logp_new; float *feat; };
     double *losspart;                        // [tiles][5]; the actor: [tiles][kActLossSlots]
     const float *ctl;                        // branch weights (written by hns_critic_loss_kernel)
     float *tilepart;                         // [2 tiles][P]
@@ -222,7 +231,7 @@ HNS_DEV float ct_token_j(const CtArgs &a, const CtRow &R, int j, int g, float (&
 
 template <bool BWD, int HEAD = 1>
 __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(const CtArgs a) {
-    static_assert(HEAD == 1 || (HEAD == kActDim && BWD), "the actor's head runs in the one-pass kernel");
+    static_assert(HEAD == 0 || HEAD == 1 || (HEAD == kActDim && BWD), "the actor's head runs in the one-pass kernel");
     extern __shared__ __align__(16) unsigned char lds_raw[];
     CtLds &L = *reinterpret_cast<CtLds *>(lds_raw);
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
@@ -289,9 +298,22 @@ __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(con
 #pragma unroll
         for (int i = 0; i < 16; ++i) u[i] = x1[i] + t[i];
         const float rstd2 = enc_layernorm(u, N.n2_w, N.n2_b, g, xh2, y);                            // y = LN2(x0' + ff)
-        float dv = 0.0f, dmu[HEAD];
+        float dv = 0.0f, dmu[HEAD ? HEAD : 1];
         float dy[16], dw[16], db[16], dx[16];
-        if constexpr (HEAD == 1) {
+        if constexpr (HEAD == 0) {
+            // ---- the encoder op: the features leave, or d features arrive, as [rows, 128]; a row that is not live is neither written nor read
+            if (!BWD) {
+                if (R.live) crow_store(a.feat + row * kCtE, kCtE, 0, g, y);
+                return;
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                dy[i] = 0.0f;
+                dw[i] = 0.0f;
+                db[i] = 0.0f;
+            }
+            if (R.live) enc_vec_load(a.dfeat + row * kCtE, g, dy);
+        } else if constexpr (HEAD == 1) {
             float hw[16];
             enc_vec_load(N.head_w, g, hw);
             s = 0.0f;
@@ -414,7 +436,7 @@ __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(con
         if constexpr (HEAD == 1) {
             if (g == 0) L.sc[r] = dv;
             ct_flush(L, u, part, a.P, O_HW, tid, r, g);
-        } else {
+        } else if constexpr (HEAD == kActDim) {
 #pragma unroll
             for (int i = 0; i < HEAD; ++i) {                        // d fc_mean.weight[i] = sum_rows d mu_i y
 #pragma unroll
@@ -800,6 +822,8 @@ HNS_DEV float *ct_dst_gemm(const CtGrad &g, int e, bool &zero) {
     }
 }
 
+// HEADS false (the encoder op): head_w, head_b and log_std have no destination
+template <bool HEADS>
 HNS_DEV float *ct_dst_tile(const CtGrad &g, int D, int heads, int e) {
     if (e < O_EWO) {
         const int f = e & 127;
@@ -810,7 +834,7 @@ HNS_DEV float *ct_dst_tile(const CtGrad &g, int D, int heads, int e) {
             case 3: return g.n1_b + f;
             case 4: return g.n2_w + f;
             case 5: return g.n2_b + f;
-            case 6: return g.head_w + f;
+            case 6: return HEADS ? g.head_w + f : nullptr;
             case 7: return g.eb[0] + f;
             case 8: return g.eb[1] ? g.eb[1] + f : nullptr;
             default: return g.eb[2] + f;
@@ -818,16 +842,18 @@ HNS_DEV float *ct_dst_tile(const CtGrad &g, int D, int heads, int e) {
     }
     if (e < O_EWC) return g.ew[1] ? g.ew[1] + ((e - O_EWO) & 127) * 3 + ((e - O_EWO) >> 7) : nullptr;
     if (e < O_HB) return g.ew[2] + ((e - O_EWC) & 127) * 5 + ((e - O_EWC) >> 7);
-    if (e < O_EWS) return e - O_HB < heads ? g.head_b + (e - O_HB) : nullptr;
+    if (e < O_EWS) return HEADS && e - O_HB < heads ? g.head_b + (e - O_HB) : nullptr;
     if (e < O_EWS + D * kCtE) return g.ew[0] + ((e - O_EWS) & 127) * D + ((e - O_EWS) >> 7);
+    if (!HEADS) return nullptr;
     const int x = e - (O_EWS + D * kCtE);                       // the actor's head: rows 1 .. heads - 1 of head_w, then log_std
     return x < (heads - 1) * kCtE ? g.head_w + kCtE + x : g.log_std + (x - (heads - 1) * kCtE);
 }
 
 // 32 gradient values per block, 8 threads each: slice s sums its range of the partials in fp64, the slices add up in order.  `ls_add` joins
 // every log_std value's sum once (the actor's -entropy_coef: the entropy term's gradient is the same constant whatever the rows)
-__global__ __launch_bounds__(256) void hns_critic_reduce_kernel(const float *gpart, int splits, const float *tpart, int nt, int P, int gblocks, const CtGrad g,
-                                                                int D, double *blockpart, int heads, double ls_add) {
+template <bool HEADS>
+HNS_DEV void ct_reduce(const float *gpart, int splits, const float *tpart, int nt, int P, int gblocks, const CtGrad &g, int D, double *blockpart, int heads,
+                       double ls_add) {
     __shared__ double sm[8][32];
     __shared__ double sq[32];
     const int tid = threadIdx.x, el = tid & 31, sl = tid >> 5;
@@ -838,7 +864,7 @@ __global__ __launch_bounds__(256) void hns_critic_reduce_kernel(const float *gpa
     const float *src = gemm ? gpart : tpart;
     float *dst = nullptr;
     bool zero = false;
-    if (e < stride) dst = gemm ? ct_dst_gemm(g, e, zero) : ct_dst_tile(g, D, heads, e);
+    if (e < stride) dst = gemm ? ct_dst_gemm(g, e, zero) : ct_dst_tile<HEADS>(g, D, heads, e);
     double acc = 0.0;
     if (dst && !zero) {
         const int lo = (int)((long long)n * sl / 8), hi = (int)((long long)n * (sl + 1) / 8);
@@ -861,6 +887,17 @@ __global__ __launch_bounds__(256) void hns_critic_reduce_kernel(const float *gpa
         for (int q = 0; q < 32; ++q) tot += sq[q];
         blockpart[blockIdx.x] = tot;
     }
+}
+
+__global__ __launch_bounds__(256) void hns_critic_reduce_kernel(const float *gpart, int splits, const float *tpart, int nt, int P, int gblocks, const CtGrad g,
+                                                                int D, double *blockpart, int heads, double ls_add) {
+    ct_reduce<true>(gpart, splits, tpart, nt, P, gblocks, g, D, blockpart, heads, ls_add);
+}
+
+// the encoder op's: the 20 encoder tensors alone (heads = 0); the per-block sums of squares are written and not used
+__global__ __launch_bounds__(256) void hns_encoder_reduce_kernel(const float *gpart, int splits, const float *tpart, int nt, int P, int gblocks, const CtGrad g,
+                                                                 int D, double *blockpart) {
+    ct_reduce<false>(gpart, splits, tpart, nt, P, gblocks, g, D, blockpart, 0, 0.0);
 }
 
 __global__ __launch_bounds__(256) void hns_critic_norm_kernel(const double *blockpart, int nb, float *grad_norm) {
@@ -910,6 +947,25 @@ bool ct_plan(int64_t rows, int32_t D, int32_t A, int32_t K, CtPlan &p, int heads
     return true;
 }
 
+// the encoder op's workspace (heads = 0: the critic's tile layout).  Forward: the packed operand image alone.  Backward: the image, the tiles'
+// partial rows, the weight-gradient partials, the staged operand pairs and the reduce kernel's per-block sums — no branch weights, no loss partials
+bool ct_plan_encoder(int64_t rows, int32_t D, int32_t A, int32_t K, bool backward, CtPlan &p) {
+    if (!ct_plan(rows, D, A, K, p, 0)) return false;
+    size_t o = 0;
+    p.o_ctl = p.o_loss = 0;
+    p.o_img = o; o += ct_up((size_t)hns::ct_img_floats(D) * sizeof(float));
+    if (backward) {
+        p.o_block = o; o += ct_up((size_t)hns::kCtMaxBlocks * sizeof(double));
+        p.o_tile = o; o += ct_up((size_t)p.tiles * 2 * p.P * sizeof(float));
+        p.o_gemm = o; o += ct_up((size_t)p.splits * 6 * hns::kCtGemmOut * sizeof(float));
+        p.o_stage = o; o += ct_up((size_t)12 * p.stage_rows * hns::kCtE * sizeof(float));
+    } else {
+        p.o_block = p.o_tile = p.o_gemm = p.o_stage = 0;
+    }
+    p.total = o;
+    return true;
+}
+
 // What the critic's and the actor's entry points share.  hns_critic_batch and hns_actor_batch carry the same leading fields under the same names:
 // the templates over the batch type read them from either.  Every refusal keeps the entry point's order: ct_check_shape, the entry's hyper-parameters,
 // ct_bind_net, ct_check_obs, the entry's per-row pointers, ct_plan_call.
@@ -926,14 +982,16 @@ int ct_check_shape(const char *fn, const Batch &b, int32_t self_dim, int32_t num
     return HNS_OK;
 }
 
-// the parameter and gradient tables, checked and copied by ONE field list (heads > 1: the actor, whose log_std joins both).  grads NULL: a
-// forward-only entry (hns_critic_train_sums) binds the parameters alone and `g` stays empty
+// the parameter and gradient tables, checked and copied by ONE field list (heads > 1: the actor, whose log_std joins both; heads 0: the encoder
+// op, whose head fields are ignored and left NULL).  grads NULL: a forward-only entry (hns_critic_train_sums, hns_encoder_forward) binds the
+// parameters alone and `g` stays empty
 int ct_bind_net(const char *fn, const hns_policy_net &net, const hns_policy_grads *grads, bool others, int heads, hns::EncNet &n, hns::CtGrad &g) {
     bool ok = true;
-#define X(f, m)                                                                                      \
-    ok = ok && net.f && hns_aligned(net.f, 16) && (!grads || (grads->f && hns_aligned(grads->f, 4)));  \
-    n.m = net.f;                                                                                     \
-    g.m = grads ? grads->f : nullptr;
+    const auto ignored = [&](const float *const *f) { return heads == 0 && (f == &net.head_w || f == &net.head_b); };
+#define X(f, m)                                                                                                                \
+    ok = ok && (ignored(&net.f) || (net.f && hns_aligned(net.f, 16) && (!grads || (grads->f && hns_aligned(grads->f, 4)))));  \
+    n.m = ignored(&net.f) ? nullptr : net.f;                                                                                   \
+    g.m = grads && !ignored(&net.f) ? grads->f : nullptr;
     HNS_CT_FIELDS(X)
 #undef X
     if (heads > 1) ok = ok && net.log_std && hns_aligned(net.log_std, 16) && (!grads || (grads->log_std && hns_aligned(grads->log_std, 4)));
@@ -961,17 +1019,21 @@ int ct_check_obs(const char *fn, const Batch &b, bool others) {
 
 // the last refusals (index, `outs`: the entry's fp32 outputs, a NULL optional one among them; the plan and the workspace), then the part of the
 // kernel arguments that is the same for both networks: observations, index, shape, the workspace's arrays
+// heads 0: the encoder op, whose plan is ct_plan_encoder's (`backward`: hns_encoder_backward's)
 template <typename Batch>
 int ct_plan_call(const char *fn, const Batch &b, std::initializer_list<const float *> outs, void *workspace, size_t workspace_bytes, int32_t self_dim,
-                 int32_t num_agents, int32_t num_cylinders, int heads, CtPlan &p, hns::CtArgs &a) {
+                 int32_t num_agents, int32_t num_cylinders, int heads, CtPlan &p, hns::CtArgs &a, bool backward = true) {
     if (b.index && !hns_aligned(b.index, 8)) return hns_fail(fn, "misaligned index");
     bool ok = hns_aligned(workspace, 256);
     for (const float *o : outs) ok = ok && hns_aligned(o, 4);
     if (!ok) return hns_fail(fn, "misaligned output (scalars 4 bytes, workspace 256)");
     const int64_t rows = b.batch * num_agents;
-    if (!ct_plan(rows, self_dim, num_agents, num_cylinders, p, heads)) return hns_fail(fn, "invalid shape");
+    if (heads == 0 ? !ct_plan_encoder(rows, self_dim, num_agents, num_cylinders, backward, p) : !ct_plan(rows, self_dim, num_agents, num_cylinders, p, heads))
+        return hns_fail(fn, "invalid shape");
     if (workspace_bytes < p.total)
-        return hns_fail(fn, heads > 1 ? "workspace too small (hns_actor_train_workspace_bytes)" : "workspace too small (hns_critic_train_workspace_bytes)");
+        return hns_fail(fn, heads > 1    ? "workspace too small (hns_actor_train_workspace_bytes)"
+                            : heads == 1 ? "workspace too small (hns_critic_train_workspace_bytes)"
+                                         : "workspace too small (hns_encoder_workspace_bytes)");
 
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     a.img = reinterpret_cast<float *>(ws + p.o_img);
@@ -998,8 +1060,8 @@ int ct_launch_pack(hipStream_t st, const hns::CtArgs &a, const CtPlan &p, void *
     return HNS_OK;
 }
 
-// the launches behind them: weight gradients, the fixed-order sums into the PyTorch layouts (`ls_add`: hns_critic_reduce_kernel's), the total norm
-// (grad_norm NULL: not launched)
+// the launches behind them: weight gradients, the fixed-order sums into the PyTorch layouts (`ls_add`: hns_critic_reduce_kernel's; heads 0: the
+// encoder op's reduce), the total norm (grad_norm NULL: not launched)
 int ct_launch_tail(hipStream_t st, const hns::CtArgs &a, const CtPlan &p, const hns::CtGrad &g, void *workspace, int heads, double ls_add, float *grad_norm) {
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     float *gpart = reinterpret_cast<float *>(ws + p.o_gemm);
@@ -1007,8 +1069,12 @@ int ct_launch_tail(hipStream_t st, const hns::CtArgs &a, const CtPlan &p, const 
     HNS_CHECK_HIP(hipGetLastError());
     double *blockpart = reinterpret_cast<double *>(ws + p.o_block);
     const int nb = p.gblocks + p.tblocks;
-    hipLaunchKernelGGL(hns::hns_critic_reduce_kernel, dim3(nb), dim3(256), 0, st, gpart, (int)p.splits, a.tilepart, (int)(2 * p.tiles), p.P, p.gblocks, g, a.D,
-                       blockpart, heads, ls_add);
+    if (heads == 0)
+        hipLaunchKernelGGL(hns::hns_encoder_reduce_kernel, dim3(nb), dim3(256), 0, st, gpart, (int)p.splits, a.tilepart, (int)(2 * p.tiles), p.P, p.gblocks, g, a.D,
+                           blockpart);
+    else
+        hipLaunchKernelGGL(hns::hns_critic_reduce_kernel, dim3(nb), dim3(256), 0, st, gpart, (int)p.splits, a.tilepart, (int)(2 * p.tiles), p.P, p.gblocks, g,
+                           a.D, blockpart, heads, ls_add);
     HNS_CHECK_HIP(hipGetLastError());
     if (!grad_norm) return HNS_OK;                              // the data-parallel entries: the local norm means nothing (hns_grad_norm after the all-reduce)
     hipLaunchKernelGGL(hns::hns_critic_norm_kernel, dim3(1), dim3(256), 0, st, blockpart, nb, grad_norm);
@@ -1102,6 +1168,40 @@ int ct_actor_call(const char *fn, bool global, const hns_policy_net *actor, cons
     return ct_launch_tail(st, a, p, g, workspace, hns::kActDim, global ? -entropy_coef * entropy_share : -entropy_coef, grad_norm);
 }
 
+// The encoder op's two entries over one body.  Forward: pack, the tile kernel without a head.  Backward: pack, the tile kernel from d features, the
+// weight gradients and the reduce without the head's destinations; no norm.
+int ct_encoder_call(const char *fn, bool backward, const hns_policy_net *net, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents,
+                    int32_t num_cylinders, float *features, const float *dfeatures, const hns_policy_grads *grads, void *workspace, size_t workspace_bytes,
+                    void *stream) {
+    if (int rc = ct_check_shape(fn, *batch, self_dim, num_agents, num_cylinders)) return rc;
+    hns::CtArgs a{};
+    hns::CtGrad g{};
+    CtPlan p;
+    if (int rc = ct_bind_net(fn, *net, grads, num_agents > 1, 0, a.net, g)) return rc;
+    if (int rc = ct_check_obs(fn, *batch, num_agents > 1)) return rc;
+    if (!hns_aligned(backward ? dfeatures : features, 16)) return hns_fail(fn, backward ? "misaligned dfeatures (16 bytes)" : "misaligned features (16 bytes)");
+    if (int rc = ct_plan_call(fn, *batch, {}, workspace, workspace_bytes, self_dim, num_agents, num_cylinders, 0, p, a, backward)) return rc;
+    if (backward) a.dfeat = dfeatures;
+    else a.feat = features;
+
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    static const hipError_t attr_f = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<false, 0>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)hns::kCtLdsFwd);
+    static const hipError_t attr_b = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<true, 0>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::CtLds));
+    HNS_CHECK_HIP(attr_f);
+    HNS_CHECK_HIP(attr_b);
+    if (int rc = ct_launch_pack(st, a, p, workspace)) return rc;
+    if (!backward) {
+        hipLaunchKernelGGL((hns::hns_critic_kernel<false, 0>), dim3((unsigned)p.tiles), dim3(hns::kCtThreads), hns::kCtLdsFwd, st, a);
+        HNS_CHECK_HIP(hipGetLastError());
+        return HNS_OK;
+    }
+    hipLaunchKernelGGL((hns::hns_critic_kernel<true, 0>), dim3((unsigned)p.tiles), dim3(hns::kCtThreads), sizeof(hns::CtLds), st, a);
+    HNS_CHECK_HIP(hipGetLastError());
+    return ct_launch_tail(st, a, p, g, workspace, 0, 0.0, nullptr);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1163,6 +1263,25 @@ int hns_actor_train_grad_global(const hns_policy_net *actor, const hns_actor_bat
     if (!actor || !batch || !grads || !policy_loss || !entropy || !ess || !workspace) return hns_fail(fn, "null pointer");
     return ct_actor_call(fn, true, actor, batch, self_dim, num_agents, num_cylinders, clip_param, entropy_coef, grads, policy_loss, entropy, ess, grad_norm,
                          log_probs, global_rows, entropy_share, workspace, workspace_bytes, stream);
+}
+
+size_t hns_encoder_workspace_bytes(int64_t rows, int32_t self_dim, int32_t num_agents, int32_t num_cylinders, int32_t backward) {
+    CtPlan p;
+    return ct_plan_encoder(rows, self_dim, num_agents, num_cylinders, backward != 0, p) ? p.total : 0;
+}
+
+int hns_encoder_forward(const hns_policy_net *net, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                        float *features, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "hns_encoder_forward";
+    if (!net || !batch || !features || !workspace) return hns_fail(fn, "null pointer");
+    return ct_encoder_call(fn, false, net, batch, self_dim, num_agents, num_cylinders, features, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+int hns_encoder_backward(const hns_policy_net *net, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                         const float *dfeatures, const hns_policy_grads *grads, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "hns_encoder_backward";
+    if (!net || !batch || !dfeatures || !grads || !workspace) return hns_fail(fn, "null pointer");
+    return ct_encoder_call(fn, true, net, batch, self_dim, num_agents, num_cylinders, nullptr, dfeatures, grads, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"
