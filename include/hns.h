@@ -692,6 +692,47 @@ int hns_encoder_forward(const hns_policy_net *net, const hns_critic_batch *batch
                         float *features, void *workspace, size_t workspace_bytes, void *stream);
 int hns_encoder_backward(const hns_policy_net *net, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
                          const float *dfeatures, const hns_policy_grads *grads, void *workspace, size_t workspace_bytes, void *stream);
+/*
+ * The recurrent block of the reference's rnn heads as a differentiable op (hns_amd.rnn): modules/rnn.py's GRU — an nn.GRUCell
+ * stepped over the sequence, the carried state multiplied by 1 - is_init before every step, LayerNorm(h + x) behind it — with input size =
+ * hidden size = 128 (the reference builds it on the encoder's 128 features).  For t = 0 .. L - 1, per sequence s:
+ *     h <- h (1 - is_init[s, t])
+ *     r = sigmoid(W_ir x_t + b_ir + W_hr h + b_hr),  z = sigmoid(W_iz x_t + b_iz + W_hz h + b_hz),  n = tanh(W_in x_t + b_in + r (W_hn h + b_hn))
+ *     h <- (1 - z) n + z h,   out_t = LayerNorm(h + x_t) (eps 1e-5, biased variance),   h_last = h after step L - 1.
+ * Parameters in nn.GRUCell's / nn.LayerNorm's layouts (gate order r, z, n), every pointer 16-byte aligned.  Sequences have a two-level index,
+ * s = b inner + a, so that the encoder op's [B L A, 128] features are read in place as [B, A, L, 128] (x_stride = {L A 128, 128, A 128}) and dx
+ * lands in the order hns_encoder_backward reads; out, dout and dx have x's strides (multiples of 4 floats, >= 0; the 128 values contiguous).
+ * Properties of both calls: one stream, no host synchronisation, no allocation, fixed-order sums, no float atomics, the same inputs give the
+ * same bits; the workspace is used from scratch.  A sequence's results do not depend on the other sequences of the call, and one call over L
+ * steps gives the bits of L one-step calls chained through h_last -> h0.
+ * Refused before any launch: a NULL struct, a NULL or misaligned (16 bytes) parameter, gradient, x, out, h_last, dout or dx; a misaligned h0,
+ * h_hist, dh_last or dh0; steps outside [1, HNS_GRU_MAX_STEPS]; outer or inner < 1 (or outer x inner x steps >= 2^40); a negative stride or one
+ * that is no multiple of 4; hns_gru_backward without h_hist; a workspace that is NULL, not 256-byte aligned or shorter than the size function's.
+ *
+ * hns_gru_workspace_bytes: bytes of device workspace for `seqs` sequences of `steps` steps; the forward pass needs none (0, and takes a NULL
+ * workspace); backward != 0: the gate gradients ([seqs steps, 512] fp32) and the partial sums; 0 for an invalid shape too.
+ * hns_gru_forward: one launch.  h_hist (may be NULL): h after every step, [S, L, 128] — the one activation the backward pass needs.
+ * hns_gru_backward: three launches (sweep, weight gradients, reduce).  WRITES (does not accumulate) the six parameter gradients of
+ * sum(out x dout) + sum(h_last x dh_last) (dh_last NULL: zeros) in their PyTorch layouts, dx, and dh0 when it is not NULL; the gates are
+ * recomputed from x, h0 and h_hist.  dh0 of a sequence with is_init[s, 0] = 1 is zero.
+ */
+#define HNS_GRU_HIDDEN 128     /* input size = hidden size */
+#define HNS_GRU_MAX_STEPS 64   /* the reference asserts train_seq_len <= train_every (64) */
+typedef struct hns_gru_net { const float *weight_ih, *weight_hh, *bias_ih, *bias_hh, *ln_w, *ln_b; } hns_gru_net;   /* [384,128] x2, [384] x2, [128] x2 */
+typedef struct hns_gru_grads { float *weight_ih, *weight_hh, *bias_ih, *bias_hh, *ln_w, *ln_b; } hns_gru_grads;
+typedef struct hns_gru_seq {
+    const float *x;            /* element (b, a, t, i) at b x_stride[0] + a x_stride[1] + t x_stride[2] + i: sequence s = b * inner + a */
+    int64_t x_stride[3];
+    int64_t outer, inner;      /* B, A: S = B * A sequences (inner = 1 for a plain [S, L, 128]) */
+    int32_t steps;             /* L in [1, HNS_GRU_MAX_STEPS] */
+    const float *h0;           /* [S, 128] contiguous, or NULL: zeros */
+    const uint8_t *is_init;    /* [S, L] contiguous, or NULL: none */
+} hns_gru_seq;
+size_t hns_gru_workspace_bytes(int64_t seqs, int32_t steps, int32_t backward);
+int hns_gru_forward(const hns_gru_net *net, const hns_gru_seq *seq, float *out, float *h_last, float *h_hist, void *workspace, size_t workspace_bytes,
+                    void *stream);
+int hns_gru_backward(const hns_gru_net *net, const hns_gru_seq *seq, const float *h_hist, const float *dout, const float *dh_last,
+                     const hns_gru_grads *grads, float *dx, float *dh0, void *workspace, size_t workspace_bytes, void *stream);
 /* The 2-norm of one flat fp32 gradient bucket: norm[0] = f32(sqrt(sum_i flat[i]^2)), in this order (tests/dp_reference.py restates it in numpy):
  * the bucket is cut into quads of four consecutive floats, the last one short by numel % 4 values that count as 0 (nothing past numel is
  * read); G = clamp(ceil(quads / 1024), 1, 64) workgroups of 256 threads, T = 256 G; thread t of the grid adds, for q = t, t + T, t + 2 T, ...,
