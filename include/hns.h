@@ -733,6 +733,40 @@ int hns_gru_forward(const hns_gru_net *net, const hns_gru_seq *seq, float *out, 
                     void *stream);
 int hns_gru_backward(const hns_gru_net *net, const hns_gru_seq *seq, const float *h_hist, const float *dout, const float *dh_last,
                      const hns_gru_grads *grads, float *dx, float *dh0, void *workspace, size_t workspace_bytes, void *stream);
+/*
+ * The recurrent policy's forward pass (actor.rnn / critic.rnn: the GRU block above behind each encoder; hns_amd.policy.RecurrentDevicePolicy;
+ * DESIGN.md §7.12): ONE launch per call runs encoder -> one GRU step -> head for both networks, the state carried by the caller on the device.
+ * Per (env e, agent a) row and per network:
+ *     f = the encoder's output, exactly hns_policy_forward's encoder on the same packed image
+ *     h = is_init[e] ? 0 : h_in[e, a]          (h_in (1 - is_init) for finite h_in; a flagged row's h_in is not read, so NaN there is harmless)
+ *     the GRU cell as stated for hns_gru_forward, one step, with x_t = f;   h_out[e, a] = h
+ *     y = LayerNorm(h + f) (eps 1e-5, biased variance)
+ *     the head on y: the actor's fc_mean, the sample or the mode and its log_prob; the critic's v_out.
+ * is_init is an ENV-level flag (uint8 [E], NULL: none) that holds for all of the env's agents (the reference's expand_right).  h_in: [E, A, 128]
+ * fp32 contiguous or NULL for zeros; h_out [E, A, 128].  h_out may be h_in (in place): a workgroup reads its rows' state before it writes
+ * them, and touches no other rows.  HNS_POLICY_DETERMINISTIC and HNS_POLICY_VALUE_ONLY as for hns_policy_forward; with value-only, action /
+ * log_prob / loc and actor_h_out are untouched and actor_h_in is not read.  Noise, seed and counter: hns_policy_forward's scheme, bump included.
+ * Summation order (NOT hns_gru_forward's: the two agree to fp32 rounding, not bit for bit): each gate pre-activation starts from its bias
+ * (b_ir + b_hr and b_iz + b_hz rounded once when the image is packed; b_in; b_hn), then takes the 128 products with f, then the 128 products
+ * with h, as v_mfma_f32_16x16x4_f32 steps of four k each, k ascending within a step's quarter (k = 4 s + kq); r = 1 / (1 + exp(-a_r)), likewise
+ * z; n = tanh(a_in + r a_hn); h' = (1 - z) n + z h without contraction; LayerNorm as the encoder's (two-pass, 1 / sqrt(var + eps)).
+ * Properties: no host synchronisation, no allocation, capturable; the same inputs give the same bits; a row's results do not depend on the
+ * other rows of the call.  Refused before any launch, in hns_policy_forward's order with, after the packed image / io / shape: a NULL or
+ * misaligned (16 bytes) rnn_packed, a NULL or misaligned (8 bytes) rio; and last: a missing or misaligned (16 bytes) critic_h_out (actor_h_out too unless
+ * value-only), a misaligned h_in.
+ *
+ * hns_policy_rnn_pack: ONE launch builds the GRUs' packed image (hns_policy_rnn_packed_bytes() bytes, 16-byte aligned; separate from
+ * hns_policy_pack's, which is unchanged) from the two networks' tensors: call it again after they change.
+ */
+typedef struct hns_policy_rnn_io {
+    const float *actor_h_in, *critic_h_in;     /* [E, A, 128] contiguous, 16-byte aligned, or NULL: zeros */
+    float *actor_h_out, *critic_h_out;         /* [E, A, 128]; may alias the matching h_in */
+    const uint8_t *is_init;                    /* [E] or NULL */
+} hns_policy_rnn_io;
+size_t hns_policy_rnn_packed_bytes(void);
+int hns_policy_rnn_pack(const hns_gru_net *actor_rnn, const hns_gru_net *critic_rnn, void *rnn_packed, void *stream);
+int hns_policy_forward_rnn(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                           const hns_policy_io *io, const hns_policy_rnn_io *rio, int32_t flags, uint64_t seed, uint64_t *counter, void *stream);
 /* The 2-norm of one flat fp32 gradient bucket: norm[0] = f32(sqrt(sum_i flat[i]^2)), in this order (tests/dp_reference.py restates it in numpy):
  * the bucket is cut into quads of four consecutive floats, the last one short by numel % 4 values that count as 0 (nothing past numel is
  * read); G = clamp(ceil(quads / 1024), 1, 64) workgroups of 256 threads, T = 256 G; thread t of the grid adds, for q = t, t + T, t + 2 T, ...,

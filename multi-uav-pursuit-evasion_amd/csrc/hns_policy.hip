@@ -22,6 +22,11 @@
 //                               embedding starts its fma chain from the bias (enc_token<true>; the updates add it last: DESIGN §7.3).
 //   hns_policy_act_kernel     : the same tile, LDS and launch bounds for ONE encoder pass, the actor's: action = loc and nothing else (evaluation
 //                               reads neither the value nor the log-probability).  Bit for bit the forward's deterministic action.
+//   hns_policy_forward_rnn_kernel : the recurrent configuration (actor.rnn / critic.rnn: a GRU behind each encoder) in the same tile,
+//                               LDS and launch bounds: per network the encoder, then ONE GRU step on the features it left in registers (six more
+//                               128 x 128 products from a second packed image, the gates in the products' accumulator layout), LayerNorm(h + f),
+//                               the head.  The state comes from and goes to HBM once per network; the features never do.
+//   hns_policy_rnn_pack_kernel: the two GRUs' tensors -> their packed image.
 //   hns_policy_bump_kernel    : the device call counter += 1 after a sampling call (Philox counter; a captured graph draws fresh noise per replay).
 // Determinism: fixed reduction orders (butterflies over the eight lanes of a row), no atomics.
 #include <hip/hip_runtime.h>
@@ -186,6 +191,48 @@ HNS_DEV float pol_head(const float *net, int o, const float (&y)[16], int g) {
     return row_sum8(s) + net[P_HB + o];
 }
 
+// the row's action (the caller's eps, Philox noise, or the mode), its log-probability and loc, written by the row's first lane
+HNS_DEV void pol_sample(const PolArgs &a, const float *net, const float (&loc)[4], long long row, bool live, int g) {
+    float eps[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!a.deterministic) {
+        if (a.eps) {
+            if (live) {
+#pragma unroll
+                for (int o = 0; o < 4; ++o) eps[o] = a.eps[row * 4 + o];
+            }
+        } else {
+            // Philox4x32-10: key = seed, counter = (call counter, row); Box-Muller on both pairs
+            const unsigned long long c = a.counter[0];
+            uint32_t u[4];
+            d_philox((uint32_t)a.seed, (uint32_t)(a.seed >> 32), (uint32_t)c, (uint32_t)(c >> 32), (uint32_t)row, (uint32_t)(row >> 32), u);
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const float u1 = (float)((u[2 * p] >> 8) + 1u) * 5.9604644775390625e-8f;   // (0, 1]
+                const float u2 = (float)(u[2 * p + 1] >> 8) * 5.9604644775390625e-8f;       // [0, 1)
+                const float rad = __builtin_sqrtf(-2.0f * logf(u1));
+                float sn, cs;
+                sincosf(6.283185307179586f * u2, &sn, &cs);
+                eps[2 * p] = rad * cs;
+                eps[2 * p + 1] = rad * sn;
+            }
+        }
+    }
+    if (live && g == 0) {
+        float lp = 0.0f;
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+            const float sc = net[P_SCALE + o];
+            const float act = a.deterministic ? loc[o] : loc[o] + sc * eps[o];
+            const float d = act - loc[o];
+            const float term = (-(d * d) / (2.0f * (sc * sc)) - net[P_LOGSCALE + o]) - 0.91893853320467274f;  // Normal.log_prob
+            lp = o == 0 ? term : lp + term;
+            a.action[row * 4 + o] = act;
+            if (a.loc) a.loc[row * 4 + o] = loc[o];
+        }
+        a.logp[row] = lp;
+    }
+}
+
 __global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_kernel(const PolArgs a) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
@@ -200,44 +247,7 @@ __global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_kernel(cons
         float loc[4];
 #pragma unroll
         for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
-        float eps[4] = {0.f, 0.f, 0.f, 0.f};
-        if (!a.deterministic) {
-            if (a.eps) {
-                if (live) {
-#pragma unroll
-                    for (int o = 0; o < 4; ++o) eps[o] = a.eps[row * 4 + o];
-                }
-            } else {
-                // Philox4x32-10: key = seed, counter = (call counter, row); Box-Muller on both pairs
-                const unsigned long long c = a.counter[0];
-                uint32_t u[4];
-                d_philox((uint32_t)a.seed, (uint32_t)(a.seed >> 32), (uint32_t)c, (uint32_t)(c >> 32), (uint32_t)row, (uint32_t)(row >> 32), u);
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    const float u1 = (float)((u[2 * p] >> 8) + 1u) * 5.9604644775390625e-8f;   // (0, 1]
-                    const float u2 = (float)(u[2 * p + 1] >> 8) * 5.9604644775390625e-8f;       // [0, 1)
-                    const float rad = __builtin_sqrtf(-2.0f * logf(u1));
-                    float sn, cs;
-                    sincosf(6.283185307179586f * u2, &sn, &cs);
-                    eps[2 * p] = rad * cs;
-                    eps[2 * p + 1] = rad * sn;
-                }
-            }
-        }
-        if (live && g == 0) {
-            float lp = 0.0f;
-#pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                const float sc = net[P_SCALE + o];
-                const float act = a.deterministic ? loc[o] : loc[o] + sc * eps[o];
-                const float d = act - loc[o];
-                const float term = (-(d * d) / (2.0f * (sc * sc)) - net[P_LOGSCALE + o]) - 0.91893853320467274f;  // Normal.log_prob
-                lp = o == 0 ? term : lp + term;
-                a.action[row * 4 + o] = act;
-                if (a.loc) a.loc[row * 4 + o] = loc[o];
-            }
-            a.logp[row] = lp;
-        }
+        pol_sample(a, net, loc, row, live, g);
         __syncthreads();                                          // the critic reuses the LDS
     }
     const float *net = a.img + a.net_floats;
@@ -262,6 +272,182 @@ __global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_kernel(const Po
 #pragma unroll
         for (int o = 0; o < 4; ++o) a.action[row * 4 + o] = loc[o];
     }
+}
+
+// ---- the recurrent configuration: one GRU step between the encoder and the head (include/hns.h: hns_policy_forward_rnn)
+// packed GRU image of one network, in floats: the six gate matrices in the encoder matrices' fragment order, then the vectors
+enum : int {
+    R_MAT = 0,                               // W_ir, W_iz, W_in, W_hr, W_hz, W_hn
+    R_BR = 6 * kEncMat,                      // b_ir + b_hr (one rounding, at pack time)
+    R_BZ = R_BR + kEncE,                     // b_iz + b_hz
+    R_BIN = R_BZ + kEncE, R_BHN = R_BIN + kEncE, R_LNW = R_BHN + kEncE, R_LNB = R_LNW + kEncE,
+    R_NET = R_LNB + kEncE,
+};
+
+struct GruSrc {
+    const float *w_ih, *w_hh, *b_ih, *b_hh, *ln_w, *ln_b;
+};
+
+HNS_DEV float pol_rnn_src(const GruSrc &s, int i) {
+    if (i < R_BR) {
+        const int m = i / kEncMat, x = i % kEncMat;
+        const int u = x & 3, lane = (x >> 2) & 63, s4 = (x >> 8) & 7, rb = x >> 11;         // enc_mat_src's fragment order
+        const int row = rb * 16 + (lane & 15), k = 4 * (4 * s4 + u) + (lane >> 4);
+        return (m < 3 ? s.w_ih : s.w_hh)[((m % 3) * kEncE + row) * kEncE + k];
+    }
+    const int sec = (i - R_BR) / kEncE, f = (i - R_BR) % kEncE;
+    switch (sec) {
+        case 0: return s.b_ih[f] + s.b_hh[f];
+        case 1: return s.b_ih[kEncE + f] + s.b_hh[kEncE + f];
+        case 2: return s.b_ih[2 * kEncE + f];
+        case 3: return s.b_hh[2 * kEncE + f];
+        case 4: return s.ln_w[f];
+        default: return s.ln_b[f];
+    }
+}
+
+__global__ __launch_bounds__(256) void hns_policy_rnn_pack_kernel(const GruSrc actor, const GruSrc critic, float *img) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < 2 * R_NET; i += gridDim.x * 256)
+        img[i] = i < R_NET ? pol_rnn_src(actor, i) : pol_rnn_src(critic, i - R_NET);
+}
+
+struct PolRnnArgs {
+    const float *img;                        // actor GRU image, the critic's at + R_NET
+    const float *h_in[2];                    // actor, critic: [rows, 128] or NULL (zeros)
+    float *h_out[2];
+    const unsigned char *is_init;            // [E] or NULL
+};
+
+HNS_DEV float pol_sigm(float z) { return 1.0f / (1.0f + expf(-z)); }
+
+// acc = the bias of the wave's output rows (row blocks 2 w, 2 w + 1; the lane's four features of each, both column blocks)
+HNS_DEV void pol_gate_start(const float *bias, int w, int kq, f32x4 (&acc)[2][2]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const f32x4 b = *reinterpret_cast<const f32x4 *>(bias + (2 * w + i) * 16 + 4 * kq);
+        acc[i][0] = b;
+        acc[i][1] = b;
+    }
+}
+
+// acc += W[128][128] IN[128][R]: enc_matvec's product (same operands, same k order) onto accumulators that stay in registers
+HNS_DEV void pol_gate_prod(const float *__restrict__ W, const float *in, int w, int lane, f32x4 (&acc)[2][2]) {
+    const int col = lane & 15, kq = lane >> 4;
+    const f32x4 *A0 = reinterpret_cast<const f32x4 *>(W) + (2 * w) * 8 * 64 + lane;
+    const f32x4 *A1 = A0 + 8 * 64;
+#pragma unroll
+    for (int s4 = 0; s4 < 8; ++s4) {
+        const f32x4 a0 = A0[s4 * 64], a1 = A1[s4 * 64];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = 4 * (4 * s4 + u) + kq;
+            const float b0 = in[k * kEncLd + col], b1 = in[k * kEncLd + 16 + col];
+            acc[0][0] = enc_mfma(a0[u], b0, acc[0][0]);
+            acc[0][1] = enc_mfma(a0[u], b1, acc[0][1]);
+            acc[1][0] = enc_mfma(a1[u], b0, acc[1][0]);
+            acc[1][1] = enc_mfma(a1[u], b1, acc[1][1]);
+        }
+    }
+}
+
+// one GRU step of the workgroup's rows on the features `y` the encoder left in registers: y <- LayerNorm(h' + y), h' -> h_out.  The gate
+// products run one after another onto one set of accumulators; the three gates of a (feature, row) pair land in the same lane, so the cell
+// runs in the accumulator layout and only h' crosses the LDS back to the eight-lanes-per-row layout.  Every read of h_in precedes the first
+// barrier and every write of h_out follows it, and a workgroup touches its own rows only: h_out may be h_in.
+HNS_DEV void pol_gru_step(const float *rn, const float *h_in, float *h_out, const unsigned char *is_init, int A, long long row0, long long rows,
+                          PolLds &L, int w, int lane, int r, int g, float (&y)[16]) {
+    float h[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) h[i] = 0.0f;
+    if (h_in && row0 + r < rows && !(is_init && is_init[(row0 + r) / A])) {          // the env's flag holds for all of its agents
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(h_in + (row0 + r) * kEncE + enc_feat(g, i, 0));
+#pragma unroll
+            for (int u = 0; u < 4; ++u) h[4 * i + u] = v[u];
+        }
+    }
+    enc_lds_store(L.x0, r, g, y);                                 // (the encoder's last reads were of t2)
+    enc_lds_store(L.t1, r, g, h);
+    __syncthreads();
+    const int col = lane & 15, kq = lane >> 4;
+    f32x4 acc[2][2], n[2][2];
+    pol_gate_start(rn + R_BR, w, kq, acc);                        // r = sigmoid(b_r + W_ir f + W_hr h)
+    pol_gate_prod(rn + R_MAT + 0 * kEncMat, L.x0, w, lane, acc);
+    pol_gate_prod(rn + R_MAT + 3 * kEncMat, L.t1, w, lane, acc);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) n[i][c][q] = pol_sigm(acc[i][c][q]);
+    pol_gate_start(rn + R_BHN, w, kq, acc);                       // r (b_hn + W_hn h)
+    pol_gate_prod(rn + R_MAT + 5 * kEncMat, L.t1, w, lane, acc);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) n[i][c][q] = n[i][c][q] * acc[i][c][q];
+    pol_gate_start(rn + R_BIN, w, kq, acc);                       // n = tanh(b_in + W_in f + r (...))
+    pol_gate_prod(rn + R_MAT + 2 * kEncMat, L.x0, w, lane, acc);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) n[i][c][q] = tanhf(acc[i][c][q] + n[i][c][q]);
+    pol_gate_start(rn + R_BZ, w, kq, acc);                        // z = sigmoid(b_z + W_iz f + W_hz h)
+    pol_gate_prod(rn + R_MAT + 1 * kEncMat, L.x0, w, lane, acc);
+    pol_gate_prod(rn + R_MAT + 4 * kEncMat, L.t1, w, lane, acc);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int f0 = (2 * w + i) * 16 + 4 * kq;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int rr = c * 16 + col;
+            f32x4 o;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float z = pol_sigm(acc[i][c][q]);
+                o[q] = (1.0f - z) * n[i][c][q] + z * L.t1[(f0 + q) * kEncLd + rr];       // h' = (1 - z) n + z h
+                L.t2[(f0 + q) * kEncLd + rr] = o[q];
+            }
+            if (row0 + rr < rows) *reinterpret_cast<f32x4 *>(h_out + (row0 + rr) * kEncE + f0) = o;
+        }
+    }
+    __syncthreads();
+    float u[16], xh[16];
+    enc_lds_load(L.t2, r, g, h);
+    enc_lds_load(L.x0, r, g, u);                                  // f again: not held in registers across the products
+#pragma unroll
+    for (int i = 0; i < 16; ++i) u[i] = h[i] + u[i];
+    enc_layernorm(u, rn + R_LNW, rn + R_LNB, g, xh, y);           // y = LayerNorm(h' + f)
+}
+
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_rnn_kernel(const PolArgs a, const PolRnnArgs ra) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
+    const long long row0 = (long long)blockIdx.x * kEncRows, row = row0 + r;
+    const bool live = row < a.rows;
+    float y[16];
+
+    if (!a.value_only) {
+        const float *net = a.img;
+        pol_encoder(a, net, L, w, lane, r, g, row, y);
+        pol_gru_step(ra.img, ra.h_in[0], ra.h_out[0], ra.is_init, a.A, row0, a.rows, L, w, lane, r, g, y);
+        float loc[4];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
+        pol_sample(a, net, loc, row, live, g);
+        __syncthreads();                                          // the critic reuses the LDS
+    }
+    const float *net = a.img + a.net_floats;
+    pol_encoder(a, net, L, w, lane, r, g, row, y);
+    pol_gru_step(ra.img + R_NET, ra.h_in[1], ra.h_out[1], ra.is_init, a.A, row0, a.rows, L, w, lane, r, g, y);
+    const float v = pol_head(net, 0, y, g);
+    if (live && g == 0) a.value[row] = v;
 }
 
 __global__ void hns_policy_bump_kernel(unsigned long long *counter) { counter[0] += 1ull; }
@@ -309,6 +495,18 @@ int pol_check_obs(const char *fn, int32_t num_agents, const hns_policy_io *io) {
     return HNS_OK;
 }
 
+// the forward's outputs, noise and counter (hns_policy_forward, hns_policy_forward_rnn)
+int pol_check_outputs(const char *fn, const hns_policy_io *io, bool value_only, bool det, const uint64_t *counter) {
+    if (!io->value || !hns_aligned(io->value, 4)) return hns_fail(fn, "value output missing or misaligned");
+    if (!value_only) {
+        if (!io->action || !io->log_prob || !hns_aligned(io->action, 4) || !hns_aligned(io->log_prob, 4) || (io->loc && !hns_aligned(io->loc, 4)))
+            return hns_fail(fn, "action / log_prob outputs missing or misaligned");
+        if (!det && !io->eps && (!counter || !hns_aligned(counter, 8))) return hns_fail(fn, "sampling without eps needs the device call counter");
+        if (io->eps && !hns_aligned(io->eps, 4)) return hns_fail(fn, "misaligned eps");
+    }
+    return HNS_OK;
+}
+
 // the image, the observation and the shape; `action` the only output (the forward adds its own)
 hns::PolArgs pol_args(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io) {
     hns::PolArgs a{};
@@ -321,6 +519,15 @@ hns::PolArgs pol_args(const void *packed, int32_t self_dim, int64_t num_envs, in
     a.action = io->action;
     a.rows = num_envs * num_agents; a.A = num_agents; a.K = num_cylinders; a.D = self_dim;
     return a;
+}
+
+int pol_gru_net(const char *fn, const hns_gru_net *n, hns::GruSrc &s) {
+    if (!n) return hns_fail(fn, "null GRU network");
+    const float *p[6] = {n->weight_ih, n->weight_hh, n->bias_ih, n->bias_hh, n->ln_w, n->ln_b};
+    for (const float *q : p)
+        if (!q || !hns_aligned(q, 4)) return hns_fail(fn, "every GRU parameter pointer must be a non-NULL fp32 array");
+    s = hns::GruSrc{n->weight_ih, n->weight_hh, n->bias_ih, n->bias_hh, n->ln_w, n->ln_b};
+    return HNS_OK;
 }
 
 }  // namespace
@@ -357,13 +564,8 @@ int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, i
     const bool value_only = flags & HNS_POLICY_VALUE_ONLY, det = flags & HNS_POLICY_DETERMINISTIC;
     rc = pol_check_obs(fn, num_agents, io);
     if (rc != HNS_OK) return rc;
-    if (!io->value || !hns_aligned(io->value, 4)) return hns_fail(fn, "value output missing or misaligned");
-    if (!value_only) {
-        if (!io->action || !io->log_prob || !hns_aligned(io->action, 4) || !hns_aligned(io->log_prob, 4) || (io->loc && !hns_aligned(io->loc, 4)))
-            return hns_fail(fn, "action / log_prob outputs missing or misaligned");
-        if (!det && !io->eps && (!counter || !hns_aligned(counter, 8))) return hns_fail(fn, "sampling without eps needs the device call counter");
-        if (io->eps && !hns_aligned(io->eps, 4)) return hns_fail(fn, "misaligned eps");
-    }
+    rc = pol_check_outputs(fn, io, value_only, det, counter);
+    if (rc != HNS_OK) return rc;
     hns::PolArgs a = pol_args(packed, self_dim, num_envs, num_agents, num_cylinders, io);
     a.eps = io->eps; a.counter = reinterpret_cast<const unsigned long long *>(counter); a.seed = seed;
     a.loc = io->loc; a.logp = io->log_prob; a.value = io->value;
@@ -374,6 +576,59 @@ int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, i
     HNS_CHECK_HIP(attr);
     const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
     hipLaunchKernelGGL(hns::hns_policy_forward_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), st, a);
+    HNS_CHECK_HIP(hipGetLastError());
+    if (!value_only && !det && !io->eps) {
+        hipLaunchKernelGGL(hns::hns_policy_bump_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<unsigned long long *>(counter));
+        HNS_CHECK_HIP(hipGetLastError());
+    }
+    return HNS_OK;
+}
+
+size_t hns_policy_rnn_packed_bytes(void) { return (size_t)(2 * hns::R_NET) * sizeof(float); }
+
+int hns_policy_rnn_pack(const hns_gru_net *actor_rnn, const hns_gru_net *critic_rnn, void *rnn_packed, void *stream) {
+    const char *fn = "hns_policy_rnn_pack";
+    if (!rnn_packed || !hns_aligned(rnn_packed, 16)) return hns_fail(fn, "packed image must be a 16-byte aligned device array");
+    hns::GruSrc sa{}, sc{};
+    int rc = pol_gru_net(fn, actor_rnn, sa);
+    if (rc != HNS_OK) return rc;
+    rc = pol_gru_net(fn, critic_rnn, sc);
+    if (rc != HNS_OK) return rc;
+    hipLaunchKernelGGL(hns::hns_policy_rnn_pack_kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream), sa, sc, static_cast<float *>(rnn_packed));
+    HNS_CHECK_HIP(hipGetLastError());
+    return HNS_OK;
+}
+
+int hns_policy_forward_rnn(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                           const hns_policy_io *io, const hns_policy_rnn_io *rio, int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
+    const char *fn = "hns_policy_forward_rnn";
+    int rc = pol_check_shape(fn, packed, self_dim, num_envs, num_agents, num_cylinders, io);
+    if (rc != HNS_OK) return rc;
+    if (!rnn_packed || !rio || !hns_aligned(rnn_packed, 16) || !hns_aligned(rio, 8)) return hns_fail(fn, "null or misaligned packed GRU image / rnn io");
+    if (flags & ~(HNS_POLICY_DETERMINISTIC | HNS_POLICY_VALUE_ONLY)) return hns_fail(fn, "unknown flag");
+    const bool value_only = flags & HNS_POLICY_VALUE_ONLY, det = flags & HNS_POLICY_DETERMINISTIC;
+    rc = pol_check_obs(fn, num_agents, io);
+    if (rc != HNS_OK) return rc;
+    rc = pol_check_outputs(fn, io, value_only, det, counter);
+    if (rc != HNS_OK) return rc;
+    if (!rio->critic_h_out || !hns_aligned(rio->critic_h_out, 16) || (!value_only && (!rio->actor_h_out || !hns_aligned(rio->actor_h_out, 16))))
+        return hns_fail(fn, "state output missing or not 16-byte aligned");
+    if (!hns_aligned(rio->critic_h_in, 16) || (!value_only && !hns_aligned(rio->actor_h_in, 16))) return hns_fail(fn, "state input not 16-byte aligned");
+    hns::PolArgs a = pol_args(packed, self_dim, num_envs, num_agents, num_cylinders, io);
+    a.eps = io->eps; a.counter = reinterpret_cast<const unsigned long long *>(counter); a.seed = seed;
+    a.loc = io->loc; a.logp = io->log_prob; a.value = io->value;
+    a.deterministic = det; a.value_only = value_only;
+    hns::PolRnnArgs ra{};
+    ra.img = static_cast<const float *>(rnn_packed);
+    ra.h_in[0] = value_only ? nullptr : rio->actor_h_in; ra.h_in[1] = rio->critic_h_in;
+    ra.h_out[0] = value_only ? nullptr : rio->actor_h_out; ra.h_out[1] = rio->critic_h_out;
+    ra.is_init = rio->is_init;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_forward_rnn_kernel),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
+    HNS_CHECK_HIP(attr);
+    const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
+    hipLaunchKernelGGL(hns::hns_policy_forward_rnn_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), st, a, ra);
     HNS_CHECK_HIP(hipGetLastError());
     if (!value_only && !det && !io->eps) {
         hipLaunchKernelGGL(hns::hns_policy_bump_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<unsigned long long *>(counter));

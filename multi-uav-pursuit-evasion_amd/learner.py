@@ -101,6 +101,9 @@ class DeviceLearner:
 
     def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, agent_name="drone", generator=None, device_policy=None, group=None):
         check_learner_config(cfg)
+        if getattr(device_policy, "recurrent", False):
+            raise P.PolicyConfigError("DeviceLearner updates the non-recurrent networks only: a recurrent policy (actor.rnn / critic.rnn) is trained "
+                                      "in torch over encoder.encode -> rnn.gru -> head (examples/recurrent_policy.py)")
         get = PT.getter(cfg)
         self.cfg, self.agent_name, self.generator = cfg, agent_name, generator
         self.actor, self.critic, self.tp_net, self.value_normalizer = actor, critic, tp_net, value_normalizer

@@ -13,7 +13,11 @@ checkpoint written by scripts/train.py (`MAPPOPolicy.state_dict()`: "actor_param
 TensorDictModule's `module.` prefix.  The packed operand image is rebuilt on the device when a parameter's data_ptr or version counter moves,
 so the next call follows an optimiser step (as env.HideAndSeek._tp_sync_weights does for the predictor).
 
-CPU tensors run a torch restatement of the reference's statements (tests, gloo runs — not the hot path).  DESIGN.md §7.3."""
+CPU tensors run a torch restatement of the reference's statements (tests, gloo runs — not the hot path).  DESIGN.md §7.3.
+
+`RecurrentDevicePolicy` is the `actor.rnn` / `critic.rnn` configuration (a GRU behind each encoder, modules/rnn.py): encoder -> one GRU step ->
+head for both networks in ONE call of `hns_policy_forward_rnn`, the two states carried on the device.  `DevicePolicy` keeps
+refusing that configuration."""
 import collections
 import ctypes as C
 import math
@@ -43,6 +47,7 @@ ACTOR_NAMES = {**{"encoder." + k: v for k, v in _ENCODER.items()},
 CRITIC_NAMES = {**{"base." + k: v for k, v in _ENCODER.items()}, "v_out.weight": "head_w", "v_out.bias": "head_b"}
 
 PolicyOutput = collections.namedtuple("PolicyOutput", ["action", "log_prob", "value", "loc"])
+RecurrentPolicyOutput = collections.namedtuple("RecurrentPolicyOutput", ["action", "log_prob", "value", "loc", "actor_state", "critic_state"])
 
 
 class PolicyConfigError(ValueError):
@@ -169,16 +174,7 @@ def torch_forward(actor, critic, xs, xo, xc, eps=None, deterministic=False, valu
     value = F.linear(_encoder(critic, xs, xo, xc), critic["head_w"], critic["head_b"])
     if value_only:
         return PolicyOutput(None, None, value, None)
-    loc = F.linear(_encoder(actor, xs, xo, xc), actor["head_w"], actor["head_b"])
-    scale = torch.broadcast_to(torch.exp(actor["log_std"]), loc.shape)
-    if deterministic:
-        action = loc
-    else:
-        if eps is None:
-            eps = torch.randn(loc.shape, dtype=loc.dtype, device=loc.device, generator=generator)
-        action = loc + scale * eps
-    log_prob = torch.distributions.Normal(loc, scale).log_prob(action).sum(-1, keepdim=True)
-    return PolicyOutput(action, log_prob, value, loc)
+    return PolicyOutput(*_heads(actor, _encoder(actor, xs, xo, xc), value, eps, deterministic, generator))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -372,6 +368,234 @@ class DevicePolicy:
     def value(self, tensordict):
         """value_op: the critic's state_value [E, A, 1] (train_op's next_value)."""
         return self.forward(*self._obs(tensordict), value_only=True).value
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the recurrent configuration (actor.rnn / critic.rnn): Actor.forward / Critic.forward with self.rnn set (mappo.py:603-660)
+def _heads(actor, y_actor, value, eps, deterministic, generator):
+    """(action, log_prob, value, loc) of the DiagGaussian head on the actor's features."""
+    loc = F.linear(y_actor, actor["head_w"], actor["head_b"])
+    scale = torch.broadcast_to(torch.exp(actor["log_std"]), loc.shape)
+    if deterministic:
+        action = loc
+    else:
+        if eps is None:
+            eps = torch.randn(loc.shape, dtype=loc.dtype, device=loc.device, generator=generator)
+        action = loc + scale * eps
+    log_prob = torch.distributions.Normal(loc, scale).log_prob(action).sum(-1, keepdim=True)
+    return action, log_prob, value, loc
+
+
+def _rnn_step(p, rnn_p, xs, xo, xc, state, is_init):
+    """One network's (LayerNorm(h' + f) [E, A, 128], h' [E, A, 128]): `_encoder`, then rnn.restatement over one step."""
+    from . import rnn as _rnn
+    f = _encoder(p, xs, xo, xc)
+    E, A, _ = f.shape
+    h0 = state.reshape(E * A, EMBED_DIM).to(f.dtype) if state is not None else f.new_zeros(E * A, EMBED_DIM)
+    if is_init is None:
+        m = f.new_zeros(E * A, 1)
+    else:
+        m = (is_init.reshape(E, 1) != 0).expand(E, A).reshape(E * A, 1).to(f.dtype)          # the env's flag for all of its agents
+    out, h = _rnn.restatement(rnn_p, f.reshape(E * A, 1, EMBED_DIM), h0, m)
+    return out.reshape(E, A, EMBED_DIM), h.reshape(E, A, EMBED_DIM)
+
+
+def torch_forward_rnn(actor, critic, actor_rnn, critic_rnn, xs, xo, xc, actor_state=None, critic_state=None, is_init=None, eps=None,
+                      deterministic=False, value_only=False, generator=None):
+    """The CPU restatement of hns_policy_forward_rnn, any dtype: parameter dicts in hns_policy_net / hns_gru_net field names, xs [E, A, 1, D],
+    states [E, A, 128] or None (zeros), is_init [E] (or [E, 1]) or None -> RecurrentPolicyOutput."""
+    yc, hc = _rnn_step(critic, critic_rnn, xs, xo, xc, critic_state, is_init)
+    value = F.linear(yc, critic["head_w"], critic["head_b"])
+    if value_only:
+        return RecurrentPolicyOutput(None, None, value, None, None, hc)
+    ya, ha = _rnn_step(actor, actor_rnn, xs, xo, xc, actor_state, is_init)
+    return RecurrentPolicyOutput(*_heads(actor, ya, value, eps, deterministic, generator), ha, hc)
+
+
+def split_rnn(params, what):
+    """(the network's parameters without its GRU, the GRU's six tensors by hns_gru_net field) from reference names: the GRU sits under
+    `rnn.` (rnn.cell.weight_ih, ..., rnn.layer_norm.bias)."""
+    from . import rnn as _rnn
+    flat = {_strip(k): v for k, v in _flatten(params).items()}
+    rest = {k: v for k, v in flat.items() if not k.startswith("rnn.")}
+    found = {k[len("rnn."):]: v for k, v in flat.items() if k.startswith("rnn.")}
+    unknown = sorted(k for k in found if k not in _rnn.NAMES)
+    if unknown:
+        raise PolicyConfigError(f"{what}: rnn parameters the GRU block does not have: {unknown[:6]}")
+    missing = sorted(k for k in _rnn.NAMES if k not in found)
+    if missing:
+        raise PolicyConfigError(f"{what}: no GRU under 'rnn.' (missing {['rnn.' + k for k in missing]}); a network without an rnn is "
+                                "DevicePolicy's")
+    try:
+        gru = _rnn.gru_parameters({_rnn.NAMES[k]: (v if v.is_contiguous() else v.detach().contiguous()) for k, v in found.items()})
+    except ValueError as e:
+        raise PolicyConfigError(f"{what}: the rnn must be GRUCell(128, 128) + LayerNorm(128): {e}") from None
+    return rest, gru
+
+
+class RecurrentDevicePolicy(DevicePolicy):
+    """MAPPOPolicy with actor.rnn / critic.rnn (a GRU(128, 128) behind each encoder) in one HIP launch per call: encoder -> GRU step -> head
+    for both networks, the states read and written on the device.  Built from the same sources as DevicePolicy; the GRU tensors are the
+    `rnn.*` entries of the actor's and the critic's parameters.  `forward` takes and returns the two states ([E, A, 128]; None: zeros) and
+    an env-level `is_init` ([E] or [E, 1]; None: no env starts an episode); `out_states` may be the input tensors (in place)."""
+    recurrent = True
+
+    def __init__(self, actor_params, critic, cfg=None, device=None, seed=0, agent_name="drone"):
+        check_config(_without_rnn(cfg))
+        actor_rest, self.actor_rnn = split_rnn(actor_params, "actor")
+        critic_rest, self.critic_rnn = split_rnn(critic, "critic")
+        super().__init__(actor_rest, critic_rest, cfg=None, device=device, seed=seed, agent_name=agent_name)
+        if {v.device for v in (*self.actor_rnn.values(), *self.critic_rnn.values())} != {self.device}:
+            self.actor_rnn = {k: v.detach().to(self.device).contiguous() for k, v in self.actor_rnn.items()}
+            self.critic_rnn = {k: v.detach().to(self.device).contiguous() for k, v in self.critic_rnn.items()}
+        if self.device.type == "cuda":
+            self.rnn_packed = torch.empty(self._lib.hns_policy_rnn_packed_bytes(), dtype=torch.uint8, device=self.device)
+
+    def _tensors(self):
+        return [*super()._tensors(), *self.actor_rnn.values(), *self.critic_rnn.values()]
+
+    def _gru_net(self, p):
+        n = abi.HnsGruNet()
+        for f, t in p.items():
+            setattr(n, f, t.data_ptr())
+        return n
+
+    def refresh(self, force=False):
+        """Re-pack both images if a parameter's storage or version counter moved (or `force`)."""
+        stamp = tuple((t.data_ptr(), t._version) for t in self._tensors())
+        if not force and stamp == self._stamp:
+            return
+        super().refresh(force=True)
+        a, c = self._gru_net(self.actor_rnn), self._gru_net(self.critic_rnn)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            rc = self._lib.hns_policy_rnn_pack(C.byref(a), C.byref(c), self.rnn_packed.data_ptr(), st)
+        self._check(rc, "hns_policy_rnn_pack")
+        self._stamp = stamp
+
+    def act(self, *args, **kwargs):
+        raise PolicyConfigError("a recurrent policy has no actor-only pass; use forward(..., deterministic=True)")
+
+    def _state(self, t, name, E, A):
+        if t is None:
+            return None
+        if (not torch.is_tensor(t) or tuple(t.shape) != (E, A, EMBED_DIM) or t.dtype != torch.float32 or t.device != self.device
+                or not t.is_contiguous() or (t.is_cuda and t.data_ptr() % 16)):
+            raise ValueError(f"{name} must be a contiguous, 16-byte aligned float32 [{E}, {A}, {EMBED_DIM}] tensor on {self.device}")
+        return t
+
+    def forward(self, obs_self, obs_others, obs_cylinders, actor_state=None, critic_state=None, is_init=None, eps=None, deterministic=False,
+                value_only=False, out_states=None):
+        """RecurrentPolicyOutput(action [E, A, 4], log_prob [E, A, 1], value [E, A, 1], loc [E, A, 4], actor_state, critic_state [E, A, 128]):
+        the states AFTER the step.  value_only: only value and critic_state are set, the actor's state is neither read nor written.
+        out_states: (actor, critic) tensors the new states are written into (either may be None: a fresh tensor)."""
+        xs, xo, xc = self._validate(obs_self, obs_others, obs_cylinders)
+        E, A, D = xs.shape
+        if eps is not None and (tuple(eps.shape) != (E, A, ACTION_DIM) or eps.dtype != torch.float32 or eps.device != self.device):
+            raise ValueError(f"eps must be float32 [{E}, {A}, {ACTION_DIM}] on {self.device}")
+        ha, hc = self._state(actor_state, "actor_state", E, A), self._state(critic_state, "critic_state", E, A)
+        oa, oc = out_states if out_states is not None else (None, None)
+        oa, oc = self._state(oa, "out_states[0]", E, A), self._state(oc, "out_states[1]", E, A)
+        if is_init is not None:
+            if not torch.is_tensor(is_init) or is_init.numel() != E or is_init.device != self.device:
+                raise ValueError(f"is_init must hold one flag per env ([{E}] or [{E}, 1]) on {self.device}")
+            is_init = is_init.reshape(E).contiguous()            # (a time slice of a stored [N, T, 1] tensor is strided)
+            is_init = is_init.view(torch.uint8) if is_init.dtype == torch.bool else (is_init != 0).view(torch.uint8)
+        if self.device.type != "cuda":
+            # contiguous observations: torch's CPU matrix products round differently for strided operands, and a stored rollout re-run from
+            # views of its storage must give the bits the collection gave
+            xs, xc, xo = xs.contiguous(), xc.contiguous(), (xo.contiguous() if xo is not None else None)
+            with torch.no_grad():
+                out = torch_forward_rnn(self.actor_p, self.critic_p, self.actor_rnn, self.critic_rnn, xs.unsqueeze(2), xo, xc, ha, hc, is_init, eps,
+                                        deterministic, value_only, self._generator)
+            new_a = out.actor_state if oa is None or value_only else oa.copy_(out.actor_state)
+            new_c = out.critic_state if oc is None else oc.copy_(out.critic_state)
+            return out._replace(actor_state=new_a, critic_state=new_c)
+        self.refresh()
+        xs, xo, xc, io = self._io(xs, xo, xc)
+        eps = eps.contiguous() if eps is not None else None
+        dev = self.device
+        value = torch.empty(E, A, 1, device=dev)
+        action = log_prob = loc = None
+        oc = oc if oc is not None else torch.empty(E, A, EMBED_DIM, device=dev)
+        if value_only:
+            oa = None
+        else:
+            action, log_prob, loc = torch.empty(E, A, ACTION_DIM, device=dev), torch.empty(E, A, 1, device=dev), torch.empty(E, A, ACTION_DIM, device=dev)
+            oa = oa if oa is not None else torch.empty(E, A, EMBED_DIM, device=dev)
+            io.action, io.log_prob, io.loc = action.data_ptr(), log_prob.data_ptr(), loc.data_ptr()
+        io.eps = eps.data_ptr() if eps is not None else None
+        io.value = value.data_ptr()
+        rio = abi.HnsPolicyRnnIo()
+        rio.actor_h_in = ha.data_ptr() if ha is not None and not value_only else None
+        rio.critic_h_in = hc.data_ptr() if hc is not None else None
+        rio.actor_h_out = oa.data_ptr() if oa is not None else None
+        rio.critic_h_out = oc.data_ptr()
+        rio.is_init = is_init.data_ptr() if is_init is not None else None
+        flags = (abi.HNS_POLICY_DETERMINISTIC if deterministic else 0) | (abi.HNS_POLICY_VALUE_ONLY if value_only else 0)
+        with torch.cuda.device(dev):
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            rc = self._lib.hns_policy_forward_rnn(self.packed.data_ptr(), self.rnn_packed.data_ptr(), self.self_dim, E, A, xc.shape[2], C.byref(io),
+                                                  C.byref(rio), flags, self.seed, self.counter.data_ptr(), st)
+        self._check(rc, "hns_policy_forward_rnn")
+        return RecurrentPolicyOutput(action, log_prob, value, loc, oa, oc)
+
+    def _keys(self):
+        return f"{self.agent_name}.actor_rnn_state", f"{self.agent_name}.critic_rnn_state"
+
+    def __call__(self, tensordict, deterministic=False):
+        """MAPPOPolicy.__call__ with rnn heads: reads "<agent>.actor_rnn_state", "<agent>.critic_rnn_state" (absent: zeros) and "is_init"
+        (absent: none), writes the action, its log-prob, the value and — as the reference does — the states AFTER the step under the two
+        state keys."""
+        ka, kc = self._keys()
+        out = self.forward(*self._obs(tensordict), actor_state=_td_get(tensordict, ka), critic_state=_td_get(tensordict, kc),
+                           is_init=_td_get(tensordict, "is_init"), deterministic=deterministic)
+        tensordict[("agents", "action")] = out.action
+        tensordict[f"{self.agent_name}.action_logp"] = out.log_prob
+        tensordict["state_value"] = out.value
+        tensordict[ka], tensordict[kc] = out.actor_state, out.critic_state
+        return tensordict
+
+    def value(self, tensordict):
+        """value_op: the critic's state_value [E, A, 1] from the tensordict's observation, critic state and is_init; nothing is written back."""
+        return self.forward(*self._obs(tensordict), critic_state=_td_get(tensordict, self._keys()[1]), is_init=_td_get(tensordict, "is_init"),
+                            value_only=True).value
+
+
+def _td_get(td, key):
+    try:
+        return td.get(key, None) if hasattr(td, "get") else td[key]
+    except KeyError:
+        return None
+
+
+def _without_rnn(cfg):
+    """The algo cfg with actor.rnn / critic.rnn taken out (what check_config refuses for DevicePolicy and this class implements)."""
+    if cfg is None:
+        return None
+    get = cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
+    out = {k: get(k) for k in ("share_actor", "critic_input") if get(k, None) is not None}
+    for part in ("actor", "critic"):
+        sub = get(part, None)
+        if sub is not None:
+            sget = sub.get if hasattr(sub, "get") else (lambda k, d=None, s=sub: getattr(s, k, d))
+            out[part] = {"tanh": sget("tanh", False)}
+    return out
+
+
+def random_rnn_parameters(seed=0):
+    """A randomly initialised GRU block under the reference's names with the `rnn.` prefix (orthogonal weights, nn.GRUCell's uniform biases,
+    LayerNorm at 1 / 0): merge it into one network's dict of `random_parameters`."""
+    g = torch.Generator().manual_seed(seed)
+    E = EMBED_DIM
+    p = {}
+    for n in ("weight_ih", "weight_hh"):
+        p[f"rnn.cell.{n}"] = torch.cat([torch.linalg.qr(torch.randn(E, E, generator=g))[0] for _ in range(3)]).contiguous()
+    bound = 1.0 / math.sqrt(E)
+    for n in ("bias_ih", "bias_hh"):
+        p[f"rnn.cell.{n}"] = (torch.rand(3 * E, generator=g) * 2 - 1) * bound
+    p["rnn.layer_norm.weight"], p["rnn.layer_norm.bias"] = torch.ones(E), torch.zeros(E)
+    return p
 
 
 def random_parameters(self_dim, num_agents, seed=0):
