@@ -3,7 +3,11 @@ names, the CPU node's semantics and every Python refusal.  The device kernels: t
 
 Gradient gate (the project's rule, BAR = 8): for each gradient of (out dy).sum() + (h_last dh).sum() — six parameter tensors, dx, dh0 —
 e_cpu <= 8 max(e_32, 2^-24 max|g_64|), errors as max-abs against fp64 autograd of tests/gru_reference.py, e_32 the error of the same
-statements in fp32."""
+statements in fp32; per PARTITION (gru_reference.gate: the r, z, n thirds of the 384-row tensors, out and dx per step), the bound from the
+partition's own e_32 and max|g_64|.
+
+Teeth (the last section): gru_reference.emulate_kernel, an fp32 restatement of the KERNELS' algorithm, passes that gate on every case the
+device gate runs, and each of nine seeded defects taken from the kernels' own structure fails it on a named case (DEFECT_TABLE)."""
 import ctypes
 import os
 
@@ -105,11 +109,9 @@ def test_cpu_gradients_pass_the_fp64_gate(shape):
     out, h = RN.gru(leaves, xl, hl, flags)
     ((out * dy).sum() + (h * dh).sum()).backward()
     got = {**{f: t.grad for f, t in leaves.items()}, "dx": xl.grad, "dh0": hl.grad}
-    for name in GR.GRADS:
-        assert np.abs(r64[name]).max() > 0, name
-        ok, e, bound = GR.gate(name, got[name].double().numpy(), r64[name], r32[name])
-        print(f"  S{S} L{L} {name}: e_cpu {e:.3e} bound {bound:.3e} ratio {e / bound:.2f}")
-        assert ok, (name, e, bound)
+    worst, whole, bad = GR.gate(f"S{S}L{L} cpu", [(name, got[name].double().numpy(), r64[name], r32[name]) for name in GR.GRADS])
+    print(f"  S{S} L{L}: worst partition ratio {worst:.2f}, worst whole-tensor ratio {whole:.2f}")
+    assert not bad, bad
     # the parameter gradients are views of ONE allocation
     g6 = torch.autograd.grad((RN.gru(leaves, x, h0, flags)[0] * dy).sum(), list(leaves.values()))
     assert len({g.untyped_storage().data_ptr() for g in g6}) == 1
@@ -239,3 +241,90 @@ def test_refusals():
         RN.gru({**p, "weight_ho": p["ln_w"]}, x, h0, flags)
     with pytest.raises(TypeError, match="must map"):
         RN.gru(list(p.values()), x, h0, flags)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Does the fp64 gate have teeth?  emulate_kernel is an fp32 restatement of the kernels' algorithm; the cases are the ones the GPU gate runs
+# (test_hip_gru.py: CASES, the five flag patterns, and (4097, 3) — a second trip of the persistent loops, tps = 2, a ragged last split).
+BIG = (4097, 3)
+GATE_CASES = [f"S{S}L{L}" for S, L in GR.CASES] + ["flags-" + q for q in GR.FLAG_PATTERNS] + ["S%dL%d" % BIG]
+
+
+def _items(res, r64, r32):
+    (o, h, g), (o64, h64, g64), (o32, h32, g32) = res, r64, r32
+    return [("out", o, o64, o32), ("h_last", h, h64, h32)] + [(n, g[n], g64[n], g32[n]) for n in GR.GRADS]
+
+
+@pytest.fixture(scope="module")
+def gate_cases():
+    """tag -> (case, names that are identically zero, fp64 reference, fp32 reference) of every case of the GPU gate."""
+    cases = {f"S{S}L{L}": (GR.shape_case(S, L), ()) for S, L in GR.CASES}
+    cases.update({"flags-" + q: (GR.flag_case(q), GR.FLAG_ZERO.get(q, ())) for q in GR.FLAG_PATTERNS})
+    cases["S%dL%d" % BIG] = (GR.shape_case(*BIG), ())
+    assert list(cases) == GATE_CASES
+    return {k: (c, zero, GR.run(*c, torch.float64), GR.run(*c, torch.float32)) for k, (c, zero) in cases.items()}
+
+
+def test_the_big_case_reaches_the_branches_the_defects_sit_in():
+    pl = GR.plan(*BIG)
+    assert pl["tiles"] == GR.MAX_GROUPS + 1 and pl["groups"] == GR.MAX_GROUPS           # workgroup 0 takes a second tile
+    assert pl["tps"] == 2 and pl["splits"] * pl["tps"] - pl["wg_tiles"] == 1            # a ragged last split: one tile of two
+    assert pl["rows"] - (pl["wg_tiles"] - 1) * GR.WG_ROWS == 3                          # ... with three live rows
+    assert all(GR.plan(S, L)["tps"] == 1 and GR.plan(S, L)["tiles"] <= GR.MAX_GROUPS for S, L in GR.CASES + [(18, 4)])
+
+
+def test_the_kernels_algorithm_in_fp32_passes_the_partition_gate_on_every_case(gate_cases):
+    """No defect: the emulation stays under the bar in every partition of every tensor, and is exactly zero where the reference is
+    identically zero.  Measured worst ratio: 2.75 per partition (S3L64, dx at one step), 2.42 per whole tensor (S1L16)."""
+    worst = whole = 0.0
+    for tag, (case, zero, r64, r32) in gate_cases.items():
+        w, ww, bad = GR.gate(tag, _items(GR.emulate_kernel(*case), r64, r32), zero=zero, verbose=False)
+        print(f"  {tag}: worst partition ratio {w:.2f}, worst whole-tensor ratio {ww:.2f}")
+        assert not bad, (tag, bad)
+        worst, whole = max(worst, w), max(whole, ww)
+    print(f"  emulate_kernel, no defect: worst ratio {worst:.2f} per partition, {whole:.2f} per whole tensor, of {GR.BAR}")
+
+
+# defect -> the case that must fail the gate with it, and the tensor it fails on.  Measured ratios on the named case and tensor (bar 8), whole
+# tensor / worst partition, and the cases that still pass:
+#   mask_after_cell              flags-mixed out 1.4e6 / 1.5e6; passes flags-none (nothing to mask)
+#   dh_unmasked                  flags-first dh0 inf / inf (an exact zero that is not); passes flags-none
+#   hn_from_an                   S16L3 weight_hh 5.0e6 / 5.0e6 (the n third); passes none
+#   bhn_outside_r                S37L16 out 3.9e5 / 5.2e5; passes none
+#   dar_without_bhn              S33L1 weight_ih 1.8e5 / 1.6e6 (the r third: the whole-tensor bound is the n third's); passes none
+#   dx_without_ln_term           S15L2 dx 5.0e6 / 5.5e6; passes none
+#   stale_state_second_trip      S4097L3 out 1.0e6 / 1.3e6; no other case has a second trip
+#   last_split_dropped           S4097L3 weight_ih 8.7e4 / 1.0e5 (the ragged split: 3 live rows); passes the three cases with one split
+#   ln_partials_first_trip_only  S4097L3 ln_w 3.9e4 / 3.9e4; no other case has a second trip
+# Every defect is three orders of magnitude past the bar on the whole tensor already: what the partitions add is the margin of the small
+# thirds (dar_without_bhn: 9 x), not a defect that only they catch.
+DEFECT_TABLE = {
+    "mask_after_cell": ("flags-mixed", "out"),
+    "dh_unmasked": ("flags-first", "dh0"),
+    "hn_from_an": ("S16L3", "weight_hh"),
+    "bhn_outside_r": ("S37L16", "out"),
+    "dar_without_bhn": ("S33L1", "weight_ih"),
+    "dx_without_ln_term": ("S15L2", "dx"),
+    "stale_state_second_trip": ("S4097L3", "out"),
+    "last_split_dropped": ("S4097L3", "weight_ih"),
+    "ln_partials_first_trip_only": ("S4097L3", "ln_w"),
+}
+
+
+def test_the_defect_table_names_every_defect():
+    assert set(DEFECT_TABLE) == set(GR.DEFECTS) and len(GR.DEFECTS) == 9
+    assert all(tag in GATE_CASES and name in ("out", "h_last") + GR.GRADS for tag, name in DEFECT_TABLE.values())
+
+
+@pytest.mark.parametrize("defect", GR.DEFECTS)
+def test_each_seeded_defect_fails_the_gate_on_its_named_case(gate_cases, defect):
+    """A subtly wrong kernel does not pass: the same emulation with ONE defect exceeds the bar on the named case and tensor; the number of
+    cases it fails on is printed."""
+    tag, name = DEFECT_TABLE[defect]
+    case, zero, r64, r32 = gate_cases[tag]
+    assert not GR.gate(tag, _items(GR.emulate_kernel(*case), r64, r32), zero=zero, verbose=False)[2]
+    item = next(it for it in _items(GR.emulate_kernel(*case, defect=defect), r64, r32) if it[0] == name)
+    whole, parts = GR.gate_ratios(*item, zero=name in zero)
+    assert max(parts.values()) > GR.BAR, (defect, tag, name, parts)
+    failing = [t for t, (c, z, a, b) in gate_cases.items() if GR.gate(t, _items(GR.emulate_kernel(*c, defect=defect), a, b), zero=z, verbose=False)[2]]
+    print(f"  {defect}: {tag} {name} whole tensor {whole:.3g}, worst partition {max(parts.values()):.3g}; fails on {len(failing)} of {len(gate_cases)} cases")

@@ -5,11 +5,14 @@ encoder's 20 gradient tensors, e_hip <= 8 max(e_32, 2^-24 max|ref_64|), errors a
 fp64 (the gradients: fp64 autograd of (encoder(...) * dy).sum() with a seeded normal dy), e_32 the error of the same statements in CPU fp32.
 Every backward case asserts first, on the CPU, that no fp64 reference gradient tensor is identically zero; in_proj_bias' k third, which the
 softmax cancels, must be exactly zero on the device.  Worst measured ratio per case: printed by test_report_ratios (RATIOS).
+The backward pass's own plan (train_plan): tiles of kEncRows = 32 rows, tps = ceil(tiles / kCtMaxSplits) tiles per row range of the weight-gradient
+kernel, kCtMaxSplits = 48.  523 env-steps x 3 agents = 1 569 rows = 50 tiles: tps 2, 25 splits, one live row in the last tile — the one shape
+that takes the tps > 1 branch through hns_encoder_backward and hns_encoder_reduce_kernel (asserted from these constants).
 
 Measured on an MI355X (worst e_hip / max(e_32, 2^-24 max|ref_64|) over a case's tensors; features / the 20 gradient tensors):
   fixture shapes: a3k5d35 0.76 / 1.03, a3k8d20 1.08 / 1.41, a1k5d20 0.83 / 1.86, a6k16d24 1.40 / 1.61;
   shape limits: A = 1 1.02 / 1.39, A = 7 0.83 / 1.43, K = 1 1.11 / 1.34, K = 16 1.22 / 1.66, D = 1 0.95 / 1.12, D = 96 1.00 / 1.27,
-  one env-step 1.35 / 2.12, 33 rows 1.22 / 1.46;
+  one env-step 1.35 / 2.12, 33 rows 1.22 / 1.46; past 48 weight-gradient tiles (523 env-steps x 3 agents: 50 tiles, two per split) 0.90 / 1.29;
   the custom critic end to end (value_loss, values, the head's and the encoder's gradients): the op path 1.96 (unclipped branch) and 1.36
   (clipped branch), the fused value_loss_and_grad on the same inputs 1.86 and 1.62."""
 import ctypes as C
@@ -34,10 +37,27 @@ pytestmark = pytest.mark.gpu
 BAR = 8.0
 RATIOS = {}
 # (A, K, D, env-steps): the four fixture shapes of g_policy.npz, then one value at its limit per case: A = 1 (no state_others) and 7, K = 1 and
-# 16, D = 1 and 96, one env-step, 11 env-steps x 3 agents = 33 rows (the second tile has a single live row)
+# 16, D = 1 and 96, one env-step, 11 env-steps x 3 agents = 33 rows (the second tile has a single live row); PAST_SPLITS: more tiles than the
+# weight-gradient kernel has row ranges (test_the_large_shape_takes_two_tiles_per_split)
+PAST_SPLITS = (3, 5, 35, 523)
 SHAPES = [(3, 5, 35, 37), (3, 8, 20, 37), (1, 5, 20, 37), (6, 16, 24, 37),
-          (1, 5, 20, 40), (7, 5, 20, 9), (3, 1, 20, 33), (3, 16, 20, 33), (3, 5, 1, 33), (3, 5, 96, 33), (3, 5, 35, 1), (3, 5, 35, 11)]
+          (1, 5, 20, 40), (7, 5, 20, 9), (3, 1, 20, 33), (3, 16, 20, 33), (3, 5, 1, 33), (3, 5, 96, 33), (3, 5, 35, 1), (3, 5, 35, 11), PAST_SPLITS]
 CANARY = 1234.5
+ROWS, MAX_SPLITS = 32, 48                                       # csrc/hns_encoder.h: kEncRows; csrc/hns_policy_train.hip: kCtMaxSplits
+
+
+def test_the_large_shape_takes_two_tiles_per_split():
+    """hns_encoder_backward's own plan (train_plan): tiles of 32 rows, tps = ceil(tiles / 48) tiles per split.  Every other shape of SHAPES has
+    at most 7 tiles (tps 1); PAST_SPLITS is the smallest A = 3 batch with tps 2 whose last tile holds ONE live row: 1 569 rows, 50 tiles, 25
+    splits."""
+    plan = lambda rows: (-(-rows // ROWS), -(-(-(-rows // ROWS)) // MAX_SPLITS))
+    A, _, _, S = PAST_SPLITS
+    rows = S * A
+    tiles, tps = plan(rows)
+    assert (rows, tiles, tps, -(-tiles // tps)) == (1569, 50, 2, 25) and tiles > MAX_SPLITS
+    assert rows - (tiles - 1) * ROWS == 1
+    assert all(plan(s[3] * s[0])[1] == 1 and plan(s[3] * s[0])[0] <= 7 for s in SHAPES if s != PAST_SPLITS)
+    assert all(plan(r)[1] == 1 or r - (plan(r)[0] - 1) * ROWS != 1 for r in range(A, rows, A))       # the smallest such batch
 
 
 def _tag(shape):
