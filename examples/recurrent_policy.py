@@ -12,7 +12,10 @@ Training: each network is AttentionEncoder -> GRU -> a torch head (hns_amd.encod
 A minibatch is a set of (env, segment) pairs; a segment starts from its STORED state, the stored flags mask the state inside it, so the
 recomputed log-probabilities are the collected ones up to rounding: the script prints max |ratio - 1| of the first minibatch before any step.
 The losses are the reference's clipped PPO surrogate with an entropy bonus and the clipped Huber value loss; the targets come from
-gae.rollout_targets with the bootstrap value of ONE value_only call on the last next observation, the stored last critic state and flags."""
+gae.rollout_targets with the bootstrap value of ONE value_only call on the last next observation, the stored last critic state and flags.
+
+--eval: after training, one seeded deterministic episode through `DeviceEvaluator(env, pol, collector=col)` — the actor alone with its state
+carried on the device (`RecurrentDevicePolicy.act_step`), the `eval/stats.*` means printed."""
 import argparse
 import os
 import sys
@@ -22,7 +25,7 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import hns_amd  # noqa: E402,F401
-from hns_amd import collector, gae, policy  # noqa: E402
+from hns_amd import collector, evaluator, gae, policy  # noqa: E402
 from hns_amd.encoder import AttentionEncoder  # noqa: E402
 from hns_amd.learner import ValueNorm1  # noqa: E402
 from hns_amd.rnn import GRU  # noqa: E402
@@ -58,13 +61,18 @@ class Network(nn.Module):
 
 
 class StandInEnv:
-    """Without a GPU: seeded random observations behind HideAndSeek's reset / step surface, lock-step episodes of `max_episode_length`."""
+    """Without a GPU: seeded random observations behind HideAndSeek's reset / step surface, lock-step episodes of `max_episode_length`.
+    For --eval: `set_seed` and one per-env statistic, the episode's sum of |action|."""
 
     def __init__(self, envs, A=3, K=5, D=35, max_episode_length=24):
         self.n, self.A, self.K, self.D = envs, A, K, D
         self.batch_size, self.max_episode_length = torch.Size([envs]), max_episode_length
         self.g = torch.Generator().manual_seed(0)
         self.progress = torch.zeros(envs, dtype=torch.long)
+        self.stats = {"action_sum": torch.zeros(envs, 1)}
+
+    def set_seed(self, seed=-1):
+        self.g.manual_seed(seed)
 
     def _td(self):
         rn = lambda *s: torch.randn(*s, generator=self.g)
@@ -75,10 +83,12 @@ class StandInEnv:
     def reset(self, td=None):
         mask = torch.ones(self.n, dtype=torch.bool) if td is None else td["_reset"].reshape(-1)
         self.progress[mask] = 0
+        self.stats["action_sum"][mask] = 0
         return self._td()
 
     def step(self, td):
         self.progress += 1
+        self.stats["action_sum"] += td[("agents", "action")].abs().sum((1, 2)).reshape(self.n, 1)
         nxt = self._td()
         nxt.set(("agents", "reward"), 0.1 * torch.randn(self.n, self.A, 1, generator=self.g))
         nxt.set("done", (self.progress >= self.max_episode_length).reshape(self.n, 1))
@@ -94,6 +104,7 @@ def main():
     ap.add_argument("--envs", type=int, default=256)
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--updates", type=int, default=4)
+    ap.add_argument("--eval", action="store_true", help="after training: one deterministic episode, the eval/stats.* means")
     args = ap.parse_args()
     if args.steps % SEQ:
         ap.error(f"--steps must be a multiple of the segment length {SEQ}")
@@ -147,6 +158,9 @@ def main():
             nn.utils.clip_grad_norm_([*actor.parameters(), *critic.parameters()], 10.0)
             opt.step()
             print(f"rollout {it} update {u}: policy loss {policy_loss.item():+.5f}  value loss {value_loss.item():.5f}  ({B} segments x {SEQ} steps x {A} agents)")
+    if args.eval:
+        for k, v in sorted(evaluator.DeviceEvaluator(env, pol, collector=col).evaluate(seed=0).items()):
+            print(f"{k} = {v:.6g}")
     env.close()
 
 

@@ -767,6 +767,21 @@ size_t hns_policy_rnn_packed_bytes(void);
 int hns_policy_rnn_pack(const hns_gru_net *actor_rnn, const hns_gru_net *critic_rnn, void *rnn_packed, void *stream);
 int hns_policy_forward_rnn(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
                            const hns_policy_io *io, const hns_policy_rnn_io *rio, int32_t flags, uint64_t seed, uint64_t *counter, void *stream);
+/* The recurrent actor alone, the mode of the distribution (recurrent evaluation; hns_amd.policy.RecurrentDevicePolicy.act_step; DESIGN.md
+ * §7.13): ONE launch runs the actor half of hns_policy_forward_rnn — the encoder over the actor image (the first half of `packed`), one GRU
+ * step on the actor's GRU image (the first half of `rnn_packed`), LayerNorm(h' + f), fc_mean — and writes io->action[row * 4 + o] = loc[o] and
+ * rio->actor_h_out[row] = h' for every row, and nothing else.  Never read or written: the critic half of `packed`, the critic half of
+ * `rnn_packed`, io->eps, the Philox call counter, io->log_prob / io->value / io->loc, rio->critic_h_in / rio->critic_h_out (NULL is fine for
+ * all of these; non-NULL is left untouched).  `action` and `actor_h_out` are bit for bit what hns_policy_forward_rnn with
+ * HNS_POLICY_DETERMINISTIC writes there for the same inputs: the same device functions in the same order, no other summation order.
+ * rio->actor_h_in: [E, A, 128] or NULL for zeros; rio->is_init: uint8 [E] or NULL, the env-level flag (a flagged row's h_in is not read, so NaN
+ * there is harmless); actor_h_out may be actor_h_in (in place).  Properties: no host synchronisation, no allocation, capturable; the same
+ * inputs give the same bits; a row's results do not depend on the other rows of the call.  Refused before the launch, in this order: a NULL or
+ * misaligned packed image / io and a shape out of range (as hns_policy_act); a NULL or misaligned rnn_packed (16 bytes) or rio (8 bytes); a
+ * missing or misaligned observation, a negative stride; a missing or misaligned action; a missing or misaligned (16 bytes) actor_h_out; a
+ * misaligned (16 bytes) actor_h_in. */
+int hns_policy_act_rnn(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                       const hns_policy_io *io, const hns_policy_rnn_io *rio, void *stream);
 /* The 2-norm of one flat fp32 gradient bucket: norm[0] = f32(sqrt(sum_i flat[i]^2)), in this order (tests/dp_reference.py restates it in numpy):
  * the bucket is cut into quads of four consecutive floats, the last one short by numel % 4 values that count as 0 (nothing past numel is
  * read); G = clamp(ceil(quads / 1024), 1, 64) workgroups of 256 threads, T = 256 G; thread t of the grid adds, for q = t, t + T, t + 2 T, ...,

@@ -26,6 +26,9 @@
 //                               LDS and launch bounds: per network the encoder, then ONE GRU step on the features it left in registers (six more
 //                               128 x 128 products from a second packed image, the gates in the products' accumulator layout), LayerNorm(h + f),
 //                               the head.  The state comes from and goes to HBM once per network; the features never do.
+//   hns_policy_act_rnn_kernel : the recurrent forward's actor half alone (encoder, GRU step on the actor's GRU image, LayerNorm, fc_mean): action =
+//                               loc and the actor's new state, nothing else (recurrent evaluation).  Bit for bit the recurrent
+//                               forward's deterministic action and actor state.
 //   hns_policy_rnn_pack_kernel: the two GRUs' tensors -> their packed image.
 //   hns_policy_bump_kernel    : the device call counter += 1 after a sampling call (Philox counter; a captured graph draws fresh noise per replay).
 // Determinism: fixed reduction orders (butterflies over the eight lanes of a row), no atomics.
@@ -450,6 +453,26 @@ __global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_rnn_kernel(
     if (live && g == 0) a.value[row] = v;
 }
 
+// the recurrent actor alone, the mode of the distribution (evaluation): the recurrent forward kernel's first encoder pass, GRU step and head
+// on the actor's two images; the actor's state in and out, the action, nothing else read or written
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_rnn_kernel(const PolArgs a, const PolRnnArgs ra) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
+    const long long row0 = (long long)blockIdx.x * kEncRows, row = row0 + r;
+    const float *net = a.img;
+    float y[16];
+    pol_encoder(a, net, L, w, lane, r, g, row, y);
+    pol_gru_step(ra.img, ra.h_in[0], ra.h_out[0], ra.is_init, a.A, row0, a.rows, L, w, lane, r, g, y);
+    float loc[4];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
+    if (row < a.rows && g == 0) {
+#pragma unroll
+        for (int o = 0; o < 4; ++o) a.action[row * 4 + o] = loc[o];
+    }
+}
+
 __global__ void hns_policy_bump_kernel(unsigned long long *counter) { counter[0] += 1ull; }
 
 }  // namespace hns
@@ -651,6 +674,32 @@ int hns_policy_act(const void *packed, int32_t self_dim, int64_t num_envs, int32
     HNS_CHECK_HIP(attr);
     const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
     hipLaunchKernelGGL(hns::hns_policy_act_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), static_cast<hipStream_t>(stream), a);
+    HNS_CHECK_HIP(hipGetLastError());
+    return HNS_OK;
+}
+
+int hns_policy_act_rnn(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                       const hns_policy_io *io, const hns_policy_rnn_io *rio, void *stream) {
+    const char *fn = "hns_policy_act_rnn";
+    int rc = pol_check_shape(fn, packed, self_dim, num_envs, num_agents, num_cylinders, io);
+    if (rc != HNS_OK) return rc;
+    if (!rnn_packed || !rio || !hns_aligned(rnn_packed, 16) || !hns_aligned(rio, 8)) return hns_fail(fn, "null or misaligned packed GRU image / rnn io");
+    rc = pol_check_obs(fn, num_agents, io);
+    if (rc != HNS_OK) return rc;
+    if (!io->action || !hns_aligned(io->action, 4)) return hns_fail(fn, "action output missing or misaligned");
+    if (!rio->actor_h_out || !hns_aligned(rio->actor_h_out, 16)) return hns_fail(fn, "state output missing or not 16-byte aligned");
+    if (!hns_aligned(rio->actor_h_in, 16)) return hns_fail(fn, "state input not 16-byte aligned");
+    const hns::PolArgs a = pol_args(packed, self_dim, num_envs, num_agents, num_cylinders, io);   // eps, counter, loc, log_prob, value stay NULL: never touched
+    hns::PolRnnArgs ra{};                                         // the critic's h_in / h_out stay NULL: never touched
+    ra.img = static_cast<const float *>(rnn_packed);
+    ra.h_in[0] = rio->actor_h_in; ra.h_out[0] = rio->actor_h_out;
+    ra.is_init = rio->is_init;
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_act_rnn_kernel),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
+    HNS_CHECK_HIP(attr);
+    const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
+    hipLaunchKernelGGL(hns::hns_policy_act_rnn_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), static_cast<hipStream_t>(stream), a,
+                       ra);
     HNS_CHECK_HIP(hipGetLastError());
     return HNS_OK;
 }

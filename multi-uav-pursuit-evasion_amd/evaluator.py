@@ -65,7 +65,11 @@ def stat_means(values, mask=None):
 
 class DeviceEvaluator:
     """env: a HideAndSeek (or a subclass, or anything with its set_seed / reset / step / stats / max_episode_length surface); policy: a
-    DevicePolicy (anything with `act(state_self, state_others, cylinders, out=None)`).  tp_net: the predictor whose parameters the env's own
+    DevicePolicy (anything with `act(state_self, state_others, cylinders, out=None)`), or a recurrent policy: one whose `recurrent` attribute
+    is true (RecurrentDevicePolicy) must offer `act_step(state_self, state_others, cylinders, state=None, is_init=None, out=None,
+    out_state=None) -> (action, state)` with state=None meaning zeros and `out_state` allowed to be `state`; the run then owns ONE persistent
+    [N, A, 128] actor state beside its one action tensor — zeros going into step 0 (the full reset), carried in place from then on, nothing
+    stored per step, the policy's call counter and a collector's own rnn states untouched.  tp_net: the predictor whose parameters the env's own
     `TP` takes before a run (the training env's, when `env` is a separate evaluation env).  collector: a DeviceCollector ON THIS env, told to
     `restart()` after every run.
 
@@ -144,9 +148,13 @@ class DeviceEvaluator:
             if hasattr(env, "clear_carried_state"):
                 env.clear_carried_state()                        # what a reset leaves alone (controller state, the predictor's window) must
             cur = env.reset()                                    # not make the run depend on what the env did before it
-            action = step_td = None
+            action = step_td = state = None
+            recurrent = getattr(self.policy, "recurrent", False)
             for t in range(int(env.max_episode_length)):
-                action = self.policy.act(*self._obs(cur), out=action)
+                if recurrent:                                    # state None at step 0: zeros, the full reset; then in place
+                    action, state = self.policy.act_step(*self._obs(cur), state=state, out=action, out_state=state)
+                else:
+                    action = self.policy.act(*self._obs(cur), out=action)
                 if step_td is None:
                     step_td = TensorDict({"agents": {"action": action}}, env.batch_size)
                 cur = env.step(step_td)["next"]

@@ -16,8 +16,9 @@ so the next call follows an optimiser step (as env.HideAndSeek._tp_sync_weights 
 CPU tensors run a torch restatement of the reference's statements (tests, gloo runs — not the hot path).  DESIGN.md §7.3.
 
 `RecurrentDevicePolicy` is the `actor.rnn` / `critic.rnn` configuration (a GRU behind each encoder, modules/rnn.py): encoder -> one GRU step ->
-head for both networks in ONE call of `hns_policy_forward_rnn`, the two states carried on the device.  `DevicePolicy` keeps
-refusing that configuration."""
+head for both networks in ONE call of `hns_policy_forward_rnn`, the two states carried on the device; its `act_step` runs
+the actor's half alone with the actor's state (`hns_policy_act_rnn`: evaluation).  `DevicePolicy` keeps refusing that
+configuration."""
 import collections
 import ctypes as C
 import math
@@ -412,6 +413,13 @@ def torch_forward_rnn(actor, critic, actor_rnn, critic_rnn, xs, xo, xc, actor_st
     return RecurrentPolicyOutput(*_heads(actor, ya, value, eps, deterministic, generator), ha, hc)
 
 
+def torch_act_rnn(actor, actor_rnn, xs, xo, xc, state=None, is_init=None):
+    """The CPU restatement of hns_policy_act_rnn: the actor's half of `torch_forward_rnn` alone -> (loc [E, A, 4], the actor's state after the
+    step [E, A, 128]); the same statements on the same operands, so the same bits as its deterministic action and actor_state."""
+    ya, ha = _rnn_step(actor, actor_rnn, xs, xo, xc, state, is_init)
+    return F.linear(ya, actor["head_w"], actor["head_b"]), ha
+
+
 def split_rnn(params, what):
     """(the network's parameters without its GRU, the GRU's six tensors by hns_gru_net field) from reference names: the GRU sits under
     `rnn.` (rnn.cell.weight_ih, ..., rnn.layer_norm.bias)."""
@@ -437,7 +445,8 @@ class RecurrentDevicePolicy(DevicePolicy):
     """MAPPOPolicy with actor.rnn / critic.rnn (a GRU(128, 128) behind each encoder) in one HIP launch per call: encoder -> GRU step -> head
     for both networks, the states read and written on the device.  Built from the same sources as DevicePolicy; the GRU tensors are the
     `rnn.*` entries of the actor's and the critic's parameters.  `forward` takes and returns the two states ([E, A, 128]; None: zeros) and
-    an env-level `is_init` ([E] or [E, 1]; None: no env starts an episode); `out_states` may be the input tensors (in place)."""
+    an env-level `is_init` ([E] or [E, 1]; None: no env starts an episode); `out_states` may be the input tensors (in place).  `act_step` is
+    the actor-only pass with the actor's state (evaluation); `act`, which has no state argument, keeps refusing."""
     recurrent = True
 
     def __init__(self, actor_params, critic, cfg=None, device=None, seed=0, agent_name="drone"):
@@ -484,6 +493,49 @@ class RecurrentDevicePolicy(DevicePolicy):
             raise ValueError(f"{name} must be a contiguous, 16-byte aligned float32 [{E}, {A}, {EMBED_DIM}] tensor on {self.device}")
         return t
 
+    def _flags(self, is_init, E):
+        """is_init as the kernels take it: uint8 [E], contiguous (None stays None)."""
+        if is_init is None:
+            return None
+        if not torch.is_tensor(is_init) or is_init.numel() != E or is_init.device != self.device:
+            raise ValueError(f"is_init must hold one flag per env ([{E}] or [{E}, 1]) on {self.device}")
+        is_init = is_init.reshape(E).contiguous()                # (a time slice of a stored [N, T, 1] tensor is strided)
+        return is_init.view(torch.uint8) if is_init.dtype == torch.bool else (is_init != 0).view(torch.uint8)
+
+    def act_step(self, obs_self, obs_others, obs_cylinders, state=None, is_init=None, out=None, out_state=None):
+        """The actor-only pass of a recurrent policy: (action [E, A, 4], state [E, A, 128]), the mode of the actor's distribution and the
+        actor's state AFTER the step (hns_policy_act_rnn: the actor's encoder, GRU step and head; no critic, no log-prob, no noise, the call
+        counter untouched) — bit for bit `forward(..., actor_state=state, is_init=is_init, deterministic=True)`'s action and actor_state.
+        state: [E, A, 128] or None for zeros; is_init as `forward` takes it.  out / out_state: contiguous fp32 tensors written in place and
+        returned; out_state may be `state` (an evaluation loop's one action and one state tensor)."""
+        xs, xo, xc = self._validate(obs_self, obs_others, obs_cylinders)
+        E, A, _ = xs.shape
+        h, oh = self._state(state, "state", E, A), self._state(out_state, "out_state", E, A)
+        is_init = self._flags(is_init, E)
+        if out is not None and (tuple(out.shape) != (E, A, ACTION_DIM) or out.dtype != torch.float32 or out.device != self.device
+                                or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 [{E}, {A}, {ACTION_DIM}] tensor on {self.device}")
+        if self.device.type != "cuda":
+            xs, xc, xo = xs.contiguous(), xc.contiguous(), (xo.contiguous() if xo is not None else None)      # as forward: the same bits
+            with torch.no_grad():
+                action, new = torch_act_rnn(self.actor_p, self.actor_rnn, xs.unsqueeze(2), xo, xc, h, is_init)
+            return (action if out is None else out.copy_(action)), (new if oh is None else oh.copy_(new))
+        self.refresh()
+        xs, xo, xc, io = self._io(xs, xo, xc)
+        action = out if out is not None else torch.empty(E, A, ACTION_DIM, device=self.device)
+        oh = oh if oh is not None else torch.empty(E, A, EMBED_DIM, device=self.device)
+        io.action = action.data_ptr()
+        rio = abi.HnsPolicyRnnIo()
+        rio.actor_h_in = h.data_ptr() if h is not None else None
+        rio.actor_h_out = oh.data_ptr()
+        rio.is_init = is_init.data_ptr() if is_init is not None else None
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            rc = self._lib.hns_policy_act_rnn(self.packed.data_ptr(), self.rnn_packed.data_ptr(), self.self_dim, E, A, xc.shape[2], C.byref(io),
+                                              C.byref(rio), st)
+        self._check(rc, "hns_policy_act_rnn")
+        return action, oh
+
     def forward(self, obs_self, obs_others, obs_cylinders, actor_state=None, critic_state=None, is_init=None, eps=None, deterministic=False,
                 value_only=False, out_states=None):
         """RecurrentPolicyOutput(action [E, A, 4], log_prob [E, A, 1], value [E, A, 1], loc [E, A, 4], actor_state, critic_state [E, A, 128]):
@@ -496,11 +548,7 @@ class RecurrentDevicePolicy(DevicePolicy):
         ha, hc = self._state(actor_state, "actor_state", E, A), self._state(critic_state, "critic_state", E, A)
         oa, oc = out_states if out_states is not None else (None, None)
         oa, oc = self._state(oa, "out_states[0]", E, A), self._state(oc, "out_states[1]", E, A)
-        if is_init is not None:
-            if not torch.is_tensor(is_init) or is_init.numel() != E or is_init.device != self.device:
-                raise ValueError(f"is_init must hold one flag per env ([{E}] or [{E}, 1]) on {self.device}")
-            is_init = is_init.reshape(E).contiguous()            # (a time slice of a stored [N, T, 1] tensor is strided)
-            is_init = is_init.view(torch.uint8) if is_init.dtype == torch.bool else (is_init != 0).view(torch.uint8)
+        is_init = self._flags(is_init, E)
         if self.device.type != "cuda":
             # contiguous observations: torch's CPU matrix products round differently for strided operands, and a stored rollout re-run from
             # views of its storage must give the bits the collection gave
