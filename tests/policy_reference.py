@@ -180,6 +180,86 @@ def log_std_case():
     return actor, critic, obs, eps
 
 
+def _f32_params(params):
+    return {k[len("module."):] if k.startswith("module.") else k: torch.as_tensor(np.asarray(v)).to(torch.float32) for k, v in params.items()}
+
+
+def _emulate_ln(x, w, b, ln_eps=1e-5):
+    x = x - x.sum(-1, keepdim=True) * (1.0 / E)
+    rstd = 1.0 / torch.sqrt((x * x).sum(-1, keepdim=True) * (1.0 / E) + ln_eps)
+    return (x * rstd) * w + b
+
+
+def _emulate_encoder(p, prefix, obs, defect=None):
+    """One network's features [.., 128] by the kernel's algorithm (emulate_kernel's docstring) in fp32; p and obs hold fp32 tensors."""
+    f32 = torch.float32
+    ln_eps = 0.0 if defect == "layernorm_eps_0" else 1e-5
+    ln = lambda x, w, b: _emulate_ln(x, w, b, ln_eps)
+    g = lambda n: p[prefix + n]
+    lnw, lnb = g("split_embed.layer_norm.weight"), g("split_embed.layer_norm.bias")
+    tok = lambda key, bias_key: ln(obs[key] @ g(f"split_embed.embed.{key}.weight").T + g(f"split_embed.embed.{bias_key}.bias"), lnw, lnb)
+    toks = [tok("state_self", "state_self")]
+    if "state_others" in obs:
+        toks.append(tok("state_others", "cylinders" if defect == "others_with_cylinder_bias" else "state_others"))
+    toks.append(tok("cylinders", "cylinders"))
+    t = torch.cat(toks, dim=-2)
+    if defect == "last_cylinder_skipped":
+        t = t[..., :-1, :]
+    t0 = t[..., 0, :]
+    W, bW = g("attn.in_proj_weight"), g("attn.in_proj_bias")
+    q = t0 @ W[:E].T + bW[:E]
+    rs = torch.tensor(1.0 / math.sqrt(E), dtype=f32)
+    if defect == "score_scale_bf16":
+        rs = rs.to(torch.bfloat16).to(f32)
+    kq = (q @ W[E:2 * E]) * rs                               # W_k^T q / sqrt(128)
+    s = (t * kq.unsqueeze(-2)).sum(-1)
+    m, l, z = s[..., 0], torch.ones_like(s[..., 0]), t0.clone()
+    for j in range(1, t.shape[-2]):
+        mn = torch.maximum(s[..., j], m)
+        cj, pj = torch.exp(m - mn), torch.exp(s[..., j] - mn)
+        l = l * cj + pj
+        z = pj.unsqueeze(-1) * t[..., j, :] + (z if defect == "softmax_rescale_omitted" else z * cj.unsqueeze(-1))
+        m = mn
+    z = z * (1.0 / l).unsqueeze(-1)
+    v = z @ W[2 * E:].T
+    if defect != "value_bias_dropped":
+        v = v + bW[2 * E:]
+    attn = v @ g("attn.out_proj.weight").T + g("attn.out_proj.bias")
+    x = ln(t0 + attn, g("norm1.weight"), g("norm1.bias"))
+    h = x @ g("linear1.weight").T + g("linear1.bias")
+    if defect == "gelu_tanh":
+        h = 0.5 * h * (1.0 + torch.tanh(0.7978845608028654 * (h + 0.044715 * h * h * h)))
+    else:
+        h = 0.5 * h * (1.0 + torch.erf(h * 0.7071067811865476))
+    return ln(x + (h @ g("linear2.weight").T + g("linear2.bias")), g("norm2.weight"), g("norm2.bias"))
+
+
+def emulate_features(actor, critic, obs):
+    """(actor features, critic features) [E, A, 128] as fp32 tensors: what emulate_kernel's two encoder passes hand to the heads (and the
+    recurrent step's emulation, policy_rnn_reference.emulate_step, to its GRUs)."""
+    a, c = _f32_params(actor), _f32_params(critic)
+    obs = {k: torch.as_tensor(np.asarray(v)).to(torch.float32) for k, v in obs.items()}
+    with torch.no_grad():
+        return _emulate_encoder(a, "encoder.", obs), _emulate_encoder(c, "base.", obs)
+
+
+def emulate_head(a, y, eps, defect=None):
+    """(loc, log_prob [.., 1]) of the kernel's DiagGaussian head on the actor's features y (fp32 tensors): the log-probability summed in
+    component order.  eps None: the mode."""
+    f32 = torch.float32
+    loc = y @ a["act_dist.fc_mean.weight"].T + a["act_dist.fc_mean.bias"]
+    sc = torch.exp(a["act_dist.log_std"])
+    lsc = torch.log(sc)
+    act = loc + sc * torch.as_tensor(np.asarray(eps)).to(f32) if eps is not None else loc
+    d = act - loc
+    lp = None
+    for o in range(4):
+        k = 0 if defect == "log_std_of_component_0" else o
+        term = (-(d[..., o] * d[..., o]) / (2.0 * (sc[k] * sc[k])) - lsc[k]) - 0.91893853320467274
+        lp = term if lp is None else lp + term
+    return loc, lp.unsqueeze(-1)
+
+
 def emulate_kernel(actor, critic, obs, eps, defect=None):
     """[loc, log_prob, value] as fp32 torch statements of hns_policy_forward_kernel's ALGORITHM (csrc/hns_policy.hip), not of the reference's
     statements: single-query algebra (W_k^T q / sqrt(128) with the key bias dropped, W_v (sum_j a_j t_j) + b_v), the online softmax in token
@@ -187,69 +267,12 @@ def emulate_kernel(actor, critic, obs, eps, defect=None):
     order.  (The order of the additions inside a dot product is torch's, not the MFMA's: fp32 noise either way.)  eps None: the mode.
     `defect` seeds one subtle error (DEFECTS) into both networks."""
     assert defect is None or defect in DEFECTS, defect
-    f32 = torch.float32
-    a = {k[len("module."):] if k.startswith("module.") else k: torch.as_tensor(np.asarray(v)).to(f32) for k, v in actor.items()}
-    c = {k[len("module."):] if k.startswith("module.") else k: torch.as_tensor(np.asarray(v)).to(f32) for k, v in critic.items()}
-    obs = {k: torch.as_tensor(np.asarray(v)).to(f32) for k, v in obs.items()}
-    ln_eps = 0.0 if defect == "layernorm_eps_0" else 1e-5
-
-    def ln(x, w, b):
-        x = x - x.sum(-1, keepdim=True) * (1.0 / E)
-        rstd = 1.0 / torch.sqrt((x * x).sum(-1, keepdim=True) * (1.0 / E) + ln_eps)
-        return (x * rstd) * w + b
-
-    def enc(p, prefix):
-        g = lambda n: p[prefix + n]
-        lnw, lnb = g("split_embed.layer_norm.weight"), g("split_embed.layer_norm.bias")
-        tok = lambda key, bias_key: ln(obs[key] @ g(f"split_embed.embed.{key}.weight").T + g(f"split_embed.embed.{bias_key}.bias"), lnw, lnb)
-        toks = [tok("state_self", "state_self")]
-        if "state_others" in obs:
-            toks.append(tok("state_others", "cylinders" if defect == "others_with_cylinder_bias" else "state_others"))
-        toks.append(tok("cylinders", "cylinders"))
-        t = torch.cat(toks, dim=-2)
-        if defect == "last_cylinder_skipped":
-            t = t[..., :-1, :]
-        t0 = t[..., 0, :]
-        W, bW = g("attn.in_proj_weight"), g("attn.in_proj_bias")
-        q = t0 @ W[:E].T + bW[:E]
-        rs = torch.tensor(1.0 / math.sqrt(E), dtype=f32)
-        if defect == "score_scale_bf16":
-            rs = rs.to(torch.bfloat16).to(f32)
-        kq = (q @ W[E:2 * E]) * rs                               # W_k^T q / sqrt(128)
-        s = (t * kq.unsqueeze(-2)).sum(-1)
-        m, l, z = s[..., 0], torch.ones_like(s[..., 0]), t0.clone()
-        for j in range(1, t.shape[-2]):
-            mn = torch.maximum(s[..., j], m)
-            cj, pj = torch.exp(m - mn), torch.exp(s[..., j] - mn)
-            l = l * cj + pj
-            z = pj.unsqueeze(-1) * t[..., j, :] + (z if defect == "softmax_rescale_omitted" else z * cj.unsqueeze(-1))
-            m = mn
-        z = z * (1.0 / l).unsqueeze(-1)
-        v = z @ W[2 * E:].T
-        if defect != "value_bias_dropped":
-            v = v + bW[2 * E:]
-        attn = v @ g("attn.out_proj.weight").T + g("attn.out_proj.bias")
-        x = ln(t0 + attn, g("norm1.weight"), g("norm1.bias"))
-        h = x @ g("linear1.weight").T + g("linear1.bias")
-        if defect == "gelu_tanh":
-            h = 0.5 * h * (1.0 + torch.tanh(0.7978845608028654 * (h + 0.044715 * h * h * h)))
-        else:
-            h = 0.5 * h * (1.0 + torch.erf(h * 0.7071067811865476))
-        return ln(x + (h @ g("linear2.weight").T + g("linear2.bias")), g("norm2.weight"), g("norm2.bias"))
-
+    a, c = _f32_params(actor), _f32_params(critic)
+    obs = {k: torch.as_tensor(np.asarray(v)).to(torch.float32) for k, v in obs.items()}
     with torch.no_grad():
-        loc = enc(a, "encoder.") @ a["act_dist.fc_mean.weight"].T + a["act_dist.fc_mean.bias"]
-        sc = torch.exp(a["act_dist.log_std"])
-        lsc = torch.log(sc)
-        act = loc + sc * torch.as_tensor(np.asarray(eps)).to(f32) if eps is not None else loc
-        d = act - loc
-        lp = None
-        for o in range(4):
-            k = 0 if defect == "log_std_of_component_0" else o
-            term = (-(d[..., o] * d[..., o]) / (2.0 * (sc[k] * sc[k])) - lsc[k]) - 0.91893853320467274
-            lp = term if lp is None else lp + term
-        value = enc(c, "base.") @ c["v_out.weight"].T + c["v_out.bias"]
-    return [loc.numpy(), lp.unsqueeze(-1).numpy(), value.numpy()]
+        loc, lp = emulate_head(a, _emulate_encoder(a, "encoder.", obs, defect), eps, defect)
+        value = _emulate_encoder(c, "base.", obs, defect) @ c["v_out.weight"].T + c["v_out.bias"]
+    return [loc.numpy(), lp.numpy(), value.numpy()]
 
 
 # the seeded defects of emulate_kernel: each must fail the gate on a committed case (test_policy_net.py names it)

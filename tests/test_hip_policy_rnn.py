@@ -7,7 +7,10 @@ themselves): the golden cases, random batches at the shapes where the tile can g
 Exact properties, refusals, and the collector against a hand-driven loop (copy_ stores, an explicit state carry, flags on every step) are
 bit for bit.  Worst ratio per case over all outputs and steps, measured on an MI355X (RATIOS, printed by the last test): goldens 1.48 / 1.76,
 random e1a3k5d35 2.08, e11a3k5d35 1.25, e5a1k5d20 1.99, e3a7k16d96 1.40, strided views 1.52; over a stored segment the ops' log_prob 1.21 and
-value 1.02, the collected (fused) ones 1.00 and 0.83, largest |log_prob_op - log_prob_fused| 9.5e-7."""
+value 1.02, the collected (fused) ones 1.00 and 0.83, largest |log_prob_op - log_prob_fused| 9.5e-7.
+
+The tile, flag, guard-row and numerical edges of the same kernels (more than two tiles, every tail length, tiles that start inside an env,
+guard rows around every output, saturated gates, a 64-step chain) are test_hip_policy_rnn_edges.py's."""
 import ctypes as C
 import os
 
@@ -16,6 +19,7 @@ import pytest
 import torch
 
 import policy_reference as R
+import policy_rnn_cases as PC
 import policy_rnn_reference as RR
 from hns_amd import abi, collector, config, encoder, rnn
 from hns_amd import policy as P
@@ -26,9 +30,9 @@ pytestmark = pytest.mark.gpu
 BAR = RR.BAR
 RATIOS = {}
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-# (E, A, K, D): three rows of a 32-row tile; 33 rows (a second tile with one live row); no state_others; every limit at its maximum
-SHAPES = [(1, 3, 5, 35), (11, 3, 5, 35), (5, 1, 5, 20), (3, 7, 16, 96)]
-STEPS = 5
+# (E, A, K, D): three rows of a 32-row tile; 33 rows (a second tile with one live row); no state_others; every limit at its maximum — and
+# their chains' generator, shared with the CPU emulation of test_policy_rnn.py
+SHAPES, STEPS, _random_chain = PC.SHAPES, PC.STEPS, PC.random_chain
 
 
 def _dev(d):
@@ -46,25 +50,6 @@ def _cuda(x):
 
 def _policy(actor, critic, seed=0):
     return P.RecurrentDevicePolicy(_dev(actor), _dev(critic), seed=seed)
-
-
-def _random_chain(E, A, K, D, seed, steps=STEPS):
-    """(obs per step, eps per step, flags per step, h0 actor, h0 critic): flags for some envs at steps 0 and 3 (E = 1: at step 3)."""
-    g = np.random.default_rng(seed)
-    obs, eps, flags = [], [], []
-    for t in range(steps):
-        o, e = R.random_obs(E, A, K, D, seed + 10 * t + 1)
-        obs.append(o)
-        eps.append(e)
-        f = np.zeros(E, bool)
-        if t in (0, 3):
-            f = g.random(E) < 0.4
-            f[0] = t == 3
-            if E > 1:
-                f[-1] = t == 0
-        flags.append(f)
-    ha, hc = RR.random_states(E, A, seed + 5)
-    return obs, eps, flags, ha, hc
 
 
 def chain_gate(tag, actor, critic, obs, eps, flags, ha, hc, view=None):

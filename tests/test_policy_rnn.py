@@ -3,7 +3,12 @@ recurrent Actor / Critic (tests/golden/g_policy_rnn.npz), its parameter parsing,
 
 The collector checks run on test_collector.py's stub env (buffers rewritten in place, episodes of chosen lengths): `is_init` is the previous
 step's `done` (all ones after the full reset), and every stored segment, re-run step by step from its STORED start state and the stored
-flags, reproduces the stored values bit for bit — a state stored from the wrong slot, or after the step instead of before it, fails that."""
+flags, reproduces the stored values bit for bit — a state stored from the wrong slot, or after the step instead of before it, fails that.
+
+Last part: teeth for the device gate of test_hip_policy_rnn.py and test_hip_policy_rnn_edges.py.  The shared cases (policy_rnn_cases.py) cover
+what they claim, derived from their seeds; every numerical edge is well posed in the two CPU restatements alone; an fp32 emulation of the
+kernels' algorithm (policy_rnn_reference.emulate_step) passes the gate on every chain the device runs, and each of thirteen seeded defects
+taken from pol_gru_step's own structure fails it on a named chain (DEFECT_TABLE)."""
 import os
 
 import numpy as np
@@ -11,6 +16,7 @@ import pytest
 import torch
 
 import policy_reference as R
+import policy_rnn_cases as PC
 import policy_rnn_reference as RR
 from hns_amd import abi, collector, learner, rnn
 from hns_amd import policy as P
@@ -278,3 +284,224 @@ def test_a_non_recurrent_policys_storage_has_none_of_the_new_names():
         st.recurrent_kwargs()
     with pytest.raises(ValueError, match="recurrent"):
         collector.DeviceCollector(env, P.DevicePolicy(actor, critic), 4, rnn_seq_len=2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Does the recurrent device gate have teeth?  policy_rnn_reference.emulate_step is an fp32 restatement of the kernels' algorithm; the cases
+# (policy_rnn_cases.py) are the chains the GPU gate runs (test_hip_policy_rnn.py, test_hip_policy_rnn_edges.py).
+_FEATURES = {}
+
+
+def _emulate_chain(tag, defect=None, mode=False):
+    """{output: worst gate ratio over the steps} of the emulation along the chain `tag`, its own states feeding its next step (as the device's
+    do in chain_gate); mode: eps None."""
+    actor, critic, obs, eps, flags, ha, hc = PC.case(tag)
+    refs = PC.references(tag, mode)
+    worst = dict.fromkeys(RR.OUTPUTS, 0.0)
+    for t in range(len(obs)):
+        if (tag, t) not in _FEATURES:                            # (the encoder's features do not depend on the defect)
+            _FEATURES[tag, t] = R.emulate_features(actor, critic, obs[t])
+        out = RR.emulate_step(actor, critic, obs[t], ha, hc, flags[t], None if mode else eps[t], defect, features=_FEATURES[tag, t])
+        for name, ratio in RR.gate_ratios(out, *refs[t]).items():
+            worst[name] = max(worst[name], ratio)
+        ha, hc = out["actor_state"], out["critic_state"]
+    return worst
+
+
+def test_the_sweep_reaches_every_tail_length_agent_count_and_tile_count():
+    """Derived from the seeds, not assumed: E A mod 32 takes every residue, every A occurs, the tile counts include 1, 2 and >= 4, and
+    residue 0 occurs with one, two and three tiles (FULL_TILES)."""
+    shapes = [PC.sweep_shape(s) for s in PC.SWEEP_SEEDS]
+    assert [E * A % 32 for E, A, _, _ in shapes] == list(range(32)) == list(PC.SWEEP_SEEDS)
+    assert {A for _, A, _, _ in shapes} == set(range(1, 8))
+    assert all(1 <= K <= 16 and 1 <= D <= 96 and E >= 1 for E, _, K, D in shapes)
+    tiles = {PC.tiles_of(s) for s in shapes}
+    assert {1, 2} <= tiles and max(tiles) >= 4 and max(tiles) <= PC.MAX_SWEEP_TILES
+    assert {K for _, _, K, _ in shapes} >= {1, 16} and len({A > 1 for _, A, _, _ in shapes}) == 2
+    full = [(E * A % 32, PC.tiles_of((E, A, K, D))) for E, A, K, D in shapes + PC.FULL_TILES]
+    assert {(0, 1), (0, 2), (0, 3)} <= set(full)
+    assert [E * A for E, A, _, _ in PC.FULL_TILES] == [32, 64, 96]
+    assert len(set(PC.CASE_TAGS)) == len(PC.CASE_TAGS)
+    for tag in PC.SWEEP_TAGS + PC.FULL_TAGS:                     # the chain: no flag, then half of the envs
+        flags = PC.case(tag)[4]
+        assert len(flags) == 2 and not flags[0].any() and flags[1].sum() == (len(flags[1]) + 1) // 2
+
+
+@pytest.mark.parametrize("shape", PC.STRADDLE_SHAPES, ids=PC.shape_tag)
+def test_the_straddle_shapes_have_tiles_that_start_inside_an_env(shape):
+    E, A, _, _ = shape
+    rows = E * A
+    assert 120 <= rows <= 280 and PC.tiles_of(shape) >= 3
+    split = PC.straddling_envs(E, A)
+    assert len(split) >= 2 and all(e * A // 32 + 1 == (e * A + A - 1) // 32 for e in split)
+    starts = [row0 % A == 0 for row0 in range(0, rows, 32)]
+    assert any(starts) and not all(starts)                       # a tile on an env boundary and one that is not
+    assert len(split) == sum(not s for s in starts)
+    # the split division names another env for some row of every tile that starts inside an env, and only there
+    wrong = [row for row in range(rows) if row // 32 * 32 // A + row % 32 // A != row // A]
+    assert wrong and {row // 32 for row in wrong} == {t for t, s in enumerate(starts) if not s}
+    flags = PC.case("straddle-" + PC.shape_tag(shape))[4][0]
+    assert sorted(np.nonzero(flags)[0]) == split
+    below = sorted({e - 1 for e in split})
+    assert below[0] >= 0 and set(below) != set(split)            # the third flag set of the device test is another one
+
+
+def test_the_long_chain_and_the_old_shapes_are_what_the_device_files_run():
+    assert PC.SHAPES == [(1, 3, 5, 35), (11, 3, 5, 35), (5, 1, 5, 20), (3, 7, 16, 96)] and PC.STEPS == 5
+    actor, critic, obs, eps, flags, ha, hc = PC.long_case()
+    assert PC.LONG_CHAIN == (11, 3, 5, 35) and len(obs) == len(eps) == len(flags) == 64
+    assert [t for t, f in enumerate(flags) if f.any()] == [0, 15, 16, 17, 40, 63] and not any(f.all() for f in flags)
+    first = PC.case(PC.LONG_CPU_TAG)
+    assert len(first[2]) == 8 and all(np.array_equal(a, b) for a, b in zip(first[4], flags))
+
+
+@pytest.mark.parametrize("name", PC.EDGES)
+def test_every_edge_case_is_well_posed_in_the_reference_alone(name):
+    """For each output and step max(e_32, 2^-24 max|ref_64|) <= 1e-4 max|ref_64|: the gate still resolves a relative error of 1e-3, and
+    everything is finite.  Measured worst per edge: flat_tokens 5.4e-5 (value), saturated_softmax 4.1e-5 and saturated_gates 4.7e-5 (the
+    states), near_flat_norm 5.9e-6 (loc), large_state 2.2e-6, large_obs 6.9e-7, carry 1.3e-7."""
+    actor, critic, obs, eps, flags, ha, hc = PC.case(name)
+    E, A = PC.EDGE_SHAPES[name][:2]
+    assert ha.shape == hc.shape == (E, A, 128) and len(obs) == 3 and 0 < flags[1].sum() < E and not flags[0].any() and not flags[2].any()
+    worst = {}
+    for r64, r32 in PC.references(name):
+        for out in RR.OUTPUTS:
+            a, b = r64[out], r32[out]
+            assert np.isfinite(a).all() and np.isfinite(b).all()
+            top = float(np.abs(a).max())
+            bound = max(float(np.abs(b - a).max()), 2.0 ** -24 * top)
+            assert bound <= PC.POSED_CAP * top, (name, out, bound / top)
+            worst[out] = max(worst.get(out, 0.0), bound / top)
+    print(f"  {name}: " + ", ".join(f"{k} {v:.2g}" for k, v in worst.items()))
+    # the edge is there: what each case is named after, in the fp64 reference
+    gru = lambda p, n: np.asarray(p["rnn.cell." + n], np.float64)
+    if name == "saturated_gates":
+        assert all(np.abs(gru(p, "weight_hh")).max() > 4 for p in (actor, critic))
+        s = PC.references(name)[0][0]["actor_state"]
+        assert (np.abs(s) > 0.999).mean() > 0.05                 # n = tanh(+-large) behind z ~ 0
+    if name == "large_state":
+        assert float(np.abs(ha).max()) > 100 and float(np.abs(hc).max()) > 100
+    if name == "large_obs":
+        assert float(np.abs(obs[0]["state_self"]).max()) > 300
+
+
+@pytest.mark.parametrize("name", ["carry", "near_flat_norm"])
+def test_the_carry_cases_update_gate_is_exactly_one_in_fp32(name):
+    """The smallest fp64 z pre-activation over all rows and steps is >= 18: expf(-a) < 2^-24, 1 + expf(-a) rounds to 1 and the fp32 gate is
+    exactly 1, so h' = (1 - 1) n + 1 h = h bit for bit (n is finite: a tanh).  near_flat_norm: the sum h0 + f the norm sees is 0.3 within a
+    few 1e-2."""
+    actor, critic, obs, eps, flags, ha, hc = PC.case(name)
+    t64 = lambda p: {k: torch.as_tensor(np.asarray(v)).double() for k, v in p.items()}
+    smallest = np.inf
+    for p, prefix, key, h0 in ((t64(actor), "encoder.", "actor_state", ha), (t64(critic), "base.", "critic_state", hc)):
+        h = torch.as_tensor(h0).double()
+        for t in range(len(obs)):
+            f = R.encoder(p, prefix, {k: torch.as_tensor(v) for k, v in obs[t].items()}, torch.float64)
+            h = h * torch.as_tensor(~flags[t]).double().reshape(-1, 1, 1)
+            a_z = (f @ p["rnn.cell.weight_ih"][128:256].T + p["rnn.cell.bias_ih"][128:256]
+                   + h @ p["rnn.cell.weight_hh"][128:256].T + p["rnn.cell.bias_hh"][128:256])
+            smallest = min(smallest, float(a_z.min()))
+            if name == "near_flat_norm" and t == 0:
+                flat = (h + f).numpy()
+                assert np.abs(flat - 0.3).max() < 0.06 and flat.std(-1).max() < 0.02
+            h = torch.as_tensor(PC.references(name)[t][0][key])
+            want = h0 if t == 0 else PC.references(name)[t - 1][0][key]
+            keep = ~flags[t]
+            assert np.abs(h.numpy()[keep] - np.asarray(want, np.float64)[keep]).max() < 1e-7        # fp64: z = 1 - 1e-11
+    print(f"  {name}: smallest z pre-activation {smallest:.2f}")
+    assert smallest >= 18
+    a = torch.tensor(18.0)
+    assert float(torch.exp(-a)) < 2.0 ** -24 and float(1.0 / (1.0 + torch.exp(-a))) == 1.0
+
+
+def test_the_kernels_algorithm_in_fp32_passes_the_gate_on_every_committed_case():
+    """No defect: the emulation stays under the bar at every step of every chain the device gate runs — the goldens, the four old shapes, the
+    sweep, the full tiles, the straddle shapes, the edges and the first 8 steps of the long chain — sampling and at the mode.  Measured worst
+    ratio 2.62 (saturated_gates; saturated_softmax 1.68, the sweep 1.89)."""
+    worst = 0.0
+    for tag in PC.CASE_TAGS:
+        ratios, det = _emulate_chain(tag), _emulate_chain(tag, mode=True)
+        for name in RR.OUTPUTS:
+            assert ratios[name] <= RR.BAR and det[name] <= RR.BAR, (tag, name, ratios, det)
+        worst = max(worst, *ratios.values(), *det.values())
+    print(f"  emulate_step, no defect: worst ratio {worst:.2f} of {RR.BAR} over {len(PC.CASE_TAGS)} chains")
+
+
+def test_a_null_state_all_flags_and_zeros_are_one_thing_to_the_emulation():
+    actor, critic, obs, eps, flags, ha, hc = PC.case("random-e11a3k5d35")
+    zeros = RR.emulate_step(actor, critic, obs[0], np.zeros_like(ha), np.zeros_like(hc), None, eps[0])
+    nan = np.full_like(ha, np.nan)
+    for other in (RR.emulate_step(actor, critic, obs[0], None, None, flags[0], eps[0]),
+                  RR.emulate_step(actor, critic, obs[0], nan, nan, np.ones(11, bool), eps[0])):        # a flagged row's state is not read
+        for name in RR.OUTPUTS + ("action",):
+            assert np.array_equal(zeros[name], other[name]), name
+
+
+# defect -> the committed chain that must fail the gate with it, and the output it fails on.  Measured ratios (bar 8; worst over the chain's
+# steps), named case / weakest failing case / cases that still pass, of the 53 chains:
+#   flag_env_split_division        straddle-e40a3k5d35 1.4e6 / flat_tokens 3.0e4 / 26: the goldens, the four old shapes, the first 8 steps of the
+#                                  long chain (33 rows) and every sweep and full-tile chain in which no tile with a flagged env starts
+#                                  inside an env (A 1, 2, 4; one tile; A 5 to 7 over two tiles with the flags elsewhere) — fails on all four
+#                                  straddle shapes (> 1e6), all seven edges (A = 3 over five and six tiles), 15 sweep chains and the 96-row full-tile chain
+#   flag_by_row                    near_flat_norm 1.6e7 / flat_tokens 3.4e4 / the nine A = 1 chains (row == env)
+#   hh_rz_swapped                  large_state 2.8e6 / flat_tokens 3.0e4 / carry, near_flat_norm (z is 1 with either matrix: the state is
+#                                  carried and the norm never sees r)
+#   bhh_rz_dropped                 a1k5d20 8.2e5 / flat_tokens 4.4e3 / carry, near_flat_norm
+#   bhn_outside_r                  a3k5d35 6.3e5 / flat_tokens 5.2e3 / carry, near_flat_norm
+#   blend_with_unmasked_h          carry 2.0e7 / flat_tokens 3.4e4 / none
+#   mask_after_cell                random-e11a3k5d35 1.5e6 / flat_tokens 2.4e4 / carry, near_flat_norm (h' = h masked before or after)
+#   norm_of_old_state              full-e32a2k3d20 2.6e6 / flat_tokens 1.9e4 / carry, near_flat_norm (h' = h)
+#   norm_eps_0                     near_flat_norm 3.8e3 / straddle-e40a5k5d35 9.4 / flat_tokens, saturated_softmax, saturated_gates,
+#                                  large_state; between 9 and 30 on every ordinary chain (17 to 19 on the old shapes)
+#   norm_unbiased_variance         sweep-30-e6a5k7d11 2.2e4 / flat_tokens 206 / none
+#   critic_flags_ignored           saturated_gates 4.1e4 / flat_tokens 2.7e4 / none
+#   critic_norm_affine_from_actor  long-first8 8.7e5 / flat_tokens 5.2e3 / the goldens (both GRUs carry g_gru.npz's one LayerNorm affine)
+#   critic_hh_from_actor_state     random-e1a3k5d35 3.0e6 / flat_tokens 3.1e4 / carry, near_flat_norm
+# (flat_tokens is the weakest nearly everywhere because its bound is the largest: e_32 of 3e-5 to 5e-5 of the outputs' size.)
+DEFECT_TABLE = {
+    "flag_env_split_division": ("straddle-e40a3k5d35", "actor_state"),
+    "flag_by_row": ("near_flat_norm", "actor_state"),
+    "hh_rz_swapped": ("large_state", "value"),
+    "bhh_rz_dropped": ("a1k5d20", "actor_state"),
+    "bhn_outside_r": ("a3k5d35", "actor_state"),
+    "blend_with_unmasked_h": ("carry", "critic_state"),
+    "mask_after_cell": ("random-e11a3k5d35", "actor_state"),
+    "norm_of_old_state": ("full-e32a2k3d20", "value"),
+    "norm_eps_0": ("near_flat_norm", "loc"),
+    "norm_unbiased_variance": (PC.sweep_tag(30), "value"),
+    "critic_flags_ignored": ("saturated_gates", "critic_state"),
+    "critic_norm_affine_from_actor": (PC.LONG_CPU_TAG, "value"),
+    "critic_hh_from_actor_state": ("random-e1a3k5d35", "critic_state"),
+}
+
+
+def test_the_defect_table_names_every_defect():
+    assert set(DEFECT_TABLE) == set(RR.DEFECTS) and len(RR.DEFECTS) == 13
+    assert all(tag in PC.CASE_TAGS and name in RR.OUTPUTS for tag, name in DEFECT_TABLE.values())
+    assert DEFECT_TABLE["flag_env_split_division"][0] in PC.STRADDLE_TAGS and DEFECT_TABLE["norm_eps_0"][0] == "near_flat_norm"
+
+
+@pytest.mark.parametrize("defect", RR.DEFECTS)
+def test_each_seeded_defect_fails_the_gate_on_its_named_case(defect):
+    """A subtly wrong kernel does not pass: the same emulation with ONE defect exceeds the bar on the named chain and output; the number of
+    chains it fails on, the weakest of them and the ones it still passes are printed."""
+    tag, name = DEFECT_TABLE[defect]
+    assert max(_emulate_chain(tag).values()) <= RR.BAR
+    ratios = _emulate_chain(tag, defect)
+    assert ratios[name] > RR.BAR, (defect, tag, ratios)
+    worst = {t: max(_emulate_chain(t, defect).values()) for t in PC.CASE_TAGS}
+    failing = {t: r for t, r in worst.items() if r > RR.BAR}
+    weakest = min(failing, key=failing.get)
+    print(f"  {defect}: {tag} {name} {ratios[name]:.3g}; fails on {len(failing)} of {len(worst)} chains, weakest {weakest} {failing[weakest]:.3g}; "
+          f"passes {[t for t in worst if t not in failing]}")
+
+
+def test_the_split_division_passes_the_four_old_shapes_and_fails_every_straddle_shape():
+    """The hole the straddle shapes close: reading the flag of row row0 + r at env row0 / A + r / A gives the same answers wherever the tiles
+    that hold live rows past r = 0 start on an env boundary — the goldens and all four shapes of test_hip_policy_rnn.py (3, 33, 5, 21 rows)."""
+    for tag in list(RR.CASES) + PC.OLD_SHAPE_TAGS:
+        clean, split = _emulate_chain(tag), _emulate_chain(tag, "flag_env_split_division")
+        assert split == clean and max(split.values()) <= RR.BAR, tag
+    for tag in PC.STRADDLE_TAGS:
+        assert max(_emulate_chain(tag).values()) <= RR.BAR
+        assert min(_emulate_chain(tag, "flag_env_split_division")[n] for n in ("actor_state", "critic_state", "loc", "value")) > 1e3 * RR.BAR, tag
