@@ -14,6 +14,10 @@ recomputed log-probabilities are the collected ones up to rounding: the script p
 The losses are the reference's clipped PPO surrogate with an entropy bonus and the clipped Huber value loss; the targets come from
 gae.rollout_targets with the bootstrap value of ONE value_only call on the last next observation, the stored last critic state and flags.
 
+--learner: train through `learner.RecurrentDeviceLearner` instead of the torch loop below — one `train_rollout` per rollout (the bootstrap
+value, the targets, the env's trajectory predictor (on the device), `--updates` PPO epochs of 4 minibatches of segments through rnn_train.update_actor_rnn / update_critic_rnn: the head and
+the loss in HIP too, two optimisers, no host synchronisation in the loop) — and print the reference's info row.
+
 --eval: after training, one seeded deterministic episode through `DeviceEvaluator(env, pol, collector=col)` — the actor alone with its state
 carried on the device (`RecurrentDevicePolicy.act_step`), the `eval/stats.*` means printed."""
 import argparse
@@ -27,7 +31,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import hns_amd  # noqa: E402,F401
 from hns_amd import collector, evaluator, gae, policy  # noqa: E402
 from hns_amd.encoder import AttentionEncoder  # noqa: E402
-from hns_amd.learner import ValueNorm1  # noqa: E402
+from hns_amd.learner import RecurrentDeviceLearner, ValueNorm1  # noqa: E402
 from hns_amd.rnn import GRU  # noqa: E402
 from hns_amd.tensordict_shim import TensorDict  # noqa: E402
 
@@ -104,6 +108,7 @@ def main():
     ap.add_argument("--envs", type=int, default=256)
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--updates", type=int, default=4)
+    ap.add_argument("--learner", action="store_true", help="train through RecurrentDeviceLearner (one train_rollout per rollout) instead of the torch loop")
     ap.add_argument("--eval", action="store_true", help="after training: one deterministic episode, the eval/stats.* means")
     args = ap.parse_args()
     if args.steps % SEQ:
@@ -126,8 +131,16 @@ def main():
     vn = ValueNorm1().to(dev)
     huber = nn.HuberLoss(delta=10.0)
     steps_of = torch.arange(SEQ, device=dev)
+    lrn = None
+    if args.learner:
+        cfg = {"ppo_epochs": args.updates, "num_minibatches": 4, "actor": {"rnn": {"train_seq_len": SEQ}}, "critic": {"rnn": {"train_seq_len": SEQ}}}
+        lrn = RecurrentDeviceLearner(actor.names(), critic.names(), cfg, tp_net=getattr(env, "TP", None), value_normalizer=vn, device_policy=pol)
     for it in range(2):
         st = col.collect()
+        if lrn is not None:
+            info = lrn.train_rollout(**st.learner_kwargs(), **st.recurrent_kwargs())
+            print(f"rollout {it}: " + "  ".join(f"{k.split('/')[-1]} {v:+.5f}" for k, v in info.items()))
+            continue
         kw, rk = st.learner_kwargs(), st.recurrent_kwargs()
         N, T = kw["reward"].shape[:2]
         S = T // SEQ

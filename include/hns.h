@@ -782,6 +782,54 @@ int hns_policy_forward_rnn(const void *packed, const void *rnn_packed, int32_t s
  * misaligned (16 bytes) actor_h_in. */
 int hns_policy_act_rnn(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
                        const hns_policy_io *io, const hns_policy_rnn_io *rio, void *stream);
+/*
+ * The head and the loss of a recurrent update over hns_gru_forward's output, forward and backward (hns_amd.rnn_train): what a
+ * recurrent learner runs between hns_gru_forward and hns_gru_backward.  A minibatch is B segments x L steps x A agents; row (b, t, a), row index
+ * (b L + t) A + a, reads the 128 values at y + b y_stride[0] + a y_stride[1] + t y_stride[2] (hns_gru_seq.x_stride's three strides: the op's
+ * [B, A, L, 128] view of [B L A, 128] is {L A 128, 128, A 128}, a plain [S, L, 128] is {L 128, 0, 128} with inner 1) and its per-row data at
+ * env-step e = segment[b] L + t of the rollout's contiguous [N T, A(, 4)] arrays, i.e. element e A + a.  segment: int64 [B] ids into the
+ * flattened [N, T / L], NULL for 0 .. B - 1; num_segments = N T / L.  A segment id outside [0, num_segments) contributes nothing (the
+ * convention of hns_critic_batch.index): its per-row data is not read, its L A rows of dy are written as zeros, it is left out of every sum, and
+ * n stays B L A.  y and dy are addressed by b alone: nothing is read or written out of bounds through a bad id.  dy has y's strides.
+ * Properties of both entries: one stream, no host synchronisation, no allocation, capturable; no float atomics; the same inputs give the same
+ * bits; the workspace is used from scratch (it may be dirty).  Order of every sum: a workgroup is 32 row groups of 8 lanes and takes TRIPS of 32
+ * consecutive rows; with G = min(ceil(B L A / 32), 512) workgroups, workgroup w takes trips w, w + G, ...; a row group adds its rows trip after
+ * trip (head-gradient products in fp32, loss terms in fp64), the workgroup's partial is its 32 row groups added in index order in fp64 (in the
+ * workspace), and the G partials are added in index order in fp64 and rounded once to fp32.  A row's 128-wide dot product is, per lane g of
+ * its group, the fmaf chain over features 4 g + 32 i + u (i, then u, ascending), then s += s[lane ^ 1], [lane ^ 2], [lane ^ 4].
+ * Refused before any launch, with the error string set: a NULL rows struct; outer < 1, inner outside [1, 7], steps outside
+ * [1, HNS_GRU_MAX_STEPS]; a NULL or misaligned pointer (16 bytes for y, dy and the head's tensors; 8 for segment; 4 for the per-row arrays, the
+ * gradients and the scalars); a negative y stride or one that is no multiple of 4; a negative num_segments; a bad clip_param / loss_kind /
+ * huber_delta; a workspace that is NULL, not 256-byte aligned or shorter than the size function's bytes (which are 0 for an invalid shape).
+ *
+ * hns_rnn_actor_head_grad: fc_mean (head_w [4, 128], head_b [4]) and log_std [4] on y.  Per row mu = W y + b, logp (formed in fp64 from the
+ * fp32 mu) and the ratio r as hns_actor_train_grad states them; the backward weight of min and clamp is that entry's: 1 inside the clip
+ * (bounds included), outside 1 where the unclipped surrogate is the smaller and 0 otherwise.  dy: the gradient of policy_loss - entropy_coef
+ * entropy with respect to y; d_head_w [4, 128], d_head_b [4], d_log_std [4]: WRITTEN (not accumulated), PyTorch layouts;
+ * policy_loss = -4 mean(min(r adv, clamp(r) adv)); entropy; ess as the reference writes it for [B, L, A, 1] ratios: the mean over the L A
+ * (step, agent) columns of exp(2 logsumexp_b(r) - logsumexp_b(2 r)), divided by B; log_probs: [B, L, A] or NULL.  Three launches.
+ * hns_rnn_critic_head_grad: v_out (head_w [1, 128], head_b [1]).  hns_critic_train_grad's statements: value_loss = max(mean loss(b_returns, v),
+ * mean loss(b_returns, b_values + clamp(v - b_values, +-clip_param))), one branch for the whole minibatch, both by halves at an exact tie;
+ * explained_var = 1 - mse(v, b_returns) / var(b_returns) (unbiased); values: [B, L, A] or NULL.  y is read twice (values and sums, then dy after
+ * the decision).  Four launches.
+ */
+typedef struct hns_rnn_rows {
+    const float *y;            /* row (b, t, a) at y + b y_stride[0] + a y_stride[1] + t y_stride[2], 128 contiguous values */
+    int64_t y_stride[3];
+    int64_t outer, inner;      /* B segments, A agents */
+    int32_t steps;             /* L in [1, HNS_GRU_MAX_STEPS] */
+    const int64_t *segment;    /* [B] ids into the flattened [N, T / L], or NULL: 0 .. B - 1 */
+    int64_t num_segments;      /* N T / L */
+} hns_rnn_rows;
+size_t hns_rnn_actor_head_workspace_bytes(int64_t outer, int32_t inner, int32_t steps);
+size_t hns_rnn_critic_head_workspace_bytes(int64_t outer, int32_t inner, int32_t steps);
+int hns_rnn_actor_head_grad(const float *head_w, const float *head_b, const float *log_std, const hns_rnn_rows *rows, const float *action,
+                            const float *log_probs_old, const float *advantages, double clip_param, double entropy_coef, float *dy, float *d_head_w,
+                            float *d_head_b, float *d_log_std, float *policy_loss, float *entropy, float *ess, float *log_probs, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int hns_rnn_critic_head_grad(const float *head_w, const float *head_b, const hns_rnn_rows *rows, const float *b_values, const float *b_returns,
+                             float clip_param, int32_t loss_kind, float huber_delta, float *dy, float *d_head_w, float *d_head_b, float *value_loss,
+                             float *explained_var, float *values, void *workspace, size_t workspace_bytes, void *stream);
 /* The 2-norm of one flat fp32 gradient bucket: norm[0] = f32(sqrt(sum_i flat[i]^2)), in this order (tests/dp_reference.py restates it in numpy):
  * the bucket is cut into quads of four consecutive floats, the last one short by numel % 4 values that count as 0 (nothing past numel is
  * read); G = clamp(ceil(quads / 1024), 1, 64) workgroups of 256 threads, T = 256 G; thread t of the grid adds, for q = t, t + T, t + 2 T, ...,

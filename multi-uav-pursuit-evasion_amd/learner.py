@@ -17,6 +17,10 @@ stays, and the finished info row crosses to the host in one copy.  The two updat
 shape and reused by all ppo_epochs x num_minibatches calls.  CPU tensors run the same driver over the modules' CPU paths (CPU tests, gloo
 runs — not the hot path).  DESIGN.md §7.6.
 
+`RecurrentDeviceLearner` is the same driver for the `actor.rnn` / `critic.rnn` configuration: the bootstrap value from the stored
+last critic state, the PPO loop over (env, segment) pairs through rnn_train.update_actor_rnn / update_critic_rnn.  `DeviceLearner` itself keeps
+refusing a recurrent policy.
+
 `DeviceLearner(..., group=)` is the data-parallel learner: W ranks, each with the rollout of its own env slice, perform ONE
 PPO update per minibatch on the union of their minibatches — the critic's branch decided on the union's sums, every mean over the union's
 rows, the norm taken from the summed gradient, the predictor's ranks weighted by their selected windows."""
@@ -26,7 +30,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import abi, actor_train, critic_train, gae, sharding, tp_train
+from . import abi, actor_train, critic_train, gae, rnn_train, sharding, tp_train
 from . import policy as P
 from . import policy_train as PT
 
@@ -104,6 +108,19 @@ class DeviceLearner:
         if getattr(device_policy, "recurrent", False):
             raise P.PolicyConfigError("DeviceLearner updates the non-recurrent networks only: a recurrent policy (actor.rnn / critic.rnn) is trained "
                                       "in torch over encoder.encode -> rnn.gru -> head (examples/recurrent_policy.py)")
+        self._configure(actor, critic, cfg, tp_net, value_normalizer, agent_name, generator)
+        self.actor_opt = actor_train.make_optimizer(actor, cfg)
+        self.critic_opt = critic_train.make_optimizer(critic, cfg)
+        self.policy = device_policy if device_policy is not None else P.DevicePolicy(actor, critic, cfg, agent_name=agent_name)
+        self.group = sharding.resolve_group(group)
+        if self.group is not None:
+            self.world = torch.distributed.get_world_size(self.group)
+            self._make_buckets()
+            self._broadcast_state()
+
+    def _configure(self, actor, critic, cfg, tp_net, value_normalizer, agent_name, generator):
+        """What every learner holds whatever its networks: the objects, train_op's settings from the algo cfg, the predictor's optimiser, the
+        workspace cache.  The two networks' optimisers, the policy and the group are the constructor's."""
         get = PT.getter(cfg)
         self.cfg, self.agent_name, self.generator = cfg, agent_name, generator
         self.actor, self.critic, self.tp_net, self.value_normalizer = actor, critic, tp_net, value_normalizer
@@ -114,18 +131,11 @@ class DeviceLearner:
         self.use_tp = tp_net is not None and bool(get("use_TP_net", 1))
         if self.ppo_epochs < 1 or self.num_minibatches < 1 or (self.use_tp and self.tp_epochs < 1):
             raise ValueError("ppo_epochs, num_minibatches and TP_epochs must be >= 1")
-        self.actor_opt = actor_train.make_optimizer(actor, cfg)
-        self.critic_opt = critic_train.make_optimizer(critic, cfg)
         self.tp_opt = tp_train.TPAdam(tp_train.parameters(tp_net), lr=1e-4) if tp_net is not None else None
-        self.policy = device_policy if device_policy is not None else P.DevicePolicy(actor, critic, cfg, agent_name=agent_name)
         self.n_updates = 0
         self._ws = {}
-        self.group = sharding.resolve_group(group)
+        self.group = None
         self.actor_bucket = self.critic_bucket = self.tp_bucket = None
-        if self.group is not None:
-            self.world = torch.distributed.get_world_size(self.group)
-            self._make_buckets()
-            self._broadcast_state()
 
     # ---- the data-parallel path's state
     def _optimizer_makers(self):
@@ -202,7 +212,10 @@ class DeviceLearner:
     # ---- the reference's entry point
     def train_op(self, tensordict):
         """MAPPOPolicy.train_op on the collector's [N, T] tensordict; returns {"<agent>/policy_loss": float, ...}."""
-        td = tensordict
+        return self.train_rollout(**self._rollout_kwargs(tensordict))
+
+    def _rollout_kwargs(self, td):
+        """train_rollout's keyword arguments from the reference's tensordict keys."""
         obs = td[("agents", "observation")]
         nxt = td["next"]
         last = nxt[("agents", "observation")]
@@ -213,7 +226,7 @@ class DeviceLearner:
             t = nxt[("agents", "TP")]
             tp = (t["TP_input"], t["TP_groundtruth"], t["TP_done"])
         xo_last = pick(last, "state_others")
-        return self.train_rollout(
+        return dict(
             obs_self=obs["state_self"], obs_others=pick(obs, "state_others"), obs_cylinders=obs["cylinders"], action=td[("agents", "action")],
             log_probs=td[f"{self.agent_name}.action_logp"], state_value=td["state_value"],
             next_obs_last=(last["state_self"][:, -1], xo_last[:, -1] if xo_last is not None else None, last["cylinders"][:, -1]),
@@ -224,6 +237,11 @@ class DeviceLearner:
         """train_op on tensors: observations [N, T, A, ...], action [N, T, A, 4], log_probs / state_value [N, T, A, 1], next_obs_last: the
         (state_self, state_others, cylinders) of the last step's next observation [N, A, ...], reward [N, T, A, r], done [N, T, 1] (the env's),
         agent_done [N, T, A, 1] or None, tp: (TP_input, TP_groundtruth, TP_done) with the predictor."""
+        return self._run(None, obs_self, obs_others, obs_cylinders, action, log_probs, state_value, next_obs_last, reward, done, agent_done, tp)
+
+    def _run(self, recurrent, obs_self, obs_others, obs_cylinders, action, log_probs, state_value, next_obs_last, reward, done, agent_done, tp):
+        """train_rollout's blocks.  `recurrent`: None, or what a recurrent learner's two hooks (_bootstrap_value, _ppo_loop) need beside the
+        rollout — handed down to them untouched."""
         if self.use_tp and tp is None:
             raise ValueError("use_TP_net: the rollout's TP_input, TP_groundtruth and TP_done are needed (tp=)")
         xs, xo, xc = PT.as_rollout(obs_self, obs_others, obs_cylinders)
@@ -235,7 +253,7 @@ class DeviceLearner:
         if agent_done is not None:
             dones = agent_done | dones
         with torch.no_grad():
-            next_value = self.policy.forward(*next_obs_last, value_only=True).value
+            next_value = self._bootstrap_value(next_obs_last, recurrent)
         adv, ret, _, (adv_mean, adv_std) = gae.rollout_targets(reward, dones, state_value, next_value, self.gamma, self.gae_lambda,
                                                                value_normalizer=self.value_normalizer, normalize_advantages=self.normalize_advantages,
                                                                return_moments=True)
@@ -246,7 +264,7 @@ class DeviceLearner:
                                          **(dict(group=self.group, bucket=self.tp_bucket) if self.group is not None else {}))
         M = self.ppo_epochs * self.num_minibatches
         table = torch.empty(M, len(COLUMNS), dtype=torch.float32, device=dev)
-        self._ppo_loop(xs, xo, xc, action, log_probs, adv, state_value, ret, table, global_rows)
+        self._ppo_loop(xs, xo, xc, action, log_probs, adv, state_value, ret, table, global_rows, recurrent)
         extras = [t.reshape(()).to(torch.float32) for t in ([tp_loss] if self.use_tp else []) + [adv_mean, adv_std]]
         if self.value_normalizer is not None:
             extras.append(self.value_normalizer.running_mean.mean().to(torch.float32))
@@ -272,7 +290,11 @@ class DeviceLearner:
         self.n_updates += 1
         return {f"{self.agent_name}/{k}": info[k] for k in INFO_KEYS if k in info}
 
-    def _ppo_loop(self, xs, xo, xc, action, log_probs, adv, state_value, ret, table, global_rows=None):
+    def _bootstrap_value(self, next_obs_last, recurrent=None):
+        """mappo.py:365-367: the critic's value of the last step's next observation, ONE value_only call."""
+        return self.policy.forward(*next_obs_last, value_only=True).value
+
+    def _ppo_loop(self, xs, xo, xc, action, log_probs, adv, state_value, ret, table, global_rows=None, recurrent=None):
         """mappo.py:446-461: per epoch one permutation, per minibatch the actor's update and then the critic's.  On the device: no host
         synchronisation — cached workspaces, scalars written into `table`'s rows, no index check.  `global_rows` (the data-parallel path):
         the updates' global forms over the group, their gradients in the two buckets."""
@@ -360,3 +382,111 @@ class DeviceLearner:
                 getattr(self, name).load_state_dict(sd[key])
         if self.group is not None:                               # one state on every rank: rank 0's
             self._broadcast_state()
+
+
+class RecurrentDeviceLearner(DeviceLearner):
+    """MAPPOPolicy's training half with actor.rnn / critic.rnn: `DeviceLearner`'s blocks in its order, with the recurrent pieces in place.
+
+    actor, critic: the networks' parameters under the reference's names with their `rnn.*` tensors (what RecurrentDevicePolicy parses) — live
+    tensors, updated in place; cfg: the algo cfg (actor.rnn.train_seq_len: the segment length L, default 16); device_policy: a
+    RecurrentDevicePolicy over the same tensors (built when None).  Two ClippedAdams, one per network as the reference holds them, each
+    over the encoder's, the GRU's and the head's tensors; the predictor's TPAdam.
+
+        next_value  ONE policy.forward(..., critic_state=last_critic_rnn_state, is_init=last_is_init, value_only=True)
+        targets     gae.rollout_targets, exactly DeviceLearner's call
+        predictor   tp_train.update_tp, unchanged (the reference groups the predictor's windows in runs of seq_len before it permutes them; the
+                    loss is a mean over windows, so only which windows share a minibatch differs)
+        PPO loop    per epoch ONE permutation of the N T / L segments (make_dataset_naive's randperm((N S // M) M).reshape(M, -1), the same
+                    generator calls), per minibatch rnn_train.update_actor_rnn, then update_critic_rnn; on the device no host
+                    synchronisation, the scalars land in the rows of the [M, 7] table, every buffer is kept per network between calls
+        info row    hns_learner_info, INFO_KEYS, one copy to the host
+
+    Refused: group= (data-parallel recurrent training), the configurations RecurrentDevicePolicy refuses, a non-recurrent device_policy, a
+    rollout whose T train_seq_len does not divide (or whose storage was cut with another segment length)."""
+
+    def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, generator=None, device_policy=None, agent_name="drone", group=None):
+        if group is not None:
+            raise NotImplementedError("RecurrentDeviceLearner: data-parallel recurrent training (group=) is not supported")
+        if device_policy is not None and not getattr(device_policy, "recurrent", False):
+            raise P.PolicyConfigError("RecurrentDeviceLearner needs a RecurrentDevicePolicy (a non-recurrent policy is DeviceLearner's)")
+        self._configure(actor, critic, cfg, tp_net, value_normalizer, agent_name, generator)
+        self.train_seq_len = rnn_train.train_seq_len(cfg)
+        if not 1 <= self.train_seq_len <= abi.HNS_GRU_MAX_STEPS:
+            raise ValueError(f"actor.rnn.train_seq_len must be in [1, {abi.HNS_GRU_MAX_STEPS}], not {self.train_seq_len}")
+        self.actor_opt = rnn_train.make_optimizer(actor, cfg, actor=True)          # (the refusals of the cfg and of the parameters come first)
+        self.critic_opt = rnn_train.make_optimizer(critic, cfg, actor=False)
+        self.policy = device_policy if device_policy is not None else P.RecurrentDevicePolicy(actor, critic, cfg, agent_name=agent_name)
+        self._rnn_ws = (rnn_train.RnnWorkspace(), rnn_train.RnnWorkspace())
+
+    def _optimizer_makers(self):
+        return (("actor_opt", "actor_opt", lambda: rnn_train.make_optimizer(self.actor, self.cfg, actor=True)),
+                ("critic_opt", "critic_opt", lambda: rnn_train.make_optimizer(self.critic, self.cfg, actor=False)),
+                ("tp_opt", "TP_opt", lambda: tp_train.TPAdam(tp_train.parameters(self.tp_net), lr=1e-4)))
+
+    def release(self):
+        super().release()
+        for ws in self._rnn_ws:
+            ws.release()
+
+    def train_op(self, tensordict):
+        """MAPPOPolicy.train_op on the collector's [N, T] tensordict with the reference's recurrent keys: "is_init" [N, T, 1] and
+        "<agent>.actor_rnn_state" / "<agent>.critic_rnn_state" — the state going INTO every step [N, T, A, 128] (every train_seq_len-th
+        step's is the segment's; a [N, T / L, A, 128] tensor is taken as it is) — and, under "next", the critic state and "is_init" (absent:
+        "done") after the last step."""
+        td, L = tensordict, self.train_seq_len
+        nxt = td["next"]
+        ka, kc = f"{self.agent_name}.actor_rnn_state", f"{self.agent_name}.critic_rnn_state"
+        T = td["is_init"].shape[1]
+        seg = lambda t: t if t.shape[1] * L == T and L > 1 else t[:, ::L].contiguous()          # noqa: E731
+        nget = lambda k: nxt.get(k, None) if hasattr(nxt, "get") else nxt[k]                     # noqa: E731
+        last_init = nget("is_init")
+        return self.train_rollout(**self._rollout_kwargs(td), is_init=td["is_init"], actor_rnn_state=seg(td[ka]), critic_rnn_state=seg(td[kc]),
+                                  rnn_seq_len=L, last_critic_rnn_state=nxt[kc][:, -1].contiguous(),
+                                  last_is_init=(last_init if last_init is not None else nxt["done"])[:, -1])
+
+    def train_rollout(self, *, obs_self, obs_others, obs_cylinders, action, log_probs, state_value, next_obs_last, reward, done, agent_done=None,
+                      tp=None, is_init=None, actor_rnn_state=None, critic_rnn_state=None, rnn_seq_len=None, last_critic_rnn_state=None,
+                      last_is_init=None):
+        """train_op on tensors: RolloutStorage.learner_kwargs() (DeviceLearner.train_rollout's arguments) and recurrent_kwargs() — is_init
+        [N, T, 1]; actor_rnn_state, critic_rnn_state [N, T / L, A, 128]: the states going into every segment; rnn_seq_len: the storage's
+        segment length (must be train_seq_len); last_critic_rnn_state [N, A, 128] and last_is_init [N, 1]: what goes into the step after
+        the last one."""
+        rk = dict(is_init=is_init, actor_rnn_state=actor_rnn_state, critic_rnn_state=critic_rnn_state, last_critic_rnn_state=last_critic_rnn_state,
+                  last_is_init=last_is_init)
+        missing = [k for k, v in rk.items() if v is None]
+        if missing:
+            raise ValueError(f"a recurrent rollout needs {missing} (RolloutStorage.recurrent_kwargs())")
+        L = self.train_seq_len
+        if rnn_seq_len is not None and int(rnn_seq_len) != L:
+            raise ValueError(f"the rollout was stored in segments of {rnn_seq_len} steps, actor.rnn.train_seq_len is {L}")
+        N, T = is_init.shape[:2]
+        if T % L:
+            raise ValueError(f"train_seq_len {L} does not divide the rollout's {T} steps")
+        if (T // L) * N < self.num_minibatches:
+            raise ValueError(f"the rollout holds {(T // L) * N} segments, fewer than num_minibatches {self.num_minibatches}")
+        return self._run(rk, obs_self, obs_others, obs_cylinders, action, log_probs, state_value, next_obs_last, reward, done, agent_done, tp)
+
+    def _bootstrap_value(self, next_obs_last, recurrent=None):
+        return self.policy.forward(*next_obs_last, critic_state=recurrent["last_critic_rnn_state"], is_init=recurrent["last_is_init"],
+                                   value_only=True).value
+
+    def _ppo_loop(self, xs, xo, xc, action, log_probs, adv, state_value, ret, table, global_rows=None, recurrent=None):
+        """mappo.py:446-461 over segments: per epoch one permutation of the N T / L (env, segment) pairs, per minibatch the actor's update
+        and then the critic's; each network's gradients in one GradBucket the learner holds."""
+        rk, L = recurrent, self.train_seq_len
+        N, T = xs.shape[:2]
+        cuda = xs.device.type == "cuda"
+        ws_a, ws_c = self._rnn_ws if cuda else (None, None)
+        if cuda and self.actor_bucket is None:
+            self.actor_bucket, self.critic_bucket = rnn_train.make_bucket(self.actor, True), rnn_train.make_bucket(self.critic, False)
+        kb_a, kb_c = (dict(bucket=self.actor_bucket), dict(bucket=self.critic_bucket)) if cuda else ({}, {})
+        m = 0
+        for _ in range(self.ppo_epochs):
+            for idx in tp_train.minibatches(N * (T // L), self.num_minibatches, xs.device, self.generator):
+                sa = rnn_train.update_actor_rnn(self.actor, xs, xo, xc, rk["actor_rnn_state"], rk["is_init"], action, log_probs, adv, self.actor_opt,
+                                                segment=idx, cfg=self.cfg, seq_len=L, workspace=ws_a, out=table[m, :len(ACTOR_COLUMNS)] if cuda else None, **kb_a)
+                sc = rnn_train.update_critic_rnn(self.critic, xs, xo, xc, rk["critic_rnn_state"], rk["is_init"], state_value, ret, self.critic_opt,
+                                                 segment=idx, cfg=self.cfg, seq_len=L, workspace=ws_c, out=table[m, len(ACTOR_COLUMNS):] if cuda else None, **kb_c)
+                if not cuda:                                       # CPU: the updates return their scalars
+                    table[m] = torch.stack([(sa | sc)[k].reshape(()).to(torch.float32) for k in COLUMNS])
+                m += 1

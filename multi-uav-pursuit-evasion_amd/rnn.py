@@ -108,17 +108,34 @@ def _stream(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
-def device_forward(p, x4, h0, init, keep):
-    """hns_gru_forward on validated device tensors: (out with x4's strides, h_last [S, 128], h_hist [S, L, 128] or None)."""
+def _buffer(t, shape, what, dev, strides=None):
+    """The caller's buffer for `what`, checked: fp32 on `dev`, 16-byte aligned, of `shape` (contiguous, or with `strides`)."""
+    want = tuple(strides) if strides is not None else None
+    ok = torch.is_tensor(t) and t.dtype == torch.float32 and t.device == dev and tuple(t.shape) == tuple(shape) and t.data_ptr() % 16 == 0
+    if ok and want is not None:
+        ok = all(t.shape[d] == 1 or t.stride(d) == want[d] for d in range(t.dim()))
+    elif ok:
+        ok = t.is_contiguous()
+    if not ok:
+        raise ValueError(f"{what} must be a 16-byte aligned float32 {tuple(shape)} tensor on {dev}" + (f" with strides {want}" if want else ", contiguous"))
+    return t
+
+
+def device_forward(p, x4, h0, init, keep, out=None, h_last=None, h_hist=None):
+    """hns_gru_forward on validated device tensors: (out with x4's strides, h_last [S, 128], h_hist [S, L, 128] or None).  out, h_last,
+    h_hist: the caller's buffers (of those shapes; out with x4's strides) instead of tensors allocated per call."""
     lib = abi.load_library()
     B, A, L, _ = x4.shape
     dev = x4.device
     for f, t in p.items():
         if t.data_ptr() % 16:
             raise ValueError(f"gru parameter {f} must be 16-byte aligned")
-    out = torch.empty_strided(x4.shape, x4.stride(), dtype=torch.float32, device=dev)
-    h_last = torch.empty(B * A, H, dtype=torch.float32, device=dev)
-    hist = torch.empty(B * A, L, H, dtype=torch.float32, device=dev) if keep else None
+    out = _buffer(out, x4.shape, "out", dev, x4.stride()) if out is not None else torch.empty_strided(x4.shape, x4.stride(), dtype=torch.float32, device=dev)
+    h_last = _buffer(h_last, (B * A, H), "h_last", dev) if h_last is not None else torch.empty(B * A, H, dtype=torch.float32, device=dev)
+    if keep:
+        hist = _buffer(h_hist, (B * A, L, H), "h_hist", dev) if h_hist is not None else torch.empty(B * A, L, H, dtype=torch.float32, device=dev)
+    else:
+        hist = None
     net, seq = _net(p), _seq(x4, h0, init)
     with torch.cuda.device(dev):
         rc = lib.hns_gru_forward(C.byref(net), C.byref(seq), out.data_ptr(), h_last.data_ptr(), hist.data_ptr() if keep else None, None, 0, _stream(dev))
@@ -126,16 +143,28 @@ def device_forward(p, x4, h0, init, keep):
     return out, h_last, hist
 
 
-def device_backward(p, x4, h0, init, hist, dout, dh_last, want_dh0):
-    """hns_gru_backward on validated device tensors: ({field: gradient} — views of one allocation, dx with x4's strides, dh0 or None)."""
+def device_backward(p, x4, h0, init, hist, dout, dh_last, want_dh0, workspace=None, flat=None, dx=None):
+    """hns_gru_backward on validated device tensors: ({field: gradient} — views of one allocation, dx with x4's strides, dh0 or None).
+    workspace: a uint8 device tensor of at least hns_gru_workspace_bytes(S, L, 1) bytes, 256-byte aligned; flat: the gradients' flat fp32
+    allocation (grad_layout's floats, 16-byte aligned); dx: a buffer with x4's shape and strides — the caller's instead of per-call ones."""
     lib = abi.load_library()
     B, A, L, _ = x4.shape
     dev = x4.device
     nbytes = lib.hns_gru_workspace_bytes(B * A, L, 1)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    flat = torch.empty(grad_layout()[1], dtype=torch.float32, device=dev)
+    if workspace is None:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    else:
+        ws = workspace
+        if not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < nbytes or ws.data_ptr() % 256:
+            raise ValueError(f"workspace must be a contiguous, 256-byte aligned uint8 tensor of at least {nbytes} bytes on {dev}")
+    n = grad_layout()[1]
+    if flat is None:
+        flat = torch.empty(n, dtype=torch.float32, device=dev)
+    elif (not torch.is_tensor(flat) or flat.dtype != torch.float32 or flat.device != dev or flat.dim() != 1 or flat.numel() < n or not flat.is_contiguous()
+          or flat.data_ptr() % 16):
+        raise ValueError(f"flat must be a contiguous 16-byte aligned float32 vector of at least {n} values on {dev}")
     grads = _views(flat)
-    dx = torch.empty_strided(x4.shape, x4.stride(), dtype=torch.float32, device=dev)
+    dx = _buffer(dx, x4.shape, "dx", dev, x4.stride()) if dx is not None else torch.empty_strided(x4.shape, x4.stride(), dtype=torch.float32, device=dev)
     dh0 = torch.empty(B * A, H, dtype=torch.float32, device=dev) if want_dh0 else None
     net, grd, seq = _net(p), _net(p, grads), _seq(x4, h0, init)
     with torch.cuda.device(dev):

@@ -1,0 +1,450 @@
+"""One recurrent MAPPO update per network on the device: MAPPOPolicy.update_actor / update_critic (learning/mappo.py:271-352) for the
+`actor.rnn` / `critic.rnn` configuration — encoder -> GRU -> head — over the stored sequences of a rollout.
+
+A minibatch is B (env, segment) pairs of L = train_seq_len steps: segment id s of the flattened [N, T / L] starts from its STORED state and
+re-runs its L steps under the stored env-level `is_init` flags, so the recomputed log-probabilities are the collected ones up to rounding.
+`update_actor_rnn` / `update_critic_rnn` run, on one stream and without a host synchronisation:
+
+    encoder.device_forward     index = segment L + t in [B, L] order: the [B L A, 128] features ARE the GRU's [B, A, L, 128] view
+    rnn.device_forward         from the gathered stored state and the flags of the segment's steps, keeping h_hist
+    hns_rnn_*_head_grad        the head, the distribution / value loss and their backward pass down to dy (csrc/hns_rnn_train.hip)
+    rnn.device_backward        dout = dy, no dh_last; dx lands in the encoder op's row order
+    encoder.device_backward    dfeatures = dx: the same memory, no permute copy
+    GradBucket.norm            ONE flat bucket: the encoder's 20 tensors, the GRU's 6 and the head's, in the optimiser's order
+    ClippedAdam.step           clip_grad_norm_ + Adam in one launch
+
+`policy_loss_and_grad_rnn` / `value_loss_and_grad_rnn` are the same calls up to the norm, as actor_train.policy_loss_and_grad is to
+update_actor.  `RnnWorkspace` keeps every buffer of a call between calls (the learner holds one per network).
+
+CPU tensors run the same statements in torch: `policy_train.encoder`, `rnn.restatement`, and `actor_head` / `critic_head` — the head and the
+loss written out with their hand-derived dy (what the kernels compute, not autograd of another formula); the encoder's and the GRU's
+gradients come from autograd over the recomputed restatements, as in `encoder.encode` and `rnn.gru` (tests — not the hot path)."""
+import collections
+import ctypes as C
+import math
+
+import torch
+
+from . import abi, actor_train, critic_train, encoder
+from . import policy as P
+from . import policy_train as PT
+from . import rnn
+from .policy_train import ClippedAdam
+
+H = abi.HNS_GRU_HIDDEN
+LOG_SQRT_2PI = 0.9189385332046727
+ActorLoss, CriticLoss = actor_train.ActorLoss, critic_train.CriticLoss
+Network = collections.namedtuple("Network", ["encoder", "gru", "head"])        # three {field: tensor} mappings of one network
+
+
+def network_parameters(network, actor):
+    """Network(encoder, gru, head) of a recurrent actor (`actor` true) or critic from the reference's names, as RecurrentDevicePolicy parses
+    them: the encoder's tensors by hns_policy_net field in encoder.FIELDS' order, the GRU's six by hns_gru_net field, the head's (head_w,
+    head_b and the actor's log_std).  Their concatenation in this order is the optimiser's and the gradient bucket's order."""
+    word = "actor" if actor else "critic"
+    rest, gru = P.split_rnn(network, word)
+    p = P.parse_parameters(rest, P.ACTOR_NAMES if actor else P.CRITIC_NAMES, word)
+    enc = encoder.encoder_parameters({f: p[f] for f in encoder.FIELDS if f in p})
+    head = {f: p[f] for f in ("head_w", "head_b") + (("log_std",) if actor else ())}
+    return Network(enc, gru, head)
+
+
+def flat_parameters(net):
+    return [*net.encoder.values(), *net.gru.values(), *net.head.values()]
+
+
+def make_optimizer(network, cfg=None, actor=True):
+    """The reference's actor_opt / critic_opt over ALL of a recurrent network's tensors (encoder, rnn, head) as a ClippedAdam: cfg is the
+    algo cfg (actor.lr / critic.lr, max_grad_norm); the refusals are actor_train.actor_cfg's / critic_train.critic_cfg's without the rnn one."""
+    sub = PT.getter(PT.getter(cfg)("actor" if actor else "critic", None))
+    (actor_train.actor_cfg if actor else critic_train.critic_cfg)(_plain_cfg(cfg))
+    return ClippedAdam(flat_parameters(network_parameters(network, actor)), lr=float(sub("lr", 5e-4)), max_grad_norm=PT.getter(cfg)("max_grad_norm", 10.0))
+
+
+def _plain_cfg(cfg):
+    """The algo cfg with the two rnn sections taken out, every other key kept: what the non-recurrent checks are asked about."""
+    if cfg is None:
+        return None
+    get = PT.getter(cfg)
+    keys = list(cfg.keys()) if hasattr(cfg, "keys") else [k for k in vars(cfg) if not k.startswith("_")]
+    out = {}
+    for k in keys:
+        v = get(k)
+        if k in ("actor", "critic") and v is not None:
+            sub = PT.getter(v)
+            v = {kk: sub(kk) for kk in (v.keys() if hasattr(v, "keys") else [a for a in vars(v) if not a.startswith("_")]) if kk != "rnn"}
+        out[k] = v
+    return out
+
+
+# ---- the head and the loss, restated: any dtype (the tests run them in fp64 against autograd of the reference's statements)
+def actor_head(head_w, head_b, log_std, y, action, log_probs_old, advantages, clip_param, entropy_coef):
+    """hns_rnn_actor_head_grad's statements on gathered rows: y [B, L, A, 128], action [B, L, A, 4], log_probs_old / advantages [B, L, A].
+    Returns a dict: dy [B, L, A, 128], d_head_w, d_head_b, d_log_std, policy_loss, entropy, ess (0-dim), log_probs [B, L, A]."""
+    B = y.shape[0]
+    n = float(y.shape[0] * y.shape[1] * y.shape[2])
+    mu = y @ head_w.t() + head_b
+    # logp is formed in fp64 from the fp32 mean (its rounding is the ratio's relative error), as the kernel forms it
+    iv64 = torch.exp(-2.0 * log_std.double())
+    dm64 = action.double() - mu.double()
+    z64 = dm64 * dm64 * iv64
+    logp64 = ((-0.5 * z64 - log_std.double()) - LOG_SQRT_2PI).sum(-1)
+    z2, logp = z64.to(y.dtype), logp64.to(y.dtype)
+    ratio = torch.exp((logp64 - log_probs_old.double()).to(y.dtype))
+    lo, hi = 1.0 - clip_param, 1.0 + clip_param
+    s1, s2 = ratio * advantages, ratio.clamp(lo, hi) * advantages
+    inside = (ratio >= lo) & (ratio <= hi)
+    wgt = (inside | (s1 < s2)).to(y.dtype)                       # min's and clamp's backward weight, per row
+    dlogp = (-float(P.ACTION_DIM) * advantages * ratio * wgt / n).unsqueeze(-1)
+    dmu = dlogp * (dm64 * iv64).to(y.dtype)
+    flat = lambda t: t.reshape(-1, t.shape[-1])                  # noqa: E731
+    ess = (2 * ratio.logsumexp(0) - (2 * ratio).logsumexp(0)).exp().mean() / B
+    return {"dy": dmu @ head_w, "d_head_w": flat(dmu).t() @ flat(y), "d_head_b": flat(dmu).sum(0),
+            "d_log_std": flat(dlogp * (z2 - 1.0)).sum(0) - entropy_coef,
+            "policy_loss": -float(P.ACTION_DIM) * torch.minimum(s1, s2).mean(), "entropy": (0.5 + LOG_SQRT_2PI + log_std).sum(), "ess": ess,
+            "log_probs": logp}
+
+
+def critic_head(head_w, head_b, y, b_values, b_returns, clip_param, loss="huber", huber_delta=10.0):
+    """hns_rnn_critic_head_grad's statements on gathered rows: y [B, L, A, 128], b_values / b_returns [B, L, A].  Returns a dict: dy,
+    d_head_w [1, 128], d_head_b [1], value_loss, explained_var (0-dim), values [B, L, A]."""
+    n = float(b_values.numel())
+    v = (y @ head_w.t() + head_b).squeeze(-1)
+    d = v - b_values
+    clipped = b_values + d.clamp(-clip_param, clip_param)
+
+    def lossf(x):
+        return x * x if loss == "mse" else torch.where(x.abs() < huber_delta, 0.5 * x * x, huber_delta * (x.abs() - 0.5 * huber_delta))
+
+    def dloss(x):
+        return 2.0 * x if loss == "mse" else x.clamp(-huber_delta, huber_delta)
+
+    e0, e1 = v - b_returns, clipped - b_returns
+    lo, lc = lossf(e0.double()).sum() / n, lossf(e1.double()).sum() / n
+    w0, w1 = (1.0, 0.0) if lo > lc else ((0.0, 1.0) if lo < lc else (0.5, 0.5))      # the max of two means: one branch, halves at a tie
+    inside = ((d >= -clip_param) & (d <= clip_param)).to(y.dtype)
+    dv = ((w0 * dloss(e0) + w1 * dloss(e1) * inside) / n).unsqueeze(-1)
+    r64 = b_returns.double()
+    var = ((r64 * r64).sum() - r64.sum() ** 2 / n) / (n - 1.0)
+    return {"dy": dv * head_w.reshape(-1), "d_head_w": (dv * y).reshape(-1, y.shape[-1]).sum(0, keepdim=True), "d_head_b": dv.sum().reshape(1),
+            "value_loss": torch.maximum(lo, lc).to(y.dtype), "explained_var": (1.0 - ((e0.double() ** 2).sum() / n) / var).to(y.dtype), "values": v}
+
+
+# ---- buffers kept between calls
+class RnnWorkspace:
+    """Every buffer of an update call, kept between calls and regrown only when a shape grows: the features, y, h_hist, dy, dx, h_last and
+    the three kernels' workspaces.  One per network (the learner holds two)."""
+
+    def __init__(self):
+        self._t = {}
+
+    def get(self, name, numel, dtype, device):
+        t = self._t.get(name)
+        if t is None or t.numel() < numel or t.device != device or t.dtype != dtype:
+            t = self._t[name] = torch.empty(max(int(numel), 1), dtype=dtype, device=device)
+            if t.data_ptr() % 256:
+                raise RuntimeError("the allocator returned a buffer that is not 256-byte aligned")
+        return t
+
+    def floats(self, name, shape, device):
+        return self.get(name, math.prod(shape), torch.float32, device)[:math.prod(shape)].view(shape)
+
+    def bytes(self, name, nbytes, device):
+        return self.get(name, nbytes, torch.uint8, device)
+
+    def release(self):
+        self._t = {}
+
+
+def make_bucket(network, actor):
+    """The gradient bucket of a recurrent network for `bucket=`: ONE flat buffer behind the .grad of the encoder's, the GRU's and the head's
+    tensors, in network_parameters' order.  A caller that makes many calls keeps one (the learner does); a call without one makes its own."""
+    return PT.GradBucket(flat_parameters(network_parameters(network, actor)))
+
+
+def _bucket(net, bucket):
+    """The call's gradient bucket: the caller's, checked, or a new one."""
+    params = flat_parameters(net)
+    if bucket is None:
+        return PT.GradBucket(params)
+    if not isinstance(bucket, PT.GradBucket) or len(bucket.params) != len(params) or any(a is not b for a, b in zip(bucket.params, params)):
+        raise ValueError("bucket= must be the GradBucket of this network's parameters in network_parameters' order (make_bucket)")
+    if bucket.flat.is_cuda and not bucket.owns(params):
+        raise ValueError("a parameter's .grad no longer lies in bucket=")
+    return bucket
+
+
+def _prepare(word, net, obs, state, is_init, per_row, segment, seq_len, check_index):
+    """The checks every entry shares; returns (xs, xo, xc, shape, segment ids [B], L, segments in the rollout)."""
+    xs, xo, xc = PT.as_rollout(*obs)
+    shape = PT.validate(word, net.encoder, xs, xo, xc, per_row, None, False)
+    N, T, A, _, _ = shape
+    L = int(seq_len)
+    if not 1 <= L <= abi.HNS_GRU_MAX_STEPS or T % L:
+        raise ValueError(f"the segment length {L} must be in [1, {abi.HNS_GRU_MAX_STEPS}] and divide the rollout's {T} steps")
+    NS = N * (T // L)
+    dev = xs.device
+    if not torch.is_tensor(state) or state.dtype != torch.float32 or state.numel() != NS * A * H or state.shape[-1] != H or state.device != dev:
+        raise ValueError(f"the stored state must be float32 [{N}, {T // L}, {A}, {H}] on {dev}")
+    if not torch.is_tensor(is_init) or is_init.numel() != N * T or is_init.device != dev:
+        raise ValueError(f"is_init must hold [{N}, {T}, 1] flags on {dev}")
+    for f, t in (*net.gru.items(), *net.head.items()):
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{word} parameter {f} must be a contiguous float32 tensor on {dev}")
+    if segment is None:
+        segment = torch.arange(NS, device=dev)
+    else:
+        if not torch.is_tensor(segment) or segment.dtype != torch.int64 or segment.dim() != 1 or segment.device != dev:
+            raise TypeError(f"segment must be a 1-d int64 tensor on {dev}")
+        if segment.numel() < 1:
+            raise ValueError("empty minibatch: the mean over zero rows is NaN")
+        segment = segment.contiguous()
+        if check_index and not (dev.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+            lo, hi = torch.stack([segment.min(), segment.max()]).tolist()        # one host synchronisation
+            if lo < 0 or hi >= NS:
+                raise IndexError(f"segment ids [{lo}, {hi}] outside the {NS} segments of the rollout")
+    return xs, xo, xc, shape, segment, L, NS
+
+
+def _gathered(state, is_init, segment, NS, A, L):
+    """(h0 [B A, 128], flags uint8 [B A, L]) of the minibatch: the stored state going into each segment and the env-level flags of its steps
+    for every agent, from clamped ids (_device_forward_to_y)."""
+    seg = segment.clamp(0, NS - 1)
+    B = seg.numel()
+    h0 = state.reshape(NS, A, H).index_select(0, seg).reshape(B * A, H)
+    f = is_init.reshape(NS, L)
+    f = f.view(torch.uint8) if f.dtype == torch.bool else (f != 0).view(torch.uint8)
+    flags = f.index_select(0, seg).unsqueeze(1).expand(B, A, L).reshape(B * A, L)
+    return h0, flags
+
+
+def _rows(per_row, segment, L, A):
+    """Per-row tensors of the rollout ([N T, A(, k)] values) gathered as [B, L, A(, k)]."""
+    idx = (segment.unsqueeze(1) * L + torch.arange(L, device=segment.device)).reshape(-1)
+    out = []
+    for t, width in per_row:
+        t = t.reshape(-1, A, width) if width > 1 else t.reshape(-1, A)
+        out.append(t.index_select(0, idx).reshape(segment.numel(), L, *t.shape[1:]))
+    return idx, out
+
+
+def _torch_update(net, xs, xo, xc, shape, segment, L, NS, state, is_init, per_row, head_fn):
+    """The CPU path of both networks: forward through the restatements with the parameters as leaves, the head's restatement on y, autograd
+    from dy back through the GRU and the encoder; leaves every parameter's .grad set.  Returns the head's dict."""
+    N, T, A, _, _ = shape
+    B = segment.numel()
+    idx, rows = _rows(per_row, segment, L, A)
+    h0, flags = _gathered(state, is_init, segment, NS, A, L)
+    enc = {f: t.detach().requires_grad_(True) for f, t in net.encoder.items()}
+    gru = {f: t.detach().requires_grad_(True) for f, t in net.gru.items()}
+    with torch.enable_grad():
+        feats = PT.encoder(enc, *encoder._gather(xs, xo, xc, idx))                                   # [B L, A, 128]
+        x = feats.view(B, L, A, H).transpose(1, 2).reshape(B * A, L, H)
+        out, _ = rnn.restatement(gru, x, h0, flags.to(x.dtype))
+        y = out.view(B, A, L, H).transpose(1, 2)                                                     # [B, L, A, 128]
+    with torch.no_grad():
+        res = head_fn(y.detach(), *rows)
+    leaves = [*enc.values(), *gru.values()]
+    grads = torch.autograd.grad(y, leaves, res["dy"])
+    for t, g in zip([*net.encoder.values(), *net.gru.values()], grads):
+        t.grad = g
+    for f, t in net.head.items():
+        t.grad = res["d_" + f].reshape(t.shape).clone()
+    return res
+
+
+def _device_forward_to_y(net, xs, xo, xc, shape, segment, L, NS, state, is_init, ws):
+    """encoder -> GRU on the device; returns what the backward half needs."""
+    N, T, A, D, K = shape
+    dev = xs.device
+    B = segment.numel()
+    lib = abi.load_library()
+    # a bad id is clamped for the encoder and the two gathers (finite features, a stored state): its rows are dead in the head entry, which
+    # takes the ids as they are, so dy, hence dx, is zero there and the segment adds nothing to any gradient
+    index = (segment.clamp(0, NS - 1).unsqueeze(1) * L + torch.arange(L, device=dev)).reshape(-1)
+    nb = lib.hns_encoder_workspace_bytes(B * L * A, D, A, K, 1)
+    if nb == 0:
+        raise ValueError(f"shape outside the kernels' limits: {B * L * A} rows, self_dim {D}, {A} agents, {K} cylinders")
+    ews = ws.bytes("encoder", nb, dev)
+    feats = ws.floats("features", (B * L, A, H), dev)
+    encoder.device_forward(net.encoder, xs, xo, xc, index, shape, workspace=ews, out=feats)
+    x4 = feats.view(B, L, A, H).transpose(1, 2)                                                      # [B, A, L, 128]: a view, read in place
+    h0, flags = _gathered(state, is_init, segment, NS, A, L)
+    view = lambda name: ws.floats(name, (B * L, A, H), dev).view(B, L, A, H).transpose(1, 2)         # noqa: E731
+    y, _, hist = rnn.device_forward(net.gru, x4, h0, flags, True, out=view("y"), h_last=ws.floats("h_last", (B * A, H), dev),
+                                    h_hist=ws.floats("h_hist", (B * A, L, H), dev))
+    return index, ews, x4, h0, flags, y, hist, view
+
+
+def _rows_struct(y, segment, NS):
+    r = abi.HnsRnnRows()
+    B, A, L, _ = y.shape
+    r.y = y.data_ptr()
+    for d in range(3):
+        r.y_stride[d] = y.stride(d) if y.shape[d] > 1 else 0
+    r.outer, r.inner, r.steps = B, A, L
+    r.segment = segment.data_ptr()
+    r.num_segments = NS
+    return r
+
+
+def _device_backward(net, bucket, xs, xo, xc, shape, index, ews, x4, h0, flags, hist, dy, view, ws):
+    """dy -> the GRU's and the encoder's gradients, written into the bucket's slices."""
+    dev = xs.device
+    B, A, L, _ = x4.shape
+    n_enc = encoder.grad_layout(net.encoder)[1]
+    n_gru = rnn.grad_layout()[1]
+    gws = ws.bytes("gru", abi.load_library().hns_gru_workspace_bytes(B * A, L, 1), dev)
+    dxbuf = ws.floats("dx", (B * L, A, H), dev)
+    rnn.device_backward(net.gru, x4, h0, flags, hist, dy, None, False, workspace=gws, flat=bucket.flat[n_enc:n_enc + n_gru],
+                        dx=dxbuf.view(B, L, A, H).transpose(1, 2))
+    encoder.device_backward(net.encoder, xs, xo, xc, index, shape, dxbuf, workspace=ews, flat=bucket.flat[:n_enc])
+
+
+def _head_grads(net, bucket):
+    """The bucket's views of the head's gradients, by field."""
+    k = len(net.encoder) + len(net.gru)
+    return dict(zip(net.head, bucket.views[k:]))
+
+
+def policy_loss_and_grad_rnn(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, segment=None,
+                             seq_len=16, clip_param=0.1, entropy_coef=0.001, check_index=True, workspace=None, out=None, bucket=None):
+    """update_actor_rnn up to the gradient norm: ActorLoss(policy_loss, entropy, ess, grad_norm: 0-dim tensors; log_probs [B, L, A, 1]) and
+    every parameter's .grad (views of ONE flat GradBucket on the device: `bucket` (make_bucket), or one made for the call).
+
+    actor: the recurrent actor's parameters under the reference's names (encoder.*, rnn.*, act_dist.*); obs_*: the rollout's [N, T, A, ...]
+    observations; actor_rnn_state [N, T / L, A, 128]: the state going into every segment; is_init [N, T, 1]; action [N, T, A, 4],
+    log_probs_old, advantages [N, T, A, 1]; segment: int64 [B] ids into the flattened [N, T / L] (None: all, in order); seq_len: L.
+    `check_index` range-checks the ids (one host synchronisation); unchecked, an id outside the rollout contributes nothing on the device (its
+    rows are dead in the head entry, the encoder and the GRU run on a clamped copy of it) and raises IndexError from torch's gather on the CPU.  `workspace`: an RnnWorkspace kept between calls; `out`: four fp32 device
+    values that receive policy_loss, entropy, ess and grad_norm.  Both are ignored on the CPU."""
+    if not clip_param >= 0:
+        raise ValueError("clip_param must be >= 0")
+    net = network_parameters(actor, True)
+    per_row = (("action", action, P.ACTION_DIM), ("log_probs_old", log_probs_old, 1), ("advantages", advantages, 1))
+    xs, xo, xc, shape, segment, L, NS = _prepare("actor", net, (obs_self, obs_others, obs_cylinders), actor_rnn_state, is_init, per_row, segment,
+                                                 seq_len, check_index)
+    A = shape[2]
+    if not xs.is_cuda:
+        res = _torch_update(net, xs, xo, xc, shape, segment, L, NS, actor_rnn_state, is_init, [(t, w) for _, t, w in per_row],
+                            lambda y, a, lpo, adv: actor_head(net.head["head_w"], net.head["head_b"], net.head["log_std"], y, a, lpo, adv,
+                                                              float(clip_param), float(entropy_coef)))
+        with torch.no_grad():
+            norm = torch.nn.utils.clip_grad_norm_(flat_parameters(net), float("inf"))
+        return ActorLoss(res["policy_loss"], res["entropy"], res["ess"], norm, res["log_probs"].unsqueeze(-1))
+    dev = xs.device
+    lib = abi.load_library()
+    ws = workspace if workspace is not None else RnnWorkspace()
+    bucket = _bucket(net, bucket)
+    scal = PT.check_out(out, 4, dev) if out is not None else torch.empty(4, dtype=torch.float32, device=dev)
+    act, lpo, adv = action.contiguous(), log_probs_old.contiguous(), advantages.contiguous()
+    index, ews, x4, h0, flags, y, hist, view = _device_forward_to_y(net, xs, xo, xc, shape, segment, L, NS, actor_rnn_state, is_init, ws)
+    B = segment.numel()
+    dy = view("dy")
+    log_probs = torch.empty(B, L, A, 1, dtype=torch.float32, device=dev)
+    nbytes = lib.hns_rnn_actor_head_workspace_bytes(B, A, L)
+    hws = ws.bytes("head", nbytes, dev)
+    g = _head_grads(net, bucket)
+    rows = _rows_struct(y, segment, NS)
+    with torch.cuda.device(dev):
+        rc = lib.hns_rnn_actor_head_grad(net.head["head_w"].data_ptr(), net.head["head_b"].data_ptr(), net.head["log_std"].data_ptr(), C.byref(rows),
+                                         act.data_ptr(), lpo.data_ptr(), adv.data_ptr(), float(clip_param), float(entropy_coef), dy.data_ptr(),
+                                         g["head_w"].data_ptr(), g["head_b"].data_ptr(), g["log_std"].data_ptr(), scal[0:].data_ptr(),
+                                         scal[1:].data_ptr(), scal[2:].data_ptr(), log_probs.data_ptr(), hws.data_ptr(), nbytes,
+                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    abi.check(rc, "hns_rnn_actor_head_grad")
+    _device_backward(net, bucket, xs, xo, xc, shape, index, ews, x4, h0, flags, hist, dy, view, ws)
+    bucket.norm(scal[3:4])
+    return ActorLoss(scal[0], scal[1], scal[2], scal[3], log_probs)
+
+
+def value_loss_and_grad_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_state, is_init, b_values, b_returns, segment=None, seq_len=16,
+                            clip_param=0.1, loss="huber", huber_delta=10.0, check_index=True, workspace=None, out=None, bucket=None):
+    """update_critic_rnn up to the gradient norm: CriticLoss(value_loss, explained_var, grad_norm: 0-dim tensors; values [B, L, A, 1]) and
+    every parameter's .grad.  critic: the recurrent critic's parameters (base.*, rnn.*, v_out.*); critic_rnn_state [N, T / L, A, 128];
+    b_values, b_returns [N, T, A, 1]; the other arguments are policy_loss_and_grad_rnn's (`out`: three values)."""
+    if loss not in critic_train.LOSSES:
+        raise ValueError(f"loss must be 'huber' or 'mse', not {loss!r}")
+    if not clip_param >= 0 or (loss == "huber" and not huber_delta > 0):
+        raise ValueError("clip_param must be >= 0 and huber_delta > 0")
+    net = network_parameters(critic, False)
+    per_row = (("b_values", b_values, 1), ("b_returns", b_returns, 1))
+    xs, xo, xc, shape, segment, L, NS = _prepare("critic", net, (obs_self, obs_others, obs_cylinders), critic_rnn_state, is_init, per_row, segment,
+                                                 seq_len, check_index)
+    A = shape[2]
+    if not xs.is_cuda:
+        res = _torch_update(net, xs, xo, xc, shape, segment, L, NS, critic_rnn_state, is_init, [(t, w) for _, t, w in per_row],
+                            lambda y, bv, ret: critic_head(net.head["head_w"], net.head["head_b"], y, bv, ret, float(clip_param), loss,
+                                                           float(huber_delta)))
+        with torch.no_grad():
+            norm = torch.nn.utils.clip_grad_norm_(flat_parameters(net), float("inf"))
+        return CriticLoss(res["value_loss"], res["explained_var"], norm, res["values"].unsqueeze(-1))
+    dev = xs.device
+    lib = abi.load_library()
+    ws = workspace if workspace is not None else RnnWorkspace()
+    bucket = _bucket(net, bucket)
+    scal = PT.check_out(out, 3, dev) if out is not None else torch.empty(3, dtype=torch.float32, device=dev)
+    bv, ret = b_values.contiguous(), b_returns.contiguous()
+    index, ews, x4, h0, flags, y, hist, view = _device_forward_to_y(net, xs, xo, xc, shape, segment, L, NS, critic_rnn_state, is_init, ws)
+    B = segment.numel()
+    dy = view("dy")
+    values = torch.empty(B, L, A, 1, dtype=torch.float32, device=dev)
+    nbytes = lib.hns_rnn_critic_head_workspace_bytes(B, A, L)
+    hws = ws.bytes("head", nbytes, dev)
+    g = _head_grads(net, bucket)
+    rows = _rows_struct(y, segment, NS)
+    with torch.cuda.device(dev):
+        rc = lib.hns_rnn_critic_head_grad(net.head["head_w"].data_ptr(), net.head["head_b"].data_ptr(), C.byref(rows), bv.data_ptr(), ret.data_ptr(),
+                                          float(clip_param), critic_train.LOSSES[loss], float(huber_delta), dy.data_ptr(), g["head_w"].data_ptr(),
+                                          g["head_b"].data_ptr(), scal[0:].data_ptr(), scal[1:].data_ptr(), values.data_ptr(), hws.data_ptr(), nbytes,
+                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    abi.check(rc, "hns_rnn_critic_head_grad")
+    _device_backward(net, bucket, xs, xo, xc, shape, index, ews, x4, h0, flags, hist, dy, view, ws)
+    bucket.norm(scal[2:3])
+    return CriticLoss(scal[0], scal[1], scal[2], values)
+
+
+def _check_optimizer(optimizer, word):
+    if not isinstance(optimizer, ClippedAdam):
+        raise TypeError(f"update_{word}_rnn takes a ClippedAdam (rnn_train.make_optimizer), not {type(optimizer).__name__}: the clip and the step "
+                        "are one launch that needs the gradient norm")
+    for pg in optimizer.param_groups:
+        if pg.get("weight_decay", 0) != 0:
+            raise NotImplementedError("weight_decay != 0 is not supported")
+
+
+def update_actor_rnn(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, optimizer, segment=None,
+                     cfg=None, seq_len=None, check_index=False, workspace=None, out=None, bucket=None):
+    """MAPPOPolicy.update_actor on one recurrent minibatch: loss, backward through the head, the GRU and the encoder, clip_grad_norm_, Adam.
+    cfg: the algo cfg (clip_param, entropy_coef, actor.rnn.train_seq_len; the reference's defaults when None; seq_len= overrides).  Returns
+    {"policy_loss", "actor_grad_norm", "entropy", "ESS"} as 0-dim tensors.  `optimizer`: a ClippedAdam over network_parameters' tensors
+    (make_optimizer).  The segment ids are NOT range-checked by default, as update_actor's index."""
+    _check_optimizer(optimizer, "actor")
+    get = PT.getter(cfg)
+    L = int(seq_len) if seq_len is not None else train_seq_len(cfg)
+    res = policy_loss_and_grad_rnn(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, segment, L,
+                                   float(get("clip_param", 0.1)), float(get("entropy_coef", 0.001)), check_index, workspace, out, bucket)
+    optimizer.step(grad_norm=res.grad_norm)
+    norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else res.grad_norm
+    return {"policy_loss": res.policy_loss, "actor_grad_norm": norm, "entropy": res.entropy, "ESS": res.ess}
+
+
+def update_critic_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_state, is_init, b_values, b_returns, optimizer, segment=None, cfg=None,
+                      seq_len=None, check_index=False, workspace=None, out=None, bucket=None):
+    """MAPPOPolicy.update_critic on one recurrent minibatch; cfg: clip_param, critic.use_huber_loss, critic.huber_delta,
+    actor.rnn.train_seq_len.  Returns {"value_loss", "critic_grad_norm", "explained_var"} as 0-dim tensors."""
+    _check_optimizer(optimizer, "critic")
+    get, sget = PT.getter(cfg), PT.getter(PT.getter(cfg)("critic", None))
+    L = int(seq_len) if seq_len is not None else train_seq_len(cfg)
+    res = value_loss_and_grad_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_state, is_init, b_values, b_returns, segment, L,
+                                  float(get("clip_param", 0.1)), "huber" if sget("use_huber_loss", True) else "mse", float(sget("huber_delta", 10.0)),
+                                  check_index, workspace, out, bucket)
+    optimizer.step(grad_norm=res.grad_norm)
+    norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else res.grad_norm
+    return {"value_loss": res.value_loss, "critic_grad_norm": norm, "explained_var": res.explained_var}
+
+
+def train_seq_len(cfg):
+    """cfg.actor.rnn.train_seq_len (cfg/algo/mappo.yaml's key), default 16."""
+    sub = PT.getter(PT.getter(PT.getter(cfg)("actor", None))("rnn", None))
+    return int(sub("train_seq_len", 16) or 16)
