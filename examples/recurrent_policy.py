@@ -16,7 +16,10 @@ gae.rollout_targets with the bootstrap value of ONE value_only call on the last 
 
 --learner: train through `learner.RecurrentDeviceLearner` instead of the torch loop below — one `train_rollout` per rollout (the bootstrap
 value, the targets, the env's trajectory predictor (on the device), `--updates` PPO epochs of 4 minibatches of segments through rnn_train.update_actor_rnn / update_critic_rnn: the head and
-the loss in HIP too, two optimisers, no host synchronisation in the loop) — and print the reference's info row.
+the loss in HIP too, two optimisers, no host synchronisation in the loop) — and print the reference's info row.  Under a launcher
+(WORLD_SIZE set) the script is then one rank of a data-parallel run: --envs is the WHOLE job's env count, each rank steps its
+`sharding.env_shard` slice, `learner.DataParallelRecurrentLearner(group="world")` performs one update on the union of the ranks' minibatches,
+and rank 0 alone prints.  The backend is HNS_DIST_BACKEND (default nccl, RCCL on ROCm; gloo runs several ranks on one card as a correctness run).
 
 --eval: after training, one seeded deterministic episode through `DeviceEvaluator(env, pol, collector=col)` — the actor alone with its state
 carried on the device (`RecurrentDevicePolicy.act_step`), the `eval/stats.*` means printed."""
@@ -29,9 +32,9 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import hns_amd  # noqa: E402,F401
-from hns_amd import collector, evaluator, gae, policy  # noqa: E402
+from hns_amd import collector, evaluator, gae, policy, sharding  # noqa: E402
 from hns_amd.encoder import AttentionEncoder  # noqa: E402
-from hns_amd.learner import RecurrentDeviceLearner, ValueNorm1  # noqa: E402
+from hns_amd.learner import DataParallelRecurrentLearner, RecurrentDeviceLearner, ValueNorm1  # noqa: E402
 from hns_amd.rnn import GRU  # noqa: E402
 from hns_amd.tensordict_shim import TensorDict  # noqa: E402
 
@@ -113,19 +116,28 @@ def main():
     args = ap.parse_args()
     if args.steps % SEQ:
         ap.error(f"--steps must be a multiple of the segment length {SEQ}")
+    rank, world = 0, 1
+    if args.learner and "WORLD_SIZE" in os.environ:              # one rank of a data-parallel run
+        import torch.distributed as dist
+        rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+        if torch.cuda.is_available():
+            torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")) % torch.cuda.device_count())
+        dist.init_process_group(os.environ.get("HNS_DIST_BACKEND", "nccl" if torch.cuda.is_available() else "gloo"), rank=rank, world_size=world)
+    offset, envs = sharding.env_shard(args.envs, world, rank)
     torch.manual_seed(0)
     if torch.cuda.is_available():
         from hns_amd import config
         from hns_amd.env import HideAndSeek
-        env = HideAndSeek(config.make_cfg({"env": {"num_envs": args.envs}}, algo={"use_TP_net": 1}))
+        env = HideAndSeek(config.make_cfg({"env": {"num_envs": envs}}, algo={"use_TP_net": 1}), env_index_offset=offset)
         env.set_seed(0)
         dev, A = env.device, env.num_agents
         D = env.observation_spec[("agents", "observation", "state_self")].shape[-1]
     else:
-        env = StandInEnv(args.envs)
+        env = StandInEnv(envs)
+        env.set_seed(rank)
         dev, A, D = torch.device("cpu"), env.A, env.D
     actor, critic = Network(D, A, True, 0).to(dev), Network(D, A, False, 1).to(dev)
-    pol = policy.RecurrentDevicePolicy(actor.names(), critic.names(), seed=0)
+    pol = policy.RecurrentDevicePolicy(actor.names(), critic.names(), seed=rank)        # every rank samples its own noise
     col = collector.DeviceCollector(env, pol, args.steps, rnn_seq_len=SEQ)
     opt = torch.optim.Adam([*actor.parameters(), *critic.parameters()], lr=5e-4)
     vn = ValueNorm1().to(dev)
@@ -134,12 +146,17 @@ def main():
     lrn = None
     if args.learner:
         cfg = {"ppo_epochs": args.updates, "num_minibatches": 4, "actor": {"rnn": {"train_seq_len": SEQ}}, "critic": {"rnn": {"train_seq_len": SEQ}}}
-        lrn = RecurrentDeviceLearner(actor.names(), critic.names(), cfg, tp_net=getattr(env, "TP", None), value_normalizer=vn, device_policy=pol)
+        if world > 1 or "WORLD_SIZE" in os.environ:
+            lrn = DataParallelRecurrentLearner(actor.names(), critic.names(), cfg, tp_net=getattr(env, "TP", None), value_normalizer=vn, device_policy=pol,
+                                               generator=torch.Generator(device=dev).manual_seed(rank), group="world")
+        else:
+            lrn = RecurrentDeviceLearner(actor.names(), critic.names(), cfg, tp_net=getattr(env, "TP", None), value_normalizer=vn, device_policy=pol)
     for it in range(2):
         st = col.collect()
         if lrn is not None:
             info = lrn.train_rollout(**st.learner_kwargs(), **st.recurrent_kwargs())
-            print(f"rollout {it}: " + "  ".join(f"{k.split('/')[-1]} {v:+.5f}" for k, v in info.items()))
+            if rank == 0:
+                print(f"rollout {it}: " + "  ".join(f"{k.split('/')[-1]} {v:+.5f}" for k, v in info.items()))
             continue
         kw, rk = st.learner_kwargs(), st.recurrent_kwargs()
         N, T = kw["reward"].shape[:2]
@@ -171,10 +188,12 @@ def main():
             nn.utils.clip_grad_norm_([*actor.parameters(), *critic.parameters()], 10.0)
             opt.step()
             print(f"rollout {it} update {u}: policy loss {policy_loss.item():+.5f}  value loss {value_loss.item():.5f}  ({B} segments x {SEQ} steps x {A} agents)")
-    if args.eval:
+    if args.eval and rank == 0:
         for k, v in sorted(evaluator.DeviceEvaluator(env, pol, collector=col).evaluate(seed=0).items()):
             print(f"{k} = {v:.6g}")
     env.close()
+    if lrn is not None and lrn.group is not None:
+        torch.distributed.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -830,6 +830,36 @@ int hns_rnn_actor_head_grad(const float *head_w, const float *head_b, const floa
 int hns_rnn_critic_head_grad(const float *head_w, const float *head_b, const hns_rnn_rows *rows, const float *b_values, const float *b_returns,
                              float clip_param, int32_t loss_kind, float huber_delta, float *dy, float *d_head_w, float *d_head_b, float *value_loss,
                              float *explained_var, float *values, void *workspace, size_t workspace_bytes, void *stream);
+/*
+ * The global forms of the two head entries: one rank's part of a data-parallel recurrent update over the union of W ranks' minibatches
+ * (they mirror hns_critic_train_sums, hns_critic_train_grad_global and hns_actor_train_grad_global).  Rows, geometry, the
+ * dead-segment rule, the order of every sum, the workspace's alignment and size functions and the properties are those above.  With one rank —
+ * global_rows = B L A, entropy_share = 1, sums = the call's own hns_rnn_critic_head_sums output — every output has the local entries' bits.
+ *
+ * hns_rnn_critic_head_sums: the values pass and the sum of its G workgroup partials, no dy and no gradient.  sums[0 .. 5) (device memory,
+ * 8-byte aligned): sum loss(v - ret), sum loss(clipped - ret), sum (v - ret)^2, sum ret, sum ret^2 in fp64 over THIS call's live rows, the
+ * partials added in the order hns_rnn_critic_head_grad adds them.  values: [B, L, A] or NULL.  Two launches.
+ * hns_rnn_critic_head_grad_global: sums are the five values of ALL ranks' rows (the caller added them), global_rows the union's row count.
+ * The decision is hns_rnn_critic_head_grad's rule with n = global_rows on the sums given — value_loss, explained_var and the branch weights
+ * are the union's, the same on every rank — and dv is scaled by f32(1 / global_rows), so the ranks' dy-driven gradients and head gradients add
+ * up to the union's.  The call stands alone: v is recomputed from y into this call's workspace (y is read twice, as in the local entry);
+ * `values` is not written.  Four launches.
+ * hns_rnn_actor_head_grad_global: every row's backward weight is scaled by f32(1 / global_rows); policy_loss = -4 sum_local min(..) /
+ * global_rows, this rank's SHARE (the shares add up to the union's loss); d_log_std takes -entropy_coef entropy_share (1 / W: a SUM over the
+ * ranks counts the entropy term once); entropy is the same on every rank; ess stays this call's own, over its own B segments (a diagnostic).
+ * Refused as the local entries refuse, and: NULL or misaligned (8 bytes) sums; global_rows < B L A; an entropy_share that is not finite.
+ */
+int hns_rnn_critic_head_sums(const float *head_w, const float *head_b, const hns_rnn_rows *rows, const float *b_values, const float *b_returns,
+                             float clip_param, int32_t loss_kind, float huber_delta, double *sums, float *values, void *workspace, size_t workspace_bytes,
+                             void *stream);
+int hns_rnn_critic_head_grad_global(const float *head_w, const float *head_b, const hns_rnn_rows *rows, const float *b_values, const float *b_returns,
+                                    float clip_param, int32_t loss_kind, float huber_delta, float *dy, float *d_head_w, float *d_head_b,
+                                    float *value_loss, float *explained_var, float *values, void *workspace, size_t workspace_bytes, void *stream,
+                                    const double *sums, int64_t global_rows);
+int hns_rnn_actor_head_grad_global(const float *head_w, const float *head_b, const float *log_std, const hns_rnn_rows *rows, const float *action,
+                                   const float *log_probs_old, const float *advantages, double clip_param, double entropy_coef, float *dy,
+                                   float *d_head_w, float *d_head_b, float *d_log_std, float *policy_loss, float *entropy, float *ess, float *log_probs,
+                                   void *workspace, size_t workspace_bytes, void *stream, int64_t global_rows, double entropy_share);
 /* The 2-norm of one flat fp32 gradient bucket: norm[0] = f32(sqrt(sum_i flat[i]^2)), in this order (tests/dp_reference.py restates it in numpy):
  * the bucket is cut into quads of four consecutive floats, the last one short by numel % 4 values that count as 0 (nothing past numel is
  * read); G = clamp(ceil(quads / 1024), 1, 64) workgroups of 256 threads, T = 256 G; thread t of the grid adds, for q = t, t + T, t + 2 T, ...,

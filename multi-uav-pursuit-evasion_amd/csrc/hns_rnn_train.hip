@@ -22,6 +22,14 @@
 //   hns_rnn_critic_grad_kernel   : per row dv from the branch weights, dy, and the head's gradient partials (y is read a second time)
 //   hns_rnn_critic_final_kernel  : element e of [d v_out.weight (128), d v_out.bias] adds the G partials in index order, rounds once
 //
+// The global forms (one rank's part of an update over the union of W ranks' minibatches) are the same row kernels with other
+// scalars — inv_n = f32(1 / global_rows), n = global_rows, entropy_coef entropy_share — and two small kernels:
+//   hns_rnn_critic_sums_kernel          : hns_rnn_critic_head_sums' second launch: the G partials of the five sums in the decide kernel's order,
+//                                         written as they are (fp64) for the caller's all-reduce
+//   hns_rnn_critic_decide_global_kernel : the decide kernel's rule (rt_decide, shared) on the union's sums and row count given by the caller
+// hns_rnn_critic_head_grad_global runs the values kernel again for v (its own workspace: the call stands alone), so y is read twice as in the
+// local entry.  With one rank every output has the local entries' bits.
+//
 // Order of every sum.  A lane adds its rows' contributions trip after trip (the head-gradient products in fp32, the loss terms in fp64: a lane
 // sees ceil(trips / G) rows); the workgroup's partial is the 32 row groups added in index order in fp64; the partials are added in workgroup
 // order in fp64 and rounded once to fp32.  G and the trips are functions of the shape alone: the same inputs give the same bits.  No atomics.
@@ -377,6 +385,16 @@ __global__ __launch_bounds__(kRtThreads, 2) void hns_rnn_critic_values_kernel(co
     }
 }
 
+// ct_loss_decide's rule on the five sums S over n rows: the branch weights, value_loss, explained_var (one thread)
+HNS_DEV void rt_decide(const double *S, double n, float *ctl, float *value_loss, float *explained_var) {
+    const double lo = S[0] / n, lc = S[1] / n;
+    ctl[0] = lo > lc ? 1.0f : (lo < lc ? 0.0f : 0.5f);
+    ctl[1] = lo > lc ? 0.0f : (lo < lc ? 1.0f : 0.5f);
+    value_loss[0] = (float)(lo > lc ? lo : lc);
+    const double var = (S[4] - S[3] * S[3] / n) / (n - 1.0);                 // unbiased, as Tensor.var()
+    explained_var[0] = (float)(1.0 - (S[2] / n) / var);
+}
+
 // value_loss, explained_var and the branch weights of max(mean loss(v), mean loss(clipped)): ct_loss_decide's rule on the five sums over n rows
 __global__ __launch_bounds__(kRtThreads) void hns_rnn_critic_decide_kernel(const double *part, int groups, double n, float *ctl, float *value_loss,
                                                                            float *explained_var) {
@@ -385,13 +403,23 @@ __global__ __launch_bounds__(kRtThreads) void hns_rnn_critic_decide_kernel(const
     const double s = rt_sum_partials(part, groups, kRtSumSlots, 0, 5, stage, threadIdx.x);
     if (threadIdx.x < kRtFinalElems) S[threadIdx.x] = s;
     __syncthreads();
+    if (threadIdx.x == 0) rt_decide(S, n, ctl, value_loss, explained_var);
+}
+
+// the forward-only entry's second launch: the G partials of each of the five sums, added in the decide kernel's order, as they are (fp64)
+__global__ __launch_bounds__(kRtThreads) void hns_rnn_critic_sums_kernel(const double *part, int groups, double *sums) {
+    __shared__ double stage[kRtMaxGroups][kRtFinalElems];
+    const double s = rt_sum_partials(part, groups, kRtSumSlots, 0, 5, stage, threadIdx.x);
+    if (threadIdx.x < 5) sums[threadIdx.x] = s;
+}
+
+// the global entry's decision: the rule on the union's sums and its row count, given by the caller
+__global__ void hns_rnn_critic_decide_global_kernel(const double *sums, double n, float *ctl, float *value_loss, float *explained_var) {
     if (threadIdx.x == 0) {
-        const double lo = S[0] / n, lc = S[1] / n;
-        ctl[0] = lo > lc ? 1.0f : (lo < lc ? 0.0f : 0.5f);
-        ctl[1] = lo > lc ? 0.0f : (lo < lc ? 1.0f : 0.5f);
-        value_loss[0] = (float)(lo > lc ? lo : lc);
-        const double var = (S[4] - S[3] * S[3] / n) / (n - 1.0);             // unbiased, as Tensor.var()
-        explained_var[0] = (float)(1.0 - (S[2] / n) / var);
+        double S[5];
+#pragma unroll
+        for (int q = 0; q < 5; ++q) S[q] = sums[q];
+        rt_decide(S, n, ctl, value_loss, explained_var);
     }
 }
 
@@ -486,12 +514,12 @@ inline RtCriticWs rt_critic_ws(long long rows) {
     return w;
 }
 
-// the refusals both entries share, in the header's order; fills the kernels' geometry
-inline int rt_check_rows(const char *fn, const hns_rnn_rows *rows, float *dy, RtGeom &G) {
+// the refusals every entry shares, in the header's order; fills the kernels' geometry.  `needs_dy` false: the forward-only entry, which has no dy
+inline int rt_check_rows(const char *fn, const hns_rnn_rows *rows, float *dy, RtGeom &G, bool needs_dy = true) {
     if (!rows) return hns_fail(fn, "null pointer (rows)");
     if (rows->inner < 1 || rows->inner > HNS_MAX_AGENTS || !rt_shape_ok(rows->outer, (int32_t)rows->inner, rows->steps))
         return hns_fail(fn, "outer must be >= 1 (and < 2^31), inner in [1, 7], steps in [1, HNS_GRU_MAX_STEPS]");
-    if (!rows->y || !dy) return hns_fail(fn, "null pointer (y, dy)");
+    if (!rows->y || (needs_dy && !dy)) return hns_fail(fn, "null pointer (y, dy)");
     if (!hns_aligned(rows->y, 16) || !hns_aligned(dy, 16)) return hns_fail(fn, "misaligned pointer: y and dy are read and written by float4 (16-byte aligned)");
     for (int d = 0; d < 3; ++d)
         if (rows->y_stride[d] < 0 || rows->y_stride[d] % 4) return hns_fail(fn, "y strides must be >= 0 and multiples of 4 floats");
@@ -503,6 +531,116 @@ inline int rt_check_rows(const char *fn, const hns_rnn_rows *rows, float *dy, Rt
     G.rows = (long long)rows->outer * G.LA;
     G.nseg = rows->num_segments;
     G.segment = reinterpret_cast<const long long *>(rows->segment);
+    return HNS_OK;
+}
+
+}  // namespace hns
+
+namespace hns {
+
+// the local and the global actor entry: n_rows is the row count every mean divides by (the call's own B L A, or the union's), share the part of
+// the entropy term's constant gradient this call adds
+static int rt_actor_entry(const char *fn, const float *head_w, const float *head_b, const float *log_std, const hns_rnn_rows *rows, const float *action,
+                          const float *log_probs_old, const float *advantages, double clip_param, double entropy_coef, float *dy, float *d_head_w,
+                          float *d_head_b, float *d_log_std, float *policy_loss, float *entropy, float *ess, float *log_probs, void *workspace,
+                          size_t workspace_bytes, void *stream, bool global, int64_t global_rows, double entropy_share) {
+    RtActorArgs a;
+    if (int rc = rt_check_rows(fn, rows, dy, a.G)) return rc;
+    if (!head_w || !head_b || !log_std || !action || !log_probs_old || !advantages || !d_head_w || !d_head_b || !d_log_std || !policy_loss || !entropy ||
+        !ess || !workspace)
+        return hns_fail(fn, "null pointer");
+    if (!hns_aligned(head_w, 16) || !hns_aligned(head_b, 16) || !hns_aligned(log_std, 16))
+        return hns_fail(fn, "misaligned pointer: the head's tensors are 16-byte aligned");
+    if (!hns_aligned(action, 4) || !hns_aligned(log_probs_old, 4) || !hns_aligned(advantages, 4) || !hns_aligned(d_head_w, 4) || !hns_aligned(d_head_b, 4) ||
+        !hns_aligned(d_log_std, 4) || !hns_aligned(policy_loss, 4) || !hns_aligned(entropy, 4) || !hns_aligned(ess, 4) || !hns_aligned(log_probs, 4))
+        return hns_fail(fn, "misaligned pointer: fp32 arrays and scalars are 4-byte aligned");
+    if (!(clip_param >= 0.0) || entropy_coef != entropy_coef) return hns_fail(fn, "clip_param must be >= 0 and entropy_coef a number");
+    if (global && global_rows < (int64_t)a.G.rows) return hns_fail(fn, "global_rows must be >= the call's own B L A rows");
+    if (global && !(entropy_share - entropy_share == 0.0)) return hns_fail(fn, "entropy_share must be finite");
+    const RtActorWs W = rt_actor_ws(a.G.rows, a.G.LA);
+    if (!hns_aligned(workspace, 256)) return hns_fail(fn, "misaligned pointer: the workspace is 256-byte aligned");
+    if (workspace_bytes < W.bytes) return hns_fail(fn, "workspace shorter than hns_rnn_actor_head_workspace_bytes");
+    char *ws = static_cast<char *>(workspace);
+    const double n = global ? (double)global_rows : (double)a.G.rows;
+    a.head_w = head_w; a.head_b = head_b; a.log_std = log_std;
+    a.action = action; a.logp_old = log_probs_old; a.adv = advantages;
+    a.clip_lo = (float)(1.0 - clip_param); a.clip_hi = (float)(1.0 + clip_param);
+    a.inv_n = (float)(1.0 / n);
+    a.logp_new = log_probs;
+    a.B = rows->outer;
+    a.part = reinterpret_cast<double *>(ws + W.part);
+    a.ratio = reinterpret_cast<float *>(ws + W.ratio);
+    double *col = reinterpret_cast<double *>(ws + W.col);
+    const int groups = rt_groups(a.G.rows);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(hns_rnn_actor_rows_kernel, dim3(groups), dim3(kRtThreads), 0, st, a);
+    HNS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hns_rnn_ess_kernel, dim3(a.G.LA), dim3(kRtThreads), 0, st, static_cast<const float *>(a.ratio), (long long)rows->outer, a.G.LA, col);
+    HNS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hns_rnn_actor_final_kernel, dim3((kRtActorUsed + kRtFinalElems - 1) / kRtFinalElems), dim3(kRtThreads), 0, st,
+                       static_cast<const double *>(a.part), groups, static_cast<const double *>(col), a.G.LA, n, (double)rows->outer,
+                       global ? entropy_coef * entropy_share : entropy_coef, log_std, d_head_w, d_head_b, d_log_std, policy_loss, entropy, ess);
+    HNS_CHECK_HIP(hipGetLastError());
+    return HNS_OK;
+}
+
+enum RtCriticMode { kRtLocal, kRtSums, kRtGlobal };
+
+// the three critic entries.  kRtLocal: values, the decision on the call's own sums, dy and the head's gradients.  kRtSums: values and the five
+// sums, nothing else.  kRtGlobal: v again (into this call's workspace), the decision on the caller's sums over global_rows, dy and the gradients.
+static int rt_critic_entry(const char *fn, RtCriticMode mode, const float *head_w, const float *head_b, const hns_rnn_rows *rows, const float *b_values,
+                           const float *b_returns, float clip_param, int32_t loss_kind, float huber_delta, float *dy, float *d_head_w, float *d_head_b,
+                           float *value_loss, float *explained_var, float *values, double *sums_out, const double *sums_in, int64_t global_rows,
+                           void *workspace, size_t workspace_bytes, void *stream) {
+    RtCriticArgs a;
+    const bool grad = mode != kRtSums;
+    if (int rc = rt_check_rows(fn, rows, dy, a.G, grad)) return rc;
+    if (!head_w || !head_b || !b_values || !b_returns || !workspace) return hns_fail(fn, "null pointer");
+    if (grad && (!d_head_w || !d_head_b || !value_loss || !explained_var)) return hns_fail(fn, "null pointer");
+    if (!hns_aligned(head_w, 16) || !hns_aligned(head_b, 16)) return hns_fail(fn, "misaligned pointer: the head's tensors are 16-byte aligned");
+    if (!hns_aligned(b_values, 4) || !hns_aligned(b_returns, 4) || !hns_aligned(d_head_w, 4) || !hns_aligned(d_head_b, 4) || !hns_aligned(value_loss, 4) ||
+        !hns_aligned(explained_var, 4) || !hns_aligned(values, 4))
+        return hns_fail(fn, "misaligned pointer: fp32 arrays and scalars are 4-byte aligned");
+    if (loss_kind != HNS_CRITIC_LOSS_HUBER && loss_kind != HNS_CRITIC_LOSS_MSE) return hns_fail(fn, "loss_kind must be HNS_CRITIC_LOSS_HUBER or HNS_CRITIC_LOSS_MSE");
+    if (!(clip_param >= 0.0f) || (loss_kind == HNS_CRITIC_LOSS_HUBER && !(huber_delta > 0.0f))) return hns_fail(fn, "clip_param must be >= 0 and huber_delta > 0");
+    if (mode == kRtSums && (!sums_out || !hns_aligned(sums_out, 8))) return hns_fail(fn, "sums must be five fp64 device values, 8-byte aligned");
+    if (mode == kRtGlobal && (!sums_in || !hns_aligned(sums_in, 8))) return hns_fail(fn, "sums must be five fp64 device values, 8-byte aligned");
+    if (mode == kRtGlobal && global_rows < (int64_t)a.G.rows) return hns_fail(fn, "global_rows must be >= the call's own B L A rows");
+    const RtCriticWs W = rt_critic_ws(a.G.rows);
+    if (!hns_aligned(workspace, 256)) return hns_fail(fn, "misaligned pointer: the workspace is 256-byte aligned");
+    if (workspace_bytes < W.bytes) return hns_fail(fn, "workspace shorter than hns_rnn_critic_head_workspace_bytes");
+    char *ws = static_cast<char *>(workspace);
+    const double n = mode == kRtGlobal ? (double)global_rows : (double)a.G.rows;
+    a.head_w = head_w; a.head_b = head_b; a.bval = b_values; a.bret = b_returns;
+    a.clip = clip_param; a.delta = huber_delta; a.mse = loss_kind == HNS_CRITIC_LOSS_MSE;
+    a.inv_n = (float)(1.0 / n);
+    a.values = mode == kRtGlobal ? nullptr : values;            // the global entry leaves them to hns_rnn_critic_head_sums
+    a.v = reinterpret_cast<float *>(ws + W.v);
+    float *ctl = reinterpret_cast<float *>(ws + W.ctl);
+    a.ctl = ctl;
+    double *sums = reinterpret_cast<double *>(ws + W.sums);
+    const int groups = rt_groups(a.G.rows);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    a.part = sums;
+    hipLaunchKernelGGL(hns_rnn_critic_values_kernel, dim3(groups), dim3(kRtThreads), 0, st, a);
+    HNS_CHECK_HIP(hipGetLastError());
+    if (mode == kRtSums) {
+        hipLaunchKernelGGL(hns_rnn_critic_sums_kernel, dim3(1), dim3(kRtThreads), 0, st, static_cast<const double *>(sums), groups, sums_out);
+        HNS_CHECK_HIP(hipGetLastError());
+        return HNS_OK;
+    }
+    if (mode == kRtGlobal)
+        hipLaunchKernelGGL(hns_rnn_critic_decide_global_kernel, dim3(1), dim3(64), 0, st, sums_in, n, ctl, value_loss, explained_var);
+    else
+        hipLaunchKernelGGL(hns_rnn_critic_decide_kernel, dim3(1), dim3(kRtThreads), 0, st, static_cast<const double *>(sums), groups, n, ctl, value_loss,
+                           explained_var);
+    HNS_CHECK_HIP(hipGetLastError());
+    a.part = reinterpret_cast<double *>(ws + W.part);
+    hipLaunchKernelGGL(hns_rnn_critic_grad_kernel, dim3(groups), dim3(kRtThreads), 0, st, a);
+    HNS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hns_rnn_critic_final_kernel, dim3((kRtCriticUsed + kRtFinalElems - 1) / kRtFinalElems), dim3(kRtThreads), 0, st,
+                       static_cast<const double *>(a.part), groups, d_head_w, d_head_b);
+    HNS_CHECK_HIP(hipGetLastError());
     return HNS_OK;
 }
 
@@ -524,83 +662,40 @@ int hns_rnn_actor_head_grad(const float *head_w, const float *head_b, const floa
                             const float *log_probs_old, const float *advantages, double clip_param, double entropy_coef, float *dy, float *d_head_w,
                             float *d_head_b, float *d_log_std, float *policy_loss, float *entropy, float *ess, float *log_probs, void *workspace,
                             size_t workspace_bytes, void *stream) {
-    const char *fn = "hns_rnn_actor_head_grad";
-    hns::RtActorArgs a;
-    if (int rc = hns::rt_check_rows(fn, rows, dy, a.G)) return rc;
-    if (!head_w || !head_b || !log_std || !action || !log_probs_old || !advantages || !d_head_w || !d_head_b || !d_log_std || !policy_loss || !entropy ||
-        !ess || !workspace)
-        return hns_fail(fn, "null pointer");
-    if (!hns_aligned(head_w, 16) || !hns_aligned(head_b, 16) || !hns_aligned(log_std, 16))
-        return hns_fail(fn, "misaligned pointer: the head's tensors are 16-byte aligned");
-    if (!hns_aligned(action, 4) || !hns_aligned(log_probs_old, 4) || !hns_aligned(advantages, 4) || !hns_aligned(d_head_w, 4) || !hns_aligned(d_head_b, 4) ||
-        !hns_aligned(d_log_std, 4) || !hns_aligned(policy_loss, 4) || !hns_aligned(entropy, 4) || !hns_aligned(ess, 4) || !hns_aligned(log_probs, 4))
-        return hns_fail(fn, "misaligned pointer: fp32 arrays and scalars are 4-byte aligned");
-    if (!(clip_param >= 0.0) || entropy_coef != entropy_coef) return hns_fail(fn, "clip_param must be >= 0 and entropy_coef a number");
-    const hns::RtActorWs W = hns::rt_actor_ws(a.G.rows, a.G.LA);
-    if (!hns_aligned(workspace, 256)) return hns_fail(fn, "misaligned pointer: the workspace is 256-byte aligned");
-    if (workspace_bytes < W.bytes) return hns_fail(fn, "workspace shorter than hns_rnn_actor_head_workspace_bytes");
-    char *ws = static_cast<char *>(workspace);
-    a.head_w = head_w; a.head_b = head_b; a.log_std = log_std;
-    a.action = action; a.logp_old = log_probs_old; a.adv = advantages;
-    a.clip_lo = (float)(1.0 - clip_param); a.clip_hi = (float)(1.0 + clip_param);
-    a.inv_n = (float)(1.0 / (double)a.G.rows);
-    a.logp_new = log_probs;
-    a.B = rows->outer;
-    a.part = reinterpret_cast<double *>(ws + W.part);
-    a.ratio = reinterpret_cast<float *>(ws + W.ratio);
-    double *col = reinterpret_cast<double *>(ws + W.col);
-    const int groups = hns::rt_groups(a.G.rows);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(hns::hns_rnn_actor_rows_kernel, dim3(groups), dim3(hns::kRtThreads), 0, st, a);
-    HNS_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hns::hns_rnn_ess_kernel, dim3(a.G.LA), dim3(hns::kRtThreads), 0, st, static_cast<const float *>(a.ratio), (long long)rows->outer, a.G.LA, col);
-    HNS_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hns::hns_rnn_actor_final_kernel, dim3((hns::kRtActorUsed + hns::kRtFinalElems - 1) / hns::kRtFinalElems), dim3(hns::kRtThreads), 0, st,
-                       static_cast<const double *>(a.part), groups, static_cast<const double *>(col), a.G.LA, (double)a.G.rows, (double)rows->outer,
-                       entropy_coef, log_std, d_head_w, d_head_b, d_log_std, policy_loss, entropy, ess);
-    HNS_CHECK_HIP(hipGetLastError());
-    return HNS_OK;
+    return hns::rt_actor_entry("hns_rnn_actor_head_grad", head_w, head_b, log_std, rows, action, log_probs_old, advantages, clip_param, entropy_coef, dy,
+                               d_head_w, d_head_b, d_log_std, policy_loss, entropy, ess, log_probs, workspace, workspace_bytes, stream, false, 0, 1.0);
+}
+
+int hns_rnn_actor_head_grad_global(const float *head_w, const float *head_b, const float *log_std, const hns_rnn_rows *rows, const float *action,
+                                   const float *log_probs_old, const float *advantages, double clip_param, double entropy_coef, float *dy,
+                                   float *d_head_w, float *d_head_b, float *d_log_std, float *policy_loss, float *entropy, float *ess, float *log_probs,
+                                   void *workspace, size_t workspace_bytes, void *stream, int64_t global_rows, double entropy_share) {
+    return hns::rt_actor_entry("hns_rnn_actor_head_grad_global", head_w, head_b, log_std, rows, action, log_probs_old, advantages, clip_param,
+                               entropy_coef, dy, d_head_w, d_head_b, d_log_std, policy_loss, entropy, ess, log_probs, workspace, workspace_bytes, stream,
+                               true, global_rows, entropy_share);
 }
 
 int hns_rnn_critic_head_grad(const float *head_w, const float *head_b, const hns_rnn_rows *rows, const float *b_values, const float *b_returns,
                              float clip_param, int32_t loss_kind, float huber_delta, float *dy, float *d_head_w, float *d_head_b, float *value_loss,
                              float *explained_var, float *values, void *workspace, size_t workspace_bytes, void *stream) {
-    const char *fn = "hns_rnn_critic_head_grad";
-    hns::RtCriticArgs a;
-    if (int rc = hns::rt_check_rows(fn, rows, dy, a.G)) return rc;
-    if (!head_w || !head_b || !b_values || !b_returns || !d_head_w || !d_head_b || !value_loss || !explained_var || !workspace) return hns_fail(fn, "null pointer");
-    if (!hns_aligned(head_w, 16) || !hns_aligned(head_b, 16)) return hns_fail(fn, "misaligned pointer: the head's tensors are 16-byte aligned");
-    if (!hns_aligned(b_values, 4) || !hns_aligned(b_returns, 4) || !hns_aligned(d_head_w, 4) || !hns_aligned(d_head_b, 4) || !hns_aligned(value_loss, 4) ||
-        !hns_aligned(explained_var, 4) || !hns_aligned(values, 4))
-        return hns_fail(fn, "misaligned pointer: fp32 arrays and scalars are 4-byte aligned");
-    if (loss_kind != HNS_CRITIC_LOSS_HUBER && loss_kind != HNS_CRITIC_LOSS_MSE) return hns_fail(fn, "loss_kind must be HNS_CRITIC_LOSS_HUBER or HNS_CRITIC_LOSS_MSE");
-    if (!(clip_param >= 0.0f) || (loss_kind == HNS_CRITIC_LOSS_HUBER && !(huber_delta > 0.0f))) return hns_fail(fn, "clip_param must be >= 0 and huber_delta > 0");
-    const hns::RtCriticWs W = hns::rt_critic_ws(a.G.rows);
-    if (!hns_aligned(workspace, 256)) return hns_fail(fn, "misaligned pointer: the workspace is 256-byte aligned");
-    if (workspace_bytes < W.bytes) return hns_fail(fn, "workspace shorter than hns_rnn_critic_head_workspace_bytes");
-    char *ws = static_cast<char *>(workspace);
-    a.head_w = head_w; a.head_b = head_b; a.bval = b_values; a.bret = b_returns;
-    a.clip = clip_param; a.delta = huber_delta; a.mse = loss_kind == HNS_CRITIC_LOSS_MSE;
-    a.inv_n = (float)(1.0 / (double)a.G.rows);
-    a.values = values;
-    a.v = reinterpret_cast<float *>(ws + W.v);
-    float *ctl = reinterpret_cast<float *>(ws + W.ctl);
-    a.ctl = ctl;
-    double *sums = reinterpret_cast<double *>(ws + W.sums);
-    const int groups = hns::rt_groups(a.G.rows);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    a.part = sums;
-    hipLaunchKernelGGL(hns::hns_rnn_critic_values_kernel, dim3(groups), dim3(hns::kRtThreads), 0, st, a);
-    HNS_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hns::hns_rnn_critic_decide_kernel, dim3(1), dim3(hns::kRtThreads), 0, st, static_cast<const double *>(sums), groups, (double)a.G.rows, ctl, value_loss,
-                       explained_var);
-    HNS_CHECK_HIP(hipGetLastError());
-    a.part = reinterpret_cast<double *>(ws + W.part);
-    hipLaunchKernelGGL(hns::hns_rnn_critic_grad_kernel, dim3(groups), dim3(hns::kRtThreads), 0, st, a);
-    HNS_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hns::hns_rnn_critic_final_kernel, dim3((hns::kRtCriticUsed + hns::kRtFinalElems - 1) / hns::kRtFinalElems), dim3(hns::kRtThreads), 0, st, static_cast<const double *>(a.part), groups, d_head_w, d_head_b);
-    HNS_CHECK_HIP(hipGetLastError());
-    return HNS_OK;
+    return hns::rt_critic_entry("hns_rnn_critic_head_grad", hns::kRtLocal, head_w, head_b, rows, b_values, b_returns, clip_param, loss_kind, huber_delta,
+                                dy, d_head_w, d_head_b, value_loss, explained_var, values, nullptr, nullptr, 0, workspace, workspace_bytes, stream);
+}
+
+int hns_rnn_critic_head_sums(const float *head_w, const float *head_b, const hns_rnn_rows *rows, const float *b_values, const float *b_returns,
+                             float clip_param, int32_t loss_kind, float huber_delta, double *sums, float *values, void *workspace, size_t workspace_bytes,
+                             void *stream) {
+    return hns::rt_critic_entry("hns_rnn_critic_head_sums", hns::kRtSums, head_w, head_b, rows, b_values, b_returns, clip_param, loss_kind, huber_delta,
+                                nullptr, nullptr, nullptr, nullptr, nullptr, values, sums, nullptr, 0, workspace, workspace_bytes, stream);
+}
+
+int hns_rnn_critic_head_grad_global(const float *head_w, const float *head_b, const hns_rnn_rows *rows, const float *b_values, const float *b_returns,
+                                    float clip_param, int32_t loss_kind, float huber_delta, float *dy, float *d_head_w, float *d_head_b,
+                                    float *value_loss, float *explained_var, float *values, void *workspace, size_t workspace_bytes, void *stream,
+                                    const double *sums, int64_t global_rows) {
+    return hns::rt_critic_entry("hns_rnn_critic_head_grad_global", hns::kRtGlobal, head_w, head_b, rows, b_values, b_returns, clip_param, loss_kind,
+                                huber_delta, dy, d_head_w, d_head_b, value_loss, explained_var, values, nullptr, sums, global_rows, workspace,
+                                workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -23,7 +23,9 @@ refusing a recurrent policy.
 
 `DeviceLearner(..., group=)` is the data-parallel learner: W ranks, each with the rollout of its own env slice, perform ONE
 PPO update per minibatch on the union of their minibatches — the critic's branch decided on the union's sums, every mean over the union's
-rows, the norm taken from the summed gradient, the predictor's ranks weighted by their selected windows."""
+rows, the norm taken from the summed gradient, the predictor's ranks weighted by their selected windows.
+`DataParallelRecurrentLearner` is the same for the recurrent configuration: `RecurrentDeviceLearner` over a process group,
+through rnn_train's global forms (hns_rnn_actor_head_grad_global; hns_rnn_critic_head_sums, hns_rnn_critic_head_grad_global)."""
 import ctypes as C
 
 import numpy as np
@@ -148,11 +150,15 @@ class DeviceLearner:
         self.critic_bucket = PT.GradBucket(critic_train.critic_parameters(self.critic))
         self.tp_bucket = PT.GradBucket(tp_train.parameters(self.tp_net)) if self.tp_net is not None else None
 
+    def _broadcast_tensors(self):
+        """Both networks' tensors, in the order they are broadcast."""
+        return list(actor_train.actor_parameters(self.actor).values()) + list(critic_train.critic_parameters(self.critic).values())
+
     def _broadcast_state(self):
         """Rank 0 of the group hands every rank its networks, ValueNorm1 buffers and Adam states (tensor by tensor: construction and checkpoint
         loading only)."""
         dist = torch.distributed
-        tensors = list(actor_train.actor_parameters(self.actor).values()) + list(critic_train.critic_parameters(self.critic).values())
+        tensors = self._broadcast_tensors()
         if self.tp_net is not None:
             tensors += tp_train.parameters(self.tp_net)
         if self.value_normalizer is not None:
@@ -172,18 +178,22 @@ class DeviceLearner:
                 if box[0][name]["state"]:
                     getattr(self, name).load_state_dict(box[0][name])
 
-    def _global_counts(self, steps, agents):
-        """The rollout's one gather of settings and counts -> (rows of a minibatch over all ranks).  Every rank sees the same table, so a
-        refusal is raised by all of them, before any collective whose shape or count depends on what disagrees."""
-        table = sharding.all_gather_rows([self.num_minibatches, self.ppo_epochs, self.tp_epochs if self.use_tp else 0, int(self.use_tp), steps, agents],
-                                         self.group)
-        for c, what in ((0, "num_minibatches"), (1, "ppo_epochs"), (2, "TP_epochs"), (3, "use_TP_net"), (5, "the number of agents")):
+    def _global_counts(self, steps, agents, unit="env-steps", rows_per_unit=1, more=()):
+        """The rollout's one gather of settings and counts -> (rows of a minibatch over all ranks, rows of the rollout over all ranks).  Every
+        rank sees the same table, so a refusal is raised by all of them, before any collective whose shape or count depends on what
+        disagrees.  `steps`: what this rank's permutation draws from — env-steps, or a recurrent learner's `unit` of `rows_per_unit` steps
+        each; `more`: further (name, value) settings that must agree."""
+        table = sharding.all_gather_rows([self.num_minibatches, self.ppo_epochs, self.tp_epochs if self.use_tp else 0, int(self.use_tp), steps, agents,
+                                          *(v for _, v in more)], self.group)
+        for c, what in ((0, "num_minibatches"), (1, "ppo_epochs"), (2, "TP_epochs"), (3, "use_TP_net"), (5, "the number of agents"),
+                        *((6 + i, name) for i, (name, _) in enumerate(more))):
             if len(set(table[:, c].tolist())) != 1:
                 raise ValueError(f"{what} differs across the ranks of the group: {table[:, c].tolist()}")
         short = [r for r, n in enumerate(table[:, 4].tolist()) if n < self.num_minibatches]
         if short:
-            raise ValueError(f"ranks {short} hold fewer env-steps than num_minibatches {self.num_minibatches}: {table[:, 4].tolist()}")
-        return sum(n // self.num_minibatches for n in table[:, 4].tolist()) * agents, sum(table[:, 4].tolist()) * agents
+            raise ValueError(f"ranks {short} hold fewer {unit} than num_minibatches {self.num_minibatches}: {table[:, 4].tolist()}")
+        return (sum(n // self.num_minibatches for n in table[:, 4].tolist()) * rows_per_unit * agents,
+                sum(table[:, 4].tolist()) * rows_per_unit * agents)
 
     def _reduce_info(self, head, rows, total_rows):
         """The three entries of [column means, action_norm] that differ from rank to rank, in ONE all-reduce of three fp64 values: policy_loss
@@ -247,7 +257,7 @@ class DeviceLearner:
         xs, xo, xc = PT.as_rollout(obs_self, obs_others, obs_cylinders)
         N, T, A, _ = xs.shape
         dev = xs.device
-        global_rows, total_rows = self._global_counts(N * T, A) if self.group is not None else (None, None)
+        global_rows, total_rows = self._rollout_counts(N, T, A) if self.group is not None else (None, None)
         # mappo.py:354-361: done = agent_done | env_done (an absent agent_done is env_done, which rollout_targets broadcasts over the agents)
         dones = done.unsqueeze(-1)
         if agent_done is not None:
@@ -289,6 +299,10 @@ class DeviceLearner:
             info["value_running_mean"] = next(rest)
         self.n_updates += 1
         return {f"{self.agent_name}/{k}": info[k] for k in INFO_KEYS if k in info}
+
+    def _rollout_counts(self, N, T, A):
+        """The data-parallel path's (rows of a minibatch, rows of the rollout) over all ranks."""
+        return self._global_counts(N * T, A)
 
     def _bootstrap_value(self, next_obs_last, recurrent=None):
         """mappo.py:365-367: the critic's value of the last step's next observation, ONE value_only call."""
@@ -401,12 +415,12 @@ class RecurrentDeviceLearner(DeviceLearner):
                     synchronisation, the scalars land in the rows of the [M, 7] table, every buffer is kept per network between calls
         info row    hns_learner_info, INFO_KEYS, one copy to the host
 
-    Refused: group= (data-parallel recurrent training), the configurations RecurrentDevicePolicy refuses, a non-recurrent device_policy, a
+    Refused: group= (data-parallel recurrent training is DataParallelRecurrentLearner's), the configurations RecurrentDevicePolicy refuses, a non-recurrent device_policy, a
     rollout whose T train_seq_len does not divide (or whose storage was cut with another segment length)."""
 
     def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, generator=None, device_policy=None, agent_name="drone", group=None):
         if group is not None:
-            raise NotImplementedError("RecurrentDeviceLearner: data-parallel recurrent training (group=) is not supported")
+            raise NotImplementedError("RecurrentDeviceLearner takes no group=: data-parallel recurrent training is DataParallelRecurrentLearner's")
         if device_policy is not None and not getattr(device_policy, "recurrent", False):
             raise P.PolicyConfigError("RecurrentDeviceLearner needs a RecurrentDevicePolicy (a non-recurrent policy is DeviceLearner's)")
         self._configure(actor, critic, cfg, tp_net, value_normalizer, agent_name, generator)
@@ -462,9 +476,12 @@ class RecurrentDeviceLearner(DeviceLearner):
         N, T = is_init.shape[:2]
         if T % L:
             raise ValueError(f"train_seq_len {L} does not divide the rollout's {T} steps")
-        if (T // L) * N < self.num_minibatches:
-            raise ValueError(f"the rollout holds {(T // L) * N} segments, fewer than num_minibatches {self.num_minibatches}")
+        self._check_segments((T // L) * N)
         return self._run(rk, obs_self, obs_others, obs_cylinders, action, log_probs, state_value, next_obs_last, reward, done, agent_done, tp)
+
+    def _check_segments(self, segments):
+        if segments < self.num_minibatches:
+            raise ValueError(f"the rollout holds {segments} segments, fewer than num_minibatches {self.num_minibatches}")
 
     def _bootstrap_value(self, next_obs_last, recurrent=None):
         return self.policy.forward(*next_obs_last, critic_state=recurrent["last_critic_rnn_state"], is_init=recurrent["last_is_init"],
@@ -480,6 +497,9 @@ class RecurrentDeviceLearner(DeviceLearner):
         if cuda and self.actor_bucket is None:
             self.actor_bucket, self.critic_bucket = rnn_train.make_bucket(self.actor, True), rnn_train.make_bucket(self.critic, False)
         kb_a, kb_c = (dict(bucket=self.actor_bucket), dict(bucket=self.critic_bucket)) if cuda else ({}, {})
+        if global_rows is not None:                              # the data-parallel path: the updates' global forms over the group
+            kb_a = dict(bucket=self.actor_bucket, global_rows=global_rows, entropy_share=1.0 / self.world, group=self.group)
+            kb_c = dict(bucket=self.critic_bucket, global_rows=global_rows, group=self.group)
         m = 0
         for _ in range(self.ppo_epochs):
             for idx in tp_train.minibatches(N * (T // L), self.num_minibatches, xs.device, self.generator):
@@ -490,3 +510,52 @@ class RecurrentDeviceLearner(DeviceLearner):
                 if not cuda:                                       # CPU: the updates return their scalars
                     table[m] = torch.stack([(sa | sc)[k].reshape(()).to(torch.float32) for k in COLUMNS])
                 m += 1
+
+
+class DataParallelRecurrentLearner(RecurrentDeviceLearner):
+    """`RecurrentDeviceLearner` over a process group: W ranks, each with the recurrent rollout of its own env slice, perform
+    ONE PPO update per minibatch on the union of their minibatches of segments.  group: a torch.distributed process group or "world"
+    (required).  What `DeviceLearner(group=)` does for the non-recurrent networks, with the recurrent pieces in place:
+
+        construction, load_state_dict   the group's rank 0 broadcasts both networks (encoder, GRU and head tensors:
+                                        rnn_train.flat_parameters), the predictor, ValueNorm1's buffers and the three Adam states
+        per train_rollout               one gather of (num_minibatches, ppo_epochs, TP_epochs, predictor on, segments = N T / L, agents,
+                                        train_seq_len): all but the segment count must agree and every rank needs one segment per
+                                        minibatch, else ValueError on every rank before any further collective;
+                                        global_rows = sum_r (segments_r // M) L A
+        per minibatch                   each rank permutes its own segments from its own generator; the actor: forward,
+                                        hns_rnn_actor_head_grad_global, backward, SUM all-reduce of its bucket, hns_grad_norm, the step; the
+                                        critic: forward, hns_rnn_critic_head_sums, SUM all-reduce of five fp64 values,
+                                        hns_rnn_critic_head_grad_global, backward, the bucket's all-reduce, the norm, the step — three
+                                        collectives per minibatch pair, ONE encoder and GRU pass per network
+        predictor, targets, info row    update_tp(group=, bucket=), rollout_targets' gather and _reduce_info, as DeviceLearner(group=):
+                                        policy_loss the sum of the shares, ESS the mean of the ranks' own values (a diagnostic),
+                                        action_norm the mean over all ranks' rows; every rank returns the same row
+
+    With one rank every parameter and every entry of the info row has RecurrentDeviceLearner's bits."""
+
+    def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, generator=None, device_policy=None, agent_name="drone", group=None):
+        if group is None:
+            raise ValueError("DataParallelRecurrentLearner needs group=: a torch.distributed process group or \"world\" (one process: "
+                             "RecurrentDeviceLearner)")
+        super().__init__(actor, critic, cfg, tp_net=tp_net, value_normalizer=value_normalizer, generator=generator, device_policy=device_policy,
+                         agent_name=agent_name)
+        self.group = sharding.resolve_group(group)
+        self.world = torch.distributed.get_world_size(self.group)
+        self._make_buckets()
+        self._broadcast_state()
+
+    def _make_buckets(self):
+        self.actor_bucket, self.critic_bucket = rnn_train.make_bucket(self.actor, True), rnn_train.make_bucket(self.critic, False)
+        self.tp_bucket = PT.GradBucket(tp_train.parameters(self.tp_net)) if self.tp_net is not None else None
+
+    def _broadcast_tensors(self):
+        return [t for net, actor in ((self.actor, True), (self.critic, False)) for t in rnn_train.flat_parameters(rnn_train.network_parameters(net, actor))]
+
+    def _rollout_counts(self, N, T, A):
+        L = self.train_seq_len
+        return self._global_counts(N * (T // L), A, unit="segments", rows_per_unit=L, more=(("actor.rnn.train_seq_len", L),))
+
+    def _check_segments(self, segments):
+        """Nothing here: a rank with fewer segments than minibatches is refused from the gather's table, on EVERY rank (this rank alone
+        raising would leave the others waiting in the gather)."""

@@ -16,6 +16,12 @@ re-runs its L steps under the stored env-level `is_init` flags, so the recompute
 `policy_loss_and_grad_rnn` / `value_loss_and_grad_rnn` are the same calls up to the norm, as actor_train.policy_loss_and_grad is to
 update_actor.  `RnnWorkspace` keeps every buffer of a call between calls (the learner holds one per network).
 
+With `global_rows=` the same calls are one rank's part of a data-parallel update over the union of the ranks' minibatches, as
+in actor_train / critic_train: only the head entries take their global forms (`hns_rnn_actor_head_grad_global`; `hns_rnn_critic_head_sums`, the
+SUM all-reduce of five fp64 values, `hns_rnn_critic_head_grad_global`) — everything behind dy is linear in it — and the bucket is all-reduced
+before its norm is taken.  `value_loss_sums_rnn` is the critic's forward half; its forward state lets `value_loss_and_grad_rnn(forward=)` go on
+from y without a second encoder and GRU pass.
+
 CPU tensors run the same statements in torch: `policy_train.encoder`, `rnn.restatement`, and `actor_head` / `critic_head` — the head and the
 loss written out with their hand-derived dy (what the kernels compute, not autograd of another formula); the encoder's and the GRU's
 gradients come from autograd over the recomputed restatements, as in `encoder.encode` and `rnn.gru` (tests — not the hot path)."""
@@ -34,6 +40,7 @@ from .policy_train import ClippedAdam
 H = abi.HNS_GRU_HIDDEN
 LOG_SQRT_2PI = 0.9189385332046727
 ActorLoss, CriticLoss = actor_train.ActorLoss, critic_train.CriticLoss
+CriticSumsRnn = collections.namedtuple("CriticSumsRnn", ["sums", "values", "forward"])
 Network = collections.namedtuple("Network", ["encoder", "gru", "head"])        # three {field: tensor} mappings of one network
 
 
@@ -78,11 +85,13 @@ def _plain_cfg(cfg):
 
 
 # ---- the head and the loss, restated: any dtype (the tests run them in fp64 against autograd of the reference's statements)
-def actor_head(head_w, head_b, log_std, y, action, log_probs_old, advantages, clip_param, entropy_coef):
+def actor_head(head_w, head_b, log_std, y, action, log_probs_old, advantages, clip_param, entropy_coef, global_rows=None, entropy_share=1.0):
     """hns_rnn_actor_head_grad's statements on gathered rows: y [B, L, A, 128], action [B, L, A, 4], log_probs_old / advantages [B, L, A].
-    Returns a dict: dy [B, L, A, 128], d_head_w, d_head_b, d_log_std, policy_loss, entropy, ess (0-dim), log_probs [B, L, A]."""
+    Returns a dict: dy [B, L, A, 128], d_head_w, d_head_b, d_log_std, policy_loss, entropy, ess (0-dim), log_probs [B, L, A].
+    `global_rows`: hns_rnn_actor_head_grad_global's — every mean divides by the union's row count, policy_loss is this part's share and
+    d_log_std takes `entropy_share` of the entropy term's constant gradient; ess stays the part's own."""
     B = y.shape[0]
-    n = float(y.shape[0] * y.shape[1] * y.shape[2])
+    n = float(y.shape[0] * y.shape[1] * y.shape[2]) if global_rows is None else float(global_rows)
     mu = y @ head_w.t() + head_b
     # logp is formed in fp64 from the fp32 mean (its rounding is the ratio's relative error), as the kernel forms it
     iv64 = torch.exp(-2.0 * log_std.double())
@@ -100,15 +109,26 @@ def actor_head(head_w, head_b, log_std, y, action, log_probs_old, advantages, cl
     flat = lambda t: t.reshape(-1, t.shape[-1])                  # noqa: E731
     ess = (2 * ratio.logsumexp(0) - (2 * ratio).logsumexp(0)).exp().mean() / B
     return {"dy": dmu @ head_w, "d_head_w": flat(dmu).t() @ flat(y), "d_head_b": flat(dmu).sum(0),
-            "d_log_std": flat(dlogp * (z2 - 1.0)).sum(0) - entropy_coef,
-            "policy_loss": -float(P.ACTION_DIM) * torch.minimum(s1, s2).mean(), "entropy": (0.5 + LOG_SQRT_2PI + log_std).sum(), "ess": ess,
+            "d_log_std": flat(dlogp * (z2 - 1.0)).sum(0) - (entropy_coef if global_rows is None else entropy_coef * entropy_share),
+            "policy_loss": -float(P.ACTION_DIM) * (torch.minimum(s1, s2).mean() if global_rows is None else torch.minimum(s1, s2).sum() / n), "entropy": (0.5 + LOG_SQRT_2PI + log_std).sum(), "ess": ess,
             "log_probs": logp}
 
 
-def critic_head(head_w, head_b, y, b_values, b_returns, clip_param, loss="huber", huber_delta=10.0):
+def critic_head_sums(head_w, head_b, y, b_values, b_returns, clip_param, loss="huber", huber_delta=10.0):
+    """hns_rnn_critic_head_sums' statements on gathered rows: (the five fp64 sums of these rows, values [B, L, A])."""
+    v = (y @ head_w.t() + head_b).squeeze(-1)
+    clipped = b_values + (v - b_values).clamp(-clip_param, clip_param)
+    e0, e1, r64 = (v - b_returns).double(), (clipped - b_returns).double(), b_returns.double()
+    lossf = lambda x: x * x if loss == "mse" else torch.where(x.abs() < huber_delta, 0.5 * x * x, huber_delta * (x.abs() - 0.5 * huber_delta))   # noqa: E731
+    return torch.stack([lossf(e0).sum(), lossf(e1).sum(), (e0 ** 2).sum(), r64.sum(), (r64 * r64).sum()]), v
+
+
+def critic_head(head_w, head_b, y, b_values, b_returns, clip_param, loss="huber", huber_delta=10.0, sums=None, global_rows=None):
     """hns_rnn_critic_head_grad's statements on gathered rows: y [B, L, A, 128], b_values / b_returns [B, L, A].  Returns a dict: dy,
-    d_head_w [1, 128], d_head_b [1], value_loss, explained_var (0-dim), values [B, L, A]."""
-    n = float(b_values.numel())
+    d_head_w [1, 128], d_head_b [1], value_loss, explained_var (0-dim), values [B, L, A].  `sums`, `global_rows`:
+    hns_rnn_critic_head_grad_global's — the decision, value_loss and explained_var from the union's five sums over global_rows, dv over
+    global_rows."""
+    n = float(b_values.numel()) if global_rows is None else float(global_rows)
     v = (y @ head_w.t() + head_b).squeeze(-1)
     d = v - b_values
     clipped = b_values + d.clamp(-clip_param, clip_param)
@@ -120,14 +140,21 @@ def critic_head(head_w, head_b, y, b_values, b_returns, clip_param, loss="huber"
         return 2.0 * x if loss == "mse" else x.clamp(-huber_delta, huber_delta)
 
     e0, e1 = v - b_returns, clipped - b_returns
-    lo, lc = lossf(e0.double()).sum() / n, lossf(e1.double()).sum() / n
+    if sums is not None:
+        S = sums.double()
+        lo, lc = S[0] / n, S[1] / n
+    else:
+        lo, lc = lossf(e0.double()).sum() / n, lossf(e1.double()).sum() / n
     w0, w1 = (1.0, 0.0) if lo > lc else ((0.0, 1.0) if lo < lc else (0.5, 0.5))      # the max of two means: one branch, halves at a tie
     inside = ((d >= -clip_param) & (d <= clip_param)).to(y.dtype)
     dv = ((w0 * dloss(e0) + w1 * dloss(e1) * inside) / n).unsqueeze(-1)
     r64 = b_returns.double()
-    var = ((r64 * r64).sum() - r64.sum() ** 2 / n) / (n - 1.0)
+    if sums is not None:
+        var, mse = (S[4] - S[3] * S[3] / n) / (n - 1.0), S[2] / n
+    else:
+        var, mse = ((r64 * r64).sum() - r64.sum() ** 2 / n) / (n - 1.0), (e0.double() ** 2).sum() / n
     return {"dy": dv * head_w.reshape(-1), "d_head_w": (dv * y).reshape(-1, y.shape[-1]).sum(0, keepdim=True), "d_head_b": dv.sum().reshape(1),
-            "value_loss": torch.maximum(lo, lc).to(y.dtype), "explained_var": (1.0 - ((e0.double() ** 2).sum() / n) / var).to(y.dtype), "values": v}
+            "value_loss": torch.maximum(lo, lc).to(y.dtype), "explained_var": (1.0 - mse / var).to(y.dtype), "values": v}
 
 
 # ---- buffers kept between calls
@@ -228,9 +255,8 @@ def _rows(per_row, segment, L, A):
     return idx, out
 
 
-def _torch_update(net, xs, xo, xc, shape, segment, L, NS, state, is_init, per_row, head_fn):
-    """The CPU path of both networks: forward through the restatements with the parameters as leaves, the head's restatement on y, autograd
-    from dy back through the GRU and the encoder; leaves every parameter's .grad set.  Returns the head's dict."""
+def _torch_forward(net, xs, xo, xc, shape, segment, L, NS, state, is_init, per_row):
+    """The CPU path's forward half: (y [B, L, A, 128] with its graph, the leaves it hangs on, the gathered per-row tensors)."""
     N, T, A, _, _ = shape
     B = segment.numel()
     idx, rows = _rows(per_row, segment, L, A)
@@ -242,9 +268,16 @@ def _torch_update(net, xs, xo, xc, shape, segment, L, NS, state, is_init, per_ro
         x = feats.view(B, L, A, H).transpose(1, 2).reshape(B * A, L, H)
         out, _ = rnn.restatement(gru, x, h0, flags.to(x.dtype))
         y = out.view(B, A, L, H).transpose(1, 2)                                                     # [B, L, A, 128]
+    return y, [*enc.values(), *gru.values()], rows
+
+
+def _torch_update(net, xs, xo, xc, shape, segment, L, NS, state, is_init, per_row, head_fn, forward=None):
+    """The CPU path of both networks: forward through the restatements with the parameters as leaves (or `forward`, an earlier
+    _torch_forward), the head's restatement on y, autograd from dy back through the GRU and the encoder; leaves every parameter's .grad set.
+    Returns the head's dict."""
+    y, leaves, rows = forward if forward is not None else _torch_forward(net, xs, xo, xc, shape, segment, L, NS, state, is_init, per_row)
     with torch.no_grad():
         res = head_fn(y.detach(), *rows)
-    leaves = [*enc.values(), *gru.values()]
     grads = torch.autograd.grad(y, leaves, res["dy"])
     for t, g in zip([*net.encoder.values(), *net.gru.values()], grads):
         t.grad = g
@@ -307,8 +340,25 @@ def _head_grads(net, bucket):
     return dict(zip(net.head, bucket.views[k:]))
 
 
+def _check_global(word, net, global_rows, rows, group, bucket):
+    """policy_train.check_global for a recurrent network (its parameters in flat_parameters' order)."""
+    PT.check_global(word, dict(enumerate(flat_parameters(net))), global_rows, rows, group, bucket)
+
+
+def _finish_cpu(net, global_rows, group, bucket):
+    """The CPU path's gradient norm: clip_grad_norm_'s total norm, or — the data-parallel call — the bucket's after its all-reduce."""
+    if global_rows is None:
+        with torch.no_grad():
+            return torch.nn.utils.clip_grad_norm_(flat_parameters(net), float("inf"))
+    if bucket is not None:
+        bucket.adopt()
+    norm = PT.finish_global(bucket, group)
+    return norm.reshape(()) if norm is not None else None
+
+
 def policy_loss_and_grad_rnn(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, segment=None,
-                             seq_len=16, clip_param=0.1, entropy_coef=0.001, check_index=True, workspace=None, out=None, bucket=None):
+                             seq_len=16, clip_param=0.1, entropy_coef=0.001, check_index=True, workspace=None, out=None, bucket=None,
+                             global_rows=None, entropy_share=1.0, group=None):
     """update_actor_rnn up to the gradient norm: ActorLoss(policy_loss, entropy, ess, grad_norm: 0-dim tensors; log_probs [B, L, A, 1]) and
     every parameter's .grad (views of ONE flat GradBucket on the device: `bucket` (make_bucket), or one made for the call).
 
@@ -317,89 +367,193 @@ def policy_loss_and_grad_rnn(actor, obs_self, obs_others, obs_cylinders, actor_r
     log_probs_old, advantages [N, T, A, 1]; segment: int64 [B] ids into the flattened [N, T / L] (None: all, in order); seq_len: L.
     `check_index` range-checks the ids (one host synchronisation); unchecked, an id outside the rollout contributes nothing on the device (its
     rows are dead in the head entry, the encoder and the GRU run on a clamped copy of it) and raises IndexError from torch's gather on the CPU.  `workspace`: an RnnWorkspace kept between calls; `out`: four fp32 device
-    values that receive policy_loss, entropy, ess and grad_norm.  Both are ignored on the CPU."""
+    values that receive policy_loss, entropy, ess and grad_norm.  Both are ignored on the CPU.
+
+    `global_rows` (None: the call above, untouched): this minibatch is one rank's part of a union of `global_rows` rows
+    (hns_rnn_actor_head_grad_global): policy_loss is this rank's SHARE, -4 sum_local / global_rows, and the gradients are the share's — over
+    the ranks both add up to the union's.  `entropy_share`: the part of the entropy term's gradient this rank adds (1 / world).  ess stays
+    this rank's own.  `bucket` is then the network's GradBucket and grad_norm its norm (None without one); `group`: the bucket is all-reduced
+    (SUM) over it first."""
     if not clip_param >= 0:
         raise ValueError("clip_param must be >= 0")
+    if not math.isfinite(float(entropy_share)):
+        raise ValueError("entropy_share must be finite")
     net = network_parameters(actor, True)
     per_row = (("action", action, P.ACTION_DIM), ("log_probs_old", log_probs_old, 1), ("advantages", advantages, 1))
     xs, xo, xc, shape, segment, L, NS = _prepare("actor", net, (obs_self, obs_others, obs_cylinders), actor_rnn_state, is_init, per_row, segment,
                                                  seq_len, check_index)
     A = shape[2]
+    B = segment.numel()
+    glob = global_rows is not None
+    if glob or group is not None:
+        _check_global("actor", net, global_rows, B * L * A, group, bucket)
     if not xs.is_cuda:
         res = _torch_update(net, xs, xo, xc, shape, segment, L, NS, actor_rnn_state, is_init, [(t, w) for _, t, w in per_row],
                             lambda y, a, lpo, adv: actor_head(net.head["head_w"], net.head["head_b"], net.head["log_std"], y, a, lpo, adv,
-                                                              float(clip_param), float(entropy_coef)))
-        with torch.no_grad():
-            norm = torch.nn.utils.clip_grad_norm_(flat_parameters(net), float("inf"))
+                                                              float(clip_param), float(entropy_coef), global_rows, float(entropy_share)))
+        norm = _finish_cpu(net, global_rows, group, bucket if glob else None)
         return ActorLoss(res["policy_loss"], res["entropy"], res["ess"], norm, res["log_probs"].unsqueeze(-1))
     dev = xs.device
     lib = abi.load_library()
     ws = workspace if workspace is not None else RnnWorkspace()
-    bucket = _bucket(net, bucket)
+    if not (glob and bucket is None):
+        bucket = _bucket(net, bucket)
     scal = PT.check_out(out, 4, dev) if out is not None else torch.empty(4, dtype=torch.float32, device=dev)
     act, lpo, adv = action.contiguous(), log_probs_old.contiguous(), advantages.contiguous()
     index, ews, x4, h0, flags, y, hist, view = _device_forward_to_y(net, xs, xo, xc, shape, segment, L, NS, actor_rnn_state, is_init, ws)
-    B = segment.numel()
     dy = view("dy")
     log_probs = torch.empty(B, L, A, 1, dtype=torch.float32, device=dev)
     nbytes = lib.hns_rnn_actor_head_workspace_bytes(B, A, L)
     hws = ws.bytes("head", nbytes, dev)
-    g = _head_grads(net, bucket)
+    own = bucket if bucket is not None else PT.GradBucket(flat_parameters(net))        # (global_rows without a bucket: the gradients only)
+    g = _head_grads(net, own)
     rows = _rows_struct(y, segment, NS)
+    args = (net.head["head_w"].data_ptr(), net.head["head_b"].data_ptr(), net.head["log_std"].data_ptr(), C.byref(rows), act.data_ptr(), lpo.data_ptr(),
+            adv.data_ptr(), float(clip_param), float(entropy_coef), dy.data_ptr(), g["head_w"].data_ptr(), g["head_b"].data_ptr(), g["log_std"].data_ptr(),
+            scal[0:].data_ptr(), scal[1:].data_ptr(), scal[2:].data_ptr(), log_probs.data_ptr(), hws.data_ptr(), nbytes,
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     with torch.cuda.device(dev):
-        rc = lib.hns_rnn_actor_head_grad(net.head["head_w"].data_ptr(), net.head["head_b"].data_ptr(), net.head["log_std"].data_ptr(), C.byref(rows),
-                                         act.data_ptr(), lpo.data_ptr(), adv.data_ptr(), float(clip_param), float(entropy_coef), dy.data_ptr(),
-                                         g["head_w"].data_ptr(), g["head_b"].data_ptr(), g["log_std"].data_ptr(), scal[0:].data_ptr(),
-                                         scal[1:].data_ptr(), scal[2:].data_ptr(), log_probs.data_ptr(), hws.data_ptr(), nbytes,
-                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    abi.check(rc, "hns_rnn_actor_head_grad")
-    _device_backward(net, bucket, xs, xo, xc, shape, index, ews, x4, h0, flags, hist, dy, view, ws)
+        if glob:
+            rc = lib.hns_rnn_actor_head_grad_global(*args, int(global_rows), float(entropy_share))
+        else:
+            rc = lib.hns_rnn_actor_head_grad(*args)
+    abi.check(rc, "hns_rnn_actor_head_grad_global" if glob else "hns_rnn_actor_head_grad")
+    _device_backward(net, own, xs, xo, xc, shape, index, ews, x4, h0, flags, hist, dy, view, ws)
+    if glob:
+        norm = PT.finish_global(bucket, group, scal[3:4])
+        return ActorLoss(scal[0], scal[1], scal[2], scal[3] if norm is not None else None, log_probs)
     bucket.norm(scal[3:4])
     return ActorLoss(scal[0], scal[1], scal[2], scal[3], log_probs)
 
 
-def value_loss_and_grad_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_state, is_init, b_values, b_returns, segment=None, seq_len=16,
-                            clip_param=0.1, loss="huber", huber_delta=10.0, check_index=True, workspace=None, out=None, bucket=None):
-    """update_critic_rnn up to the gradient norm: CriticLoss(value_loss, explained_var, grad_norm: 0-dim tensors; values [B, L, A, 1]) and
-    every parameter's .grad.  critic: the recurrent critic's parameters (base.*, rnn.*, v_out.*); critic_rnn_state [N, T / L, A, 128];
-    b_values, b_returns [N, T, A, 1]; the other arguments are policy_loss_and_grad_rnn's (`out`: three values)."""
+def _critic_checks(loss, clip_param, huber_delta):
     if loss not in critic_train.LOSSES:
         raise ValueError(f"loss must be 'huber' or 'mse', not {loss!r}")
     if not clip_param >= 0 or (loss == "huber" and not huber_delta > 0):
         raise ValueError("clip_param must be >= 0 and huber_delta > 0")
+
+
+class _Forward:
+    """value_loss_sums_rnn's forward state for value_loss_and_grad_rnn(forward=): opaque.  On the device the tensors lie in the caller's
+    RnnWorkspace (y, h_hist, the features) or are the call's own (the gathered h0 / flags, the index); on the CPU it is y with its graph."""
+
+    def __init__(self, key, state):
+        self.key, self.state = key, state
+
+
+def _forward_key(net, xs, segment, L, ws):
+    return (id(net.head["head_w"]), xs.data_ptr(), tuple(xs.shape), segment.data_ptr(), segment.numel(), L, id(ws))
+
+
+def value_loss_sums_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_state, is_init, b_values, b_returns, segment=None, seq_len=16,
+                        clip_param=0.1, loss="huber", huber_delta=10.0, check_index=True, workspace=None):
+    """The forward half of a data-parallel value_loss_and_grad_rnn: encoder -> GRU -> hns_rnn_critic_head_sums.  Returns
+    CriticSumsRnn(sums, values, forward): the five fp64 values of THIS rank's rows (sum loss(v - ret), sum loss(clipped - ret),
+    sum (v - ret)^2, sum ret, sum ret^2), values [B, L, A, 1], and the forward state.  No gradient is touched.  The caller adds the ranks' sums
+    (one SUM all-reduce) and passes the result to value_loss_and_grad_rnn(sums=, global_rows=, forward=): with `forward` that call goes on
+    from y instead of running the encoder and the GRU again.  The state is valid until the next call that uses `workspace` (segment= must
+    be the same tensor in both calls).  Arguments and refusals: value_loss_and_grad_rnn's."""
+    _critic_checks(loss, clip_param, huber_delta)
     net = network_parameters(critic, False)
     per_row = (("b_values", b_values, 1), ("b_returns", b_returns, 1))
     xs, xo, xc, shape, segment, L, NS = _prepare("critic", net, (obs_self, obs_others, obs_cylinders), critic_rnn_state, is_init, per_row, segment,
                                                  seq_len, check_index)
     A = shape[2]
     if not xs.is_cuda:
+        fwd = _torch_forward(net, xs, xo, xc, shape, segment, L, NS, critic_rnn_state, is_init, [(t, w) for _, t, w in per_row])
+        with torch.no_grad():
+            sums, v = critic_head_sums(net.head["head_w"], net.head["head_b"], fwd[0].detach(), *fwd[2], float(clip_param), loss, float(huber_delta))
+        return CriticSumsRnn(sums, v.unsqueeze(-1), _Forward(_forward_key(net, xs, segment, L, None), fwd))
+    dev = xs.device
+    lib = abi.load_library()
+    ws = workspace if workspace is not None else RnnWorkspace()
+    bv, ret = b_values.contiguous(), b_returns.contiguous()
+    state = _device_forward_to_y(net, xs, xo, xc, shape, segment, L, NS, critic_rnn_state, is_init, ws)
+    y = state[5]
+    B = segment.numel()
+    sums = torch.empty(5, dtype=torch.float64, device=dev)
+    values = torch.empty(B, L, A, 1, dtype=torch.float32, device=dev)
+    nbytes = lib.hns_rnn_critic_head_workspace_bytes(B, A, L)
+    hws = ws.bytes("head", nbytes, dev)
+    rows = _rows_struct(y, segment, NS)
+    with torch.cuda.device(dev):
+        rc = lib.hns_rnn_critic_head_sums(net.head["head_w"].data_ptr(), net.head["head_b"].data_ptr(), C.byref(rows), bv.data_ptr(), ret.data_ptr(),
+                                          float(clip_param), critic_train.LOSSES[loss], float(huber_delta), sums.data_ptr(), values.data_ptr(),
+                                          hws.data_ptr(), nbytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    abi.check(rc, "hns_rnn_critic_head_sums")
+    return CriticSumsRnn(sums, values, _Forward(_forward_key(net, xs, segment, L, ws), (state, segment)))
+
+
+def value_loss_and_grad_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_state, is_init, b_values, b_returns, segment=None, seq_len=16,
+                            clip_param=0.1, loss="huber", huber_delta=10.0, check_index=True, workspace=None, out=None, bucket=None, sums=None,
+                            global_rows=None, group=None, forward=None):
+    """update_critic_rnn up to the gradient norm: CriticLoss(value_loss, explained_var, grad_norm: 0-dim tensors; values [B, L, A, 1]) and
+    every parameter's .grad.  critic: the recurrent critic's parameters (base.*, rnn.*, v_out.*); critic_rnn_state [N, T / L, A, 128];
+    b_values, b_returns [N, T, A, 1]; the other arguments are policy_loss_and_grad_rnn's (`out`: three values).
+
+    `sums`, `global_rows` (both None: the call above, untouched): this minibatch is one rank's part of a union of `global_rows` rows whose
+    five fp64 sums are `sums` (value_loss_sums_rnn's over all ranks, added): hns_rnn_critic_head_grad_global takes the branch, value_loss and
+    explained_var from them — the same on every rank — and the gradients are this rank's part, which adds up over the ranks to the union's.
+    `values` is None on the device (value_loss_sums_rnn returned them).  `forward`: value_loss_sums_rnn's state of the SAME arguments and
+    workspace; without it the encoder and the GRU run again.  `bucket`, `group`: policy_loss_and_grad_rnn's."""
+    _critic_checks(loss, clip_param, huber_delta)
+    if (sums is None) != (global_rows is None):
+        raise ValueError("sums= and global_rows= travel together: the union's five sums and its row count")
+    if forward is not None and sums is None:
+        raise ValueError("forward= belongs to the data-parallel call: pass sums= and global_rows= as well")
+    net = network_parameters(critic, False)
+    per_row = (("b_values", b_values, 1), ("b_returns", b_returns, 1))
+    xs, xo, xc, shape, segment, L, NS = _prepare("critic", net, (obs_self, obs_others, obs_cylinders), critic_rnn_state, is_init, per_row, segment,
+                                                 seq_len, check_index and forward is None)
+    A = shape[2]
+    B = segment.numel()
+    glob = global_rows is not None
+    if glob or group is not None:
+        _check_global("critic", net, global_rows, B * L * A, group, bucket)
+    if sums is not None and (not torch.is_tensor(sums) or sums.dtype != torch.float64 or sums.numel() != 5 or sums.device != xs.device or
+                             not sums.is_contiguous()):
+        raise ValueError(f"sums must be five contiguous float64 values on {xs.device}")
+    if forward is not None and (not isinstance(forward, _Forward) or forward.key != _forward_key(net, xs, segment, L, workspace if xs.is_cuda else None)):
+        raise ValueError("forward= must be value_loss_sums_rnn's state of the same critic, observations, segment tensor, seq_len and workspace")
+    if not xs.is_cuda:
         res = _torch_update(net, xs, xo, xc, shape, segment, L, NS, critic_rnn_state, is_init, [(t, w) for _, t, w in per_row],
                             lambda y, bv, ret: critic_head(net.head["head_w"], net.head["head_b"], y, bv, ret, float(clip_param), loss,
-                                                           float(huber_delta)))
-        with torch.no_grad():
-            norm = torch.nn.utils.clip_grad_norm_(flat_parameters(net), float("inf"))
+                                                           float(huber_delta), sums, global_rows),
+                            forward=forward.state if forward is not None else None)
+        norm = _finish_cpu(net, global_rows, group, bucket if glob else None)
         return CriticLoss(res["value_loss"], res["explained_var"], norm, res["values"].unsqueeze(-1))
     dev = xs.device
     lib = abi.load_library()
     ws = workspace if workspace is not None else RnnWorkspace()
-    bucket = _bucket(net, bucket)
+    if not (glob and bucket is None):
+        bucket = _bucket(net, bucket)
     scal = PT.check_out(out, 3, dev) if out is not None else torch.empty(3, dtype=torch.float32, device=dev)
     bv, ret = b_values.contiguous(), b_returns.contiguous()
-    index, ews, x4, h0, flags, y, hist, view = _device_forward_to_y(net, xs, xo, xc, shape, segment, L, NS, critic_rnn_state, is_init, ws)
-    B = segment.numel()
+    if forward is not None:
+        index, ews, x4, h0, flags, y, hist, view = forward.state[0]
+    else:
+        index, ews, x4, h0, flags, y, hist, view = _device_forward_to_y(net, xs, xo, xc, shape, segment, L, NS, critic_rnn_state, is_init, ws)
     dy = view("dy")
-    values = torch.empty(B, L, A, 1, dtype=torch.float32, device=dev)
+    values = None if glob else torch.empty(B, L, A, 1, dtype=torch.float32, device=dev)
     nbytes = lib.hns_rnn_critic_head_workspace_bytes(B, A, L)
     hws = ws.bytes("head", nbytes, dev)
-    g = _head_grads(net, bucket)
+    own = bucket if bucket is not None else PT.GradBucket(flat_parameters(net))
+    g = _head_grads(net, own)
     rows = _rows_struct(y, segment, NS)
+    args = (net.head["head_w"].data_ptr(), net.head["head_b"].data_ptr(), C.byref(rows), bv.data_ptr(), ret.data_ptr(), float(clip_param),
+            critic_train.LOSSES[loss], float(huber_delta), dy.data_ptr(), g["head_w"].data_ptr(), g["head_b"].data_ptr(), scal[0:].data_ptr(),
+            scal[1:].data_ptr(), values.data_ptr() if values is not None else None, hws.data_ptr(), nbytes,
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     with torch.cuda.device(dev):
-        rc = lib.hns_rnn_critic_head_grad(net.head["head_w"].data_ptr(), net.head["head_b"].data_ptr(), C.byref(rows), bv.data_ptr(), ret.data_ptr(),
-                                          float(clip_param), critic_train.LOSSES[loss], float(huber_delta), dy.data_ptr(), g["head_w"].data_ptr(),
-                                          g["head_b"].data_ptr(), scal[0:].data_ptr(), scal[1:].data_ptr(), values.data_ptr(), hws.data_ptr(), nbytes,
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    abi.check(rc, "hns_rnn_critic_head_grad")
-    _device_backward(net, bucket, xs, xo, xc, shape, index, ews, x4, h0, flags, hist, dy, view, ws)
+        if glob:
+            rc = lib.hns_rnn_critic_head_grad_global(*args, sums.data_ptr(), int(global_rows))
+        else:
+            rc = lib.hns_rnn_critic_head_grad(*args)
+    abi.check(rc, "hns_rnn_critic_head_grad_global" if glob else "hns_rnn_critic_head_grad")
+    _device_backward(net, own, xs, xo, xc, shape, index, ews, x4, h0, flags, hist, dy, view, ws)
+    if glob:
+        norm = PT.finish_global(bucket, group, scal[2:3])
+        return CriticLoss(scal[0], scal[1], scal[2] if norm is not None else None, None)
     bucket.norm(scal[2:3])
     return CriticLoss(scal[0], scal[1], scal[2], values)
 
@@ -414,31 +568,55 @@ def _check_optimizer(optimizer, word):
 
 
 def update_actor_rnn(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, optimizer, segment=None,
-                     cfg=None, seq_len=None, check_index=False, workspace=None, out=None, bucket=None):
+                     cfg=None, seq_len=None, check_index=False, workspace=None, out=None, bucket=None, global_rows=None, entropy_share=1.0, group=None):
     """MAPPOPolicy.update_actor on one recurrent minibatch: loss, backward through the head, the GRU and the encoder, clip_grad_norm_, Adam.
     cfg: the algo cfg (clip_param, entropy_coef, actor.rnn.train_seq_len; the reference's defaults when None; seq_len= overrides).  Returns
     {"policy_loss", "actor_grad_norm", "entropy", "ESS"} as 0-dim tensors.  `optimizer`: a ClippedAdam over network_parameters' tensors
-    (make_optimizer).  The segment ids are NOT range-checked by default, as update_actor's index."""
+    (make_optimizer).  The segment ids are NOT range-checked by default, as update_actor's index.  `global_rows`, `entropy_share`, `group`,
+    `bucket`: policy_loss_and_grad_rnn's data-parallel form — forward, the global head entry, backward, the bucket's all-reduce and norm, the
+    step, one collective."""
+    if global_rows is not None and bucket is None:
+        raise ValueError("update_actor_rnn with global_rows= steps on the bucket's norm: pass bucket=")
     _check_optimizer(optimizer, "actor")
     get = PT.getter(cfg)
     L = int(seq_len) if seq_len is not None else train_seq_len(cfg)
     res = policy_loss_and_grad_rnn(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, segment, L,
-                                   float(get("clip_param", 0.1)), float(get("entropy_coef", 0.001)), check_index, workspace, out, bucket)
+                                   float(get("clip_param", 0.1)), float(get("entropy_coef", 0.001)), check_index, workspace, out, bucket,
+                                   **(dict(global_rows=global_rows, entropy_share=entropy_share, group=group) if global_rows is not None or group is not None else {}))
     optimizer.step(grad_norm=res.grad_norm)
     norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else res.grad_norm
     return {"policy_loss": res.policy_loss, "actor_grad_norm": norm, "entropy": res.entropy, "ESS": res.ess}
 
 
 def update_critic_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_state, is_init, b_values, b_returns, optimizer, segment=None, cfg=None,
-                      seq_len=None, check_index=False, workspace=None, out=None, bucket=None):
+                      seq_len=None, check_index=False, workspace=None, out=None, bucket=None, sums=None, global_rows=None, group=None):
     """MAPPOPolicy.update_critic on one recurrent minibatch; cfg: clip_param, critic.use_huber_loss, critic.huber_delta,
-    actor.rnn.train_seq_len.  Returns {"value_loss", "critic_grad_norm", "explained_var"} as 0-dim tensors."""
+    actor.rnn.train_seq_len.  Returns {"value_loss", "critic_grad_norm", "explained_var"} as 0-dim tensors.  `global_rows`, `bucket`: one
+    rank's part of a data-parallel update over a union of `global_rows` rows.  With `group` the call runs value_loss_sums_rnn, the SUM
+    all-reduce of the five values, value_loss_and_grad_rnn(sums=, forward=, group=) — ONE encoder and GRU pass — and the step; `sums` given
+    instead: the caller added the ranks' sums itself."""
+    if global_rows is not None and bucket is None:
+        raise ValueError("update_critic_rnn with global_rows= steps on the bucket's norm: pass bucket=")
+    if global_rows is not None and sums is None and group is None:
+        raise ValueError("update_critic_rnn with global_rows= needs the union's sums= or the group= to add them over")
     _check_optimizer(optimizer, "critic")
     get, sget = PT.getter(cfg), PT.getter(PT.getter(cfg)("critic", None))
     L = int(seq_len) if seq_len is not None else train_seq_len(cfg)
-    res = value_loss_and_grad_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_state, is_init, b_values, b_returns, segment, L,
-                                  float(get("clip_param", 0.1)), "huber" if sget("use_huber_loss", True) else "mse", float(sget("huber_delta", 10.0)),
-                                  check_index, workspace, out, bucket)
+    hyper = (float(get("clip_param", 0.1)), "huber" if sget("use_huber_loss", True) else "mse", float(sget("huber_delta", 10.0)))
+    kw = {}
+    if global_rows is not None or group is not None or sums is not None:
+        kw = dict(sums=sums, global_rows=global_rows, group=group)
+        if global_rows is not None and sums is None:
+            from . import sharding
+            if segment is not None:
+                segment = segment.contiguous()                   # (the forward state is tied to the tensor both calls see)
+            half = value_loss_sums_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_state, is_init, b_values, b_returns, segment, L, *hyper,
+                                       check_index, workspace)
+            kw["sums"] = sharding.all_reduce_sum(half.sums, group)
+            if segment is not None:
+                kw["forward"] = half.forward
+    res = value_loss_and_grad_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_state, is_init, b_values, b_returns, segment, L, *hyper,
+                                  check_index, workspace, out, bucket, **kw)
     optimizer.step(grad_norm=res.grad_norm)
     norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else res.grad_norm
     return {"value_loss": res.value_loss, "critic_grad_norm": norm, "explained_var": res.explained_var}

@@ -13,7 +13,14 @@ then a whole RecurrentDeviceLearner.train_rollout against (b) driven by hand ove
 included in both).  Times are wall clock around a block with a device synchronisation at both ends: the host's share counts.
 
     python tools/rnn_learner_cost.py [--envs 2048 65536] [--rounds 5] [--pairs 8]
-    python tools/rnn_learner_cost.py --trace          # a few (a) pairs at both sizes and nothing else: run under a kernel trace"""
+    python tools/rnn_learner_cost.py --trace          # a few (a) pairs at both sizes and nothing else: run under a kernel trace
+    python tools/rnn_learner_cost.py --group [--envs 2048] [--rounds 5]
+
+--group (profiles/r24_dp_rnn_learner_cost.txt): one train_rollout with the predictor on (4 epochs x 16 minibatches) through
+RecurrentDeviceLearner without a group against DataParallelRecurrentLearner over a ONE-rank gloo group (a file store in a temporary directory),
+in alternating blocks of this one process, and the same group-less learner a second time: the spread.  The difference is the data-parallel
+path's cost with nobody to talk to — the global entries, the three collectives per minibatch pair, which gloo runs on host copies (a device
+synchronisation each): an upper bound of the path's host cost under gloo, not an RCCL figure."""
 import argparse
 import os
 import statistics
@@ -161,6 +168,44 @@ def report(name, xs):
     return statistics.median(xs)
 
 
+HIST, FUTURE = 10, 5                                            # the predictor's window and horizon (tests/rnn_update_reference.py's)
+
+
+def group_cost(N, rounds):
+    import tempfile
+
+    import torch.distributed as dist
+
+    from hns_amd.tp_net import TPNet
+    kw, rk = rollout(N)
+    g = torch.Generator(device=DEV).manual_seed(3)
+    kw["tp"] = (0.5 * torch.randn(N, T, HIST, 7 + 3 * A, device=DEV, generator=g), torch.rand(N, T, 3, device=DEV, generator=g) * 2 - 1,
+                torch.ones(N, T, 1, device=DEV))
+    cfg = {"ppo_epochs": 4, "num_minibatches": M, "TP_epochs": 1, "use_TP_net": 1, "actor": {"rnn": {"train_seq_len": L}}, "critic": {"rnn": {"train_seq_len": L}}}
+    with tempfile.TemporaryDirectory() as tmp:
+        dist.init_process_group("gloo", rank=0, world_size=1, store=dist.FileStore(os.path.join(tmp, "store"), 1))
+
+        def make(cls, **more):
+            nets = Network(True, 0).to(DEV), Network(False, 1).to(DEV)
+            torch.manual_seed(5)
+            return cls(nets[0].names(), nets[1].names(), cfg, tp_net=TPNet(7 + 3 * A, 3 * FUTURE, FUTURE, 1).to(DEV),
+                       value_normalizer=learner.ValueNorm1().to(DEV), generator=torch.Generator(device=DEV).manual_seed(2), **more)
+        arms = {"group=None": make(learner.RecurrentDeviceLearner), "group=None again": make(learner.RecurrentDeviceLearner),
+                "one-rank gloo group": make(learner.DataParallelRecurrentLearner, group="world")}
+        times = {k: [] for k in arms}
+        for arm in arms.values():
+            arm.train_rollout(**kw, **rk)
+        for _ in range(rounds):
+            for k, arm in arms.items():
+                times[k].append(timed(lambda: arm.train_rollout(**kw, **rk), 1))
+        print(f"{N} envs x {T} steps x {A} agents, L = {L}, predictor on: one train_rollout (4 epochs x {M} minibatches = {4 * M} pairs)")
+        med = {k: report(k, v) for k, v in times.items()}
+        extra = med["one-rank gloo group"] - med["group=None"]
+        print(f"    spread group=None against itself: {abs(med['group=None'] - med['group=None again']):.3f} ms; the group's cost: {extra:.3f} ms a rollout, "
+              f"{extra / (4 * M):.4f} ms a minibatch pair")
+        dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, nargs="+", default=[2048, 65536])
@@ -168,7 +213,12 @@ def main():
     ap.add_argument("--pairs", type=int, default=8, help="minibatch pairs per timed block")
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--skip-reference", action="store_true", help="leave (c) out (it is the slowest arm by far at 65 536 envs)")
+    ap.add_argument("--group", action="store_true", help="a one-rank gloo group against group=None, whole rollouts, predictor on")
     args = ap.parse_args()
+    if args.group:
+        for N in args.envs if args.envs != [2048, 65536] else [2048]:
+            group_cost(N, args.rounds)
+        return
     for N in args.envs:
         kw, rk = rollout(N)
         NS = N * (T // L)
