@@ -552,6 +552,33 @@ int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, i
  * packed image / io, a shape out of range, a missing or misaligned observation, a negative stride, a missing or misaligned action. */
 int hns_policy_act(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
                    void *stream);
+/*
+ * One actor per agent (cfg/algo/mappo.yaml's share_actor: false, mappo.py:148-152, :243-246): the reference stacks the actors'
+ * parameters over the agents and vmaps the actor over the agent axis; the critic stays shared.  `actors`: a hns_policy_net whose every tensor is
+ * the stacked one, [A, ...] in its PyTorch layout and contiguous, so agent a's slice is a hns_policy_net of its own.  The entries above keep
+ * serving the shared actor alone and are unchanged.
+ *
+ * hns_policy_packed_agents_bytes: bytes of the image of num_agents actors followed by ONE critic, each hns_policy_pack's image of one network
+ * (hns_policy_packed_bytes / 2 bytes); 0 for self_dim outside [1, 96] or num_agents outside [1, 7].
+ * hns_policy_pack_agents: ONE launch builds that image (16-byte aligned); call it again after the parameters change.  num_agents is the number
+ * of actors (and, as for hns_policy_pack, > 1 says the networks have the state_others embedding).  Refused before the launch, as
+ * hns_policy_pack refuses: self_dim or num_agents out of range, a NULL or misaligned image, a NULL or misaligned parameter pointer, a missing
+ * state_others embedding with num_agents > 1, actors without log_std.
+ * hns_policy_forward_agents: hns_policy_forward's arguments, flags, outputs, output layouts ([E, A, ...]), noise scheme and refusals (all
+ * before any launch, in its order) on that image, and its launch count: ONE launch, and the bump of the counter when the call samples without
+ * io->eps.  A workgroup's 32 rows are 32 consecutive envs of ONE agent: the actor pass reads that agent's image, the critic pass the shared
+ * one.  Row (e, a) keeps its number e A + a — outputs, eps and the Philox counter (*counter, e A + a) — and its arithmetic, which does not
+ * depend on the rows it shares a tile with: for every agent a, row (e, a) is bit for bit what hns_policy_forward writes for that row on
+ * hns_policy_pack's image of (agent a's slice, critic).  Deterministic: fixed-order sums, no atomics.
+ * hns_policy_act_agents: hns_policy_act on that image in the same tiles (ONE launch, the actor pass alone; its refusals, before the launch):
+ * bit for bit hns_policy_forward_agents' action with HNS_POLICY_DETERMINISTIC.
+ */
+size_t hns_policy_packed_agents_bytes(int32_t self_dim, int32_t num_agents);
+int hns_policy_pack_agents(const hns_policy_net *actors, const hns_policy_net *critic, int32_t self_dim, int32_t num_agents, void *packed, void *stream);
+int hns_policy_forward_agents(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
+                              int32_t flags, uint64_t seed, uint64_t *counter, void *stream);
+int hns_policy_act_agents(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
+                          void *stream);
 
 /*
  * The MAPPO critic's update (learning/mappo.py:326-352 on make_critic's network at the defaults: critic_input obs, no rnn): value
@@ -631,6 +658,28 @@ size_t hns_actor_train_workspace_bytes(int64_t rows, int32_t self_dim, int32_t n
 int hns_actor_train_grad(const hns_policy_net *actor, const hns_actor_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
                          double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
                          float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream);
+/* The actor's update with one actor per agent (share_actor: false: MAPPOPolicy.update_actor's else branch, mappo.py:288-291) on
+ * one minibatch of `batch` env-steps x A agents.  `actors`, `grads`: the STACKED tensors ([A, ...] in PyTorch layouts, contiguous, 16-byte
+ * aligned; every slice is then aligned too) and their gradients in the same layouts.  Agent a's rows run on agent a's slice.  The loss is the
+ * reference's: policy_loss = -mean over all batch A rows of min(surr1, surr2) 4 (every row carries 1 / (batch A), as above); entropy: the mean
+ * over the same rows, that is the mean over the agents of each agent's entropy, so each agent's d log_std takes -entropy_coef / A once; ess as
+ * above (it is per agent over the batch already); grads: agent a's slice is the gradient of the whole loss with respect to agent a's parameters
+ * (only its rows contribute; in_proj_b's k third receives zeros per agent); grad_norm: the total 2-norm over ALL agents' gradients
+ * (clip_grad_norm_ over the stacked tensors).  The step is hns_adam_clipped over the 23 stacked tensors.  log_probs [batch, A] (or NULL) is bit
+ * for bit what hns_actor_train_grad writes for row (b, a) with agent a's slice as the actor.
+ * Six launches in one stream, the pipeline above for all agents together: pack (A images), ONE pass over the tiles, the scalars, weight
+ * gradients, reduce (each agent's partials into its slice), ONE norm.  A tile is 32 minibatch positions of ONE agent and the tiles are numbered
+ * agent-major, each agent's count padded to whole row ranges of the weight-gradient kernel (rows that are not live), so no range holds rows of
+ * two agents.  Refused before any launch, as hns_actor_train_grad refuses and in its order: a NULL pointer, a shape out of range (self_dim in
+ * [1, 96], num_agents in [1, 7], num_cylinders in [1, 16], batch >= 1), a negative or non-finite clip_param, a non-finite entropy_coef, a NULL or
+ * misaligned parameter or gradient, a missing or misaligned observation, a negative stride, missing or misaligned action / log_probs_old /
+ * advantages, a misaligned index, output or workspace, a workspace below hns_actor_train_agents_workspace_bytes(batch x num_agents, ...) (0 for
+ * an invalid shape or rows that are no multiple of num_agents).  The workspace is the caller's: nothing is allocated, so it can be cached and
+ * the call captured.  Deterministic: every sum has a fixed order, no float atomics. */
+size_t hns_actor_train_agents_workspace_bytes(int64_t rows, int32_t self_dim, int32_t num_agents, int32_t num_cylinders);
+int hns_actor_train_grad_agents(const hns_policy_net *actors, const hns_actor_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                                double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
+                                float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * The data-parallel learner's entries (hns_amd.learner.DeviceLearner(group=)): W ranks, each holding a part of a minibatch,

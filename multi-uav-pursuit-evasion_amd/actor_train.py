@@ -15,6 +15,9 @@ With `global_rows=` the same calls are one rank's part of a data-parallel update
 by 1 / global_rows and the entropy term by `entropy_share`, the gradients land in a `policy_train.GradBucket`, and with `group=` the bucket is
 all-reduced and its norm taken before the step.
 
+The `*_per_agent` functions are the same update with share_actor: False (one actor per agent: the reference's stacked `actor_params`, every
+tensor [A, ...]; update_actor's else branch, mappo.py:288-291) on ONE call of `hns_actor_train_grad_agents`; DESIGN.md §7.16.
+
 `update_actor` is the reference's function.  CPU tensors run the reference's torch statements throughout (CPU tests, gloo runs — not the
 hot path).  DESIGN.md §7.5."""
 import collections
@@ -170,6 +173,121 @@ def update_actor(actor, obs_self, obs_others, obs_cylinders, action, log_probs_o
     res = policy_loss_and_grad(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index,
                                clip_param=float(get("clip_param", 0.1)), entropy_coef=float(get("entropy_coef", 0.001)), check_index=check_index,
                                workspace=workspace, out=out, global_rows=global_rows, entropy_share=entropy_share, group=group, bucket=bucket)
+    optimizer.step(grad_norm=res.grad_norm)
+    norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else res.grad_norm
+    return {"policy_loss": res.policy_loss, "actor_grad_norm": norm, "entropy": res.entropy, "ESS": res.ess}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# one actor per agent (share_actor: False)
+def actor_parameters_per_agent(actor):
+    """The STACKED actor's tensors ([A, ...] each) by hns_policy_net field, in registration order (clip_grad_norm_'s: the reference clips the
+    stacked tensors)."""
+    return P.parse_parameters_per_agent(actor, "actor")[0]
+
+
+def _torch_loss_and_grad_per_agent(p, xs, xo, xc, action, log_probs_old, advantages, index, clip_param, entropy_coef):
+    """update_actor's statements with the else branch of mappo.py:288-291: the actor mapped over dim 1 of its input and dim 0 of the stacked
+    parameters, the outputs stacked on dim 1; then `_torch_loss_and_grad`'s statements on [B, A, 1]."""
+    N, T, A, D_ = xs.shape
+    xs, xc = xs.reshape(N * T, A, 1, D_), xc.reshape(N * T, A, xc.shape[3], 5)
+    xo = xo.reshape(N * T, A, A - 1, 3) if xo is not None else None
+    action = action.reshape(N * T, A, P.ACTION_DIM)
+    log_probs_old, advantages = log_probs_old.reshape(N * T, A, 1), advantages.reshape(N * T, A, 1)
+    if index is not None:
+        xs, xc, action, log_probs_old, advantages = xs[index], xc[index], action[index], log_probs_old[index], advantages[index]
+        xo = xo[index] if xo is not None else None
+    leaves = {k: v.detach().requires_grad_(True) for k, v in p.items()}
+    logp, ent = [], []
+    for a in range(A):
+        la = P.agent_slice(leaves, a)
+        mean = F.linear(PT.encoder(la, xs[:, a], xo[:, a] if xo is not None else None, xc[:, a]), la["head_w"], la["head_b"])
+        dist = D.Independent(D.Normal(mean, torch.broadcast_to(torch.exp(la["log_std"]), mean.shape), validate_args=False), 1, validate_args=False)
+        logp.append(dist.log_prob(action[:, a]).unsqueeze(-1))
+        ent.append(dist.entropy().unsqueeze(-1))
+    log_probs_new, dist_entropy = torch.stack(logp, dim=1), torch.stack(ent, dim=1)
+    ratio = torch.exp(log_probs_new - log_probs_old)
+    surr1 = ratio * advantages
+    surr2 = torch.clamp(ratio, 1.0 - clip_param, 1.0 + clip_param) * advantages
+    policy_loss = - torch.mean(torch.min(surr1, surr2) * P.ACTION_DIM)
+    entropy_loss = - torch.mean(dist_entropy)
+    grads = torch.autograd.grad(policy_loss + entropy_loss * entropy_coef, list(leaves.values()))
+    for t, g in zip(p.values(), grads):
+        t.grad = g
+    with torch.no_grad():
+        grad_norm = nn.utils.clip_grad_norm_(list(p.values()), float("inf"))
+        ess = (2 * ratio.logsumexp(0) - (2 * ratio).logsumexp(0)).exp().mean() / ratio.shape[0]
+    return ActorLoss(policy_loss.detach(), -entropy_loss.detach(), ess, grad_norm, log_probs_new.detach())
+
+
+def policy_loss_and_grad_per_agent(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index=None, clip_param=0.1,
+                                   entropy_coef=0.001, check_index=True, workspace=None, out=None):
+    """`policy_loss_and_grad` with one actor per agent: `actor` holds the STACKED tensors ([A, ...], the reference's actor_params with
+    share_actor: False), agent a's rows run on slice a, and every stacked tensor's .grad ([A, ...]) is as zero_grad() + backward() leave it.
+    policy_loss is the mean over all B A rows, entropy the mean over the agents of each agent's entropy (each d log_std takes
+    -entropy_coef / A), ess as for the shared actor, grad_norm the total norm over all agents' gradients.  Arguments, layouts, `workspace`
+    (at least hns_actor_train_agents_workspace_bytes bytes) and `out` as `policy_loss_and_grad`; no data-parallel form.  log_probs [B, A, 1]
+    is bit for bit `policy_loss_and_grad`'s for row (b, a) with slice a as the shared actor."""
+    if not clip_param >= 0:
+        raise ValueError("clip_param must be >= 0")
+    p = actor_parameters_per_agent(actor)
+    for k, t in p.items():
+        if not t.is_contiguous():
+            raise ValueError(f"actor parameter {k} must be contiguous")
+    xs, xo, xc = PT.as_rollout(obs_self, obs_others, obs_cylinders)
+    shape = PT.validate("actor", P.agent_slice(p, 0), xs, xo, xc, (("action", action, P.ACTION_DIM), ("log_probs_old", log_probs_old, 1),
+                                                                   ("advantages", advantages, 1)), index, check_index)
+    A = int(p["in_proj_w"].shape[0])
+    if shape[2] != A:
+        raise ValueError(f"the observation has {shape[2]} agents, the stacked actor {A}")
+    if not xs.is_cuda:
+        return _torch_loss_and_grad_per_agent(p, xs, xo, xc, action, log_probs_old, advantages, index, float(clip_param), float(entropy_coef))
+    lib = abi.load_library()
+    act, lpo, adv = action.contiguous(), log_probs_old.contiguous(), advantages.contiguous()
+    net, grd, b, ws, nbytes, scal, B, st = PT.prepare_call("actor", p, xs, xo, xc, index, shape, lib.hns_actor_train_agents_workspace_bytes, workspace,
+                                                           out, 4, abi.HnsActorBatch)
+    _, _, A, D_, K = shape
+    b.action, b.log_probs_old, b.advantages = act.data_ptr(), lpo.data_ptr(), adv.data_ptr()
+    log_probs = torch.empty(B, A, 1, dtype=torch.float32, device=xs.device)
+    with torch.cuda.device(xs.device):
+        rc = lib.hns_actor_train_grad_agents(C.byref(net), C.byref(b), D_, A, K, float(clip_param), float(entropy_coef), C.byref(grd), scal[0:].data_ptr(),
+                                             scal[1:].data_ptr(), scal[2:].data_ptr(), scal[3:].data_ptr(), log_probs.data_ptr(), ws.data_ptr(), nbytes, st)
+    abi.check(rc, "hns_actor_train_grad_agents")
+    return ActorLoss(scal[0], scal[1], scal[2], scal[3], log_probs)
+
+
+def actor_cfg_per_agent(cfg):
+    """`actor_cfg` for one actor per agent: policy.check_config_per_agent's refusals, then actor.lr_scheduler and actor.weight_decay."""
+    P.check_config_per_agent(cfg)
+    sget = PT.getter(PT.getter(cfg)("actor", None))
+    if sget("lr_scheduler", None):
+        raise P.PolicyConfigError("actor.lr_scheduler is not supported")
+    if float(sget("weight_decay", 0.0) or 0.0) != 0:
+        raise NotImplementedError("actor.weight_decay != 0 is not supported")
+    return PT.getter(cfg), sget
+
+
+def make_optimizer_per_agent(actor, cfg=None):
+    """`make_optimizer` over the 23 STACKED tensors: ONE Adam and one clip over all agents' parameters, as the reference's actor_opt."""
+    get, sget = actor_cfg_per_agent(cfg)
+    return ClippedAdam(actor_parameters_per_agent(actor).values(), lr=float(sget("lr", 5e-4)), max_grad_norm=get("max_grad_norm", 10.0),
+                       weight_decay=float(sget("weight_decay", 0.0) or 0.0))
+
+
+def update_actor_per_agent(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, optimizer, index=None, cfg=None,
+                           check_index=False, workspace=None, out=None):
+    """`update_actor` with one actor per agent (MAPPOPolicy.update_actor with share_actor: False): `policy_loss_and_grad_per_agent`, then the
+    clip and the Adam step of `optimizer` (make_optimizer_per_agent) over the stacked tensors.  The same info dict."""
+    if not isinstance(optimizer, ClippedAdam):
+        raise TypeError(f"update_actor_per_agent takes a ClippedAdam (actor_train.make_optimizer_per_agent), not {type(optimizer).__name__}: the "
+                        "clip and the step are one launch that needs the gradient norm")
+    get, _ = actor_cfg_per_agent(cfg)
+    for pg in optimizer.param_groups:
+        if pg.get("weight_decay", 0) != 0:
+            raise NotImplementedError("weight_decay != 0 is not supported")
+    res = policy_loss_and_grad_per_agent(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index,
+                                         clip_param=float(get("clip_param", 0.1)), entropy_coef=float(get("entropy_coef", 0.001)),
+                                         check_index=check_index, workspace=workspace, out=out)
     optimizer.step(grad_norm=res.grad_norm)
     norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else res.grad_norm
     return {"policy_loss": res.policy_loss, "actor_grad_norm": norm, "entropy": res.entropy, "ESS": res.ess}

@@ -35,6 +35,23 @@ struct EncNet {
     X(in_proj_b, in_b) X(out_proj_w, out_w) X(out_proj_b, out_b) X(linear1_w, l1_w) X(linear1_b, l1_b) X(linear2_w, l2_w) X(linear2_b, l2_b)   \
     X(norm1_w, n1_w) X(norm1_b, n1_b) X(norm2_w, n2_w) X(norm2_b, n2_b) X(head_w, head_w) X(head_b, head_b)
 
+// One actor per agent (share_actor: false): every tensor is stacked over the agents, [A, ...] in its PyTorch layout, so agent
+// `ag`'s slice is a contiguous network of its own.  T: EncNet, or the training kernels' gradient table (the same members); `heads`: head_w's rows.
+template <typename T>
+static __host__ __device__ __forceinline__ T enc_agent_slice(T s, int D, int heads, int ag) {
+    s.ew[0] += ag * kEncE * D; s.eb[0] += ag * kEncE;
+    if (s.ew[1]) { s.ew[1] += ag * kEncE * 3; s.eb[1] += ag * kEncE; }
+    s.ew[2] += ag * kEncE * 5; s.eb[2] += ag * kEncE;
+    s.ln_w += ag * kEncE; s.ln_b += ag * kEncE;
+    s.in_w += ag * 3 * kEncMat; s.in_b += ag * 3 * kEncE;
+    s.out_w += ag * kEncMat; s.out_b += ag * kEncE;
+    s.l1_w += ag * kEncMat; s.l1_b += ag * kEncE; s.l2_w += ag * kEncMat; s.l2_b += ag * kEncE;
+    s.n1_w += ag * kEncE; s.n1_b += ag * kEncE; s.n2_w += ag * kEncE; s.n2_b += ag * kEncE;
+    s.head_w += ag * heads * kEncE; s.head_b += ag * heads;
+    if (s.log_std) s.log_std += ag * heads;
+    return s;
+}
+
 // float x of packed matrix m, in MFMA A-operand fragment order (one float4 per lane per four k-steps): m 0-5 are Q, K^T, V, O, L1, L2, m 6-11
 // their transposes (the backward pass' operands)
 HNS_DEV float enc_mat_src(const EncNet &s, int m, int x) {

@@ -31,6 +31,9 @@
 //                               forward's deterministic action and actor state.
 //   hns_policy_rnn_pack_kernel: the two GRUs' tensors -> their packed image.
 //   hns_policy_bump_kernel    : the device call counter += 1 after a sampling call (Philox counter; a captured graph draws fresh noise per replay).
+//   hns_policy_pack_agents_kernel, hns_policy_forward_agents_kernel, hns_policy_act_agents_kernel : one actor per agent (share_actor: false;
+//                               DESIGN §7.16): A actor images and the critic's; a workgroup's rows are 32 envs of ONE agent (blockIdx.y), its actor pass
+//                               reads that agent's image; the same per-row functions, so row (e, a) has the shared kernels' bits with agent a's image.
 // Determinism: fixed reduction orders (butterflies over the eight lanes of a row), no atomics.
 #include <hip/hip_runtime.h>
 
@@ -475,6 +478,66 @@ __global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_rnn_kernel(cons
 
 __global__ void hns_policy_bump_kernel(unsigned long long *counter) { counter[0] += 1ull; }
 
+// ---- one actor per agent (share_actor: false; include/hns.h: hns_policy_forward_agents)
+// The image holds A actor images, then the critic's.  A workgroup's rows are 32 consecutive envs of ONE agent (blockIdx.y), so its six products
+// read one weight image as before; the row keeps its number env * A + agent (outputs, eps, the Philox counter) and its arithmetic is
+// pol_encoder / pol_head / pol_sample untouched: row (e, a) has the bits the shared kernels give it with agent a's image as the actor.
+struct PolNets {
+    EncNet n[HNS_MAX_AGENTS + 1];            // the agents' slices of the stacked actor (formed on the host), then the critic
+};
+
+__global__ __launch_bounds__(256) void hns_policy_pack_agents_kernel(const PolNets nets, int D, float *img) {
+    const long long n = pol_net_floats(D);
+    float *dst = img + blockIdx.y * n;                           // image blockIdx.y: 0 .. A - 1 the agents' actors, A the critic
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) dst[i] = pol_src(nets.n[blockIdx.y], D, i);
+}
+
+// the row of thread row r of the workgroup: env (tile, r) of agent blockIdx.y; past the last env a row that is not live
+HNS_DEV long long pol_agent_row(const PolArgs &a, int r) {
+    const long long e = (long long)blockIdx.x * kEncRows + r;
+    return e * a.A < a.rows ? e * a.A + blockIdx.y : a.rows;
+}
+
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_agents_kernel(const PolArgs a) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
+    const long long row = pol_agent_row(a, r);
+    const bool live = row < a.rows;
+    float y[16];
+
+    if (!a.value_only) {
+        const float *net = a.img + (long long)blockIdx.y * a.net_floats;      // the agent's actor, formed once per tile
+        pol_encoder(a, net, L, w, lane, r, g, row, y);
+        float loc[4];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
+        pol_sample(a, net, loc, row, live, g);
+        __syncthreads();                                          // the critic reuses the LDS
+    }
+    const float *net = a.img + (long long)a.A * a.net_floats;    // the shared critic, behind the A actors
+    pol_encoder(a, net, L, w, lane, r, g, row, y);
+    const float v = pol_head(net, 0, y, g);
+    if (live && g == 0) a.value[row] = v;
+}
+
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_agents_kernel(const PolArgs a) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
+    const long long row = pol_agent_row(a, r);
+    const float *net = a.img + (long long)blockIdx.y * a.net_floats;
+    float y[16];
+    pol_encoder(a, net, L, w, lane, r, g, row, y);
+    float loc[4];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
+    if (row < a.rows && g == 0) {
+#pragma unroll
+        for (int o = 0; o < 4; ++o) a.action[row * 4 + o] = loc[o];
+    }
+}
+
 }  // namespace hns
 
 namespace {
@@ -578,9 +641,9 @@ int hns_policy_pack(const hns_policy_net *actor, const hns_policy_net *critic, i
     return HNS_OK;
 }
 
-int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
-                       int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
-    const char *fn = "hns_policy_forward";
+// hns_policy_forward and hns_policy_forward_agents: the same refusals in the same order, the same arguments; `agents` picks the kernel and its grid
+static int pol_forward_call(const char *fn, bool agents, const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                            const hns_policy_io *io, int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
     int rc = pol_check_shape(fn, packed, self_dim, num_envs, num_agents, num_cylinders, io);
     if (rc != HNS_OK) return rc;
     if (flags & ~(HNS_POLICY_DETERMINISTIC | HNS_POLICY_VALUE_ONLY)) return hns_fail(fn, "unknown flag");
@@ -596,15 +659,57 @@ int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, i
     const hipStream_t st = static_cast<hipStream_t>(stream);
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_forward_kernel),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));   // 72 KB: above the default cap
+    static const hipError_t attr_ag = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_forward_agents_kernel),
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
     HNS_CHECK_HIP(attr);
-    const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
-    hipLaunchKernelGGL(hns::hns_policy_forward_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), st, a);
+    HNS_CHECK_HIP(attr_ag);
+    if (agents) {                                                 // a tile: 32 consecutive envs of one agent
+        const long long tiles = (num_envs + hns::kEncRows - 1) / hns::kEncRows;
+        hipLaunchKernelGGL(hns::hns_policy_forward_agents_kernel, dim3((unsigned)tiles, (unsigned)num_agents), dim3(hns::kEncThreads), sizeof(hns::PolLds), st, a);
+    } else {
+        const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
+        hipLaunchKernelGGL(hns::hns_policy_forward_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), st, a);
+    }
     HNS_CHECK_HIP(hipGetLastError());
     if (!value_only && !det && !io->eps) {
         hipLaunchKernelGGL(hns::hns_policy_bump_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<unsigned long long *>(counter));
         HNS_CHECK_HIP(hipGetLastError());
     }
     return HNS_OK;
+}
+
+int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
+                       int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
+    return pol_forward_call("hns_policy_forward", false, packed, self_dim, num_envs, num_agents, num_cylinders, io, flags, seed, counter, stream);
+}
+
+size_t hns_policy_packed_agents_bytes(int32_t self_dim, int32_t num_agents) {
+    if (self_dim < 1 || self_dim > hns::kPolMaxSelf || num_agents < 1 || num_agents > HNS_MAX_AGENTS) return 0;
+    return (size_t)((num_agents + 1) * hns::pol_net_floats(self_dim)) * sizeof(float);
+}
+
+int hns_policy_pack_agents(const hns_policy_net *actors, const hns_policy_net *critic, int32_t self_dim, int32_t num_agents, void *packed, void *stream) {
+    const char *fn = "hns_policy_pack_agents";
+    if (self_dim < 1 || self_dim > hns::kPolMaxSelf) return hns_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kPolMaxSelf) + "]");
+    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return hns_fail(fn, "num_agents must be in [1, 7]");
+    if (!packed || !hns_aligned(packed, 16)) return hns_fail(fn, "packed image must be a 16-byte aligned device array");
+    hns::EncNet sa{}, sc{};
+    int rc = pol_net(fn, actors, num_agents > 1, true, sa);
+    if (rc != HNS_OK) return rc;
+    rc = pol_net(fn, critic, num_agents > 1, false, sc);
+    if (rc != HNS_OK) return rc;
+    hns::PolNets nets{};
+    for (int ag = 0; ag < num_agents; ++ag) nets.n[ag] = hns::enc_agent_slice(sa, self_dim, 4, ag);
+    nets.n[num_agents] = sc;
+    hipLaunchKernelGGL(hns::hns_policy_pack_agents_kernel, dim3(256, (unsigned)num_agents + 1), dim3(256), 0, static_cast<hipStream_t>(stream), nets,
+                       (int)self_dim, static_cast<float *>(packed));
+    HNS_CHECK_HIP(hipGetLastError());
+    return HNS_OK;
+}
+
+int hns_policy_forward_agents(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
+                              int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
+    return pol_forward_call("hns_policy_forward_agents", true, packed, self_dim, num_envs, num_agents, num_cylinders, io, flags, seed, counter, stream);
 }
 
 size_t hns_policy_rnn_packed_bytes(void) { return (size_t)(2 * hns::R_NET) * sizeof(float); }
@@ -660,9 +765,9 @@ int hns_policy_forward_rnn(const void *packed, const void *rnn_packed, int32_t s
     return HNS_OK;
 }
 
-int hns_policy_act(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
-                   void *stream) {
-    const char *fn = "hns_policy_act";
+// hns_policy_act and hns_policy_act_agents over one body, as the forward's two
+static int pol_act_call(const char *fn, bool agents, const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                        const hns_policy_io *io, void *stream) {
     int rc = pol_check_shape(fn, packed, self_dim, num_envs, num_agents, num_cylinders, io);
     if (rc != HNS_OK) return rc;
     rc = pol_check_obs(fn, num_agents, io);
@@ -671,11 +776,30 @@ int hns_policy_act(const void *packed, int32_t self_dim, int64_t num_envs, int32
     const hns::PolArgs a = pol_args(packed, self_dim, num_envs, num_agents, num_cylinders, io);   // eps, counter, loc, log_prob, value stay NULL: never touched
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_act_kernel),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
+    static const hipError_t attr_ag = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_act_agents_kernel),
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
     HNS_CHECK_HIP(attr);
-    const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
-    hipLaunchKernelGGL(hns::hns_policy_act_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), static_cast<hipStream_t>(stream), a);
+    HNS_CHECK_HIP(attr_ag);
+    if (agents) {
+        const long long tiles = (num_envs + hns::kEncRows - 1) / hns::kEncRows;
+        hipLaunchKernelGGL(hns::hns_policy_act_agents_kernel, dim3((unsigned)tiles, (unsigned)num_agents), dim3(hns::kEncThreads), sizeof(hns::PolLds),
+                           static_cast<hipStream_t>(stream), a);
+    } else {
+        const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
+        hipLaunchKernelGGL(hns::hns_policy_act_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), static_cast<hipStream_t>(stream), a);
+    }
     HNS_CHECK_HIP(hipGetLastError());
     return HNS_OK;
+}
+
+int hns_policy_act(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
+                   void *stream) {
+    return pol_act_call("hns_policy_act", false, packed, self_dim, num_envs, num_agents, num_cylinders, io, stream);
+}
+
+int hns_policy_act_agents(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
+                          void *stream) {
+    return pol_act_call("hns_policy_act_agents", true, packed, self_dim, num_envs, num_agents, num_cylinders, io, stream);
 }
 
 int hns_policy_act_rnn(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,

@@ -38,6 +38,15 @@
 //   hns_critic_kernel<true, 0>  : recomputes the tile's forward pass, reads the row's dy from a [rows, 128] array (as given: no 1 / n) and runs the
 //                                 backward pass above; a tile's partial rows carry no head entries.
 //   wgrad as above; hns_encoder_reduce_kernel is the reduce kernel's body without the head's destinations; no norm launch.
+// One actor per agent (share_actor: false: update_actor's else branch, mappo.py:288-291; hns_actor_train_grad_agents) is the actor's
+// pipeline for all agents together on the STACKED tensors:
+//   hns_actor_pack_agents_kernel   : A operand images, one per agent's slice.
+//   hns_actor_agents_kernel        : the one-pass tile kernel's body (hns_policy_train_bodies.inc, shared as text with hns_critic_kernel) on tiles of
+//                                    32 minibatch positions of ONE agent, numbered agent-major; the agent's image and slice formed once per tile.
+//   hns_actor_loss_agents_kernel   : the scalars; entropy is the mean over the agents.
+//   hns_critic_wgrad_kernel        : unchanged — an agent's tiles are padded to whole row ranges, so no range straddles two agents.
+//   hns_actor_reduce_agents_kernel : each agent's partials into its slice of the stacked gradients (-entropy_coef / A on its d log_std);
+//                                    hns_critic_norm_kernel: ONE norm over all agents' per-block sums.
 // Determinism: every sum has a fixed order, no float atomics: the same inputs give the same bits.
 #include <hip/hip_runtime.h>
 
@@ -231,402 +240,58 @@ HNS_DEV float ct_token_j(const CtArgs &a, const CtRow &R, int j, int g, float (&
 
 template <bool BWD, int HEAD = 1>
 __global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_kernel(const CtArgs a) {
-    static_assert(HEAD == 0 || HEAD == 1 || (HEAD == kActDim && BWD), "the actor's head runs in the one-pass kernel");
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    CtLds &L = *reinterpret_cast<CtLds *>(lds_raw);
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
-    const float *img = a.img;
-    const EncNet &N = a.net;
-    const int ntok = a.A + a.K;
-    float *part = BWD ? a.tilepart + (long long)blockIdx.x * 2 * a.P : nullptr;
+#define CT_BODY_TILE
+#define CT_TILE_BLOCK blockIdx.x
+#define CT_TILE_ROW ((long long)tile * kCtRows + r)
+#define CT_TILE_FIRST (int)((ag + a.A - (long long)tile * kCtRows % a.A) % a.A)
+#define CT_TILE_STEP a.A
+#include "hns_policy_train_bodies.inc"
+#undef CT_TILE_BLOCK
+#undef CT_TILE_ROW
+#undef CT_TILE_FIRST
+#undef CT_TILE_STEP
+}
 
-    {   // one tile per workgroup: its two partial rows are written, never accumulated
-        const int tile = blockIdx.x;
-        const long long row = (long long)tile * kCtRows + r;
-        const CtRow R = ct_row(a, row);
-        float *stg = BWD ? a.stage + (long long)tile * kCtRows * kCtE : nullptr;
-        const long long SA = a.stage_rows * kCtE;               // floats per staging array
+// One actor per agent (share_actor: false; include/hns.h: hns_actor_train_grad_agents).  `a0.net` holds the STACKED tensors
+// ([A, ...]) and `a0.img` A packed images; workgroup (t, agent) runs tile t of the agent's a0.tiles / A tiles — minibatch positions 32 t .. 32 t + 31
+// of that agent — on the agent's slice and image, formed here once per tile.  The tiles are numbered agent-major, so the staged operand pairs,
+// partial rows and loss partials of an agent are contiguous and no row range of the weight-gradient kernel straddles two agents.  A position past
+// the agent's last one (the tail of its last tile, and the tiles that pad its count to whole row ranges) is a row that is not live.
+__global__ __launch_bounds__(kCtThreads, 1) void hns_actor_agents_kernel(const CtArgs a0) {
+    constexpr bool BWD = true;
+    constexpr int HEAD = kActDim;
+    const int agent = blockIdx.y, tpa = a0.tiles / a0.A;
+    CtArgs a = a0;
+    a.img = a0.img + (long long)agent * ct_img_floats(a0.D);
+    a.net = enc_agent_slice(a0.net, a0.D, kActDim, agent);
+#define CT_TILE_BLOCK (agent * tpa + blockIdx.x)
+#define CT_TILE_ROW (((long long)blockIdx.x * kCtRows + r) * a.A < a.rows ? ((long long)blockIdx.x * kCtRows + r) * a.A + agent : a.rows)
+#define CT_TILE_FIRST (ag == agent ? 0 : kCtRows)
+#define CT_TILE_STEP 1
+#include "hns_policy_train_bodies.inc"
+#undef CT_TILE_BLOCK
+#undef CT_TILE_ROW
+#undef CT_TILE_FIRST
+#undef CT_TILE_STEP
+#undef CT_BODY_TILE
+}
 
-        // ---- forward
-        float t[16], xh[16];
-        ct_token(img + I_EW, N.eb[0], R.xs, a.D, N, g, xh, t);                 // token 0
-        enc_lds_store(L.a, r, g, t);
-        if (BWD) crow_store(stg + 1 * SA, kCtE, r, g, t);
-        __syncthreads();
-        enc_matvec<0>(img + 0 * kCtMat, N.in_b, L.a, L.b, nullptr, BWD ? stg + 2 * SA : nullptr, w, lane);          // q
-        __syncthreads();
-        enc_matvec<2>(img + 1 * kCtMat, nullptr, L.b, L.c, nullptr, nullptr, w, lane);       // W_k^T q / sqrt(128)
-        __syncthreads();
-        float kq[16], z[16];
-        enc_lds_load(L.c, r, g, kq);
-        float s, m = enc_score(kq, t), l = 1.0f;
-        const float s0 = m;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) z[i] = t[i];
-        for (int j = 1; j < ntok; ++j) {
-            const float *x;
-            int n;
-            ct_token_j(a, R, j, g, xh, t, x, n);
-            enc_softmax_step(kq, t, m, l, z);
+// the A packed images of the stacked actors: hns_critic_pack_kernel's per agent (blockIdx.y)
+__global__ __launch_bounds__(256) void hns_actor_pack_agents_kernel(const EncNet s0, int D, float *img) {
+    const long long n = ct_img_floats(D);
+    const EncNet s = enc_agent_slice(s0, D, kActDim, blockIdx.y);
+    float *dst = img + blockIdx.y * n;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        float v;
+        if (i < I_EW) v = enc_mat_src(s, (int)(i / kCtMat), (int)(i % kCtMat));
+        else {
+            const long long e = i - I_EW;
+            const int in = (int)(e / kCtE), f = (int)(e % kCtE);
+            if (in < D) v = s.ew[0][f * D + in];
+            else if (in < D + 3) v = s.ew[1] ? s.ew[1][f * 3 + (in - D)] : 0.0f;
+            else v = s.ew[2][f * 5 + (in - D - 3)];
         }
-        const float il = 1.0f / l;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) z[i] *= il;
-        enc_lds_store(L.b, r, g, z);
-        if (BWD) crow_store(stg + 5 * SA, kCtE, r, g, z);
-        __syncthreads();
-        enc_matvec<0>(img + 2 * kCtMat, N.in_b + 2 * kCtE, L.b, L.c, nullptr, BWD ? stg + 7 * SA : nullptr, w, lane);   // v = W_v z + b_v
-        __syncthreads();
-        enc_matvec<0>(img + 3 * kCtMat, N.out_b, L.c, L.b, nullptr, nullptr, w, lane);       // attn
-        __syncthreads();
-        float x1[16], xh1[16], u[16];
-        enc_lds_load(L.a, r, g, u);
-        enc_lds_load(L.b, r, g, t);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) u[i] += t[i];
-        const float rstd1 = enc_layernorm(u, N.n1_w, N.n1_b, g, xh1, x1);                           // x0' = LN1(x0 + attn)
-        enc_lds_store(L.a, r, g, x1);
-        if (BWD) crow_store(stg + 9 * SA, kCtE, r, g, x1);
-        __syncthreads();
-        if (BWD) enc_matvec<4>(img + 4 * kCtMat, N.l1_b, L.a, L.b, L.p, stg + 11 * SA, w, lane);   // h = gelu(W_1 x0' + b_1), the pre-activation to p
-        else enc_matvec<1>(img + 4 * kCtMat, N.l1_b, L.a, L.b, nullptr, nullptr, w, lane);
-        __syncthreads();
-        enc_matvec<0>(img + 5 * kCtMat, N.l2_b, L.b, L.c, nullptr, nullptr, w, lane);        // W_2 h + b_2
-        __syncthreads();
-        float y[16], xh2[16];
-        enc_lds_load(L.c, r, g, t);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) u[i] = x1[i] + t[i];
-        const float rstd2 = enc_layernorm(u, N.n2_w, N.n2_b, g, xh2, y);                            // y = LN2(x0' + ff)
-        float dv = 0.0f, dmu[HEAD ? HEAD : 1];
-        float dy[16], dw[16], db[16], dx[16];
-        if constexpr (HEAD == 0) {
-            // ---- the encoder op: the features leave, or d features arrive, as [rows, 128]; a row that is not live is neither written nor read
-            if (!BWD) {
-                if (R.live) crow_store(a.feat + row * kCtE, kCtE, 0, g, y);
-                return;
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                dy[i] = 0.0f;
-                dw[i] = 0.0f;
-                db[i] = 0.0f;
-            }
-            if (R.live) enc_vec_load(a.dfeat + row * kCtE, g, dy);
-        } else if constexpr (HEAD == 1) {
-            float hw[16];
-            enc_vec_load(N.head_w, g, hw);
-            s = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) s = __builtin_fmaf(hw[i], y[i], s);
-            const float v = row_sum8(s) + N.head_b[0];
-            float ret = 0.0f, bv = 0.0f;
-            if (R.live) {
-                ret = a.bret[R.e * a.A + R.ag];
-                bv = a.bval[R.e * a.A + R.ag];
-            }
-            const float d = v - bv;
-            const float dcl = fminf(fmaxf(d, -a.clip), a.clip);
-            const float clipped = bv + dcl;
-
-            if (!BWD) {
-                if (g == 0) {
-                    double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0, q4 = 0.0;
-                    if (R.live) {
-                        if (a.values) a.values[row] = v;
-                        const double e0 = (double)v - (double)ret, e1 = (double)clipped - (double)ret;
-                        q0 = ct_loss64(e0, (double)a.delta, a.mse);
-                        q1 = ct_loss64(e1, (double)a.delta, a.mse);
-                        q2 = e0 * e0;
-                        q3 = (double)ret;
-                        q4 = (double)ret * (double)ret;
-                    }
-                    L.dred[0 * kCtRows + r] = q0; L.dred[1 * kCtRows + r] = q1; L.dred[2 * kCtRows + r] = q2;
-                    L.dred[3 * kCtRows + r] = q3; L.dred[4 * kCtRows + r] = q4;
-                }
-                __syncthreads();
-                if (tid < 5) {
-                    double acc = 0.0;
-                    for (int rr = 0; rr < kCtRows; ++rr) acc += L.dred[tid * kCtRows + rr];
-                    a.losspart[(long long)tile * 5 + tid] = acc;
-                }
-                return;
-            }
-
-            // ---- backward: dv from the branch weights of max(mean loss(v), mean loss(clipped))
-            if (R.live) {
-                const float g0 = ct_dloss(v - ret, a.delta, a.mse);
-                const float g1 = (d >= -a.clip && d <= a.clip) ? ct_dloss(clipped - ret, a.delta, a.mse) : 0.0f;   // clamp's backward: inside, bounds included
-                dv = (a.ctl[0] * g0 + a.ctl[1] * g1) * a.inv_n;
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                dy[i] = dv * hw[i];
-                u[i] = dv * y[i];                                   // d head_w
-                dw[i] = 0.0f;
-                db[i] = 0.0f;
-            }
-        } else {
-            // ---- the actor's head: mu = fc_mean(y), Normal(mu, exp(log_std)).log_prob(action) summed, the ratio and the clipped surrogate;
-            // d logp = -k adv r w / n with w per row (1 inside the clip, bounds included; outside 1 where the unclipped surrogate is the smaller)
-            // logp sums four terms of order 1 to a number of order 10 whose ROUNDING is the ratio's relative error (r = exp(logp - logp_old)): the terms
-            // and their sum are formed in fp64 from the fp32 mean, so the ratio carries the mean's error only
-            float am[HEAD], dls[HEAD], hr[16];
-            double lp = 0.0;
-#pragma unroll
-            for (int i = 0; i < HEAD; ++i) {
-                enc_vec_load(N.head_w + i * kCtE, g, hr);              // fc_mean.weight's row, read again in the backward pass (not kept)
-                s = 0.0f;
-#pragma unroll
-                for (int q = 0; q < 16; ++q) s = __builtin_fmaf(hr[q], y[q], s);
-                const float mu = row_sum8(s) + N.head_b[i];
-                const float ls = N.log_std[i];
-                const double iv = exp(-2.0 * (double)ls);                          // 1 / sigma^2
-                const float act = R.live ? a.action[(R.e * a.A + R.ag) * HEAD + i] : mu;
-                const double dm = (double)act - (double)mu, z2 = dm * dm * iv;
-                am[i] = (float)(dm * iv);                                          // (a - mu) / sigma^2
-                dls[i] = (float)z2;                                                // (a - mu)^2 / sigma^2
-                lp += (-0.5 * z2 - (double)ls) - 0.9189385332046727;               // log sqrt(2 pi)
-            }
-            const float logp = (float)lp;
-            float ratio = -1.0f, dlogp = 0.0f;
-            double q0 = 0.0;
-            if (R.live) {
-                const float adv = a.adv[R.e * a.A + R.ag];
-                ratio = expf((float)(lp - (double)a.logp_old[R.e * a.A + R.ag]));
-                const float rc = fminf(fmaxf(ratio, a.clip_lo), a.clip_hi);
-                const float s1 = ratio * adv, s2 = rc * adv;
-                const bool inside = ratio >= a.clip_lo && ratio <= a.clip_hi;
-                const float wgt = (inside || s1 < s2) ? 1.0f : 0.0f;
-                const double d1 = (double)ratio * (double)adv, d2 = (double)rc * (double)adv;
-                q0 = d1 < d2 ? d1 : d2;
-                dlogp = -(float)HEAD * adv * ratio * wgt * a.inv_n;
-            }
-#pragma unroll
-            for (int i = 0; i < HEAD; ++i) {
-                dmu[i] = dlogp * am[i];
-                dls[i] = dlogp * (dls[i] - 1.0f);
-            }
-            if (g == 0) {
-                if (R.live && a.logp_new) a.logp_new[row] = logp;
-                L.dred[0 * kCtRows + r] = q0;
-                L.dred[1 * kCtRows + r] = (double)ratio;            // -1: the row is not part of the minibatch
-#pragma unroll
-                for (int i = 0; i < HEAD; ++i) {
-                    L.sx[i * kCtRows + r] = dmu[i];
-                    L.sx[(HEAD + i) * kCtRows + r] = dls[i];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                dy[i] = 0.0f;
-                dw[i] = 0.0f;
-                db[i] = 0.0f;
-            }
-#pragma unroll
-            for (int i = 0; i < HEAD; ++i) {
-                enc_vec_load(N.head_w + i * kCtE, g, hr);
-#pragma unroll
-                for (int q = 0; q < 16; ++q) dy[q] = __builtin_fmaf(dmu[i], hr[q], dy[q]);
-            }
-        }
-        ct_ln_bwd(dy, xh2, rstd2, N.n2_w, g, dx, dw, db);       // dx = d(x0' + ff)
-        enc_lds_store(L.b, r, g, dx);
-        crow_store(stg + 10 * SA, kCtE, r, g, dx);
-        if constexpr (HEAD == 1) {
-            if (g == 0) L.sc[r] = dv;
-            ct_flush(L, u, part, a.P, O_HW, tid, r, g);
-        } else if constexpr (HEAD == kActDim) {
-#pragma unroll
-            for (int i = 0; i < HEAD; ++i) {                        // d fc_mean.weight[i] = sum_rows d mu_i y
-#pragma unroll
-                for (int q = 0; q < 16; ++q) u[q] = dmu[i] * y[q];
-                ct_flush(L, u, part, a.P, i == 0 ? O_HW : O_EWS + a.D * kCtE + (i - 1) * kCtE, tid, r, g);
-            }
-            if (tid < 4 * HEAD) {                                   // d fc_mean.bias and the rows' part of d log_std: the two halves' sums
-                const int half = tid & 1, q = tid >> 1;
-                float sb = 0.0f;
-                for (int rr = 0; rr < 16; ++rr) sb += L.sx[q * kCtRows + half * 16 + rr];
-                float *dst = part + (long long)half * a.P + (q < HEAD ? O_HB + q : O_EWS + a.D * kCtE + (HEAD - 1) * kCtE + (q - HEAD));
-                *dst = sb;
-            } else if (tid >= 32 && tid < 32 + a.A) {               // the ratios of agent tid - 32: max, sum exp(r - max), sum exp(2 (r - max))
-                const int ag = tid - 32;
-                const int first = (int)((ag + a.A - (long long)tile * kCtRows % a.A) % a.A);
-                double mx = -1.0, e1 = 0.0, e2 = 0.0;
-                for (int rr = first; rr < kCtRows; rr += a.A) mx = L.dred[kCtRows + rr] > mx ? L.dred[kCtRows + rr] : mx;
-                for (int rr = first; rr < kCtRows; rr += a.A) {
-                    const double x = L.dred[kCtRows + rr];
-                    if (x >= 0.0 || x != x) {
-                        const double ex = exp(x - mx);
-                        e1 += ex;
-                        e2 += ex * ex;
-                    }
-                }
-                double *dst = a.losspart + (long long)tile * kActLossSlots + 1 + 3 * ag;
-                dst[0] = mx; dst[1] = e1; dst[2] = e2;
-            } else if (tid == 64) {
-                double acc = 0.0;
-                for (int rr = 0; rr < kCtRows; ++rr) acc += L.dred[rr];
-                a.losspart[(long long)tile * kActLossSlots] = acc;
-            }
-        }
-        ct_flush(L, dw, part, a.P, O_N2W, tid, r, g);
-        ct_flush(L, db, part, a.P, O_N2B, tid, r, g);
-        if constexpr (HEAD == 1) {
-            if ((tid & 127) == 0) {                                 // d head_b: the two halves' sums of dv
-                const int half = tid >> 7;
-                float sb = 0.0f;
-                for (int rr = 0; rr < 16; ++rr) sb += L.sc[half * 16 + rr];
-                float *dst = part + (long long)half * a.P + O_HB;
-                *dst = sb;
-            }
-        }
-        enc_matvec<3>(img + 11 * kCtMat, nullptr, L.b, L.c, nullptr, nullptr, w, lane);      // dh = W_2^T dff
-        __syncthreads();
-        enc_lds_load(L.c, r, g, t);
-        enc_lds_load(L.p, r, g, u);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {                          // gelu'(x) = Phi(x) + x phi(x)
-            const float xx = u[i];
-            const float dg = 0.5f * (1.0f + erff(xx * 0.7071067811865476f)) + xx * (0.3989422804014327f * expf(-0.5f * xx * xx));
-            t[i] = t[i] * dg;
-        }
-        enc_lds_store(L.c, r, g, t);
-        crow_store(stg + 8 * SA, kCtE, r, g, t);
-        __syncthreads();
-        enc_matvec<3>(img + 10 * kCtMat, nullptr, L.c, L.p, nullptr, nullptr, w, lane);      // W_1^T dh'
-        __syncthreads();
-        enc_lds_load(L.b, r, g, dy);
-        enc_lds_load(L.p, r, g, t);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            dy[i] += t[i];                                      // d x0'
-            dw[i] = 0.0f;
-            db[i] = 0.0f;
-        }
-        ct_ln_bwd(dy, xh1, rstd1, N.n1_w, g, dx, dw, db);       // dx = d(x0 + attn)
-        enc_lds_store(L.a, r, g, dx);
-        crow_store(stg + 6 * SA, kCtE, r, g, dx);
-        ct_flush(L, dw, part, a.P, O_N1W, tid, r, g);
-        ct_flush(L, db, part, a.P, O_N1B, tid, r, g);
-        enc_matvec<3>(img + 9 * kCtMat, nullptr, L.a, L.b, nullptr, stg + 4 * SA, w, lane);  // dv = W_o^T dattn
-        __syncthreads();
-        enc_matvec<3>(img + 8 * kCtMat, nullptr, L.b, L.c, nullptr, nullptr, w, lane);       // dz = W_v^T dv
-        __syncthreads();
-
-        // ---- token pass backward: alpha_j = exp(s_j - m) / l, ds_j = alpha_j (dz.t_j - dz.z), dt_j = alpha_j dz + ds_j kq
-        float dz[16], dkq[16], dt0[16];
-        enc_lds_load(L.c, r, g, dz);
-        s = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s = __builtin_fmaf(dz[i], z[i], s);
-        const float dzz = row_sum8(s);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            dw[i] = 0.0f;                                       // d ln_w, d ln_b over every token of the row
-            db[i] = 0.0f;
-        }
-        {
-            // token 0: its LayerNorm backward waits for W_q^T dq
-            ct_token(img + I_EW, N.eb[0], R.xs, a.D, N, g, xh, t);
-            s = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) s = __builtin_fmaf(dz[i], t[i], s);
-            const float al = expf(s0 - m) * il, ds = al * (row_sum8(s) - dzz);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                dt0[i] = __builtin_fmaf(ds, kq[i], al * dz[i]);
-                dkq[i] = ds * t[i];
-            }
-        }
-        float eo[4] = {0.f, 0.f, 0.f, 0.f}, ec[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // the thread's (feature, half) sums: bias, then the inputs
-        const int ef = tid & 127, eh = tid >> 7;
-        for (int j = 1; j < ntok; ++j) {
-            const float *x;
-            int n;
-            const float rs = ct_token_j(a, R, j, g, xh, t, x, n);
-            float sa = 0.0f, sd = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                sa = __builtin_fmaf(kq[i], t[i], sa);
-                sd = __builtin_fmaf(dz[i], t[i], sd);
-            }
-            const float al = expf(row_sum8(sa) - m) * il, ds = al * (row_sum8(sd) - dzz);
-            float dt[16], de[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                dt[i] = __builtin_fmaf(ds, kq[i], al * dz[i]);
-                dkq[i] = __builtin_fmaf(ds, t[i], dkq[i]);
-            }
-            ct_ln_bwd(dt, xh, rs, N.ln_w, g, de, dw, db);
-            crow_store(L.red, kCtRedLd, r, g, de);
-            if (g < n) L.sx[g * kCtRows + r] = x ? x[g] : 0.0f;
-            __syncthreads();
-            if (j < a.A) {
-#pragma unroll
-                for (int rr = 0; rr < 16; ++rr) {
-                    const int q = eh * 16 + rr;
-                    const float dd = L.red[q * kCtRedLd + ef];
-                    eo[0] += dd;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) eo[1 + k] = __builtin_fmaf(dd, L.sx[k * kCtRows + q], eo[1 + k]);
-                }
-            } else {
-#pragma unroll
-                for (int rr = 0; rr < 16; ++rr) {
-                    const int q = eh * 16 + rr;
-                    const float dd = L.red[q * kCtRedLd + ef];
-                    ec[0] += dd;
-#pragma unroll
-                    for (int k = 0; k < 5; ++k) ec[1 + k] = __builtin_fmaf(dd, L.sx[k * kCtRows + q], ec[1 + k]);
-                }
-            }
-            __syncthreads();
-        }
-        {
-            float *ph = part + (long long)eh * a.P;
-            ph[O_EBO + ef] = eo[0];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) ph[O_EWO + k * kCtE + ef] = eo[1 + k];
-            ph[O_EBC + ef] = ec[0];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) ph[O_EWC + k * kCtE + ef] = ec[1 + k];
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) dkq[i] *= 0.08838834764831845f;          // d(W_k^T q) = dkq / sqrt(128)
-        enc_lds_store(L.b, r, g, dkq);
-        crow_store(stg + 3 * SA, kCtE, r, g, dkq);
-        __syncthreads();
-        enc_matvec<3>(img + 7 * kCtMat, nullptr, L.b, L.c, nullptr, stg + 0 * SA, w, lane);  // dq = W_k d(W_k^T q)
-        __syncthreads();
-        enc_matvec<3>(img + 6 * kCtMat, nullptr, L.c, L.b, nullptr, nullptr, w, lane);       // W_q^T dq
-        __syncthreads();
-        {
-            float de[16];
-            enc_lds_load(L.a, r, g, u);
-            enc_lds_load(L.b, r, g, y);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) dt0[i] = (dt0[i] + u[i]) + y[i];
-            const float rs = ct_token(img + I_EW, N.eb[0], R.xs, a.D, N, g, xh, t);
-            ct_ln_bwd(dt0, xh, rs, N.ln_w, g, de, dw, db);
-            crow_store(L.red, kCtRedLd, r, g, de);
-            for (int k = g; k < a.D; k += 8) L.sx[k * kCtRows + r] = R.xs ? R.xs[k] : 0.0f;
-            __syncthreads();
-            float *ph = part + (long long)eh * a.P;
-            float sb = 0.0f;
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) sb += L.red[(eh * 16 + rr) * kCtRedLd + ef];
-            ph[O_EBS + ef] = sb;
-            for (int k = 0; k < a.D; ++k) {
-                float sw = 0.0f;
-#pragma unroll
-                for (int rr = 0; rr < 16; ++rr) sw = __builtin_fmaf(L.red[(eh * 16 + rr) * kCtRedLd + ef], L.sx[k * kCtRows + eh * 16 + rr], sw);
-                ph[O_EWS + k * kCtE + ef] = sw;
-            }
-            __syncthreads();
-        }
-        ct_flush(L, dw, part, a.P, O_LNW, tid, r, g);
-        ct_flush(L, db, part, a.P, O_LNB, tid, r, g);
+        dst[i] = v;
     }
 }
 
@@ -695,53 +360,23 @@ __global__ __launch_bounds__(64) void hns_critic_decide_kernel(const double *sum
 // every row); ESS = mean over agents of exp(2 logsumexp_batch(r) - logsumexp_batch(2 r)) / batch — of the ratio itself, as the reference writes it
 __global__ __launch_bounds__(64) void hns_actor_loss_kernel(const double *part, int tiles, int A, double n, double batch, const float *log_std, float *policy_loss,
                                                             float *entropy, float *ess) {
-    __shared__ double sm[kActLossSlots][64];
-    const int tid = threadIdx.x;
-    double acc = 0.0, mx[HNS_MAX_AGENTS], s1[HNS_MAX_AGENTS], s2[HNS_MAX_AGENTS];
-#pragma unroll
-    for (int q = 0; q < HNS_MAX_AGENTS; ++q) { mx[q] = -1.0; s1[q] = 0.0; s2[q] = 0.0; }
-    for (int i = tid; i < tiles; i += 64) {
-        const double *t = part + (long long)i * kActLossSlots;
-        acc += t[0];
-#pragma unroll
-        for (int q = 0; q < HNS_MAX_AGENTS; ++q) {
-            if (q >= A) continue;
-            const double m = t[1 + 3 * q], e1 = t[2 + 3 * q], e2 = t[3 + 3 * q];
-            if (e1 == 0.0) continue;                            // no row of this agent in the tile
-            const double M = m > mx[q] ? m : mx[q];
-            const double c0 = s1[q] == 0.0 ? 0.0 : exp(mx[q] - M), c1 = exp(m - M);
-            s1[q] = s1[q] * c0 + e1 * c1;
-            s2[q] = s2[q] * (c0 * c0) + e2 * (c1 * c1);
-            mx[q] = M;
-        }
-    }
-    sm[0][tid] = acc;
-#pragma unroll
-    for (int q = 0; q < HNS_MAX_AGENTS; ++q) { sm[1 + 3 * q][tid] = mx[q]; sm[2 + 3 * q][tid] = s1[q]; sm[3 + 3 * q][tid] = s2[q]; }
-    __syncthreads();
-    if (tid == 0) {
-        double tot = 0.0;
-        for (int i = 0; i < 64; ++i) tot += sm[0][i];
-        policy_loss[0] = (float)(-(double)kActDim * tot / n);
-        double ent = 0.0;
-        for (int i = 0; i < kActDim; ++i) ent += 0.5 + 0.9189385332046727 + (double)log_std[i];
-        entropy[0] = (float)ent;
-        double es = 0.0;
-        for (int q = 0; q < A; ++q) {
-            double M = -1.0, a1 = 0.0, a2 = 0.0;
-            for (int i = 0; i < 64; ++i) {
-                const double m = sm[1 + 3 * q][i], e1 = sm[2 + 3 * q][i], e2 = sm[3 + 3 * q][i];
-                if (e1 == 0.0) continue;
-                const double Mn = m > M ? m : M;
-                const double c0 = a1 == 0.0 ? 0.0 : exp(M - Mn), c1 = exp(m - Mn);
-                a1 = a1 * c0 + e1 * c1;
-                a2 = a2 * (c0 * c0) + e2 * (c1 * c1);
-                M = Mn;
-            }
-            es += a1 * a1 / a2;                                 // exp(2 (M + log a1) - (2 M + log a2))
-        }
-        ess[0] = (float)(es / (double)A / batch);
-    }
+#define CT_BODY_LOSS
+#define CT_LOSS_NLS 1
+#define CT_LOSS_ENTROPY ent
+#include "hns_policy_train_bodies.inc"
+#undef CT_LOSS_NLS
+#undef CT_LOSS_ENTROPY
+}
+
+// one actor per agent: log_std [A][4]; the rows' mean entropy is the mean over the agents of each agent's
+__global__ __launch_bounds__(64) void hns_actor_loss_agents_kernel(const double *part, int tiles, int A, double n, double batch, const float *log_std,
+                                                                   float *policy_loss, float *entropy, float *ess) {
+#define CT_LOSS_NLS A
+#define CT_LOSS_ENTROPY (ent / (double)A)
+#include "hns_policy_train_bodies.inc"
+#undef CT_LOSS_NLS
+#undef CT_LOSS_ENTROPY
+#undef CT_BODY_LOSS
 }
 
 // dW partials: per (row range, matrix) the 128 x 128 product dy^T x over the range's rows, and the column sums of dy
@@ -900,6 +535,16 @@ __global__ __launch_bounds__(256) void hns_encoder_reduce_kernel(const float *gp
     ct_reduce<false>(gpart, splits, tpart, nt, P, gblocks, g, D, blockpart, 0, 0.0);
 }
 
+// one actor per agent: workgroup (b, agent) is the reduce kernel's block b on the agent's weight-gradient partials (`spa` row ranges), partial rows
+// (`ntpa`) and slice of the stacked gradient tensors; the per-block sums of squares of all agents lie side by side for ONE norm over everything
+__global__ __launch_bounds__(256) void hns_actor_reduce_agents_kernel(const float *gpart, int spa, const float *tpart, int ntpa, int P, int gblocks, const CtGrad g0,
+                                                                      int D, double *blockpart, double ls_add) {
+    const int agent = blockIdx.y;
+    const CtGrad g = enc_agent_slice(g0, D, kActDim, agent);
+    ct_reduce<true>(gpart + (long long)agent * spa * 6 * kCtGemmOut, spa, tpart + (long long)agent * ntpa * P, ntpa, P, gblocks, g, D,
+                    blockpart + (long long)agent * gridDim.x, kActDim, ls_add);
+}
+
 __global__ __launch_bounds__(256) void hns_critic_norm_kernel(const double *blockpart, int nb, float *grad_norm) {
     __shared__ double sm[256];
     const int tid = threadIdx.x;
@@ -940,6 +585,31 @@ bool ct_plan(int64_t rows, int32_t D, int32_t A, int32_t K, CtPlan &p, int heads
     p.o_loss = o; o += ct_up((size_t)p.tiles * (heads > 1 ? hns::kActLossSlots : 5) * sizeof(double));
     p.o_block = o; o += ct_up((size_t)hns::kCtMaxBlocks * sizeof(double));
     p.o_img = o; o += ct_up((size_t)hns::ct_img_floats(D) * sizeof(float));
+    p.o_tile = o; o += ct_up((size_t)p.tiles * 2 * p.P * sizeof(float));
+    p.o_gemm = o; o += ct_up((size_t)p.splits * 6 * hns::kCtGemmOut * sizeof(float));
+    p.o_stage = o; o += ct_up((size_t)12 * p.stage_rows * hns::kCtE * sizeof(float));
+    p.total = o;
+    return true;
+}
+
+// One actor per agent: `batch` positions per agent in tiles of one agent, numbered agent-major.  An agent's tile count is padded to a whole number
+// of the weight-gradient kernel's row ranges (tps tiles each; the padding tiles' rows are not live and stage dy = 0), so no range straddles two
+// agents; an image and a set of per-block sums per agent.
+bool ct_plan_agents(int64_t rows, int32_t D, int32_t A, int32_t K, CtPlan &p) {
+    if (A < 1 || A > HNS_MAX_AGENTS || rows < A || rows % A || !ct_plan(rows, D, A, K, p, hns::kActDim)) return false;
+    const long long tpa = (rows / A + hns::kCtRows - 1) / hns::kCtRows;
+    long long spa = std::max(1, hns::kCtMaxSplits / A);
+    p.tps = (tpa + spa - 1) / spa;
+    spa = (tpa + p.tps - 1) / p.tps;
+    p.tiles = (long long)A * spa * p.tps;
+    p.splits = (long long)A * spa;
+    p.stage_rows = p.tiles * hns::kCtRows;
+    if (p.stage_rows > ((int64_t)1 << 31) - 64) return false;
+    size_t o = 0;
+    p.o_ctl = o; o += ct_up(64 * sizeof(float));
+    p.o_loss = o; o += ct_up((size_t)p.tiles * hns::kActLossSlots * sizeof(double));
+    p.o_block = o; o += ct_up((size_t)A * (p.gblocks + p.tblocks) * sizeof(double));
+    p.o_img = o; o += ct_up((size_t)A * hns::ct_img_floats(D) * sizeof(float));
     p.o_tile = o; o += ct_up((size_t)p.tiles * 2 * p.P * sizeof(float));
     p.o_gemm = o; o += ct_up((size_t)p.splits * 6 * hns::kCtGemmOut * sizeof(float));
     p.o_stage = o; o += ct_up((size_t)12 * p.stage_rows * hns::kCtE * sizeof(float));
@@ -1022,16 +692,18 @@ int ct_check_obs(const char *fn, const Batch &b, bool others) {
 // heads 0: the encoder op, whose plan is ct_plan_encoder's (`backward`: hns_encoder_backward's)
 template <typename Batch>
 int ct_plan_call(const char *fn, const Batch &b, std::initializer_list<const float *> outs, void *workspace, size_t workspace_bytes, int32_t self_dim,
-                 int32_t num_agents, int32_t num_cylinders, int heads, CtPlan &p, hns::CtArgs &a, bool backward = true) {
+                 int32_t num_agents, int32_t num_cylinders, int heads, CtPlan &p, hns::CtArgs &a, bool backward = true, bool agents = false) {
     if (b.index && !hns_aligned(b.index, 8)) return hns_fail(fn, "misaligned index");
     bool ok = hns_aligned(workspace, 256);
     for (const float *o : outs) ok = ok && hns_aligned(o, 4);
     if (!ok) return hns_fail(fn, "misaligned output (scalars 4 bytes, workspace 256)");
     const int64_t rows = b.batch * num_agents;
-    if (heads == 0 ? !ct_plan_encoder(rows, self_dim, num_agents, num_cylinders, backward, p) : !ct_plan(rows, self_dim, num_agents, num_cylinders, p, heads))
+    if (agents ? !ct_plan_agents(rows, self_dim, num_agents, num_cylinders, p)
+               : (heads == 0 ? !ct_plan_encoder(rows, self_dim, num_agents, num_cylinders, backward, p) : !ct_plan(rows, self_dim, num_agents, num_cylinders, p, heads)))
         return hns_fail(fn, "invalid shape");
     if (workspace_bytes < p.total)
-        return hns_fail(fn, heads > 1    ? "workspace too small (hns_actor_train_workspace_bytes)"
+        return hns_fail(fn, agents       ? "workspace too small (hns_actor_train_agents_workspace_bytes)"
+                            : heads > 1  ? "workspace too small (hns_actor_train_workspace_bytes)"
                             : heads == 1 ? "workspace too small (hns_critic_train_workspace_bytes)"
                                          : "workspace too small (hns_encoder_workspace_bytes)");
 
@@ -1132,7 +804,9 @@ int ct_critic_call(const char *fn, CtMode mode, const hns_policy_net *critic, co
 
 // The actor's two entries over one body.  global: the rows' backward weight and policy_loss are scaled by 1 / global_rows instead of 1 / rows (this
 // rank's share of the loss and of the gradient: the ranks' shares add up), the entropy term's constant gradient joins by `entropy_share` of it.
-int ct_actor_call(const char *fn, bool global, const hns_policy_net *actor, const hns_actor_batch *batch, int32_t self_dim, int32_t num_agents,
+// `agents`: hns_actor_train_grad_agents — `actor` and `grads` hold the stacked tensors, every launch but the weight gradients' and the norm's is the
+// per-agent kernel (same order, same count).
+int ct_actor_call(const char *fn, bool global, bool agents, const hns_policy_net *actor, const hns_actor_batch *batch, int32_t self_dim, int32_t num_agents,
                   int32_t num_cylinders, double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
                   float *grad_norm, float *log_probs, int64_t global_rows, double entropy_share, void *workspace, size_t workspace_bytes, void *stream) {
     if (int rc = ct_check_shape(fn, *batch, self_dim, num_agents, num_cylinders)) return rc;
@@ -1148,7 +822,7 @@ int ct_actor_call(const char *fn, bool global, const hns_policy_net *actor, cons
         !hns_aligned(batch->advantages, 4))
         return hns_fail(fn, "action / log_probs_old / advantages missing or misaligned");
     if (int rc = ct_plan_call(fn, *batch, {policy_loss, entropy, ess, grad_norm, log_probs}, workspace, workspace_bytes, self_dim, num_agents, num_cylinders,
-                              hns::kActDim, p, a))
+                              hns::kActDim, p, a, true, agents))
         return rc;
     a.logp_old = batch->log_probs_old; a.adv = batch->advantages; a.action = batch->action;
     a.clip_lo = (float)(1.0 - clip_param); a.clip_hi = (float)(1.0 + clip_param);
@@ -1158,7 +832,32 @@ int ct_actor_call(const char *fn, bool global, const hns_policy_net *actor, cons
     const hipStream_t st = static_cast<hipStream_t>(stream);
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<true, hns::kActDim>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::CtLds));
+    static const hipError_t attr_ag = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_actor_agents_kernel),
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::CtLds));
     HNS_CHECK_HIP(attr);
+    HNS_CHECK_HIP(attr_ag);
+    if (agents) {
+        const int A = num_agents, nb = p.gblocks + p.tblocks;
+        unsigned char *ws = static_cast<unsigned char *>(workspace);
+        hipLaunchKernelGGL(hns::hns_actor_pack_agents_kernel, dim3(256, A), dim3(256), 0, st, a.net, a.D, reinterpret_cast<float *>(ws + p.o_img));
+        HNS_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(hns::hns_actor_agents_kernel, dim3((unsigned)(p.tiles / A), A), dim3(hns::kCtThreads), sizeof(hns::CtLds), st, a);
+        HNS_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(hns::hns_actor_loss_agents_kernel, dim3(1), dim3(64), 0, st, a.losspart, (int)p.tiles, A, (double)a.rows, (double)batch->batch,
+                           actor->log_std, policy_loss, entropy, ess);
+        HNS_CHECK_HIP(hipGetLastError());
+        float *gpart = reinterpret_cast<float *>(ws + p.o_gemm);
+        hipLaunchKernelGGL(hns::hns_critic_wgrad_kernel, dim3((unsigned)p.splits, 6), dim3(256), 0, st, a.stage, a.stage_rows, (int)p.tiles, (int)p.tps, gpart);
+        HNS_CHECK_HIP(hipGetLastError());
+        double *blockpart = reinterpret_cast<double *>(ws + p.o_block);
+        // each agent's d log_std takes its share of the mean entropy's constant gradient
+        hipLaunchKernelGGL(hns::hns_actor_reduce_agents_kernel, dim3(nb, A), dim3(256), 0, st, gpart, (int)(p.splits / A), a.tilepart, (int)(2 * p.tiles / A), p.P,
+                           p.gblocks, g, a.D, blockpart, -entropy_coef / (double)A);
+        HNS_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(hns::hns_critic_norm_kernel, dim3(1), dim3(256), 0, st, blockpart, nb * A, grad_norm);
+        HNS_CHECK_HIP(hipGetLastError());
+        return HNS_OK;
+    }
     if (int rc = ct_launch_pack(st, a, p, workspace)) return rc;
     hipLaunchKernelGGL((hns::hns_critic_kernel<true, hns::kActDim>), dim3((unsigned)p.tiles), dim3(hns::kCtThreads), sizeof(hns::CtLds), st, a);
     HNS_CHECK_HIP(hipGetLastError());
@@ -1251,7 +950,7 @@ int hns_actor_train_grad(const hns_policy_net *actor, const hns_actor_batch *bat
                          float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream) {
     const char *fn = "hns_actor_train_grad";
     if (!actor || !batch || !grads || !policy_loss || !entropy || !ess || !grad_norm || !workspace) return hns_fail(fn, "null pointer");
-    return ct_actor_call(fn, false, actor, batch, self_dim, num_agents, num_cylinders, clip_param, entropy_coef, grads, policy_loss, entropy, ess, grad_norm,
+    return ct_actor_call(fn, false, false, actor, batch, self_dim, num_agents, num_cylinders, clip_param, entropy_coef, grads, policy_loss, entropy, ess, grad_norm,
                          log_probs, 0, 1.0, workspace, workspace_bytes, stream);
 }
 
@@ -1261,8 +960,22 @@ int hns_actor_train_grad_global(const hns_policy_net *actor, const hns_actor_bat
                                 double entropy_share) {
     const char *fn = "hns_actor_train_grad_global";
     if (!actor || !batch || !grads || !policy_loss || !entropy || !ess || !workspace) return hns_fail(fn, "null pointer");
-    return ct_actor_call(fn, true, actor, batch, self_dim, num_agents, num_cylinders, clip_param, entropy_coef, grads, policy_loss, entropy, ess, grad_norm,
+    return ct_actor_call(fn, true, false, actor, batch, self_dim, num_agents, num_cylinders, clip_param, entropy_coef, grads, policy_loss, entropy, ess, grad_norm,
                          log_probs, global_rows, entropy_share, workspace, workspace_bytes, stream);
+}
+
+size_t hns_actor_train_agents_workspace_bytes(int64_t rows, int32_t self_dim, int32_t num_agents, int32_t num_cylinders) {
+    CtPlan p;
+    return ct_plan_agents(rows, self_dim, num_agents, num_cylinders, p) ? p.total : 0;
+}
+
+int hns_actor_train_grad_agents(const hns_policy_net *actors, const hns_actor_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                                double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
+                                float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "hns_actor_train_grad_agents";
+    if (!actors || !batch || !grads || !policy_loss || !entropy || !ess || !grad_norm || !workspace) return hns_fail(fn, "null pointer");
+    return ct_actor_call(fn, false, true, actors, batch, self_dim, num_agents, num_cylinders, clip_param, entropy_coef, grads, policy_loss, entropy, ess,
+                         grad_norm, log_probs, 0, 1.0, workspace, workspace_bytes, stream);
 }
 
 size_t hns_encoder_workspace_bytes(int64_t rows, int32_t self_dim, int32_t num_agents, int32_t num_cylinders, int32_t backward) {

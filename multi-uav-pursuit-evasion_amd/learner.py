@@ -21,6 +21,9 @@ runs — not the hot path).  DESIGN.md §7.6.
 last critic state, the PPO loop over (env, segment) pairs through rnn_train.update_actor_rnn / update_critic_rnn.  `DeviceLearner` itself keeps
 refusing a recurrent policy.
 
+`PerAgentDeviceLearner` is the same for share_actor: False (one actor per agent): the actor block through
+actor_train.update_actor_per_agent over the stacked tensors, everything else DeviceLearner's.  `DeviceLearner` keeps refusing that configuration.
+
 `DeviceLearner(..., group=)` is the data-parallel learner: W ranks, each with the rollout of its own env slice, perform ONE
 PPO update per minibatch on the union of their minibatches — the critic's branch decided on the union's sums, every mean over the union's
 rows, the norm taken from the summed gradient, the predictor's ranks weighted by their selected windows.
@@ -308,6 +311,12 @@ class DeviceLearner:
         """mappo.py:365-367: the critic's value of the last step's next observation, ONE value_only call."""
         return self.policy.forward(*next_obs_last, value_only=True).value
 
+    # the actor block's two pieces (PerAgentDeviceLearner: the *_per_agent ones)
+    _ACTOR_WORKSPACE = "hns_actor_train_workspace_bytes"
+
+    def _update_actor(self, *args, **kw):
+        return actor_train.update_actor(*args, **kw)
+
     def _ppo_loop(self, xs, xo, xc, action, log_probs, adv, state_value, ret, table, global_rows=None, recurrent=None):
         """mappo.py:446-461: per epoch one permutation, per minibatch the actor's update and then the critic's.  On the device: no host
         synchronisation — cached workspaces, scalars written into `table`'s rows, no index check.  `global_rows` (the data-parallel path):
@@ -320,7 +329,7 @@ class DeviceLearner:
         if dev.type == "cuda":
             lib = abi.load_library()
             rows = (N * T // self.num_minibatches) * A
-            na, nc = lib.hns_actor_train_workspace_bytes(rows, D, A, K), lib.hns_critic_train_workspace_bytes(rows, D, A, K)
+            na, nc = getattr(lib, self._ACTOR_WORKSPACE)(rows, D, A, K), lib.hns_critic_train_workspace_bytes(rows, D, A, K)
             if rows < 1 or na == 0 or nc == 0:
                 raise ValueError(f"shape outside the kernels' limits: {rows} rows per minibatch, self_dim {D}, {A} agents, {K} cylinders")
             ws_a, ws_c = self._workspace("actor", na, dev), self._workspace("critic", nc, dev)
@@ -329,8 +338,8 @@ class DeviceLearner:
             for idx in tp_train.minibatches(N * T, self.num_minibatches, dev, self.generator):
                 out_a = table[m, :len(ACTOR_COLUMNS)] if ws_a is not None else None
                 out_c = table[m, len(ACTOR_COLUMNS):] if ws_c is not None else None
-                sa = actor_train.update_actor(self.actor, xs, xo, xc, action, log_probs, adv, self.actor_opt, index=idx, cfg=self.cfg,
-                                              workspace=ws_a, out=out_a, **kw_a)
+                sa = self._update_actor(self.actor, xs, xo, xc, action, log_probs, adv, self.actor_opt, index=idx, cfg=self.cfg,
+                                        workspace=ws_a, out=out_a, **kw_a)
                 sc = critic_train.update_critic(self.critic, xs, xo, xc, state_value, ret, self.critic_opt, index=idx, cfg=self.cfg,
                                                 workspace=ws_c, out=out_c, **kw_c)
                 if ws_a is None:                                 # CPU: the updates return their scalars
@@ -396,6 +405,53 @@ class DeviceLearner:
                 getattr(self, name).load_state_dict(sd[key])
         if self.group is not None:                               # one state on every rank: rank 0's
             self._broadcast_state()
+
+
+def _without_share_actor(cfg):
+    """The algo cfg as a dict without its share_actor key: what the shared critic's functions (and policy.check_config behind them) take."""
+    if cfg is None:
+        return None
+    keys = list(cfg.keys()) if hasattr(cfg, "keys") else list(vars(cfg))
+    get = PT.getter(cfg)
+    return {k: get(k) for k in keys if k != "share_actor"}
+
+
+class PerAgentDeviceLearner(DeviceLearner):
+    """MAPPOPolicy's training half with share_actor: False (one actor per agent): `DeviceLearner`'s train_op / train_rollout,
+    info row and state_dict, with the actor block through actor_train.update_actor_per_agent (one `hns_actor_train_grad_agents` call and one
+    ClippedAdam step over the 23 stacked tensors per minibatch, a cached workspace, no host synchronisation in the PPO loop).  The critic
+    block, the targets, the predictor and the bootstrap value are DeviceLearner's, unchanged.
+
+    actor: the STACKED actor's parameters (every tensor [A, ...]: the reference's actor_params; "actor_params" of state_dict()), live tensors
+    updated in place; device_policy: a PerAgentDevicePolicy over the same tensors (built when None).  Refused before anything is built:
+    group= (NotImplementedError), a recurrent policy and whatever PerAgentDevicePolicy refuses (PolicyConfigError), a device_policy that is
+    not per-agent, and the cfg refusals of DeviceLearner with their exception types."""
+
+    _ACTOR_WORKSPACE = "hns_actor_train_agents_workspace_bytes"
+
+    def _update_actor(self, *args, **kw):
+        return actor_train.update_actor_per_agent(*args, **kw)
+
+    def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, agent_name="drone", generator=None, device_policy=None, group=None):
+        if group is not None:
+            raise NotImplementedError("PerAgentDeviceLearner takes no group=: data-parallel training of per-agent actors is not implemented")
+        if getattr(device_policy, "recurrent", False):
+            raise P.PolicyConfigError("PerAgentDeviceLearner updates the non-recurrent networks only: per-agent actors with actor.rnn / critic.rnn are "
+                                      "not implemented")
+        if device_policy is not None and not getattr(device_policy, "per_agent", False):
+            raise P.PolicyConfigError("PerAgentDeviceLearner needs a PerAgentDevicePolicy (a shared actor is DeviceLearner's)")
+        actor_train.actor_cfg_per_agent(cfg)
+        shared = _without_share_actor(cfg)
+        critic_train.critic_cfg(shared)
+        self._configure(actor, critic, shared, tp_net, value_normalizer, agent_name, generator)
+        self.actor_opt = actor_train.make_optimizer_per_agent(actor, shared)
+        self.critic_opt = critic_train.make_optimizer(critic, shared)
+        self.policy = device_policy if device_policy is not None else P.PerAgentDevicePolicy(actor, critic, shared, agent_name=agent_name)
+
+    def _optimizer_makers(self):
+        return (("actor_opt", "actor_opt", lambda: actor_train.make_optimizer_per_agent(self.actor, self.cfg)),
+                ("critic_opt", "critic_opt", lambda: critic_train.make_optimizer(self.critic, self.cfg)),
+                ("tp_opt", "TP_opt", lambda: tp_train.TPAdam(tp_train.parameters(self.tp_net), lr=1e-4)))
 
 
 class RecurrentDeviceLearner(DeviceLearner):

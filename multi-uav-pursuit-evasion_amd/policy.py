@@ -18,7 +18,12 @@ CPU tensors run a torch restatement of the reference's statements (tests, gloo r
 `RecurrentDevicePolicy` is the `actor.rnn` / `critic.rnn` configuration (a GRU behind each encoder, modules/rnn.py): encoder -> one GRU step ->
 head for both networks in ONE call of `hns_policy_forward_rnn`, the two states carried on the device; its `act_step` runs
 the actor's half alone with the actor's state (`hns_policy_act_rnn`: evaluation).  `DevicePolicy` keeps refusing that
-configuration."""
+configuration.
+
+`PerAgentDevicePolicy` is the `share_actor: False` configuration (one actor per agent: the stacked `actor_params`, every tensor [A, ...]; the
+critic shared) on `hns_policy_forward_agents` / `hns_policy_act_agents`: a tile is 32 envs of ONE agent and reads that agent's weight image,
+and agent a's rows are bit for bit `DevicePolicy`'s with slice a as the shared actor.  `DevicePolicy` keeps refusing
+stacked parameters."""
 import collections
 import ctypes as C
 import math
@@ -188,14 +193,17 @@ class DevicePolicy:
 
     def __init__(self, actor_params, critic, cfg=None, device=None, seed=0, agent_name="drone"):
         check_config(cfg)
-        self.actor_p = parse_parameters(actor_params, ACTOR_NAMES, "actor")
-        self.critic_p = parse_parameters(critic, CRITIC_NAMES, "critic")
+        self._setup(parse_parameters(actor_params, ACTOR_NAMES, "actor"), parse_parameters(critic, CRITIC_NAMES, "critic"), device, seed, agent_name)
+
+    def _setup(self, actor_p, critic_p, device, seed, agent_name):
+        """Everything behind the parsing: the device, the shapes the two networks must agree on, the packed image and the noise."""
+        self.actor_p, self.critic_p = actor_p, critic_p
         ds = {v.device for v in (*self.actor_p.values(), *self.critic_p.values())}
         self.device = torch.device(device) if device is not None else next(iter(ds))
         if ds != {self.device}:
             self.actor_p = {k: v.detach().to(self.device).contiguous() for k, v in self.actor_p.items()}
             self.critic_p = {k: v.detach().to(self.device).contiguous() for k, v in self.critic_p.items()}
-        self.self_dim = int(self.actor_p["embed_self_w"].shape[1])
+        self.self_dim = int(self.actor_p["embed_self_w"].shape[-1])
         if int(self.critic_p["embed_self_w"].shape[1]) != self.self_dim:
             raise PolicyConfigError("actor and critic see state_self rows of different widths")
         if ("embed_others_w" in self.actor_p) != ("embed_others_w" in self.critic_p):
@@ -207,7 +215,7 @@ class DevicePolicy:
         self._generator = None
         if self.device.type == "cuda":
             self._lib = abi.load_library()
-            nbytes = self._lib.hns_policy_packed_bytes(self.self_dim)
+            nbytes = self._packed_bytes()
             self.packed = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             self.counter = torch.zeros(1, dtype=torch.int64, device=self.device)   # the Philox call counter (uint64 on the device)
         else:
@@ -224,6 +232,18 @@ class DevicePolicy:
         return cls(checkpoint["actor_params"], checkpoint["critic"], cfg=cfg, device=device, seed=seed)
 
     # ---- packed image
+    _PACK, _FORWARD, _ACT = "hns_policy_pack", "hns_policy_forward", "hns_policy_act"     # the C entries (PerAgentDevicePolicy: the *_agents ones)
+
+    def _packed_bytes(self):
+        return self._lib.hns_policy_packed_bytes(self.self_dim)
+
+    def _pack_agents(self):
+        """hns_policy_pack's num_agents: only > 1 matters (the networks have the state_others embedding)."""
+        return 2 if self.has_others else 1
+
+    def _cpu_forward(self, xs, xo, xc, eps=None, deterministic=False, value_only=False):
+        return torch_forward(self.actor_p, self.critic_p, xs.unsqueeze(2), xo, xc, eps, deterministic, value_only, self._generator)
+
     def _tensors(self):
         return [*self.actor_p.values(), *self.critic_p.values()]
 
@@ -244,8 +264,8 @@ class DevicePolicy:
         a, c = self._net(self.actor_p), self._net(self.critic_p)
         with torch.cuda.device(self.device):
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            rc = self._lib.hns_policy_pack(C.byref(a), C.byref(c), self.self_dim, 2 if self.has_others else 1, self.packed.data_ptr(), st)
-        self._check(rc, "hns_policy_pack")
+            rc = getattr(self._lib, self._PACK)(C.byref(a), C.byref(c), self.self_dim, self._pack_agents(), self.packed.data_ptr(), st)
+        self._check(rc, self._PACK)
         self._stamp = stamp
 
     @property
@@ -308,7 +328,7 @@ class DevicePolicy:
             raise ValueError(f"eps must be float32 [{E}, {A}, {ACTION_DIM}] on {self.device}")
         if self.device.type != "cuda":
             with torch.no_grad():
-                return torch_forward(self.actor_p, self.critic_p, xs.unsqueeze(2), xo, xc, eps, deterministic, value_only, self._generator)
+                return self._cpu_forward(xs, xo, xc, eps, deterministic, value_only)
         self.refresh()
         xs, xo, xc, io = self._io(xs, xo, xc)
         eps = eps.contiguous() if eps is not None else None
@@ -324,9 +344,9 @@ class DevicePolicy:
         flags = (abi.HNS_POLICY_DETERMINISTIC if deterministic else 0) | (abi.HNS_POLICY_VALUE_ONLY if value_only else 0)
         with torch.cuda.device(dev):
             st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            rc = self._lib.hns_policy_forward(self.packed.data_ptr(), self.self_dim, E, A, xc.shape[2], C.byref(io), flags, self.seed,
-                                              self.counter.data_ptr(), st)
-        self._check(rc, "hns_policy_forward")
+            rc = getattr(self._lib, self._FORWARD)(self.packed.data_ptr(), self.self_dim, E, A, xc.shape[2], C.byref(io), flags, self.seed,
+                                                   self.counter.data_ptr(), st)
+        self._check(rc, self._FORWARD)
         return PolicyOutput(action, log_prob, value, loc)
 
     def act(self, obs_self, obs_others, obs_cylinders, out=None):
@@ -340,7 +360,7 @@ class DevicePolicy:
             raise ValueError(f"out must be a contiguous float32 [{E}, {A}, {ACTION_DIM}] tensor on {self.device}")
         if self.device.type != "cuda":
             with torch.no_grad():
-                action = torch_forward(self.actor_p, self.critic_p, xs.unsqueeze(2), xo, xc, deterministic=True).action
+                action = self._cpu_forward(xs, xo, xc, deterministic=True).action
             return action if out is None else out.copy_(action)
         self.refresh()
         xs, xo, xc, io = self._io(xs, xo, xc)
@@ -348,8 +368,8 @@ class DevicePolicy:
         io.action = action.data_ptr()
         with torch.cuda.device(self.device):
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            rc = self._lib.hns_policy_act(self.packed.data_ptr(), self.self_dim, E, A, xc.shape[2], C.byref(io), st)
-        self._check(rc, "hns_policy_act")
+            rc = getattr(self._lib, self._ACT)(self.packed.data_ptr(), self.self_dim, E, A, xc.shape[2], C.byref(io), st)
+        self._check(rc, self._ACT)
         return action
 
     @staticmethod
@@ -369,6 +389,118 @@ class DevicePolicy:
     def value(self, tensordict):
         """value_op: the critic's state_value [E, A, 1] (train_op's next_value)."""
         return self.forward(*self._obs(tensordict), value_only=True).value
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# one actor per agent (share_actor: False): the parameters stacked over the agents (mappo.py:148-152), the actor vmapped over the agent axis
+# (mappo.py:243-246); the critic stays shared.  DESIGN.md §7.16
+def parse_parameters_per_agent(params, what="actor"):
+    """(the hns_policy_net fields of the STACKED actor, every tensor [A, ...]; A) from reference parameter names.  Each agent's slice is held
+    to `parse_parameters`' checks; tensors that are not stacked, or whose leading sizes disagree, raise PolicyConfigError."""
+    flat = {_strip(k): v for k, v in _flatten(params).items()}
+    w = flat.get("encoder.attn.in_proj_weight")
+    if w is not None and w.dim() == 2:
+        raise PolicyConfigError(f"{what}: the parameters have no leading agent dimension (a shared actor is DevicePolicy's)")
+    sizes = {int(v.shape[0]) if v.dim() else None for v in flat.values()}
+    if len(sizes) != 1 or None in sizes:
+        raise PolicyConfigError(f"{what}: every stacked tensor needs the same leading agent dimension, not {sorted(str(s) for s in sizes)}")
+    A = sizes.pop()
+    if not 1 <= A <= abi.HNS_MAX_AGENTS:
+        raise PolicyConfigError(f"{what}: {A} stacked actors outside [1, {abi.HNS_MAX_AGENTS}]")
+    first = parse_parameters({k: v[0] for k, v in flat.items()}, ACTOR_NAMES, what)      # names, shapes, dtypes: every slice has slice 0's
+    if ("embed_others_w" in first) != (A > 1):
+        raise PolicyConfigError(f"{what}: {A} stacked actors {'need' if A > 1 else 'have no'} state_others embedding")
+    return {ACTOR_NAMES[k]: v for k, v in flat.items()}, A
+
+
+def agent_slice(actor_p, a):
+    """Agent a's network out of the stacked one: views, a `parse_parameters` dict of its own."""
+    return {k: v[a] for k, v in actor_p.items()}
+
+
+def torch_forward_per_agent(actors, critic, xs, xo, xc, eps=None, deterministic=False, value_only=False, generator=None):
+    """The CPU path of PerAgentDevicePolicy: `torch_forward` with the stacked actor — a loop over the agents' slices through `_encoder` and
+    `_heads`.  Each slice runs on the WHOLE observation and keeps its own agent's rows, so agent a's rows are exactly `torch_forward`'s with
+    slice a as the shared actor (a CPU matrix product's bits depend on its shape; this path serves tests, not speed)."""
+    value = F.linear(_encoder(critic, xs, xo, xc), critic["head_w"], critic["head_b"])
+    if value_only:
+        return PolicyOutput(None, None, value, None)
+    E, A = xs.shape[:2]
+    if eps is None and not deterministic:
+        eps = torch.randn((E, A, ACTION_DIM), dtype=xs.dtype, device=xs.device, generator=generator)
+    rows = []
+    for a in range(A):
+        p = agent_slice(actors, a)
+        rows.append([t[:, a:a + 1] for t in _heads(p, _encoder(p, xs, xo, xc), value, eps, deterministic, generator)])
+    action, log_prob, _, loc = (torch.cat(t, dim=1) for t in zip(*rows))
+    return PolicyOutput(action, log_prob, value, loc)
+
+
+def _without_share_actor(cfg):
+    """The algo cfg with share_actor taken out (what check_config refuses for DevicePolicy and PerAgentDevicePolicy implements)."""
+    if cfg is None:
+        return None
+    get = cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
+    return {k: get(k) for k in ("critic_input", "actor", "critic") if get(k, None) is not None}
+
+
+def check_config_per_agent(cfg):
+    """`check_config` for one actor per agent: everything it refuses but share_actor: False; share_actor: True is refused instead."""
+    if cfg is not None:
+        get = cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
+        if get("share_actor", False):
+            raise PolicyConfigError("share_actor: True with one actor per agent; the shared actor is DevicePolicy's")
+    check_config(_without_share_actor(cfg))
+
+
+class PerAgentDevicePolicy(DevicePolicy):
+    """MAPPOPolicy with share_actor: False — one actor per pursuer, the critic shared — in one HIP launch per call.
+
+    `PerAgentDevicePolicy(actor_params, critic)`: actor_params the STACKED actor (TensorDictParams / TensorDict / mapping, every leaf
+    [A, ...], as the reference's `actor_params`), critic as for DevicePolicy.  `forward`, `act`, `__call__` and `value` are DevicePolicy's,
+    on `hns_policy_forward_agents` / `hns_policy_act_agents`: a tile is 32 envs of one agent and reads that agent's image, and row (e, a)
+    is bit for bit DevicePolicy's with agent a's slice as the shared actor.  `scale` is [A, 4].  Refused with PolicyConfigError: whatever
+    DevicePolicy refuses except share_actor: False; share_actor: True; tensors that are not stacked or whose leading sizes disagree; an
+    observation with another number of agents (ValueError, as the other shape refusals)."""
+    per_agent = True
+    _PACK, _FORWARD, _ACT = "hns_policy_pack_agents", "hns_policy_forward_agents", "hns_policy_act_agents"
+
+    def __init__(self, actor_params, critic, cfg=None, device=None, seed=0, agent_name="drone"):
+        check_config_per_agent(cfg)
+        actor_p, self.num_agents = parse_parameters_per_agent(actor_params, "actor")
+        self._setup(actor_p, parse_parameters(critic, CRITIC_NAMES, "critic"), device, seed, agent_name)
+
+    def _packed_bytes(self):
+        return self._lib.hns_policy_packed_agents_bytes(self.self_dim, self.num_agents)
+
+    def _pack_agents(self):
+        return self.num_agents
+
+    def _cpu_forward(self, xs, xo, xc, eps=None, deterministic=False, value_only=False):
+        return torch_forward_per_agent(self.actor_p, self.critic_p, xs.unsqueeze(2), xo, xc, eps, deterministic, value_only, self._generator)
+
+    def _validate(self, xs, xo, xc):
+        xs, xo, xc = super()._validate(xs, xo, xc)
+        if xs.shape[1] != self.num_agents:
+            raise ValueError(f"the observation has {xs.shape[1]} agents, the policy {self.num_agents} actors")
+        return xs, xo, xc
+
+    @property
+    def scale(self):
+        """exp(log_std) per agent, [A, 4], as the kernel uses it (device: read from the agents' packed images)."""
+        if self.device.type != "cuda":
+            return torch.exp(self.actor_p["log_std"].detach())
+        self.refresh()
+        img = self.packed.view(torch.float32).view(self.num_agents + 1, -1)
+        off = 6 * EMBED_DIM * EMBED_DIM + 18 * EMBED_DIM + 4          # P_SCALE of hns_policy.hip
+        return img[:self.num_agents, off:off + ACTION_DIM]
+
+
+def random_parameters_per_agent(self_dim, num_agents, seed=0):
+    """`random_parameters` for share_actor: False: (the stacked actor — `num_agents` independently initialised actors, every tensor
+    [A, ...] — and the critic) in the reference's names, CPU fp32."""
+    nets = [random_parameters(self_dim, num_agents, seed + 1000 * a) for a in range(num_agents)]
+    return {k: torch.stack([n[0][k] for n in nets]).contiguous() for k in nets[0][0]}, nets[0][1]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
