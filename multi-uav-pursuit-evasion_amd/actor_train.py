@@ -16,7 +16,8 @@ by 1 / global_rows and the entropy term by `entropy_share`, the gradients land i
 all-reduced and its norm taken before the step.
 
 The `*_per_agent` functions are the same update with share_actor: False (one actor per agent: the reference's stacked `actor_params`, every
-tensor [A, ...]; update_actor's else branch, mappo.py:288-291) on ONE call of `hns_actor_train_grad_agents`; DESIGN.md §7.16.
+tensor [A, ...]; update_actor's else branch, mappo.py:288-291) on ONE call of `hns_actor_train_grad_agents`; DESIGN.md §7.16.  Both forms
+run ONE CPU function (`_torch_loss_and_grad`) and ONE device half (`_device_loss_and_grad`, handed the entry and its workspace query).
 
 `update_actor` is the reference's function.  CPU tensors run the reference's torch statements throughout (CPU tests, gloo runs — not the
 hot path).  DESIGN.md §7.5."""
@@ -41,10 +42,20 @@ def actor_parameters(actor):
     return P.parse_parameters(actor, P.ACTOR_NAMES, "actor")
 
 
+def _distribution(p, xs, xo, xc, action):
+    """(log_probs_new, dist_entropy), [B, A, 1] each, of Actor.forward(eval_action=True) and DiagGaussian.forward (mappo.py:612-624,
+    distributions.py:78-82) for the network `p` on rows of any leading shape; autograd through policy_train's encoder."""
+    action_mean = F.linear(PT.encoder(p, xs, xo, xc), p["head_w"], p["head_b"])
+    action_std = torch.broadcast_to(torch.exp(p["log_std"]), action_mean.shape)
+    action_dist = D.Independent(D.Normal(action_mean, action_std, validate_args=False), 1, validate_args=False)
+    return action_dist.log_prob(action).unsqueeze(-1), action_dist.entropy().unsqueeze(-1)
+
+
 def _torch_loss_and_grad(p, xs, xo, xc, action, log_probs_old, advantages, index, clip_param, entropy_coef, global_rows=None, entropy_share=1.0,
-                         group=None, bucket=None):
-    """update_actor's statements (mappo.py:293-318) on the gathered minibatch, Actor.forward(eval_action=True) and DiagGaussian.forward
-    (mappo.py:612-624, distributions.py:78-82) in front of them; autograd through policy_train's encoder."""
+                         group=None, bucket=None, per_agent=False):
+    """update_actor's statements (mappo.py:293-318) on the gathered minibatch, behind the shared actor's `_distribution` or — `per_agent`,
+    the else branch of mappo.py:288-291 — the actor mapped over dim 1 of its input and dim 0 of the stacked parameters, the outputs stacked
+    on dim 1."""
     N, T, A, D_ = xs.shape
     xs, xc = xs.reshape(N * T, A, 1, D_), xc.reshape(N * T, A, xc.shape[3], 5)
     xo = xo.reshape(N * T, A, A - 1, 3) if xo is not None else None
@@ -54,11 +65,11 @@ def _torch_loss_and_grad(p, xs, xo, xc, action, log_probs_old, advantages, index
         xs, xc, action, log_probs_old, advantages = xs[index], xc[index], action[index], log_probs_old[index], advantages[index]
         xo = xo[index] if xo is not None else None
     leaves = {k: v.detach().requires_grad_(True) for k, v in p.items()}
-    action_mean = F.linear(PT.encoder(leaves, xs, xo, xc), leaves["head_w"], leaves["head_b"])
-    action_std = torch.broadcast_to(torch.exp(leaves["log_std"]), action_mean.shape)
-    action_dist = D.Independent(D.Normal(action_mean, action_std, validate_args=False), 1, validate_args=False)
-    log_probs_new = action_dist.log_prob(action).unsqueeze(-1)
-    dist_entropy = action_dist.entropy().unsqueeze(-1)
+    if per_agent:
+        each = [_distribution(P.agent_slice(leaves, a), xs[:, a], xo[:, a] if xo is not None else None, xc[:, a], action[:, a]) for a in range(A)]
+        log_probs_new, dist_entropy = (torch.stack(t, dim=1) for t in zip(*each))
+    else:
+        log_probs_new, dist_entropy = _distribution(leaves, xs, xo, xc, action)
     ratio = torch.exp(log_probs_new - log_probs_old)
     surr1 = ratio * advantages
     surr2 = torch.clamp(ratio, 1.0 - clip_param, 1.0 + clip_param) * advantages
@@ -81,6 +92,23 @@ def _torch_loss_and_grad(p, xs, xo, xc, action, log_probs_old, advantages, index
             grad_norm = PT.finish_global(bucket, group)
         ess = (2 * ratio.logsumexp(0) - (2 * ratio).logsumexp(0)).exp().mean() / ratio.shape[0]
     return ActorLoss(policy_loss.detach(), -entropy_loss.detach(), ess, grad_norm, log_probs_new.detach())
+
+
+def _device_loss_and_grad(entry, workspace_bytes, p, xs, xo, xc, shape, action, log_probs_old, advantages, index, clip_param, entropy_coef, workspace,
+                          out, more=()):
+    """The device half of both `policy_loss_and_grad`s: ONE call of `entry` — hns_actor_train_grad, or its _agents or _global form, with its
+    workspace query, both taken from the library — on validated device tensors.  `more`: the global form's arguments behind the stream;
+    with them the entry leaves grad_norm to the caller.  Returns (the four result slots, log_probs [B, A, 1])."""
+    act, lpo, adv = action.contiguous(), log_probs_old.contiguous(), advantages.contiguous()
+    net, grd, b, ws, nbytes, scal, B, st = PT.prepare_call("actor", p, xs, xo, xc, index, shape, workspace_bytes, workspace, out, 4, abi.HnsActorBatch)
+    _, _, A, D_, K = shape
+    b.action, b.log_probs_old, b.advantages = act.data_ptr(), lpo.data_ptr(), adv.data_ptr()
+    log_probs = torch.empty(B, A, 1, dtype=torch.float32, device=xs.device)
+    with torch.cuda.device(xs.device):
+        rc = entry(C.byref(net), C.byref(b), D_, A, K, float(clip_param), float(entropy_coef), C.byref(grd), scal[0:].data_ptr(), scal[1:].data_ptr(),
+                   scal[2:].data_ptr(), None if more else scal[3:].data_ptr(), log_probs.data_ptr(), ws.data_ptr(), nbytes, st, *more)
+    abi.check(rc, entry.__name__)
+    return scal, log_probs
 
 
 def policy_loss_and_grad(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index=None, clip_param=0.1,
@@ -113,31 +141,19 @@ def policy_loss_and_grad(actor, obs_self, obs_others, obs_cylinders, action, log
         return _torch_loss_and_grad(p, xs, xo, xc, action, log_probs_old, advantages, index, float(clip_param), float(entropy_coef), global_rows,
                                     float(entropy_share), group, bucket)
     lib = abi.load_library()
-    act, lpo, adv = action.contiguous(), log_probs_old.contiguous(), advantages.contiguous()
-    net, grd, b, ws, nbytes, scal, B, st = PT.prepare_call("actor", p, xs, xo, xc, index, shape, lib.hns_actor_train_workspace_bytes, workspace,
-                                                           out, 4, abi.HnsActorBatch)
-    _, _, A, D_, K = shape
-    b.action, b.log_probs_old, b.advantages = act.data_ptr(), lpo.data_ptr(), adv.data_ptr()
-    log_probs = torch.empty(B, A, 1, dtype=torch.float32, device=xs.device)
+    args = (lib.hns_actor_train_workspace_bytes, p, xs, xo, xc, shape, action, log_probs_old, advantages, index, clip_param, entropy_coef, workspace, out)
     if global_rows is not None:
-        with torch.cuda.device(xs.device):
-            rc = lib.hns_actor_train_grad_global(C.byref(net), C.byref(b), D_, A, K, float(clip_param), float(entropy_coef), C.byref(grd),
-                                                 scal[0:].data_ptr(), scal[1:].data_ptr(), scal[2:].data_ptr(), None, log_probs.data_ptr(), ws.data_ptr(),
-                                                 nbytes, st, int(global_rows), float(entropy_share))
-        abi.check(rc, "hns_actor_train_grad_global")
+        scal, log_probs = _device_loss_and_grad(lib.hns_actor_train_grad_global, *args, more=(int(global_rows), float(entropy_share)))
         norm = PT.finish_global(bucket, group, scal[3:4])
         return ActorLoss(scal[0], scal[1], scal[2], scal[3] if norm is not None else None, log_probs)
-    with torch.cuda.device(xs.device):
-        rc = lib.hns_actor_train_grad(C.byref(net), C.byref(b), D_, A, K, float(clip_param), float(entropy_coef), C.byref(grd), scal[0:].data_ptr(),
-                                      scal[1:].data_ptr(), scal[2:].data_ptr(), scal[3:].data_ptr(), log_probs.data_ptr(), ws.data_ptr(), nbytes, st)
-    abi.check(rc, "hns_actor_train_grad")
+    scal, log_probs = _device_loss_and_grad(lib.hns_actor_train_grad, *args)
     return ActorLoss(scal[0], scal[1], scal[2], scal[3], log_probs)
 
 
-def actor_cfg(cfg):
-    """The refusals of the actor's part of the algo cfg (policy.check_config's, then actor.lr_scheduler, actor.weight_decay); returns the cfg's and
-    the actor section's getters."""
-    P.check_config(cfg)
+def actor_cfg(cfg, per_agent=False):
+    """The refusals of the actor's part of the algo cfg (policy.check_config's — `per_agent`: check_config_per_agent's — then
+    actor.lr_scheduler, actor.weight_decay); returns the cfg's and the actor section's getters."""
+    (P.check_config_per_agent if per_agent else P.check_config)(cfg)
     sget = PT.getter(PT.getter(cfg)("actor", None))
     if sget("lr_scheduler", None):
         raise P.PolicyConfigError("actor.lr_scheduler is not supported")
@@ -146,11 +162,16 @@ def actor_cfg(cfg):
     return PT.getter(cfg), sget
 
 
-def make_optimizer(actor, cfg=None):
-    """The reference's actor_opt (mappo.py:154, :489) as a ClippedAdam: cfg is the algo cfg (actor.lr, actor.weight_decay, max_grad_norm)."""
-    get, sget = actor_cfg(cfg)
-    return ClippedAdam(actor_parameters(actor).values(), lr=float(sget("lr", 5e-4)), max_grad_norm=get("max_grad_norm", 10.0),
-                       weight_decay=float(sget("weight_decay", 0.0) or 0.0))
+def make_optimizer(actor, cfg=None, per_agent=False):
+    """The reference's actor_opt (mappo.py:154, :489) as a ClippedAdam: cfg is the algo cfg (actor.lr, actor.weight_decay, max_grad_norm).
+    `per_agent`: over the 23 STACKED tensors — ONE Adam and one clip over all agents' parameters, as the reference's."""
+    get, sget = actor_cfg(cfg, per_agent)
+    return ClippedAdam((actor_parameters_per_agent if per_agent else actor_parameters)(actor).values(), lr=float(sget("lr", 5e-4)),
+                       max_grad_norm=get("max_grad_norm", 10.0), weight_decay=float(sget("weight_decay", 0.0) or 0.0))
+
+
+def _info(res, norm):
+    return {"policy_loss": res.policy_loss, "actor_grad_norm": norm, "entropy": res.entropy, "ESS": res.ess}
 
 
 def update_actor(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, optimizer, index=None, cfg=None, check_index=False,
@@ -163,19 +184,11 @@ def update_actor(actor, obs_self, obs_others, obs_cylinders, action, log_probs_o
     (group may be None where the caller summed the buckets itself)."""
     if global_rows is not None and bucket is None:
         raise ValueError("update_actor with global_rows= steps on the bucket's norm: pass bucket=")
-    if not isinstance(optimizer, ClippedAdam):
-        raise TypeError(f"update_actor takes a ClippedAdam (actor_train.make_optimizer), not {type(optimizer).__name__}: the clip and the "
-                        "step are one launch that needs the gradient norm")
-    get, _ = actor_cfg(cfg)
-    for pg in optimizer.param_groups:
-        if pg.get("weight_decay", 0) != 0:
-            raise NotImplementedError("weight_decay != 0 is not supported")
+    get, _ = PT.check_optimizer(optimizer, "update_actor", "actor_train.make_optimizer", actor_cfg, cfg)
     res = policy_loss_and_grad(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index,
                                clip_param=float(get("clip_param", 0.1)), entropy_coef=float(get("entropy_coef", 0.001)), check_index=check_index,
                                workspace=workspace, out=out, global_rows=global_rows, entropy_share=entropy_share, group=group, bucket=bucket)
-    optimizer.step(grad_norm=res.grad_norm)
-    norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else res.grad_norm
-    return {"policy_loss": res.policy_loss, "actor_grad_norm": norm, "entropy": res.entropy, "ESS": res.ess}
+    return _info(res, PT.clipped_step(optimizer, res.grad_norm))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -184,40 +197,6 @@ def actor_parameters_per_agent(actor):
     """The STACKED actor's tensors ([A, ...] each) by hns_policy_net field, in registration order (clip_grad_norm_'s: the reference clips the
     stacked tensors)."""
     return P.parse_parameters_per_agent(actor, "actor")[0]
-
-
-def _torch_loss_and_grad_per_agent(p, xs, xo, xc, action, log_probs_old, advantages, index, clip_param, entropy_coef):
-    """update_actor's statements with the else branch of mappo.py:288-291: the actor mapped over dim 1 of its input and dim 0 of the stacked
-    parameters, the outputs stacked on dim 1; then `_torch_loss_and_grad`'s statements on [B, A, 1]."""
-    N, T, A, D_ = xs.shape
-    xs, xc = xs.reshape(N * T, A, 1, D_), xc.reshape(N * T, A, xc.shape[3], 5)
-    xo = xo.reshape(N * T, A, A - 1, 3) if xo is not None else None
-    action = action.reshape(N * T, A, P.ACTION_DIM)
-    log_probs_old, advantages = log_probs_old.reshape(N * T, A, 1), advantages.reshape(N * T, A, 1)
-    if index is not None:
-        xs, xc, action, log_probs_old, advantages = xs[index], xc[index], action[index], log_probs_old[index], advantages[index]
-        xo = xo[index] if xo is not None else None
-    leaves = {k: v.detach().requires_grad_(True) for k, v in p.items()}
-    logp, ent = [], []
-    for a in range(A):
-        la = P.agent_slice(leaves, a)
-        mean = F.linear(PT.encoder(la, xs[:, a], xo[:, a] if xo is not None else None, xc[:, a]), la["head_w"], la["head_b"])
-        dist = D.Independent(D.Normal(mean, torch.broadcast_to(torch.exp(la["log_std"]), mean.shape), validate_args=False), 1, validate_args=False)
-        logp.append(dist.log_prob(action[:, a]).unsqueeze(-1))
-        ent.append(dist.entropy().unsqueeze(-1))
-    log_probs_new, dist_entropy = torch.stack(logp, dim=1), torch.stack(ent, dim=1)
-    ratio = torch.exp(log_probs_new - log_probs_old)
-    surr1 = ratio * advantages
-    surr2 = torch.clamp(ratio, 1.0 - clip_param, 1.0 + clip_param) * advantages
-    policy_loss = - torch.mean(torch.min(surr1, surr2) * P.ACTION_DIM)
-    entropy_loss = - torch.mean(dist_entropy)
-    grads = torch.autograd.grad(policy_loss + entropy_loss * entropy_coef, list(leaves.values()))
-    for t, g in zip(p.values(), grads):
-        t.grad = g
-    with torch.no_grad():
-        grad_norm = nn.utils.clip_grad_norm_(list(p.values()), float("inf"))
-        ess = (2 * ratio.logsumexp(0) - (2 * ratio).logsumexp(0)).exp().mean() / ratio.shape[0]
-    return ActorLoss(policy_loss.detach(), -entropy_loss.detach(), ess, grad_norm, log_probs_new.detach())
 
 
 def policy_loss_and_grad_per_agent(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index=None, clip_param=0.1,
@@ -241,53 +220,29 @@ def policy_loss_and_grad_per_agent(actor, obs_self, obs_others, obs_cylinders, a
     if shape[2] != A:
         raise ValueError(f"the observation has {shape[2]} agents, the stacked actor {A}")
     if not xs.is_cuda:
-        return _torch_loss_and_grad_per_agent(p, xs, xo, xc, action, log_probs_old, advantages, index, float(clip_param), float(entropy_coef))
+        return _torch_loss_and_grad(p, xs, xo, xc, action, log_probs_old, advantages, index, float(clip_param), float(entropy_coef), per_agent=True)
     lib = abi.load_library()
-    act, lpo, adv = action.contiguous(), log_probs_old.contiguous(), advantages.contiguous()
-    net, grd, b, ws, nbytes, scal, B, st = PT.prepare_call("actor", p, xs, xo, xc, index, shape, lib.hns_actor_train_agents_workspace_bytes, workspace,
-                                                           out, 4, abi.HnsActorBatch)
-    _, _, A, D_, K = shape
-    b.action, b.log_probs_old, b.advantages = act.data_ptr(), lpo.data_ptr(), adv.data_ptr()
-    log_probs = torch.empty(B, A, 1, dtype=torch.float32, device=xs.device)
-    with torch.cuda.device(xs.device):
-        rc = lib.hns_actor_train_grad_agents(C.byref(net), C.byref(b), D_, A, K, float(clip_param), float(entropy_coef), C.byref(grd), scal[0:].data_ptr(),
-                                             scal[1:].data_ptr(), scal[2:].data_ptr(), scal[3:].data_ptr(), log_probs.data_ptr(), ws.data_ptr(), nbytes, st)
-    abi.check(rc, "hns_actor_train_grad_agents")
+    scal, log_probs = _device_loss_and_grad(lib.hns_actor_train_grad_agents, lib.hns_actor_train_agents_workspace_bytes, p, xs, xo, xc, shape, action,
+                                            log_probs_old, advantages, index, clip_param, entropy_coef, workspace, out)
     return ActorLoss(scal[0], scal[1], scal[2], scal[3], log_probs)
 
 
 def actor_cfg_per_agent(cfg):
     """`actor_cfg` for one actor per agent: policy.check_config_per_agent's refusals, then actor.lr_scheduler and actor.weight_decay."""
-    P.check_config_per_agent(cfg)
-    sget = PT.getter(PT.getter(cfg)("actor", None))
-    if sget("lr_scheduler", None):
-        raise P.PolicyConfigError("actor.lr_scheduler is not supported")
-    if float(sget("weight_decay", 0.0) or 0.0) != 0:
-        raise NotImplementedError("actor.weight_decay != 0 is not supported")
-    return PT.getter(cfg), sget
+    return actor_cfg(cfg, per_agent=True)
 
 
 def make_optimizer_per_agent(actor, cfg=None):
     """`make_optimizer` over the 23 STACKED tensors: ONE Adam and one clip over all agents' parameters, as the reference's actor_opt."""
-    get, sget = actor_cfg_per_agent(cfg)
-    return ClippedAdam(actor_parameters_per_agent(actor).values(), lr=float(sget("lr", 5e-4)), max_grad_norm=get("max_grad_norm", 10.0),
-                       weight_decay=float(sget("weight_decay", 0.0) or 0.0))
+    return make_optimizer(actor, cfg, per_agent=True)
 
 
 def update_actor_per_agent(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, optimizer, index=None, cfg=None,
                            check_index=False, workspace=None, out=None):
     """`update_actor` with one actor per agent (MAPPOPolicy.update_actor with share_actor: False): `policy_loss_and_grad_per_agent`, then the
     clip and the Adam step of `optimizer` (make_optimizer_per_agent) over the stacked tensors.  The same info dict."""
-    if not isinstance(optimizer, ClippedAdam):
-        raise TypeError(f"update_actor_per_agent takes a ClippedAdam (actor_train.make_optimizer_per_agent), not {type(optimizer).__name__}: the "
-                        "clip and the step are one launch that needs the gradient norm")
-    get, _ = actor_cfg_per_agent(cfg)
-    for pg in optimizer.param_groups:
-        if pg.get("weight_decay", 0) != 0:
-            raise NotImplementedError("weight_decay != 0 is not supported")
+    get, _ = PT.check_optimizer(optimizer, "update_actor_per_agent", "actor_train.make_optimizer_per_agent", actor_cfg_per_agent, cfg)
     res = policy_loss_and_grad_per_agent(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index,
                                          clip_param=float(get("clip_param", 0.1)), entropy_coef=float(get("entropy_coef", 0.001)),
                                          check_index=check_index, workspace=workspace, out=out)
-    optimizer.step(grad_norm=res.grad_norm)
-    norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else res.grad_norm
-    return {"policy_loss": res.policy_loss, "actor_grad_norm": norm, "entropy": res.entropy, "ESS": res.ess}
+    return _info(res, PT.clipped_step(optimizer, res.grad_norm))

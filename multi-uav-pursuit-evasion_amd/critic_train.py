@@ -96,13 +96,7 @@ def _torch_loss_and_grad_global(p, xs, xo, xc, b_values, b_returns, index, clip_
 
 def _torch_loss_and_grad(p, xs, xo, xc, b_values, b_returns, index, clip_param, loss, huber_delta):
     """update_critic's statements (mappo.py:328-341) on the gathered minibatch; autograd through policy_train's encoder."""
-    N, T, A, D = xs.shape
-    xs, xc = xs.reshape(N * T, A, 1, D), xc.reshape(N * T, A, xc.shape[3], 5)
-    xo = xo.reshape(N * T, A, A - 1, 3) if xo is not None else None
-    bv, ret = b_values.reshape(N * T, A, 1), b_returns.reshape(N * T, A, 1)
-    if index is not None:
-        xs, xc, bv, ret = xs[index], xc[index], bv[index], ret[index]
-        xo = xo[index] if xo is not None else None
+    xs, xo, xc, bv, ret = _gather(xs, xo, xc, b_values, b_returns, index)
     leaves = {k: v.detach().requires_grad_(True) for k, v in p.items()}
     values = F.linear(PT.encoder(leaves, xs, xo, xc), leaves["head_w"], leaves["head_b"])
     clipped = bv + (values - bv).clamp(-clip_param, clip_param)
@@ -252,13 +246,7 @@ def update_critic(critic, obs_self, obs_others, obs_cylinders, b_values, b_retur
         raise ValueError("update_critic with global_rows= steps on the bucket's norm: pass bucket=")
     if global_rows is not None and sums is None and group is None:
         raise ValueError("update_critic with global_rows= needs the union's sums= or the group= to add them over")
-    if not isinstance(optimizer, ClippedAdam):
-        raise TypeError(f"update_critic takes a ClippedAdam (critic_train.make_optimizer), not {type(optimizer).__name__}: the clip and the "
-                        "step are one launch that needs the gradient norm")
-    get, sget = critic_cfg(cfg)
-    for pg in optimizer.param_groups:
-        if pg.get("weight_decay", 0) != 0:
-            raise NotImplementedError("weight_decay != 0 is not supported")
+    get, sget = PT.check_optimizer(optimizer, "update_critic", "critic_train.make_optimizer", critic_cfg, cfg)
     kw = dict(clip_param=float(get("clip_param", 0.1)), loss="huber" if sget("use_huber_loss", True) else "mse",
               huber_delta=float(sget("huber_delta", 10.0)), check_index=check_index, workspace=workspace)
     if global_rows is not None and sums is None:
@@ -266,6 +254,4 @@ def update_critic(critic, obs_self, obs_others, obs_cylinders, b_values, b_retur
         sums = sharding.all_reduce_sum(value_loss_sums(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, index, **kw).sums, group)
     res = value_loss_and_grad(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, index, out=out, sums=sums, global_rows=global_rows,
                               group=group, bucket=bucket, **kw)
-    optimizer.step(grad_norm=res.grad_norm)
-    norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else res.grad_norm
-    return {"value_loss": res.value_loss, "critic_grad_norm": norm, "explained_var": res.explained_var}
+    return {"value_loss": res.value_loss, "critic_grad_norm": PT.clipped_step(optimizer, res.grad_norm), "explained_var": res.explained_var}

@@ -24,6 +24,10 @@ refusing a recurrent policy.
 `PerAgentDeviceLearner` is the same for share_actor: False (one actor per agent): the actor block through
 actor_train.update_actor_per_agent over the stacked tensors, everything else DeviceLearner's.  `DeviceLearner` keeps refusing that configuration.
 
+`DeviceLearner._ppo_loop` is the only PPO loop.  A variant overrides what differs and nothing else: the units a permutation draws from
+(`_units`), its update call for one index (`_actor_step`, `_critic_step`), its cached buffers (`_workspaces`), and its optimisers and tensors
+(`_make_actor_opt`, `_make_critic_opt`, `_network_tensors`: checkpoints, buckets and the broadcast are written once over them).
+
 `DeviceLearner(..., group=)` is the data-parallel learner: W ranks, each with the rollout of its own env slice, perform ONE
 PPO update per minibatch on the union of their minibatches — the critic's branch decided on the union's sums, every mean over the union's
 rows, the norm taken from the summed gradient, the predictor's ranks weighted by their selected windows.
@@ -114,18 +118,12 @@ class DeviceLearner:
             raise P.PolicyConfigError("DeviceLearner updates the non-recurrent networks only: a recurrent policy (actor.rnn / critic.rnn) is trained "
                                       "in torch over encoder.encode -> rnn.gru -> head (examples/recurrent_policy.py)")
         self._configure(actor, critic, cfg, tp_net, value_normalizer, agent_name, generator)
-        self.actor_opt = actor_train.make_optimizer(actor, cfg)
-        self.critic_opt = critic_train.make_optimizer(critic, cfg)
-        self.policy = device_policy if device_policy is not None else P.DevicePolicy(actor, critic, cfg, agent_name=agent_name)
-        self.group = sharding.resolve_group(group)
-        if self.group is not None:
-            self.world = torch.distributed.get_world_size(self.group)
-            self._make_buckets()
-            self._broadcast_state()
+        self._make_networks_state(device_policy, P.DevicePolicy)
+        self._join(group)
 
     def _configure(self, actor, critic, cfg, tp_net, value_normalizer, agent_name, generator):
         """What every learner holds whatever its networks: the objects, train_op's settings from the algo cfg, the predictor's optimiser, the
-        workspace cache.  The two networks' optimisers, the policy and the group are the constructor's."""
+        workspace cache.  The two networks' optimisers and the policy (_make_networks_state) and the group (_join) follow it."""
         get = PT.getter(cfg)
         self.cfg, self.agent_name, self.generator = cfg, agent_name, generator
         self.actor, self.critic, self.tp_net, self.value_normalizer = actor, critic, tp_net, value_normalizer
@@ -136,32 +134,54 @@ class DeviceLearner:
         self.use_tp = tp_net is not None and bool(get("use_TP_net", 1))
         if self.ppo_epochs < 1 or self.num_minibatches < 1 or (self.use_tp and self.tp_epochs < 1):
             raise ValueError("ppo_epochs, num_minibatches and TP_epochs must be >= 1")
-        self.tp_opt = tp_train.TPAdam(tp_train.parameters(tp_net), lr=1e-4) if tp_net is not None else None
+        self.tp_opt = self._make_tp_opt() if tp_net is not None else None
         self.n_updates = 0
         self._ws = {}
         self.group = None
         self.actor_bucket = self.critic_bucket = self.tp_bucket = None
 
-    # ---- the data-parallel path's state
+    # ---- a variant's two networks: their optimisers, their tensors in the optimisers' order
+    def _make_actor_opt(self):
+        return actor_train.make_optimizer(self.actor, self.cfg)
+
+    def _make_critic_opt(self):
+        return critic_train.make_optimizer(self.critic, self.cfg)
+
+    def _network_tensors(self):
+        """(the actor's tensors, the critic's): the order of a network's gradient bucket and of the broadcast."""
+        return list(actor_train.actor_parameters(self.actor).values()), list(critic_train.critic_parameters(self.critic).values())
+
+    def _make_tp_opt(self):
+        return tp_train.TPAdam(tp_train.parameters(self.tp_net), lr=1e-4)
+
+    def _make_networks_state(self, device_policy, policy_class):
+        """The two networks' optimisers (the refusals of the cfg and of the parameters come first) and the policy of the bootstrap value."""
+        self.actor_opt, self.critic_opt = self._make_actor_opt(), self._make_critic_opt()
+        self.policy = device_policy if device_policy is not None else policy_class(self.actor, self.critic, self.cfg, agent_name=self.agent_name)
+
     def _optimizer_makers(self):
-        return (("actor_opt", "actor_opt", lambda: actor_train.make_optimizer(self.actor, self.cfg)),
-                ("critic_opt", "critic_opt", lambda: critic_train.make_optimizer(self.critic, self.cfg)),
-                ("tp_opt", "TP_opt", lambda: tp_train.TPAdam(tp_train.parameters(self.tp_net), lr=1e-4)))
+        """(attribute, state_dict key, maker) of the three optimisers."""
+        return (("actor_opt", "actor_opt", self._make_actor_opt), ("critic_opt", "critic_opt", self._make_critic_opt), ("tp_opt", "TP_opt", self._make_tp_opt))
 
-    def _make_buckets(self):
-        self.actor_bucket = PT.GradBucket(actor_train.actor_parameters(self.actor))
-        self.critic_bucket = PT.GradBucket(critic_train.critic_parameters(self.critic))
-        self.tp_bucket = PT.GradBucket(tp_train.parameters(self.tp_net)) if self.tp_net is not None else None
+    def _make_network_buckets(self):
+        """ONE flat gradient buffer per network, behind its tensors' .grad."""
+        self.actor_bucket, self.critic_bucket = (PT.GradBucket(t) for t in self._network_tensors())
 
-    def _broadcast_tensors(self):
-        """Both networks' tensors, in the order they are broadcast."""
-        return list(actor_train.actor_parameters(self.actor).values()) + list(critic_train.critic_parameters(self.critic).values())
+    # ---- the data-parallel path's state
+    def _join(self, group):
+        """The data-parallel learner's part of construction: the group, the gradient buckets, rank 0's state on every rank."""
+        self.group = sharding.resolve_group(group)
+        if self.group is not None:
+            self.world = torch.distributed.get_world_size(self.group)
+            self._make_network_buckets()
+            self.tp_bucket = PT.GradBucket(tp_train.parameters(self.tp_net)) if self.tp_net is not None else None
+            self._broadcast_state()
 
     def _broadcast_state(self):
         """Rank 0 of the group hands every rank its networks, ValueNorm1 buffers and Adam states (tensor by tensor: construction and checkpoint
         loading only)."""
         dist = torch.distributed
-        tensors = self._broadcast_tensors()
+        tensors = [t for net in self._network_tensors() for t in net]
         if self.tp_net is not None:
             tensors += tp_train.parameters(self.tp_net)
         if self.value_normalizer is not None:
@@ -311,37 +331,46 @@ class DeviceLearner:
         """mappo.py:365-367: the critic's value of the last step's next observation, ONE value_only call."""
         return self.policy.forward(*next_obs_last, value_only=True).value
 
-    # the actor block's two pieces (PerAgentDeviceLearner: the *_per_agent ones)
-    _ACTOR_WORKSPACE = "hns_actor_train_workspace_bytes"
+    # ---- the PPO loop and what a variant supplies to it
+    def _units(self, N, T):
+        """What a permutation draws from: the rollout's env-steps."""
+        return N * T
 
-    def _update_actor(self, *args, **kw):
-        return actor_train.update_actor(*args, **kw)
+    def _workspaces(self, xs, xc, actor_workspace_bytes=None):
+        """The device loop's (actor, critic) workspaces, cached between calls.  actor_workspace_bytes: the actor entry's query (None:
+        hns_actor_train_workspace_bytes)."""
+        N, T, A, D = xs.shape
+        dev, K, lib = xs.device, int(xc.shape[3]), abi.load_library()
+        rows = (N * T // self.num_minibatches) * A
+        na, nc = (actor_workspace_bytes or lib.hns_actor_train_workspace_bytes)(rows, D, A, K), lib.hns_critic_train_workspace_bytes(rows, D, A, K)
+        if rows < 1 or na == 0 or nc == 0:
+            raise ValueError(f"shape outside the kernels' limits: {rows} rows per minibatch, self_dim {D}, {A} agents, {K} cylinders")
+        return self._workspace("actor", na, dev), self._workspace("critic", nc, dev)
+
+    def _actor_step(self, idx, obs, action, log_probs, adv, recurrent, **kw):
+        return actor_train.update_actor(self.actor, *obs, action, log_probs, adv, self.actor_opt, index=idx, cfg=self.cfg, **kw)
+
+    def _critic_step(self, idx, obs, state_value, ret, recurrent, **kw):
+        return critic_train.update_critic(self.critic, *obs, state_value, ret, self.critic_opt, index=idx, cfg=self.cfg, **kw)
 
     def _ppo_loop(self, xs, xo, xc, action, log_probs, adv, state_value, ret, table, global_rows=None, recurrent=None):
-        """mappo.py:446-461: per epoch one permutation, per minibatch the actor's update and then the critic's.  On the device: no host
-        synchronisation — cached workspaces, scalars written into `table`'s rows, no index check.  `global_rows` (the data-parallel path):
-        the updates' global forms over the group, their gradients in the two buckets."""
-        kw_a = dict(global_rows=global_rows, entropy_share=1.0 / self.world, group=self.group, bucket=self.actor_bucket) if global_rows is not None else {}
-        kw_c = dict(global_rows=global_rows, group=self.group, bucket=self.critic_bucket) if global_rows is not None else {}
-        N, T, A, D = xs.shape
-        dev, K = xs.device, int(xc.shape[3])
-        ws_a = ws_c = None
-        if dev.type == "cuda":
-            lib = abi.load_library()
-            rows = (N * T // self.num_minibatches) * A
-            na, nc = getattr(lib, self._ACTOR_WORKSPACE)(rows, D, A, K), lib.hns_critic_train_workspace_bytes(rows, D, A, K)
-            if rows < 1 or na == 0 or nc == 0:
-                raise ValueError(f"shape outside the kernels' limits: {rows} rows per minibatch, self_dim {D}, {A} agents, {K} cylinders")
-            ws_a, ws_c = self._workspace("actor", na, dev), self._workspace("critic", nc, dev)
+        """mappo.py:446-461: per epoch one permutation of the variant's units, per minibatch the actor's update and then the critic's.  On
+        the device: no host synchronisation — cached workspaces, scalars written into `table`'s rows, no index check.  `global_rows` (the
+        data-parallel path): the updates' global forms over the group.  Each network's gradients lie in its bucket where the learner holds
+        one."""
+        N, T = xs.shape[:2]
+        dev, obs, na = xs.device, (xs, xo, xc), len(ACTOR_COLUMNS)
+        ws_a, ws_c = self._workspaces(xs, xc) if dev.type == "cuda" else (None, None)
+        kw_a, kw_c = {"bucket": self.actor_bucket}, {"bucket": self.critic_bucket}
+        if global_rows is not None:
+            kw_a.update(global_rows=global_rows, entropy_share=1.0 / self.world, group=self.group)
+            kw_c.update(global_rows=global_rows, group=self.group)
         m = 0
         for _ in range(self.ppo_epochs):
-            for idx in tp_train.minibatches(N * T, self.num_minibatches, dev, self.generator):
-                out_a = table[m, :len(ACTOR_COLUMNS)] if ws_a is not None else None
-                out_c = table[m, len(ACTOR_COLUMNS):] if ws_c is not None else None
-                sa = self._update_actor(self.actor, xs, xo, xc, action, log_probs, adv, self.actor_opt, index=idx, cfg=self.cfg,
-                                        workspace=ws_a, out=out_a, **kw_a)
-                sc = critic_train.update_critic(self.critic, xs, xo, xc, state_value, ret, self.critic_opt, index=idx, cfg=self.cfg,
-                                                workspace=ws_c, out=out_c, **kw_c)
+            for idx in tp_train.minibatches(self._units(N, T), self.num_minibatches, dev, self.generator):
+                out_a, out_c = (table[m, :na], table[m, na:]) if ws_a is not None else (None, None)
+                sa = self._actor_step(idx, obs, action, log_probs, adv, recurrent, workspace=ws_a, out=out_a, **kw_a)
+                sc = self._critic_step(idx, obs, state_value, ret, recurrent, workspace=ws_c, out=out_c, **kw_c)
                 if ws_a is None:                                 # CPU: the updates return their scalars
                     table[m] = torch.stack([(sa | sc)[k].reshape(()).to(torch.float32) for k in COLUMNS])
                 m += 1
@@ -407,15 +436,6 @@ class DeviceLearner:
             self._broadcast_state()
 
 
-def _without_share_actor(cfg):
-    """The algo cfg as a dict without its share_actor key: what the shared critic's functions (and policy.check_config behind them) take."""
-    if cfg is None:
-        return None
-    keys = list(cfg.keys()) if hasattr(cfg, "keys") else list(vars(cfg))
-    get = PT.getter(cfg)
-    return {k: get(k) for k in keys if k != "share_actor"}
-
-
 class PerAgentDeviceLearner(DeviceLearner):
     """MAPPOPolicy's training half with share_actor: False (one actor per agent): `DeviceLearner`'s train_op / train_rollout,
     info row and state_dict, with the actor block through actor_train.update_actor_per_agent (one `hns_actor_train_grad_agents` call and one
@@ -427,11 +447,6 @@ class PerAgentDeviceLearner(DeviceLearner):
     group= (NotImplementedError), a recurrent policy and whatever PerAgentDevicePolicy refuses (PolicyConfigError), a device_policy that is
     not per-agent, and the cfg refusals of DeviceLearner with their exception types."""
 
-    _ACTOR_WORKSPACE = "hns_actor_train_agents_workspace_bytes"
-
-    def _update_actor(self, *args, **kw):
-        return actor_train.update_actor_per_agent(*args, **kw)
-
     def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, agent_name="drone", generator=None, device_policy=None, group=None):
         if group is not None:
             raise NotImplementedError("PerAgentDeviceLearner takes no group=: data-parallel training of per-agent actors is not implemented")
@@ -441,17 +456,19 @@ class PerAgentDeviceLearner(DeviceLearner):
         if device_policy is not None and not getattr(device_policy, "per_agent", False):
             raise P.PolicyConfigError("PerAgentDeviceLearner needs a PerAgentDevicePolicy (a shared actor is DeviceLearner's)")
         actor_train.actor_cfg_per_agent(cfg)
-        shared = _without_share_actor(cfg)
+        shared = P.cfg_without(cfg, "share_actor")               # what the shared critic's functions (and policy.check_config behind them) take
         critic_train.critic_cfg(shared)
         self._configure(actor, critic, shared, tp_net, value_normalizer, agent_name, generator)
-        self.actor_opt = actor_train.make_optimizer_per_agent(actor, shared)
-        self.critic_opt = critic_train.make_optimizer(critic, shared)
-        self.policy = device_policy if device_policy is not None else P.PerAgentDevicePolicy(actor, critic, shared, agent_name=agent_name)
+        self._make_networks_state(device_policy, P.PerAgentDevicePolicy)
 
-    def _optimizer_makers(self):
-        return (("actor_opt", "actor_opt", lambda: actor_train.make_optimizer_per_agent(self.actor, self.cfg)),
-                ("critic_opt", "critic_opt", lambda: critic_train.make_optimizer(self.critic, self.cfg)),
-                ("tp_opt", "TP_opt", lambda: tp_train.TPAdam(tp_train.parameters(self.tp_net), lr=1e-4)))
+    def _make_actor_opt(self):
+        return actor_train.make_optimizer_per_agent(self.actor, self.cfg)
+
+    def _workspaces(self, xs, xc):
+        return super()._workspaces(xs, xc, abi.load_library().hns_actor_train_agents_workspace_bytes)
+
+    def _actor_step(self, idx, obs, action, log_probs, adv, recurrent, bucket=None, **kw):        # (no group, so no bucket)
+        return actor_train.update_actor_per_agent(self.actor, *obs, action, log_probs, adv, self.actor_opt, index=idx, cfg=self.cfg, **kw)
 
 
 class RecurrentDeviceLearner(DeviceLearner):
@@ -483,15 +500,17 @@ class RecurrentDeviceLearner(DeviceLearner):
         self.train_seq_len = rnn_train.train_seq_len(cfg)
         if not 1 <= self.train_seq_len <= abi.HNS_GRU_MAX_STEPS:
             raise ValueError(f"actor.rnn.train_seq_len must be in [1, {abi.HNS_GRU_MAX_STEPS}], not {self.train_seq_len}")
-        self.actor_opt = rnn_train.make_optimizer(actor, cfg, actor=True)          # (the refusals of the cfg and of the parameters come first)
-        self.critic_opt = rnn_train.make_optimizer(critic, cfg, actor=False)
-        self.policy = device_policy if device_policy is not None else P.RecurrentDevicePolicy(actor, critic, cfg, agent_name=agent_name)
+        self._make_networks_state(device_policy, P.RecurrentDevicePolicy)
         self._rnn_ws = (rnn_train.RnnWorkspace(), rnn_train.RnnWorkspace())
 
-    def _optimizer_makers(self):
-        return (("actor_opt", "actor_opt", lambda: rnn_train.make_optimizer(self.actor, self.cfg, actor=True)),
-                ("critic_opt", "critic_opt", lambda: rnn_train.make_optimizer(self.critic, self.cfg, actor=False)),
-                ("tp_opt", "TP_opt", lambda: tp_train.TPAdam(tp_train.parameters(self.tp_net), lr=1e-4)))
+    def _make_actor_opt(self):
+        return rnn_train.make_optimizer(self.actor, self.cfg, actor=True)
+
+    def _make_critic_opt(self):
+        return rnn_train.make_optimizer(self.critic, self.cfg, actor=False)
+
+    def _network_tensors(self):
+        return tuple(rnn_train.flat_parameters(rnn_train.network_parameters(net, actor)) for net, actor in ((self.actor, True), (self.critic, False)))
 
     def release(self):
         super().release()
@@ -543,29 +562,23 @@ class RecurrentDeviceLearner(DeviceLearner):
         return self.policy.forward(*next_obs_last, critic_state=recurrent["last_critic_rnn_state"], is_init=recurrent["last_is_init"],
                                    value_only=True).value
 
-    def _ppo_loop(self, xs, xo, xc, action, log_probs, adv, state_value, ret, table, global_rows=None, recurrent=None):
-        """mappo.py:446-461 over segments: per epoch one permutation of the N T / L (env, segment) pairs, per minibatch the actor's update
-        and then the critic's; each network's gradients in one GradBucket the learner holds."""
-        rk, L = recurrent, self.train_seq_len
-        N, T = xs.shape[:2]
-        cuda = xs.device.type == "cuda"
-        ws_a, ws_c = self._rnn_ws if cuda else (None, None)
-        if cuda and self.actor_bucket is None:
-            self.actor_bucket, self.critic_bucket = rnn_train.make_bucket(self.actor, True), rnn_train.make_bucket(self.critic, False)
-        kb_a, kb_c = (dict(bucket=self.actor_bucket), dict(bucket=self.critic_bucket)) if cuda else ({}, {})
-        if global_rows is not None:                              # the data-parallel path: the updates' global forms over the group
-            kb_a = dict(bucket=self.actor_bucket, global_rows=global_rows, entropy_share=1.0 / self.world, group=self.group)
-            kb_c = dict(bucket=self.critic_bucket, global_rows=global_rows, group=self.group)
-        m = 0
-        for _ in range(self.ppo_epochs):
-            for idx in tp_train.minibatches(N * (T // L), self.num_minibatches, xs.device, self.generator):
-                sa = rnn_train.update_actor_rnn(self.actor, xs, xo, xc, rk["actor_rnn_state"], rk["is_init"], action, log_probs, adv, self.actor_opt,
-                                                segment=idx, cfg=self.cfg, seq_len=L, workspace=ws_a, out=table[m, :len(ACTOR_COLUMNS)] if cuda else None, **kb_a)
-                sc = rnn_train.update_critic_rnn(self.critic, xs, xo, xc, rk["critic_rnn_state"], rk["is_init"], state_value, ret, self.critic_opt,
-                                                 segment=idx, cfg=self.cfg, seq_len=L, workspace=ws_c, out=table[m, len(ACTOR_COLUMNS):] if cuda else None, **kb_c)
-                if not cuda:                                       # CPU: the updates return their scalars
-                    table[m] = torch.stack([(sa | sc)[k].reshape(()).to(torch.float32) for k in COLUMNS])
-                m += 1
+    # the PPO loop over segments: per epoch one permutation of the N T / L (env, segment) pairs
+    def _units(self, N, T):
+        return N * (T // self.train_seq_len)
+
+    def _workspaces(self, xs, xc):
+        """Every buffer is kept per network; the two gradient buckets are made at the first use on the device."""
+        if self.actor_bucket is None:
+            self._make_network_buckets()
+        return self._rnn_ws
+
+    def _actor_step(self, idx, obs, action, log_probs, adv, rk, **kw):
+        return rnn_train.update_actor_rnn(self.actor, *obs, rk["actor_rnn_state"], rk["is_init"], action, log_probs, adv, self.actor_opt, segment=idx,
+                                          cfg=self.cfg, seq_len=self.train_seq_len, **kw)
+
+    def _critic_step(self, idx, obs, state_value, ret, rk, **kw):
+        return rnn_train.update_critic_rnn(self.critic, *obs, rk["critic_rnn_state"], rk["is_init"], state_value, ret, self.critic_opt, segment=idx,
+                                           cfg=self.cfg, seq_len=self.train_seq_len, **kw)
 
 
 class DataParallelRecurrentLearner(RecurrentDeviceLearner):
@@ -596,17 +609,7 @@ class DataParallelRecurrentLearner(RecurrentDeviceLearner):
                              "RecurrentDeviceLearner)")
         super().__init__(actor, critic, cfg, tp_net=tp_net, value_normalizer=value_normalizer, generator=generator, device_policy=device_policy,
                          agent_name=agent_name)
-        self.group = sharding.resolve_group(group)
-        self.world = torch.distributed.get_world_size(self.group)
-        self._make_buckets()
-        self._broadcast_state()
-
-    def _make_buckets(self):
-        self.actor_bucket, self.critic_bucket = rnn_train.make_bucket(self.actor, True), rnn_train.make_bucket(self.critic, False)
-        self.tp_bucket = PT.GradBucket(tp_train.parameters(self.tp_net)) if self.tp_net is not None else None
-
-    def _broadcast_tensors(self):
-        return [t for net, actor in ((self.actor, True), (self.critic, False)) for t in rnn_train.flat_parameters(rnn_train.network_parameters(net, actor))]
+        self._join(group)
 
     def _rollout_counts(self, N, T, A):
         L = self.train_seq_len

@@ -60,20 +60,40 @@ class PolicyConfigError(ValueError):
     """The network or configuration is one this forward pass does not implement."""
 
 
+def getter(cfg):
+    """get(key, default) of a cfg section, whether it is a mapping, an attribute object or None (every default)."""
+    if cfg is None:
+        return lambda k, d=None: d
+    return cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
+
+
+def cfg_without(cfg, *dotted_keys):
+    """The cfg (a mapping, an attribute object or None, which stays None) as a dict without `dotted_keys` — "share_actor"; "actor.rnn": the
+    key rnn of the section actor — and with every other key kept: what a check written for another configuration is asked about."""
+    if cfg is None:
+        return None
+    get = getter(cfg)
+    out = {k: get(k) for k in (cfg.keys() if hasattr(cfg, "keys") else [k for k in vars(cfg) if not k.startswith("_")])}
+    for dotted in dotted_keys:
+        key, _, rest = dotted.partition(".")
+        if not rest:
+            out.pop(key, None)
+        elif out.get(key) is not None:
+            out[key] = cfg_without(out[key], rest)
+    return out
+
+
 def check_config(cfg):
     """Refuse the algo configurations the device forward pass does not cover (cfg: the algo cfg mapping, or None)."""
     if cfg is None:
         return
-    get = cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
+    get = getter(cfg)
     if not get("share_actor", True):
         raise PolicyConfigError("share_actor: False (one actor per agent) is not supported; only the shared actor is")
     if get("critic_input", "obs") != "obs":
         raise PolicyConfigError(f"critic_input: {get('critic_input')} (the centralised critic) is not supported; only critic_input: obs is")
     for part in ("actor", "critic"):
-        sub = get(part, None)
-        if sub is None:
-            continue
-        sget = sub.get if hasattr(sub, "get") else (lambda k, d=None, s=sub: getattr(s, k, d))
+        sget = getter(get(part, None))
         if sget("rnn", None):
             raise PolicyConfigError(f"{part}.rnn is not supported")
         if part == "actor" and sget("tanh", False):
@@ -436,21 +456,11 @@ def torch_forward_per_agent(actors, critic, xs, xo, xc, eps=None, deterministic=
     return PolicyOutput(action, log_prob, value, loc)
 
 
-def _without_share_actor(cfg):
-    """The algo cfg with share_actor taken out (what check_config refuses for DevicePolicy and PerAgentDevicePolicy implements)."""
-    if cfg is None:
-        return None
-    get = cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
-    return {k: get(k) for k in ("critic_input", "actor", "critic") if get(k, None) is not None}
-
-
 def check_config_per_agent(cfg):
     """`check_config` for one actor per agent: everything it refuses but share_actor: False; share_actor: True is refused instead."""
-    if cfg is not None:
-        get = cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
-        if get("share_actor", False):
-            raise PolicyConfigError("share_actor: True with one actor per agent; the shared actor is DevicePolicy's")
-    check_config(_without_share_actor(cfg))
+    if getter(cfg)("share_actor", False):
+        raise PolicyConfigError("share_actor: True with one actor per agent; the shared actor is DevicePolicy's")
+    check_config(cfg_without(cfg, "share_actor"))
 
 
 class PerAgentDevicePolicy(DevicePolicy):
@@ -582,7 +592,7 @@ class RecurrentDevicePolicy(DevicePolicy):
     recurrent = True
 
     def __init__(self, actor_params, critic, cfg=None, device=None, seed=0, agent_name="drone"):
-        check_config(_without_rnn(cfg))
+        check_config(cfg_without(cfg, "actor.rnn", "critic.rnn"))
         actor_rest, self.actor_rnn = split_rnn(actor_params, "actor")
         critic_rest, self.critic_rnn = split_rnn(critic, "critic")
         super().__init__(actor_rest, critic_rest, cfg=None, device=device, seed=seed, agent_name=agent_name)
@@ -747,20 +757,6 @@ def _td_get(td, key):
         return td.get(key, None) if hasattr(td, "get") else td[key]
     except KeyError:
         return None
-
-
-def _without_rnn(cfg):
-    """The algo cfg with actor.rnn / critic.rnn taken out (what check_config refuses for DevicePolicy and this class implements)."""
-    if cfg is None:
-        return None
-    get = cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
-    out = {k: get(k) for k in ("share_actor", "critic_input") if get(k, None) is not None}
-    for part in ("actor", "critic"):
-        sub = get(part, None)
-        if sub is not None:
-            sget = sub.get if hasattr(sub, "get") else (lambda k, d=None, s=sub: getattr(s, k, d))
-            out[part] = {"tanh": sget("tanh", False)}
-    return out
 
 
 def random_rnn_parameters(seed=0):

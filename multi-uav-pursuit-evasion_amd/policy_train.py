@@ -1,5 +1,6 @@
 """What the MAPPO critic's and actor's updates share on the host side of csrc/hns_policy_train.hip: the checks of a minibatch read in place from
-the rollout, the preparation of a `hns_*_train_grad` call, and the training restatement of the encoder.
+the rollout, the preparation of a `hns_*_train_grad` call, the training restatement of the encoder, and the tail of every `update_*` — the
+shared, the per-agent and the recurrent ones (`check_optimizer` before anything is launched, `clipped_step` behind the gradient call).
 
 `critic_train` and `actor_train` keep what is their own — the reference's loss statements, their C call, their part of the cfg — and
 `learner` drives both.  `validate` and `prepare_call` take the network's word ("critic" / "actor") and its per-row tensors, so a refusal
@@ -23,10 +24,27 @@ from . import sharding
 from .optim import ClippedAdam  # noqa: F401  (the two updates' optimiser, public here)
 
 
-def getter(cfg):
-    if cfg is None:
-        return lambda k, d=None: d
-    return cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
+getter = P.getter
+
+
+def check_optimizer(optimizer, caller, maker, cfg_check=None, cfg=None):
+    """The refusals every update_* raises about its optimiser before anything is launched, in their order: not a ClippedAdam (TypeError
+    naming `caller` and its `maker`), then `cfg_check(cfg)`'s — the caller's part of the algo cfg, whose result is returned — then a
+    parameter group with weight_decay."""
+    if not isinstance(optimizer, ClippedAdam):
+        raise TypeError(f"{caller} takes a ClippedAdam ({maker}), not {type(optimizer).__name__}: the clip and the step are one launch that "
+                        "needs the gradient norm")
+    checked = cfg_check(cfg) if cfg_check is not None else None
+    for pg in optimizer.param_groups:
+        if pg.get("weight_decay", 0) != 0:
+            raise NotImplementedError("weight_decay != 0 is not supported")
+    return checked
+
+
+def clipped_step(optimizer, grad_norm):
+    """The tail of every update_*: clip_grad_norm_ + Adam on `grad_norm` (the loss-and-gradient call's); returns the norm to report."""
+    optimizer.step(grad_norm=grad_norm)
+    return optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else grad_norm
 
 
 def check_workspace(workspace, nbytes, dev):

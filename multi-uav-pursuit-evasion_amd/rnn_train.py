@@ -14,7 +14,8 @@ re-runs its L steps under the stored env-level `is_init` flags, so the recompute
     ClippedAdam.step           clip_grad_norm_ + Adam in one launch
 
 `policy_loss_and_grad_rnn` / `value_loss_and_grad_rnn` are the same calls up to the norm, as actor_train.policy_loss_and_grad is to
-update_actor.  `RnnWorkspace` keeps every buffer of a call between calls (the learner holds one per network).
+update_actor; with `value_loss_sums_rnn` they are the three callers of ONE path (`_run`), which a `_Head` — the C call, its restatement, its
+per-row tensors and result keys — is all that tells apart.  `RnnWorkspace` keeps every buffer of a call between calls (the learner holds one per network).
 
 With `global_rows=` the same calls are one rank's part of a data-parallel update over the union of the ranks' minibatches, as
 in actor_train / critic_train: only the head entries take their global forms (`hns_rnn_actor_head_grad_global`; `hns_rnn_critic_head_sums`, the
@@ -64,24 +65,8 @@ def make_optimizer(network, cfg=None, actor=True):
     """The reference's actor_opt / critic_opt over ALL of a recurrent network's tensors (encoder, rnn, head) as a ClippedAdam: cfg is the
     algo cfg (actor.lr / critic.lr, max_grad_norm); the refusals are actor_train.actor_cfg's / critic_train.critic_cfg's without the rnn one."""
     sub = PT.getter(PT.getter(cfg)("actor" if actor else "critic", None))
-    (actor_train.actor_cfg if actor else critic_train.critic_cfg)(_plain_cfg(cfg))
+    (actor_train.actor_cfg if actor else critic_train.critic_cfg)(P.cfg_without(cfg, "actor.rnn", "critic.rnn"))
     return ClippedAdam(flat_parameters(network_parameters(network, actor)), lr=float(sub("lr", 5e-4)), max_grad_norm=PT.getter(cfg)("max_grad_norm", 10.0))
-
-
-def _plain_cfg(cfg):
-    """The algo cfg with the two rnn sections taken out, every other key kept: what the non-recurrent checks are asked about."""
-    if cfg is None:
-        return None
-    get = PT.getter(cfg)
-    keys = list(cfg.keys()) if hasattr(cfg, "keys") else [k for k in vars(cfg) if not k.startswith("_")]
-    out = {}
-    for k in keys:
-        v = get(k)
-        if k in ("actor", "critic") and v is not None:
-            sub = PT.getter(v)
-            v = {kk: sub(kk) for kk in (v.keys() if hasattr(v, "keys") else [a for a in vars(v) if not a.startswith("_")]) if kk != "rnn"}
-        out[k] = v
-    return out
 
 
 # ---- the head and the loss, restated: any dtype (the tests run them in fp64 against autograd of the reference's statements)
@@ -245,9 +230,14 @@ def _gathered(state, is_init, segment, NS, A, L):
     return h0, flags
 
 
+def _step_index(segment, L):
+    """The env-steps of the segments, in [B, L] order: segment L + t."""
+    return (segment.unsqueeze(1) * L + torch.arange(L, device=segment.device)).reshape(-1)
+
+
 def _rows(per_row, segment, L, A):
     """Per-row tensors of the rollout ([N T, A(, k)] values) gathered as [B, L, A(, k)]."""
-    idx = (segment.unsqueeze(1) * L + torch.arange(L, device=segment.device)).reshape(-1)
+    idx = _step_index(segment, L)
     out = []
     for t, width in per_row:
         t = t.reshape(-1, A, width) if width > 1 else t.reshape(-1, A)
@@ -271,13 +261,12 @@ def _torch_forward(net, xs, xo, xc, shape, segment, L, NS, state, is_init, per_r
     return y, [*enc.values(), *gru.values()], rows
 
 
-def _torch_update(net, xs, xo, xc, shape, segment, L, NS, state, is_init, per_row, head_fn, forward=None):
-    """The CPU path of both networks: forward through the restatements with the parameters as leaves (or `forward`, an earlier
-    _torch_forward), the head's restatement on y, autograd from dy back through the GRU and the encoder; leaves every parameter's .grad set.
-    Returns the head's dict."""
-    y, leaves, rows = forward if forward is not None else _torch_forward(net, xs, xo, xc, shape, segment, L, NS, state, is_init, per_row)
+def _torch_update(net, forward, restate):
+    """The CPU path's backward half for both networks: the head's restatement on `forward`'s y (_torch_forward's), autograd from dy back
+    through the GRU and the encoder; leaves every parameter's .grad set.  Returns the head's dict."""
+    y, leaves, rows = forward
     with torch.no_grad():
-        res = head_fn(y.detach(), *rows)
+        res = restate(net.head, y.detach(), *rows)
     grads = torch.autograd.grad(y, leaves, res["dy"])
     for t, g in zip([*net.encoder.values(), *net.gru.values()], grads):
         t.grad = g
@@ -294,7 +283,7 @@ def _device_forward_to_y(net, xs, xo, xc, shape, segment, L, NS, state, is_init,
     lib = abi.load_library()
     # a bad id is clamped for the encoder and the two gathers (finite features, a stored state): its rows are dead in the head entry, which
     # takes the ids as they are, so dy, hence dx, is zero there and the segment adds nothing to any gradient
-    index = (segment.clamp(0, NS - 1).unsqueeze(1) * L + torch.arange(L, device=dev)).reshape(-1)
+    index = _step_index(segment.clamp(0, NS - 1), L)
     nb = lib.hns_encoder_workspace_bytes(B * L * A, D, A, K, 1)
     if nb == 0:
         raise ValueError(f"shape outside the kernels' limits: {B * L * A} rows, self_dim {D}, {A} agents, {K} cylinders")
@@ -334,105 +323,6 @@ def _device_backward(net, bucket, xs, xo, xc, shape, index, ews, x4, h0, flags, 
     encoder.device_backward(net.encoder, xs, xo, xc, index, shape, dxbuf, workspace=ews, flat=bucket.flat[:n_enc])
 
 
-def _head_grads(net, bucket):
-    """The bucket's views of the head's gradients, by field."""
-    k = len(net.encoder) + len(net.gru)
-    return dict(zip(net.head, bucket.views[k:]))
-
-
-def _check_global(word, net, global_rows, rows, group, bucket):
-    """policy_train.check_global for a recurrent network (its parameters in flat_parameters' order)."""
-    PT.check_global(word, dict(enumerate(flat_parameters(net))), global_rows, rows, group, bucket)
-
-
-def _finish_cpu(net, global_rows, group, bucket):
-    """The CPU path's gradient norm: clip_grad_norm_'s total norm, or — the data-parallel call — the bucket's after its all-reduce."""
-    if global_rows is None:
-        with torch.no_grad():
-            return torch.nn.utils.clip_grad_norm_(flat_parameters(net), float("inf"))
-    if bucket is not None:
-        bucket.adopt()
-    norm = PT.finish_global(bucket, group)
-    return norm.reshape(()) if norm is not None else None
-
-
-def policy_loss_and_grad_rnn(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, segment=None,
-                             seq_len=16, clip_param=0.1, entropy_coef=0.001, check_index=True, workspace=None, out=None, bucket=None,
-                             global_rows=None, entropy_share=1.0, group=None):
-    """update_actor_rnn up to the gradient norm: ActorLoss(policy_loss, entropy, ess, grad_norm: 0-dim tensors; log_probs [B, L, A, 1]) and
-    every parameter's .grad (views of ONE flat GradBucket on the device: `bucket` (make_bucket), or one made for the call).
-
-    actor: the recurrent actor's parameters under the reference's names (encoder.*, rnn.*, act_dist.*); obs_*: the rollout's [N, T, A, ...]
-    observations; actor_rnn_state [N, T / L, A, 128]: the state going into every segment; is_init [N, T, 1]; action [N, T, A, 4],
-    log_probs_old, advantages [N, T, A, 1]; segment: int64 [B] ids into the flattened [N, T / L] (None: all, in order); seq_len: L.
-    `check_index` range-checks the ids (one host synchronisation); unchecked, an id outside the rollout contributes nothing on the device (its
-    rows are dead in the head entry, the encoder and the GRU run on a clamped copy of it) and raises IndexError from torch's gather on the CPU.  `workspace`: an RnnWorkspace kept between calls; `out`: four fp32 device
-    values that receive policy_loss, entropy, ess and grad_norm.  Both are ignored on the CPU.
-
-    `global_rows` (None: the call above, untouched): this minibatch is one rank's part of a union of `global_rows` rows
-    (hns_rnn_actor_head_grad_global): policy_loss is this rank's SHARE, -4 sum_local / global_rows, and the gradients are the share's — over
-    the ranks both add up to the union's.  `entropy_share`: the part of the entropy term's gradient this rank adds (1 / world).  ess stays
-    this rank's own.  `bucket` is then the network's GradBucket and grad_norm its norm (None without one); `group`: the bucket is all-reduced
-    (SUM) over it first."""
-    if not clip_param >= 0:
-        raise ValueError("clip_param must be >= 0")
-    if not math.isfinite(float(entropy_share)):
-        raise ValueError("entropy_share must be finite")
-    net = network_parameters(actor, True)
-    per_row = (("action", action, P.ACTION_DIM), ("log_probs_old", log_probs_old, 1), ("advantages", advantages, 1))
-    xs, xo, xc, shape, segment, L, NS = _prepare("actor", net, (obs_self, obs_others, obs_cylinders), actor_rnn_state, is_init, per_row, segment,
-                                                 seq_len, check_index)
-    A = shape[2]
-    B = segment.numel()
-    glob = global_rows is not None
-    if glob or group is not None:
-        _check_global("actor", net, global_rows, B * L * A, group, bucket)
-    if not xs.is_cuda:
-        res = _torch_update(net, xs, xo, xc, shape, segment, L, NS, actor_rnn_state, is_init, [(t, w) for _, t, w in per_row],
-                            lambda y, a, lpo, adv: actor_head(net.head["head_w"], net.head["head_b"], net.head["log_std"], y, a, lpo, adv,
-                                                              float(clip_param), float(entropy_coef), global_rows, float(entropy_share)))
-        norm = _finish_cpu(net, global_rows, group, bucket if glob else None)
-        return ActorLoss(res["policy_loss"], res["entropy"], res["ess"], norm, res["log_probs"].unsqueeze(-1))
-    dev = xs.device
-    lib = abi.load_library()
-    ws = workspace if workspace is not None else RnnWorkspace()
-    if not (glob and bucket is None):
-        bucket = _bucket(net, bucket)
-    scal = PT.check_out(out, 4, dev) if out is not None else torch.empty(4, dtype=torch.float32, device=dev)
-    act, lpo, adv = action.contiguous(), log_probs_old.contiguous(), advantages.contiguous()
-    index, ews, x4, h0, flags, y, hist, view = _device_forward_to_y(net, xs, xo, xc, shape, segment, L, NS, actor_rnn_state, is_init, ws)
-    dy = view("dy")
-    log_probs = torch.empty(B, L, A, 1, dtype=torch.float32, device=dev)
-    nbytes = lib.hns_rnn_actor_head_workspace_bytes(B, A, L)
-    hws = ws.bytes("head", nbytes, dev)
-    own = bucket if bucket is not None else PT.GradBucket(flat_parameters(net))        # (global_rows without a bucket: the gradients only)
-    g = _head_grads(net, own)
-    rows = _rows_struct(y, segment, NS)
-    args = (net.head["head_w"].data_ptr(), net.head["head_b"].data_ptr(), net.head["log_std"].data_ptr(), C.byref(rows), act.data_ptr(), lpo.data_ptr(),
-            adv.data_ptr(), float(clip_param), float(entropy_coef), dy.data_ptr(), g["head_w"].data_ptr(), g["head_b"].data_ptr(), g["log_std"].data_ptr(),
-            scal[0:].data_ptr(), scal[1:].data_ptr(), scal[2:].data_ptr(), log_probs.data_ptr(), hws.data_ptr(), nbytes,
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    with torch.cuda.device(dev):
-        if glob:
-            rc = lib.hns_rnn_actor_head_grad_global(*args, int(global_rows), float(entropy_share))
-        else:
-            rc = lib.hns_rnn_actor_head_grad(*args)
-    abi.check(rc, "hns_rnn_actor_head_grad_global" if glob else "hns_rnn_actor_head_grad")
-    _device_backward(net, own, xs, xo, xc, shape, index, ews, x4, h0, flags, hist, dy, view, ws)
-    if glob:
-        norm = PT.finish_global(bucket, group, scal[3:4])
-        return ActorLoss(scal[0], scal[1], scal[2], scal[3] if norm is not None else None, log_probs)
-    bucket.norm(scal[3:4])
-    return ActorLoss(scal[0], scal[1], scal[2], scal[3], log_probs)
-
-
-def _critic_checks(loss, clip_param, huber_delta):
-    if loss not in critic_train.LOSSES:
-        raise ValueError(f"loss must be 'huber' or 'mse', not {loss!r}")
-    if not clip_param >= 0 or (loss == "huber" and not huber_delta > 0):
-        raise ValueError("clip_param must be >= 0 and huber_delta > 0")
-
-
 class _Forward:
     """value_loss_sums_rnn's forward state for value_loss_and_grad_rnn(forward=): opaque.  On the device the tensors lie in the caller's
     RnnWorkspace (y, h_hist, the features) or are the call's own (the gathered h0 / flags, the index); on the CPU it is y with its graph."""
@@ -445,6 +335,124 @@ def _forward_key(net, xs, segment, L, ws):
     return (id(net.head["head_w"]), xs.data_ptr(), tuple(xs.shape), segment.data_ptr(), segment.numel(), L, id(ws))
 
 
+# What varies between the entries below, the head: actor (or critic); per_row: (name, tensor, values per agent row) of the update's own
+# tensors; keys, row_key: the scalars and the per-row result in the restatement's dict, in the result's order (no keys: the forward-only head
+# of value_loss_sums_rnn); restate(head parameters, y, *gathered rows): the CPU statements; launch(lib, head parameters, hns_rnn_rows, the
+# per-row tensors, dy, the head's gradient views, the result slots, head workspace, its bytes, stream, (B, L, A)): the C call, returning
+# the per-row result; check(device): the caller's refusals that need the prepared tensors.
+_Head = collections.namedtuple("_Head", ["actor", "per_row", "keys", "row_key", "restate", "launch", "check"], defaults=(None,))
+
+
+def _run(head, network, obs, state, is_init, segment, seq_len, check_index, workspace=None, out=None, bucket=None, global_rows=None, group=None,
+         forward=None):
+    """The one path behind the three entries, for both networks, the local and the global form, the CPU and the device: prepare, forward to y
+    (or go on from `forward`), the head, backward from dy into the bucket, the norm.  Returns (the head's scalars, grad_norm, its per-row
+    result) — or, for the forward-only head, (sums, values, the forward state)."""
+    word = "actor" if head.actor else "critic"
+    net = network_parameters(network, head.actor)
+    xs, xo, xc, shape, segment, L, NS = _prepare(word, net, obs, state, is_init, head.per_row, segment, seq_len, check_index and forward is None)
+    A, B, glob = shape[2], segment.numel(), global_rows is not None
+    if glob or group is not None:
+        PT.check_global(word, dict(enumerate(flat_parameters(net))), global_rows, B * L * A, group, bucket)
+    if head.check is not None:
+        head.check(xs.device)
+    if forward is not None and (not isinstance(forward, _Forward) or forward.key != _forward_key(net, xs, segment, L, workspace if xs.is_cuda else None)):
+        raise ValueError("forward= must be value_loss_sums_rnn's state of the same critic, observations, segment tensor, seq_len and workspace")
+    if not xs.is_cuda:
+        fwd = forward.state if forward is not None else _torch_forward(net, xs, xo, xc, shape, segment, L, NS, state, is_init,
+                                                                       [(t, w) for _, t, w in head.per_row])
+        if not head.keys:
+            with torch.no_grad():
+                sums, v = head.restate(net.head, fwd[0].detach(), *fwd[2])
+            return sums, v.unsqueeze(-1), _Forward(_forward_key(net, xs, segment, L, None), fwd)
+        res = _torch_update(net, fwd, head.restate)
+        if not glob:
+            with torch.no_grad():                                # clip_grad_norm_'s total norm
+                norm = torch.nn.utils.clip_grad_norm_(flat_parameters(net), float("inf"))
+        else:                                                    # the data-parallel call: the bucket's norm after its all-reduce
+            if bucket is not None:
+                bucket.adopt()
+            norm = PT.finish_global(bucket, group)
+            norm = norm.reshape(()) if norm is not None else None
+        return [res[k] for k in head.keys], norm, res[head.row_key].unsqueeze(-1)
+    dev, lib, n = xs.device, abi.load_library(), len(head.keys)
+    ws = workspace if workspace is not None else RnnWorkspace()
+    scal = None
+    if head.keys:
+        if not (glob and bucket is None):
+            bucket = _bucket(net, bucket)
+        scal = PT.check_out(out, n + 1, dev) if out is not None else torch.empty(n + 1, dtype=torch.float32, device=dev)
+    per_row = [t.contiguous() for _, t, _ in head.per_row]
+    fwd = forward.state[0] if forward is not None else _device_forward_to_y(net, xs, xo, xc, shape, segment, L, NS, state, is_init, ws)
+    index, ews, x4, h0, flags, y, hist, view = fwd
+    nbytes = (lib.hns_rnn_actor_head_workspace_bytes if head.actor else lib.hns_rnn_critic_head_workspace_bytes)(B, A, L)
+    call = (lib, net.head, _rows_struct(y, segment, NS), per_row)
+    tail = (ws.bytes("head", nbytes, dev), nbytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), (B, L, A))
+    if not head.keys:
+        with torch.cuda.device(dev):
+            sums, values = head.launch(*call, None, None, None, *tail)
+        return sums, values, _Forward(_forward_key(net, xs, segment, L, ws), (fwd, segment))
+    dy = view("dy")
+    own = bucket if bucket is not None else PT.GradBucket(flat_parameters(net))        # (global_rows without a bucket: the gradients only)
+    with torch.cuda.device(dev):
+        rows_out = head.launch(*call, dy, dict(zip(net.head, own.views[len(net.encoder) + len(net.gru):])), scal, *tail)
+    _device_backward(net, own, xs, xo, xc, shape, index, ews, x4, h0, flags, hist, dy, view, ws)
+    norm = PT.finish_global(bucket, group, scal[n:]) if glob else bucket.norm(scal[n:])
+    return scal[:n].unbind(), scal[n] if norm is not None else None, rows_out
+
+
+def policy_loss_and_grad_rnn(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, segment=None,
+                             seq_len=16, clip_param=0.1, entropy_coef=0.001, check_index=True, workspace=None, out=None, bucket=None,
+                             global_rows=None, entropy_share=1.0, group=None):
+    """update_actor_rnn up to the gradient norm: ActorLoss(policy_loss, entropy, ess, grad_norm: 0-dim tensors; log_probs [B, L, A, 1]) and
+    every parameter's .grad (views of ONE flat GradBucket on the device: `bucket` (make_bucket), or one made for the call).
+
+    actor: the recurrent actor's parameters under the reference's names (encoder.*, rnn.*, act_dist.*); obs_*: the rollout's [N, T, A, ...]
+    observations; actor_rnn_state [N, T / L, A, 128]: the state going into every segment; is_init [N, T, 1]; action [N, T, A, 4],
+    log_probs_old, advantages [N, T, A, 1]; segment: int64 [B] ids into the flattened [N, T / L] (None: all, in order); seq_len: L.
+    `check_index` range-checks the ids (one host synchronisation); unchecked, an id outside the rollout contributes nothing on the device (its
+    rows are dead in the head entry, the encoder and the GRU run on a clamped copy of it) and raises IndexError from torch's gather on the
+    CPU.  `workspace`: an RnnWorkspace kept between calls; `out`: four fp32 device values that receive policy_loss, entropy, ess and
+    grad_norm.  Both are ignored on the CPU.
+
+    `global_rows` (None: the call above, untouched): this minibatch is one rank's part of a union of `global_rows` rows
+    (hns_rnn_actor_head_grad_global): policy_loss is this rank's SHARE, -4 sum_local / global_rows, and the gradients are the share's — over
+    the ranks both add up to the union's.  `entropy_share`: the part of the entropy term's gradient this rank adds (1 / world).  ess stays
+    this rank's own.  `bucket` is then the network's GradBucket and grad_norm its norm (None without one); `group`: the bucket is all-reduced
+    (SUM) over it first."""
+    if not clip_param >= 0:
+        raise ValueError("clip_param must be >= 0")
+    if not math.isfinite(float(entropy_share)):
+        raise ValueError("entropy_share must be finite")
+
+    def restate(p, y, a, lpo, adv):
+        return actor_head(p["head_w"], p["head_b"], p["log_std"], y, a, lpo, adv, float(clip_param), float(entropy_coef), global_rows,
+                          float(entropy_share))
+
+    def launch(lib, p, rows, per_row, dy, g, scal, hws, nbytes, st, dims):
+        log_probs = torch.empty(*dims, 1, dtype=torch.float32, device=hws.device)
+        entry, more = (lib.hns_rnn_actor_head_grad, ()) if global_rows is None else \
+            (lib.hns_rnn_actor_head_grad_global, (int(global_rows), float(entropy_share)))
+        rc = entry(p["head_w"].data_ptr(), p["head_b"].data_ptr(), p["log_std"].data_ptr(), C.byref(rows), *(t.data_ptr() for t in per_row),
+                   float(clip_param), float(entropy_coef), dy.data_ptr(), g["head_w"].data_ptr(), g["head_b"].data_ptr(), g["log_std"].data_ptr(),
+                   scal[0:].data_ptr(), scal[1:].data_ptr(), scal[2:].data_ptr(), log_probs.data_ptr(), hws.data_ptr(), nbytes, st, *more)
+        abi.check(rc, entry.__name__)
+        return log_probs
+
+    head = _Head(True, (("action", action, P.ACTION_DIM), ("log_probs_old", log_probs_old, 1), ("advantages", advantages, 1)),
+                 ("policy_loss", "entropy", "ess"), "log_probs", restate, launch)
+    scalars, norm, log_probs = _run(head, actor, (obs_self, obs_others, obs_cylinders), actor_rnn_state, is_init, segment, seq_len, check_index,
+                                    workspace, out, bucket, global_rows, group)
+    return ActorLoss(*scalars, norm, log_probs)
+
+
+def _critic_checks(loss, clip_param, huber_delta):
+    if loss not in critic_train.LOSSES:
+        raise ValueError(f"loss must be 'huber' or 'mse', not {loss!r}")
+    if not clip_param >= 0 or (loss == "huber" and not huber_delta > 0):
+        raise ValueError("clip_param must be >= 0 and huber_delta > 0")
+
+
 def value_loss_sums_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_state, is_init, b_values, b_returns, segment=None, seq_len=16,
                         clip_param=0.1, loss="huber", huber_delta=10.0, check_index=True, workspace=None):
     """The forward half of a data-parallel value_loss_and_grad_rnn: encoder -> GRU -> hns_rnn_critic_head_sums.  Returns
@@ -454,34 +462,21 @@ def value_loss_sums_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_
     from y instead of running the encoder and the GRU again.  The state is valid until the next call that uses `workspace` (segment= must
     be the same tensor in both calls).  Arguments and refusals: value_loss_and_grad_rnn's."""
     _critic_checks(loss, clip_param, huber_delta)
-    net = network_parameters(critic, False)
-    per_row = (("b_values", b_values, 1), ("b_returns", b_returns, 1))
-    xs, xo, xc, shape, segment, L, NS = _prepare("critic", net, (obs_self, obs_others, obs_cylinders), critic_rnn_state, is_init, per_row, segment,
-                                                 seq_len, check_index)
-    A = shape[2]
-    if not xs.is_cuda:
-        fwd = _torch_forward(net, xs, xo, xc, shape, segment, L, NS, critic_rnn_state, is_init, [(t, w) for _, t, w in per_row])
-        with torch.no_grad():
-            sums, v = critic_head_sums(net.head["head_w"], net.head["head_b"], fwd[0].detach(), *fwd[2], float(clip_param), loss, float(huber_delta))
-        return CriticSumsRnn(sums, v.unsqueeze(-1), _Forward(_forward_key(net, xs, segment, L, None), fwd))
-    dev = xs.device
-    lib = abi.load_library()
-    ws = workspace if workspace is not None else RnnWorkspace()
-    bv, ret = b_values.contiguous(), b_returns.contiguous()
-    state = _device_forward_to_y(net, xs, xo, xc, shape, segment, L, NS, critic_rnn_state, is_init, ws)
-    y = state[5]
-    B = segment.numel()
-    sums = torch.empty(5, dtype=torch.float64, device=dev)
-    values = torch.empty(B, L, A, 1, dtype=torch.float32, device=dev)
-    nbytes = lib.hns_rnn_critic_head_workspace_bytes(B, A, L)
-    hws = ws.bytes("head", nbytes, dev)
-    rows = _rows_struct(y, segment, NS)
-    with torch.cuda.device(dev):
-        rc = lib.hns_rnn_critic_head_sums(net.head["head_w"].data_ptr(), net.head["head_b"].data_ptr(), C.byref(rows), bv.data_ptr(), ret.data_ptr(),
+
+    def restate(p, y, bv, ret):
+        return critic_head_sums(p["head_w"], p["head_b"], y, bv, ret, float(clip_param), loss, float(huber_delta))
+
+    def launch(lib, p, rows, per_row, dy, g, scal, hws, nbytes, st, dims):
+        sums = torch.empty(5, dtype=torch.float64, device=hws.device)
+        values = torch.empty(*dims, 1, dtype=torch.float32, device=hws.device)
+        rc = lib.hns_rnn_critic_head_sums(p["head_w"].data_ptr(), p["head_b"].data_ptr(), C.byref(rows), *(t.data_ptr() for t in per_row),
                                           float(clip_param), critic_train.LOSSES[loss], float(huber_delta), sums.data_ptr(), values.data_ptr(),
-                                          hws.data_ptr(), nbytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    abi.check(rc, "hns_rnn_critic_head_sums")
-    return CriticSumsRnn(sums, values, _Forward(_forward_key(net, xs, segment, L, ws), (state, segment)))
+                                          hws.data_ptr(), nbytes, st)
+        abi.check(rc, "hns_rnn_critic_head_sums")
+        return sums, values
+
+    head = _Head(False, (("b_values", b_values, 1), ("b_returns", b_returns, 1)), (), None, restate, launch)
+    return CriticSumsRnn(*_run(head, critic, (obs_self, obs_others, obs_cylinders), critic_rnn_state, is_init, segment, seq_len, check_index, workspace))
 
 
 def value_loss_and_grad_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_state, is_init, b_values, b_returns, segment=None, seq_len=16,
@@ -501,70 +496,28 @@ def value_loss_and_grad_rnn(critic, obs_self, obs_others, obs_cylinders, critic_
         raise ValueError("sums= and global_rows= travel together: the union's five sums and its row count")
     if forward is not None and sums is None:
         raise ValueError("forward= belongs to the data-parallel call: pass sums= and global_rows= as well")
-    net = network_parameters(critic, False)
-    per_row = (("b_values", b_values, 1), ("b_returns", b_returns, 1))
-    xs, xo, xc, shape, segment, L, NS = _prepare("critic", net, (obs_self, obs_others, obs_cylinders), critic_rnn_state, is_init, per_row, segment,
-                                                 seq_len, check_index and forward is None)
-    A = shape[2]
-    B = segment.numel()
-    glob = global_rows is not None
-    if glob or group is not None:
-        _check_global("critic", net, global_rows, B * L * A, group, bucket)
-    if sums is not None and (not torch.is_tensor(sums) or sums.dtype != torch.float64 or sums.numel() != 5 or sums.device != xs.device or
-                             not sums.is_contiguous()):
-        raise ValueError(f"sums must be five contiguous float64 values on {xs.device}")
-    if forward is not None and (not isinstance(forward, _Forward) or forward.key != _forward_key(net, xs, segment, L, workspace if xs.is_cuda else None)):
-        raise ValueError("forward= must be value_loss_sums_rnn's state of the same critic, observations, segment tensor, seq_len and workspace")
-    if not xs.is_cuda:
-        res = _torch_update(net, xs, xo, xc, shape, segment, L, NS, critic_rnn_state, is_init, [(t, w) for _, t, w in per_row],
-                            lambda y, bv, ret: critic_head(net.head["head_w"], net.head["head_b"], y, bv, ret, float(clip_param), loss,
-                                                           float(huber_delta), sums, global_rows),
-                            forward=forward.state if forward is not None else None)
-        norm = _finish_cpu(net, global_rows, group, bucket if glob else None)
-        return CriticLoss(res["value_loss"], res["explained_var"], norm, res["values"].unsqueeze(-1))
-    dev = xs.device
-    lib = abi.load_library()
-    ws = workspace if workspace is not None else RnnWorkspace()
-    if not (glob and bucket is None):
-        bucket = _bucket(net, bucket)
-    scal = PT.check_out(out, 3, dev) if out is not None else torch.empty(3, dtype=torch.float32, device=dev)
-    bv, ret = b_values.contiguous(), b_returns.contiguous()
-    if forward is not None:
-        index, ews, x4, h0, flags, y, hist, view = forward.state[0]
-    else:
-        index, ews, x4, h0, flags, y, hist, view = _device_forward_to_y(net, xs, xo, xc, shape, segment, L, NS, critic_rnn_state, is_init, ws)
-    dy = view("dy")
-    values = None if glob else torch.empty(B, L, A, 1, dtype=torch.float32, device=dev)
-    nbytes = lib.hns_rnn_critic_head_workspace_bytes(B, A, L)
-    hws = ws.bytes("head", nbytes, dev)
-    own = bucket if bucket is not None else PT.GradBucket(flat_parameters(net))
-    g = _head_grads(net, own)
-    rows = _rows_struct(y, segment, NS)
-    args = (net.head["head_w"].data_ptr(), net.head["head_b"].data_ptr(), C.byref(rows), bv.data_ptr(), ret.data_ptr(), float(clip_param),
-            critic_train.LOSSES[loss], float(huber_delta), dy.data_ptr(), g["head_w"].data_ptr(), g["head_b"].data_ptr(), scal[0:].data_ptr(),
-            scal[1:].data_ptr(), values.data_ptr() if values is not None else None, hws.data_ptr(), nbytes,
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    with torch.cuda.device(dev):
-        if glob:
-            rc = lib.hns_rnn_critic_head_grad_global(*args, sums.data_ptr(), int(global_rows))
-        else:
-            rc = lib.hns_rnn_critic_head_grad(*args)
-    abi.check(rc, "hns_rnn_critic_head_grad_global" if glob else "hns_rnn_critic_head_grad")
-    _device_backward(net, own, xs, xo, xc, shape, index, ews, x4, h0, flags, hist, dy, view, ws)
-    if glob:
-        norm = PT.finish_global(bucket, group, scal[2:3])
-        return CriticLoss(scal[0], scal[1], scal[2] if norm is not None else None, None)
-    bucket.norm(scal[2:3])
-    return CriticLoss(scal[0], scal[1], scal[2], values)
 
+    def check(dev):
+        if sums is not None and (not torch.is_tensor(sums) or sums.dtype != torch.float64 or sums.numel() != 5 or sums.device != dev or
+                                 not sums.is_contiguous()):
+            raise ValueError(f"sums must be five contiguous float64 values on {dev}")
 
-def _check_optimizer(optimizer, word):
-    if not isinstance(optimizer, ClippedAdam):
-        raise TypeError(f"update_{word}_rnn takes a ClippedAdam (rnn_train.make_optimizer), not {type(optimizer).__name__}: the clip and the step "
-                        "are one launch that needs the gradient norm")
-    for pg in optimizer.param_groups:
-        if pg.get("weight_decay", 0) != 0:
-            raise NotImplementedError("weight_decay != 0 is not supported")
+    def restate(p, y, bv, ret):
+        return critic_head(p["head_w"], p["head_b"], y, bv, ret, float(clip_param), loss, float(huber_delta), sums, global_rows)
+
+    def launch(lib, p, rows, per_row, dy, g, scal, hws, nbytes, st, dims):
+        values = None if sums is not None else torch.empty(*dims, 1, dtype=torch.float32, device=hws.device)
+        entry, more = (lib.hns_rnn_critic_head_grad, ()) if sums is None else (lib.hns_rnn_critic_head_grad_global, (sums.data_ptr(), int(global_rows)))
+        rc = entry(p["head_w"].data_ptr(), p["head_b"].data_ptr(), C.byref(rows), *(t.data_ptr() for t in per_row), float(clip_param),
+                   critic_train.LOSSES[loss], float(huber_delta), dy.data_ptr(), g["head_w"].data_ptr(), g["head_b"].data_ptr(), scal[0:].data_ptr(),
+                   scal[1:].data_ptr(), values.data_ptr() if values is not None else None, hws.data_ptr(), nbytes, st, *more)
+        abi.check(rc, entry.__name__)
+        return values
+
+    head = _Head(False, (("b_values", b_values, 1), ("b_returns", b_returns, 1)), ("value_loss", "explained_var"), "values", restate, launch, check)
+    scalars, norm, values = _run(head, critic, (obs_self, obs_others, obs_cylinders), critic_rnn_state, is_init, segment, seq_len, check_index,
+                                 workspace, out, bucket, global_rows, group, forward)
+    return CriticLoss(*scalars, norm, values)
 
 
 def update_actor_rnn(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, optimizer, segment=None,
@@ -577,15 +530,13 @@ def update_actor_rnn(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state
     step, one collective."""
     if global_rows is not None and bucket is None:
         raise ValueError("update_actor_rnn with global_rows= steps on the bucket's norm: pass bucket=")
-    _check_optimizer(optimizer, "actor")
+    PT.check_optimizer(optimizer, "update_actor_rnn", "rnn_train.make_optimizer")
     get = PT.getter(cfg)
     L = int(seq_len) if seq_len is not None else train_seq_len(cfg)
     res = policy_loss_and_grad_rnn(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, segment, L,
                                    float(get("clip_param", 0.1)), float(get("entropy_coef", 0.001)), check_index, workspace, out, bucket,
                                    **(dict(global_rows=global_rows, entropy_share=entropy_share, group=group) if global_rows is not None or group is not None else {}))
-    optimizer.step(grad_norm=res.grad_norm)
-    norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else res.grad_norm
-    return {"policy_loss": res.policy_loss, "actor_grad_norm": norm, "entropy": res.entropy, "ESS": res.ess}
+    return {"policy_loss": res.policy_loss, "actor_grad_norm": PT.clipped_step(optimizer, res.grad_norm), "entropy": res.entropy, "ESS": res.ess}
 
 
 def update_critic_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_state, is_init, b_values, b_returns, optimizer, segment=None, cfg=None,
@@ -599,7 +550,7 @@ def update_critic_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_st
         raise ValueError("update_critic_rnn with global_rows= steps on the bucket's norm: pass bucket=")
     if global_rows is not None and sums is None and group is None:
         raise ValueError("update_critic_rnn with global_rows= needs the union's sums= or the group= to add them over")
-    _check_optimizer(optimizer, "critic")
+    PT.check_optimizer(optimizer, "update_critic_rnn", "rnn_train.make_optimizer")
     get, sget = PT.getter(cfg), PT.getter(PT.getter(cfg)("critic", None))
     L = int(seq_len) if seq_len is not None else train_seq_len(cfg)
     hyper = (float(get("clip_param", 0.1)), "huber" if sget("use_huber_loss", True) else "mse", float(sget("huber_delta", 10.0)))
@@ -617,9 +568,7 @@ def update_critic_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_st
                 kw["forward"] = half.forward
     res = value_loss_and_grad_rnn(critic, obs_self, obs_others, obs_cylinders, critic_rnn_state, is_init, b_values, b_returns, segment, L, *hyper,
                                   check_index, workspace, out, bucket, **kw)
-    optimizer.step(grad_norm=res.grad_norm)
-    norm = optimizer.last_grad_norm if getattr(optimizer, "last_grad_norm", None) is not None else res.grad_norm
-    return {"value_loss": res.value_loss, "critic_grad_norm": norm, "explained_var": res.explained_var}
+    return {"value_loss": res.value_loss, "critic_grad_norm": PT.clipped_step(optimizer, res.grad_norm), "explained_var": res.explained_var}
 
 
 def train_seq_len(cfg):

@@ -117,7 +117,7 @@ def main():
         tp = P.parse_parameters_per_agent(pt)[0]
 
         def torch_step():
-            res = AT._torch_loss_and_grad_per_agent(tp, xs, xo, xc, action, lpo, adv, idx, 0.1, 0.001)
+            res = AT._torch_loss_and_grad(tp, xs, xo, xc, action, lpo, adv, idx, 0.1, 0.001, per_agent=True)
             nn.utils.clip_grad_norm_(list(tp.values()), 10.0)
             ot.step()
             return res
