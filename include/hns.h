@@ -832,6 +832,39 @@ int hns_policy_forward_rnn(const void *packed, const void *rnn_packed, int32_t s
 int hns_policy_act_rnn(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
                        const hns_policy_io *io, const hns_policy_rnn_io *rio, void *stream);
 /*
+ * One RECURRENT actor per agent (share_actor: false with actor.rnn / critic.rnn; hns_amd.policy.PerAgentRecurrentDevicePolicy; DESIGN.md
+ * §7.17): the reference stacks the actor's parameters — its GRU's among them — over the agents and vmaps the actor over the agent axis
+ * (mappo.py:148-152, :243-246, :281-284); the critic and the critic's GRU stay shared.  `packed` is hns_policy_pack_agents' image (A actor
+ * images, then the critic's); `rnn_packed` the image below.  The entries above keep their behaviour.
+ *
+ * hns_policy_rnn_packed_agents_bytes: bytes of num_agents actor-GRU images followed by ONE critic-GRU image, each one network's half of
+ * hns_policy_rnn_pack's image (hns_policy_rnn_packed_bytes() / 2 bytes); 0 for num_agents outside [1, 7].
+ * hns_policy_rnn_pack_agents: ONE launch builds that image (16-byte aligned); call it again after the tensors change.  `actor_rnns`: a
+ * hns_gru_net whose every tensor is the stacked one ([A, 384, 128] x2, [A, 384] x2, [A, 128] x2, contiguous), so agent a's slice is a
+ * hns_gru_net of its own; `critic_rnn` as for hns_policy_rnn_pack.  Image a (a < A) is byte for byte the actor half of hns_policy_rnn_pack's
+ * image of (agent a's slice, critic_rnn) — the pre-added b_ir + b_hr and b_iz + b_hz included — and image A its critic half.  Refused before
+ * the launch: num_agents out of range, then what hns_policy_rnn_pack refuses (a NULL or misaligned image, a NULL network, a NULL or
+ * misaligned tensor pointer).
+ * hns_policy_forward_rnn_agents: hns_policy_forward_rnn's arguments, flags, outputs, layouts ([E, A, ...]; the states [E, A, 128]), noise
+ * scheme (the Philox counter of row e A + a is the call counter and e A + a; the bump after a sampling call without io->eps), in-place rule
+ * (h_out may be h_in) and refusals in its order, all before any launch.  ONE launch (plus the bump): a workgroup is 32 consecutive envs of ONE
+ * agent, its actor pass reads that agent's two images, its critic pass the shared two; a tile's state rows lie A 512 bytes apart.  The
+ * per-row arithmetic is hns_policy_forward_rnn's and a row's results do not depend on the rows it shares a tile with: for every agent a,
+ * every output of row (e, a) — action, loc, log_prob, value, actor_h_out, critic_h_out — is bit for bit what hns_policy_forward_rnn writes
+ * for that row on hns_policy_pack's and hns_policy_rnn_pack's images of (agent a's slices, critic).  Deterministic: fixed-order sums, no
+ * atomics; no host synchronisation, no allocation, capturable.
+ * hns_policy_act_rnn_agents: hns_policy_act_rnn on those images in the same tiles (ONE launch, the actor half alone; its arguments and its
+ * refusals, before the launch): bit for bit hns_policy_forward_rnn_agents' action and actor_h_out with HNS_POLICY_DETERMINISTIC; nothing
+ * else is read or written.
+ */
+size_t hns_policy_rnn_packed_agents_bytes(int32_t num_agents);
+int hns_policy_rnn_pack_agents(const hns_gru_net *actor_rnns, const hns_gru_net *critic_rnn, int32_t num_agents, void *rnn_packed, void *stream);
+int hns_policy_forward_rnn_agents(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents,
+                                  int32_t num_cylinders, const hns_policy_io *io, const hns_policy_rnn_io *rio, int32_t flags, uint64_t seed,
+                                  uint64_t *counter, void *stream);
+int hns_policy_act_rnn_agents(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                              const hns_policy_io *io, const hns_policy_rnn_io *rio, void *stream);
+/*
  * The head and the loss of a recurrent update over hns_gru_forward's output, forward and backward (hns_amd.rnn_train): what a
  * recurrent learner runs between hns_gru_forward and hns_gru_backward.  A minibatch is B segments x L steps x A agents; row (b, t, a), row index
  * (b L + t) A + a, reads the 128 values at y + b y_stride[0] + a y_stride[1] + t y_stride[2] (hns_gru_seq.x_stride's three strides: the op's

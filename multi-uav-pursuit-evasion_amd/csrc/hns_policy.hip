@@ -34,6 +34,10 @@
 //   hns_policy_pack_agents_kernel, hns_policy_forward_agents_kernel, hns_policy_act_agents_kernel : one actor per agent (share_actor: false;
 //                               DESIGN §7.16): A actor images and the critic's; a workgroup's rows are 32 envs of ONE agent (blockIdx.y), its actor pass
 //                               reads that agent's image; the same per-row functions, so row (e, a) has the shared kernels' bits with agent a's image.
+//   hns_policy_rnn_pack_agents_kernel, hns_policy_forward_rnn_agents_kernel, hns_policy_act_rnn_agents_kernel : one RECURRENT actor per agent
+//                               (DESIGN §7.17): A actor GRU images and the critic's beside the A + 1 encoder images, the same agent-major tile;
+//                               the state rows keep their place e A + a in [E, A, 128] (pol_gru_step<true>), so row (e, a) has the shared
+//                               recurrent kernels' bits with agent a's two images.
 // Determinism: fixed reduction orders (butterflies over the eight lanes of a row), no atomics.
 #include <hip/hip_runtime.h>
 
@@ -360,15 +364,30 @@ HNS_DEV void pol_gate_prod(const float *__restrict__ W, const float *in, int w, 
 // products run one after another onto one set of accumulators; the three gates of a (feature, row) pair land in the same lane, so the cell
 // runs in the accumulator layout and only h' crosses the LDS back to the eight-lanes-per-row layout.  Every read of h_in precedes the first
 // barrier and every write of h_out follows it, and a workgroup touches its own rows only: h_out may be h_in.
+//
+// AGENTS (one actor per agent): the tile is 32 consecutive envs of agent blockIdx.y, so `row0` is the tile's first ENV and `rows`
+// the number of envs; tile position p is live iff row0 + p < rows, its state row is (row0 + p) A + agent — A 512 bytes apart instead of
+// contiguous, on the load (position r) and on the accumulator-layout store (position rr) alike — and its flag is_init[row0 + p].  The
+// arithmetic is the same statements; the shared form (AGENTS false) compiles to what it was.
+template <bool AGENTS = false>
 HNS_DEV void pol_gru_step(const float *rn, const float *h_in, float *h_out, const unsigned char *is_init, int A, long long row0, long long rows,
                           PolLds &L, int w, int lane, int r, int g, float (&y)[16]) {
     float h[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) h[i] = 0.0f;
-    if (h_in && row0 + r < rows && !(is_init && is_init[(row0 + r) / A])) {          // the env's flag holds for all of its agents
+    bool read;
+    long long hr;
+    if constexpr (AGENTS) {
+        read = h_in && row0 + r < rows && !(is_init && is_init[row0 + r]);
+        hr = (row0 + r) * A + blockIdx.y;
+    } else {
+        read = h_in && row0 + r < rows && !(is_init && is_init[(row0 + r) / A]);     // the env's flag holds for all of its agents
+        hr = row0 + r;
+    }
+    if (read) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(h_in + (row0 + r) * kEncE + enc_feat(g, i, 0));
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(h_in + hr * kEncE + enc_feat(g, i, 0));
 #pragma unroll
             for (int u = 0; u < 4; ++u) h[4 * i + u] = v[u];
         }
@@ -419,7 +438,10 @@ HNS_DEV void pol_gru_step(const float *rn, const float *h_in, float *h_out, cons
                 o[q] = (1.0f - z) * n[i][c][q] + z * L.t1[(f0 + q) * kEncLd + rr];       // h' = (1 - z) n + z h
                 L.t2[(f0 + q) * kEncLd + rr] = o[q];
             }
-            if (row0 + rr < rows) *reinterpret_cast<f32x4 *>(h_out + (row0 + rr) * kEncE + f0) = o;
+            if (row0 + rr < rows) {
+                const long long orow = AGENTS ? (row0 + rr) * A + blockIdx.y : row0 + rr;
+                *reinterpret_cast<f32x4 *>(h_out + orow * kEncE + f0) = o;
+            }
         }
     }
     __syncthreads();
@@ -529,6 +551,64 @@ __global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_agents_kernel(c
     const float *net = a.img + (long long)blockIdx.y * a.net_floats;
     float y[16];
     pol_encoder(a, net, L, w, lane, r, g, row, y);
+    float loc[4];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
+    if (row < a.rows && g == 0) {
+#pragma unroll
+        for (int o = 0; o < 4; ++o) a.action[row * 4 + o] = loc[o];
+    }
+}
+
+// ---- one recurrent actor per agent (share_actor: false with actor.rnn / critic.rnn; include/hns.h: hns_policy_forward_rnn_agents)
+// The two images hold A actor images / A actor-GRU images, then the critic's one of each.  The tile is §7.16's (32 envs of agent blockIdx.y); the
+// actor pass reads the agent's two images, the critic pass the shared two; the state rows keep their place e A + a in [E, A, 128]
+// (pol_gru_step<true>).  Row (e, a) has the bits hns_policy_forward_rnn gives it on the images of (agent a's slices, critic).
+struct GruSrcs {
+    GruSrc n[HNS_MAX_AGENTS + 1];            // the agents' slices of the stacked actor GRU (formed on the host), then the critic's GRU
+};
+
+__global__ __launch_bounds__(256) void hns_policy_rnn_pack_agents_kernel(const GruSrcs nets, float *img) {
+    float *dst = img + (long long)blockIdx.y * R_NET;            // image blockIdx.y: 0 .. A - 1 the agents' actor GRUs, A the critic's
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < R_NET; i += gridDim.x * 256) dst[i] = pol_rnn_src(nets.n[blockIdx.y], i);
+}
+
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_rnn_agents_kernel(const PolArgs a, const PolRnnArgs ra) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
+    const long long env0 = (long long)blockIdx.x * kEncRows, envs = a.rows / a.A;
+    const long long row = pol_agent_row(a, r);
+    const bool live = row < a.rows;
+    float y[16];
+
+    if (!a.value_only) {
+        const float *net = a.img + (long long)blockIdx.y * a.net_floats;      // the agent's actor and its GRU, formed once per tile
+        pol_encoder(a, net, L, w, lane, r, g, row, y);
+        pol_gru_step<true>(ra.img + (long long)blockIdx.y * R_NET, ra.h_in[0], ra.h_out[0], ra.is_init, a.A, env0, envs, L, w, lane, r, g, y);
+        float loc[4];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
+        pol_sample(a, net, loc, row, live, g);
+        __syncthreads();                                          // the critic reuses the LDS
+    }
+    const float *net = a.img + (long long)a.A * a.net_floats;    // the shared critic and its GRU, behind the A actors'
+    pol_encoder(a, net, L, w, lane, r, g, row, y);
+    pol_gru_step<true>(ra.img + (long long)a.A * R_NET, ra.h_in[1], ra.h_out[1], ra.is_init, a.A, env0, envs, L, w, lane, r, g, y);
+    const float v = pol_head(net, 0, y, g);
+    if (live && g == 0) a.value[row] = v;
+}
+
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_rnn_agents_kernel(const PolArgs a, const PolRnnArgs ra) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
+    const long long env0 = (long long)blockIdx.x * kEncRows, envs = a.rows / a.A;
+    const long long row = pol_agent_row(a, r);
+    const float *net = a.img + (long long)blockIdx.y * a.net_floats;
+    float y[16];
+    pol_encoder(a, net, L, w, lane, r, g, row, y);
+    pol_gru_step<true>(ra.img + (long long)blockIdx.y * R_NET, ra.h_in[0], ra.h_out[0], ra.is_init, a.A, env0, envs, L, w, lane, r, g, y);
     float loc[4];
 #pragma unroll
     for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
@@ -727,9 +807,10 @@ int hns_policy_rnn_pack(const hns_gru_net *actor_rnn, const hns_gru_net *critic_
     return HNS_OK;
 }
 
-int hns_policy_forward_rnn(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
-                           const hns_policy_io *io, const hns_policy_rnn_io *rio, int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
-    const char *fn = "hns_policy_forward_rnn";
+// hns_policy_forward_rnn and hns_policy_forward_rnn_agents: the same refusals in the same order, the same arguments; `agents` picks the kernel and its grid
+static int pol_forward_rnn_call(const char *fn, bool agents, const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs,
+                                int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io, const hns_policy_rnn_io *rio, int32_t flags,
+                                uint64_t seed, uint64_t *counter, void *stream) {
     int rc = pol_check_shape(fn, packed, self_dim, num_envs, num_agents, num_cylinders, io);
     if (rc != HNS_OK) return rc;
     if (!rnn_packed || !rio || !hns_aligned(rnn_packed, 16) || !hns_aligned(rio, 8)) return hns_fail(fn, "null or misaligned packed GRU image / rnn io");
@@ -754,15 +835,63 @@ int hns_policy_forward_rnn(const void *packed, const void *rnn_packed, int32_t s
     const hipStream_t st = static_cast<hipStream_t>(stream);
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_forward_rnn_kernel),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
+    static const hipError_t attr_ag = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_forward_rnn_agents_kernel),
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
     HNS_CHECK_HIP(attr);
-    const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
-    hipLaunchKernelGGL(hns::hns_policy_forward_rnn_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), st, a, ra);
+    HNS_CHECK_HIP(attr_ag);
+    if (agents) {                                                 // a tile: 32 consecutive envs of one agent
+        const long long tiles = (num_envs + hns::kEncRows - 1) / hns::kEncRows;
+        hipLaunchKernelGGL(hns::hns_policy_forward_rnn_agents_kernel, dim3((unsigned)tiles, (unsigned)num_agents), dim3(hns::kEncThreads), sizeof(hns::PolLds), st,
+                           a, ra);
+    } else {
+        const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
+        hipLaunchKernelGGL(hns::hns_policy_forward_rnn_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), st, a, ra);
+    }
     HNS_CHECK_HIP(hipGetLastError());
     if (!value_only && !det && !io->eps) {
         hipLaunchKernelGGL(hns::hns_policy_bump_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<unsigned long long *>(counter));
         HNS_CHECK_HIP(hipGetLastError());
     }
     return HNS_OK;
+}
+
+int hns_policy_forward_rnn(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                           const hns_policy_io *io, const hns_policy_rnn_io *rio, int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
+    return pol_forward_rnn_call("hns_policy_forward_rnn", false, packed, rnn_packed, self_dim, num_envs, num_agents, num_cylinders, io, rio, flags, seed,
+                                counter, stream);
+}
+
+size_t hns_policy_rnn_packed_agents_bytes(int32_t num_agents) {
+    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return 0;
+    return (size_t)((num_agents + 1) * hns::R_NET) * sizeof(float);
+}
+
+int hns_policy_rnn_pack_agents(const hns_gru_net *actor_rnns, const hns_gru_net *critic_rnn, int32_t num_agents, void *rnn_packed, void *stream) {
+    const char *fn = "hns_policy_rnn_pack_agents";
+    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return hns_fail(fn, "num_agents must be in [1, 7]");
+    if (!rnn_packed || !hns_aligned(rnn_packed, 16)) return hns_fail(fn, "packed image must be a 16-byte aligned device array");
+    hns::GruSrc sa{}, sc{};
+    int rc = pol_gru_net(fn, actor_rnns, sa);
+    if (rc != HNS_OK) return rc;
+    rc = pol_gru_net(fn, critic_rnn, sc);
+    if (rc != HNS_OK) return rc;
+    hns::GruSrcs nets{};
+    constexpr long long E = hns::kEncE;
+    for (int ag = 0; ag < num_agents; ++ag)                       // agent ag's slice of the stacked tensors: [A, 384, 128] x2, [A, 384] x2, [A, 128] x2
+        nets.n[ag] = hns::GruSrc{sa.w_ih + ag * 3 * E * E, sa.w_hh + ag * 3 * E * E, sa.b_ih + ag * 3 * E, sa.b_hh + ag * 3 * E, sa.ln_w + ag * E,
+                                 sa.ln_b + ag * E};
+    nets.n[num_agents] = sc;
+    hipLaunchKernelGGL(hns::hns_policy_rnn_pack_agents_kernel, dim3(128, (unsigned)num_agents + 1), dim3(256), 0, static_cast<hipStream_t>(stream), nets,
+                       static_cast<float *>(rnn_packed));
+    HNS_CHECK_HIP(hipGetLastError());
+    return HNS_OK;
+}
+
+int hns_policy_forward_rnn_agents(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents,
+                                  int32_t num_cylinders, const hns_policy_io *io, const hns_policy_rnn_io *rio, int32_t flags, uint64_t seed,
+                                  uint64_t *counter, void *stream) {
+    return pol_forward_rnn_call("hns_policy_forward_rnn_agents", true, packed, rnn_packed, self_dim, num_envs, num_agents, num_cylinders, io, rio, flags,
+                                seed, counter, stream);
 }
 
 // hns_policy_act and hns_policy_act_agents over one body, as the forward's two
@@ -802,9 +931,9 @@ int hns_policy_act_agents(const void *packed, int32_t self_dim, int64_t num_envs
     return pol_act_call("hns_policy_act_agents", true, packed, self_dim, num_envs, num_agents, num_cylinders, io, stream);
 }
 
-int hns_policy_act_rnn(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
-                       const hns_policy_io *io, const hns_policy_rnn_io *rio, void *stream) {
-    const char *fn = "hns_policy_act_rnn";
+// hns_policy_act_rnn and hns_policy_act_rnn_agents over one body, as the forward's two
+static int pol_act_rnn_call(const char *fn, bool agents, const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents,
+                            int32_t num_cylinders, const hns_policy_io *io, const hns_policy_rnn_io *rio, void *stream) {
     int rc = pol_check_shape(fn, packed, self_dim, num_envs, num_agents, num_cylinders, io);
     if (rc != HNS_OK) return rc;
     if (!rnn_packed || !rio || !hns_aligned(rnn_packed, 16) || !hns_aligned(rio, 8)) return hns_fail(fn, "null or misaligned packed GRU image / rnn io");
@@ -820,12 +949,31 @@ int hns_policy_act_rnn(const void *packed, const void *rnn_packed, int32_t self_
     ra.is_init = rio->is_init;
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_act_rnn_kernel),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
+    static const hipError_t attr_ag = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_act_rnn_agents_kernel),
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
     HNS_CHECK_HIP(attr);
-    const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
-    hipLaunchKernelGGL(hns::hns_policy_act_rnn_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), static_cast<hipStream_t>(stream), a,
-                       ra);
+    HNS_CHECK_HIP(attr_ag);
+    if (agents) {
+        const long long tiles = (num_envs + hns::kEncRows - 1) / hns::kEncRows;
+        hipLaunchKernelGGL(hns::hns_policy_act_rnn_agents_kernel, dim3((unsigned)tiles, (unsigned)num_agents), dim3(hns::kEncThreads), sizeof(hns::PolLds),
+                           static_cast<hipStream_t>(stream), a, ra);
+    } else {
+        const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
+        hipLaunchKernelGGL(hns::hns_policy_act_rnn_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), static_cast<hipStream_t>(stream),
+                           a, ra);
+    }
     HNS_CHECK_HIP(hipGetLastError());
     return HNS_OK;
+}
+
+int hns_policy_act_rnn(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                       const hns_policy_io *io, const hns_policy_rnn_io *rio, void *stream) {
+    return pol_act_rnn_call("hns_policy_act_rnn", false, packed, rnn_packed, self_dim, num_envs, num_agents, num_cylinders, io, rio, stream);
+}
+
+int hns_policy_act_rnn_agents(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                              const hns_policy_io *io, const hns_policy_rnn_io *rio, void *stream) {
+    return pol_act_rnn_call("hns_policy_act_rnn_agents", true, packed, rnn_packed, self_dim, num_envs, num_agents, num_cylinders, io, rio, stream);
 }
 
 }  // extern "C"

@@ -489,6 +489,7 @@ class RecurrentDeviceLearner(DeviceLearner):
         info row    hns_learner_info, INFO_KEYS, one copy to the host
 
     Refused: group= (data-parallel recurrent training is DataParallelRecurrentLearner's), the configurations RecurrentDevicePolicy refuses, a non-recurrent device_policy, a
+    per_agent device_policy or stacked actor tensors (recurrent per-agent actors are collected and evaluated, not yet trained: DESIGN.md §7.17), a
     rollout whose T train_seq_len does not divide (or whose storage was cut with another segment length)."""
 
     def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, generator=None, device_policy=None, agent_name="drone", group=None):
@@ -496,6 +497,10 @@ class RecurrentDeviceLearner(DeviceLearner):
             raise NotImplementedError("RecurrentDeviceLearner takes no group=: data-parallel recurrent training is DataParallelRecurrentLearner's")
         if device_policy is not None and not getattr(device_policy, "recurrent", False):
             raise P.PolicyConfigError("RecurrentDeviceLearner needs a RecurrentDevicePolicy (a non-recurrent policy is DeviceLearner's)")
+        if getattr(device_policy, "per_agent", False) or P.is_stacked(actor):
+            raise P.PolicyConfigError(f"{type(self).__name__} updates ONE shared recurrent actor: the update of recurrent per-agent actors (share_actor: "
+                                      "False with actor.rnn; PerAgentRecurrentDevicePolicy collects and evaluates them) is an open item "
+                                      "(DESIGN-open-items.md #13)")
         self._configure(actor, critic, cfg, tp_net, value_normalizer, agent_name, generator)
         self.train_seq_len = rnn_train.train_seq_len(cfg)
         if not 1 <= self.train_seq_len <= abi.HNS_GRU_MAX_STEPS:

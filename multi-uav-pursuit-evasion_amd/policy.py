@@ -23,7 +23,12 @@ configuration.
 `PerAgentDevicePolicy` is the `share_actor: False` configuration (one actor per agent: the stacked `actor_params`, every tensor [A, ...]; the
 critic shared) on `hns_policy_forward_agents` / `hns_policy_act_agents`: a tile is 32 envs of ONE agent and reads that agent's weight image,
 and agent a's rows are bit for bit `DevicePolicy`'s with slice a as the shared actor.  `DevicePolicy` keeps refusing
-stacked parameters."""
+stacked parameters.
+
+`PerAgentRecurrentDevicePolicy` is both at once — the configuration the reference's recurrent update is written for (mappo.py:281-284 vmaps
+over dim 0 of the stacked `actor_params`): one actor AND one actor GRU per agent, the critic and its GRU shared, on
+`hns_policy_forward_rnn_agents` / `hns_policy_act_rnn_agents` in §7.16's tile, the state rows where they were ([E, A, 128]); row (e, a) is bit
+for bit `RecurrentDevicePolicy`'s with agent a's slices.  Collection and evaluation only: its update is an open item."""
 import collections
 import ctypes as C
 import math
@@ -562,9 +567,8 @@ def torch_act_rnn(actor, actor_rnn, xs, xo, xc, state=None, is_init=None):
     return F.linear(ya, actor["head_w"], actor["head_b"]), ha
 
 
-def split_rnn(params, what):
-    """(the network's parameters without its GRU, the GRU's six tensors by hns_gru_net field) from reference names: the GRU sits under
-    `rnn.` (rnn.cell.weight_ih, ..., rnn.layer_norm.bias)."""
+def _split_rnn_names(params, what):
+    """(the parameters outside `rnn.`, the ones under it by their name behind `rnn.`), the latter held to the GRU block's six names."""
     from . import rnn as _rnn
     flat = {_strip(k): v for k, v in _flatten(params).items()}
     rest = {k: v for k, v in flat.items() if not k.startswith("rnn.")}
@@ -576,6 +580,14 @@ def split_rnn(params, what):
     if missing:
         raise PolicyConfigError(f"{what}: no GRU under 'rnn.' (missing {['rnn.' + k for k in missing]}); a network without an rnn is "
                                 "DevicePolicy's")
+    return rest, found
+
+
+def split_rnn(params, what):
+    """(the network's parameters without its GRU, the GRU's six tensors by hns_gru_net field) from reference names: the GRU sits under
+    `rnn.` (rnn.cell.weight_ih, ..., rnn.layer_norm.bias)."""
+    from . import rnn as _rnn
+    rest, found = _split_rnn_names(params, what)
     try:
         gru = _rnn.gru_parameters({_rnn.NAMES[k]: (v if v.is_contiguous() else v.detach().contiguous()) for k, v in found.items()})
     except ValueError as e:
@@ -590,17 +602,36 @@ class RecurrentDevicePolicy(DevicePolicy):
     an env-level `is_init` ([E] or [E, 1]; None: no env starts an episode); `out_states` may be the input tensors (in place).  `act_step` is
     the actor-only pass with the actor's state (evaluation); `act`, which has no state argument, keeps refusing."""
     recurrent = True
+    # the C entries of the recurrent pass (PerAgentRecurrentDevicePolicy: the *_agents ones)
+    _FORWARD_RNN, _ACT_RNN = "hns_policy_forward_rnn", "hns_policy_act_rnn"
 
     def __init__(self, actor_params, critic, cfg=None, device=None, seed=0, agent_name="drone"):
         check_config(cfg_without(cfg, "actor.rnn", "critic.rnn"))
         actor_rest, self.actor_rnn = split_rnn(actor_params, "actor")
         critic_rest, self.critic_rnn = split_rnn(critic, "critic")
         super().__init__(actor_rest, critic_rest, cfg=None, device=device, seed=seed, agent_name=agent_name)
+        self._setup_rnn()
+
+    def _setup_rnn(self):
+        """Behind `_setup`: the GRU tensors on the policy's device and their packed image."""
         if {v.device for v in (*self.actor_rnn.values(), *self.critic_rnn.values())} != {self.device}:
             self.actor_rnn = {k: v.detach().to(self.device).contiguous() for k, v in self.actor_rnn.items()}
             self.critic_rnn = {k: v.detach().to(self.device).contiguous() for k, v in self.critic_rnn.items()}
         if self.device.type == "cuda":
-            self.rnn_packed = torch.empty(self._lib.hns_policy_rnn_packed_bytes(), dtype=torch.uint8, device=self.device)
+            self.rnn_packed = torch.empty(self._rnn_packed_bytes(), dtype=torch.uint8, device=self.device)
+
+    def _rnn_packed_bytes(self):
+        return self._lib.hns_policy_rnn_packed_bytes()
+
+    def _rnn_pack(self, a, c, st):
+        """(return code, entry) of the GRU images' pack call."""
+        return self._lib.hns_policy_rnn_pack(C.byref(a), C.byref(c), self.rnn_packed.data_ptr(), st), "hns_policy_rnn_pack"
+
+    def _cpu_forward_rnn(self, *args):
+        return torch_forward_rnn(self.actor_p, self.critic_p, self.actor_rnn, self.critic_rnn, *args)
+
+    def _cpu_act_rnn(self, *args):
+        return torch_act_rnn(self.actor_p, self.actor_rnn, *args)
 
     def _tensors(self):
         return [*super()._tensors(), *self.actor_rnn.values(), *self.critic_rnn.values()]
@@ -620,8 +651,8 @@ class RecurrentDevicePolicy(DevicePolicy):
         a, c = self._gru_net(self.actor_rnn), self._gru_net(self.critic_rnn)
         with torch.cuda.device(self.device):
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            rc = self._lib.hns_policy_rnn_pack(C.byref(a), C.byref(c), self.rnn_packed.data_ptr(), st)
-        self._check(rc, "hns_policy_rnn_pack")
+            rc, entry = self._rnn_pack(a, c, st)
+        self._check(rc, entry)
         self._stamp = stamp
 
     def act(self, *args, **kwargs):
@@ -660,7 +691,7 @@ class RecurrentDevicePolicy(DevicePolicy):
         if self.device.type != "cuda":
             xs, xc, xo = xs.contiguous(), xc.contiguous(), (xo.contiguous() if xo is not None else None)      # as forward: the same bits
             with torch.no_grad():
-                action, new = torch_act_rnn(self.actor_p, self.actor_rnn, xs.unsqueeze(2), xo, xc, h, is_init)
+                action, new = self._cpu_act_rnn(xs.unsqueeze(2), xo, xc, h, is_init)
             return (action if out is None else out.copy_(action)), (new if oh is None else oh.copy_(new))
         self.refresh()
         xs, xo, xc, io = self._io(xs, xo, xc)
@@ -673,9 +704,9 @@ class RecurrentDevicePolicy(DevicePolicy):
         rio.is_init = is_init.data_ptr() if is_init is not None else None
         with torch.cuda.device(self.device):
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            rc = self._lib.hns_policy_act_rnn(self.packed.data_ptr(), self.rnn_packed.data_ptr(), self.self_dim, E, A, xc.shape[2], C.byref(io),
-                                              C.byref(rio), st)
-        self._check(rc, "hns_policy_act_rnn")
+            rc = getattr(self._lib, self._ACT_RNN)(self.packed.data_ptr(), self.rnn_packed.data_ptr(), self.self_dim, E, A, xc.shape[2], C.byref(io),
+                                                   C.byref(rio), st)
+        self._check(rc, self._ACT_RNN)
         return action, oh
 
     def forward(self, obs_self, obs_others, obs_cylinders, actor_state=None, critic_state=None, is_init=None, eps=None, deterministic=False,
@@ -696,8 +727,7 @@ class RecurrentDevicePolicy(DevicePolicy):
             # views of its storage must give the bits the collection gave
             xs, xc, xo = xs.contiguous(), xc.contiguous(), (xo.contiguous() if xo is not None else None)
             with torch.no_grad():
-                out = torch_forward_rnn(self.actor_p, self.critic_p, self.actor_rnn, self.critic_rnn, xs.unsqueeze(2), xo, xc, ha, hc, is_init, eps,
-                                        deterministic, value_only, self._generator)
+                out = self._cpu_forward_rnn(xs.unsqueeze(2), xo, xc, ha, hc, is_init, eps, deterministic, value_only, self._generator)
             new_a = out.actor_state if oa is None or value_only else oa.copy_(out.actor_state)
             new_c = out.critic_state if oc is None else oc.copy_(out.critic_state)
             return out._replace(actor_state=new_a, critic_state=new_c)
@@ -725,9 +755,9 @@ class RecurrentDevicePolicy(DevicePolicy):
         flags = (abi.HNS_POLICY_DETERMINISTIC if deterministic else 0) | (abi.HNS_POLICY_VALUE_ONLY if value_only else 0)
         with torch.cuda.device(dev):
             st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            rc = self._lib.hns_policy_forward_rnn(self.packed.data_ptr(), self.rnn_packed.data_ptr(), self.self_dim, E, A, xc.shape[2], C.byref(io),
-                                                  C.byref(rio), flags, self.seed, self.counter.data_ptr(), st)
-        self._check(rc, "hns_policy_forward_rnn")
+            rc = getattr(self._lib, self._FORWARD_RNN)(self.packed.data_ptr(), self.rnn_packed.data_ptr(), self.self_dim, E, A, xc.shape[2],
+                                                       C.byref(io), C.byref(rio), flags, self.seed, self.counter.data_ptr(), st)
+        self._check(rc, self._FORWARD_RNN)
         return RecurrentPolicyOutput(action, log_prob, value, loc, oa, oc)
 
     def _keys(self):
@@ -750,6 +780,129 @@ class RecurrentDevicePolicy(DevicePolicy):
         """value_op: the critic's state_value [E, A, 1] from the tensordict's observation, critic state and is_init; nothing is written back."""
         return self.forward(*self._obs(tensordict), critic_state=_td_get(tensordict, self._keys()[1]), is_init=_td_get(tensordict, "is_init"),
                             value_only=True).value
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# one RECURRENT actor per agent (share_actor: False with actor.rnn / critic.rnn): the stacked `actor_params` hold the actor's GRU too, so
+# every agent has an encoder, a GRU and a head of its own; the critic and the critic's GRU stay shared.  DESIGN.md §7.17
+def is_stacked(params, name="encoder.attn.in_proj_weight"):
+    """Whether `params` (any source `parse_parameters` reads) holds the stacked actor of share_actor: False: its in_proj_weight is [A, 384, 128]."""
+    if params is None:
+        return False
+    w = {_strip(k): v for k, v in _flatten(params).items()}.get(name)
+    return w is not None and w.dim() == 3
+
+
+def split_rnn_per_agent(params, what="actor"):
+    """`split_rnn` for the stacked actor: (the stacked parameters without the GRUs, the GRUs' six STACKED tensors by hns_gru_net field — every
+    one [A, ...], contiguous —, A).  Each agent's slice is held to `gru_parameters`' checks; rnn tensors that are not stacked, or whose
+    leading sizes disagree, raise PolicyConfigError."""
+    from . import rnn as _rnn
+    rest, found = _split_rnn_names(params, what)
+    if any(v.dim() != (3 if k.endswith("weight_ih") or k.endswith("weight_hh") else 2) for k, v in found.items()):
+        raise PolicyConfigError(f"{what}: the rnn tensors have no leading agent dimension (a shared recurrent actor is RecurrentDevicePolicy's)")
+    sizes = {int(v.shape[0]) for v in found.values()}
+    if len(sizes) != 1:
+        raise PolicyConfigError(f"{what}: every stacked rnn tensor needs the same leading agent dimension, not {sorted(sizes)}")
+    A = sizes.pop()
+    if not 1 <= A <= abi.HNS_MAX_AGENTS:
+        raise PolicyConfigError(f"{what}: {A} stacked GRUs outside [1, {abi.HNS_MAX_AGENTS}]")
+    gru = {_rnn.NAMES[k]: (v if v.is_contiguous() else v.detach().contiguous()) for k, v in found.items()}
+    for a in range(A):
+        try:
+            _rnn.gru_parameters({f: v[a] for f, v in gru.items()})
+        except ValueError as e:
+            raise PolicyConfigError(f"{what}: agent {a}'s rnn must be GRUCell(128, 128) + LayerNorm(128): {e}") from None
+    return rest, {f: gru[f] for f in _rnn.FIELDS}, A
+
+
+def torch_forward_rnn_per_agent(actors, critic, actor_rnns, critic_rnn, xs, xo, xc, actor_state=None, critic_state=None, is_init=None, eps=None,
+                                deterministic=False, value_only=False, generator=None):
+    """The CPU path of PerAgentRecurrentDevicePolicy: `torch_forward_rnn` with the stacked actor and the stacked actor GRU — a loop over the
+    agents' slices, as `torch_forward_per_agent`.  Each slice runs on the WHOLE observation and state and keeps its own agent's rows, so
+    agent a's rows (the state's too) are exactly `torch_forward_rnn`'s with slice a as the shared actor."""
+    yc, hc = _rnn_step(critic, critic_rnn, xs, xo, xc, critic_state, is_init)
+    value = F.linear(yc, critic["head_w"], critic["head_b"])
+    if value_only:
+        return RecurrentPolicyOutput(None, None, value, None, None, hc)
+    E, A = xs.shape[:2]
+    if eps is None and not deterministic:
+        eps = torch.randn((E, A, ACTION_DIM), dtype=xs.dtype, device=xs.device, generator=generator)
+    rows = []
+    for a in range(A):
+        p = agent_slice(actors, a)
+        ya, ha = _rnn_step(p, agent_slice(actor_rnns, a), xs, xo, xc, actor_state, is_init)
+        rows.append([t[:, a:a + 1] for t in (*_heads(p, ya, value, eps, deterministic, generator), ha)])
+    action, log_prob, _, loc, ha = (torch.cat(t, dim=1) for t in zip(*rows))
+    return RecurrentPolicyOutput(action, log_prob, value, loc, ha, hc)
+
+
+def torch_act_rnn_per_agent(actors, actor_rnns, xs, xo, xc, state=None, is_init=None):
+    """The CPU restatement of hns_policy_act_rnn_agents: the actor half of `torch_forward_rnn_per_agent` alone -> (loc [E, A, 4], the actors'
+    states after the step [E, A, 128]); the same statements on the same operands, so the same bits as its deterministic action and state."""
+    rows = []
+    for a in range(xs.shape[1]):
+        p = agent_slice(actors, a)
+        ya, ha = _rnn_step(p, agent_slice(actor_rnns, a), xs, xo, xc, state, is_init)
+        rows.append((F.linear(ya, p["head_w"], p["head_b"])[:, a:a + 1], ha[:, a:a + 1]))
+    return tuple(torch.cat(t, dim=1) for t in zip(*rows))
+
+
+class PerAgentRecurrentDevicePolicy(RecurrentDevicePolicy):
+    """MAPPOPolicy with share_actor: False AND actor.rnn / critic.rnn — one actor and one actor GRU per pursuer, the critic and its GRU
+    shared — in one HIP launch per call (`hns_policy_forward_rnn_agents`; `act_step`: `hns_policy_act_rnn_agents`).
+
+    `PerAgentRecurrentDevicePolicy(actor_params, critic)`: actor_params the STACKED actor with its `rnn.*` leaves stacked too (every leaf
+    [A, ...], as the reference's `actor_params` of this configuration), critic as for RecurrentDevicePolicy.  `from_checkpoint`, `refresh`,
+    `forward`, `act_step`, `__call__` and `value` are RecurrentDevicePolicy's over the agents' entries: a tile is 32 envs of one agent and
+    reads that agent's two images, the states stay [E, A, 128], and row (e, a) is bit for bit RecurrentDevicePolicy's with agent a's slices
+    as the shared actor.  `scale` is [A, 4].  Refused with PolicyConfigError before anything is built: whatever RecurrentDevicePolicy
+    refuses except share_actor: False; share_actor: True; tensors that are not stacked or whose leading sizes disagree; an rnn on only one
+    of the two networks; a critic with stacked tensors; an observation with another number of agents (ValueError).  It is not trained on
+    the device yet: every learner refuses it (DESIGN-open-items.md #13)."""
+    per_agent = True
+    _PACK, _FORWARD, _ACT = PerAgentDevicePolicy._PACK, PerAgentDevicePolicy._FORWARD, PerAgentDevicePolicy._ACT
+    _FORWARD_RNN, _ACT_RNN = "hns_policy_forward_rnn_agents", "hns_policy_act_rnn_agents"
+
+    def __init__(self, actor_params, critic, cfg=None, device=None, seed=0, agent_name="drone"):
+        check_config_per_agent(cfg_without(cfg, "actor.rnn", "critic.rnn"))
+        if is_stacked(critic, "base.attn.in_proj_weight"):
+            raise PolicyConfigError("critic: parameters with a leading agent dimension; the reference stacks the actor only")
+        actor_rest, self.actor_rnn, rnn_agents = split_rnn_per_agent(actor_params, "actor")
+        critic_rest, self.critic_rnn = split_rnn(critic, "critic")
+        actor_p, self.num_agents = parse_parameters_per_agent(actor_rest, "actor")
+        if rnn_agents != self.num_agents:
+            raise PolicyConfigError(f"actor: {self.num_agents} stacked actors with {rnn_agents} stacked GRUs")
+        self._setup(actor_p, parse_parameters(critic_rest, CRITIC_NAMES, "critic"), device, seed, agent_name)
+        self._setup_rnn()
+
+    _packed_bytes, _pack_agents, scale = PerAgentDevicePolicy._packed_bytes, PerAgentDevicePolicy._pack_agents, PerAgentDevicePolicy.scale
+
+    def _rnn_packed_bytes(self):
+        return self._lib.hns_policy_rnn_packed_agents_bytes(self.num_agents)
+
+    def _rnn_pack(self, a, c, st):
+        return (self._lib.hns_policy_rnn_pack_agents(C.byref(a), C.byref(c), self.num_agents, self.rnn_packed.data_ptr(), st),
+                "hns_policy_rnn_pack_agents")
+
+    def _cpu_forward_rnn(self, *args):
+        return torch_forward_rnn_per_agent(self.actor_p, self.critic_p, self.actor_rnn, self.critic_rnn, *args)
+
+    def _cpu_act_rnn(self, *args):
+        return torch_act_rnn_per_agent(self.actor_p, self.actor_rnn, *args)
+
+    def _validate(self, xs, xo, xc):
+        xs, xo, xc = super()._validate(xs, xo, xc)
+        if xs.shape[1] != self.num_agents:
+            raise ValueError(f"the observation has {xs.shape[1]} agents, the policy {self.num_agents} actors")
+        return xs, xo, xc
+
+
+def random_rnn_parameters_per_agent(num_agents, seed=0):
+    """`random_rnn_parameters` for share_actor: False: `num_agents` independently initialised GRU blocks, every tensor [A, ...], under the
+    reference's names with the `rnn.` prefix: merge it into `random_parameters_per_agent`'s stacked actor."""
+    nets = [random_rnn_parameters(seed + 1000 * a) for a in range(num_agents)]
+    return {k: torch.stack([n[k] for n in nets]).contiguous() for k in nets[0]}
 
 
 def _td_get(td, key):
