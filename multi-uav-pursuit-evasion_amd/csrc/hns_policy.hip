@@ -15,29 +15,37 @@
 // matrices' fragment order — are hns_encoder.h's, which hns_policy_train.hip uses too.  Here: the packed image's vector sections, the head,
 // sampling, the log-probability, the entry points.
 //
-//   hns_policy_pack_kernel    : parameter tensors (PyTorch layouts) -> the packed image: the six matrices in MFMA A-operand fragment order (one
-//                               float4 per lane per four k-steps), the vectors, the head, the embedding weights transposed.
-//   hns_policy_forward_kernel : one workgroup of four waves per kEncRows rows.  Activations live in LDS as [128 features][kEncRows rows]; wave w
-//                               owns output row blocks 2w, 2w + 1 of every product, so each weight element is read once per workgroup.  The
-//                               embedding starts its fma chain from the bias (enc_token<true>; the updates add it last: DESIGN §7.3).
-//   hns_policy_act_kernel     : the same tile, LDS and launch bounds for ONE encoder pass, the actor's: action = loc and nothing else (evaluation
-//                               reads neither the value nor the log-probability).  Bit for bit the forward's deterministic action.
-//   hns_policy_forward_rnn_kernel : the recurrent configuration (actor.rnn / critic.rnn: a GRU behind each encoder) in the same tile,
-//                               LDS and launch bounds: per network the encoder, then ONE GRU step on the features it left in registers (six more
-//                               128 x 128 products from a second packed image, the gates in the products' accumulator layout), LayerNorm(h + f),
-//                               the head.  The state comes from and goes to HBM once per network; the features never do.
-//   hns_policy_act_rnn_kernel : the recurrent forward's actor half alone (encoder, GRU step on the actor's GRU image, LayerNorm, fc_mean): action =
-//                               loc and the actor's new state, nothing else (recurrent evaluation).  Bit for bit the recurrent
-//                               forward's deterministic action and actor state.
-//   hns_policy_rnn_pack_kernel: the two GRUs' tensors -> their packed image.
-//   hns_policy_bump_kernel    : the device call counter += 1 after a sampling call (Philox counter; a captured graph draws fresh noise per replay).
-//   hns_policy_pack_agents_kernel, hns_policy_forward_agents_kernel, hns_policy_act_agents_kernel : one actor per agent (share_actor: false;
-//                               DESIGN §7.16): A actor images and the critic's; a workgroup's rows are 32 envs of ONE agent (blockIdx.y), its actor pass
-//                               reads that agent's image; the same per-row functions, so row (e, a) has the shared kernels' bits with agent a's image.
-//   hns_policy_rnn_pack_agents_kernel, hns_policy_forward_rnn_agents_kernel, hns_policy_act_rnn_agents_kernel : one RECURRENT actor per agent
-//                               (DESIGN §7.17): A actor GRU images and the critic's beside the A + 1 encoder images, the same agent-major tile;
-//                               the state rows keep their place e A + a in [E, A, 128] (pol_gru_step<true>), so row (e, a) has the shared
-//                               recurrent kernels' bits with agent a's two images.
+// The tile (pol_tile): one workgroup of four waves per kEncRows rows.  Activations live in LDS as [128 features][kEncRows rows]; wave w owns
+// output row blocks 2w, 2w + 1 of every product, so each weight element is read once per workgroup.  The embedding starts its fma chain from the
+// bias (enc_token<true>; the updates add it last: DESIGN §7.3).  Per network: pol_encoder, [one GRU step], the head.  Eight kernels are that ONE
+// body under three compile-time flags — the same tile, LDS (PolLds, taken dynamically) and launch bounds, the same per-row device functions in
+// the same order, so what two of them both compute has the same bits:
+//   AGENTS : one actor per agent (share_actor: false).  The image holds A actor images, then the critic's; a workgroup's
+//            rows are 32 consecutive envs of ONE agent (blockIdx.y) and its actor pass reads that agent's image(s).  A row keeps its number
+//            e A + a (outputs, eps, the Philox counter, the state rows: pol_gru_step<true>), so row (e, a) has the shared kernel's bits with
+//            agent a's image(s) as the actor.  Without the flag rows are tiled as they lie and the image is [actor, critic].
+//   RNN    : the recurrent configuration (actor.rnn / critic.rnn: a GRU behind each encoder).  ONE GRU step on the features the
+//            encoder left in registers (six more 128 x 128 products from a second packed image, the gates in the products' accumulator
+//            layout), LayerNorm(h + f), then the head.  The state comes from and goes to HBM once per network; the features never do.
+//   ACT    : the actor's pass alone, action = loc (and the actor's new state) and nothing else read or written: evaluation reads neither the
+//            value nor the log-probability.  Bit for bit the forward's deterministic action (and actor state).
+//
+//   kernel                                  AGENTS  RNN  ACT
+//   hns_policy_forward_kernel                  -     -    -
+//   hns_policy_act_kernel                      -     -    x
+//   hns_policy_forward_rnn_kernel              -     x    -
+//   hns_policy_act_rnn_kernel                  -     x    x
+//   hns_policy_forward_agents_kernel           x     -    -
+//   hns_policy_act_agents_kernel               x     -    x
+//   hns_policy_forward_rnn_agents_kernel       x     x    -
+//   hns_policy_act_rnn_agents_kernel           x     x    x
+//
+//   hns_policy_pack_agents_kernel     : parameter tensors (PyTorch layouts) -> packed images, one per blockIdx.y: the six matrices in MFMA A-operand
+//                                       fragment order (one float4 per lane per four k-steps), the vectors, the head, the embedding weights
+//                                       transposed.  The shared image [actor, critic] is the per-agent image [A actors, critic] at one actor.
+//   hns_policy_rnn_pack_agents_kernel : the GRUs' tensors -> their packed images, the same way.
+//   hns_policy_bump_kernel            : the device call counter += 1 after a sampling call (Philox counter; a captured graph draws fresh noise
+//                                       per replay).
 // Determinism: fixed reduction orders (butterflies over the eight lanes of a row), no atomics.
 #include <hip/hip_runtime.h>
 
@@ -104,14 +112,18 @@ HNS_DEV float pol_src(const EncNet &s, int D, long long i) {
     return s.ew[2][f * 5 + (in - D - 3)];
 }
 
-__global__ __launch_bounds__(256) void hns_policy_pack_kernel(const EncNet actor, const EncNet critic, int D, float *img) {
+struct PolNets {
+    EncNet n[HNS_MAX_AGENTS + 1];            // the actor — with one actor per agent the agents' slices of the stacked actor (formed on the host) — then the critic
+};
+
+__global__ __launch_bounds__(256) void hns_policy_pack_agents_kernel(const PolNets nets, int D, float *img) {
     const long long n = pol_net_floats(D);
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < 2 * n; i += (long long)gridDim.x * 256)
-        img[i] = i < n ? pol_src(actor, D, i) : pol_src(critic, D, i - n);
+    float *dst = img + blockIdx.y * n;                           // image blockIdx.y: the actors', then the critic's
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) dst[i] = pol_src(nets.n[blockIdx.y], D, i);
 }
 
 struct PolArgs {
-    const float *img;                        // actor image, critic image at + net_floats
+    const float *img;                        // the actor image(s), then the critic's, net_floats each
     long long net_floats;
     const float *xs, *xo, *xc;               // obs_self [E, A, D], obs_others [E, A, A - 1, 3], obs_cylinders [E, A, K, 5]
     long long sse, ssa, soe, soa, sot, sce, sca, sct;
@@ -243,47 +255,6 @@ HNS_DEV void pol_sample(const PolArgs &a, const float *net, const float (&loc)[4
     }
 }
 
-__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_kernel(const PolArgs a) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
-    const long long row = (long long)blockIdx.x * kEncRows + r;
-    const bool live = row < a.rows;
-    float y[16];
-
-    if (!a.value_only) {
-        const float *net = a.img;
-        pol_encoder(a, net, L, w, lane, r, g, row, y);
-        float loc[4];
-#pragma unroll
-        for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
-        pol_sample(a, net, loc, row, live, g);
-        __syncthreads();                                          // the critic reuses the LDS
-    }
-    const float *net = a.img + a.net_floats;
-    pol_encoder(a, net, L, w, lane, r, g, row, y);
-    const float v = pol_head(net, 0, y, g);
-    if (live && g == 0) a.value[row] = v;
-}
-
-// the actor alone, the mode of the distribution (evaluation): the forward kernel's first encoder pass and head, nothing else read or written
-__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_kernel(const PolArgs a) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
-    const long long row = (long long)blockIdx.x * kEncRows + r;
-    const float *net = a.img;
-    float y[16];
-    pol_encoder(a, net, L, w, lane, r, g, row, y);
-    float loc[4];
-#pragma unroll
-    for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
-    if (row < a.rows && g == 0) {
-#pragma unroll
-        for (int o = 0; o < 4; ++o) a.action[row * 4 + o] = loc[o];
-    }
-}
-
 // ---- the recurrent configuration: one GRU step between the encoder and the head (include/hns.h: hns_policy_forward_rnn)
 // packed GRU image of one network, in floats: the six gate matrices in the encoder matrices' fragment order, then the vectors
 enum : int {
@@ -316,13 +287,17 @@ HNS_DEV float pol_rnn_src(const GruSrc &s, int i) {
     }
 }
 
-__global__ __launch_bounds__(256) void hns_policy_rnn_pack_kernel(const GruSrc actor, const GruSrc critic, float *img) {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < 2 * R_NET; i += gridDim.x * 256)
-        img[i] = i < R_NET ? pol_rnn_src(actor, i) : pol_rnn_src(critic, i - R_NET);
+struct GruSrcs {
+    GruSrc n[HNS_MAX_AGENTS + 1];            // the actor's GRU — with one actor per agent the agents' slices of the stacked GRU (formed on the host) — then the critic's
+};
+
+__global__ __launch_bounds__(256) void hns_policy_rnn_pack_agents_kernel(const GruSrcs nets, float *img) {
+    float *dst = img + (long long)blockIdx.y * R_NET;            // image blockIdx.y: the actors' GRUs, then the critic's
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < R_NET; i += gridDim.x * 256) dst[i] = pol_rnn_src(nets.n[blockIdx.y], i);
 }
 
 struct PolRnnArgs {
-    const float *img;                        // actor GRU image, the critic's at + R_NET
+    const float *img;                        // the actor GRU image(s), then the critic's, R_NET floats each
     const float *h_in[2];                    // actor, critic: [rows, 128] or NULL (zeros)
     float *h_out[2];
     const unsigned char *is_init;            // [E] or NULL
@@ -369,7 +344,7 @@ HNS_DEV void pol_gate_prod(const float *__restrict__ W, const float *in, int w, 
 // the number of envs; tile position p is live iff row0 + p < rows, its state row is (row0 + p) A + agent — A 512 bytes apart instead of
 // contiguous, on the load (position r) and on the accumulator-layout store (position rr) alike — and its flag is_init[row0 + p].  The
 // arithmetic is the same statements; the shared form (AGENTS false) compiles to what it was.
-template <bool AGENTS = false>
+template <bool AGENTS>
 HNS_DEV void pol_gru_step(const float *rn, const float *h_in, float *h_out, const unsigned char *is_init, int A, long long row0, long long rows,
                           PolLds &L, int w, int lane, int r, int g, float (&y)[16]) {
     float h[16];
@@ -453,170 +428,70 @@ HNS_DEV void pol_gru_step(const float *rn, const float *h_in, float *h_out, cons
     enc_layernorm(u, rn + R_LNW, rn + R_LNB, g, xh, y);           // y = LayerNorm(h' + f)
 }
 
-__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_rnn_kernel(const PolArgs a, const PolRnnArgs ra) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
-    const long long row0 = (long long)blockIdx.x * kEncRows, row = row0 + r;
-    const bool live = row < a.rows;
-    float y[16];
-
-    if (!a.value_only) {
-        const float *net = a.img;
-        pol_encoder(a, net, L, w, lane, r, g, row, y);
-        pol_gru_step(ra.img, ra.h_in[0], ra.h_out[0], ra.is_init, a.A, row0, a.rows, L, w, lane, r, g, y);
-        float loc[4];
-#pragma unroll
-        for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
-        pol_sample(a, net, loc, row, live, g);
-        __syncthreads();                                          // the critic reuses the LDS
-    }
-    const float *net = a.img + a.net_floats;
-    pol_encoder(a, net, L, w, lane, r, g, row, y);
-    pol_gru_step(ra.img + R_NET, ra.h_in[1], ra.h_out[1], ra.is_init, a.A, row0, a.rows, L, w, lane, r, g, y);
-    const float v = pol_head(net, 0, y, g);
-    if (live && g == 0) a.value[row] = v;
-}
-
-// the recurrent actor alone, the mode of the distribution (evaluation): the recurrent forward kernel's first encoder pass, GRU step and head
-// on the actor's two images; the actor's state in and out, the action, nothing else read or written
-__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_rnn_kernel(const PolArgs a, const PolRnnArgs ra) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
-    const long long row0 = (long long)blockIdx.x * kEncRows, row = row0 + r;
-    const float *net = a.img;
-    float y[16];
-    pol_encoder(a, net, L, w, lane, r, g, row, y);
-    pol_gru_step(ra.img, ra.h_in[0], ra.h_out[0], ra.is_init, a.A, row0, a.rows, L, w, lane, r, g, y);
-    float loc[4];
-#pragma unroll
-    for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
-    if (row < a.rows && g == 0) {
-#pragma unroll
-        for (int o = 0; o < 4; ++o) a.action[row * 4 + o] = loc[o];
-    }
-}
-
-__global__ void hns_policy_bump_kernel(unsigned long long *counter) { counter[0] += 1ull; }
-
-// ---- one actor per agent (share_actor: false; include/hns.h: hns_policy_forward_agents)
-// The image holds A actor images, then the critic's.  A workgroup's rows are 32 consecutive envs of ONE agent (blockIdx.y), so its six products
-// read one weight image as before; the row keeps its number env * A + agent (outputs, eps, the Philox counter) and its arithmetic is
-// pol_encoder / pol_head / pol_sample untouched: row (e, a) has the bits the shared kernels give it with agent a's image as the actor.
-struct PolNets {
-    EncNet n[HNS_MAX_AGENTS + 1];            // the agents' slices of the stacked actor (formed on the host), then the critic
-};
-
-__global__ __launch_bounds__(256) void hns_policy_pack_agents_kernel(const PolNets nets, int D, float *img) {
-    const long long n = pol_net_floats(D);
-    float *dst = img + blockIdx.y * n;                           // image blockIdx.y: 0 .. A - 1 the agents' actors, A the critic
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) dst[i] = pol_src(nets.n[blockIdx.y], D, i);
-}
-
-// the row of thread row r of the workgroup: env (tile, r) of agent blockIdx.y; past the last env a row that is not live
+// the row of thread row r of an agent-major workgroup: env (tile, r) of agent blockIdx.y; past the last env a row that is not live
 HNS_DEV long long pol_agent_row(const PolArgs &a, int r) {
     const long long e = (long long)blockIdx.x * kEncRows + r;
     return e * a.A < a.rows ? e * a.A + blockIdx.y : a.rows;
 }
 
-__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_agents_kernel(const PolArgs a) {
+// ---- the tile: the body of all eight kernels (the flags: the head of this file; include/hns.h: hns_policy_forward and its seven siblings)
+// AGENTS: the images hold A actor images / A actor-GRU images, then the critic's one of each; the actor pass reads
+// agent blockIdx.y's, the critic pass the shared ones.  The row keeps its number env * A + agent and its arithmetic is pol_encoder /
+// pol_gru_step / pol_head / pol_sample untouched: row (e, a) has the bits the shared kernels give it with agent a's images as the actor.
+template <bool AGENTS, bool RNN, bool ACT>
+HNS_DEV void pol_tile(const PolArgs &a, const PolRnnArgs &ra) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
-    const long long row = pol_agent_row(a, r);
+    // what pol_gru_step tiles: rows as they lie, or the envs of one agent (its state-row addressing note)
+    const long long row0 = (long long)blockIdx.x * kEncRows, rows0 = AGENTS ? a.rows / a.A : a.rows;
+    long long row;
+    if constexpr (AGENTS) row = pol_agent_row(a, r);
+    else row = row0 + r;
+    // their places in both images (long long straight from the unsigned blockIdx.y: through an int it is sign-extended, three instructions more)
+    const long long actor = AGENTS ? blockIdx.y : 0, critic = AGENTS ? a.A : 1;
     const bool live = row < a.rows;
     float y[16];
 
-    if (!a.value_only) {
-        const float *net = a.img + (long long)blockIdx.y * a.net_floats;      // the agent's actor, formed once per tile
+    bool actor_pass = true;
+    if constexpr (!ACT) actor_pass = !a.value_only;
+    if (actor_pass) {
+        const float *net = a.img + actor * a.net_floats;          // the agent's actor (and its GRU), formed once per tile
         pol_encoder(a, net, L, w, lane, r, g, row, y);
+        if constexpr (RNN) pol_gru_step<AGENTS>(ra.img + actor * R_NET, ra.h_in[0], ra.h_out[0], ra.is_init, a.A, row0, rows0, L, w, lane, r, g, y);
         float loc[4];
 #pragma unroll
         for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
-        pol_sample(a, net, loc, row, live, g);
-        __syncthreads();                                          // the critic reuses the LDS
-    }
-    const float *net = a.img + (long long)a.A * a.net_floats;    // the shared critic, behind the A actors
-    pol_encoder(a, net, L, w, lane, r, g, row, y);
-    const float v = pol_head(net, 0, y, g);
-    if (live && g == 0) a.value[row] = v;
-}
-
-__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_agents_kernel(const PolArgs a) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
-    const long long row = pol_agent_row(a, r);
-    const float *net = a.img + (long long)blockIdx.y * a.net_floats;
-    float y[16];
-    pol_encoder(a, net, L, w, lane, r, g, row, y);
-    float loc[4];
+        if constexpr (ACT) {                                      // the mode of the distribution (evaluation), nothing else read or written
+            if (live && g == 0) {
 #pragma unroll
-    for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
-    if (row < a.rows && g == 0) {
-#pragma unroll
-        for (int o = 0; o < 4; ++o) a.action[row * 4 + o] = loc[o];
+                for (int o = 0; o < 4; ++o) a.action[row * 4 + o] = loc[o];
+            }
+        } else {
+            pol_sample(a, net, loc, row, live, g);
+            __syncthreads();                                      // the critic reuses the LDS
+        }
     }
-}
-
-// ---- one recurrent actor per agent (share_actor: false with actor.rnn / critic.rnn; include/hns.h: hns_policy_forward_rnn_agents)
-// The two images hold A actor images / A actor-GRU images, then the critic's one of each.  The tile is §7.16's (32 envs of agent blockIdx.y); the
-// actor pass reads the agent's two images, the critic pass the shared two; the state rows keep their place e A + a in [E, A, 128]
-// (pol_gru_step<true>).  Row (e, a) has the bits hns_policy_forward_rnn gives it on the images of (agent a's slices, critic).
-struct GruSrcs {
-    GruSrc n[HNS_MAX_AGENTS + 1];            // the agents' slices of the stacked actor GRU (formed on the host), then the critic's GRU
-};
-
-__global__ __launch_bounds__(256) void hns_policy_rnn_pack_agents_kernel(const GruSrcs nets, float *img) {
-    float *dst = img + (long long)blockIdx.y * R_NET;            // image blockIdx.y: 0 .. A - 1 the agents' actor GRUs, A the critic's
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < R_NET; i += gridDim.x * 256) dst[i] = pol_rnn_src(nets.n[blockIdx.y], i);
-}
-
-__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_rnn_agents_kernel(const PolArgs a, const PolRnnArgs ra) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
-    const long long env0 = (long long)blockIdx.x * kEncRows, envs = a.rows / a.A;
-    const long long row = pol_agent_row(a, r);
-    const bool live = row < a.rows;
-    float y[16];
-
-    if (!a.value_only) {
-        const float *net = a.img + (long long)blockIdx.y * a.net_floats;      // the agent's actor and its GRU, formed once per tile
+    if constexpr (!ACT) {
+        const float *net = a.img + critic * a.net_floats;         // the (shared) critic and its GRU, behind the actors'
         pol_encoder(a, net, L, w, lane, r, g, row, y);
-        pol_gru_step<true>(ra.img + (long long)blockIdx.y * R_NET, ra.h_in[0], ra.h_out[0], ra.is_init, a.A, env0, envs, L, w, lane, r, g, y);
-        float loc[4];
-#pragma unroll
-        for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
-        pol_sample(a, net, loc, row, live, g);
-        __syncthreads();                                          // the critic reuses the LDS
+        if constexpr (RNN) pol_gru_step<AGENTS>(ra.img + critic * R_NET, ra.h_in[1], ra.h_out[1], ra.is_init, a.A, row0, rows0, L, w, lane, r, g, y);
+        const float v = pol_head(net, 0, y, g);
+        if (live && g == 0) a.value[row] = v;
     }
-    const float *net = a.img + (long long)a.A * a.net_floats;    // the shared critic and its GRU, behind the A actors'
-    pol_encoder(a, net, L, w, lane, r, g, row, y);
-    pol_gru_step<true>(ra.img + (long long)a.A * R_NET, ra.h_in[1], ra.h_out[1], ra.is_init, a.A, env0, envs, L, w, lane, r, g, y);
-    const float v = pol_head(net, 0, y, g);
-    if (live && g == 0) a.value[row] = v;
 }
 
-__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_rnn_agents_kernel(const PolArgs a, const PolRnnArgs ra) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
-    const long long env0 = (long long)blockIdx.x * kEncRows, envs = a.rows / a.A;
-    const long long row = pol_agent_row(a, r);
-    const float *net = a.img + (long long)blockIdx.y * a.net_floats;
-    float y[16];
-    pol_encoder(a, net, L, w, lane, r, g, row, y);
-    pol_gru_step<true>(ra.img + (long long)blockIdx.y * R_NET, ra.h_in[0], ra.h_out[0], ra.is_init, a.A, env0, envs, L, w, lane, r, g, y);
-    float loc[4];
-#pragma unroll
-    for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
-    if (row < a.rows && g == 0) {
-#pragma unroll
-        for (int o = 0; o < 4; ++o) a.action[row * 4 + o] = loc[o];
-    }
-}
+// the kernels' names are the records' (profiles/, rocprofv3 output): one per set of flags, <AGENTS, RNN, ACT>
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_kernel(const PolArgs a) { pol_tile<false, false, false>(a, PolRnnArgs{}); }
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_kernel(const PolArgs a) { pol_tile<false, false, true>(a, PolRnnArgs{}); }
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_rnn_kernel(const PolArgs a, const PolRnnArgs ra) { pol_tile<false, true, false>(a, ra); }
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_rnn_kernel(const PolArgs a, const PolRnnArgs ra) { pol_tile<false, true, true>(a, ra); }
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_agents_kernel(const PolArgs a) { pol_tile<true, false, false>(a, PolRnnArgs{}); }
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_agents_kernel(const PolArgs a) { pol_tile<true, false, true>(a, PolRnnArgs{}); }
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_rnn_agents_kernel(const PolArgs a, const PolRnnArgs ra) { pol_tile<true, true, false>(a, ra); }
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_rnn_agents_kernel(const PolArgs a, const PolRnnArgs ra) { pol_tile<true, true, true>(a, ra); }
+
+__global__ void hns_policy_bump_kernel(unsigned long long *counter) { counter[0] += 1ull; }
 
 }  // namespace hns
 
@@ -673,20 +548,6 @@ int pol_check_outputs(const char *fn, const hns_policy_io *io, bool value_only, 
     return HNS_OK;
 }
 
-// the image, the observation and the shape; `action` the only output (the forward adds its own)
-hns::PolArgs pol_args(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io) {
-    hns::PolArgs a{};
-    a.img = static_cast<const float *>(packed);
-    a.net_floats = hns::pol_net_floats(self_dim);
-    a.xs = io->obs_self; a.xo = io->obs_others; a.xc = io->obs_cylinders;
-    a.sse = io->self_stride[0]; a.ssa = io->self_stride[1];
-    a.soe = io->others_stride[0]; a.soa = io->others_stride[1]; a.sot = io->others_stride[2];
-    a.sce = io->cyl_stride[0]; a.sca = io->cyl_stride[1]; a.sct = io->cyl_stride[2];
-    a.action = io->action;
-    a.rows = num_envs * num_agents; a.A = num_agents; a.K = num_cylinders; a.D = self_dim;
-    return a;
-}
-
 int pol_gru_net(const char *fn, const hns_gru_net *n, hns::GruSrc &s) {
     if (!n) return hns_fail(fn, "null GRU network");
     const float *p[6] = {n->weight_ih, n->weight_hh, n->bias_ih, n->bias_hh, n->ln_w, n->ln_b};
@@ -696,17 +557,9 @@ int pol_gru_net(const char *fn, const hns_gru_net *n, hns::GruSrc &s) {
     return HNS_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t hns_policy_packed_bytes(int32_t self_dim) {
-    if (self_dim < 1 || self_dim > hns::kPolMaxSelf) return 0;
-    return (size_t)(2 * hns::pol_net_floats(self_dim)) * sizeof(float);
-}
-
-int hns_policy_pack(const hns_policy_net *actor, const hns_policy_net *critic, int32_t self_dim, int32_t num_agents, void *packed, void *stream) {
-    const char *fn = "hns_policy_pack";
+// hns_policy_pack and hns_policy_pack_agents: `actors` images of the (stacked) actor's slices — one: the tensors themselves — then the critic's
+int pol_pack_call(const char *fn, const hns_policy_net *actor, const hns_policy_net *critic, int32_t self_dim, int32_t num_agents, bool per_agent,
+                  void *packed, void *stream) {
     if (self_dim < 1 || self_dim > hns::kPolMaxSelf) return hns_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kPolMaxSelf) + "]");
     if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return hns_fail(fn, "num_agents must be in [1, 7]");
     if (!packed || !hns_aligned(packed, 16)) return hns_fail(fn, "packed image must be a 16-byte aligned device array");
@@ -715,265 +568,181 @@ int hns_policy_pack(const hns_policy_net *actor, const hns_policy_net *critic, i
     if (rc != HNS_OK) return rc;
     rc = pol_net(fn, critic, num_agents > 1, false, sc);
     if (rc != HNS_OK) return rc;
-    hipLaunchKernelGGL(hns::hns_policy_pack_kernel, dim3(512), dim3(256), 0, static_cast<hipStream_t>(stream), sa, sc, (int)self_dim,
-                       static_cast<float *>(packed));
-    HNS_CHECK_HIP(hipGetLastError());
-    return HNS_OK;
-}
-
-// hns_policy_forward and hns_policy_forward_agents: the same refusals in the same order, the same arguments; `agents` picks the kernel and its grid
-static int pol_forward_call(const char *fn, bool agents, const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
-                            const hns_policy_io *io, int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
-    int rc = pol_check_shape(fn, packed, self_dim, num_envs, num_agents, num_cylinders, io);
-    if (rc != HNS_OK) return rc;
-    if (flags & ~(HNS_POLICY_DETERMINISTIC | HNS_POLICY_VALUE_ONLY)) return hns_fail(fn, "unknown flag");
-    const bool value_only = flags & HNS_POLICY_VALUE_ONLY, det = flags & HNS_POLICY_DETERMINISTIC;
-    rc = pol_check_obs(fn, num_agents, io);
-    if (rc != HNS_OK) return rc;
-    rc = pol_check_outputs(fn, io, value_only, det, counter);
-    if (rc != HNS_OK) return rc;
-    hns::PolArgs a = pol_args(packed, self_dim, num_envs, num_agents, num_cylinders, io);
-    a.eps = io->eps; a.counter = reinterpret_cast<const unsigned long long *>(counter); a.seed = seed;
-    a.loc = io->loc; a.logp = io->log_prob; a.value = io->value;
-    a.deterministic = det; a.value_only = value_only;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_forward_kernel),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));   // 72 KB: above the default cap
-    static const hipError_t attr_ag = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_forward_agents_kernel),
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
-    HNS_CHECK_HIP(attr);
-    HNS_CHECK_HIP(attr_ag);
-    if (agents) {                                                 // a tile: 32 consecutive envs of one agent
-        const long long tiles = (num_envs + hns::kEncRows - 1) / hns::kEncRows;
-        hipLaunchKernelGGL(hns::hns_policy_forward_agents_kernel, dim3((unsigned)tiles, (unsigned)num_agents), dim3(hns::kEncThreads), sizeof(hns::PolLds), st, a);
-    } else {
-        const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
-        hipLaunchKernelGGL(hns::hns_policy_forward_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), st, a);
-    }
-    HNS_CHECK_HIP(hipGetLastError());
-    if (!value_only && !det && !io->eps) {
-        hipLaunchKernelGGL(hns::hns_policy_bump_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<unsigned long long *>(counter));
-        HNS_CHECK_HIP(hipGetLastError());
-    }
-    return HNS_OK;
-}
-
-int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
-                       int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
-    return pol_forward_call("hns_policy_forward", false, packed, self_dim, num_envs, num_agents, num_cylinders, io, flags, seed, counter, stream);
-}
-
-size_t hns_policy_packed_agents_bytes(int32_t self_dim, int32_t num_agents) {
-    if (self_dim < 1 || self_dim > hns::kPolMaxSelf || num_agents < 1 || num_agents > HNS_MAX_AGENTS) return 0;
-    return (size_t)((num_agents + 1) * hns::pol_net_floats(self_dim)) * sizeof(float);
-}
-
-int hns_policy_pack_agents(const hns_policy_net *actors, const hns_policy_net *critic, int32_t self_dim, int32_t num_agents, void *packed, void *stream) {
-    const char *fn = "hns_policy_pack_agents";
-    if (self_dim < 1 || self_dim > hns::kPolMaxSelf) return hns_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kPolMaxSelf) + "]");
-    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return hns_fail(fn, "num_agents must be in [1, 7]");
-    if (!packed || !hns_aligned(packed, 16)) return hns_fail(fn, "packed image must be a 16-byte aligned device array");
-    hns::EncNet sa{}, sc{};
-    int rc = pol_net(fn, actors, num_agents > 1, true, sa);
-    if (rc != HNS_OK) return rc;
-    rc = pol_net(fn, critic, num_agents > 1, false, sc);
-    if (rc != HNS_OK) return rc;
+    const int actors = per_agent ? num_agents : 1;
     hns::PolNets nets{};
-    for (int ag = 0; ag < num_agents; ++ag) nets.n[ag] = hns::enc_agent_slice(sa, self_dim, 4, ag);
-    nets.n[num_agents] = sc;
-    hipLaunchKernelGGL(hns::hns_policy_pack_agents_kernel, dim3(256, (unsigned)num_agents + 1), dim3(256), 0, static_cast<hipStream_t>(stream), nets,
+    for (int ag = 0; ag < actors; ++ag) nets.n[ag] = hns::enc_agent_slice(sa, self_dim, 4, ag);
+    nets.n[actors] = sc;
+    hipLaunchKernelGGL(hns::hns_policy_pack_agents_kernel, dim3(256, (unsigned)actors + 1), dim3(256), 0, static_cast<hipStream_t>(stream), nets,
                        (int)self_dim, static_cast<float *>(packed));
     HNS_CHECK_HIP(hipGetLastError());
     return HNS_OK;
 }
 
-int hns_policy_forward_agents(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
-                              int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
-    return pol_forward_call("hns_policy_forward_agents", true, packed, self_dim, num_envs, num_agents, num_cylinders, io, flags, seed, counter, stream);
-}
-
-size_t hns_policy_rnn_packed_bytes(void) { return (size_t)(2 * hns::R_NET) * sizeof(float); }
-
-int hns_policy_rnn_pack(const hns_gru_net *actor_rnn, const hns_gru_net *critic_rnn, void *rnn_packed, void *stream) {
-    const char *fn = "hns_policy_rnn_pack";
+// hns_policy_rnn_pack and hns_policy_rnn_pack_agents, the same way
+int pol_rnn_pack_call(const char *fn, const hns_gru_net *actor_rnn, const hns_gru_net *critic_rnn, int actors, void *rnn_packed, void *stream) {
     if (!rnn_packed || !hns_aligned(rnn_packed, 16)) return hns_fail(fn, "packed image must be a 16-byte aligned device array");
     hns::GruSrc sa{}, sc{};
     int rc = pol_gru_net(fn, actor_rnn, sa);
     if (rc != HNS_OK) return rc;
     rc = pol_gru_net(fn, critic_rnn, sc);
     if (rc != HNS_OK) return rc;
-    hipLaunchKernelGGL(hns::hns_policy_rnn_pack_kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream), sa, sc, static_cast<float *>(rnn_packed));
+    hns::GruSrcs nets{};
+    constexpr long long E = hns::kEncE;
+    for (int ag = 0; ag < actors; ++ag)                           // agent ag's slice of the stacked tensors: [A, 384, 128] x2, [A, 384] x2, [A, 128] x2
+        nets.n[ag] = hns::GruSrc{sa.w_ih + ag * 3 * E * E, sa.w_hh + ag * 3 * E * E, sa.b_ih + ag * 3 * E, sa.b_hh + ag * 3 * E, sa.ln_w + ag * E,
+                                 sa.ln_b + ag * E};
+    nets.n[actors] = sc;
+    hipLaunchKernelGGL(hns::hns_policy_rnn_pack_agents_kernel, dim3(128, (unsigned)actors + 1), dim3(256), 0, static_cast<hipStream_t>(stream), nets,
+                       static_cast<float *>(rnn_packed));
     HNS_CHECK_HIP(hipGetLastError());
     return HNS_OK;
 }
 
-// hns_policy_forward_rnn and hns_policy_forward_rnn_agents: the same refusals in the same order, the same arguments; `agents` picks the kernel and its grid
-static int pol_forward_rnn_call(const char *fn, bool agents, const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs,
-                                int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io, const hns_policy_rnn_io *rio, int32_t flags,
-                                uint64_t seed, uint64_t *counter, void *stream) {
+// the tile kernels by 4 agents + 2 recurrent + actor-only (the table at the head of this file)
+#define K(name) reinterpret_cast<const void *>(&hns::name)
+const void *const kPolKernels[8] = {K(hns_policy_forward_kernel),        K(hns_policy_act_kernel),        K(hns_policy_forward_rnn_kernel),
+                                    K(hns_policy_act_rnn_kernel),        K(hns_policy_forward_agents_kernel), K(hns_policy_act_agents_kernel),
+                                    K(hns_policy_forward_rnn_agents_kernel), K(hns_policy_act_rnn_agents_kernel)};
+#undef K
+
+// All eight entries: the same refusals in the same order, one set of arguments, one launch.  `agents` picks the agent-major tile and its grid,
+// `rnn` adds the GRU image and the states, `act` is the actor's pass alone (flags 0, no counter): its eps, counter, loc, log_prob, value and
+// critic states stay NULL and are never touched, as the actor's states are under HNS_POLICY_VALUE_ONLY.
+int pol_call(const char *fn, bool agents, bool rnn, bool act, const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs,
+             int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io, const hns_policy_rnn_io *rio, int32_t flags, uint64_t seed,
+             uint64_t *counter, void *stream) {
     int rc = pol_check_shape(fn, packed, self_dim, num_envs, num_agents, num_cylinders, io);
     if (rc != HNS_OK) return rc;
-    if (!rnn_packed || !rio || !hns_aligned(rnn_packed, 16) || !hns_aligned(rio, 8)) return hns_fail(fn, "null or misaligned packed GRU image / rnn io");
+    if (rnn && (!rnn_packed || !rio || !hns_aligned(rnn_packed, 16) || !hns_aligned(rio, 8))) return hns_fail(fn, "null or misaligned packed GRU image / rnn io");
     if (flags & ~(HNS_POLICY_DETERMINISTIC | HNS_POLICY_VALUE_ONLY)) return hns_fail(fn, "unknown flag");
     const bool value_only = flags & HNS_POLICY_VALUE_ONLY, det = flags & HNS_POLICY_DETERMINISTIC;
     rc = pol_check_obs(fn, num_agents, io);
     if (rc != HNS_OK) return rc;
-    rc = pol_check_outputs(fn, io, value_only, det, counter);
-    if (rc != HNS_OK) return rc;
-    if (!rio->critic_h_out || !hns_aligned(rio->critic_h_out, 16) || (!value_only && (!rio->actor_h_out || !hns_aligned(rio->actor_h_out, 16))))
-        return hns_fail(fn, "state output missing or not 16-byte aligned");
-    if (!hns_aligned(rio->critic_h_in, 16) || (!value_only && !hns_aligned(rio->actor_h_in, 16))) return hns_fail(fn, "state input not 16-byte aligned");
-    hns::PolArgs a = pol_args(packed, self_dim, num_envs, num_agents, num_cylinders, io);
-    a.eps = io->eps; a.counter = reinterpret_cast<const unsigned long long *>(counter); a.seed = seed;
-    a.loc = io->loc; a.logp = io->log_prob; a.value = io->value;
-    a.deterministic = det; a.value_only = value_only;
-    hns::PolRnnArgs ra{};
-    ra.img = static_cast<const float *>(rnn_packed);
-    ra.h_in[0] = value_only ? nullptr : rio->actor_h_in; ra.h_in[1] = rio->critic_h_in;
-    ra.h_out[0] = value_only ? nullptr : rio->actor_h_out; ra.h_out[1] = rio->critic_h_out;
-    ra.is_init = rio->is_init;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_forward_rnn_kernel),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
-    static const hipError_t attr_ag = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_forward_rnn_agents_kernel),
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
-    HNS_CHECK_HIP(attr);
-    HNS_CHECK_HIP(attr_ag);
-    if (agents) {                                                 // a tile: 32 consecutive envs of one agent
-        const long long tiles = (num_envs + hns::kEncRows - 1) / hns::kEncRows;
-        hipLaunchKernelGGL(hns::hns_policy_forward_rnn_agents_kernel, dim3((unsigned)tiles, (unsigned)num_agents), dim3(hns::kEncThreads), sizeof(hns::PolLds), st,
-                           a, ra);
+    if (act) {
+        if (!io->action || !hns_aligned(io->action, 4)) return hns_fail(fn, "action output missing or misaligned");
     } else {
-        const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
-        hipLaunchKernelGGL(hns::hns_policy_forward_rnn_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), st, a, ra);
+        rc = pol_check_outputs(fn, io, value_only, det, counter);
+        if (rc != HNS_OK) return rc;
     }
-    HNS_CHECK_HIP(hipGetLastError());
-    if (!value_only && !det && !io->eps) {
+    hns::PolRnnArgs ra{};
+    if (rnn) {
+        const bool actor_h = !value_only, critic_h = !act;       // the states the call touches
+        if ((critic_h && (!rio->critic_h_out || !hns_aligned(rio->critic_h_out, 16))) || (actor_h && (!rio->actor_h_out || !hns_aligned(rio->actor_h_out, 16))))
+            return hns_fail(fn, "state output missing or not 16-byte aligned");
+        if ((critic_h && !hns_aligned(rio->critic_h_in, 16)) || (actor_h && !hns_aligned(rio->actor_h_in, 16))) return hns_fail(fn, "state input not 16-byte aligned");
+        ra.img = static_cast<const float *>(rnn_packed);
+        if (actor_h) { ra.h_in[0] = rio->actor_h_in; ra.h_out[0] = rio->actor_h_out; }
+        if (critic_h) { ra.h_in[1] = rio->critic_h_in; ra.h_out[1] = rio->critic_h_out; }
+        ra.is_init = rio->is_init;
+    }
+    hns::PolArgs a{};
+    a.img = static_cast<const float *>(packed);
+    a.net_floats = hns::pol_net_floats(self_dim);
+    a.xs = io->obs_self; a.xo = io->obs_others; a.xc = io->obs_cylinders;
+    a.sse = io->self_stride[0]; a.ssa = io->self_stride[1];
+    a.soe = io->others_stride[0]; a.soa = io->others_stride[1]; a.sot = io->others_stride[2];
+    a.sce = io->cyl_stride[0]; a.sca = io->cyl_stride[1]; a.sct = io->cyl_stride[2];
+    a.action = io->action;
+    a.rows = num_envs * num_agents; a.A = num_agents; a.K = num_cylinders; a.D = self_dim;
+    if (!act) {
+        a.eps = io->eps; a.counter = reinterpret_cast<const unsigned long long *>(counter); a.seed = seed;
+        a.loc = io->loc; a.logp = io->log_prob; a.value = io->value;
+        a.deterministic = det; a.value_only = value_only;
+    }
+    static const hipError_t attr = [] {                           // 72 KB of dynamic LDS: above the default cap
+        hipError_t e = hipSuccess;
+        for (const void *k : kPolKernels)
+            if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
+        return e;
+    }();
+    HNS_CHECK_HIP(attr);
+    // a tile: kEncRows rows as they lie, or (agents) kEncRows consecutive envs of one agent, blockIdx.y
+    const long long tiles = ((agents ? num_envs : a.rows) + hns::kEncRows - 1) / hns::kEncRows;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    void *args[] = {&a, &ra};                                     // the kernels without a GRU take `a` alone
+    HNS_CHECK_HIP(hipLaunchKernel(kPolKernels[4 * agents + 2 * rnn + act], dim3((unsigned)tiles, agents ? (unsigned)num_agents : 1u), dim3(hns::kEncThreads), args,
+                                  sizeof(hns::PolLds), st));
+    if (!act && !value_only && !det && !io->eps) {
         hipLaunchKernelGGL(hns::hns_policy_bump_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<unsigned long long *>(counter));
         HNS_CHECK_HIP(hipGetLastError());
     }
     return HNS_OK;
 }
 
-int hns_policy_forward_rnn(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
-                           const hns_policy_io *io, const hns_policy_rnn_io *rio, int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
-    return pol_forward_rnn_call("hns_policy_forward_rnn", false, packed, rnn_packed, self_dim, num_envs, num_agents, num_cylinders, io, rio, flags, seed,
-                                counter, stream);
+}  // namespace
+
+extern "C" {
+
+size_t hns_policy_packed_agents_bytes(int32_t self_dim, int32_t num_agents) {
+    if (self_dim < 1 || self_dim > hns::kPolMaxSelf || num_agents < 1 || num_agents > HNS_MAX_AGENTS) return 0;
+    return (size_t)((num_agents + 1) * hns::pol_net_floats(self_dim)) * sizeof(float);
 }
+
+size_t hns_policy_packed_bytes(int32_t self_dim) { return hns_policy_packed_agents_bytes(self_dim, 1); }
 
 size_t hns_policy_rnn_packed_agents_bytes(int32_t num_agents) {
     if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return 0;
     return (size_t)((num_agents + 1) * hns::R_NET) * sizeof(float);
 }
 
+size_t hns_policy_rnn_packed_bytes(void) { return hns_policy_rnn_packed_agents_bytes(1); }
+
+int hns_policy_pack(const hns_policy_net *actor, const hns_policy_net *critic, int32_t self_dim, int32_t num_agents, void *packed, void *stream) {
+    return pol_pack_call("hns_policy_pack", actor, critic, self_dim, num_agents, false, packed, stream);
+}
+
+int hns_policy_pack_agents(const hns_policy_net *actors, const hns_policy_net *critic, int32_t self_dim, int32_t num_agents, void *packed, void *stream) {
+    return pol_pack_call("hns_policy_pack_agents", actors, critic, self_dim, num_agents, true, packed, stream);
+}
+
+int hns_policy_rnn_pack(const hns_gru_net *actor_rnn, const hns_gru_net *critic_rnn, void *rnn_packed, void *stream) {
+    return pol_rnn_pack_call("hns_policy_rnn_pack", actor_rnn, critic_rnn, 1, rnn_packed, stream);
+}
+
 int hns_policy_rnn_pack_agents(const hns_gru_net *actor_rnns, const hns_gru_net *critic_rnn, int32_t num_agents, void *rnn_packed, void *stream) {
-    const char *fn = "hns_policy_rnn_pack_agents";
-    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return hns_fail(fn, "num_agents must be in [1, 7]");
-    if (!rnn_packed || !hns_aligned(rnn_packed, 16)) return hns_fail(fn, "packed image must be a 16-byte aligned device array");
-    hns::GruSrc sa{}, sc{};
-    int rc = pol_gru_net(fn, actor_rnns, sa);
-    if (rc != HNS_OK) return rc;
-    rc = pol_gru_net(fn, critic_rnn, sc);
-    if (rc != HNS_OK) return rc;
-    hns::GruSrcs nets{};
-    constexpr long long E = hns::kEncE;
-    for (int ag = 0; ag < num_agents; ++ag)                       // agent ag's slice of the stacked tensors: [A, 384, 128] x2, [A, 384] x2, [A, 128] x2
-        nets.n[ag] = hns::GruSrc{sa.w_ih + ag * 3 * E * E, sa.w_hh + ag * 3 * E * E, sa.b_ih + ag * 3 * E, sa.b_hh + ag * 3 * E, sa.ln_w + ag * E,
-                                 sa.ln_b + ag * E};
-    nets.n[num_agents] = sc;
-    hipLaunchKernelGGL(hns::hns_policy_rnn_pack_agents_kernel, dim3(128, (unsigned)num_agents + 1), dim3(256), 0, static_cast<hipStream_t>(stream), nets,
-                       static_cast<float *>(rnn_packed));
-    HNS_CHECK_HIP(hipGetLastError());
-    return HNS_OK;
+    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return hns_fail("hns_policy_rnn_pack_agents", "num_agents must be in [1, 7]");
+    return pol_rnn_pack_call("hns_policy_rnn_pack_agents", actor_rnns, critic_rnn, num_agents, rnn_packed, stream);
+}
+
+int hns_policy_forward(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
+                       int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
+    return pol_call("hns_policy_forward", false, false, false, packed, nullptr, self_dim, num_envs, num_agents, num_cylinders, io, nullptr, flags, seed, counter, stream);
+}
+
+int hns_policy_forward_agents(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
+                              int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
+    return pol_call("hns_policy_forward_agents", true, false, false, packed, nullptr, self_dim, num_envs, num_agents, num_cylinders, io, nullptr, flags, seed, counter, stream);
+}
+
+int hns_policy_forward_rnn(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                           const hns_policy_io *io, const hns_policy_rnn_io *rio, int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
+    return pol_call("hns_policy_forward_rnn", false, true, false, packed, rnn_packed, self_dim, num_envs, num_agents, num_cylinders, io, rio, flags, seed, counter, stream);
 }
 
 int hns_policy_forward_rnn_agents(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents,
                                   int32_t num_cylinders, const hns_policy_io *io, const hns_policy_rnn_io *rio, int32_t flags, uint64_t seed,
                                   uint64_t *counter, void *stream) {
-    return pol_forward_rnn_call("hns_policy_forward_rnn_agents", true, packed, rnn_packed, self_dim, num_envs, num_agents, num_cylinders, io, rio, flags,
-                                seed, counter, stream);
-}
-
-// hns_policy_act and hns_policy_act_agents over one body, as the forward's two
-static int pol_act_call(const char *fn, bool agents, const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
-                        const hns_policy_io *io, void *stream) {
-    int rc = pol_check_shape(fn, packed, self_dim, num_envs, num_agents, num_cylinders, io);
-    if (rc != HNS_OK) return rc;
-    rc = pol_check_obs(fn, num_agents, io);
-    if (rc != HNS_OK) return rc;
-    if (!io->action || !hns_aligned(io->action, 4)) return hns_fail(fn, "action output missing or misaligned");
-    const hns::PolArgs a = pol_args(packed, self_dim, num_envs, num_agents, num_cylinders, io);   // eps, counter, loc, log_prob, value stay NULL: never touched
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_act_kernel),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
-    static const hipError_t attr_ag = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_act_agents_kernel),
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
-    HNS_CHECK_HIP(attr);
-    HNS_CHECK_HIP(attr_ag);
-    if (agents) {
-        const long long tiles = (num_envs + hns::kEncRows - 1) / hns::kEncRows;
-        hipLaunchKernelGGL(hns::hns_policy_act_agents_kernel, dim3((unsigned)tiles, (unsigned)num_agents), dim3(hns::kEncThreads), sizeof(hns::PolLds),
-                           static_cast<hipStream_t>(stream), a);
-    } else {
-        const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
-        hipLaunchKernelGGL(hns::hns_policy_act_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), static_cast<hipStream_t>(stream), a);
-    }
-    HNS_CHECK_HIP(hipGetLastError());
-    return HNS_OK;
+    return pol_call("hns_policy_forward_rnn_agents", true, true, false, packed, rnn_packed, self_dim, num_envs, num_agents, num_cylinders, io, rio, flags, seed, counter, stream);
 }
 
 int hns_policy_act(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
                    void *stream) {
-    return pol_act_call("hns_policy_act", false, packed, self_dim, num_envs, num_agents, num_cylinders, io, stream);
+    return pol_call("hns_policy_act", false, false, true, packed, nullptr, self_dim, num_envs, num_agents, num_cylinders, io, nullptr, 0, 0, nullptr, stream);
 }
 
 int hns_policy_act_agents(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
                           void *stream) {
-    return pol_act_call("hns_policy_act_agents", true, packed, self_dim, num_envs, num_agents, num_cylinders, io, stream);
-}
-
-// hns_policy_act_rnn and hns_policy_act_rnn_agents over one body, as the forward's two
-static int pol_act_rnn_call(const char *fn, bool agents, const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents,
-                            int32_t num_cylinders, const hns_policy_io *io, const hns_policy_rnn_io *rio, void *stream) {
-    int rc = pol_check_shape(fn, packed, self_dim, num_envs, num_agents, num_cylinders, io);
-    if (rc != HNS_OK) return rc;
-    if (!rnn_packed || !rio || !hns_aligned(rnn_packed, 16) || !hns_aligned(rio, 8)) return hns_fail(fn, "null or misaligned packed GRU image / rnn io");
-    rc = pol_check_obs(fn, num_agents, io);
-    if (rc != HNS_OK) return rc;
-    if (!io->action || !hns_aligned(io->action, 4)) return hns_fail(fn, "action output missing or misaligned");
-    if (!rio->actor_h_out || !hns_aligned(rio->actor_h_out, 16)) return hns_fail(fn, "state output missing or not 16-byte aligned");
-    if (!hns_aligned(rio->actor_h_in, 16)) return hns_fail(fn, "state input not 16-byte aligned");
-    const hns::PolArgs a = pol_args(packed, self_dim, num_envs, num_agents, num_cylinders, io);   // eps, counter, loc, log_prob, value stay NULL: never touched
-    hns::PolRnnArgs ra{};                                         // the critic's h_in / h_out stay NULL: never touched
-    ra.img = static_cast<const float *>(rnn_packed);
-    ra.h_in[0] = rio->actor_h_in; ra.h_out[0] = rio->actor_h_out;
-    ra.is_init = rio->is_init;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_act_rnn_kernel),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
-    static const hipError_t attr_ag = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_act_rnn_agents_kernel),
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
-    HNS_CHECK_HIP(attr);
-    HNS_CHECK_HIP(attr_ag);
-    if (agents) {
-        const long long tiles = (num_envs + hns::kEncRows - 1) / hns::kEncRows;
-        hipLaunchKernelGGL(hns::hns_policy_act_rnn_agents_kernel, dim3((unsigned)tiles, (unsigned)num_agents), dim3(hns::kEncThreads), sizeof(hns::PolLds),
-                           static_cast<hipStream_t>(stream), a, ra);
-    } else {
-        const long long grid = (a.rows + hns::kEncRows - 1) / hns::kEncRows;
-        hipLaunchKernelGGL(hns::hns_policy_act_rnn_kernel, dim3((unsigned)grid), dim3(hns::kEncThreads), sizeof(hns::PolLds), static_cast<hipStream_t>(stream),
-                           a, ra);
-    }
-    HNS_CHECK_HIP(hipGetLastError());
-    return HNS_OK;
+    return pol_call("hns_policy_act_agents", true, false, true, packed, nullptr, self_dim, num_envs, num_agents, num_cylinders, io, nullptr, 0, 0, nullptr, stream);
 }
 
 int hns_policy_act_rnn(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
                        const hns_policy_io *io, const hns_policy_rnn_io *rio, void *stream) {
-    return pol_act_rnn_call("hns_policy_act_rnn", false, packed, rnn_packed, self_dim, num_envs, num_agents, num_cylinders, io, rio, stream);
+    return pol_call("hns_policy_act_rnn", false, true, true, packed, rnn_packed, self_dim, num_envs, num_agents, num_cylinders, io, rio, 0, 0, nullptr, stream);
 }
 
 int hns_policy_act_rnn_agents(const void *packed, const void *rnn_packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
                               const hns_policy_io *io, const hns_policy_rnn_io *rio, void *stream) {
-    return pol_act_rnn_call("hns_policy_act_rnn_agents", true, packed, rnn_packed, self_dim, num_envs, num_agents, num_cylinders, io, rio, stream);
+    return pol_call("hns_policy_act_rnn_agents", true, true, true, packed, rnn_packed, self_dim, num_envs, num_agents, num_cylinders, io, rio, 0, 0, nullptr, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Every output bit of the encoder's three users on a fixed list of cases, for a before / after comparison of a change that must not move any:
-hns_policy_forward (policy.DevicePolicy), the critic's update (critic_train.value_loss_and_grad) and the actor's (actor_train.policy_loss_and_grad).
+hns_policy_forward (policy.DevicePolicy), the critic's update (critic_train.value_loss_and_grad) and the actor's (actor_train.policy_loss_and_grad);
+and of the four policy classes through all eight policy entries, with their packed images (policy_section).
 
     python tools/encoder_bits.py OUT.npz                 # on an MI355X: runs every case, writes every output array
     python tools/encoder_bits.py --compare A.npz B.npz   # anywhere: the first array that differs (np.array_equal on the uint32 views); exit 1 if any
@@ -17,6 +18,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 TAGS = ("a3k5d35", "a3k8d20", "a1k5d20", "a6k16d24")
 TRAIN_LIMITS = [(1, 5, 20, 40), (7, 5, 20, 9), (3, 1, 20, 33), (3, 16, 20, 33), (3, 5, 1, 33), (3, 5, 96, 33), (3, 5, 35, 1), (3, 5, 35, 11)]   # (A, K, D, batch): the tests' list
+# (E, A, K) of the policy section: no state_others and one live row; 33 rows (the shared grid's second tile has one live row, the agent-major
+# tile is partial); agent-major: two tiles per agent, the second with one live env; both maxima
+POLICY_SHAPES = [(1, 1, 1), (11, 3, 5), (33, 3, 2), (5, 7, 16)]
 
 
 def compare(a, b):
@@ -36,6 +40,58 @@ def compare(a, b):
         return 1
     print(f"all {len(za.files)} arrays are bit-identical ({sum(za[k].size for k in za.files)} values)")
     return 0
+
+
+def policy_section(put, torch, P, device="cuda"):
+    """Every output array of the four policy classes through all their entries (hns_policy_forward / _act and their _rnn, _agents and
+    _rnn_agents forms) and the packed images themselves.  policy.py and abi.py decide nothing about the bits, so HNS_LIBRARY=<another
+    build> python tools/encoder_bits.py OUT.npz is the other arm in the same tree.  No NaN goes in: operand order may move a NaN's payload."""
+    dev, D = torch.device(device), 35                            # (on "cpu" the classes run their restatements: a rehearsal of this loop)
+    put_out = lambda tag, o: [put(f"{tag}:{n}", getattr(o, n)) for n in o._fields if getattr(o, n) is not None]      # noqa: E731
+    for E, A, K in POLICY_SHAPES:
+        g = torch.Generator().manual_seed(9000 + 100 * E + 10 * A + K)
+        r = lambda *s: torch.randn(*s, generator=g).to(dev)                                                         # noqa: E731
+        xs, xo, xc, eps = r(E, A, D), (r(E, A, A - 1, 3) if A > 1 else None), r(E, A, K, 5), r(E, A, 4)
+        h0 = (r(E, A, 128), r(E, A, 128))
+        mixed = (torch.arange(E) % 2 == 0).to(dev)
+        on = lambda d: {k: v.to(dev) for k, v in d.items()}                                                         # noqa: E731
+        sa, sc = P.random_parameters(D, A, 3)
+        pa, pc = P.random_parameters_per_agent(D, A, 4)
+        ra, rc = {**sa, **P.random_rnn_parameters(5)}, {**sc, **P.random_rnn_parameters(6)}
+        qa, qc = {**pa, **P.random_rnn_parameters_per_agent(A, 7)}, {**pc, **P.random_rnn_parameters(8)}
+        seed = 2 ** 40 + 12345
+        modes = {"eps": dict(eps=eps), "philox": {}, "det": dict(deterministic=True), "vo": dict(value_only=True)}
+        for cls, (a, c) in {"DevicePolicy": (sa, sc), "PerAgentDevicePolicy": (pa, pc)}.items():
+            pol, tag = getattr(P, cls)(on(a), on(c), seed=seed), f"pol:{cls}:e{E}a{A}k{K}"
+            if dev.type == "cuda":
+                pol.refresh()
+                put(f"{tag}:packed", pol.packed.view(torch.float32))
+            for mode, kw in modes.items():
+                pol.counter.fill_(7)
+                put_out(f"{tag}:{mode}", pol.forward(xs, xo, xc, **kw))
+                put(f"{tag}:{mode}:counter", pol.counter)
+            put(f"{tag}:act", pol.act(xs, xo, xc))
+        for cls, (a, c) in {"RecurrentDevicePolicy": (ra, rc), "PerAgentRecurrentDevicePolicy": (qa, qc)}.items():
+            pol, tag = getattr(P, cls)(on(a), on(c), seed=seed), f"pol:{cls}:e{E}a{A}k{K}"
+            if dev.type == "cuda":
+                pol.refresh()
+                put(f"{tag}:packed", pol.packed.view(torch.float32))
+                put(f"{tag}:rnn_packed", pol.rnn_packed.view(torch.float32))
+            for st in ("absent", "given", "inplace"):
+                for fl, is_init in (("noflags", None), ("mixed", mixed)):
+                    t = f"{tag}:{st}:{fl}"
+                    for mode, kw in modes.items():
+                        ha, hc = (None, None) if st == "absent" else (h0[0].clone(), h0[1].clone())
+                        pol.counter.fill_(7)
+                        o = pol.forward(xs, xo, xc, actor_state=ha, critic_state=hc, is_init=is_init, out_states=(ha, hc) if st == "inplace" else None, **kw)
+                        put_out(f"{t}:{mode}", o)
+                        put(f"{t}:{mode}:counter", pol.counter)
+                        if st == "inplace":                       # what value_only must leave alone included
+                            put(f"{t}:{mode}:actor_buffer", ha)
+                    h = None if st == "absent" else h0[0].clone()
+                    action, new = pol.act_step(xs, xo, xc, state=h, is_init=is_init, out_state=h if st == "inplace" else None)
+                    put(f"{t}:act_step:action", action)
+                    put(f"{t}:act_step:state", new)
 
 
 def dump(path):
@@ -84,6 +140,7 @@ def dump(path):
     actor, critic = R.random_net(35, 3, 61)
     obs, _ = R.random_obs(5, 3, 5, 35, 62)                     # 15 rows: a partial tile
     forward_case("philox", actor, critic, obs, None, seed=2 ** 40 + 12345, counter=7)
+    policy_section(put, torch, P)
 
     # ---- the updates: every scalar, values / log_probs, every parameter's .grad
     def critic_case(tag, critic, obs, bv, ret, index, shape=None, **kw):
