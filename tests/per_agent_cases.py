@@ -87,6 +87,77 @@ def hand_train_op(state, opts, ro, gen, cfg=CFG, use_tp=True):
     return info
 
 
+# ---------------------------------------------------------------------------------------------------------------- the padded plan
+# csrc/hns_policy_train.hip restated: kCtRows, kCtMaxSplits, kCtE, kCtMat, kCtGemmOut, kActLossSlots (1 + 3 HNS_MAX_AGENTS), I_EW, O_EWS, kActDim
+ROWS, MAX_SPLITS, E, ACT = 32, 48, 128, 4
+MAT, LOSS_SLOTS, I_EW, O_EWS = E * E, 1 + 3 * 7, 12 * E * E, 1280 + 3 * E + 5 * E + 4
+GEMM_OUT = MAT + E
+
+
+def agents_plan(B, A):
+    """ct_plan_agents for B minibatch positions of each of A agents: (tiles per agent, tiles per row range of the weight-gradient kernel,
+    row ranges per agent, padding tiles per agent, tiles in all)."""
+    tpa = -(-B // ROWS)
+    spa = max(1, MAX_SPLITS // A)
+    tps = -(-tpa // spa)
+    spa = -(-tpa // tps)
+    return tpa, tps, spa, spa * tps - tpa, A * spa * tps
+
+
+def agents_workspace_bytes(B, D, A, K):
+    """hns_actor_train_agents_workspace_bytes(B A, D, A, K): ct_plan_agents' sum of 256-byte aligned arrays — the control floats, the tiles' loss
+    partials (fp64), the agents' per-block sums (fp64), the A packed images, two partial rows per tile, six weight-gradient partials per row
+    range, twelve staged operand arrays of 32 rows per tile."""
+    up = lambda v: (v + 255) & ~255                                                 # noqa: E731
+    _, _, spa, _, tiles = agents_plan(B, A)
+    P = O_EWS + D * E + (ACT - 1) * E + ACT                                         # ct_partial_floats(D, kActDim)
+    img = I_EW + (D + 8) * E                                                        # ct_img_floats(D)
+    gblocks, tblocks = (6 * GEMM_OUT + 31) // 32, (P + 31) // 32
+    return (up(64 * 4) + up(tiles * LOSS_SLOTS * 8) + up(A * (gblocks + tblocks) * 8) + up(A * img * 4) + up(tiles * 2 * P * 4) +
+            up(A * spa * 6 * GEMM_OUT * 4) + up(12 * tiles * ROWS * E * 4))
+
+
+# (A, K, D, S, B) -> (tpa, tps, spa, padding tiles per agent, tiles): the smallest shapes that reach each mechanism of the padded plan.  B None:
+# no index, the rollout's S env-steps read in place
+EDGE_PLANS = {
+    (7, 16, 24, 200, 192): (6, 1, 6, 0, 42),       # the last B at tps = 1 for A = 7
+    (7, 16, 24, 200, 193): (7, 2, 4, 1, 56),       # first tps = 2; a one-row last live tile next to a padding tile in one range
+    (7, 16, 24, 260, 256): (8, 2, 4, 0, 56),       # tps = 2, exact fit
+    (7, 16, 24, 400, 385): (13, 3, 5, 2, 105),     # tps = 3, two padding tiles in the last range, the loss merge's second trip (105 > 64)
+    (5, 8, 20, 330, 321): (11, 2, 6, 1, 60),       # an A whose 48 / A is not exact
+    (3, 5, 35, 520, 513): (17, 2, 9, 1, 54),       # the default shape's A, K, D
+    (2, 8, 20, 780, 769): (25, 2, 13, 1, 52),
+    (1, 5, 20, 1540, 1537): (49, 2, 25, 1, 50),    # A = 1, no state_others
+    (3, 5, 35, 513, None): (17, 2, 9, 1, 54),      # no index
+}
+EDGE_CASES = list(EDGE_PLANS)
+EXACT_FIT = [(7, 16, 24, 200, 192), (7, 16, 24, 260, 256)]
+# The seed of a case is test_hip_per_agent._case's 500 + A + S, but for the four cases whose seed leaves some agent's ONE-row last live tile a
+# clipped row (w = 0: zero gradient, so a kernel that dropped the tile would show nothing; agents 1 and 4 at (7; 193), agent 0 at (7; 385),
+# agent 1 at (2; 769), the agent of (1; 1537)): there the first seed 500 + A + S + 1000 k, k = 1, 2, .., that is off the clip, has w equal in
+# fp64 and fp32 and gives every agent's last live tile a row with w = 1 and a non-zero advantage.  k (below) was found from the log-probabilities
+# of the fp64 / fp32 references alone, before anything ran on a device; tests/test_per_agent_edges.py re-asserts all three for every case
+EDGE_SEEDS = {(7, 16, 24, 200, 193): 500 + 7 + 200 + 1000 * 6, (7, 16, 24, 400, 385): 500 + 7 + 400 + 1000 * 13,
+              (2, 8, 20, 780, 769): 500 + 2 + 780 + 1000 * 1, (1, 5, 20, 1540, 1537): 500 + 1 + 1540 + 1000 * 1}
+
+
+def edge_tag(case):
+    A, K, D, S, B = case
+    return f"a{A}k{K}d{D}-s{S}b{B if B else 'all'}"
+
+
+def edge_positions(case):
+    """The positions per agent of a case's minibatch."""
+    return case[4] if case[4] else case[3]
+
+
+def edge_case(case):
+    """(actors, obs, action, log_probs_old, advantages, index) of test_hip_per_agent._case at the case's seed."""
+    import test_hip_per_agent as THP                             # (its data builders; importing it starts nothing on a device)
+    A, K, D, S, B = case
+    return THP._case(S, A, K, D, EDGE_SEEDS.get(case, 500 + A + S), B=B)
+
+
 def check_info(info, hand, use_tp=True):
     """The learner's info row against the hand-driven one: the same floats (the column means are one fp64 sum rounded once on both sides)."""
     keys = [k for k in learner.INFO_KEYS if k != "action_norm" and (use_tp or k != "TP_loss")]
