@@ -81,6 +81,9 @@ def _net(p, grads=None):
 def _seq(x4, h0, init):
     s = abi.HnsGruSeq()
     B, A, L, _ = x4.shape
+    for t, what, n in ((h0, "h0 [S, 128]", B * A * H), (init, "is_init [S, L]", B * A * L)):   # the kernels index them as declared: no strides travel
+        if t is not None and (not t.is_contiguous() or t.numel() != n):
+            raise ValueError(f"{what} must be contiguous and hold S = {B * A} sequences")
     s.x = x4.data_ptr()
     for d in range(3):
         s.x_stride[d] = x4.stride(d) if x4.shape[d] > 1 else 0

@@ -226,7 +226,9 @@ def _gathered(state, is_init, segment, NS, A, L):
     h0 = state.reshape(NS, A, H).index_select(0, seg).reshape(B * A, H)
     f = is_init.reshape(NS, L)
     f = f.view(torch.uint8) if f.dtype == torch.bool else (f != 0).view(torch.uint8)
-    flags = f.index_select(0, seg).unsqueeze(1).expand(B, A, L).reshape(B * A, L)
+    # (contiguous(): for B = 1 the reshape of the expanded [1, A, L] is a VIEW with stride 0 over the agents, which the kernels, reading
+    # flags[s L + t], would take for A L bytes: the agents past the first read behind the segment's L flags)
+    flags = f.index_select(0, seg).unsqueeze(1).expand(B, A, L).reshape(B * A, L).contiguous()
     return h0, flags
 
 

@@ -28,6 +28,7 @@ import pytest
 import torch
 
 import rnn_update_reference as U
+from rnn_update_cases import rescaled as _rescaled          # the references on the kept segments at n = B L A (the module docstring)
 from hns_amd import abi, rnn_train
 
 pytestmark = pytest.mark.gpu
@@ -180,23 +181,6 @@ def test_same_bits_twice_and_with_a_dirty_workspace():
     for x, y in ((a1, a2), (a1, a3), (v1, v2), (v1, v3)):
         for n in x:
             assert np.array_equal(x[n], y[n]), n
-
-
-def _rescaled(c, keep, dtype, loss="huber"):
-    """The references on the kept segments at n = B L A (the module docstring)."""
-    B = c["y"].shape[0]
-    sub = {k: (v[keep] if k in ("y", "action", "log_probs_old", "advantages", "b_values", "b_returns") else v) for k, v in c.items()}
-    a, v = U.actor_head_autograd(sub, dtype), U.critic_head_autograd(sub, dtype, loss=loss)
-    f = len(keep) / B
-    n = float(np.prod(c["y"].shape[:3]))
-    full = lambda x: np.concatenate([x, np.zeros((B - len(keep),) + x.shape[1:])])[np.argsort(list(keep) + [b for b in range(B) if b not in keep])]   # noqa: E731
-    ra = {"dy": full(a["dy"] * f), "d_head_w": a["d_head_w"] * f, "d_head_b": a["d_head_b"] * f, "d_log_std": (a["d_log_std"] + 1e-3) * f - 1e-3,
-          "policy_loss": a["policy_loss"] * f, "entropy": a["entropy"], "ess": a["ess"] * f, "log_probs": a["log_probs"], "ratio": a["ratio"], "w": a["w"]}
-    val, ret = v["values"], np.asarray(sub["b_returns"], np.float64 if dtype == torch.float64 else np.float32).astype(np.float64)
-    var = ((ret * ret).sum() - ret.sum() ** 2 / n) / (n - 1.0)
-    rv = {"dy": full(v["dy"] * f), "d_head_w": v["d_head_w"] * f, "d_head_b": v["d_head_b"] * f, "value_loss": v["value_loss"] * f,
-          "explained_var": 1.0 - (((val - ret) ** 2).sum() / n) / var, "values": v["values"], "l_orig": v["l_orig"], "l_clip": v["l_clip"], "dist": v["dist"]}
-    return ra, rv
 
 
 def test_an_out_of_range_segment_id_contributes_nothing():
