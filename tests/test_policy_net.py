@@ -177,6 +177,26 @@ def test_new_symbols_are_exported_and_refuse_bad_arguments():
     assert b"non-NULL" in L.hns_last_error()
 
 
+def test_the_entry_table_of_the_four_classes_names_the_eight_exported_entries():
+    """For every (per_agent, recurrent, act) the class's entry is a symbol of the loaded library, and the four classes together name exactly
+    the eight forward / act entries that include/hns.h declares."""
+    import re
+    with open(os.path.join(ROOT, "include", "hns.h")) as f:
+        declared = set(re.findall(r"^int (hns_policy_(?:forward|act)\w*)\(", f.read(), re.M))
+    assert len(declared) == 8
+    lib = abi.load_library()
+    classes = [P.DevicePolicy, P.PerAgentDevicePolicy, P.RecurrentDevicePolicy, P.PerAgentRecurrentDevicePolicy]
+    assert sorted((c.per_agent, c.recurrent) for c in classes) == [(False, False), (False, True), (True, False), (True, True)]
+    named = set()
+    for c in classes:
+        for act in (False, True):
+            sym = P.ENTRIES[c.per_agent, c.recurrent, act]
+            assert sym in abi.EXPORTED_SYMBOLS and getattr(lib, sym).argtypes, sym       # exported, and its arguments declared in abi.py
+            assert ("_agents" in sym, "_rnn" in sym, "_act" in sym) == (c.per_agent, c.recurrent, act), sym
+            named.add(sym)
+    assert named == declared == set(P.ENTRIES.values())
+
+
 FAKE = 1 << 20                                   # a made-up, 16-byte aligned address: every call below is refused by argument checking alone
 DET, VAL = abi.HNS_POLICY_DETERMINISTIC, abi.HNS_POLICY_VALUE_ONLY
 

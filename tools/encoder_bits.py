@@ -4,6 +4,7 @@ hns_policy_forward (policy.DevicePolicy), the critic's update (critic_train.valu
 and of the four policy classes through all eight policy entries, with their packed images (policy_section).
 
     python tools/encoder_bits.py OUT.npz                 # on an MI355X: runs every case, writes every output array
+    python tools/encoder_bits.py --cpu OUT.npz           # anywhere: the policy section alone on CPU tensors (the classes' restatements)
     python tools/encoder_bits.py --compare A.npz B.npz   # anywhere: the first array that differs (np.array_equal on the uint32 views); exit 1 if any
 
 Run it once in a tree of the commit before the change (with that tree's own build of the library) and once in the tree after it, on the same
@@ -47,6 +48,7 @@ def policy_section(put, torch, P, device="cuda"):
     _rnn_agents forms) and the packed images themselves.  policy.py and abi.py decide nothing about the bits, so HNS_LIBRARY=<another
     build> python tools/encoder_bits.py OUT.npz is the other arm in the same tree.  No NaN goes in: operand order may move a NaN's payload."""
     dev, D = torch.device(device), 35                            # (on "cpu" the classes run their restatements: a rehearsal of this loop)
+    cuda = dev.type == "cuda"                                    # the packed images and the call counter exist on the device only
     put_out = lambda tag, o: [put(f"{tag}:{n}", getattr(o, n)) for n in o._fields if getattr(o, n) is not None]      # noqa: E731
     for E, A, K in POLICY_SHAPES:
         g = torch.Generator().manual_seed(9000 + 100 * E + 10 * A + K)
@@ -63,17 +65,19 @@ def policy_section(put, torch, P, device="cuda"):
         modes = {"eps": dict(eps=eps), "philox": {}, "det": dict(deterministic=True), "vo": dict(value_only=True)}
         for cls, (a, c) in {"DevicePolicy": (sa, sc), "PerAgentDevicePolicy": (pa, pc)}.items():
             pol, tag = getattr(P, cls)(on(a), on(c), seed=seed), f"pol:{cls}:e{E}a{A}k{K}"
-            if dev.type == "cuda":
+            if cuda:
                 pol.refresh()
                 put(f"{tag}:packed", pol.packed.view(torch.float32))
             for mode, kw in modes.items():
-                pol.counter.fill_(7)
+                if cuda:
+                    pol.counter.fill_(7)
                 put_out(f"{tag}:{mode}", pol.forward(xs, xo, xc, **kw))
-                put(f"{tag}:{mode}:counter", pol.counter)
+                if cuda:
+                    put(f"{tag}:{mode}:counter", pol.counter)
             put(f"{tag}:act", pol.act(xs, xo, xc))
         for cls, (a, c) in {"RecurrentDevicePolicy": (ra, rc), "PerAgentRecurrentDevicePolicy": (qa, qc)}.items():
             pol, tag = getattr(P, cls)(on(a), on(c), seed=seed), f"pol:{cls}:e{E}a{A}k{K}"
-            if dev.type == "cuda":
+            if cuda:
                 pol.refresh()
                 put(f"{tag}:packed", pol.packed.view(torch.float32))
                 put(f"{tag}:rnn_packed", pol.rnn_packed.view(torch.float32))
@@ -82,16 +86,38 @@ def policy_section(put, torch, P, device="cuda"):
                     t = f"{tag}:{st}:{fl}"
                     for mode, kw in modes.items():
                         ha, hc = (None, None) if st == "absent" else (h0[0].clone(), h0[1].clone())
-                        pol.counter.fill_(7)
+                        if cuda:
+                            pol.counter.fill_(7)
                         o = pol.forward(xs, xo, xc, actor_state=ha, critic_state=hc, is_init=is_init, out_states=(ha, hc) if st == "inplace" else None, **kw)
                         put_out(f"{t}:{mode}", o)
-                        put(f"{t}:{mode}:counter", pol.counter)
+                        if cuda:
+                            put(f"{t}:{mode}:counter", pol.counter)
                         if st == "inplace":                       # what value_only must leave alone included
                             put(f"{t}:{mode}:actor_buffer", ha)
                     h = None if st == "absent" else h0[0].clone()
                     action, new = pol.act_step(xs, xo, xc, state=h, is_init=is_init, out_state=h if st == "inplace" else None)
                     put(f"{t}:act_step:action", action)
                     put(f"{t}:act_step:state", new)
+
+
+def flat(t):
+    return np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32, copy=False)).reshape(-1)
+
+
+def save(path, out):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.savez(path, **out)
+    print(f"{len(out)} arrays, {sum(v.size for v in out.values())} values -> {path}")
+
+
+def dump_cpu(path):
+    import torch
+    sys.path.insert(0, ROOT)
+    import hns_amd  # noqa: F401
+    from hns_amd import policy as P
+    out = {}
+    policy_section(lambda name, t: out.__setitem__(name, flat(t)), torch, P, device="cpu")
+    save(path, out)
 
 
 def dump(path):
@@ -111,7 +137,7 @@ def dump(path):
     out = {}
 
     def put(name, t):
-        out[name] = np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32, copy=False)).reshape(-1)
+        out[name] = flat(t)
 
     dev = lambda d: {k: torch.as_tensor(np.asarray(v)).cuda() for k, v in d.items()}
 
@@ -200,14 +226,14 @@ def dump(path):
         put(f"actor:strided:grad:{k}", v.grad)
 
     torch.cuda.synchronize()
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    np.savez(path, **out)
-    print(f"{len(out)} arrays, {sum(v.size for v in out.values())} values -> {path}")
+    save(path, out)
 
 
 if __name__ == "__main__":
     if len(sys.argv) == 4 and sys.argv[1] == "--compare":
         sys.exit(compare(sys.argv[2], sys.argv[3]))
+    if len(sys.argv) == 3 and sys.argv[1] == "--cpu":
+        sys.exit(dump_cpu(sys.argv[2]))
     if len(sys.argv) != 2 or sys.argv[1].startswith("-"):
         sys.exit(__doc__)
     dump(sys.argv[1])
