@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Heterogeneous recurrent pursuers: MAPPO with share_actor: False AND actor.rnn / critic.rnn — one actor and one actor GRU per agent, the critic
-and its GRU shared — collected and evaluated on the device.
+and its GRU shared — collected, evaluated and trained on the device.
 
     python examples/per_agent_recurrent.py --envs 64 --steps 16 --seq-len 8
+    python examples/per_agent_recurrent.py --envs 64 --steps 16 --seq-len 8 --learner --updates 2     # ... and trained
     python examples/per_agent_recurrent.py --checkpoint checkpoint_final.pt     # the reference's dict (MAPPOPolicy.state_dict())
 
 env -> PerAgentRecurrentDevicePolicy -> DeviceCollector(rnn_seq_len=) -> DeviceEvaluator: the loop of examples/recurrent_policy.py with the
@@ -11,9 +12,11 @@ stacked actor in the shared one's place.  This is the configuration the referenc
 leaves among them.  The collector carries both rnn states [N, A, 128] on the device and stores `is_init` per step and the states going into
 every segment; the evaluator carries ONE actor state in place.  The collector and the evaluator are the ones every policy uses.
 
-Training this configuration on the device is not built yet (every learner refuses the policy: DESIGN-open-items.md #13); the stored rollout is
-what a torch update over hns_amd.encoder / hns_amd.rnn per agent would read.  The script saves the checkpoint dict, loads it into a second
-policy and shows that both act with the same bits."""
+--learner: train through `learner.PerAgentRecurrentDeviceLearner` — one `train_rollout` per rollout: the bootstrap value, the
+targets, the env's trajectory predictor, `--updates` PPO epochs of 4 minibatches of segments through rnn_train.update_actor_rnn_per_agent (the
+encoder op, the GRU op and the head entry on the stacked tensors, ONE ClippedAdam step over the 29 stacked tensors) and update_critic_rnn.
+Before the first step it recomputes the first minibatch's log-probabilities from the stored states and flags and prints max |ratio - 1|,
+which is 0 up to rounding.  The script saves the checkpoint dict, loads it into a second policy and shows that both act with the same bits."""
 import argparse
 import os
 import sys
@@ -23,7 +26,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import hns_amd  # noqa: E402,F401
-from hns_amd import collector, config, evaluator, policy  # noqa: E402
+from hns_amd import collector, config, evaluator, learner, policy, rnn_train  # noqa: E402
 from hns_amd.env import HideAndSeek  # noqa: E402
 
 ALGO = {"use_TP_net": 1, "share_actor": False, "critic_input": "obs", "actor": {"tanh": False, "rnn": {"cls": "gru", "train_seq_len": 8}},
@@ -49,6 +52,8 @@ def main():
     ap.add_argument("--episode", type=int, default=40, help="max_episode_length of the two envs")
     ap.add_argument("--checkpoint", default=None, help="a MAPPOPolicy.state_dict() file with stacked recurrent actor_params")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--learner", action="store_true", help="train through PerAgentRecurrentDeviceLearner: one train_rollout per rollout, two rollouts")
+    ap.add_argument("--updates", type=int, default=2, help="PPO epochs per rollout (--learner)")
     args = ap.parse_args()
     torch.manual_seed(args.seed)
     task = {"env": {"num_envs": args.envs, "max_episode_length": args.episode}}
@@ -67,6 +72,25 @@ def main():
     rk = storage.recurrent_kwargs()
     print(f"collected [{args.envs} envs x {args.steps} steps]: is_init {tuple(rk['is_init'].shape)} ({int(rk['is_init'].sum())} set), the states going "
           f"into {args.steps // args.seq_len} segments {tuple(rk['actor_rnn_state'].shape)}, reward mean {float(storage.data['reward'].mean()):+.4f}")
+
+    if args.learner:
+        algo = {**ALGO, "ppo_epochs": args.updates, "num_minibatches": 4, "actor": {**ALGO["actor"], "rnn": {"cls": "gru", "train_seq_len": args.seq_len}},
+                "critic": {"rnn": {"cls": "gru", "train_seq_len": args.seq_len}}}
+        lrn = learner.PerAgentRecurrentDeviceLearner(ckpt["actor_params"], ckpt["critic"], algo, tp_net=env.TP, value_normalizer=learner.ValueNorm1().to(env.device),
+                                                     device_policy=net)
+        for it in range(2):
+            kw = storage.learner_kwargs()
+            if it == 0:                                          # the first minibatch before any step: the stored log-probabilities, recomputed
+                segs = torch.arange(max(1, args.envs * (args.steps // args.seq_len) // 4), device=env.device)
+                res = rnn_train.policy_loss_and_grad_rnn_per_agent(ckpt["actor_params"], kw["obs_self"], kw["obs_others"], kw["obs_cylinders"],
+                                                                   rk["actor_rnn_state"], rk["is_init"], kw["action"], kw["log_probs"], kw["reward"],
+                                                                   segment=segs, seq_len=args.seq_len)
+                old = kw["log_probs"].reshape(-1, args.seq_len, net.num_agents, 1)[segs]
+                print(f"first minibatch, before any step: max |ratio - 1| = {float((torch.exp(res.log_probs - old) - 1).abs().max()):.3e}")
+            info = lrn.train_rollout(**kw, **rk)
+            print(f"rollout {it}: " + "  ".join(f"{k.split('/')[-1]} {v:+.5f}" for k, v in info.items()))
+            storage = collect.collect()
+            rk = storage.recurrent_kwargs()
 
     state = torch.get_rng_state()
     eval_env = HideAndSeek(config.make_cfg(task, algo={"use_TP_net": 1}))

@@ -742,6 +742,24 @@ int hns_encoder_forward(const hns_policy_net *net, const hns_critic_batch *batch
 int hns_encoder_backward(const hns_policy_net *net, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
                          const float *dfeatures, const hns_policy_grads *grads, void *workspace, size_t workspace_bytes, void *stream);
 /*
+ * The encoder op on the STACKED tensors (the encoder of one recurrent actor per agent: share_actor: false with actor.rnn):
+ * hns_encoder_forward / hns_encoder_backward with a hns_policy_net / hns_policy_grads whose every encoder tensor is stacked over the agents
+ * ([A, ...], contiguous, as hns_actor_train_grad_agents takes them; the head fields are ignored): agent a's rows run on slice a, and agent a's
+ * slice of every gradient is the sum over its own rows (in_proj_b's k third receives zeros per agent).  features / dfeatures keep the shared
+ * op's layout, [batch x num_agents, 128] with row = position x num_agents + agent, so the GRU op reads and writes them in place; a row's
+ * features are bit for bit hns_encoder_forward's with slice a.  The pack, the tiles (32 minibatch positions of ONE agent, numbered agent-major,
+ * each agent's count padded to whole row ranges of the weight-gradient kernel), the weight-gradient launch and the order of every sum are
+ * hns_actor_train_grad_agents'; the reduce writes each agent's partials into its slice; no norm.  The forward pass launches the agents' live
+ * tiles alone.  Properties: one stream, no allocation, no host synchronisation, fixed-order sums, no float atomics, capturable.  Refusals:
+ * hns_encoder_forward's / hns_encoder_backward's, in their order.  hns_encoder_agents_workspace_bytes: as hns_encoder_workspace_bytes (A packed
+ * images forward); 0 for an invalid shape and for `rows` that are no multiple of num_agents.
+ */
+size_t hns_encoder_agents_workspace_bytes(int64_t rows, int32_t self_dim, int32_t num_agents, int32_t num_cylinders, int32_t backward);
+int hns_encoder_forward_agents(const hns_policy_net *nets, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                               float *features, void *workspace, size_t workspace_bytes, void *stream);
+int hns_encoder_backward_agents(const hns_policy_net *nets, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                                const float *dfeatures, const hns_policy_grads *grads, void *workspace, size_t workspace_bytes, void *stream);
+/*
  * The recurrent block of the reference's rnn heads as a differentiable op (hns_amd.rnn): modules/rnn.py's GRU — an nn.GRUCell
  * stepped over the sequence, the carried state multiplied by 1 - is_init before every step, LayerNorm(h + x) behind it — with input size =
  * hidden size = 128 (the reference builds it on the encoder's 128 features).  For t = 0 .. L - 1, per sequence s:
@@ -782,6 +800,28 @@ int hns_gru_forward(const hns_gru_net *net, const hns_gru_seq *seq, float *out, 
                     void *stream);
 int hns_gru_backward(const hns_gru_net *net, const hns_gru_seq *seq, const float *h_hist, const float *dout, const float *dh_last,
                      const hns_gru_grads *grads, float *dx, float *dh0, void *workspace, size_t workspace_bytes, void *stream);
+/*
+ * One GRU per agent (the stacked actor of share_actor: false with actor.rnn; hns_amd.rnn with stacked parameters):
+ * hns_gru_forward / hns_gru_backward with a hns_gru_net / hns_gru_grads whose every tensor is stacked over `inner` = A agents
+ * ([A, 384, 128] x2, [A, 384] x2, [A, 128] x2, contiguous): sequence s = b inner + a runs on slice a, and agent a's slice of every gradient
+ * is the sum over its own sequences.  x, out, dout, dx, h0, is_init, h_hist, h_last and dh0 keep the layouts and the index order above.
+ * Per sequence the arithmetic and its order are hns_gru_forward's and hns_gru_backward's: out, h_last, h_hist, dx and dh0 of sequence (b, a)
+ * are bit for bit those of the shared entries called with slice a.
+ * The division of the work is a function of the shape alone.  Sweeps: a tile is 16 sequences of ONE agent (b = 16 i .. 16 i + 15 at fixed
+ * a), tpa = ceil(outer / 16) tiles per agent; the grid has A gpa workgroups, gpa = min(tpa, floor(256 / A)); workgroup g belongs to agent
+ * g / gpa for the whole launch and runs that agent's tiles g % gpa, g % gpa + gpa, ...  Weight gradients: the gate-gradient workspace is
+ * numbered agent-major, row (a, b L + t), each agent's outer L rows padded to spa row ranges of tps 32-row tiles (t = ceil(outer L / 32),
+ * tps = ceil(t / floor(256 / A)), spa = ceil(t / tps)), so no range holds two agents; the padding rows are neither written nor read.  Sums:
+ * a weight-gradient partial adds its range's rows in index order; agent a's gradient value is the fp64 sum of its spa range partials in index
+ * order (the LayerNorm's: of its gpa workgroups' partial rows, each the workgroup's tiles in the order it ran them), rounded once.
+ * Refusals: hns_gru_forward's / hns_gru_backward's, in their order, and behind the shape checks `inner` outside [1, HNS_MAX_AGENTS].
+ * hns_gru_agents_workspace_bytes: as hns_gru_workspace_bytes for `outer` x `inner` sequences (0 forward, and for an invalid shape).
+ */
+size_t hns_gru_agents_workspace_bytes(int64_t outer, int64_t inner, int32_t steps, int32_t backward);
+int hns_gru_forward_agents(const hns_gru_net *nets, const hns_gru_seq *seq, float *out, float *h_last, float *h_hist, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int hns_gru_backward_agents(const hns_gru_net *nets, const hns_gru_seq *seq, const float *h_hist, const float *dout, const float *dh_last,
+                            const hns_gru_grads *grads, float *dx, float *dh0, void *workspace, size_t workspace_bytes, void *stream);
 /*
  * The recurrent policy's forward pass (actor.rnn / critic.rnn: the GRU block above behind each encoder; hns_amd.policy.RecurrentDevicePolicy;
  * DESIGN.md §7.12): ONE launch per call runs encoder -> one GRU step -> head for both networks, the state carried by the caller on the device.
@@ -912,6 +952,26 @@ int hns_rnn_actor_head_grad(const float *head_w, const float *head_b, const floa
 int hns_rnn_critic_head_grad(const float *head_w, const float *head_b, const hns_rnn_rows *rows, const float *b_values, const float *b_returns,
                              float clip_param, int32_t loss_kind, float huber_delta, float *dy, float *d_head_w, float *d_head_b, float *value_loss,
                              float *explained_var, float *values, void *workspace, size_t workspace_bytes, void *stream);
+/*
+ * One head per agent (the stacked actor of share_actor: false with actor.rnn; hns_amd.rnn_train.policy_loss_and_grad_rnn_per_agent; DESIGN.md
+ * §7.18): hns_rnn_actor_head_grad with head_w [A, 4, 128], head_b [A, 4] and log_std [A, 4] (A = rows->inner, contiguous) and their gradients
+ * stacked the same way; row (b, t, a) runs on slice a, and agent a's slices of the gradients are the sums over its own rows.  policy_loss =
+ * -4 mean over ALL B L A rows of min(..) (every row's backward weight carries 1 / (B L A)); entropy = the mean over the agents of each agent's
+ * entropy, so each agent's d_log_std takes -entropy_coef / A once; ess is hns_rnn_actor_head_grad's (its columns are per agent).  The
+ * dead-segment rule, the geometry struct, the log_probs layout, the ESS launch, the properties and the refusals are hns_rnn_actor_head_grad's;
+ * dy and log_probs of row (b, t, a) are bit for bit those of hns_rnn_actor_head_grad with agent a's head over all rows.
+ * Order of every sum (a function of the shape alone): the rows kernel runs A gpa workgroups, gpa = min(ceil(B L / 32), floor(512 / A));
+ * workgroup w belongs to agent w / gpa and takes trips w % gpa, w % gpa + gpa, ... of that agent's B L positions p = b L + t, 32 consecutive
+ * positions to a trip; a row group adds its rows trip after trip (head-gradient products in fp32, loss terms in fp64), the workgroup's partial
+ * is its 32 row groups added in index order in fp64; agent a's gradient values add its gpa partials in index order in fp64, rounded once; the
+ * loss sum adds all A gpa partials in workgroup order (agent-major); the entropy adds each agent's four terms in index order, then the agents
+ * in index order, and divides by A.  hns_rnn_actor_head_agents_workspace_bytes: the bytes for that plan (0 for an invalid shape).
+ */
+size_t hns_rnn_actor_head_agents_workspace_bytes(int64_t outer, int32_t inner, int32_t steps);
+int hns_rnn_actor_head_grad_agents(const float *head_w, const float *head_b, const float *log_std, const hns_rnn_rows *rows, const float *action,
+                                   const float *log_probs_old, const float *advantages, double clip_param, double entropy_coef, float *dy,
+                                   float *d_head_w, float *d_head_b, float *d_log_std, float *policy_loss, float *entropy, float *ess, float *log_probs,
+                                   void *workspace, size_t workspace_bytes, void *stream);
 /*
  * The global forms of the two head entries: one rank's part of a data-parallel recurrent update over the union of W ranks' minibatches
  * (they mirror hns_critic_train_sums, hns_critic_train_grad_global and hns_actor_train_grad_global).  Rows, geometry, the

@@ -21,6 +21,15 @@
 // predictor's sigmoid and tanh (hns_tp_train.hip).  The x products come first in every gate's chain, then the h products: the order does not
 // depend on L or on the tile, which is what makes a chained one-step call give the bits of the whole sequence.
 // Determinism: tiles go to workgroups by index, every sum has a fixed order, no float atomics.
+// One GRU per agent (the stacked actor of share_actor: false; hns_gru_forward_agents / hns_gru_backward_agents) is the same
+// four bodies on tensors stacked over `inner` = A, sequence (b, a) on slice a:
+//   hns_gru_fwd_agents_kernel, hns_gru_bwd_agents_kernel : a tile is 16 sequences of ONE agent (b = 16 i .. 16 i + 15 at fixed a).  The grid is
+//                           A x gpa workgroups, gpa = min(ceil(outer / 16), floor(256 / A)): workgroup g belongs to agent g / gpa for the whole
+//                           launch (its W_hh slice in registers as above) and walks that agent's tiles g % gpa, g % gpa + gpa, ...
+//   hns_gru_wgrad_agents_kernel : the gate gradients are numbered agent-major, each agent's outer L rows padded to spa row ranges of tps 32-row
+//                           tiles (spa = ceil(t / tps), tps = ceil(t / max(1, floor(256 / A))), t = ceil(outer L / 32)), so no range holds two
+//                           agents; range r belongs to agent r / spa.  The padding rows are never read.
+//   hns_gru_reduce_agents_kernel : agent a's spa weight partials and gpa LayerNorm partial rows, in index order, into slice a.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -62,6 +71,27 @@ struct GruArgs {
 HNS_DEV float gru_sigm(float z) { return 1.0f / (1.0f + expf(-z)); }
 HNS_DEV f32x4 gru_mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 HNS_DEV long long gru_seq_off(const GruArgs &a, long long q) { return (q / a.inner) * a.s0 + (q % a.inner) * a.s1; }
+
+// One GRU per agent: what the _agents kernels take beside GruArgs, whose six parameter pointers are then the STACKED tensors, `tiles` the tiles
+// of ONE agent and `dgate` the agent-major workspace
+struct GruAgents {
+    long long outer;                         // sequences per agent
+    long long rpa;                           // gate-gradient rows per agent, padded to whole row ranges
+    int gpa, spa;                            // sweep workgroups and weight-gradient row ranges per agent
+};
+
+// agent `ag`'s arguments: its slices of the stacked parameters and its block of the gate gradients
+HNS_DEV GruArgs gru_agent_args(const GruArgs &a0, const GruAgents &g, int ag) {
+    GruArgs a = a0;
+    a.w_ih += (long long)ag * 3 * (kGruH * kGruH);
+    a.w_hh += (long long)ag * 3 * (kGruH * kGruH);
+    a.b_ih += ag * 3 * kGruH;
+    a.b_hh += ag * 3 * kGruH;
+    a.ln_w += ag * kGruH;
+    a.ln_b += ag * kGruH;
+    if (a.dgate) a.dgate += (long long)ag * g.rpa * (4 * kGruH);
+    return a;
+}
 
 // LDS: x_t and the masked h_{t-1} of the tile as B operands [k][sequence]; the waves' partial sums of the LayerNorm; (backward) the gate gradients
 struct GruLds {
@@ -147,271 +177,88 @@ HNS_DEV float gru_unit_sum(GruLds &L, int slot, float v, int w, int col, int kq)
     return s;
 }
 
+// The sweeps' and the weight-gradient kernel's bodies are hns_gru_bodies.inc, included as text by the shared kernels and by the _agents ones
+// (one GRU per agent) under the macros that file names.  First the shared kernels: a tile is 16 consecutive sequences, tiles go round the grid.
+#define GRU_TILE_FIRST blockIdx.x
+#define GRU_TILE_STEP gridDim.x
+#define GRU_SEQ(p) (p)
+#define GRU_LIVE(p, q) ((q) < a.S)
+#define GRU_GATE_SEQ qc
+#define GRU_WG_RANGE split
+#define GRU_WG_HROW row
 __global__ __launch_bounds__(kGruThreads, 2) void hns_gru_fwd_kernel(const GruArgs a) {
-    __shared__ __align__(16) GruLds L;
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, col = lane & 15, kq = lane >> 4;
-    const int u0 = 16 * w + 4 * kq;                             // the lane's four units
-    GruWeights W;
-    gru_load_weights(a, w, col, kq, W);
-    const int Ls = a.L;
-    for (int tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
-        const long long q0 = (long long)tile * kGruTile, qc = q0 + col, qs = q0 + (tid & 15);
-        const bool valid = qc < a.S;
-        const long long xoff = valid ? gru_seq_off(a, qc) : 0;
-        const float *xrow = qs < a.S ? a.x + gru_seq_off(a, qs) : nullptr;
-        f32x4 h = (valid && a.h0) ? *reinterpret_cast<const f32x4 *>(a.h0 + qc * kGruH + u0) : f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int t = 0; t < Ls; ++t) {
-            const float m = (valid && a.is_init && a.is_init[qc * Ls + t]) ? 0.0f : 1.0f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) h[r] = h[r] * m;
-            gru_stage(L, a, xrow, t, tid, u0, col, h);
-            __syncthreads();
-            f32x4 acc[4];
-            gru_gates(L, W, a, w, u0, col, kq, acc);
-            f32x4 y;
-            float s1 = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float rg = gru_sigm(acc[0][r]), zg = gru_sigm(acc[1][r]), ng = tanhf(acc[2][r] + rg * acc[3][r]);
-                h[r] = (1.0f - zg) * ng + zg * h[r];
-                y[r] = h[r] + L.xs[gru_xslot(u0 + r) * kGruTile + col];
-                s1 += y[r];
-            }
-            const float mean = gru_unit_sum(L, 0, s1, w, col, kq) * (1.0f / kGruH);
-            float s2 = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                y[r] = y[r] - mean;
-                s2 += y[r] * y[r];
-            }
-            const float rstd = 1.0f / sqrtf(gru_unit_sum(L, 1, s2, w, col, kq) * (1.0f / kGruH) + kGruEps);
-            if (valid) {
-                const f32x4 lw = *reinterpret_cast<const f32x4 *>(a.ln_w + u0), lb = *reinterpret_cast<const f32x4 *>(a.ln_b + u0);
-                f32x4 o;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] = (y[r] * rstd) * lw[r] + lb[r];
-                *reinterpret_cast<f32x4 *>(a.out + xoff + (long long)t * a.s2 + u0) = o;
-                if (a.h_hist) *reinterpret_cast<f32x4 *>(a.h_hist + (qc * Ls + t) * kGruH + u0) = h;
-            }
-        }
-        if (valid) *reinterpret_cast<f32x4 *>(a.h_last + qc * kGruH + u0) = h;
-        __syncthreads();                                        // (the next tile's staging rewrites the LDS)
-    }
+#define GRU_BODY_FWD
+#include "hns_gru_bodies.inc"
+#undef GRU_BODY_FWD
 }
 
 __global__ __launch_bounds__(kGruThreads, 2) void hns_gru_bwd_kernel(const GruArgs a) {
-    __shared__ __align__(16) GruBwdLds B;
-    GruLds &L = B.f;
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, col = lane & 15, kq = lane >> 4;
-    const int u0 = 16 * w + 4 * kq;
-    GruWeights W;
-    gru_load_weights(a, w, col, kq, W);
-    const int Ls = a.L;
-    f32x4 dlnw = f32x4{0.f, 0.f, 0.f, 0.f}, dlnb = f32x4{0.f, 0.f, 0.f, 0.f};      // the lane's sequence only; summed over the lanes at the end
-    for (int tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
-        const long long q0 = (long long)tile * kGruTile, qc = q0 + col, qs = q0 + (tid & 15);
-        const bool valid = qc < a.S;
-        const long long xoff = valid ? gru_seq_off(a, qc) : 0;
-        const float *xrow = qs < a.S ? a.x + gru_seq_off(a, qs) : nullptr;
-        f32x4 dh = (valid && a.dh_last) ? *reinterpret_cast<const f32x4 *>(a.dh_last + qc * kGruH + u0) : f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int t = Ls - 1; t >= 0; --t) {
-            f32x4 hp = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (valid) {
-                if (t > 0) hp = *reinterpret_cast<const f32x4 *>(a.hist + (qc * Ls + t - 1) * kGruH + u0);
-                else if (a.h0) hp = *reinterpret_cast<const f32x4 *>(a.h0 + qc * kGruH + u0);
-            }
-            const float m = (valid && a.is_init && a.is_init[qc * Ls + t]) ? 0.0f : 1.0f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) hp[r] = hp[r] * m;
-            gru_stage(L, a, xrow, t, tid, u0, col, hp);
-            __syncthreads();
-            f32x4 acc[4];
-            gru_gates(L, W, a, w, u0, col, kq, acc);
-            f32x4 rg, zg, ng, xh;
-            float s1 = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                rg[r] = gru_sigm(acc[0][r]);
-                zg[r] = gru_sigm(acc[1][r]);
-                ng[r] = tanhf(acc[2][r] + rg[r] * acc[3][r]);
-                const float hn = (1.0f - zg[r]) * ng[r] + zg[r] * hp[r];
-                xh[r] = hn + L.xs[gru_xslot(u0 + r) * kGruTile + col];
-                s1 += xh[r];
-            }
-            const float mean = gru_unit_sum(L, 0, s1, w, col, kq) * (1.0f / kGruH);
-            float s2 = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                xh[r] = xh[r] - mean;
-                s2 += xh[r] * xh[r];
-            }
-            const float rstd = 1.0f / sqrtf(gru_unit_sum(L, 1, s2, w, col, kq) * (1.0f / kGruH) + kGruEps);
-            // LayerNorm backward: dy = rstd (g - mean(g) - xhat mean(g xhat)), g = dout ln_w
-            const f32x4 dout = valid ? *reinterpret_cast<const f32x4 *>(a.dout + xoff + (long long)t * a.s2 + u0) : f32x4{0.f, 0.f, 0.f, 0.f};
-            const f32x4 lw = *reinterpret_cast<const f32x4 *>(a.ln_w + u0);
-            f32x4 g;
-            float sg = 0.0f, sgx = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                xh[r] = xh[r] * rstd;
-                g[r] = dout[r] * lw[r];
-                sg += g[r];
-                sgx += g[r] * xh[r];
-                dlnw[r] += dout[r] * xh[r];
-                dlnb[r] += dout[r];
-            }
-            // (two sums behind one barrier: the slots differ)
-            sg += __shfl_xor(sg, 16, 64);
-            sg += __shfl_xor(sg, 32, 64);
-            sgx += __shfl_xor(sgx, 16, 64);
-            sgx += __shfl_xor(sgx, 32, 64);
-            if (kq == 0) {
-                L.red[2][w][col] = sg;
-                L.red[3][w][col] = sgx;
-            }
-            __syncthreads();
-            float mg = L.red[2][0][col], mgx = L.red[3][0][col];
-#pragma unroll
-            for (int k = 1; k < kGruWaves; ++k) {
-                mg += L.red[2][k][col];
-                mgx += L.red[3][k][col];
-            }
-            mg *= 1.0f / kGruH;
-            mgx *= 1.0f / kGruH;
-            f32x4 dy, dhz, dar, daz, dan, dahn;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                dy[r] = rstd * ((g[r] - mg) - xh[r] * mgx);
-                const float dht = dh[r] + dy[r];                // d h_t: from the steps after t, and from out_t
-                const float dn = dht * (1.0f - zg[r]), dz = dht * (hp[r] - ng[r]);
-                dan[r] = dn * (1.0f - ng[r] * ng[r]);
-                daz[r] = dz * (zg[r] * (1.0f - zg[r]));
-                dar[r] = (dan[r] * acc[3][r]) * (rg[r] * (1.0f - rg[r]));
-                dahn[r] = dan[r] * rg[r];
-                dhz[r] = dht * zg[r];
-                const int e = (u0 + r) * kGruTile + col;
-                B.da[0][e] = dar[r];
-                B.da[1][e] = daz[r];
-                B.da[2][e] = dan[r];
-                B.da[3][e] = dahn[r];
-            }
-            if (valid) {
-                float *dg = a.dgate + (qc * Ls + t) * kGruGate + u0;
-                *reinterpret_cast<f32x4 *>(dg) = dar;
-                *reinterpret_cast<f32x4 *>(dg + kGruH) = daz;
-                *reinterpret_cast<f32x4 *>(dg + 2 * kGruH) = dan;
-                *reinterpret_cast<f32x4 *>(dg + 3 * kGruH) = dahn;
-            }
-            __syncthreads();
-            // dx_t = W_ih^T dA_i, dh_{t-1} = W_hh^T dA_h for the wave's 16 units: k = gate row j = 4 s + kq over all 384 rows
-            f32x4 dxa = f32x4{0.f, 0.f, 0.f, 0.f}, dha = f32x4{0.f, 0.f, 0.f, 0.f};
-            const float *wi = a.w_ih + 16 * w + col, *wh = a.w_hh + 16 * w + col;
-#pragma unroll 8
-            for (int s = 0; s < 96; ++s) {
-                const int j = 4 * s + kq, gt = s >> 5, e = (j & (kGruH - 1)) * kGruTile + col;
-                const float bi = B.da[gt][e], bh = gt == 2 ? B.da[3][e] : bi;
-                dxa = gru_mfma(wi[(long long)j * kGruH], bi, dxa);
-                dha = gru_mfma(wh[(long long)j * kGruH], bh, dha);
-            }
-            if (valid) {
-                f32x4 dxv;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) dxv[r] = dxa[r] + dy[r];
-                *reinterpret_cast<f32x4 *>(a.dx + xoff + (long long)t * a.s2 + u0) = dxv;
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dh[r] = (dha[r] + dhz[r]) * m;
-        }
-        if (valid && a.dh0) *reinterpret_cast<f32x4 *>(a.dh0 + qc * kGruH + u0) = dh;
-        __syncthreads();
-    }
-    // this workgroup's LayerNorm partials: over the 16 sequences (lanes col = 0 .. 15 of this kq), fixed butterfly
-    float *lp = a.lnpart + (long long)blockIdx.x * (2 * kGruH);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        float sw = dlnw[r], sb = dlnb[r];
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {
-            sw += __shfl_xor(sw, o, 64);
-            sb += __shfl_xor(sb, o, 64);
-        }
-        if (col == 0) {
-            lp[u0 + r] = sw;
-            lp[kGruH + u0 + r] = sb;
-        }
-    }
+#define GRU_BODY_BWD
+#include "hns_gru_bodies.inc"
+#undef GRU_BODY_BWD
 }
 
 // dW partials: per (row range, matrix) the 128 x 128 product dA^T operand over the range's rows, and the column sums of dA.  Matrices 0-2:
 // W_ih's r, z, n thirds (dA blocks 0, 1, 2; operand x_t); 3-5: W_hh's (dA blocks 0, 1, 3; operand the masked h_{t-1}).  Row = s L + t.
 __global__ __launch_bounds__(256, 2) void hns_gru_wgrad_kernel(const GruArgs a, long long rows, int tiles, int tps, float *part) {
-    __shared__ __align__(16) float sdy[kGruWgRows * kGruWgLd];
-    __shared__ __align__(16) float sxx[kGruWgRows * kGruWgLd];
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, col = lane & 15, kq = lane >> 4;
-    const int m = blockIdx.y, split = blockIdx.x;
-    const int blk = m < 3 ? m : (m == 5 ? 3 : m - 3);
-    const int t0 = split * tps, t1 = t0 + tps < tiles ? t0 + tps : tiles;
-    f32x4 acc[2][8];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int c = 0; c < 8; ++c) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float bs0 = 0.0f, bs1 = 0.0f;
-    for (int t = t0; t < t1; ++t) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int idx = tid + 256 * i, rr = idx >> 5, c4 = idx & 31;
-            const long long row = (long long)t * kGruWgRows + rr;
-            f32x4 dv = f32x4{0.f, 0.f, 0.f, 0.f}, ov = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (row < rows) {
-                dv = *reinterpret_cast<const f32x4 *>(a.dgate + row * kGruGate + blk * kGruH + 4 * c4);
-                const long long q = row / a.L;
-                const int st = (int)(row - q * a.L);
-                if (m < 3) {
-                    ov = *reinterpret_cast<const f32x4 *>(a.x + gru_seq_off(a, q) + (long long)st * a.s2 + 4 * c4);
-                } else {
-                    if (st > 0) ov = *reinterpret_cast<const f32x4 *>(a.hist + (row - 1) * kGruH + 4 * c4);
-                    else if (a.h0) ov = *reinterpret_cast<const f32x4 *>(a.h0 + q * kGruH + 4 * c4);
-                    const float mk = (a.is_init && a.is_init[row]) ? 0.0f : 1.0f;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) ov[j] = ov[j] * mk;
-                }
-            }
-            *reinterpret_cast<f32x4 *>(&sdy[rr * kGruWgLd + 4 * c4]) = dv;
-            *reinterpret_cast<f32x4 *>(&sxx[rr * kGruWgLd + 4 * c4]) = ov;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const int k = 4 * s + kq;
-            const float a0 = sdy[k * kGruWgLd + (2 * w) * 16 + col], a1 = sdy[k * kGruWgLd + (2 * w + 1) * 16 + col];
-            bs0 += a0;
-            bs1 += a1;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const float b = sxx[k * kGruWgLd + c * 16 + col];
-                acc[0][c] = gru_mfma(a0, b, acc[0][c]);
-                acc[1][c] = gru_mfma(a1, b, acc[1][c]);
-            }
-        }
-        __syncthreads();
-    }
-    float *out = part + ((long long)split * 6 + m) * kGruWgOut;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) out[((2 * w + i) * 16 + 4 * kq + r) * kGruH + c * 16 + col] = acc[i][c][r];
-    bs0 += __shfl_xor(bs0, 16, 64);
-    bs0 += __shfl_xor(bs0, 32, 64);
-    bs1 += __shfl_xor(bs1, 16, 64);
-    bs1 += __shfl_xor(bs1, 32, 64);
-    if (kq == 0) {
-        out[kGruMat + (2 * w) * 16 + col] = bs0;
-        out[kGruMat + (2 * w + 1) * 16 + col] = bs1;
-    }
+#define GRU_BODY_WGRAD
+#include "hns_gru_bodies.inc"
+#undef GRU_BODY_WGRAD
 }
+
+#undef GRU_TILE_FIRST
+#undef GRU_TILE_STEP
+#undef GRU_SEQ
+#undef GRU_LIVE
+#undef GRU_GATE_SEQ
+#undef GRU_WG_RANGE
+#undef GRU_WG_HROW
+
+// One GRU per agent: `g` says how the grid is divided, `a` is the agent's (gru_agent_args).
+#define GRU_TILE_FIRST (blockIdx.x % g.gpa)
+#define GRU_TILE_STEP g.gpa
+#define GRU_SEQ(p) ((p) * a.inner + agent)
+#define GRU_LIVE(p, q) ((p) < g.outer)
+#define GRU_GATE_SEQ (q0 + col)
+#define GRU_WG_RANGE (split % g.spa)
+#define GRU_WG_HROW (q * a.L + st)
+// one GRU per agent: workgroup blockIdx.x belongs to agent blockIdx.x / gpa for the whole launch and walks that agent's tiles
+__global__ __launch_bounds__(kGruThreads, 2) void hns_gru_fwd_agents_kernel(const GruArgs a0, const GruAgents g) {
+    const int agent = blockIdx.x / g.gpa;
+    const GruArgs a = gru_agent_args(a0, g, agent);
+#define GRU_BODY_FWD
+#include "hns_gru_bodies.inc"
+#undef GRU_BODY_FWD
+}
+
+// (the LayerNorm partial row is the workgroup's, hence one agent's)
+__global__ __launch_bounds__(kGruThreads, 2) void hns_gru_bwd_agents_kernel(const GruArgs a0, const GruAgents g) {
+    const int agent = blockIdx.x / g.gpa;
+    const GruArgs a = gru_agent_args(a0, g, agent);
+#define GRU_BODY_BWD
+#include "hns_gru_bodies.inc"
+#undef GRU_BODY_BWD
+}
+
+// one GRU per agent: range blockIdx.x is range blockIdx.x % spa of agent blockIdx.x / spa.  `rows`: ONE agent's live rows (row = b L + t of its
+// block of the gate gradients; the sequence is b inner + agent everywhere else); `tiles`: its padded tile count, whole ranges
+__global__ __launch_bounds__(256, 2) void hns_gru_wgrad_agents_kernel(const GruArgs a0, const GruAgents g, int tps, float *part) {
+    const int agent = blockIdx.x / g.spa;
+    const GruArgs a = gru_agent_args(a0, g, agent);
+    const long long rows = g.outer * a.L;
+    const int tiles = g.spa * tps;
+#define GRU_BODY_WGRAD
+#include "hns_gru_bodies.inc"
+#undef GRU_BODY_WGRAD
+}
+
+#undef GRU_TILE_FIRST
+#undef GRU_TILE_STEP
+#undef GRU_SEQ
+#undef GRU_LIVE
+#undef GRU_GATE_SEQ
+#undef GRU_WG_RANGE
+#undef GRU_WG_HROW
 
 struct GruGradOut {
     float *w_ih, *w_hh, *b_ih, *b_hh, *ln_w, *ln_b;
@@ -421,7 +268,7 @@ constexpr int kGruReduceN = 6 * kGruWgOut + 2 * kGruH;
 
 // gradient value e: the fp64 sum of its partials in index order, rounded once.  e < 6 (128 128 + 128): matrix m's value or bias over the row
 // ranges; then ln_w [128], ln_b [128] over the sweep's workgroups
-__global__ __launch_bounds__(256) void hns_gru_reduce_kernel(const float *wpart, int splits, const float *lnpart, int groups, const GruGradOut o) {
+HNS_DEV void gru_reduce_body(const float *wpart, int splits, const float *lnpart, int groups, const GruGradOut &o) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= kGruReduceN) return;
     double acc = 0.0;
@@ -436,6 +283,19 @@ __global__ __launch_bounds__(256) void hns_gru_reduce_kernel(const float *wpart,
         for (int g = 0; g < groups; ++g) acc += (double)lnpart[(long long)g * (2 * kGruH) + f];
         (f < kGruH ? o.ln_w : o.ln_b - kGruH)[f] = (float)acc;
     }
+}
+
+__global__ __launch_bounds__(256) void hns_gru_reduce_kernel(const float *wpart, int splits, const float *lnpart, int groups, const GruGradOut o) {
+    gru_reduce_body(wpart, splits, lnpart, groups, o);
+}
+
+// one GRU per agent: workgroup (b, agent) is the reduce kernel's block b on the agent's `spa` weight partials and `gpa` LayerNorm partial rows,
+// written into the agent's slice of the stacked gradients
+__global__ __launch_bounds__(256) void hns_gru_reduce_agents_kernel(const float *wpart, int spa, const float *lnpart, int gpa, const GruGradOut o0) {
+    const int ag = blockIdx.y;
+    const GruGradOut o{o0.w_ih + (long long)ag * 3 * kGruMat, o0.w_hh + (long long)ag * 3 * kGruMat, o0.b_ih + ag * 3 * kGruH, o0.b_hh + ag * 3 * kGruH,
+                       o0.ln_w + ag * kGruH, o0.ln_b + ag * kGruH};
+    gru_reduce_body(wpart + (long long)ag * spa * 6 * kGruWgOut, spa, lnpart + (long long)ag * gpa * (2 * kGruH), gpa, o);
 }
 
 }  // namespace hns
@@ -469,6 +329,31 @@ bool gru_plan(int64_t seqs, int32_t steps, GruPlan &p) {
     return true;
 }
 
+// One GRU per agent: `outer` sequences per agent, `inner` = A agents.  The sweeps' A gpa workgroups and the weight-gradient kernel's A spa row
+// ranges are divided evenly among the agents (both a function of the shape alone); the gate gradients hold rpa rows per agent
+struct GruAgentsPlan {
+    int tpa, gpa, tps, spa;
+    long long rpa;
+    size_t o_gate, o_wpart, o_ln, bytes;
+};
+
+bool gru_plan_agents(int64_t outer, int64_t inner, int32_t steps, GruAgentsPlan &p) {
+    GruPlan one;
+    if (inner < 1 || inner > HNS_MAX_AGENTS || outer < 1 || outer >= ((int64_t)1 << 40) / inner || !gru_plan(outer * inner, steps, one)) return false;
+    const int A = (int)inner;
+    p.tpa = (int)((outer + hns::kGruTile - 1) / hns::kGruTile);
+    p.gpa = std::min(p.tpa, hns::kGruMaxGroups / A);
+    const long long wg = (outer * steps + hns::kGruWgRows - 1) / hns::kGruWgRows;
+    p.tps = (int)((wg + hns::kGruMaxSplits / A - 1) / (hns::kGruMaxSplits / A));
+    p.spa = (int)((wg + p.tps - 1) / p.tps);
+    p.rpa = (long long)p.spa * p.tps * hns::kGruWgRows;
+    p.o_gate = 0;
+    p.o_wpart = gru_round((size_t)A * p.rpa * hns::kGruGate * sizeof(float));
+    p.o_ln = p.o_wpart + gru_round((size_t)A * p.spa * 6 * hns::kGruWgOut * sizeof(float));
+    p.bytes = p.o_ln + gru_round((size_t)A * p.gpa * 2 * hns::kGruH * sizeof(float));
+    return true;
+}
+
 // the checks both entries share; fills the kernels' arguments
 int gru_check(const char *fn, const hns_gru_net *net, const hns_gru_seq *seq, hns::GruArgs &a, GruPlan &p) {
     if (!net || !seq) return hns_fail(fn, "null pointer");
@@ -491,6 +376,78 @@ int gru_check(const char *fn, const hns_gru_net *net, const hns_gru_seq *seq, hn
     return HNS_OK;
 }
 
+// hns_gru_forward and hns_gru_forward_agents (`agents`: the parameters stacked over seq->inner, one GRU per agent)
+int gru_forward(const char *fn, bool agents, const hns_gru_net *net, const hns_gru_seq *seq, float *out, float *h_last, float *h_hist, void *workspace,
+                void *stream) {
+    hns::GruArgs a;
+    GruPlan p;
+    GruAgentsPlan pa;
+    const int rc = gru_check(fn, net, seq, a, p);
+    if (rc != HNS_OK) return rc;
+    if (agents && !gru_plan_agents(seq->outer, seq->inner, seq->steps, pa)) return hns_fail(fn, "inner (one GRU per agent) must be in [1, 7]");
+    if (!out || !h_last || !hns_aligned(out, 16) || !hns_aligned(h_last, 16)) return hns_fail(fn, "out and h_last must be non-NULL and 16-byte aligned");
+    if (h_hist && !hns_aligned(h_hist, 16)) return hns_fail(fn, "h_hist must be 16-byte aligned");
+    if (workspace && !hns_aligned(workspace, 256)) return hns_fail(fn, "workspace must be 256-byte aligned");
+    a.out = out; a.h_last = h_last; a.h_hist = h_hist;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (agents) {
+        a.tiles = pa.tpa;
+        const hns::GruAgents g{seq->outer, pa.rpa, pa.gpa, pa.spa};
+        hipLaunchKernelGGL(hns::hns_gru_fwd_agents_kernel, dim3((int)seq->inner * pa.gpa), dim3(hns::kGruThreads), 0, st, a, g);
+    } else {
+        hipLaunchKernelGGL(hns::hns_gru_fwd_kernel, dim3(p.groups), dim3(hns::kGruThreads), 0, st, a);
+    }
+    HNS_CHECK_HIP(hipGetLastError());
+    return HNS_OK;
+}
+
+// hns_gru_backward and hns_gru_backward_agents
+int gru_backward(const char *fn, bool agents, const hns_gru_net *net, const hns_gru_seq *seq, const float *h_hist, const float *dout, const float *dh_last,
+                 const hns_gru_grads *grads, float *dx, float *dh0, void *workspace, size_t workspace_bytes, void *stream) {
+    hns::GruArgs a;
+    GruPlan p;
+    GruAgentsPlan pa;
+    const int rc = gru_check(fn, net, seq, a, p);
+    if (rc != HNS_OK) return rc;
+    if (agents && !gru_plan_agents(seq->outer, seq->inner, seq->steps, pa)) return hns_fail(fn, "inner (one GRU per agent) must be in [1, 7]");
+    if (!grads) return hns_fail(fn, "null pointer");
+    float *gw[6] = {grads->weight_ih, grads->weight_hh, grads->bias_ih, grads->bias_hh, grads->ln_w, grads->ln_b};
+    for (int k = 0; k < 6; ++k)
+        if (!gw[k] || !hns_aligned(gw[k], 16)) return hns_fail(fn, "gradient pointers must be non-NULL and 16-byte aligned");
+    if (!h_hist) return hns_fail(fn, "h_hist is required: the forward pass's hidden states");
+    if (!dout || !dx || !hns_aligned(h_hist, 16) || !hns_aligned(dout, 16) || !hns_aligned(dx, 16))
+        return hns_fail(fn, "h_hist, dout and dx must be non-NULL and 16-byte aligned");
+    if ((dh_last && !hns_aligned(dh_last, 16)) || (dh0 && !hns_aligned(dh0, 16))) return hns_fail(fn, "dh_last and dh0 must be 16-byte aligned");
+    if (!workspace || !hns_aligned(workspace, 256)) return hns_fail(fn, "workspace must be non-NULL and 256-byte aligned");
+    if (workspace_bytes < (agents ? pa.bytes : p.bytes)) return hns_fail(fn, "workspace too small");
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    float *wpart = reinterpret_cast<float *>(ws + (agents ? pa.o_wpart : p.o_wpart));
+    a.hist = h_hist; a.dout = dout; a.dh_last = dh_last; a.dx = dx; a.dh0 = dh0;
+    a.dgate = reinterpret_cast<float *>(ws + (agents ? pa.o_gate : p.o_gate));
+    a.lnpart = reinterpret_cast<float *>(ws + (agents ? pa.o_ln : p.o_ln));
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const hns::GruGradOut o{gw[0], gw[1], gw[2], gw[3], gw[4], gw[5]};
+    const dim3 reduce((hns::kGruReduceN + 255) / 256, agents ? (int)seq->inner : 1);
+    if (agents) {
+        const int A = (int)seq->inner;
+        a.tiles = pa.tpa;
+        const hns::GruAgents g{seq->outer, pa.rpa, pa.gpa, pa.spa};
+        hipLaunchKernelGGL(hns::hns_gru_bwd_agents_kernel, dim3(A * pa.gpa), dim3(hns::kGruThreads), 0, st, a, g);
+        HNS_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(hns::hns_gru_wgrad_agents_kernel, dim3(A * pa.spa, 6), dim3(256), 0, st, a, g, pa.tps, wpart);
+        HNS_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(hns::hns_gru_reduce_agents_kernel, reduce, dim3(256), 0, st, wpart, pa.spa, a.lnpart, pa.gpa, o);
+    } else {
+        hipLaunchKernelGGL(hns::hns_gru_bwd_kernel, dim3(p.groups), dim3(hns::kGruThreads), 0, st, a);
+        HNS_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(hns::hns_gru_wgrad_kernel, dim3(p.splits, 6), dim3(256), 0, st, a, p.rows, p.wg_tiles, p.tps, wpart);
+        HNS_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(hns::hns_gru_reduce_kernel, reduce, dim3(256), 0, st, wpart, p.splits, a.lnpart, p.groups, o);
+    }
+    HNS_CHECK_HIP(hipGetLastError());
+    return HNS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -501,54 +458,32 @@ size_t hns_gru_workspace_bytes(int64_t seqs, int32_t steps, int32_t backward) {
     return backward ? p.bytes : 0;
 }
 
+size_t hns_gru_agents_workspace_bytes(int64_t outer, int64_t inner, int32_t steps, int32_t backward) {
+    GruAgentsPlan p;
+    if (!gru_plan_agents(outer, inner, steps, p)) return 0;
+    return backward ? p.bytes : 0;
+}
+
 int hns_gru_forward(const hns_gru_net *net, const hns_gru_seq *seq, float *out, float *h_last, float *h_hist, void *workspace, size_t workspace_bytes,
                     void *stream) {
-    const char *fn = "hns_gru_forward";
-    hns::GruArgs a;
-    GruPlan p;
-    const int rc = gru_check(fn, net, seq, a, p);
-    if (rc != HNS_OK) return rc;
     (void)workspace_bytes;
-    if (!out || !h_last || !hns_aligned(out, 16) || !hns_aligned(h_last, 16)) return hns_fail(fn, "out and h_last must be non-NULL and 16-byte aligned");
-    if (h_hist && !hns_aligned(h_hist, 16)) return hns_fail(fn, "h_hist must be 16-byte aligned");
-    if (workspace && !hns_aligned(workspace, 256)) return hns_fail(fn, "workspace must be 256-byte aligned");
-    a.out = out; a.h_last = h_last; a.h_hist = h_hist;
-    hipLaunchKernelGGL(hns::hns_gru_fwd_kernel, dim3(p.groups), dim3(hns::kGruThreads), 0, static_cast<hipStream_t>(stream), a);
-    HNS_CHECK_HIP(hipGetLastError());
-    return HNS_OK;
+    return gru_forward("hns_gru_forward", false, net, seq, out, h_last, h_hist, workspace, stream);
+}
+
+int hns_gru_forward_agents(const hns_gru_net *nets, const hns_gru_seq *seq, float *out, float *h_last, float *h_hist, void *workspace,
+                           size_t workspace_bytes, void *stream) {
+    (void)workspace_bytes;
+    return gru_forward("hns_gru_forward_agents", true, nets, seq, out, h_last, h_hist, workspace, stream);
 }
 
 int hns_gru_backward(const hns_gru_net *net, const hns_gru_seq *seq, const float *h_hist, const float *dout, const float *dh_last,
                      const hns_gru_grads *grads, float *dx, float *dh0, void *workspace, size_t workspace_bytes, void *stream) {
-    const char *fn = "hns_gru_backward";
-    hns::GruArgs a;
-    GruPlan p;
-    const int rc = gru_check(fn, net, seq, a, p);
-    if (rc != HNS_OK) return rc;
-    if (!grads) return hns_fail(fn, "null pointer");
-    float *gw[6] = {grads->weight_ih, grads->weight_hh, grads->bias_ih, grads->bias_hh, grads->ln_w, grads->ln_b};
-    for (int k = 0; k < 6; ++k)
-        if (!gw[k] || !hns_aligned(gw[k], 16)) return hns_fail(fn, "gradient pointers must be non-NULL and 16-byte aligned");
-    if (!h_hist) return hns_fail(fn, "h_hist is required: the forward pass's hidden states");
-    if (!dout || !dx || !hns_aligned(h_hist, 16) || !hns_aligned(dout, 16) || !hns_aligned(dx, 16))
-        return hns_fail(fn, "h_hist, dout and dx must be non-NULL and 16-byte aligned");
-    if ((dh_last && !hns_aligned(dh_last, 16)) || (dh0 && !hns_aligned(dh0, 16))) return hns_fail(fn, "dh_last and dh0 must be 16-byte aligned");
-    if (!workspace || !hns_aligned(workspace, 256)) return hns_fail(fn, "workspace must be non-NULL and 256-byte aligned");
-    if (workspace_bytes < p.bytes) return hns_fail(fn, "workspace too small");
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    float *wpart = reinterpret_cast<float *>(ws + p.o_wpart);
-    a.hist = h_hist; a.dout = dout; a.dh_last = dh_last; a.dx = dx; a.dh0 = dh0;
-    a.dgate = reinterpret_cast<float *>(ws + p.o_gate);
-    a.lnpart = reinterpret_cast<float *>(ws + p.o_ln);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(hns::hns_gru_bwd_kernel, dim3(p.groups), dim3(hns::kGruThreads), 0, st, a);
-    HNS_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(hns::hns_gru_wgrad_kernel, dim3(p.splits, 6), dim3(256), 0, st, a, p.rows, p.wg_tiles, p.tps, wpart);
-    HNS_CHECK_HIP(hipGetLastError());
-    const hns::GruGradOut o{gw[0], gw[1], gw[2], gw[3], gw[4], gw[5]};
-    hipLaunchKernelGGL(hns::hns_gru_reduce_kernel, dim3((hns::kGruReduceN + 255) / 256), dim3(256), 0, st, wpart, p.splits, a.lnpart, p.groups, o);
-    HNS_CHECK_HIP(hipGetLastError());
-    return HNS_OK;
+    return gru_backward("hns_gru_backward", false, net, seq, h_hist, dout, dh_last, grads, dx, dh0, workspace, workspace_bytes, stream);
+}
+
+int hns_gru_backward_agents(const hns_gru_net *nets, const hns_gru_seq *seq, const float *h_hist, const float *dout, const float *dh_last,
+                            const hns_gru_grads *grads, float *dx, float *dh0, void *workspace, size_t workspace_bytes, void *stream) {
+    return gru_backward("hns_gru_backward_agents", true, nets, seq, h_hist, dout, dh_last, grads, dx, dh0, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

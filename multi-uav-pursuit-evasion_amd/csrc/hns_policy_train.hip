@@ -47,6 +47,13 @@
 //   hns_critic_wgrad_kernel        : unchanged — an agent's tiles are padded to whole row ranges, so no range straddles two agents.
 //   hns_actor_reduce_agents_kernel : each agent's partials into its slice of the stacked gradients (-entropy_coef / A on its d log_std);
 //                                    hns_critic_norm_kernel: ONE norm over all agents' per-block sums.
+// The encoder op on the stacked tensors (hns_encoder_forward_agents / hns_encoder_backward_agents; DESIGN.md §7.18: the encoder of one recurrent
+// actor per agent) is the two above combined — HEAD = 0 on the per-agent tiles:
+//   hns_actor_pack_agents_kernel       : as above.
+//   hns_encoder_agents_kernel<BWD>     : the tile body with HEAD = 0 on hns_actor_agents_kernel's tiles; features and d features keep the shared
+//                                        op's [rows, 128] layout, row = position x A + agent.
+//   hns_critic_wgrad_kernel            : unchanged, on the padded agent-major tiles.
+//   hns_encoder_reduce_agents_kernel   : each agent's partials into its slice of the 20 stacked encoder tensors; no norm launch.
 // Determinism: every sum has a fixed order, no float atomics: the same inputs give the same bits.
 #include <hip/hip_runtime.h>
 
@@ -264,6 +271,26 @@ __global__ __launch_bounds__(kCtThreads, 1) void hns_actor_agents_kernel(const C
     CtArgs a = a0;
     a.img = a0.img + (long long)agent * ct_img_floats(a0.D);
     a.net = enc_agent_slice(a0.net, a0.D, kActDim, agent);
+#define CT_TILE_BLOCK (agent * tpa + blockIdx.x)
+#define CT_TILE_ROW (((long long)blockIdx.x * kCtRows + r) * a.A < a.rows ? ((long long)blockIdx.x * kCtRows + r) * a.A + agent : a.rows)
+#define CT_TILE_FIRST (ag == agent ? 0 : kCtRows)
+#define CT_TILE_STEP 1
+#include "hns_policy_train_bodies.inc"
+#undef CT_TILE_BLOCK
+#undef CT_TILE_ROW
+#undef CT_TILE_FIRST
+#undef CT_TILE_STEP
+}
+
+// The encoder alone on the stacked tensors (hns_encoder_forward_agents / hns_encoder_backward_agents): hns_actor_agents_kernel's tiles, agent slice
+// and image with HEAD = 0 — features [rows, 128] out, or d features in, at row = position x A + agent as the shared op has them.  The forward
+// launch has no padding tiles (nothing is staged): its grid is the agents' live tiles alone.
+template <bool BWD, int HEAD = 0>                              // (HEAD a parameter: the body's `if constexpr` discards only dependent branches)
+__global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_encoder_agents_kernel(const CtArgs a0) {
+    const int agent = blockIdx.y, tpa = a0.tiles / a0.A;
+    CtArgs a = a0;
+    a.img = a0.img + (long long)agent * ct_img_floats(a0.D);
+    a.net = enc_agent_slice(a0.net, a0.D, 0, agent);
 #define CT_TILE_BLOCK (agent * tpa + blockIdx.x)
 #define CT_TILE_ROW (((long long)blockIdx.x * kCtRows + r) * a.A < a.rows ? ((long long)blockIdx.x * kCtRows + r) * a.A + agent : a.rows)
 #define CT_TILE_FIRST (ag == agent ? 0 : kCtRows)
@@ -545,6 +572,15 @@ __global__ __launch_bounds__(256) void hns_actor_reduce_agents_kernel(const floa
                     blockpart + (long long)agent * gridDim.x, kActDim, ls_add);
 }
 
+// the encoder op on the stacked tensors: hns_actor_reduce_agents_kernel without the head's destinations
+__global__ __launch_bounds__(256) void hns_encoder_reduce_agents_kernel(const float *gpart, int spa, const float *tpart, int ntpa, int P, int gblocks, const CtGrad g0,
+                                                                        int D, double *blockpart) {
+    const int agent = blockIdx.y;
+    const CtGrad g = enc_agent_slice(g0, D, 0, agent);
+    ct_reduce<false>(gpart + (long long)agent * spa * 6 * kCtGemmOut, spa, tpart + (long long)agent * ntpa * P, ntpa, P, gblocks, g, D,
+                     blockpart + (long long)agent * gridDim.x, 0, 0.0);
+}
+
 __global__ __launch_bounds__(256) void hns_critic_norm_kernel(const double *blockpart, int nb, float *grad_norm) {
     __shared__ double sm[256];
     const int tid = threadIdx.x;
@@ -636,6 +672,27 @@ bool ct_plan_encoder(int64_t rows, int32_t D, int32_t A, int32_t K, bool backwar
     return true;
 }
 
+// the encoder op on the stacked tensors: ct_plan_agents' tiles and row ranges with the encoder op's partial rows (heads = 0) and arrays — forward
+// the A images alone
+bool ct_plan_encoder_agents(int64_t rows, int32_t D, int32_t A, int32_t K, bool backward, CtPlan &p) {
+    if (!ct_plan_agents(rows, D, A, K, p)) return false;
+    p.P = hns::ct_partial_floats(D, 0);
+    p.tblocks = (p.P + 31) / 32;
+    size_t o = 0;
+    p.o_ctl = p.o_loss = 0;
+    p.o_img = o; o += ct_up((size_t)A * hns::ct_img_floats(D) * sizeof(float));
+    if (backward) {
+        p.o_block = o; o += ct_up((size_t)A * (p.gblocks + p.tblocks) * sizeof(double));
+        p.o_tile = o; o += ct_up((size_t)p.tiles * 2 * p.P * sizeof(float));
+        p.o_gemm = o; o += ct_up((size_t)p.splits * 6 * hns::kCtGemmOut * sizeof(float));
+        p.o_stage = o; o += ct_up((size_t)12 * p.stage_rows * hns::kCtE * sizeof(float));
+    } else {
+        p.o_block = p.o_tile = p.o_gemm = p.o_stage = 0;
+    }
+    p.total = o;
+    return true;
+}
+
 // What the critic's and the actor's entry points share.  hns_critic_batch and hns_actor_batch carry the same leading fields under the same names:
 // the templates over the batch type read them from either.  Every refusal keeps the entry point's order: ct_check_shape, the entry's hyper-parameters,
 // ct_bind_net, ct_check_obs, the entry's per-row pointers, ct_plan_call.
@@ -698,11 +755,13 @@ int ct_plan_call(const char *fn, const Batch &b, std::initializer_list<const flo
     for (const float *o : outs) ok = ok && hns_aligned(o, 4);
     if (!ok) return hns_fail(fn, "misaligned output (scalars 4 bytes, workspace 256)");
     const int64_t rows = b.batch * num_agents;
-    if (agents ? !ct_plan_agents(rows, self_dim, num_agents, num_cylinders, p)
+    if (agents ? (heads == 0 ? !ct_plan_encoder_agents(rows, self_dim, num_agents, num_cylinders, backward, p)
+                             : !ct_plan_agents(rows, self_dim, num_agents, num_cylinders, p))
                : (heads == 0 ? !ct_plan_encoder(rows, self_dim, num_agents, num_cylinders, backward, p) : !ct_plan(rows, self_dim, num_agents, num_cylinders, p, heads)))
         return hns_fail(fn, "invalid shape");
     if (workspace_bytes < p.total)
-        return hns_fail(fn, agents       ? "workspace too small (hns_actor_train_agents_workspace_bytes)"
+        return hns_fail(fn, agents       ? (heads == 0 ? "workspace too small (hns_encoder_agents_workspace_bytes)"
+                                                        : "workspace too small (hns_actor_train_agents_workspace_bytes)")
                             : heads > 1  ? "workspace too small (hns_actor_train_workspace_bytes)"
                             : heads == 1 ? "workspace too small (hns_critic_train_workspace_bytes)"
                                          : "workspace too small (hns_encoder_workspace_bytes)");
@@ -869,7 +928,7 @@ int ct_actor_call(const char *fn, bool global, bool agents, const hns_policy_net
 
 // The encoder op's two entries over one body.  Forward: pack, the tile kernel without a head.  Backward: pack, the tile kernel from d features, the
 // weight gradients and the reduce without the head's destinations; no norm.
-int ct_encoder_call(const char *fn, bool backward, const hns_policy_net *net, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents,
+int ct_encoder_call(const char *fn, bool backward, bool agents, const hns_policy_net *net, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents,
                     int32_t num_cylinders, float *features, const float *dfeatures, const hns_policy_grads *grads, void *workspace, size_t workspace_bytes,
                     void *stream) {
     if (int rc = ct_check_shape(fn, *batch, self_dim, num_agents, num_cylinders)) return rc;
@@ -879,11 +938,38 @@ int ct_encoder_call(const char *fn, bool backward, const hns_policy_net *net, co
     if (int rc = ct_bind_net(fn, *net, grads, num_agents > 1, 0, a.net, g)) return rc;
     if (int rc = ct_check_obs(fn, *batch, num_agents > 1)) return rc;
     if (!hns_aligned(backward ? dfeatures : features, 16)) return hns_fail(fn, backward ? "misaligned dfeatures (16 bytes)" : "misaligned features (16 bytes)");
-    if (int rc = ct_plan_call(fn, *batch, {}, workspace, workspace_bytes, self_dim, num_agents, num_cylinders, 0, p, a, backward)) return rc;
+    if (int rc = ct_plan_call(fn, *batch, {}, workspace, workspace_bytes, self_dim, num_agents, num_cylinders, 0, p, a, backward, agents)) return rc;
     if (backward) a.dfeat = dfeatures;
     else a.feat = features;
 
     const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (agents) {
+        static const hipError_t ag_f = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_encoder_agents_kernel<false>),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)hns::kCtLdsFwd);
+        static const hipError_t ag_b = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_encoder_agents_kernel<true>),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::CtLds));
+        HNS_CHECK_HIP(ag_f);
+        HNS_CHECK_HIP(ag_b);
+        const int A = num_agents, nb = p.gblocks + p.tblocks;
+        unsigned char *ws = static_cast<unsigned char *>(workspace);
+        hipLaunchKernelGGL(hns::hns_actor_pack_agents_kernel, dim3(256, A), dim3(256), 0, st, a.net, a.D, reinterpret_cast<float *>(ws + p.o_img));
+        HNS_CHECK_HIP(hipGetLastError());
+        if (!backward) {
+            const unsigned live = (unsigned)((batch->batch + hns::kCtRows - 1) / hns::kCtRows);
+            hipLaunchKernelGGL(hns::hns_encoder_agents_kernel<false>, dim3(live, A), dim3(hns::kCtThreads), hns::kCtLdsFwd, st, a);
+            HNS_CHECK_HIP(hipGetLastError());
+            return HNS_OK;
+        }
+        hipLaunchKernelGGL(hns::hns_encoder_agents_kernel<true>, dim3((unsigned)(p.tiles / A), A), dim3(hns::kCtThreads), sizeof(hns::CtLds), st, a);
+        HNS_CHECK_HIP(hipGetLastError());
+        float *gpart = reinterpret_cast<float *>(ws + p.o_gemm);
+        hipLaunchKernelGGL(hns::hns_critic_wgrad_kernel, dim3((unsigned)p.splits, 6), dim3(256), 0, st, a.stage, a.stage_rows, (int)p.tiles, (int)p.tps, gpart);
+        HNS_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(hns::hns_encoder_reduce_agents_kernel, dim3(nb, A), dim3(256), 0, st, gpart, (int)(p.splits / A), a.tilepart, (int)(2 * p.tiles / A), p.P,
+                           p.gblocks, g, a.D, reinterpret_cast<double *>(ws + p.o_block));
+        HNS_CHECK_HIP(hipGetLastError());
+        return HNS_OK;
+    }
     static const hipError_t attr_f = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<false, 0>),
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)hns::kCtLdsFwd);
     static const hipError_t attr_b = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_kernel<true, 0>),
@@ -987,14 +1073,33 @@ int hns_encoder_forward(const hns_policy_net *net, const hns_critic_batch *batch
                         float *features, void *workspace, size_t workspace_bytes, void *stream) {
     const char *fn = "hns_encoder_forward";
     if (!net || !batch || !features || !workspace) return hns_fail(fn, "null pointer");
-    return ct_encoder_call(fn, false, net, batch, self_dim, num_agents, num_cylinders, features, nullptr, nullptr, workspace, workspace_bytes, stream);
+    return ct_encoder_call(fn, false, false, net, batch, self_dim, num_agents, num_cylinders, features, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 int hns_encoder_backward(const hns_policy_net *net, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
                          const float *dfeatures, const hns_policy_grads *grads, void *workspace, size_t workspace_bytes, void *stream) {
     const char *fn = "hns_encoder_backward";
     if (!net || !batch || !dfeatures || !grads || !workspace) return hns_fail(fn, "null pointer");
-    return ct_encoder_call(fn, true, net, batch, self_dim, num_agents, num_cylinders, nullptr, dfeatures, grads, workspace, workspace_bytes, stream);
+    return ct_encoder_call(fn, true, false, net, batch, self_dim, num_agents, num_cylinders, nullptr, dfeatures, grads, workspace, workspace_bytes, stream);
+}
+
+size_t hns_encoder_agents_workspace_bytes(int64_t rows, int32_t self_dim, int32_t num_agents, int32_t num_cylinders, int32_t backward) {
+    CtPlan p;
+    return ct_plan_encoder_agents(rows, self_dim, num_agents, num_cylinders, backward != 0, p) ? p.total : 0;
+}
+
+int hns_encoder_forward_agents(const hns_policy_net *nets, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                               float *features, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "hns_encoder_forward_agents";
+    if (!nets || !batch || !features || !workspace) return hns_fail(fn, "null pointer");
+    return ct_encoder_call(fn, false, true, nets, batch, self_dim, num_agents, num_cylinders, features, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+int hns_encoder_backward_agents(const hns_policy_net *nets, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                                const float *dfeatures, const hns_policy_grads *grads, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "hns_encoder_backward_agents";
+    if (!nets || !batch || !dfeatures || !grads || !workspace) return hns_fail(fn, "null pointer");
+    return ct_encoder_call(fn, true, true, nets, batch, self_dim, num_agents, num_cylinders, nullptr, dfeatures, grads, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -30,6 +30,16 @@
 // hns_rnn_critic_head_grad_global runs the values kernel again for v (its own workspace: the call stands alone), so y is read twice as in the
 // local entry.  With one rank every output has the local entries' bits.
 //
+// One head per agent (hns_rnn_actor_head_grad_agents): head_w [A, 4, 128], head_b [A, 4], log_std [A, 4], the row's agent
+// selects the slices.
+//   hns_rnn_actor_rows_agents_kernel  : the rows kernel's body (hns_rnn_bodies.inc, shared as text) on A gpa workgroups, gpa = min(ceil(B L / 32),
+//                                       floor(512 / A)); workgroup w belongs to agent w / gpa and takes trips w % gpa, w % gpa + gpa, ... of that
+//                                       agent's B L positions (b, t), 32 to a trip — the per-row arithmetic is the shared kernel's
+//   hns_rnn_ess_kernel                : unchanged (its columns are per agent already)
+//   hns_rnn_actor_final_agents_kernel : agent a's slice of the stacked gradients from its gpa partials in index order; d log_std[a] takes
+//                                       -entropy_coef / A once; the loss sum adds all A gpa partials in workgroup order (agent-major);
+//                                       entropy = the agents' entropies (four terms in index order each) added in agent order, over A
+//
 // Order of every sum.  A lane adds its rows' contributions trip after trip (the head-gradient products in fp32, the loss terms in fp64: a lane
 // sees ceil(trips / G) rows); the workgroup's partial is the 32 row groups added in index order in fp64; the partials are added in workgroup
 // order in fp64 and rounded once to fp32.  G and the trips are functions of the shape alone: the same inputs give the same bits.  No atomics.
@@ -145,102 +155,37 @@ struct RtActorArgs {
     double *part;
 };
 
+#define RT_TRIP_ROWS a.G.rows
+#define RT_TRIP_FIRST blockIdx.x
+#define RT_TRIP_STEP gridDim.x
+#define RT_ROW(p) (p)
 __global__ __launch_bounds__(kRtThreads, 2) void hns_rnn_actor_rows_kernel(const RtActorArgs a) {
-    __shared__ __align__(16) float red[kRtRows][kRtE];
-    __shared__ double reds[kRtRows][9];
-    const int tid = threadIdx.x, r = tid >> 3, g = tid & 7;
-    float w[kRtAct][16], hb[kRtAct], ls[kRtAct];
-    double iv[kRtAct];
-#pragma unroll
-    for (int i = 0; i < kRtAct; ++i) {
-        rt_load(a.head_w + i * kRtE, g, w[i]);
-        hb[i] = a.head_b[i];
-        ls[i] = a.log_std[i];
-        iv[i] = exp(-2.0 * (double)ls[i]);                      // 1 / sigma^2
-    }
-    float aw[kRtAct][16], ab[kRtAct], al[kRtAct];
-    double aq = 0.0;
-#pragma unroll
-    for (int i = 0; i < kRtAct; ++i) {
-        ab[i] = 0.0f;
-        al[i] = 0.0f;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) aw[i][q] = 0.0f;
-    }
-    const long long trips = (a.G.rows + kRtRows - 1) / kRtRows;
-    for (long long trip = blockIdx.x; trip < trips; trip += gridDim.x) {
-        const long long row = trip * kRtRows + r;
-        const RtRow R = rt_row(a.G, row);
-        float y[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) y[q] = 0.0f;
-        if (R.live) rt_load(a.G.y + R.yoff, g, y);
-        // logp sums four terms of order 1; its rounding is the ratio's relative error, so the terms and their sum are fp64 from the fp32 mean
-        float am[kRtAct], dl[kRtAct];
-        double lp = 0.0;
-#pragma unroll
-        for (int i = 0; i < kRtAct; ++i) {
-            const float mu = rt_dot(w[i], y) + hb[i];
-            const float act = R.live ? a.action[R.idx * kRtAct + i] : mu;
-            const double dm = (double)act - (double)mu, z2 = dm * dm * iv[i];
-            am[i] = (float)(dm * iv[i]);                        // (a - mu) / sigma^2
-            dl[i] = (float)z2;                                  // (a - mu)^2 / sigma^2
-            lp += (-0.5 * z2 - (double)ls[i]) - 0.9189385332046727;   // log sqrt(2 pi)
-        }
-        float ratio = -1.0f, dlogp = 0.0f;                      // -1: the row is not part of the minibatch
-        double q0 = 0.0;
-        if (R.live) {
-            const float adv = a.adv[R.idx];
-            ratio = expf((float)(lp - (double)a.logp_old[R.idx]));
-            const float rc = fminf(fmaxf(ratio, a.clip_lo), a.clip_hi);
-            const float s1 = ratio * adv, s2 = rc * adv;
-            const bool inside = ratio >= a.clip_lo && ratio <= a.clip_hi;
-            const float wgt = (inside || s1 < s2) ? 1.0f : 0.0f;
-            const double d1 = (double)ratio * (double)adv, d2 = (double)rc * (double)adv;
-            q0 = d1 < d2 ? d1 : d2;
-            dlogp = -(float)kRtAct * adv * ratio * wgt * a.inv_n;
-        }
-        float dy[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) dy[q] = 0.0f;
-#pragma unroll
-        for (int i = 0; i < kRtAct; ++i) {
-            const float dmu = dlogp * am[i];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                dy[q] = __builtin_fmaf(dmu, w[i][q], dy[q]);
-                aw[i][q] += dmu * y[q];                         // d fc_mean.weight[i]
-            }
-            ab[i] += dmu;
-            al[i] += dlogp * (dl[i] - 1.0f);
-        }
-        aq += q0;
-        if (R.in) {
-            rt_store(a.G.dy + R.yoff, g, dy);                   // a dead row's dy: zeros
-            if (g == 0) {
-                a.ratio[(row % a.G.LA) * a.B + row / a.G.LA] = ratio;        // [column (t, a)][segment b]: the ESS kernel reads a column contiguously
-                if (R.live && a.logp_new) a.logp_new[row] = (float)lp;
-            }
-        }
-    }
-    double *part = a.part + (long long)blockIdx.x * kRtActorSlots;
-#pragma unroll
-    for (int i = 0; i < kRtAct; ++i) rt_flush(red, aw[i], part + i * kRtE, tid, r, g);
-    if (g == 0) {
-#pragma unroll
-        for (int i = 0; i < kRtAct; ++i) {
-            reds[r][i] = (double)ab[i];
-            reds[r][kRtAct + i] = (double)al[i];
-        }
-        reds[r][8] = aq;
-    }
-    __syncthreads();
-    if (tid < 9) {
-        double s = 0.0;
-        for (int rr = 0; rr < kRtRows; ++rr) s += reds[rr][tid];
-        part[kRtAct * kRtE + tid] = s;
-    }
+#include "hns_rnn_bodies.inc"
 }
+#undef RT_TRIP_ROWS
+#undef RT_TRIP_FIRST
+#undef RT_TRIP_STEP
+#undef RT_ROW
+
+// One head per agent (hns_rnn_actor_head_grad_agents): a0's head tensors are the stacked ones.  The grid is A gpa workgroups; workgroup w belongs
+// to agent w / gpa for the whole launch — that agent's head in its registers, its partial that agent's alone — and takes trips w % gpa,
+// w % gpa + gpa, ... of the agent's B L positions p = b L + t, 32 to a trip: row p A + agent.
+#define RT_TRIP_ROWS (a.G.rows / a.G.A)
+#define RT_TRIP_FIRST (blockIdx.x % gpa)
+#define RT_TRIP_STEP gpa
+#define RT_ROW(p) ((p) < a.G.rows / a.G.A ? (p) * a.G.A + agent : a.G.rows)
+__global__ __launch_bounds__(kRtThreads, 2) void hns_rnn_actor_rows_agents_kernel(const RtActorArgs a0, int gpa) {
+    const int agent = blockIdx.x / gpa;
+    RtActorArgs a = a0;
+    a.head_w += agent * kRtAct * kRtE;
+    a.head_b += agent * kRtAct;
+    a.log_std += agent * kRtAct;
+#include "hns_rnn_bodies.inc"
+}
+#undef RT_TRIP_ROWS
+#undef RT_TRIP_FIRST
+#undef RT_TRIP_STEP
+#undef RT_ROW
 
 // the G workgroup partials of the block's kRtFinalElems elements e0 .. e0 + 7, staged through LDS (independent loads: a thread that walked the
 // partials itself would pay one memory latency per partial) and added in workgroup order by the element's thread; returns the sum on tid < 8
@@ -315,6 +260,42 @@ __global__ __launch_bounds__(kRtThreads) void hns_rnn_actor_final_kernel(const d
         double ent = 0.0;
         for (int i = 0; i < kRtAct; ++i) ent += 0.5 + 0.9189385332046727 + (double)log_std[i];
         entropy[0] = (float)ent;
+        double es = 0.0;
+        for (int c = 0; c < LA; ++c) es += cols[c];
+        ess[0] = (float)(es / (double)LA / batch);
+    }
+}
+
+// One head per agent: workgroup (x, agent) is the final kernel's block x on the agent's gpa partials and slice of the stacked gradients; every
+// agent's d log_std takes -entropy_coef / A once (the entropy is the mean over the agents of each agent's).  The loss sum — the one element of
+// the last block — adds ALL A gpa partials in workgroup order (agent-major), in agent 0's block, which forms the three scalars.
+static_assert(kRtActorUsed - 1 == (kRtActorUsed - 1) / kRtFinalElems * kRtFinalElems, "the loss sum must be the only element of the last final block");
+__global__ __launch_bounds__(kRtThreads) void hns_rnn_actor_final_agents_kernel(const double *part, int gpa, int A, const double *col, int LA, double n, double batch,
+                                                                                double entropy_coef, const float *log_std, float *d_head_w, float *d_head_b,
+                                                                                float *d_log_std, float *policy_loss, float *entropy, float *ess) {
+    __shared__ double stage[kRtMaxGroups][kRtFinalElems];
+    __shared__ double cols[HNS_GRU_MAX_STEPS * HNS_MAX_AGENTS];
+    const int tid = threadIdx.x, e0 = blockIdx.x * kRtFinalElems, agent = blockIdx.y;
+    const bool last = e0 + kRtFinalElems >= kRtActorUsed;
+    if (last && agent > 0) return;
+    if (last)
+        for (int c = tid; c < LA; c += kRtThreads) cols[c] = col[c];
+    const double s = last ? rt_sum_partials(part, A * gpa, kRtActorSlots, e0, kRtActorUsed, stage, tid)
+                          : rt_sum_partials(part + (long long)agent * gpa * kRtActorSlots, gpa, kRtActorSlots, e0, kRtActorUsed, stage, tid);
+    const int e = e0 + tid;
+    if (tid >= kRtFinalElems || e >= kRtActorUsed) return;
+    if (e < kRtAct * kRtE) d_head_w[agent * kRtAct * kRtE + e] = (float)s;
+    else if (e < kRtAct * kRtE + kRtAct) d_head_b[agent * kRtAct + e - kRtAct * kRtE] = (float)s;
+    else if (e < kRtAct * kRtE + 2 * kRtAct) d_log_std[agent * kRtAct + e - kRtAct * kRtE - kRtAct] = (float)(s - entropy_coef / (double)A);
+    else {
+        policy_loss[0] = (float)(-(double)kRtAct * s / n);
+        double ent = 0.0;                                       // each agent's four terms in index order, the agents in index order
+        for (int ag = 0; ag < A; ++ag) {
+            double ea = 0.0;
+            for (int i = 0; i < kRtAct; ++i) ea += 0.5 + 0.9189385332046727 + (double)log_std[ag * kRtAct + i];
+            ent += ea;
+        }
+        entropy[0] = (float)(ent / (double)A);
         double es = 0.0;
         for (int c = 0; c < LA; ++c) es += cols[c];
         ess[0] = (float)(es / (double)LA / batch);
@@ -503,6 +484,22 @@ inline RtActorWs rt_actor_ws(long long rows, int LA) {
     return w;
 }
 
+// one head per agent: sweep workgroups per agent, min(trips of an agent's B L positions, floor(512 / A)) — a function of the shape alone
+inline int rt_groups_per_agent(long long rows, int A) {
+    const long long t = (rows / A + kRtRows - 1) / kRtRows;
+    return (int)(t > kRtMaxGroups / A ? kRtMaxGroups / A : t);
+}
+
+inline RtActorWs rt_actor_agents_ws(long long rows, int A, int LA) {
+    RtActorWs w;
+    const size_t G = (size_t)A * rt_groups_per_agent(rows, A);
+    w.part = 0;
+    w.ratio = w.part + rt_up(G * kRtActorSlots * sizeof(double));
+    w.col = w.ratio + rt_up((size_t)rows * sizeof(float));
+    w.bytes = w.col + rt_up((size_t)LA * sizeof(double));
+    return w;
+}
+
 inline RtCriticWs rt_critic_ws(long long rows) {
     RtCriticWs w;
     const size_t G = (size_t)rt_groups(rows);
@@ -543,7 +540,7 @@ namespace hns {
 static int rt_actor_entry(const char *fn, const float *head_w, const float *head_b, const float *log_std, const hns_rnn_rows *rows, const float *action,
                           const float *log_probs_old, const float *advantages, double clip_param, double entropy_coef, float *dy, float *d_head_w,
                           float *d_head_b, float *d_log_std, float *policy_loss, float *entropy, float *ess, float *log_probs, void *workspace,
-                          size_t workspace_bytes, void *stream, bool global, int64_t global_rows, double entropy_share) {
+                          size_t workspace_bytes, void *stream, bool global, int64_t global_rows, double entropy_share, bool agents = false) {
     RtActorArgs a;
     if (int rc = rt_check_rows(fn, rows, dy, a.G)) return rc;
     if (!head_w || !head_b || !log_std || !action || !log_probs_old || !advantages || !d_head_w || !d_head_b || !d_log_std || !policy_loss || !entropy ||
@@ -557,9 +554,10 @@ static int rt_actor_entry(const char *fn, const float *head_w, const float *head
     if (!(clip_param >= 0.0) || entropy_coef != entropy_coef) return hns_fail(fn, "clip_param must be >= 0 and entropy_coef a number");
     if (global && global_rows < (int64_t)a.G.rows) return hns_fail(fn, "global_rows must be >= the call's own B L A rows");
     if (global && !(entropy_share - entropy_share == 0.0)) return hns_fail(fn, "entropy_share must be finite");
-    const RtActorWs W = rt_actor_ws(a.G.rows, a.G.LA);
+    const RtActorWs W = agents ? rt_actor_agents_ws(a.G.rows, a.G.A, a.G.LA) : rt_actor_ws(a.G.rows, a.G.LA);
     if (!hns_aligned(workspace, 256)) return hns_fail(fn, "misaligned pointer: the workspace is 256-byte aligned");
-    if (workspace_bytes < W.bytes) return hns_fail(fn, "workspace shorter than hns_rnn_actor_head_workspace_bytes");
+    if (workspace_bytes < W.bytes)
+        return hns_fail(fn, agents ? "workspace shorter than hns_rnn_actor_head_agents_workspace_bytes" : "workspace shorter than hns_rnn_actor_head_workspace_bytes");
     char *ws = static_cast<char *>(workspace);
     const double n = global ? (double)global_rows : (double)a.G.rows;
     a.head_w = head_w; a.head_b = head_b; a.log_std = log_std;
@@ -571,12 +569,20 @@ static int rt_actor_entry(const char *fn, const float *head_w, const float *head
     a.part = reinterpret_cast<double *>(ws + W.part);
     a.ratio = reinterpret_cast<float *>(ws + W.ratio);
     double *col = reinterpret_cast<double *>(ws + W.col);
-    const int groups = rt_groups(a.G.rows);
+    const int groups = rt_groups(a.G.rows), gpa = rt_groups_per_agent(a.G.rows, a.G.A);
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(hns_rnn_actor_rows_kernel, dim3(groups), dim3(kRtThreads), 0, st, a);
+    if (agents) hipLaunchKernelGGL(hns_rnn_actor_rows_agents_kernel, dim3(a.G.A * gpa), dim3(kRtThreads), 0, st, a, gpa);
+    else hipLaunchKernelGGL(hns_rnn_actor_rows_kernel, dim3(groups), dim3(kRtThreads), 0, st, a);
     HNS_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(hns_rnn_ess_kernel, dim3(a.G.LA), dim3(kRtThreads), 0, st, static_cast<const float *>(a.ratio), (long long)rows->outer, a.G.LA, col);
     HNS_CHECK_HIP(hipGetLastError());
+    if (agents) {
+        hipLaunchKernelGGL(hns_rnn_actor_final_agents_kernel, dim3((kRtActorUsed + kRtFinalElems - 1) / kRtFinalElems, a.G.A), dim3(kRtThreads), 0, st,
+                           static_cast<const double *>(a.part), gpa, a.G.A, static_cast<const double *>(col), a.G.LA, n, (double)rows->outer, entropy_coef,
+                           log_std, d_head_w, d_head_b, d_log_std, policy_loss, entropy, ess);
+        HNS_CHECK_HIP(hipGetLastError());
+        return HNS_OK;
+    }
     hipLaunchKernelGGL(hns_rnn_actor_final_kernel, dim3((kRtActorUsed + kRtFinalElems - 1) / kRtFinalElems), dim3(kRtThreads), 0, st,
                        static_cast<const double *>(a.part), groups, static_cast<const double *>(col), a.G.LA, n, (double)rows->outer,
                        global ? entropy_coef * entropy_share : entropy_coef, log_std, d_head_w, d_head_b, d_log_std, policy_loss, entropy, ess);
@@ -664,6 +670,20 @@ int hns_rnn_actor_head_grad(const float *head_w, const float *head_b, const floa
                             size_t workspace_bytes, void *stream) {
     return hns::rt_actor_entry("hns_rnn_actor_head_grad", head_w, head_b, log_std, rows, action, log_probs_old, advantages, clip_param, entropy_coef, dy,
                                d_head_w, d_head_b, d_log_std, policy_loss, entropy, ess, log_probs, workspace, workspace_bytes, stream, false, 0, 1.0);
+}
+
+size_t hns_rnn_actor_head_agents_workspace_bytes(int64_t outer, int32_t inner, int32_t steps) {
+    if (!hns::rt_shape_ok(outer, inner, steps)) return 0;
+    return hns::rt_actor_agents_ws((long long)outer * inner * steps, inner, inner * steps).bytes;
+}
+
+int hns_rnn_actor_head_grad_agents(const float *head_w, const float *head_b, const float *log_std, const hns_rnn_rows *rows, const float *action,
+                                   const float *log_probs_old, const float *advantages, double clip_param, double entropy_coef, float *dy,
+                                   float *d_head_w, float *d_head_b, float *d_log_std, float *policy_loss, float *entropy, float *ess, float *log_probs,
+                                   void *workspace, size_t workspace_bytes, void *stream) {
+    return hns::rt_actor_entry("hns_rnn_actor_head_grad_agents", head_w, head_b, log_std, rows, action, log_probs_old, advantages, clip_param,
+                               entropy_coef, dy, d_head_w, d_head_b, d_log_std, policy_loss, entropy, ess, log_probs, workspace, workspace_bytes, stream,
+                               false, 0, 1.0, true);
 }
 
 int hns_rnn_actor_head_grad_global(const float *head_w, const float *head_b, const float *log_std, const hns_rnn_rows *rows, const float *action,

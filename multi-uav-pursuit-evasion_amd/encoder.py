@@ -37,9 +37,10 @@ def _shapes(D):
             **{f: (E,) for f in ("ln_w", "ln_b", "out_proj_b", "linear1_b", "linear2_b", "norm1_w", "norm1_b", "norm2_w", "norm2_b")}}
 
 
-def encoder_parameters(params):
+def encoder_parameters(params, stacked=False):
     """The encoder's tensors by hns_policy_net field in FIELDS' order from a mapping of field names (a head's fields are ignored), checked:
-    every tensor but the state_others embedding present, fp32, of the encoder's shapes."""
+    every tensor but the state_others embedding present, fp32, of the encoder's shapes.  stacked (one encoder per agent: DESIGN.md §7.18):
+    every tensor [A, ...] with one A in [1, HNS_MAX_AGENTS], each slice of those shapes."""
     if not hasattr(params, "items"):
         raise TypeError(f"params must map hns_policy_net field names to tensors, not {type(params).__name__}")
     unknown = sorted(k for k in params if k not in FIELDS and k not in _HEAD)
@@ -55,13 +56,38 @@ def encoder_parameters(params):
         if t.dtype != torch.float32:
             raise TypeError(f"encoder parameter {f} must be float32, not {t.dtype}")
     sw = p["embed_self_w"]
-    if sw.dim() != 2 or not 1 <= sw.shape[1] <= abi.HNS_POLICY_MAX_SELF_DIM:
-        raise ValueError(f"encoder: the state_self embedding must be Linear(D, 128) with D in [1, {abi.HNS_POLICY_MAX_SELF_DIM}], not {tuple(sw.shape)}")
-    want = _shapes(int(sw.shape[1]))
+    lead = 1 if stacked else 0
+    if sw.dim() != 2 + lead or not 1 <= sw.shape[-1] <= abi.HNS_POLICY_MAX_SELF_DIM:
+        raise ValueError(f"encoder: the state_self embedding must be Linear(D, 128) with D in [1, {abi.HNS_POLICY_MAX_SELF_DIM}]"
+                         f"{' under a leading agent dimension' if stacked else ''}, not {tuple(sw.shape)}")
+    want = _shapes(int(sw.shape[-1]))
     for f, t in p.items():
-        if tuple(t.shape) != want[f]:
-            raise ValueError(f"encoder parameter {f} must be {want[f]}, not {tuple(t.shape)}")
+        if tuple(t.shape[lead:]) != want[f] or t.dim() != len(want[f]) + lead:
+            raise ValueError(f"encoder parameter {f} must be {('A',) + want[f] if stacked else want[f]}, not {tuple(t.shape)}")
+    if stacked:
+        sizes = sorted({int(t.shape[0]) for t in p.values()})
+        if len(sizes) != 1 or not 1 <= sizes[0] <= abi.HNS_MAX_AGENTS:
+            raise ValueError(f"stacked encoder parameters need one leading agent dimension in [1, {abi.HNS_MAX_AGENTS}], not {sizes}")
+        for f, t in p.items():
+            if not t.is_contiguous():
+                raise ValueError(f"stacked encoder parameter {f} must be contiguous")
     return p
+
+
+def stacked_agents(p):
+    """A of a stacked encoder (one per agent: in_proj_w [A, 384, 128]); None for a single one."""
+    return int(p["in_proj_w"].shape[0]) if p["in_proj_w"].dim() == 3 else None
+
+
+def _entries(p, shape, backward):
+    """(the entry, its workspace query) for these parameters: the shared op's, or for stacked parameters the _agents forms'."""
+    lib = abi.load_library()
+    agents = stacked_agents(p)
+    if agents is None:
+        return (lib.hns_encoder_backward if backward else lib.hns_encoder_forward), lib.hns_encoder_workspace_bytes
+    if agents != shape[2]:
+        raise ValueError(f"the observation has {shape[2]} agents, the stacked encoder {agents}")
+    return (lib.hns_encoder_backward_agents if backward else lib.hns_encoder_forward_agents), lib.hns_encoder_agents_workspace_bytes
 
 
 def _gather(xs, xo, xc, index):
@@ -82,7 +108,8 @@ def _net(p, grads=None):
 
 
 def grad_layout(p):
-    """(offsets by field, floats) of the flat gradient allocation: FIELDS' order, every tensor on a 16-byte boundary."""
+    """(offsets by field, floats) of the flat gradient allocation: FIELDS' order, every tensor — stacked ones whole, [A, ...] — on a 16-byte
+    boundary."""
     offsets, n = {}, 0
     for f, t in p.items():
         offsets[f] = n
@@ -92,15 +119,16 @@ def grad_layout(p):
 
 def device_forward(p, xs, xo, xc, index, shape, workspace=None, out=None):
     """hns_encoder_forward on validated device tensors: features [B, A, 128] (`out`: a contiguous fp32 tensor of that many values, written in
-    place).  `workspace`: a uint8 device tensor of at least hns_encoder_workspace_bytes(rows, ..., 0) bytes, 256-byte aligned."""
-    lib = abi.load_library()
+    place).  `workspace`: a uint8 device tensor of at least hns_encoder_workspace_bytes(rows, ..., 0) bytes, 256-byte aligned.  Stacked
+    parameters ([A, ...]: one encoder per agent, row (b, a) on slice a) go to hns_encoder_forward_agents, with its workspace query."""
+    entry, query = _entries(p, shape, False)
     N, T, A, D, K = shape
     dev = xs.device
     B = index.numel() if index is not None else N * T
     for f, t in p.items():
         if t.data_ptr() % 16:
             raise ValueError(f"encoder parameter {f} must be 16-byte aligned")
-    nbytes = lib.hns_encoder_workspace_bytes(B * A, D, A, K, 0)
+    nbytes = query(B * A, D, A, K, 0)
     if nbytes == 0:
         raise ValueError(f"shape outside the kernel's limits: {B * A} rows, self_dim {D}, {A} agents, {K} cylinders")
     ws = PT.check_workspace(workspace, nbytes, dev) if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -108,16 +136,16 @@ def device_forward(p, xs, xo, xc, index, shape, workspace=None, out=None):
     feats = out if out is not None else torch.empty(B, A, P.EMBED_DIM, dtype=torch.float32, device=dev)
     net = _net(p)
     with torch.cuda.device(dev):
-        rc = lib.hns_encoder_forward(C.byref(net), C.byref(b), D, A, K, feats.data_ptr(), ws.data_ptr(), nbytes,
-                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    abi.check(rc, "hns_encoder_forward")
+        rc = entry(C.byref(net), C.byref(b), D, A, K, feats.data_ptr(), ws.data_ptr(), nbytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    abi.check(rc, entry.__name__)
     return feats
 
 
 def device_backward(p, xs, xo, xc, index, shape, dfeatures, workspace=None, flat=None):
     """hns_encoder_backward on validated device tensors: ({field: gradient}, flat) — every gradient a view of the ONE allocation `flat`
-    (grad_layout; `flat`: the caller's, at least that many fp32 values, 16-byte aligned).  dfeatures: contiguous fp32 [B, A, 128]."""
-    lib = abi.load_library()
+    (grad_layout; `flat`: the caller's, at least that many fp32 values, 16-byte aligned).  dfeatures: contiguous fp32 [B, A, 128].  Stacked
+    parameters go to hns_encoder_backward_agents: every gradient [A, ...], agent a's slice from its own rows."""
+    entry, query = _entries(p, shape, True)
     N, T, A, D, K = shape
     dev = xs.device
     B = index.numel() if index is not None else N * T
@@ -125,7 +153,7 @@ def device_backward(p, xs, xo, xc, index, shape, dfeatures, workspace=None, flat
         raise ValueError(f"d features must be contiguous float32 [{B}, {A}, {P.EMBED_DIM}] on {dev}")
     if dfeatures.data_ptr() % 16:
         dfeatures = dfeatures.clone()
-    nbytes = lib.hns_encoder_workspace_bytes(B * A, D, A, K, 1)
+    nbytes = query(B * A, D, A, K, 1)
     if nbytes == 0:
         raise ValueError(f"shape outside the kernel's limits: {B * A} rows, self_dim {D}, {A} agents, {K} cylinders")
     ws = PT.check_workspace(workspace, nbytes, dev) if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -138,9 +166,9 @@ def device_backward(p, xs, xo, xc, index, shape, dfeatures, workspace=None, flat
     b = PT.fill_batch(abi.HnsCriticBatch, xs, xo, xc, index, shape)
     net, grd = _net(p), _net(p, grads)
     with torch.cuda.device(dev):
-        rc = lib.hns_encoder_backward(C.byref(net), C.byref(b), D, A, K, dfeatures.data_ptr(), C.byref(grd), ws.data_ptr(), nbytes,
-                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    abi.check(rc, "hns_encoder_backward")
+        rc = entry(C.byref(net), C.byref(b), D, A, K, dfeatures.data_ptr(), C.byref(grd), ws.data_ptr(), nbytes,
+                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    abi.check(rc, entry.__name__)
     return grads, flat
 
 

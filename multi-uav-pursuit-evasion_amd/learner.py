@@ -24,6 +24,9 @@ refusing a recurrent policy.
 `PerAgentDeviceLearner` is the same for share_actor: False (one actor per agent): the actor block through
 actor_train.update_actor_per_agent over the stacked tensors, everything else DeviceLearner's.  `DeviceLearner` keeps refusing that configuration.
 
+`PerAgentRecurrentDeviceLearner` is `RecurrentDeviceLearner` for share_actor: False with actor.rnn / critic.rnn (one actor and one actor GRU per
+agent): the actor step through rnn_train.update_actor_rnn_per_agent over the stacked tensors, everything else inherited.
+
 `DeviceLearner._ppo_loop` is the only PPO loop.  A variant overrides what differs and nothing else: the units a permutation draws from
 (`_units`), its update call for one index (`_actor_step`, `_critic_step`), its cached buffers (`_workspaces`), and its optimisers and tensors
 (`_make_actor_opt`, `_make_critic_opt`, `_network_tensors`: checkpoints, buckets and the broadcast are written once over them).
@@ -489,7 +492,7 @@ class RecurrentDeviceLearner(DeviceLearner):
         info row    hns_learner_info, INFO_KEYS, one copy to the host
 
     Refused: group= (data-parallel recurrent training is DataParallelRecurrentLearner's), the configurations RecurrentDevicePolicy refuses, a non-recurrent device_policy, a
-    per_agent device_policy or stacked actor tensors (recurrent per-agent actors are collected and evaluated, not yet trained: DESIGN.md §7.17), a
+    per_agent device_policy or stacked actor tensors (recurrent per-agent actors are PerAgentRecurrentDeviceLearner's: DESIGN.md §7.18), a
     rollout whose T train_seq_len does not divide (or whose storage was cut with another segment length)."""
 
     def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, generator=None, device_policy=None, agent_name="drone", group=None):
@@ -498,24 +501,32 @@ class RecurrentDeviceLearner(DeviceLearner):
         if device_policy is not None and not getattr(device_policy, "recurrent", False):
             raise P.PolicyConfigError("RecurrentDeviceLearner needs a RecurrentDevicePolicy (a non-recurrent policy is DeviceLearner's)")
         if getattr(device_policy, "per_agent", False) or P.is_stacked(actor):
-            raise P.PolicyConfigError(f"{type(self).__name__} updates ONE shared recurrent actor: the update of recurrent per-agent actors (share_actor: "
-                                      "False with actor.rnn; PerAgentRecurrentDevicePolicy collects and evaluates them) is an open item "
+            raise P.PolicyConfigError(f"{type(self).__name__} updates ONE shared recurrent actor: recurrent per-agent actors (share_actor: False with "
+                                      "actor.rnn) are PerAgentRecurrentDeviceLearner's; their data-parallel update is an open item "
                                       "(DESIGN-open-items.md #13)")
+        self._build(actor, critic, cfg, tp_net, value_normalizer, agent_name, generator, device_policy, P.RecurrentDevicePolicy)
+
+    stacked_actor = False                                        # PerAgentRecurrentDeviceLearner: the actor's tensors are stacked over the agents
+
+    def _build(self, actor, critic, cfg, tp_net, value_normalizer, agent_name, generator, device_policy, policy_class):
+        """What follows the refusals of the constructor's own arguments: the settings, the segment length, the optimisers, the policy, the
+        two networks' buffers."""
         self._configure(actor, critic, cfg, tp_net, value_normalizer, agent_name, generator)
         self.train_seq_len = rnn_train.train_seq_len(cfg)
         if not 1 <= self.train_seq_len <= abi.HNS_GRU_MAX_STEPS:
             raise ValueError(f"actor.rnn.train_seq_len must be in [1, {abi.HNS_GRU_MAX_STEPS}], not {self.train_seq_len}")
-        self._make_networks_state(device_policy, P.RecurrentDevicePolicy)
+        self._make_networks_state(device_policy, policy_class)
         self._rnn_ws = (rnn_train.RnnWorkspace(), rnn_train.RnnWorkspace())
 
     def _make_actor_opt(self):
-        return rnn_train.make_optimizer(self.actor, self.cfg, actor=True)
+        return rnn_train.make_optimizer(self.actor, self.cfg, actor=True, stacked=self.stacked_actor)
 
     def _make_critic_opt(self):
         return rnn_train.make_optimizer(self.critic, self.cfg, actor=False)
 
     def _network_tensors(self):
-        return tuple(rnn_train.flat_parameters(rnn_train.network_parameters(net, actor)) for net, actor in ((self.actor, True), (self.critic, False)))
+        return tuple(rnn_train.flat_parameters(rnn_train.network_parameters(net, actor, actor and self.stacked_actor))
+                     for net, actor in ((self.actor, True), (self.critic, False)))
 
     def release(self):
         super().release()
@@ -584,6 +595,39 @@ class RecurrentDeviceLearner(DeviceLearner):
     def _critic_step(self, idx, obs, state_value, ret, rk, **kw):
         return rnn_train.update_critic_rnn(self.critic, *obs, rk["critic_rnn_state"], rk["is_init"], state_value, ret, self.critic_opt, segment=idx,
                                            cfg=self.cfg, seq_len=self.train_seq_len, **kw)
+
+
+class PerAgentRecurrentDeviceLearner(RecurrentDeviceLearner):
+    """MAPPOPolicy's training half with share_actor: False AND actor.rnn / critic.rnn (one actor and one actor GRU per agent, the critic and
+    its GRU shared): `RecurrentDeviceLearner`'s blocks in its order, with the actor step through
+    rnn_train.update_actor_rnn_per_agent — the encoder op, the GRU op and the head entry on the stacked tensors, ONE gradient bucket, ONE norm
+    and ONE ClippedAdam step over the 29 stacked tensors per minibatch.  The critic block, the bootstrap value, the targets, the predictor,
+    the info row and state_dict are inherited unchanged.
+
+    actor: the STACKED actor's parameters with their `rnn.*` leaves stacked too (every tensor [A, ...]: the reference's actor_params;
+    "actor_params" of state_dict()), live tensors updated in place; device_policy: a PerAgentRecurrentDevicePolicy over the same tensors
+    (built when None).  Refused before anything is built: group= (NotImplementedError: the data-parallel form is an open item), a
+    device_policy that is not both per-agent and recurrent, actor tensors that are not stacked, share_actor: True, and whatever
+    PerAgentRecurrentDevicePolicy and the cfg checks of RecurrentDeviceLearner refuse (PolicyConfigError)."""
+    stacked_actor = True
+
+    def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, generator=None, device_policy=None, agent_name="drone", group=None):
+        if group is not None:
+            raise NotImplementedError("PerAgentRecurrentDeviceLearner takes no group=: data-parallel training of recurrent per-agent actors is an "
+                                      "open item (DESIGN-open-items.md #13)")
+        if device_policy is not None and not (getattr(device_policy, "per_agent", False) and getattr(device_policy, "recurrent", False)):
+            raise P.PolicyConfigError("PerAgentRecurrentDeviceLearner needs a PerAgentRecurrentDevicePolicy (a shared recurrent actor is "
+                                      "RecurrentDeviceLearner's, per-agent actors without an rnn PerAgentDeviceLearner's)")
+        if not P.is_stacked(actor):
+            raise P.PolicyConfigError("PerAgentRecurrentDeviceLearner: the actor's parameters have no leading agent dimension (a shared recurrent "
+                                      "actor is RecurrentDeviceLearner's)")
+        P.check_config_per_agent(P.cfg_without(cfg, "actor.rnn", "critic.rnn"))
+        shared = P.cfg_without(cfg, "share_actor")               # what the shared critic's functions (and policy.check_config behind them) take
+        self._build(actor, critic, shared, tp_net, value_normalizer, agent_name, generator, device_policy, P.PerAgentRecurrentDevicePolicy)
+
+    def _actor_step(self, idx, obs, action, log_probs, adv, rk, **kw):
+        return rnn_train.update_actor_rnn_per_agent(self.actor, *obs, rk["actor_rnn_state"], rk["is_init"], action, log_probs, adv, self.actor_opt,
+                                                    segment=idx, cfg=self.cfg, seq_len=self.train_seq_len, **kw)
 
 
 class DataParallelRecurrentLearner(RecurrentDeviceLearner):

@@ -831,8 +831,8 @@ class PerAgentRecurrentDevicePolicy(RecurrentDevicePolicy):
     [E, A, 128], and row (e, a) is bit for bit RecurrentDevicePolicy's with agent a's slices as the shared actor.  `scale` is [A, 4].
     Refused with PolicyConfigError before anything is built: whatever RecurrentDevicePolicy refuses except share_actor: False;
     share_actor: True; tensors that are not stacked or whose leading sizes disagree; an rnn on only one of the two networks; a critic with
-    stacked tensors; an observation with another number of agents (ValueError).  It is not trained on the device yet: every learner
-    refuses it (DESIGN-open-items.md #13)."""
+    stacked tensors; an observation with another number of agents (ValueError).  It is trained by
+    learner.PerAgentRecurrentDeviceLearner."""
     per_agent = True
 
     def __init__(self, actor_params, critic, cfg=None, device=None, seed=0, agent_name="drone"):

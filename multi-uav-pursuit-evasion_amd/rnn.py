@@ -32,9 +32,9 @@ _SHAPES = {"weight_ih": (3 * H, H), "weight_hh": (3 * H, H), "bias_ih": (3 * H,)
 _N_FIXED = 4                                                   # _Gru.apply's arguments in front of the parameter tensors
 
 
-def gru_parameters(params):
+def gru_parameters(params, stacked=False):
     """The six tensors by hns_gru_net field in FIELDS' order from a mapping of field names, checked: all present, fp32, contiguous, of the
-    GRU's shapes."""
+    GRU's shapes.  stacked (one GRU per agent: DESIGN.md §7.18): every tensor [A, ...] with one A in [1, HNS_MAX_AGENTS]."""
     if not hasattr(params, "items"):
         raise TypeError(f"params must map hns_gru_net field names to tensors, not {type(params).__name__}")
     unknown = sorted(k for k in params if k not in FIELDS)
@@ -49,11 +49,18 @@ def gru_parameters(params):
             raise TypeError(f"gru parameter {f} must be a tensor, not {type(t).__name__}")
         if t.dtype != torch.float32:
             raise TypeError(f"gru parameter {f} must be float32, not {t.dtype}")
-        if tuple(t.shape) != _SHAPES[f]:
-            raise ValueError(f"gru parameter {f} must be {_SHAPES[f]}, not {tuple(t.shape)}")
+        if tuple(t.shape[1:] if stacked else t.shape) != _SHAPES[f] or (stacked and t.dim() != len(_SHAPES[f]) + 1):
+            raise ValueError(f"gru parameter {f} must be {('A',) + _SHAPES[f] if stacked else _SHAPES[f]}, not {tuple(t.shape)}")
         if not t.is_contiguous():
             raise ValueError(f"gru parameter {f} must be contiguous")
+    if stacked and (len({t.shape[0] for t in p.values()}) != 1 or not 1 <= p[FIELDS[0]].shape[0] <= abi.HNS_MAX_AGENTS):
+        raise ValueError(f"stacked gru parameters need one leading agent dimension in [1, {abi.HNS_MAX_AGENTS}], not {sorted({t.shape[0] for t in p.values()})}")
     return p
+
+
+def stacked_agents(p):
+    """A of a stacked GRU (one per agent: weight_ih [A, 384, 128]); None for a single one."""
+    return p["weight_ih"].shape[0] if p["weight_ih"].dim() == 3 else None
 
 
 def restatement(p, x, h0, is_init):
@@ -93,18 +100,28 @@ def _seq(x4, h0, init):
     return s
 
 
-def grad_layout():
-    """(offsets by field, floats) of the flat gradient allocation: FIELDS' order (every size is a multiple of four floats)."""
+def grad_layout(agents=None):
+    """(offsets by field, floats) of the flat gradient allocation: FIELDS' order (every size is a multiple of four floats).  agents: A of a
+    stacked GRU — every tensor A times the size, in the same order."""
     offsets, n = {}, 0
     for f in FIELDS:
         offsets[f] = n
-        n += _SHAPES[f][0] * (_SHAPES[f][1] if len(_SHAPES[f]) > 1 else 1)
+        n += (agents or 1) * _SHAPES[f][0] * (_SHAPES[f][1] if len(_SHAPES[f]) > 1 else 1)
     return offsets, n
 
 
-def _views(flat):
-    offsets, _ = grad_layout()
-    return {f: flat[offsets[f]:offsets[f] + torch.Size(_SHAPES[f]).numel()].view(_SHAPES[f]) for f in FIELDS}
+def _views(flat, agents=None):
+    offsets, _ = grad_layout(agents)
+    lead = (agents,) if agents else ()
+    return {f: flat[offsets[f]:offsets[f] + torch.Size(lead + _SHAPES[f]).numel()].view(lead + _SHAPES[f]) for f in FIELDS}
+
+
+def _agents_of(p, x4):
+    """A of stacked parameters, checked against x4's agent dimension; None for a single GRU."""
+    agents = stacked_agents(p)
+    if agents is not None and agents != x4.shape[1]:
+        raise ValueError(f"x has {x4.shape[1]} agents (dimension 1), the stacked GRU {agents}")
+    return agents
 
 
 def _stream(dev):
@@ -126,9 +143,11 @@ def _buffer(t, shape, what, dev, strides=None):
 
 def device_forward(p, x4, h0, init, keep, out=None, h_last=None, h_hist=None):
     """hns_gru_forward on validated device tensors: (out with x4's strides, h_last [S, 128], h_hist [S, L, 128] or None).  out, h_last,
-    h_hist: the caller's buffers (of those shapes; out with x4's strides) instead of tensors allocated per call."""
+    h_hist: the caller's buffers (of those shapes; out with x4's strides) instead of tensors allocated per call.  Stacked parameters
+    ([A, ...]: one GRU per agent, sequence (b, a) on slice a) go to hns_gru_forward_agents."""
     lib = abi.load_library()
     B, A, L, _ = x4.shape
+    entry = lib.hns_gru_forward if _agents_of(p, x4) is None else lib.hns_gru_forward_agents
     dev = x4.device
     for f, t in p.items():
         if t.data_ptr() % 16:
@@ -141,39 +160,43 @@ def device_forward(p, x4, h0, init, keep, out=None, h_last=None, h_hist=None):
         hist = None
     net, seq = _net(p), _seq(x4, h0, init)
     with torch.cuda.device(dev):
-        rc = lib.hns_gru_forward(C.byref(net), C.byref(seq), out.data_ptr(), h_last.data_ptr(), hist.data_ptr() if keep else None, None, 0, _stream(dev))
-    abi.check(rc, "hns_gru_forward")
+        rc = entry(C.byref(net), C.byref(seq), out.data_ptr(), h_last.data_ptr(), hist.data_ptr() if keep else None, None, 0, _stream(dev))
+    abi.check(rc, entry.__name__)
     return out, h_last, hist
 
 
 def device_backward(p, x4, h0, init, hist, dout, dh_last, want_dh0, workspace=None, flat=None, dx=None):
     """hns_gru_backward on validated device tensors: ({field: gradient} — views of one allocation, dx with x4's strides, dh0 or None).
     workspace: a uint8 device tensor of at least hns_gru_workspace_bytes(S, L, 1) bytes, 256-byte aligned; flat: the gradients' flat fp32
-    allocation (grad_layout's floats, 16-byte aligned); dx: a buffer with x4's shape and strides — the caller's instead of per-call ones."""
+    allocation (grad_layout's floats, 16-byte aligned); dx: a buffer with x4's shape and strides — the caller's instead of per-call ones.
+    Stacked parameters go to hns_gru_backward_agents: the workspace is hns_gru_agents_workspace_bytes(B, A, L, 1), the gradients [A, ...]
+    in grad_layout(A)'s floats."""
     lib = abi.load_library()
     B, A, L, _ = x4.shape
     dev = x4.device
-    nbytes = lib.hns_gru_workspace_bytes(B * A, L, 1)
+    agents = _agents_of(p, x4)
+    entry = lib.hns_gru_backward if agents is None else lib.hns_gru_backward_agents
+    nbytes = lib.hns_gru_workspace_bytes(B * A, L, 1) if agents is None else lib.hns_gru_agents_workspace_bytes(B, A, L, 1)
     if workspace is None:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     else:
         ws = workspace
         if not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < nbytes or ws.data_ptr() % 256:
             raise ValueError(f"workspace must be a contiguous, 256-byte aligned uint8 tensor of at least {nbytes} bytes on {dev}")
-    n = grad_layout()[1]
+    n = grad_layout(agents)[1]
     if flat is None:
         flat = torch.empty(n, dtype=torch.float32, device=dev)
     elif (not torch.is_tensor(flat) or flat.dtype != torch.float32 or flat.device != dev or flat.dim() != 1 or flat.numel() < n or not flat.is_contiguous()
           or flat.data_ptr() % 16):
         raise ValueError(f"flat must be a contiguous 16-byte aligned float32 vector of at least {n} values on {dev}")
-    grads = _views(flat)
+    grads = _views(flat, agents)
     dx = _buffer(dx, x4.shape, "dx", dev, x4.stride()) if dx is not None else torch.empty_strided(x4.shape, x4.stride(), dtype=torch.float32, device=dev)
     dh0 = torch.empty(B * A, H, dtype=torch.float32, device=dev) if want_dh0 else None
     net, grd, seq = _net(p), _net(p, grads), _seq(x4, h0, init)
     with torch.cuda.device(dev):
-        rc = lib.hns_gru_backward(C.byref(net), C.byref(seq), hist.data_ptr(), dout.data_ptr(), dh_last.data_ptr() if dh_last is not None else None,
-                                  C.byref(grd), dx.data_ptr(), dh0.data_ptr() if want_dh0 else None, ws.data_ptr(), nbytes, _stream(dev))
-    abi.check(rc, "hns_gru_backward")
+        rc = entry(C.byref(net), C.byref(seq), hist.data_ptr(), dout.data_ptr(), dh_last.data_ptr() if dh_last is not None else None,
+                   C.byref(grd), dx.data_ptr(), dh0.data_ptr() if want_dh0 else None, ws.data_ptr(), nbytes, _stream(dev))
+    abi.check(rc, entry.__name__)
     return grads, dx, dh0
 
 

@@ -23,6 +23,11 @@ SUM all-reduce of five fp64 values, `hns_rnn_critic_head_grad_global`) — every
 before its norm is taken.  `value_loss_sums_rnn` is the critic's forward half; its forward state lets `value_loss_and_grad_rnn(forward=)` go on
 from y without a second encoder and GRU pass.
 
+The `*_per_agent` functions are the actor's update with share_actor: False (one actor AND one actor GRU per agent: the reference's stacked
+`actor_params`, every tensor [A, ...]) through the SAME path: the encoder op and the GRU op take the stacked tensors
+(`hns_encoder_*_agents`, `hns_gru_*_agents`), the head entry is `hns_rnn_actor_head_grad_agents`, and ONE bucket, ONE norm and ONE ClippedAdam
+step run over the 29 stacked tensors.  The critic stays shared: `update_critic_rnn`, untouched.  No data-parallel form.
+
 CPU tensors run the same statements in torch: `policy_train.encoder`, `rnn.restatement`, and `actor_head` / `critic_head` — the head and the
 loss written out with their hand-derived dy (what the kernels compute, not autograd of another formula); the encoder's and the GRU's
 gradients come from autograd over the recomputed restatements, as in `encoder.encode` and `rnn.gru` (tests — not the hot path)."""
@@ -45,14 +50,23 @@ CriticSumsRnn = collections.namedtuple("CriticSumsRnn", ["sums", "values", "forw
 Network = collections.namedtuple("Network", ["encoder", "gru", "head"])        # three {field: tensor} mappings of one network
 
 
-def network_parameters(network, actor):
+def network_parameters(network, actor, stacked=False):
     """Network(encoder, gru, head) of a recurrent actor (`actor` true) or critic from the reference's names, as RecurrentDevicePolicy parses
     them: the encoder's tensors by hns_policy_net field in encoder.FIELDS' order, the GRU's six by hns_gru_net field, the head's (head_w,
-    head_b and the actor's log_std).  Their concatenation in this order is the optimiser's and the gradient bucket's order."""
+    head_b and the actor's log_std).  Their concatenation in this order is the optimiser's and the gradient bucket's order.  stacked (one
+    actor per agent, as PerAgentRecurrentDevicePolicy parses it): every tensor [A, ...] with one A."""
     word = "actor" if actor else "critic"
-    rest, gru = P.split_rnn(network, word)
-    p = P.parse_parameters(rest, P.ACTOR_NAMES if actor else P.CRITIC_NAMES, word)
-    enc = encoder.encoder_parameters({f: p[f] for f in encoder.FIELDS if f in p})
+    if stacked:
+        if not actor:
+            raise P.PolicyConfigError("critic: the critic is shared; only the actor's tensors are stacked over the agents")
+        rest, gru, A_rnn = P.split_rnn(network, word, stacked=True)
+        p, A = P.parse_parameters(rest, P.ACTOR_NAMES, word, stacked=True)
+        if A != A_rnn:
+            raise P.PolicyConfigError(f"actor: {A} stacked actors with {A_rnn} stacked GRUs")
+    else:
+        rest, gru = P.split_rnn(network, word)
+        p = P.parse_parameters(rest, P.ACTOR_NAMES if actor else P.CRITIC_NAMES, word)
+    enc = encoder.encoder_parameters({f: p[f] for f in encoder.FIELDS if f in p}, stacked)
     head = {f: p[f] for f in ("head_w", "head_b") + (("log_std",) if actor else ())}
     return Network(enc, gru, head)
 
@@ -61,12 +75,24 @@ def flat_parameters(net):
     return [*net.encoder.values(), *net.gru.values(), *net.head.values()]
 
 
-def make_optimizer(network, cfg=None, actor=True):
+def make_optimizer(network, cfg=None, actor=True, stacked=False):
     """The reference's actor_opt / critic_opt over ALL of a recurrent network's tensors (encoder, rnn, head) as a ClippedAdam: cfg is the
-    algo cfg (actor.lr / critic.lr, max_grad_norm); the refusals are actor_train.actor_cfg's / critic_train.critic_cfg's without the rnn one."""
+    algo cfg (actor.lr / critic.lr, max_grad_norm); the refusals are actor_train.actor_cfg's / critic_train.critic_cfg's without the rnn one
+    (`stacked`: actor_cfg_per_agent's — share_actor must be False)."""
     sub = PT.getter(PT.getter(cfg)("actor" if actor else "critic", None))
-    (actor_train.actor_cfg if actor else critic_train.critic_cfg)(P.cfg_without(cfg, "actor.rnn", "critic.rnn"))
-    return ClippedAdam(flat_parameters(network_parameters(network, actor)), lr=float(sub("lr", 5e-4)), max_grad_norm=PT.getter(cfg)("max_grad_norm", 10.0))
+    rest = P.cfg_without(cfg, "actor.rnn", "critic.rnn")
+    if actor:
+        actor_train.actor_cfg(rest, per_agent=stacked)
+    else:
+        critic_train.critic_cfg(rest)
+    return ClippedAdam(flat_parameters(network_parameters(network, actor, stacked)), lr=float(sub("lr", 5e-4)),
+                       max_grad_norm=PT.getter(cfg)("max_grad_norm", 10.0))
+
+
+def make_optimizer_per_agent(actor, cfg=None):
+    """`make_optimizer` over the 29 STACKED tensors of one recurrent actor per agent: ONE Adam and one clip over all agents' parameters, as the
+    reference's actor_opt."""
+    return make_optimizer(actor, cfg, actor=True, stacked=True)
 
 
 # ---- the head and the loss, restated: any dtype (the tests run them in fp64 against autograd of the reference's statements)
@@ -74,10 +100,15 @@ def actor_head(head_w, head_b, log_std, y, action, log_probs_old, advantages, cl
     """hns_rnn_actor_head_grad's statements on gathered rows: y [B, L, A, 128], action [B, L, A, 4], log_probs_old / advantages [B, L, A].
     Returns a dict: dy [B, L, A, 128], d_head_w, d_head_b, d_log_std, policy_loss, entropy, ess (0-dim), log_probs [B, L, A].
     `global_rows`: hns_rnn_actor_head_grad_global's — every mean divides by the union's row count, policy_loss is this part's share and
-    d_log_std takes `entropy_share` of the entropy term's constant gradient; ess stays the part's own."""
+    d_log_std takes `entropy_share` of the entropy term's constant gradient; ess stays the part's own.
+    One head per agent (hns_rnn_actor_head_grad_agents): head_w [A, 4, 128], head_b / log_std [A, 4] — row (b, t, a) runs on slice a, the
+    gradients are stacked the same way, entropy is the mean over the agents of each agent's and every d_log_std[a] takes -entropy_coef / A."""
     B = y.shape[0]
     n = float(y.shape[0] * y.shape[1] * y.shape[2]) if global_rows is None else float(global_rows)
-    mu = y @ head_w.t() + head_b
+    per_agent = head_w.dim() == 3
+    if per_agent and global_rows is not None:
+        raise NotImplementedError("one head per agent has no data-parallel form")
+    mu = torch.einsum("blah,aoh->blao", y, head_w) + head_b if per_agent else y @ head_w.t() + head_b
     # logp is formed in fp64 from the fp32 mean (its rounding is the ratio's relative error), as the kernel forms it
     iv64 = torch.exp(-2.0 * log_std.double())
     dm64 = action.double() - mu.double()
@@ -93,6 +124,11 @@ def actor_head(head_w, head_b, log_std, y, action, log_probs_old, advantages, cl
     dmu = dlogp * (dm64 * iv64).to(y.dtype)
     flat = lambda t: t.reshape(-1, t.shape[-1])                  # noqa: E731
     ess = (2 * ratio.logsumexp(0) - (2 * ratio).logsumexp(0)).exp().mean() / B
+    if per_agent:
+        A = head_w.shape[0]
+        return {"dy": torch.einsum("blao,aoh->blah", dmu, head_w), "d_head_w": torch.einsum("blao,blah->aoh", dmu, y), "d_head_b": dmu.sum((0, 1)),
+                "d_log_std": (dlogp * (z2 - 1.0)).sum((0, 1)) - entropy_coef / A, "policy_loss": -float(P.ACTION_DIM) * torch.minimum(s1, s2).mean(),
+                "entropy": (0.5 + LOG_SQRT_2PI + log_std).sum(-1).mean(), "ess": ess, "log_probs": logp}
     return {"dy": dmu @ head_w, "d_head_w": flat(dmu).t() @ flat(y), "d_head_b": flat(dmu).sum(0),
             "d_log_std": flat(dlogp * (z2 - 1.0)).sum(0) - (entropy_coef if global_rows is None else entropy_coef * entropy_share),
             "policy_loss": -float(P.ACTION_DIM) * (torch.minimum(s1, s2).mean() if global_rows is None else torch.minimum(s1, s2).sum() / n), "entropy": (0.5 + LOG_SQRT_2PI + log_std).sum(), "ess": ess,
@@ -168,10 +204,11 @@ class RnnWorkspace:
         self._t = {}
 
 
-def make_bucket(network, actor):
+def make_bucket(network, actor, stacked=False):
     """The gradient bucket of a recurrent network for `bucket=`: ONE flat buffer behind the .grad of the encoder's, the GRU's and the head's
-    tensors, in network_parameters' order.  A caller that makes many calls keeps one (the learner does); a call without one makes its own."""
-    return PT.GradBucket(flat_parameters(network_parameters(network, actor)))
+    tensors (`stacked`: the 29 stacked tensors of one actor per agent), in network_parameters' order.  A caller that makes many calls keeps
+    one (the learner does); a call without one makes its own."""
+    return PT.GradBucket(flat_parameters(network_parameters(network, actor, stacked)))
 
 
 def _bucket(net, bucket):
@@ -189,8 +226,11 @@ def _bucket(net, bucket):
 def _prepare(word, net, obs, state, is_init, per_row, segment, seq_len, check_index):
     """The checks every entry shares; returns (xs, xo, xc, shape, segment ids [B], L, segments in the rollout)."""
     xs, xo, xc = PT.as_rollout(*obs)
-    shape = PT.validate(word, net.encoder, xs, xo, xc, per_row, None, False)
+    agents = encoder.stacked_agents(net.encoder)
+    shape = PT.validate(word, net.encoder if agents is None else P.agent_slice(net.encoder, 0), xs, xo, xc, per_row, None, False)
     N, T, A, _, _ = shape
+    if agents is not None and agents != A:
+        raise ValueError(f"the observation has {A} agents, the stacked {word} {agents}")
     L = int(seq_len)
     if not 1 <= L <= abi.HNS_GRU_MAX_STEPS or T % L:
         raise ValueError(f"the segment length {L} must be in [1, {abi.HNS_GRU_MAX_STEPS}] and divide the rollout's {T} steps")
@@ -256,10 +296,17 @@ def _torch_forward(net, xs, xo, xc, shape, segment, L, NS, state, is_init, per_r
     enc = {f: t.detach().requires_grad_(True) for f, t in net.encoder.items()}
     gru = {f: t.detach().requires_grad_(True) for f, t in net.gru.items()}
     with torch.enable_grad():
-        feats = PT.encoder(enc, *encoder._gather(xs, xo, xc, idx))                                   # [B L, A, 128]
-        x = feats.view(B, L, A, H).transpose(1, 2).reshape(B * A, L, H)
-        out, _ = rnn.restatement(gru, x, h0, flags.to(x.dtype))
-        y = out.view(B, A, L, H).transpose(1, 2)                                                     # [B, L, A, 128]
+        if encoder.stacked_agents(enc) is None:
+            feats = PT.encoder(enc, *encoder._gather(xs, xo, xc, idx))                               # [B L, A, 128]
+            x = feats.view(B, L, A, H).transpose(1, 2).reshape(B * A, L, H)
+            out, _ = rnn.restatement(gru, x, h0, flags.to(x.dtype))
+            y = out.view(B, A, L, H).transpose(1, 2)                                                 # [B, L, A, 128]
+        else:                                                    # one actor per agent: agent a's rows and sequences on slice a
+            gs, go, gc = encoder._gather(xs, xo, xc, idx)
+            feats = torch.stack([PT.encoder(P.agent_slice(enc, a), gs[:, a], go[:, a] if go is not None else None, gc[:, a]).reshape(B * L, H)
+                                 for a in range(A)], 1)
+            x, h4, f4 = feats.view(B, L, A, H), h0.view(B, A, H), flags.view(B, A, L).to(feats.dtype)
+            y = torch.stack([rnn.restatement(P.agent_slice(gru, a), x[:, :, a], h4[:, a], f4[:, a])[0] for a in range(A)], 2)
     return y, [*enc.values(), *gru.values()], rows
 
 
@@ -286,7 +333,8 @@ def _device_forward_to_y(net, xs, xo, xc, shape, segment, L, NS, state, is_init,
     # a bad id is clamped for the encoder and the two gathers (finite features, a stored state): its rows are dead in the head entry, which
     # takes the ids as they are, so dy, hence dx, is zero there and the segment adds nothing to any gradient
     index = _step_index(segment.clamp(0, NS - 1), L)
-    nb = lib.hns_encoder_workspace_bytes(B * L * A, D, A, K, 1)
+    stacked = encoder.stacked_agents(net.encoder) is not None
+    nb = (lib.hns_encoder_agents_workspace_bytes if stacked else lib.hns_encoder_workspace_bytes)(B * L * A, D, A, K, 1)
     if nb == 0:
         raise ValueError(f"shape outside the kernels' limits: {B * L * A} rows, self_dim {D}, {A} agents, {K} cylinders")
     ews = ws.bytes("encoder", nb, dev)
@@ -317,8 +365,9 @@ def _device_backward(net, bucket, xs, xo, xc, shape, index, ews, x4, h0, flags, 
     dev = xs.device
     B, A, L, _ = x4.shape
     n_enc = encoder.grad_layout(net.encoder)[1]
-    n_gru = rnn.grad_layout()[1]
-    gws = ws.bytes("gru", abi.load_library().hns_gru_workspace_bytes(B * A, L, 1), dev)
+    agents, lib = rnn.stacked_agents(net.gru), abi.load_library()
+    n_gru = rnn.grad_layout(agents)[1]
+    gws = ws.bytes("gru", lib.hns_gru_workspace_bytes(B * A, L, 1) if agents is None else lib.hns_gru_agents_workspace_bytes(B, A, L, 1), dev)
     dxbuf = ws.floats("dx", (B * L, A, H), dev)
     rnn.device_backward(net.gru, x4, h0, flags, hist, dy, None, False, workspace=gws, flat=bucket.flat[n_enc:n_enc + n_gru],
                         dx=dxbuf.view(B, L, A, H).transpose(1, 2))
@@ -341,8 +390,9 @@ def _forward_key(net, xs, segment, L, ws):
 # tensors; keys, row_key: the scalars and the per-row result in the restatement's dict, in the result's order (no keys: the forward-only head
 # of value_loss_sums_rnn); restate(head parameters, y, *gathered rows): the CPU statements; launch(lib, head parameters, hns_rnn_rows, the
 # per-row tensors, dy, the head's gradient views, the result slots, head workspace, its bytes, stream, (B, L, A)): the C call, returning
-# the per-row result; check(device): the caller's refusals that need the prepared tensors.
-_Head = collections.namedtuple("_Head", ["actor", "per_row", "keys", "row_key", "restate", "launch", "check"], defaults=(None,))
+# the per-row result; check(device): the caller's refusals that need the prepared tensors; stacked: one actor per agent — the network's
+# tensors are the stacked ones and the head entry the _agents form.
+_Head = collections.namedtuple("_Head", ["actor", "per_row", "keys", "row_key", "restate", "launch", "check", "stacked"], defaults=(None, False))
 
 
 def _run(head, network, obs, state, is_init, segment, seq_len, check_index, workspace=None, out=None, bucket=None, global_rows=None, group=None,
@@ -351,7 +401,7 @@ def _run(head, network, obs, state, is_init, segment, seq_len, check_index, work
     (or go on from `forward`), the head, backward from dy into the bucket, the norm.  Returns (the head's scalars, grad_norm, its per-row
     result) — or, for the forward-only head, (sums, values, the forward state)."""
     word = "actor" if head.actor else "critic"
-    net = network_parameters(network, head.actor)
+    net = network_parameters(network, head.actor, head.stacked)
     xs, xo, xc, shape, segment, L, NS = _prepare(word, net, obs, state, is_init, head.per_row, segment, seq_len, check_index and forward is None)
     A, B, glob = shape[2], segment.numel(), global_rows is not None
     if glob or group is not None:
@@ -387,7 +437,8 @@ def _run(head, network, obs, state, is_init, segment, seq_len, check_index, work
     per_row = [t.contiguous() for _, t, _ in head.per_row]
     fwd = forward.state[0] if forward is not None else _device_forward_to_y(net, xs, xo, xc, shape, segment, L, NS, state, is_init, ws)
     index, ews, x4, h0, flags, y, hist, view = fwd
-    nbytes = (lib.hns_rnn_actor_head_workspace_bytes if head.actor else lib.hns_rnn_critic_head_workspace_bytes)(B, A, L)
+    nbytes = (lib.hns_rnn_actor_head_agents_workspace_bytes if head.stacked else
+              lib.hns_rnn_actor_head_workspace_bytes if head.actor else lib.hns_rnn_critic_head_workspace_bytes)(B, A, L)
     call = (lib, net.head, _rows_struct(y, segment, NS), per_row)
     tail = (ws.bytes("head", nbytes, dev), nbytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), (B, L, A))
     if not head.keys:
@@ -422,6 +473,29 @@ def policy_loss_and_grad_rnn(actor, obs_self, obs_others, obs_cylinders, actor_r
     the ranks both add up to the union's.  `entropy_share`: the part of the entropy term's gradient this rank adds (1 / world).  ess stays
     this rank's own.  `bucket` is then the network's GradBucket and grad_norm its norm (None without one); `group`: the bucket is all-reduced
     (SUM) over it first."""
+    return _policy_loss_and_grad(False, actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, segment,
+                                 seq_len, clip_param, entropy_coef, check_index, workspace, out, bucket, global_rows, entropy_share, group)
+
+
+def policy_loss_and_grad_rnn_per_agent(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages,
+                                       segment=None, seq_len=16, clip_param=0.1, entropy_coef=0.001, check_index=True, workspace=None, out=None,
+                                       bucket=None, global_rows=None, group=None):
+    """`policy_loss_and_grad_rnn` with one actor per agent (MAPPOPolicy.update_actor with share_actor: False on a recurrent minibatch,
+    mappo.py:281-284): `actor` holds the STACKED tensors ([A, ...] each, the `rnn.*` leaves among them), row (b, t, a) and sequence (b, a) run
+    on slice a, and every stacked tensor's .grad is as zero_grad() + backward() leave it (agent a's slice from its own rows).  policy_loss is
+    -4 times the mean over ALL B L A rows, entropy the mean over the agents of each agent's (each d log_std takes -entropy_coef / A), ess as
+    for the shared actor, grad_norm ONE norm over all 29 stacked tensors.  Arguments, layouts, `workspace`, `out` and `bucket`
+    (make_bucket(stacked=True)) as `policy_loss_and_grad_rnn`; `is_init` is env-level and holds for all agents.  No data-parallel form:
+    `global_rows=` / `group=` raise NotImplementedError."""
+    if global_rows is not None or group is not None:
+        raise NotImplementedError("one recurrent actor per agent has no data-parallel form yet (DESIGN-open-items.md #13)")
+    return _policy_loss_and_grad(True, actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, segment,
+                                 seq_len, clip_param, entropy_coef, check_index, workspace, out, bucket, None, 1.0, None)
+
+
+def _policy_loss_and_grad(stacked, actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, segment,
+                          seq_len, clip_param, entropy_coef, check_index, workspace, out, bucket, global_rows, entropy_share, group):
+    """policy_loss_and_grad_rnn and its _per_agent form: the `_Head` of the shared or the stacked head through `_run`."""
     if not clip_param >= 0:
         raise ValueError("clip_param must be >= 0")
     if not math.isfinite(float(entropy_share)):
@@ -433,7 +507,7 @@ def policy_loss_and_grad_rnn(actor, obs_self, obs_others, obs_cylinders, actor_r
 
     def launch(lib, p, rows, per_row, dy, g, scal, hws, nbytes, st, dims):
         log_probs = torch.empty(*dims, 1, dtype=torch.float32, device=hws.device)
-        entry, more = (lib.hns_rnn_actor_head_grad, ()) if global_rows is None else \
+        entry, more = (lib.hns_rnn_actor_head_grad_agents if stacked else lib.hns_rnn_actor_head_grad, ()) if global_rows is None else \
             (lib.hns_rnn_actor_head_grad_global, (int(global_rows), float(entropy_share)))
         rc = entry(p["head_w"].data_ptr(), p["head_b"].data_ptr(), p["log_std"].data_ptr(), C.byref(rows), *(t.data_ptr() for t in per_row),
                    float(clip_param), float(entropy_coef), dy.data_ptr(), g["head_w"].data_ptr(), g["head_b"].data_ptr(), g["log_std"].data_ptr(),
@@ -442,7 +516,7 @@ def policy_loss_and_grad_rnn(actor, obs_self, obs_others, obs_cylinders, actor_r
         return log_probs
 
     head = _Head(True, (("action", action, P.ACTION_DIM), ("log_probs_old", log_probs_old, 1), ("advantages", advantages, 1)),
-                 ("policy_loss", "entropy", "ess"), "log_probs", restate, launch)
+                 ("policy_loss", "entropy", "ess"), "log_probs", restate, launch, None, stacked)
     scalars, norm, log_probs = _run(head, actor, (obs_self, obs_others, obs_cylinders), actor_rnn_state, is_init, segment, seq_len, check_index,
                                     workspace, out, bucket, global_rows, group)
     return ActorLoss(*scalars, norm, log_probs)
@@ -538,6 +612,21 @@ def update_actor_rnn(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state
     res = policy_loss_and_grad_rnn(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, segment, L,
                                    float(get("clip_param", 0.1)), float(get("entropy_coef", 0.001)), check_index, workspace, out, bucket,
                                    **(dict(global_rows=global_rows, entropy_share=entropy_share, group=group) if global_rows is not None or group is not None else {}))
+    return {"policy_loss": res.policy_loss, "actor_grad_norm": PT.clipped_step(optimizer, res.grad_norm), "entropy": res.entropy, "ESS": res.ess}
+
+
+def update_actor_rnn_per_agent(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, optimizer,
+                               segment=None, cfg=None, seq_len=None, check_index=False, workspace=None, out=None, bucket=None, global_rows=None, group=None):
+    """`update_actor_rnn` with one actor per agent (MAPPOPolicy.update_actor with share_actor: False and actor.rnn):
+    `policy_loss_and_grad_rnn_per_agent`, then the clip and the Adam step of `optimizer` (make_optimizer_per_agent) over the 29 stacked
+    tensors.  The same info dict.  `global_rows=` / `group=` raise NotImplementedError."""
+    if global_rows is not None or group is not None:
+        raise NotImplementedError("one recurrent actor per agent has no data-parallel form yet (DESIGN-open-items.md #13)")
+    PT.check_optimizer(optimizer, "update_actor_rnn_per_agent", "rnn_train.make_optimizer_per_agent")
+    get = PT.getter(cfg)
+    L = int(seq_len) if seq_len is not None else train_seq_len(cfg)
+    res = policy_loss_and_grad_rnn_per_agent(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages,
+                                             segment, L, float(get("clip_param", 0.1)), float(get("entropy_coef", 0.001)), check_index, workspace, out, bucket)
     return {"policy_loss": res.policy_loss, "actor_grad_norm": PT.clipped_step(optimizer, res.grad_norm), "entropy": res.entropy, "ESS": res.ess}
 
 
