@@ -268,7 +268,7 @@ def test_load_policy_checkpoint(tmp_path):
 def test_tp_saturated_gates_stay_finite():
     """Parameters 20x the default init drive the gate pre-activations far into saturation (|z| ~ 100: exp2 overflows
     to inf / underflows to 0 inside the sigmoids): everything stays finite.  With such gains the recurrence amplifies
-    last-bit differences (plain fp32 against fp64 is off by 5e-6 on one golden window already, tools/tp_split_error.py),
+    last-bit differences (plain fp32 against fp64 is off by 5e-6 on one golden window already, tests/test_tp_accuracy.py),
     so HIP and oracle are compared on the bulk (median) and with a loose bound on the tail."""
     E, A = 256, 3
     env = _env(E, A, critic_input="state")

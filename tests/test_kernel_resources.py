@@ -43,6 +43,15 @@ def test_no_kernel_spills_or_uses_scratch(kernels):
     assert not bad, "kernels with spilled vector registers / scratch bytes: " + "; ".join(f"{n}: {v} VGPRs spilled, {s} B scratch" for n, v, s in bad)
 
 
+def test_predictor_ships_exactly_the_kernels_it_can_launch(kernels):
+    """csrc/hns_tp.hip: the pack kernel and the eleven instantiations hns_tp_observe selects from — one to five frame chunks with one or four column tiles per
+    workgroup, two tiles for one-chunk frames only.  An instantiation nothing launches is dead weight in every build and every register table.
+    (By object and by name: the training kernels of csrc/hns_tp_train.hip are `hns_tp_grad_*`, in an object of their own.)"""
+    got = sorted(k["demangled"] for k in kernels if k["object"] == "hns_tp.o" or k["demangled"].startswith(("hns_tp_lstm", "hns_tp_pack")))
+    want = ["hns_tp_pack_ws_kernel"] + [f"hns_tp_lstm_ws_kernel<{nxc}, {tiles}>" for nxc in range(1, 6) for tiles in ((1, 2, 4) if nxc == 1 else (1, 4))]
+    assert got == sorted(want)
+
+
 def test_register_budgets_of_the_headline_kernels(kernels):
     """Occupancy the design counts on: the 3v1 tile kernel runs four 4-wave workgroups per CU (<= 128 VGPRs), the 6v2 shard two 7-wave
     workgroups (<= 128), the small-batch mapping two 7-wave workgroups (<= 128), the predictor — every tile count of the one-chunk frame — four waves per SIMD

@@ -9,12 +9,9 @@ with e_hip / e_32 the largest absolute error against fp64 of the kernel / of the
 u = 2^-24 * max |fp64 output|.  The columns that are not predictions must be bit-exact with the oracle.
 
 CPU part: the fp64 reference against the reference's goldens, the oracle against the fp64 reference on the stress cases (the checker
-checks itself), and a numpy emulation of the shipped split arithmetic (csrc/hns_tp.hip, weight-stationary kernel) that passes the gate
+checks itself), and a numpy emulation of the shipped split arithmetic (csrc/hns_tp.hip) that passes the gate
 while the same emulation with one low split term dropped fails it.  GPU part: the kernel on the same stress cases."""
 import json
-import os
-import subprocess
-import sys
 import zlib
 
 import numpy as np
@@ -25,7 +22,7 @@ import hns_oracle as O
 import tp_f64_reference as R64
 from hns_amd import abi, config
 
-C_GATE = 5.0        # MI355X: worst e_hip / max(e_32, u) 2.37 over every case, output and call (weight-stationary kernel, "wide_early"); 2.1x headroom.
+C_GATE = 5.0        # MI355X: worst e_hip / max(e_32, u) 2.37 over every case, output and call ("wide_early"); 2.1x headroom.
                     # One low split term dropped from the kernel (recurrent h, W_hh, last frame chunk, output layer, W_ih chunk 0): 6.9 .. 4 600
 ARENA, MAX_H = 0.9, 1.2
 
@@ -361,9 +358,6 @@ def test_emulated_split_without_a_low_term_fails_the_gate(emu_inputs, drop):
 
 
 # ---- GPU: the kernel against fp64, next to the oracle ------------------------------------------------------------------------------
-TILE_CASES = ["ref_3v1_2048", "x3_late", "x3_long_episode", "wide_early", "gates_late", "fcsat", "T1", "T16", "F10", "3v2"]   # one-chunk frames
-
-
 def run_gpu_case(cs, g):
     """N_CALLS calls of hns_tp_observe on crafted states: per call and output, (e_hip, e_32, u).  Asserts on the way that the window
     is the oracle's and that every column of the rows that is not a prediction is the oracle's, bit for bit."""
@@ -405,41 +399,18 @@ def check_gate(name, calls):
     return worst
 
 
-def _report(kernel, name, calls):
+def _report(name, calls):
     """One line per case (pytest -s): the largest e_hip, e_32 and ratio over the calls and outputs."""
     rows = [(e_hip, e_32, u, ratio(e_hip, e_32, u)) for res in calls for (e_hip, e_32, u) in res.values()]
     k = max(range(len(rows)), key=lambda i: rows[i][3])
-    print("TPACC " + json.dumps({"kernel": kernel, "case": name, "e_hip": max(r[0] for r in rows), "e_32": max(r[1] for r in rows),
+    print("TPACC " + json.dumps({"case": name, "e_hip": max(r[0] for r in rows), "e_32": max(r[1] for r in rows),
                                  "u": max(r[2] for r in rows), "worst_ratio": rows[k][3]}))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("cs", CASES, ids=CASE_IDS)
 def test_kernel_is_as_accurate_as_fp32(golden, cs):
-    """hns_tp_observe as shipped (the weight-stationary kernel serves every frame width by default) within the gate."""
+    """hns_tp_observe as shipped (one kernel serves every frame width and batch size) within the gate."""
     calls = run_gpu_case(cs, golden("g_tp_obs"))
-    _report("default", cs["name"], calls)
+    _report(cs["name"], calls)
     check_gate(cs["name"], calls)
-
-
-@pytest.mark.gpu
-def test_tile_kernel_is_as_accurate_as_fp32():
-    """The one-chunk tile kernel (HNS_TP_KERNEL=tile, read once per process: one child process for all its cases) within the gate."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, HNS_TP_KERNEL="tile")
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = (f"import sys; sys.path[:0] = {[root, os.path.join(root, 'oracle'), here]!r}; import hns_amd; import test_tp_accuracy as t; "
-            f"t._child({TILE_CASES!r})")
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600, cwd=root)
-    assert out.returncode == 0, out.stderr[-3000:]
-    res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
-    assert sorted(res) == sorted(TILE_CASES)
-    for name, calls in res.items():
-        calls = [{k: tuple(v) for k, v in r.items()} for r in calls]
-        _report("tile", name, calls)
-        check_gate("tile " + name, calls)
-
-
-def _child(names):
-    g = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g_tp_obs.npz")))
-    print(json.dumps({n: run_gpu_case(next(c for c in CASES if c["name"] == n), g) for n in names}))

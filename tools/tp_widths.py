@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """hns_tp_observe alone (events around 200 launches) at the predictor's frame widths: 1 chunk (3 pursuers), 2 chunks (3 pursuers + 5 cylinders in the
-frame, the reference's use_obstacles shape: 31 values), 3 chunks (3 + 8: 40 values), 4 (6 + 12: 61) and 5 (6 + 16: 73).  HNS_TP_KERNEL=tile|ws forces
-a kernel where both exist (read once per process: run this once per setting).  usage: tp_widths.py [envs]"""
+frame, the reference's use_obstacles shape: 31 values), 3 chunks (3 + 8: 40 values), 4 (6 + 12: 61) and 5 (6 + 16: 73).
+usage: tp_widths.py [envs]"""
 import os
 import sys
 
@@ -28,7 +28,7 @@ for A, Cn, obst in ((3, 8, 0), (3, 5, 1), (3, 8, 1), (6, 12, 1), (6, 16, 1)):
         env._tp_observe()
     e1.record()
     torch.cuda.synchronize()
-    print(f"HNS_TP_KERNEL={os.environ.get('HNS_TP_KERNEL', '(default)')}: A={A} C={Cn} use_obstacles={obst} frame {env.tp_frame_dim} values "
+    print(f"A={A} C={Cn} use_obstacles={obst} frame {env.tp_frame_dim} values "
           f"({(env.tp_frame_dim + 15) // 16} chunks): hns_tp_observe {e0.elapsed_time(e1) / 200 * 1e3:.1f} us", flush=True)
     del env
     torch.cuda.empty_cache()
