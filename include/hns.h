@@ -716,6 +716,21 @@ int hns_actor_train_grad_global(const hns_policy_net *actor, const hns_actor_bat
                                 double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
                                 float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream, int64_t global_rows,
                                 double entropy_share);
+/* hns_actor_train_grad_agents' arguments, then `global_rows` and `entropy_share`: one rank's part of a data-parallel update of one actor per
+ * agent (hns_amd.learner.DataParallelPerAgentLearner).  It is to hns_actor_train_grad_agents what hns_actor_train_grad_global
+ * is to hns_actor_train_grad, on that entry's launches, plan, tiles and workspace (hns_actor_train_agents_workspace_bytes): every row's backward
+ * weight carries f32(1 / global_rows); policy_loss = -4 sum_local min(..) / global_rows is this rank's SHARE; each agent's d log_std takes
+ * (-entropy_coef x entropy_share) / A, formed in that order, so a share of 1 leaves the local constant and a SUM over W ranks with share 1 / W
+ * counts the entropy term once; entropy (the mean over the agents) is the same on every rank; ess stays this rank's own.  grad_norm may be NULL:
+ * the norm launch is skipped (five launches).  Order of every sum: hns_actor_train_grad_agents' — the tiles agent-major and padded to whole row
+ * ranges, the loss kernel's tile partials in its fixed order with n = global_rows, each agent's weight-gradient partials in split order, its
+ * tile partials in tile order.  With one rank (global_rows = batch x num_agents, entropy_share 1) every output has hns_actor_train_grad_agents'
+ * bits.  Refused as that entry refuses and in its order (grad_norm excepted), plus, after clip_param and entropy_coef, global_rows < batch x
+ * num_agents and a non-finite entropy_share. */
+int hns_actor_train_grad_agents_global(const hns_policy_net *actors, const hns_actor_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                                       double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
+                                       float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream, int64_t global_rows,
+                                       double entropy_share);
 /*
  * The PartialAttentionEncoder alone as a differentiable op (hns_amd.encoder): the forward pass gives the 128 features of every
  * (env-step, agent) row of a minibatch, the backward pass takes d features and gives the gradients of the encoder's 20 parameter tensors, so any
@@ -1002,6 +1017,19 @@ int hns_rnn_actor_head_grad_global(const float *head_w, const float *head_b, con
                                    const float *log_probs_old, const float *advantages, double clip_param, double entropy_coef, float *dy,
                                    float *d_head_w, float *d_head_b, float *d_log_std, float *policy_loss, float *entropy, float *ess, float *log_probs,
                                    void *workspace, size_t workspace_bytes, void *stream, int64_t global_rows, double entropy_share);
+/* The global form of hns_rnn_actor_head_grad_agents (one head per agent, data-parallel: hns_amd.learner.DataParallelPerAgentRecurrentLearner;
+ * DESIGN.md §7.19): that entry's arguments, launches, order of every sum and workspace (hns_rnn_actor_head_agents_workspace_bytes), with
+ * hns_rnn_actor_head_grad_global's scalars.  Every row's backward weight is scaled by f32(1 / global_rows); policy_loss = -4 sum_local min(..) /
+ * global_rows is this rank's SHARE; each agent's d_log_std takes (-entropy_coef entropy_share) / A, the product formed first, so a share of 1
+ * leaves the local constant; entropy is the same on every rank; ess stays this call's own.  The dead-segment rule is unchanged and n stays
+ * global_rows.  With global_rows = B L A and entropy_share = 1 every output (dy, the three gradients, the scalars, log_probs) has
+ * hns_rnn_actor_head_grad_agents' bits.  Refused as that entry refuses and in its order, then global_rows < B L A and an entropy_share that is
+ * not finite (both before the workspace is looked at). */
+int hns_rnn_actor_head_grad_agents_global(const float *head_w, const float *head_b, const float *log_std, const hns_rnn_rows *rows, const float *action,
+                                          const float *log_probs_old, const float *advantages, double clip_param, double entropy_coef, float *dy,
+                                          float *d_head_w, float *d_head_b, float *d_log_std, float *policy_loss, float *entropy, float *ess,
+                                          float *log_probs, void *workspace, size_t workspace_bytes, void *stream, int64_t global_rows,
+                                          double entropy_share);
 /* The 2-norm of one flat fp32 gradient bucket: norm[0] = f32(sqrt(sum_i flat[i]^2)), in this order (tests/dp_reference.py restates it in numpy):
  * the bucket is cut into quads of four consecutive floats, the last one short by numel % 4 values that count as 0 (nothing past numel is
  * read); G = clamp(ceil(quads / 1024), 1, 64) workgroups of 256 threads, T = 256 G; thread t of the grid adds, for q = t, t + T, t + 2 T, ...,

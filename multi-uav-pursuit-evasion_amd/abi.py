@@ -399,6 +399,8 @@ def load_library():
     lib.hns_critic_train_grad_global.restype = C.c_int
     lib.hns_actor_train_grad_global.argtypes = lib.hns_actor_train_grad.argtypes + [C.c_int64, C.c_double]
     lib.hns_actor_train_grad_global.restype = C.c_int
+    lib.hns_actor_train_grad_agents_global.argtypes = lib.hns_actor_train_grad_global.argtypes     # one actor per agent, data-parallel
+    lib.hns_actor_train_grad_agents_global.restype = C.c_int
     # the encoder as a differentiable op (include/hns.h; hns_amd.encoder)
     lib.hns_encoder_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     lib.hns_encoder_workspace_bytes.restype = C.c_size_t
@@ -451,6 +453,8 @@ def load_library():
     lib.hns_rnn_critic_head_grad_global.restype = C.c_int
     lib.hns_rnn_actor_head_grad_global.argtypes = lib.hns_rnn_actor_head_grad.argtypes + [C.c_int64, C.c_double]
     lib.hns_rnn_actor_head_grad_global.restype = C.c_int
+    lib.hns_rnn_actor_head_grad_agents_global.argtypes = lib.hns_rnn_actor_head_grad_global.argtypes   # one head per agent, data-parallel (§7.19)
+    lib.hns_rnn_actor_head_grad_agents_global.restype = C.c_int
     lib.hns_grad_norm_workspace_bytes.argtypes = [C.c_longlong]
     lib.hns_grad_norm_workspace_bytes.restype = C.c_size_t
     lib.hns_grad_norm.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -522,5 +526,5 @@ def check(rc, what):
 EXPORTED_SYMBOLS = [
     "hns_create", "hns_destroy", "hns_bind", "hns_step", "hns_reset", "hns_reset_tasks", "hns_raycast", "hns_set_v_prey",
     "hns_set_smoothness_coef", "hns_set_reset_epoch", "hns_get_reset_epoch", "hns_enable_timing",
-    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_gae", "hns_rollout_normalise", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_selected_kernels", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_tp_train_workspace_bytes", "hns_tp_train_grad", "hns_tp_adam", "hns_policy_packed_bytes", "hns_policy_pack", "hns_policy_forward", "hns_policy_act", "hns_critic_train_workspace_bytes", "hns_critic_train_grad", "hns_actor_train_workspace_bytes", "hns_actor_train_grad", "hns_critic_train_sums", "hns_critic_train_grad_global", "hns_actor_train_grad_global", "hns_grad_norm_workspace_bytes", "hns_grad_norm", "hns_adam_clipped", "hns_learner_info_workspace_bytes", "hns_learner_info", "hns_rollout_store", "hns_eval_means", "hns_encoder_workspace_bytes", "hns_encoder_forward", "hns_encoder_backward", "hns_gru_workspace_bytes", "hns_gru_forward", "hns_gru_backward", "hns_policy_rnn_packed_bytes", "hns_policy_rnn_pack", "hns_policy_forward_rnn", "hns_policy_act_rnn", "hns_rnn_actor_head_workspace_bytes", "hns_rnn_critic_head_workspace_bytes", "hns_rnn_actor_head_grad", "hns_rnn_critic_head_grad", "hns_rnn_critic_head_sums", "hns_rnn_critic_head_grad_global", "hns_rnn_actor_head_grad_global", "hns_policy_packed_agents_bytes", "hns_policy_pack_agents", "hns_policy_forward_agents", "hns_policy_act_agents", "hns_actor_train_agents_workspace_bytes", "hns_actor_train_grad_agents", "hns_policy_rnn_packed_agents_bytes", "hns_policy_rnn_pack_agents", "hns_policy_forward_rnn_agents", "hns_policy_act_rnn_agents", "hns_gru_agents_workspace_bytes", "hns_gru_forward_agents", "hns_gru_backward_agents", "hns_encoder_agents_workspace_bytes", "hns_encoder_forward_agents", "hns_encoder_backward_agents", "hns_rnn_actor_head_agents_workspace_bytes", "hns_rnn_actor_head_grad_agents", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
+    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_gae", "hns_rollout_normalise", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_selected_kernels", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_tp_train_workspace_bytes", "hns_tp_train_grad", "hns_tp_adam", "hns_policy_packed_bytes", "hns_policy_pack", "hns_policy_forward", "hns_policy_act", "hns_critic_train_workspace_bytes", "hns_critic_train_grad", "hns_actor_train_workspace_bytes", "hns_actor_train_grad", "hns_critic_train_sums", "hns_critic_train_grad_global", "hns_actor_train_grad_global", "hns_grad_norm_workspace_bytes", "hns_grad_norm", "hns_adam_clipped", "hns_learner_info_workspace_bytes", "hns_learner_info", "hns_rollout_store", "hns_eval_means", "hns_encoder_workspace_bytes", "hns_encoder_forward", "hns_encoder_backward", "hns_gru_workspace_bytes", "hns_gru_forward", "hns_gru_backward", "hns_policy_rnn_packed_bytes", "hns_policy_rnn_pack", "hns_policy_forward_rnn", "hns_policy_act_rnn", "hns_rnn_actor_head_workspace_bytes", "hns_rnn_critic_head_workspace_bytes", "hns_rnn_actor_head_grad", "hns_rnn_critic_head_grad", "hns_rnn_critic_head_sums", "hns_rnn_critic_head_grad_global", "hns_rnn_actor_head_grad_global", "hns_policy_packed_agents_bytes", "hns_policy_pack_agents", "hns_policy_forward_agents", "hns_policy_act_agents", "hns_actor_train_agents_workspace_bytes", "hns_actor_train_grad_agents", "hns_policy_rnn_packed_agents_bytes", "hns_policy_rnn_pack_agents", "hns_policy_forward_rnn_agents", "hns_policy_act_rnn_agents", "hns_gru_agents_workspace_bytes", "hns_gru_forward_agents", "hns_gru_backward_agents", "hns_encoder_agents_workspace_bytes", "hns_encoder_forward_agents", "hns_encoder_backward_agents", "hns_rnn_actor_head_agents_workspace_bytes", "hns_rnn_actor_head_grad_agents", "hns_actor_train_grad_agents_global", "hns_rnn_actor_head_grad_agents_global", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
 ]

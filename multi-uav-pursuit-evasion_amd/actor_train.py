@@ -16,8 +16,10 @@ by 1 / global_rows and the entropy term by `entropy_share`, the gradients land i
 all-reduced and its norm taken before the step.
 
 The `*_per_agent` functions are the same update with share_actor: False (one actor per agent: the reference's stacked `actor_params`, every
-tensor [A, ...]; update_actor's else branch, mappo.py:288-291) on ONE call of `hns_actor_train_grad_agents`; DESIGN.md §7.16.  Both forms
-run ONE CPU function (`_torch_loss_and_grad`) and ONE device half (`_device_loss_and_grad`, handed the entry and its workspace query).
+tensor [A, ...]; update_actor's else branch, mappo.py:288-291) on ONE call of `hns_actor_train_grad_agents`; DESIGN.md §7.16.  Their
+data-parallel forms are `policy_loss_and_grad_per_agent_global` and `update_actor_per_agent_global` (`hns_actor_train_grad_agents_global`, the
+bucket over the 23 stacked tensors).  All forms run ONE CPU function (`_torch_loss_and_grad`) and ONE device half
+(`_device_loss_and_grad`, handed the entry and its workspace query).
 
 `update_actor` is the reference's function.  CPU tensors run the reference's torch statements throughout (CPU tests, gloo runs — not the
 hot path).  DESIGN.md §7.5."""
@@ -91,7 +93,14 @@ def _torch_loss_and_grad(p, xs, xo, xc, action, log_probs_old, advantages, index
                 bucket.adopt()
             grad_norm = PT.finish_global(bucket, group)
         ess = (2 * ratio.logsumexp(0) - (2 * ratio).logsumexp(0)).exp().mean() / ratio.shape[0]
-    return ActorLoss(policy_loss.detach(), -entropy_loss.detach(), ess, grad_norm, log_probs_new.detach())
+        entropy = -entropy_loss.detach()
+        if per_agent and global_rows is not None:
+            # The same on every rank: the fp32 mean over the rows above rounds differently for different row counts once the agents' entropies
+            # differ, so the global form states what hns_actor_train_grad_agents_global computes — each agent's four terms and the mean over the
+            # agents in fp64, rounded once.  It is the row mean's value up to that mean's own summation error.
+            ls = p["log_std"].detach()
+            entropy = (0.5 + 0.9189385332046727 + ls.double()).sum(-1).mean().to(ls.dtype)
+    return ActorLoss(policy_loss.detach(), entropy, ess, grad_norm, log_probs_new.detach())
 
 
 def _device_loss_and_grad(entry, workspace_bytes, p, xs, xo, xc, shape, action, log_probs_old, advantages, index, clip_param, entropy_coef, workspace,
@@ -199,14 +208,10 @@ def actor_parameters_per_agent(actor):
     return P.parse_parameters_per_agent(actor, "actor")[0]
 
 
-def policy_loss_and_grad_per_agent(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index=None, clip_param=0.1,
-                                   entropy_coef=0.001, check_index=True, workspace=None, out=None):
-    """`policy_loss_and_grad` with one actor per agent: `actor` holds the STACKED tensors ([A, ...], the reference's actor_params with
-    share_actor: False), agent a's rows run on slice a, and every stacked tensor's .grad ([A, ...]) is as zero_grad() + backward() leave it.
-    policy_loss is the mean over all B A rows, entropy the mean over the agents of each agent's entropy (each d log_std takes
-    -entropy_coef / A), ess as for the shared actor, grad_norm the total norm over all agents' gradients.  Arguments, layouts, `workspace`
-    (at least hns_actor_train_agents_workspace_bytes bytes) and `out` as `policy_loss_and_grad`; no data-parallel form.  log_probs [B, A, 1]
-    is bit for bit `policy_loss_and_grad`'s for row (b, a) with slice a as the shared actor."""
+def _loss_and_grad_per_agent(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index, clip_param, entropy_coef, check_index,
+                             workspace, out, global_rows=None, entropy_share=1.0, group=None, bucket=None):
+    """Both per-agent `policy_loss_and_grad`s: the local call (global_rows None: hns_actor_train_grad_agents) and one rank's part of a
+    data-parallel update (hns_actor_train_grad_agents_global, then policy_train.finish_global on the bucket)."""
     if not clip_param >= 0:
         raise ValueError("clip_param must be >= 0")
     p = actor_parameters_per_agent(actor)
@@ -219,12 +224,48 @@ def policy_loss_and_grad_per_agent(actor, obs_self, obs_others, obs_cylinders, a
     A = int(p["in_proj_w"].shape[0])
     if shape[2] != A:
         raise ValueError(f"the observation has {shape[2]} agents, the stacked actor {A}")
+    B = index.numel() if index is not None else shape[0] * shape[1]
+    PT.check_global("actor", p, global_rows, B * A, group, bucket)
     if not xs.is_cuda:
-        return _torch_loss_and_grad(p, xs, xo, xc, action, log_probs_old, advantages, index, float(clip_param), float(entropy_coef), per_agent=True)
+        return _torch_loss_and_grad(p, xs, xo, xc, action, log_probs_old, advantages, index, float(clip_param), float(entropy_coef), global_rows,
+                                    float(entropy_share), group, bucket, per_agent=True)
     lib = abi.load_library()
-    scal, log_probs = _device_loss_and_grad(lib.hns_actor_train_grad_agents, lib.hns_actor_train_agents_workspace_bytes, p, xs, xo, xc, shape, action,
-                                            log_probs_old, advantages, index, clip_param, entropy_coef, workspace, out)
+    args = (lib.hns_actor_train_agents_workspace_bytes, p, xs, xo, xc, shape, action, log_probs_old, advantages, index, clip_param, entropy_coef, workspace,
+            out)
+    if global_rows is not None:
+        scal, log_probs = _device_loss_and_grad(lib.hns_actor_train_grad_agents_global, *args, more=(int(global_rows), float(entropy_share)))
+        norm = PT.finish_global(bucket, group, scal[3:4])
+        return ActorLoss(scal[0], scal[1], scal[2], scal[3] if norm is not None else None, log_probs)
+    scal, log_probs = _device_loss_and_grad(lib.hns_actor_train_grad_agents, *args)
     return ActorLoss(scal[0], scal[1], scal[2], scal[3], log_probs)
+
+
+def policy_loss_and_grad_per_agent(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index=None, clip_param=0.1,
+                                   entropy_coef=0.001, check_index=True, workspace=None, out=None):
+    """`policy_loss_and_grad` with one actor per agent: `actor` holds the STACKED tensors ([A, ...], the reference's actor_params with
+    share_actor: False), agent a's rows run on slice a, and every stacked tensor's .grad ([A, ...]) is as zero_grad() + backward() leave it.
+    policy_loss is the mean over all B A rows, entropy the mean over the agents of each agent's entropy (each d log_std takes
+    -entropy_coef / A), ess as for the shared actor, grad_norm the total norm over all agents' gradients.  Arguments, layouts, `workspace`
+    (at least hns_actor_train_agents_workspace_bytes bytes) and `out` as `policy_loss_and_grad`; the data-parallel form is
+    `policy_loss_and_grad_per_agent_global`.  log_probs [B, A, 1] is bit for bit `policy_loss_and_grad`'s for row (b, a) with slice a as the
+    shared actor."""
+    return _loss_and_grad_per_agent(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index, clip_param, entropy_coef,
+                                    check_index, workspace, out)
+
+
+def policy_loss_and_grad_per_agent_global(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index=None, clip_param=0.1,
+                                          entropy_coef=0.001, check_index=True, workspace=None, out=None, global_rows=None, entropy_share=1.0,
+                                          group=None, bucket=None):
+    """`policy_loss_and_grad_per_agent` as one rank's part of a data-parallel update (hns_actor_train_grad_agents_global),
+    with the semantics of `policy_loss_and_grad(global_rows=...)`: this minibatch is a part of a union of `global_rows` agent rows, policy_loss
+    is this rank's SHARE (-4 sum_local / global_rows), every stacked gradient is the share's, each agent's d log_std takes
+    (-entropy_coef entropy_share) / A, entropy is the same on every rank and ess stays this rank's own.  `bucket`: the `policy_train.GradBucket`
+    of the 23 stacked tensors; grad_norm is the bucket's norm (None without one).  `group`: the bucket is all-reduced (SUM) over it first.
+    With global_rows = this call's own rows and entropy_share 1 every output has `policy_loss_and_grad_per_agent`'s bits."""
+    if global_rows is None:
+        raise ValueError("policy_loss_and_grad_per_agent_global needs global_rows= (the local call is policy_loss_and_grad_per_agent)")
+    return _loss_and_grad_per_agent(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index, clip_param, entropy_coef,
+                                    check_index, workspace, out, global_rows, entropy_share, group, bucket)
 
 
 def actor_cfg_per_agent(cfg):
@@ -245,4 +286,19 @@ def update_actor_per_agent(actor, obs_self, obs_others, obs_cylinders, action, l
     res = policy_loss_and_grad_per_agent(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index,
                                          clip_param=float(get("clip_param", 0.1)), entropy_coef=float(get("entropy_coef", 0.001)),
                                          check_index=check_index, workspace=workspace, out=out)
+    return _info(res, PT.clipped_step(optimizer, res.grad_norm))
+
+
+def update_actor_per_agent_global(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, optimizer, index=None, cfg=None,
+                                  check_index=False, workspace=None, out=None, global_rows=None, entropy_share=1.0, group=None, bucket=None):
+    """`update_actor_per_agent` as one rank's part of a data-parallel update: `policy_loss_and_grad_per_agent_global`, then the clip by the
+    bucket's norm and the Adam step over the stacked tensors.  The step needs the union's gradients, so `global_rows` and `bucket` are
+    required (`group` may be None where the caller summed the buckets itself), as `update_actor(global_rows=...)`."""
+    if global_rows is None or bucket is None:
+        raise ValueError("update_actor_per_agent_global steps on the bucket's norm over the union: pass global_rows= and bucket=")
+    get, _ = PT.check_optimizer(optimizer, "update_actor_per_agent_global", "actor_train.make_optimizer_per_agent", actor_cfg_per_agent, cfg)
+    res = policy_loss_and_grad_per_agent_global(actor, obs_self, obs_others, obs_cylinders, action, log_probs_old, advantages, index,
+                                                clip_param=float(get("clip_param", 0.1)), entropy_coef=float(get("entropy_coef", 0.001)),
+                                                check_index=check_index, workspace=workspace, out=out, global_rows=global_rows,
+                                                entropy_share=entropy_share, group=group, bucket=bucket)
     return _info(res, PT.clipped_step(optimizer, res.grad_norm))

@@ -864,7 +864,8 @@ int ct_critic_call(const char *fn, CtMode mode, const hns_policy_net *critic, co
 // The actor's two entries over one body.  global: the rows' backward weight and policy_loss are scaled by 1 / global_rows instead of 1 / rows (this
 // rank's share of the loss and of the gradient: the ranks' shares add up), the entropy term's constant gradient joins by `entropy_share` of it.
 // `agents`: hns_actor_train_grad_agents — `actor` and `grads` hold the stacked tensors, every launch but the weight gradients' and the norm's is the
-// per-agent kernel (same order, same count).
+// per-agent kernel (same order, same count).  Both flags: hns_actor_train_grad_agents_global — the same launches with the global scalars (f32(1 /
+// global_rows) on the rows, n = global_rows in the loss kernel, (-entropy_coef entropy_share) / A on each agent's d log_std); no kernel of its own.
 int ct_actor_call(const char *fn, bool global, bool agents, const hns_policy_net *actor, const hns_actor_batch *batch, int32_t self_dim, int32_t num_agents,
                   int32_t num_cylinders, double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
                   float *grad_norm, float *log_probs, int64_t global_rows, double entropy_share, void *workspace, size_t workspace_bytes, void *stream) {
@@ -902,17 +903,19 @@ int ct_actor_call(const char *fn, bool global, bool agents, const hns_policy_net
         HNS_CHECK_HIP(hipGetLastError());
         hipLaunchKernelGGL(hns::hns_actor_agents_kernel, dim3((unsigned)(p.tiles / A), A), dim3(hns::kCtThreads), sizeof(hns::CtLds), st, a);
         HNS_CHECK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(hns::hns_actor_loss_agents_kernel, dim3(1), dim3(64), 0, st, a.losspart, (int)p.tiles, A, (double)a.rows, (double)batch->batch,
-                           actor->log_std, policy_loss, entropy, ess);
+        hipLaunchKernelGGL(hns::hns_actor_loss_agents_kernel, dim3(1), dim3(64), 0, st, a.losspart, (int)p.tiles, A, (double)(global ? global_rows : a.rows),
+                           (double)batch->batch, actor->log_std, policy_loss, entropy, ess);
         HNS_CHECK_HIP(hipGetLastError());
         float *gpart = reinterpret_cast<float *>(ws + p.o_gemm);
         hipLaunchKernelGGL(hns::hns_critic_wgrad_kernel, dim3((unsigned)p.splits, 6), dim3(256), 0, st, a.stage, a.stage_rows, (int)p.tiles, (int)p.tps, gpart);
         HNS_CHECK_HIP(hipGetLastError());
         double *blockpart = reinterpret_cast<double *>(ws + p.o_block);
-        // each agent's d log_std takes its share of the mean entropy's constant gradient
+        // each agent's d log_std takes its share of the mean entropy's constant gradient (global: this rank's entropy_share of it, formed before the
+        // division so that a share of 1 leaves the local entry's constant)
         hipLaunchKernelGGL(hns::hns_actor_reduce_agents_kernel, dim3(nb, A), dim3(256), 0, st, gpart, (int)(p.splits / A), a.tilepart, (int)(2 * p.tiles / A), p.P,
-                           p.gblocks, g, a.D, blockpart, -entropy_coef / (double)A);
+                           p.gblocks, g, a.D, blockpart, (global ? -entropy_coef * entropy_share : -entropy_coef) / (double)A);
         HNS_CHECK_HIP(hipGetLastError());
+        if (!grad_norm) return HNS_OK;                          // the data-parallel entry: hns_grad_norm after the all-reduce
         hipLaunchKernelGGL(hns::hns_critic_norm_kernel, dim3(1), dim3(256), 0, st, blockpart, nb * A, grad_norm);
         HNS_CHECK_HIP(hipGetLastError());
         return HNS_OK;
@@ -1062,6 +1065,16 @@ int hns_actor_train_grad_agents(const hns_policy_net *actors, const hns_actor_ba
     if (!actors || !batch || !grads || !policy_loss || !entropy || !ess || !grad_norm || !workspace) return hns_fail(fn, "null pointer");
     return ct_actor_call(fn, false, true, actors, batch, self_dim, num_agents, num_cylinders, clip_param, entropy_coef, grads, policy_loss, entropy, ess,
                          grad_norm, log_probs, 0, 1.0, workspace, workspace_bytes, stream);
+}
+
+int hns_actor_train_grad_agents_global(const hns_policy_net *actors, const hns_actor_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                                       double clip_param, double entropy_coef, const hns_policy_grads *grads, float *policy_loss, float *entropy, float *ess,
+                                       float *grad_norm, float *log_probs, void *workspace, size_t workspace_bytes, void *stream, int64_t global_rows,
+                                       double entropy_share) {
+    const char *fn = "hns_actor_train_grad_agents_global";
+    if (!actors || !batch || !grads || !policy_loss || !entropy || !ess || !workspace) return hns_fail(fn, "null pointer");
+    return ct_actor_call(fn, true, true, actors, batch, self_dim, num_agents, num_cylinders, clip_param, entropy_coef, grads, policy_loss, entropy, ess,
+                         grad_norm, log_probs, global_rows, entropy_share, workspace, workspace_bytes, stream);
 }
 
 size_t hns_encoder_workspace_bytes(int64_t rows, int32_t self_dim, int32_t num_agents, int32_t num_cylinders, int32_t backward) {

@@ -39,6 +39,8 @@
 //   hns_rnn_actor_final_agents_kernel : agent a's slice of the stacked gradients from its gpa partials in index order; d log_std[a] takes
 //                                       -entropy_coef / A once; the loss sum adds all A gpa partials in workgroup order (agent-major);
 //                                       entropy = the agents' entropies (four terms in index order each) added in agent order, over A
+// hns_rnn_actor_head_grad_agents_global is these launches with the global forms' scalars: inv_n = f32(1 / global_rows),
+// n = global_rows, and entropy_coef entropy_share where the final kernel takes entropy_coef, so d log_std[a] takes -(entropy_coef entropy_share) / A.
 //
 // Order of every sum.  A lane adds its rows' contributions trip after trip (the head-gradient products in fp32, the loss terms in fp64: a lane
 // sees ceil(trips / G) rows); the workgroup's partial is the 32 row groups added in index order in fp64; the partials are added in workgroup
@@ -578,7 +580,8 @@ static int rt_actor_entry(const char *fn, const float *head_w, const float *head
     HNS_CHECK_HIP(hipGetLastError());
     if (agents) {
         hipLaunchKernelGGL(hns_rnn_actor_final_agents_kernel, dim3((kRtActorUsed + kRtFinalElems - 1) / kRtFinalElems, a.G.A), dim3(kRtThreads), 0, st,
-                           static_cast<const double *>(a.part), gpa, a.G.A, static_cast<const double *>(col), a.G.LA, n, (double)rows->outer, entropy_coef,
+                           static_cast<const double *>(a.part), gpa, a.G.A, static_cast<const double *>(col), a.G.LA, n, (double)rows->outer,
+                           global ? entropy_coef * entropy_share : entropy_coef,    // the kernel divides by A: (entropy_coef entropy_share) / A
                            log_std, d_head_w, d_head_b, d_log_std, policy_loss, entropy, ess);
         HNS_CHECK_HIP(hipGetLastError());
         return HNS_OK;
@@ -693,6 +696,16 @@ int hns_rnn_actor_head_grad_global(const float *head_w, const float *head_b, con
     return hns::rt_actor_entry("hns_rnn_actor_head_grad_global", head_w, head_b, log_std, rows, action, log_probs_old, advantages, clip_param,
                                entropy_coef, dy, d_head_w, d_head_b, d_log_std, policy_loss, entropy, ess, log_probs, workspace, workspace_bytes, stream,
                                true, global_rows, entropy_share);
+}
+
+int hns_rnn_actor_head_grad_agents_global(const float *head_w, const float *head_b, const float *log_std, const hns_rnn_rows *rows, const float *action,
+                                          const float *log_probs_old, const float *advantages, double clip_param, double entropy_coef, float *dy,
+                                          float *d_head_w, float *d_head_b, float *d_log_std, float *policy_loss, float *entropy, float *ess,
+                                          float *log_probs, void *workspace, size_t workspace_bytes, void *stream, int64_t global_rows,
+                                          double entropy_share) {
+    return hns::rt_actor_entry("hns_rnn_actor_head_grad_agents_global", head_w, head_b, log_std, rows, action, log_probs_old, advantages, clip_param,
+                               entropy_coef, dy, d_head_w, d_head_b, d_log_std, policy_loss, entropy, ess, log_probs, workspace, workspace_bytes, stream,
+                               true, global_rows, entropy_share, true);
 }
 
 int hns_rnn_critic_head_grad(const float *head_w, const float *head_b, const hns_rnn_rows *rows, const float *b_values, const float *b_returns,

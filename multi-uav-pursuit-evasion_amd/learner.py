@@ -35,7 +35,10 @@ agent): the actor step through rnn_train.update_actor_rnn_per_
 PPO update per minibatch on the union of their minibatches — the critic's branch decided on the union's sums, every mean over the union's
 rows, the norm taken from the summed gradient, the predictor's ranks weighted by their selected windows.
 `DataParallelRecurrentLearner` is the same for the recurrent configuration: `RecurrentDeviceLearner` over a process group,
-through rnn_train's global forms (hns_rnn_actor_head_grad_global; hns_rnn_critic_head_sums, hns_rnn_critic_head_grad_global)."""
+through rnn_train's global forms (hns_rnn_actor_head_grad_global; hns_rnn_critic_head_sums, hns_rnn_critic_head_grad_global).
+`DataParallelPerAgentLearner` and `DataParallelPerAgentRecurrentLearner` are the two per-agent learners over a process group (DESIGN.md
+§7.19): the actor step through actor_train.update_actor_per_agent_global / rnn_train.update_actor_rnn_per_agent_global, the bucket and the
+broadcast over the stacked tensors, everything else as the two data-parallel learners above."""
 import ctypes as C
 
 import numpy as np
@@ -447,12 +450,13 @@ class PerAgentDeviceLearner(DeviceLearner):
 
     actor: the STACKED actor's parameters (every tensor [A, ...]: the reference's actor_params; "actor_params" of state_dict()), live tensors
     updated in place; device_policy: a PerAgentDevicePolicy over the same tensors (built when None).  Refused before anything is built:
-    group= (NotImplementedError), a recurrent policy and whatever PerAgentDevicePolicy refuses (PolicyConfigError), a device_policy that is
-    not per-agent, and the cfg refusals of DeviceLearner with their exception types."""
+    group= (NotImplementedError: the data-parallel form is DataParallelPerAgentLearner), a recurrent policy and whatever PerAgentDevicePolicy
+    refuses (PolicyConfigError), a device_policy that is not per-agent, and the cfg refusals of DeviceLearner with their exception types."""
 
     def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, agent_name="drone", generator=None, device_policy=None, group=None):
         if group is not None:
-            raise NotImplementedError("PerAgentDeviceLearner takes no group=: data-parallel training of per-agent actors is not implemented")
+            raise NotImplementedError("PerAgentDeviceLearner takes no group=: data-parallel training of per-agent actors is "
+                                      "DataParallelPerAgentLearner's")
         if getattr(device_policy, "recurrent", False):
             raise P.PolicyConfigError("PerAgentDeviceLearner updates the non-recurrent networks only: per-agent actors with actor.rnn / critic.rnn are "
                                       "not implemented")
@@ -466,6 +470,10 @@ class PerAgentDeviceLearner(DeviceLearner):
 
     def _make_actor_opt(self):
         return actor_train.make_optimizer_per_agent(self.actor, self.cfg)
+
+    def _network_tensors(self):
+        """The 23 stacked tensors in the optimiser's order, and the shared critic's."""
+        return list(actor_train.actor_parameters_per_agent(self.actor).values()), list(critic_train.critic_parameters(self.critic).values())
 
     def _workspaces(self, xs, xc):
         return super()._workspaces(xs, xc, abi.load_library().hns_actor_train_agents_workspace_bytes)
@@ -502,8 +510,8 @@ class RecurrentDeviceLearner(DeviceLearner):
             raise P.PolicyConfigError("RecurrentDeviceLearner needs a RecurrentDevicePolicy (a non-recurrent policy is DeviceLearner's)")
         if getattr(device_policy, "per_agent", False) or P.is_stacked(actor):
             raise P.PolicyConfigError(f"{type(self).__name__} updates ONE shared recurrent actor: recurrent per-agent actors (share_actor: False with "
-                                      "actor.rnn) are PerAgentRecurrentDeviceLearner's; their data-parallel update is an open item "
-                                      "(DESIGN-open-items.md #13)")
+                                      "actor.rnn) are PerAgentRecurrentDeviceLearner's, and data-parallel "
+                                      "DataParallelPerAgentRecurrentLearner's, which closed the open item DESIGN-open-items.md #13")
         self._build(actor, critic, cfg, tp_net, value_normalizer, agent_name, generator, device_policy, P.RecurrentDevicePolicy)
 
     stacked_actor = False                                        # PerAgentRecurrentDeviceLearner: the actor's tensors are stacked over the agents
@@ -606,15 +614,15 @@ class PerAgentRecurrentDeviceLearner(RecurrentDeviceLearner):
 
     actor: the STACKED actor's parameters with their `rnn.*` leaves stacked too (every tensor [A, ...]: the reference's actor_params;
     "actor_params" of state_dict()), live tensors updated in place; device_policy: a PerAgentRecurrentDevicePolicy over the same tensors
-    (built when None).  Refused before anything is built: group= (NotImplementedError: the data-parallel form is an open item), a
+    (built when None).  Refused before anything is built: group= (NotImplementedError: DataParallelPerAgentRecurrentLearner's), a
     device_policy that is not both per-agent and recurrent, actor tensors that are not stacked, share_actor: True, and whatever
     PerAgentRecurrentDevicePolicy and the cfg checks of RecurrentDeviceLearner refuse (PolicyConfigError)."""
     stacked_actor = True
 
     def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, generator=None, device_policy=None, agent_name="drone", group=None):
         if group is not None:
-            raise NotImplementedError("PerAgentRecurrentDeviceLearner takes no group=: data-parallel training of recurrent per-agent actors is an "
-                                      "open item (DESIGN-open-items.md #13)")
+            raise NotImplementedError("PerAgentRecurrentDeviceLearner takes no group=: data-parallel training of recurrent per-agent actors is "
+                                      "DataParallelPerAgentRecurrentLearner's")
         if device_policy is not None and not (getattr(device_policy, "per_agent", False) and getattr(device_policy, "recurrent", False)):
             raise P.PolicyConfigError("PerAgentRecurrentDeviceLearner needs a PerAgentRecurrentDevicePolicy (a shared recurrent actor is "
                                       "RecurrentDeviceLearner's, per-agent actors without an rnn PerAgentDeviceLearner's)")
@@ -630,7 +638,21 @@ class PerAgentRecurrentDeviceLearner(RecurrentDeviceLearner):
                                                     segment=idx, cfg=self.cfg, seq_len=self.train_seq_len, **kw)
 
 
-class DataParallelRecurrentLearner(RecurrentDeviceLearner):
+class _SegmentCounts:
+    """What a data-parallel learner over SEGMENTS replaces in its recurrent parent (DataParallelRecurrentLearner and
+    DataParallelPerAgentRecurrentLearner): the rollout's gather counts segments of train_seq_len steps, and the one refusal that depends on
+    this rank's count alone moves into that gather's table."""
+
+    def _rollout_counts(self, N, T, A):
+        L = self.train_seq_len
+        return self._global_counts(N * (T // L), A, unit="segments", rows_per_unit=L, more=(("actor.rnn.train_seq_len", L),))
+
+    def _check_segments(self, segments):
+        """Nothing here: a rank with fewer segments than minibatches is refused from the gather's table, on EVERY rank (this rank alone
+        raising would leave the others waiting in the gather)."""
+
+
+class DataParallelRecurrentLearner(_SegmentCounts, RecurrentDeviceLearner):
     """`RecurrentDeviceLearner` over a process group: W ranks, each with the recurrent rollout of its own env slice, perform
     ONE PPO update per minibatch on the union of their minibatches of segments.  group: a torch.distributed process group or "world"
     (required).  What `DeviceLearner(group=)` does for the non-recurrent networks, with the recurrent pieces in place:
@@ -660,10 +682,43 @@ class DataParallelRecurrentLearner(RecurrentDeviceLearner):
                          agent_name=agent_name)
         self._join(group)
 
-    def _rollout_counts(self, N, T, A):
-        L = self.train_seq_len
-        return self._global_counts(N * (T // L), A, unit="segments", rows_per_unit=L, more=(("actor.rnn.train_seq_len", L),))
 
-    def _check_segments(self, segments):
-        """Nothing here: a rank with fewer segments than minibatches is refused from the gather's table, on EVERY rank (this rank alone
-        raising would leave the others waiting in the gather)."""
+class DataParallelPerAgentLearner(PerAgentDeviceLearner):
+    """`PerAgentDeviceLearner` over a process group (share_actor: False, data-parallel): what `DeviceLearner(group=)` does for
+    the shared actor, with the actor block through actor_train.update_actor_per_agent_global.  group: a torch.distributed process group or
+    "world" (required).  Rank 0 broadcasts the 23 STACKED actor tensors, the critic, the predictor, ValueNorm1's buffers and the three Adam
+    states; per train_rollout one gather (DeviceLearner(group=)'s table and refusals); per minibatch the actor's
+    hns_actor_train_grad_agents_global, the SUM all-reduce of the bucket over the stacked tensors, hns_grad_norm, ONE step; the critic block is
+    DeviceLearner(group=)'s, unchanged — three collectives per minibatch pair.  The info row goes through _reduce_info as it is.  With one rank
+    every parameter and every entry of the info row is PerAgentDeviceLearner's, as DeviceLearner(group=) is DeviceLearner's."""
+
+    def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, agent_name="drone", generator=None, device_policy=None, group=None):
+        if group is None:
+            raise ValueError("DataParallelPerAgentLearner needs group=: a torch.distributed process group or \"world\" (one process: "
+                             "PerAgentDeviceLearner)")
+        super().__init__(actor, critic, cfg, tp_net=tp_net, value_normalizer=value_normalizer, agent_name=agent_name, generator=generator,
+                         device_policy=device_policy)
+        self._join(group)
+
+    def _actor_step(self, idx, obs, action, log_probs, adv, recurrent, **kw):
+        return actor_train.update_actor_per_agent_global(self.actor, *obs, action, log_probs, adv, self.actor_opt, index=idx, cfg=self.cfg, **kw)
+
+
+class DataParallelPerAgentRecurrentLearner(_SegmentCounts, PerAgentRecurrentDeviceLearner):
+    """`PerAgentRecurrentDeviceLearner` over a process group (share_actor: False with actor.rnn / critic.rnn, data-parallel):
+    `DataParallelRecurrentLearner`'s construction, gather, collectives and info row, with the actor step through
+    rnn_train.update_actor_rnn_per_agent_global — the encoder op, the GRU op and hns_rnn_actor_head_grad_agents_global on the stacked tensors,
+    the SUM all-reduce of ONE bucket over the 29 stacked tensors, ONE norm, ONE step.  group: required.  With one rank every parameter and every
+    entry of the info row has PerAgentRecurrentDeviceLearner's bits."""
+
+    def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, generator=None, device_policy=None, agent_name="drone", group=None):
+        if group is None:
+            raise ValueError("DataParallelPerAgentRecurrentLearner needs group=: a torch.distributed process group or \"world\" (one process: "
+                             "PerAgentRecurrentDeviceLearner)")
+        super().__init__(actor, critic, cfg, tp_net=tp_net, value_normalizer=value_normalizer, generator=generator, device_policy=device_policy,
+                         agent_name=agent_name)
+        self._join(group)
+
+    def _actor_step(self, idx, obs, action, log_probs, adv, rk, **kw):
+        return rnn_train.update_actor_rnn_per_agent_global(self.actor, *obs, rk["actor_rnn_state"], rk["is_init"], action, log_probs, adv, self.actor_opt,
+                                                           segment=idx, cfg=self.cfg, seq_len=self.train_seq_len, **kw)

@@ -26,7 +26,9 @@ from y without a second encoder and GRU pass.
 The `*_per_agent` functions are the actor's update with share_actor: False (one actor AND one actor GRU per agent: the reference's stacked
 `actor_params`, every tensor [A, ...]) through the SAME path: the encoder op and the GRU op take the stacked tensors
 (`hns_encoder_*_agents`, `hns_gru_*_agents`), the head entry is `hns_rnn_actor_head_grad_agents`, and ONE bucket, ONE norm and ONE ClippedAdam
-step run over the 29 stacked tensors.  The critic stays shared: `update_critic_rnn`, untouched.  No data-parallel form.
+step run over the 29 stacked tensors.  The critic stays shared: `update_critic_rnn`, untouched.  Their data-parallel forms are
+`policy_loss_and_grad_rnn_per_agent_global` / `update_actor_rnn_per_agent_global` (`hns_rnn_actor_head_grad_agents_global`, the bucket over the
+29 stacked tensors).
 
 CPU tensors run the same statements in torch: `policy_train.encoder`, `rnn.restatement`, and `actor_head` / `critic_head` — the head and the
 loss written out with their hand-derived dy (what the kernels compute, not autograd of another formula); the encoder's and the GRU's
@@ -102,12 +104,11 @@ def actor_head(head_w, head_b, log_std, y, action, log_probs_old, advantages, cl
     `global_rows`: hns_rnn_actor_head_grad_global's — every mean divides by the union's row count, policy_loss is this part's share and
     d_log_std takes `entropy_share` of the entropy term's constant gradient; ess stays the part's own.
     One head per agent (hns_rnn_actor_head_grad_agents): head_w [A, 4, 128], head_b / log_std [A, 4] — row (b, t, a) runs on slice a, the
-    gradients are stacked the same way, entropy is the mean over the agents of each agent's and every d_log_std[a] takes -entropy_coef / A."""
+    gradients are stacked the same way, entropy is the mean over the agents of each agent's and every d_log_std[a] takes -entropy_coef / A
+    (with `global_rows`, hns_rnn_actor_head_grad_agents_global's: -(entropy_coef entropy_share) / A, and every mean over the union)."""
     B = y.shape[0]
     n = float(y.shape[0] * y.shape[1] * y.shape[2]) if global_rows is None else float(global_rows)
     per_agent = head_w.dim() == 3
-    if per_agent and global_rows is not None:
-        raise NotImplementedError("one head per agent has no data-parallel form")
     mu = torch.einsum("blah,aoh->blao", y, head_w) + head_b if per_agent else y @ head_w.t() + head_b
     # logp is formed in fp64 from the fp32 mean (its rounding is the ratio's relative error), as the kernel forms it
     iv64 = torch.exp(-2.0 * log_std.double())
@@ -127,7 +128,8 @@ def actor_head(head_w, head_b, log_std, y, action, log_probs_old, advantages, cl
     if per_agent:
         A = head_w.shape[0]
         return {"dy": torch.einsum("blao,aoh->blah", dmu, head_w), "d_head_w": torch.einsum("blao,blah->aoh", dmu, y), "d_head_b": dmu.sum((0, 1)),
-                "d_log_std": (dlogp * (z2 - 1.0)).sum((0, 1)) - entropy_coef / A, "policy_loss": -float(P.ACTION_DIM) * torch.minimum(s1, s2).mean(),
+                "d_log_std": (dlogp * (z2 - 1.0)).sum((0, 1)) - (entropy_coef if global_rows is None else entropy_coef * entropy_share) / A,
+                "policy_loss": -float(P.ACTION_DIM) * (torch.minimum(s1, s2).mean() if global_rows is None else torch.minimum(s1, s2).sum() / n),
                 "entropy": (0.5 + LOG_SQRT_2PI + log_std).sum(-1).mean(), "ess": ess, "log_probs": logp}
     return {"dy": dmu @ head_w, "d_head_w": flat(dmu).t() @ flat(y), "d_head_b": flat(dmu).sum(0),
             "d_log_std": flat(dlogp * (z2 - 1.0)).sum(0) - (entropy_coef if global_rows is None else entropy_coef * entropy_share),
@@ -485,12 +487,28 @@ def policy_loss_and_grad_rnn_per_agent(actor, obs_self, obs_others, obs_cylinder
     on slice a, and every stacked tensor's .grad is as zero_grad() + backward() leave it (agent a's slice from its own rows).  policy_loss is
     -4 times the mean over ALL B L A rows, entropy the mean over the agents of each agent's (each d log_std takes -entropy_coef / A), ess as
     for the shared actor, grad_norm ONE norm over all 29 stacked tensors.  Arguments, layouts, `workspace`, `out` and `bucket`
-    (make_bucket(stacked=True)) as `policy_loss_and_grad_rnn`; `is_init` is env-level and holds for all agents.  No data-parallel form:
-    `global_rows=` / `group=` raise NotImplementedError."""
+    (make_bucket(stacked=True)) as `policy_loss_and_grad_rnn`; `is_init` is env-level and holds for all agents.  This is the local call:
+    `global_rows=` / `group=` raise NotImplementedError — the data-parallel form is `policy_loss_and_grad_rnn_per_agent_global`."""
     if global_rows is not None or group is not None:
-        raise NotImplementedError("one recurrent actor per agent has no data-parallel form yet (DESIGN-open-items.md #13)")
+        raise NotImplementedError("policy_loss_and_grad_rnn_per_agent is the local call: the data-parallel form (global_rows=, group=) is "
+                                  "rnn_train.policy_loss_and_grad_rnn_per_agent_global")
     return _policy_loss_and_grad(True, actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, segment,
                                  seq_len, clip_param, entropy_coef, check_index, workspace, out, bucket, None, 1.0, None)
+
+
+def policy_loss_and_grad_rnn_per_agent_global(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages,
+                                              segment=None, seq_len=16, clip_param=0.1, entropy_coef=0.001, check_index=True, workspace=None, out=None,
+                                              bucket=None, global_rows=None, entropy_share=1.0, group=None):
+    """`policy_loss_and_grad_rnn_per_agent` as one rank's part of a data-parallel update over a union of `global_rows` rows
+    (hns_rnn_actor_head_grad_agents_global), with `policy_loss_and_grad_rnn(global_rows=...)`'s semantics: policy_loss is this
+    rank's SHARE, every stacked gradient the share's, each agent's d log_std takes (-entropy_coef entropy_share) / A, entropy is the same on
+    every rank, ess stays this rank's own.  `bucket` (make_bucket(stacked=True)): the 29 stacked tensors' GradBucket, grad_norm its norm (None
+    without one); `group`: the bucket is all-reduced (SUM) over it first.  With global_rows = the call's own B L A and entropy_share 1 every
+    output has the local call's bits."""
+    if global_rows is None:
+        raise ValueError("policy_loss_and_grad_rnn_per_agent_global needs global_rows= (the local call is policy_loss_and_grad_rnn_per_agent)")
+    return _policy_loss_and_grad(True, actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, segment,
+                                 seq_len, clip_param, entropy_coef, check_index, workspace, out, bucket, global_rows, entropy_share, group)
 
 
 def _policy_loss_and_grad(stacked, actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, segment,
@@ -508,7 +526,7 @@ def _policy_loss_and_grad(stacked, actor, obs_self, obs_others, obs_cylinders, a
     def launch(lib, p, rows, per_row, dy, g, scal, hws, nbytes, st, dims):
         log_probs = torch.empty(*dims, 1, dtype=torch.float32, device=hws.device)
         entry, more = (lib.hns_rnn_actor_head_grad_agents if stacked else lib.hns_rnn_actor_head_grad, ()) if global_rows is None else \
-            (lib.hns_rnn_actor_head_grad_global, (int(global_rows), float(entropy_share)))
+            (lib.hns_rnn_actor_head_grad_agents_global if stacked else lib.hns_rnn_actor_head_grad_global, (int(global_rows), float(entropy_share)))
         rc = entry(p["head_w"].data_ptr(), p["head_b"].data_ptr(), p["log_std"].data_ptr(), C.byref(rows), *(t.data_ptr() for t in per_row),
                    float(clip_param), float(entropy_coef), dy.data_ptr(), g["head_w"].data_ptr(), g["head_b"].data_ptr(), g["log_std"].data_ptr(),
                    scal[0:].data_ptr(), scal[1:].data_ptr(), scal[2:].data_ptr(), log_probs.data_ptr(), hws.data_ptr(), nbytes, st, *more)
@@ -619,14 +637,33 @@ def update_actor_rnn_per_agent(actor, obs_self, obs_others, obs_cylinders, actor
                                segment=None, cfg=None, seq_len=None, check_index=False, workspace=None, out=None, bucket=None, global_rows=None, group=None):
     """`update_actor_rnn` with one actor per agent (MAPPOPolicy.update_actor with share_actor: False and actor.rnn):
     `policy_loss_and_grad_rnn_per_agent`, then the clip and the Adam step of `optimizer` (make_optimizer_per_agent) over the 29 stacked
-    tensors.  The same info dict.  `global_rows=` / `group=` raise NotImplementedError."""
+    tensors.  The same info dict.  `global_rows=` / `group=` raise NotImplementedError: the data-parallel form is
+    `update_actor_rnn_per_agent_global`."""
     if global_rows is not None or group is not None:
-        raise NotImplementedError("one recurrent actor per agent has no data-parallel form yet (DESIGN-open-items.md #13)")
+        raise NotImplementedError("update_actor_rnn_per_agent is the local call: the data-parallel form (global_rows=, group=) is "
+                                  "rnn_train.update_actor_rnn_per_agent_global")
     PT.check_optimizer(optimizer, "update_actor_rnn_per_agent", "rnn_train.make_optimizer_per_agent")
     get = PT.getter(cfg)
     L = int(seq_len) if seq_len is not None else train_seq_len(cfg)
     res = policy_loss_and_grad_rnn_per_agent(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages,
                                              segment, L, float(get("clip_param", 0.1)), float(get("entropy_coef", 0.001)), check_index, workspace, out, bucket)
+    return {"policy_loss": res.policy_loss, "actor_grad_norm": PT.clipped_step(optimizer, res.grad_norm), "entropy": res.entropy, "ESS": res.ess}
+
+
+def update_actor_rnn_per_agent_global(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old, advantages, optimizer,
+                                      segment=None, cfg=None, seq_len=None, check_index=False, workspace=None, out=None, bucket=None, global_rows=None,
+                                      entropy_share=1.0, group=None):
+    """`update_actor_rnn_per_agent` as one rank's part of a data-parallel update: `policy_loss_and_grad_rnn_per_agent_global`
+    — forward, the global per-agent head entry, backward, the bucket's all-reduce and norm — then the clip and the Adam step over the 29
+    stacked tensors; one collective.  `global_rows` and `bucket` are required (`group` may be None where the caller summed the buckets)."""
+    if global_rows is None or bucket is None:
+        raise ValueError("update_actor_rnn_per_agent_global steps on the bucket's norm over the union: pass global_rows= and bucket=")
+    PT.check_optimizer(optimizer, "update_actor_rnn_per_agent_global", "rnn_train.make_optimizer_per_agent")
+    get = PT.getter(cfg)
+    L = int(seq_len) if seq_len is not None else train_seq_len(cfg)
+    res = policy_loss_and_grad_rnn_per_agent_global(actor, obs_self, obs_others, obs_cylinders, actor_rnn_state, is_init, action, log_probs_old,
+                                                    advantages, segment, L, float(get("clip_param", 0.1)), float(get("entropy_coef", 0.001)), check_index,
+                                                    workspace, out, bucket, global_rows, entropy_share, group)
     return {"policy_loss": res.policy_loss, "actor_grad_norm": PT.clipped_step(optimizer, res.grad_norm), "entropy": res.entropy, "ESS": res.ess}
 
 

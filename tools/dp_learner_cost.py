@@ -6,6 +6,9 @@ minibatch pair — with nobody to wait for.  ONE process, alternating timed bloc
 between two synchronisations, wall time per rollout.  Both arms start every block from the same weights and the same generator seed.
 
   dp_learner_cost.py [--envs 2048 --steps 64 --epochs 4 --minibatches 16 --blocks 5 --reps 2 --backend gloo]
+  dp_learner_cost.py --per-agent    the same two arms with one actor per agent (share_actor: False): PerAgentDeviceLearner
+                                    against DataParallelPerAgentLearner over the one-rank group (hns_actor_train_grad_agents_global, the
+                                    bucket over the 23 stacked tensors)
   dp_learner_cost.py --profile      one plain update pair and hns_grad_norm at the actor's and the critic's bucket sizes, for a
                                     `rocprofv3 --kernel-trace --stats` run of its own: hns_grad_norm's two kernels beside the
                                     hns_critic_norm_kernel launch they replace
@@ -40,12 +43,19 @@ CFG = {"use_TP_net": 1, "ppo_epochs": 4, "num_minibatches": 16, "TP_epochs": 1, 
        "actor": {"lr": 5e-4, "weight_decay": 0.0, "tanh": False}, "critic": {"lr": 5e-4, "weight_decay": 0.0, "use_huber_loss": True, "huber_delta": 10}}
 
 
-def make_learner(start, cfg, group):
-    state = {"actor": {k: torch.nn.Parameter(v.detach().clone()) for k, v in start["actor"].items()},
+def make_learner(start, cfg, group, per_agent=False):
+    """per_agent: the shared actor stacked over the agents (slice a shifted by 0.01 a: the agents differ), share_actor: False."""
+    stack = (lambda v: torch.stack([v.detach() + 0.01 * a for a in range(LCOST.A)]).contiguous()) if per_agent else (lambda v: v.detach().clone())
+    state = {"actor": {k: torch.nn.Parameter(stack(v)) for k, v in start["actor"].items()},
              "critic": {k: torch.nn.Parameter(v.detach().clone()) for k, v in start["critic"].items()}, "tp": copy.deepcopy(start["tp"]),
              "vn": copy.deepcopy(start["vn"])}
-    return learner.DeviceLearner(state["actor"], state["critic"], cfg, tp_net=state["tp"], value_normalizer=state["vn"],
-                                 generator=torch.Generator(device="cuda").manual_seed(5), group=group)
+    args = dict(tp_net=state["tp"], value_normalizer=state["vn"], generator=torch.Generator(device="cuda").manual_seed(5))
+    if not per_agent:
+        return learner.DeviceLearner(state["actor"], state["critic"], cfg, group=group, **args)
+    cfg = dict(cfg, share_actor=False)
+    if group is None:
+        return learner.PerAgentDeviceLearner(state["actor"], state["critic"], cfg, **args)
+    return learner.DataParallelPerAgentLearner(state["actor"], state["critic"], cfg, group=group, **args)
 
 
 def profile(start, ro, cfg):
@@ -71,6 +81,7 @@ def main():
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--backend", default="gloo", help="the one-rank group's backend (gloo; nccl is RCCL)")
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--per-agent", action="store_true", help="one actor per agent: PerAgentDeviceLearner against DataParallelPerAgentLearner")
     args = ap.parse_args()
     cfg = dict(CFG, ppo_epochs=args.epochs, num_minibatches=args.minibatches)
     start = LCOST.make_state("cuda", cfg)
@@ -82,11 +93,11 @@ def main():
     arms = {"none": None, "group": dist.group.WORLD}
     times = {k: [] for k in arms}
     for k, g in arms.items():                                    # warm-up: workspaces, buckets, the kernels' first launches
-        make_learner(start, cfg, g).train_rollout(**ro)
+        make_learner(start, cfg, g, args.per_agent).train_rollout(**ro)
     torch.cuda.synchronize()
     for b in range(args.blocks):
         for k in (list(arms) if b % 2 == 0 else list(arms)[::-1]):
-            L = make_learner(start, cfg, arms[k])
+            L = make_learner(start, cfg, arms[k], args.per_agent)
             L.train_rollout(**ro)                                # (the learner's own first call allocates; not timed)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -95,7 +106,7 @@ def main():
             torch.cuda.synchronize()
             times[k].append((time.perf_counter() - t0) / args.reps * 1e3)
     pairs = args.epochs * args.minibatches
-    print(f"train_rollout, {args.envs} envs x {args.steps} steps x {LCOST.A} agents, {args.epochs} epochs x {args.minibatches} minibatches, predictor on; "
+    print(f"{'PerAgentDeviceLearner / DataParallelPerAgentLearner' if args.per_agent else 'DeviceLearner'}.train_rollout, {args.envs} envs x {args.steps} steps x {LCOST.A} agents, {args.epochs} epochs x {args.minibatches} minibatches, predictor on; "
           f"{args.blocks} alternating blocks of {args.reps} rollouts, ms per rollout")
     for k, v in times.items():
         print(f"  group={'None' if k == 'none' else 'one rank (' + args.backend + ')':<16} median {statistics.median(v):9.3f}  min {min(v):9.3f}  max {max(v):9.3f}")

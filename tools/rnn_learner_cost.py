@@ -14,13 +14,15 @@ included in both).  Times are wall clock around a block with a device synchronis
 
     python tools/rnn_learner_cost.py [--envs 2048 65536] [--rounds 5] [--pairs 8]
     python tools/rnn_learner_cost.py --trace          # a few (a) pairs at both sizes and nothing else: run under a kernel trace
-    python tools/rnn_learner_cost.py --group [--envs 2048] [--rounds 5]
+    python tools/rnn_learner_cost.py --group [--per-agent] [--envs 2048] [--rounds 5]
 
 --group (profiles/r24_dp_rnn_learner_cost.txt): one train_rollout with the predictor on (4 epochs x 16 minibatches) through
 RecurrentDeviceLearner without a group against DataParallelRecurrentLearner over a ONE-rank gloo group (a file store in a temporary directory),
 in alternating blocks of this one process, and the same group-less learner a second time: the spread.  The difference is the data-parallel
 path's cost with nobody to talk to — the global entries, the three collectives per minibatch pair, which gloo runs on host copies (a device
-synchronisation each): an upper bound of the path's host cost under gloo, not an RCCL figure."""
+synchronisation each): an upper bound of the path's host cost under gloo, not an RCCL figure.  --per-agent: the same three arms with one
+actor and one actor GRU per agent (profiles/r30_dp_per_agent_cost.txt): PerAgentRecurrentDeviceLearner against
+DataParallelPerAgentRecurrentLearner."""
 import argparse
 import os
 import statistics
@@ -171,7 +173,7 @@ def report(name, xs):
 HIST, FUTURE = 10, 5                                            # the predictor's window and horizon (tests/rnn_update_reference.py's)
 
 
-def group_cost(N, rounds):
+def group_cost(N, rounds, per_agent=False):
     import tempfile
 
     import torch.distributed as dist
@@ -185,20 +187,28 @@ def group_cost(N, rounds):
     with tempfile.TemporaryDirectory() as tmp:
         dist.init_process_group("gloo", rank=0, world_size=1, store=dist.FileStore(os.path.join(tmp, "store"), 1))
 
+        if per_agent:
+            cfg["share_actor"] = False
+        local, dp = (learner.PerAgentRecurrentDeviceLearner, learner.DataParallelPerAgentRecurrentLearner) if per_agent else \
+            (learner.RecurrentDeviceLearner, learner.DataParallelRecurrentLearner)
+
         def make(cls, **more):
             nets = Network(True, 0).to(DEV), Network(False, 1).to(DEV)
+            actor = nets[0].names()
+            if per_agent:                                        # A independently initialised actors, stacked
+                each = [actor] + [Network(True, 10 + a).to(DEV).names() for a in range(1, A)]
+                actor = {k: torch.stack([e[k].detach() for e in each]).contiguous() for k in actor}
             torch.manual_seed(5)
-            return cls(nets[0].names(), nets[1].names(), cfg, tp_net=TPNet(7 + 3 * A, 3 * FUTURE, FUTURE, 1).to(DEV),
+            return cls(actor, nets[1].names(), cfg, tp_net=TPNet(7 + 3 * A, 3 * FUTURE, FUTURE, 1).to(DEV),
                        value_normalizer=learner.ValueNorm1().to(DEV), generator=torch.Generator(device=DEV).manual_seed(2), **more)
-        arms = {"group=None": make(learner.RecurrentDeviceLearner), "group=None again": make(learner.RecurrentDeviceLearner),
-                "one-rank gloo group": make(learner.DataParallelRecurrentLearner, group="world")}
+        arms = {"group=None": make(local), "group=None again": make(local), "one-rank gloo group": make(dp, group="world")}
         times = {k: [] for k in arms}
         for arm in arms.values():
             arm.train_rollout(**kw, **rk)
         for _ in range(rounds):
             for k, arm in arms.items():
                 times[k].append(timed(lambda: arm.train_rollout(**kw, **rk), 1))
-        print(f"{N} envs x {T} steps x {A} agents, L = {L}, predictor on: one train_rollout (4 epochs x {M} minibatches = {4 * M} pairs)")
+        print(f"{local.__name__} / {dp.__name__}, {N} envs x {T} steps x {A} agents, L = {L}, predictor on: one train_rollout (4 epochs x {M} minibatches = {4 * M} pairs)")
         med = {k: report(k, v) for k, v in times.items()}
         extra = med["one-rank gloo group"] - med["group=None"]
         print(f"    spread group=None against itself: {abs(med['group=None'] - med['group=None again']):.3f} ms; the group's cost: {extra:.3f} ms a rollout, "
@@ -214,10 +224,11 @@ def main():
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--skip-reference", action="store_true", help="leave (c) out (it is the slowest arm by far at 65 536 envs)")
     ap.add_argument("--group", action="store_true", help="a one-rank gloo group against group=None, whole rollouts, predictor on")
+    ap.add_argument("--per-agent", action="store_true", help="with --group: one actor per agent (share_actor: False)")
     args = ap.parse_args()
     if args.group:
         for N in args.envs if args.envs != [2048, 65536] else [2048]:
-            group_cost(N, args.rounds)
+            group_cost(N, args.rounds, args.per_agent)
         return
     for N in args.envs:
         kw, rk = rollout(N)
