@@ -579,6 +579,41 @@ int hns_policy_forward_agents(const void *packed, int32_t self_dim, int64_t num_
                               int32_t flags, uint64_t seed, uint64_t *counter, void *stream);
 int hns_policy_act_agents(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders, const hns_policy_io *io,
                           void *stream);
+/*
+ * The centralised critic (cfg/algo/mappo.yaml's critic_input: state; make_critic(centralized=True), mappo.py:165-181, :553-566, :644-660;
+ * hns_amd.policy.CentralCriticDevicePolicy) beside the shared actor.  The critic is ONE row per env: a PartialAttentionEncoder
+ * over the state spec — the A rows of state_drones through ONE Linear(D, 128), then the K cylinder rows through Linear(5, 128); token 0 (drone
+ * 0) is the query — and v_out = Linear(128, A): value[e, a] = v_out.weight[a] . feat[e] + v_out.bias[a].  The entries above are unchanged.
+ *
+ * hns_policy_packed_central_bytes: bytes of the image [the shared actor's, the centralised critic's]; 0 for self_dim outside [1, 96] or
+ * num_agents outside [1, 7].
+ * hns_policy_pack_central: ONE launch builds that image (16-byte aligned); call it again after the parameters change.  Its first
+ * hns_policy_packed_bytes / 2 bytes are byte for byte the actor half of hns_policy_pack's image, so hns_policy_act serves this image
+ * unchanged.  `critic`: embed_self_w / embed_self_b are the state_drones embedding, embed_others_* must be NULL (the state has no such key),
+ * head_w is [A, 128] and head_b [A] with A = num_agents.  Refused before the launch: what hns_policy_pack refuses, and a critic with a
+ * state_others embedding.
+ * hns_policy_central_forward: hns_policy_forward's arguments, flags, outputs, output layouts, noise scheme and launch count (ONE launch, and
+ * the bump of the counter when the call samples without io->eps) with `state`, what the critic reads.  The grid is ceil(E A / 32) actor
+ * workgroups — tiles of 32 (env, agent) rows as hns_policy_forward's, whose action, log_prob and loc of every row are bit for bit
+ * hns_policy_forward's for the same actor, eps or (seed, *counter, row) — followed by ceil(E / 32) critic workgroups, tiles of 32 envs, which
+ * write io->value[e A + a] for a < A.  With one agent and `state` = the observation's rows, value is bit for bit hns_policy_forward's for the
+ * same 20 tensors.  HNS_POLICY_VALUE_ONLY launches the critic workgroups alone: the observation pointers are not read (NULL is fine) and
+ * action / log_prob / loc are untouched.  Refused before any launch, in hns_policy_forward's order: a NULL or misaligned packed image / io, a
+ * shape out of range, an unknown flag, (unless value-only) a missing or misaligned observation or a negative stride, a NULL state or a NULL or
+ * misaligned pointer or a negative stride in it, then the outputs as hns_policy_forward.  Deterministic: fixed-order sums, no atomics.
+ * (Named hns_policy_central_*, not hns_policy_forward_*: the eight hns_policy_forward* / hns_policy_act* entries are the four policy classes'
+ * table, keyed (agents, rnn, act), and this one takes a further argument.)
+ */
+typedef struct hns_policy_state {
+    const float *state_drones;             /* [E, A, D]: element (e, a, i) at e s[0] + a s[1] + i */
+    const float *cylinders;                /* [E, K, 5]: (e, k, i) at e s[0] + k s[1] + i.  s[0] = A K 5 reads agent 0's rows of a contiguous
+                                            * obs_cylinders [E, A, K, 5] in place */
+    int64_t drones_stride[2], cyl_stride[2];
+} hns_policy_state;
+size_t hns_policy_packed_central_bytes(int32_t self_dim, int32_t num_agents);
+int hns_policy_pack_central(const hns_policy_net *actor, const hns_policy_net *critic, int32_t self_dim, int32_t num_agents, void *packed, void *stream);
+int hns_policy_central_forward(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                               const hns_policy_io *io, const hns_policy_state *state, int32_t flags, uint64_t seed, uint64_t *counter, void *stream);
 
 /*
  * The MAPPO critic's update (learning/mappo.py:326-352 on make_critic's network at the defaults: critic_input obs, no rnn): value
@@ -615,6 +650,19 @@ size_t hns_critic_train_workspace_bytes(int64_t rows, int32_t self_dim, int32_t 
 int hns_critic_train_grad(const hns_policy_net *critic, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
                           float clip_param, int32_t loss_kind, float huber_delta, const hns_policy_grads *grads, float *value_loss,
                           float *explained_var, float *grad_norm, float *values, void *workspace, size_t workspace_bytes, void *stream);
+/* The centralised critic's update (critic_input: state; the network of hns_policy_central_forward; hns_amd.critic_train.update_critic_central;
+ * DESIGN.md §7.20): hns_critic_train_grad's arguments, outputs, scalars, launches (seven) and refusals on hns_critic_batch REINTERPRETED:
+ * obs_self is state_drones [N, T, A, D] — token j of an env-step's row at j self_stride[2] —, obs_others must be NULL (as the critic's
+ * embed_others_*: refused after the hyper-parameters), obs_cylinders is read at agent index 0 (cyl_stride[2] is ignored; cyl_stride[3] steps
+ * the K rows), b_values / b_returns / values stay [.., A].  A tile is 32 env-steps; a row's A values come from head_w [A, 128] and head_b [A] on
+ * its one feature vector; the means are over the batch x A values.  d head_w / d head_b come from the row's A value gradients, d embed_self_*
+ * sum over all A drone tokens (the query's through its key / value path and its residual path), there are no state_others gradients.  With
+ * one agent every output is bit for bit hns_critic_train_grad's on the same tensors.  hns_critic_train_central_workspace_bytes takes `batch`
+ * (env-steps, not batch x num_agents). */
+size_t hns_critic_train_central_workspace_bytes(int64_t batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders);
+int hns_critic_train_grad_central(const hns_policy_net *critic, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                                  float clip_param, int32_t loss_kind, float huber_delta, const hns_policy_grads *grads, float *value_loss,
+                                  float *explained_var, float *grad_norm, float *values, void *workspace, size_t workspace_bytes, void *stream);
 typedef struct hns_adam_tensor {
     float *param, *grad, *exp_avg, *exp_avg_sq;
     int64_t numel;

@@ -27,6 +27,12 @@ and otherwise not handed to the kernel at all.  The storage gains `is_init` [N, 
 last step's next `is_init` (its `done`) and critic state join `next_obs_last`.  `recurrent_kwargs()` hands them out.  A non-recurrent policy
 takes none of this: the same calls, launches and bits as before.
 
+With a policy that reads the state (`policy.needs_state`: CentralCriticDevicePolicy, critic_input: state) the collector reads
+("agents", "state", "state_drones") each step, hands it to `forward` and stores it as `state_drones` [N, T, A, D] — one more segment of the
+pre-step store, not one more launch — and the last step's next one beside `next_obs_last`; `learner_kwargs()` gains `state_drones` and
+`next_state_last`.  The state's cylinders are agent 0's rows of the stored obs_cylinders: no second copy is stored.  Every other policy takes
+none of this.
+
 CPU tensors take plain indexing assignment (tests; not the hot path).  DESIGN.md §7.7."""
 import ctypes as C
 
@@ -40,6 +46,7 @@ OBS_KEYS = (("obs_self", "state_self"), ("obs_others", "state_others"), ("obs_cy
 TP_KEYS = ("TP_input", "TP_groundtruth", "TP_done")
 LAST_NAMES = tuple(n for n, _ in OBS_KEYS)
 RNN_STATES = ("actor_rnn_state", "critic_rnn_state")
+STATE_NAME = "state_drones"                                     # storage name and key under ("agents", "state") of what a centralised critic reads
 RNN_LAST_NAMES = LAST_NAMES + ("critic_rnn_state", "is_init")   # what the bootstrap value of a recurrent critic needs beside the observation
 
 
@@ -170,6 +177,8 @@ class RolloutStorage:
               "next_obs_last": (l["obs_self"], l.get("obs_others"), l["obs_cylinders"]), "reward": d["reward"], "done": d["done"]}
         if "TP_input" in d:
             kw["tp"] = tuple(d[k] for k in TP_KEYS)
+        if STATE_NAME in d:                                      # a centralised critic's (CentralCriticDeviceLearner.train_rollout)
+            kw["state_drones"], kw["next_state_last"] = d[STATE_NAME], l[STATE_NAME]
         return kw
 
     def recurrent_kwargs(self):
@@ -203,6 +212,9 @@ class DeviceCollector:
             raise ValueError("num_steps must be >= 1")
         self.env, self.policy, self.num_steps = env, policy, int(num_steps)
         self.recurrent = bool(getattr(policy, "recurrent", False))
+        self.needs_state = bool(getattr(policy, "needs_state", False))
+        if self.recurrent and self.needs_state:
+            raise ValueError("a recurrent policy that reads the state is not supported")
         if self.recurrent:
             self.rnn_seq_len = 16 if rnn_seq_len is None else int(rnn_seq_len)          # the reference's train_seq_len
             if self.rnn_seq_len < 1 or self.num_steps % self.rnn_seq_len:
@@ -229,6 +241,10 @@ class DeviceCollector:
         obs = td[("agents", "observation")]
         return {name: _get(obs, key) for name, key in OBS_KEYS}
 
+    @staticmethod
+    def _state(td):
+        return td[("agents", "state")][STATE_NAME]
+
     def _done_count(self, done):
         """The loop's one host read-back: how many envs are done."""
         self.done_reads += 1
@@ -248,13 +264,16 @@ class DeviceCollector:
             obs = self._obs(cur)
             if self.recurrent:
                 out, rnn_pre = self._rnn_forward(t, obs)
+            elif self.needs_state:                               # (rnn_pre: what joins the pre-step store beside the observation)
+                rnn_pre = {STATE_NAME: self._state(cur)}
+                out = self.policy.forward(obs["obs_self"], obs["obs_others"], obs["obs_cylinders"], rnn_pre[STATE_NAME])
             else:
                 out, rnn_pre = self.policy.forward(obs["obs_self"], obs["obs_others"], obs["obs_cylinders"]), {}
             pre = {**obs, "action": out.action, "log_probs": out.log_prob, "state_value": out.value, **rnn_pre}
             if self.storage is None:
                 n = obs["obs_self"].shape[0]
                 self.storage = RolloutStorage(n, T, {k: v for k, v in pre.items() if v is not None},
-                                              last=RNN_LAST_NAMES if self.recurrent else LAST_NAMES)
+                                              last=RNN_LAST_NAMES if self.recurrent else LAST_NAMES + (STATE_NAME,) if self.needs_state else LAST_NAMES)
                 if self.recurrent:
                     self.storage.allocate_segments(dict(zip(RNN_STATES, self._states)), self.rnn_seq_len)
             self.storage.store(t, pre)
@@ -277,7 +296,7 @@ class DeviceCollector:
             if t == T - 1:
                 # (recurrent: the next step's is_init is this step's done, and the reset below leaves the states alone)
                 self.storage.store_last({**self._obs(nxt), "critic_rnn_state": self._states[1], "is_init": done} if self.recurrent
-                                        else self._obs(nxt))
+                                        else {**self._obs(nxt), STATE_NAME: self._state(nxt)} if self.needs_state else self._obs(nxt))
             cur = nxt
             self._since_full_reset += 1
             if self._since_full_reset >= self.max_episode_length:

@@ -15,6 +15,9 @@ five fp64 sums of this rank's rows (`hns_critic_train_sums`); the caller adds th
 decides on the union's sums and scales the rows by 1 / global_rows (`hns_critic_train_grad_global`), so the ranks' gradients add up to the
 union's in a `policy_train.GradBucket`.  `update_critic(group=)` runs the whole sequence.
 
+`value_loss_and_grad_central` / `update_critic_central` are the same two functions for the centralised critic (critic_input: state): ONE call
+of `hns_critic_train_grad_central` on tiles of env-steps, the state read in place.
+
 `update_critic` is the reference's function.  CPU tensors run the reference's torch statements throughout (CPU tests, gloo runs — not the
 hot path).  DESIGN.md §7.4."""
 import collections
@@ -211,10 +214,10 @@ def value_loss_and_grad(critic, obs_self, obs_others, obs_cylinders, b_values, b
     return CriticLoss(scal[0], scal[1], scal[2], values)
 
 
-def critic_cfg(cfg):
-    """The refusals of the critic's part of the algo cfg (policy.check_config's, then critic.lr_scheduler, critic.weight_decay,
-    critic.num_critics); returns the cfg's and the critic section's getters."""
-    P.check_config(cfg)
+def critic_cfg(cfg, central=False):
+    """The refusals of the critic's part of the algo cfg (policy.check_config's — central: policy.check_config_central's —, then
+    critic.lr_scheduler, critic.weight_decay, critic.num_critics); returns the cfg's and the critic section's getters."""
+    (P.check_config_central if central else P.check_config)(cfg)
     sget = PT.getter(PT.getter(cfg)("critic", None))
     if sget("lr_scheduler", None):
         raise P.PolicyConfigError("critic.lr_scheduler is not supported")
@@ -226,9 +229,11 @@ def critic_cfg(cfg):
 
 
 def make_optimizer(critic, cfg=None):
-    """The reference's critic_opt (mappo.py:198-200) as a ClippedAdam: cfg is the algo cfg (critic.lr, critic.weight_decay, max_grad_norm)."""
-    get, sget = critic_cfg(cfg)
-    return ClippedAdam(critic_parameters(critic).values(), lr=float(sget("lr", 5e-4)), max_grad_norm=get("max_grad_norm", 10.0),
+    """The reference's critic_opt (mappo.py:198-200) as a ClippedAdam: cfg is the algo cfg (critic.lr, critic.weight_decay, max_grad_norm).
+    The centralised critic (its parameters embed state_drones) is taken with its own 20 tensors and critic_input: state."""
+    central = is_central(critic)
+    get, sget = critic_cfg(cfg, central=central)
+    return ClippedAdam((central_critic_parameters(critic) if central else critic_parameters(critic)).values(), lr=float(sget("lr", 5e-4)), max_grad_norm=get("max_grad_norm", 10.0),
                        weight_decay=float(sget("weight_decay", 0.0) or 0.0))
 
 
@@ -254,4 +259,144 @@ def update_critic(critic, obs_self, obs_others, obs_cylinders, b_values, b_retur
         sums = sharding.all_reduce_sum(value_loss_sums(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, index, **kw).sums, group)
     res = value_loss_and_grad(critic, obs_self, obs_others, obs_cylinders, b_values, b_returns, index, out=out, sums=sums, global_rows=global_rows,
                               group=group, bucket=bucket, **kw)
+    return {"value_loss": res.value_loss, "critic_grad_norm": PT.clipped_step(optimizer, res.grad_norm), "explained_var": res.explained_var}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The centralised critic (critic_input: state; policy.CentralCriticDevicePolicy): ONE row per env-step over the state —
+# the A rows of state_drones through one embedding, then the K cylinders — and v_out = Linear(128, A).  b_values, b_returns, the value
+# loss (the mean over batch x A values), ValueNorm and GAE are the obs critic's.
+
+def central_critic_parameters(critic):
+    """The centralised critic's 20 tensors by hns_policy_net field (embed_self_*: the state_drones embedding), in registration order."""
+    return P.parse_parameters_central(critic, "critic")[0]
+
+
+def is_central(critic):
+    """Whether `critic` (any source `parse_parameters` reads) is the centralised critic: it embeds state_drones."""
+    return any(".state_drones." in "." + P._strip(k) for k in P._flatten(critic))
+
+
+def _central_state(state_drones, state_cylinders):
+    """(state_drones [N, T, A, D], the state's cylinders [N, T, K, 5]) as views: a flat [R, ...] batch is [R, 1, ...]; cylinders given as the
+    rollout's obs_cylinders [N, T, A, K, 5] are agent 0's rows of it, in place."""
+    sd, sc = state_drones, state_cylinders
+    if sd.dim() == 3:
+        sd, sc = sd.unsqueeze(1), sc.unsqueeze(1)
+    if sd.dim() != 4:
+        raise ValueError(f"state_drones must be [N, T, A, D] or [R, A, D], not {tuple(state_drones.shape)}")
+    if sc.dim() == 5:
+        sc = sc[:, :, 0]
+    return sd, sc
+
+
+def _validate_central(p, sd, sc, b_values, b_returns, index, check_index):
+    """policy_train.validate's refusals for the centralised critic's tensors; returns (N, T, A, D, K)."""
+    for k, t in p.items():
+        if not t.is_contiguous():
+            raise ValueError(f"critic parameter {k} must be contiguous")
+    D, A = int(p["embed_self_w"].shape[1]), int(p["head_w"].shape[0])
+    N, T, Ax, Dx = sd.shape
+    if Dx != D:
+        raise ValueError(f"state_drones rows have {Dx} values, the critic takes {D}")
+    if Ax != A:
+        raise ValueError(f"state_drones holds {Ax} drones, v_out has {A} rows")
+    if sc.dim() != 4 or tuple(sc.shape[:2]) != (N, T) or sc.shape[-1] != 5 or not 1 <= sc.shape[2] <= abi.HNS_MAX_CYLINDERS:
+        raise ValueError(f"the state's cylinders must be [{N}, {T}, K, 5] (or the rollout's [{N}, {T}, {A}, K, 5]) with K in "
+                         f"[1, {abi.HNS_MAX_CYLINDERS}], not {tuple(sc.shape)}")
+    for name, t in (("state_drones", sd), ("cylinders", sc), ("b_values", b_values), ("b_returns", b_returns)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, not {t.dtype}")
+    steps = N * T
+    if steps == 0:
+        raise ValueError("the rollout holds no env-step")
+    for name, t in (("b_values", b_values), ("b_returns", b_returns)):
+        if t.numel() != steps * A:
+            raise ValueError(f"{name} must hold [N * T, A] = [{steps}, {A}] values, not {tuple(t.shape)}")
+    if index is not None:
+        if index.dtype != torch.int64 or index.dim() != 1:
+            raise TypeError("index must be a 1-d int64 tensor")
+        if index.numel() < 1:
+            raise ValueError("empty minibatch: the mean over zero rows is NaN")
+        if not index.is_contiguous():
+            raise ValueError("index must be contiguous (the kernel reads it in place as consecutive int64): pass index.contiguous()")
+        if check_index and not (sd.is_cuda and torch.cuda.is_current_stream_capturing()):
+            lo, hi = torch.stack([index.min(), index.max()]).tolist()     # one host synchronisation
+            if lo < 0 or hi >= steps:
+                raise IndexError(f"index values [{lo}, {hi}] outside the {steps} env-steps of the rollout")
+    devs = {t.device for t in (*p.values(), sd, sc, b_values, b_returns)} | ({index.device} if index is not None else set())
+    if len(devs) != 1:
+        raise ValueError(f"parameters, state, b_values, b_returns and index must share one device, not {devs}")
+    return N, T, A, D, int(sc.shape[2])
+
+
+def _torch_loss_and_grad_central(p, sd, sc, b_values, b_returns, index, clip_param, loss, huber_delta):
+    """update_critic's statements (mappo.py:328-341) on the gathered minibatch of the centralised critic: values [B, A, 1] from ONE encoder
+    row per env-step (Critic.forward with centralized=True, mappo.py:644-660); autograd through policy_train's encoder."""
+    N, T, A, D = sd.shape
+    sd, sc = sd.reshape(N * T, A, D), sc.reshape(N * T, sc.shape[2], 5)
+    bv, ret = b_values.reshape(N * T, A, 1), b_returns.reshape(N * T, A, 1)
+    if index is not None:
+        sd, sc, bv, ret = sd[index], sc[index], bv[index], ret[index]
+    leaves = {k: v.detach().requires_grad_(True) for k, v in p.items()}
+    values = F.linear(PT.encoder(leaves, sd, None, sc), leaves["head_w"], leaves["head_b"]).unsqueeze(-1)
+    clipped = bv + (values - bv).clamp(-clip_param, clip_param)
+    loss_fn = nn.HuberLoss(delta=huber_delta) if loss == "huber" else nn.MSELoss()
+    l_clip = loss_fn(ret, clipped)
+    l_orig = loss_fn(ret, values)
+    value_loss = torch.max(l_orig, l_clip)
+    grads = torch.autograd.grad(value_loss, list(leaves.values()))
+    for t, g in zip(p.values(), grads):
+        t.grad = g
+    with torch.no_grad():
+        grad_norm = nn.utils.clip_grad_norm_(list(p.values()), float("inf"))
+        # in fp64 from the fp32 values, as the kernel's loss partials: 1 - mse / var cancels, and in fp32 the rounding of that difference
+        # (one ulp of 1) is many ulps of a small explained variance
+        explained_var = (1 - F.mse_loss(values.double(), ret.double()) / ret.double().var()).to(torch.float32)
+    return CriticLoss(value_loss.detach(), explained_var, grad_norm, values.detach())
+
+
+def value_loss_and_grad_central(critic, state_drones, state_cylinders, b_values, b_returns, index=None, clip_param=0.1, loss="huber",
+                                huber_delta=10.0, check_index=True, workspace=None, out=None):
+    """`value_loss_and_grad` for the centralised critic, ONE call of `hns_critic_train_grad_central`: the clipped value loss over the
+    minibatch's batch x A values and every parameter's .grad.  Returns CriticLoss(value_loss, explained_var, grad_norm; values [B, A, 1]).
+
+    state_drones: the rollout's [N, T, A, D] (or a flat [R, A, D]), read in place; state_cylinders: [N, T, K, 5] — any strided view, so the
+    stored obs_cylinders[:, :, 0] costs no copy — or the rollout's obs_cylinders [N, T, A, K, 5] itself, of which agent 0's rows are read;
+    b_values, b_returns, index, check_index, workspace (hns_critic_train_central_workspace_bytes bytes) and out: value_loss_and_grad's."""
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be 'huber' or 'mse', not {loss!r}")
+    if not clip_param >= 0 or (loss == "huber" and not huber_delta > 0):
+        raise ValueError("clip_param must be >= 0 and huber_delta > 0")
+    p = central_critic_parameters(critic)
+    sd, sc = _central_state(state_drones, state_cylinders)
+    shape = _validate_central(p, sd, sc, b_values, b_returns, index, check_index)
+    if not sd.is_cuda:
+        return _torch_loss_and_grad_central(p, sd, sc, b_values, b_returns, index, float(clip_param), loss, float(huber_delta))
+    lib = abi.load_library()
+    bv, ret = b_values.contiguous(), b_returns.contiguous()
+    _, _, A, D, K = shape
+    # the batch struct reinterpreted (include/hns.h): obs_self is state_drones, obs_cylinders the [N, T, K, 5] view with a unit agent axis
+    net, grd, b, ws, nbytes, scal, B, st = PT.prepare_call(
+        "critic", p, sd, None, sc.unsqueeze(2), index, shape,
+        lambda rows, D_, A_, K_: lib.hns_critic_train_central_workspace_bytes(rows // A_, D_, A_, K_), workspace, out, 3, abi.HnsCriticBatch)
+    b.b_values, b.b_returns = bv.data_ptr(), ret.data_ptr()
+    values = torch.empty(B, A, 1, dtype=torch.float32, device=sd.device)
+    with torch.cuda.device(sd.device):
+        rc = lib.hns_critic_train_grad_central(C.byref(net), C.byref(b), D, A, K, float(clip_param), LOSSES[loss], float(huber_delta), C.byref(grd),
+                                               scal[0:].data_ptr(), scal[1:].data_ptr(), scal[2:].data_ptr(), values.data_ptr(), ws.data_ptr(), nbytes,
+                                               st)
+    abi.check(rc, "hns_critic_train_grad_central")
+    return CriticLoss(scal[0], scal[1], scal[2], values)
+
+
+def update_critic_central(critic, state_drones, state_cylinders, b_values, b_returns, optimizer, index=None, cfg=None, check_index=False,
+                          workspace=None, out=None):
+    """MAPPOPolicy.update_critic on one minibatch with the centralised critic: loss, backward, clip_grad_norm_, Adam.  `update_critic`'s
+    cfg, info dict ({"value_loss", "critic_grad_norm", "explained_var"} as 0-dim tensors), optimizer, index and workspace handling; the
+    state arguments are value_loss_and_grad_central's.  A process group is not supported (there is no data-parallel form)."""
+    get, sget = PT.check_optimizer(optimizer, "update_critic_central", "critic_train.make_optimizer", lambda c: critic_cfg(c, central=True), cfg)
+    res = value_loss_and_grad_central(critic, state_drones, state_cylinders, b_values, b_returns, index, clip_param=float(get("clip_param", 0.1)),
+                                      loss="huber" if sget("use_huber_loss", True) else "mse", huber_delta=float(sget("huber_delta", 10.0)),
+                                      check_index=check_index, workspace=workspace, out=out)
     return {"value_loss": res.value_loss, "critic_grad_norm": PT.clipped_step(optimizer, res.grad_norm), "explained_var": res.explained_var}

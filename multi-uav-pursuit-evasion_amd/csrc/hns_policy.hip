@@ -44,6 +44,9 @@
 //                                       fragment order (one float4 per lane per four k-steps), the vectors, the head, the embedding weights
 //                                       transposed.  The shared image [actor, critic] is the per-agent image [A actors, critic] at one actor.
 //   hns_policy_rnn_pack_agents_kernel : the GRUs' tensors -> their packed images, the same way.
+//   hns_policy_forward_central_kernel : the centralised critic's configuration (critic_input: state): the grid is the shared
+//                                       actor's tiles — pol_tile's actor pass — followed by the critic's tiles of 32 ENVS on pol_encoder<true>
+//                                       (the state's tokens) and a head of A rows; hns_policy_pack_central_kernel builds its image.
 //   hns_policy_bump_kernel            : the device call counter += 1 after a sampling call (Philox counter; a captured graph draws fresh noise
 //                                       per replay).
 // Determinism: fixed reduction orders (butterflies over the eight lanes of a row), no atomics.
@@ -112,6 +115,27 @@ HNS_DEV float pol_src(const EncNet &s, int D, long long i) {
     return s.ew[2][f * 5 + (in - D - 3)];
 }
 
+// the centralised critic's image (critic_input: state), in floats: a network's sections up to its embedding biases (the
+// state_others slot zeros: the state has no such key), then a head of up to seven rows and the two embeddings it has
+enum : int {
+    C_HW = P_HW,                             // head weight [8][128]: v_out's A rows, zeros behind them
+    C_HB = C_HW + 8 * kEncE,                 // head bias [8]
+    C_EW = C_HB + 8,                         // embedding weights transposed: state_drones [D][128], cylinders [5][128]
+};
+static __host__ __device__ __forceinline__ long long pol_central_floats(int D) { return C_EW + (long long)(D + 5) * kEncE; }
+
+HNS_DEV float pol_central_src(const EncNet &s, int D, long long i) {
+    if (i < C_HW) return pol_src(s, D, i);
+    if (i < C_HB) {
+        const int o = (int)((i - C_HW) / kEncE), f = (int)((i - C_HW) % kEncE);
+        return o < s.head_n ? s.head_w[o * kEncE + f] : 0.0f;
+    }
+    if (i < C_EW) return (int)(i - C_HB) < s.head_n ? s.head_b[i - C_HB] : 0.0f;
+    const long long e = i - C_EW;
+    const int in = (int)(e / kEncE), f = (int)(e % kEncE);
+    return in < D ? s.ew[0][f * D + in] : s.ew[2][f * 5 + (in - D)];
+}
+
 struct PolNets {
     EncNet n[HNS_MAX_AGENTS + 1];            // the actor — with one actor per agent the agents' slices of the stacked actor (formed on the host) — then the critic
 };
@@ -120,6 +144,15 @@ __global__ __launch_bounds__(256) void hns_policy_pack_agents_kernel(const PolNe
     const long long n = pol_net_floats(D);
     float *dst = img + blockIdx.y * n;                           // image blockIdx.y: the actors', then the critic's
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) dst[i] = pol_src(nets.n[blockIdx.y], D, i);
+}
+
+// [the shared actor's image as hns_policy_pack_agents_kernel writes it, the centralised critic's]: nets.n[0], nets.n[1]
+__global__ __launch_bounds__(256) void hns_policy_pack_central_kernel(const PolNets nets, int D, float *img) {
+    const bool critic = blockIdx.y;
+    const long long n = critic ? pol_central_floats(D) : pol_net_floats(D);
+    float *dst = img + (critic ? pol_net_floats(D) : 0);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+        dst[i] = critic ? pol_central_src(nets.n[1], D, i) : pol_src(nets.n[0], D, i);
 }
 
 struct PolArgs {
@@ -141,12 +174,16 @@ struct PolLds {
     float t2[kEncE * kEncLd];
 };
 
-// one network on the workgroup's rows; leaves the encoder output y (the thread's 16 features of row r) in `y`
+// one network on the workgroup's rows; leaves the encoder output y (the thread's 16 features of row r) in `y`.
+// CENTRAL (the centralised critic's image): a row is an ENV (a.rows of them); its tokens are the A rows of a.xs (state_drones,
+// sse / ssa apart) through the ONE embedding of token 0, then the K rows of a.xc (the state's cylinders [E, K, 5]: sce / sct apart).  The
+// statements behind the tokens are the same ones; without the flag the function compiles to what it was.
+template <bool CENTRAL = false>
 HNS_DEV void pol_encoder(const PolArgs &a, const float *net, PolLds &L, int w, int lane, int r, int g, long long row, float (&y)[16]) {
     const bool live = row < a.rows;
-    const long long e = live ? row / a.A : 0;
-    const int ag = live ? (int)(row % a.A) : 0;
-    const int D = a.D, eo = P_EW + D * kEncE, ec = eo + 3 * kEncE;
+    const long long e = live ? (CENTRAL ? row : row / a.A) : 0;
+    const int ag = live && !CENTRAL ? (int)(row % a.A) : 0;
+    const int D = a.D, es = CENTRAL ? C_EW : P_EW, eo = P_EW + D * kEncE, ec = CENTRAL ? C_EW + D * kEncE : eo + 3 * kEncE;
     const float *xs = live ? a.xs + e * a.sse + ag * a.ssa : nullptr;
     const float *xo = live && a.xo ? a.xo + e * a.soe + ag * a.soa : nullptr;
     const float *xc = live ? a.xc + e * a.sce + ag * a.sca : nullptr;
@@ -154,7 +191,7 @@ HNS_DEV void pol_encoder(const PolArgs &a, const float *net, PolLds &L, int w, i
     // the image's sections are `net + offset` at each call: pointers formed once in front of the token loop made the kernel 5 % slower
     // (profiles/r15_encoder_fold.txt)
     float t[16], xh[16];                                          // xh: the normalised vectors, which only a backward pass reads
-    enc_token<true>(net + P_EW, net + P_EB, xs, D, net + P_LNW, net + P_LNB, g, xh, t);          // token 0
+    enc_token<true>(net + es, net + P_EB, xs, D, net + P_LNW, net + P_LNB, g, xh, t);            // token 0
     enc_lds_store(L.x0, r, g, t);
     __syncthreads();
     enc_matvec<0>(net + P_MAT + 0 * kEncMat, net + P_BQ, L.x0, L.t1, nullptr, nullptr, w, lane);     // q
@@ -170,7 +207,8 @@ HNS_DEV void pol_encoder(const PolArgs &a, const float *net, PolLds &L, int w, i
     for (int i = 0; i < 16; ++i) z[i] = t[i];
     const int N = a.A + a.K;
     for (int j = 1; j < N; ++j) {
-        if (j < a.A) enc_token<true>(net + eo, net + P_EB + kEncE, xo ? xo + (j - 1) * a.sot : nullptr, 3, net + P_LNW, net + P_LNB, g, xh, t);
+        if (CENTRAL && j < a.A) enc_token<true>(net + es, net + P_EB, xs ? xs + j * a.ssa : nullptr, D, net + P_LNW, net + P_LNB, g, xh, t);
+        else if (j < a.A) enc_token<true>(net + eo, net + P_EB + kEncE, xo ? xo + (j - 1) * a.sot : nullptr, 3, net + P_LNW, net + P_LNB, g, xh, t);
         else enc_token<true>(net + ec, net + P_EB + 2 * kEncE, xc ? xc + (j - a.A) * a.sct : nullptr, 5, net + P_LNW, net + P_LNB, g, xh, t);
         enc_softmax_step(kq, t, m, l, z);
     }
@@ -491,6 +529,46 @@ __global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_agents_kernel(c
 __global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_rnn_agents_kernel(const PolArgs a, const PolRnnArgs ra) { pol_tile<true, true, false>(a, ra); }
 __global__ __launch_bounds__(kEncThreads, 2) void hns_policy_act_rnn_agents_kernel(const PolArgs a, const PolRnnArgs ra) { pol_tile<true, true, true>(a, ra); }
 
+// ---- the centralised critic (critic_input: state; include/hns.h: hns_policy_central_forward)
+// pol_head on the central image: row o of v_out (the same chain, so one row gives pol_head's bits)
+HNS_DEV float pol_head_central(const float *net, int o, const float (&y)[16], int g) {
+    const float *hw = net + C_HW + o * kEncE;
+    float s = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const f32x4 wv = *reinterpret_cast<const f32x4 *>(hw + enc_feat(g, i, 0));
+#pragma unroll
+        for (int u = 0; u < 4; ++u) s = __builtin_fmaf(wv[u], y[4 * i + u], s);
+    }
+    return row_sum8(s) + net[C_HB + o];
+}
+
+// The grid is two ranges of workgroups: the first `actor_tiles` are the shared actor's tiles of 32 (env, agent) rows — pol_tile's actor pass,
+// statement for statement, on `a` — and the rest the critic's tiles of 32 ENVS on `c` (img: the central image; xs / xc: the state), each env's
+// A values from A evaluations of the head on its one feature row.  The two never share a workgroup: at 2 048 envs x 3 that is 192 + 64
+// workgroups side by side instead of 192 running both passes back to back.
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_central_kernel(const PolArgs a, const PolArgs c, const unsigned actor_tiles) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
+    float y[16];
+    if (blockIdx.x < actor_tiles) {
+        const long long row = (long long)blockIdx.x * kEncRows + r;
+        pol_encoder(a, a.img, L, w, lane, r, g, row, y);
+        float loc[4];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) loc[o] = pol_head(a.img, o, y, g);
+        pol_sample(a, a.img, loc, row, row < a.rows, g);
+    } else {
+        const long long env = (long long)(blockIdx.x - actor_tiles) * kEncRows + r;
+        pol_encoder<true>(c, c.img, L, w, lane, r, g, env, y);
+        for (int o = 0; o < c.A; ++o) {
+            const float v = pol_head_central(c.img, o, y, g);
+            if (env < c.rows && g == 0) c.value[env * c.A + o] = v;
+        }
+    }
+}
+
 __global__ void hns_policy_bump_kernel(unsigned long long *counter) { counter[0] += 1ull; }
 
 }  // namespace hns
@@ -672,6 +750,80 @@ int pol_call(const char *fn, bool agents, bool rnn, bool act, const void *packed
 }  // namespace
 
 extern "C" {
+
+size_t hns_policy_packed_central_bytes(int32_t self_dim, int32_t num_agents) {
+    if (self_dim < 1 || self_dim > hns::kPolMaxSelf || num_agents < 1 || num_agents > HNS_MAX_AGENTS) return 0;
+    return (size_t)(hns::pol_net_floats(self_dim) + hns::pol_central_floats(self_dim)) * sizeof(float);
+}
+
+int hns_policy_pack_central(const hns_policy_net *actor, const hns_policy_net *critic, int32_t self_dim, int32_t num_agents, void *packed, void *stream) {
+    const char *fn = "hns_policy_pack_central";
+    if (self_dim < 1 || self_dim > hns::kPolMaxSelf) return hns_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kPolMaxSelf) + "]");
+    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return hns_fail(fn, "num_agents must be in [1, 7]");
+    if (!packed || !hns_aligned(packed, 16)) return hns_fail(fn, "packed image must be a 16-byte aligned device array");
+    hns::PolNets nets{};
+    int rc = pol_net(fn, actor, num_agents > 1, true, nets.n[0]);
+    if (rc != HNS_OK) return rc;
+    rc = pol_net(fn, critic, false, false, nets.n[1]);
+    if (rc != HNS_OK) return rc;
+    if (critic->embed_others_w || critic->embed_others_b) return hns_fail(fn, "the centralised critic has no state_others embedding");
+    nets.n[1].head_n = num_agents;                               // v_out = Linear(128, A)
+    hipLaunchKernelGGL(hns::hns_policy_pack_central_kernel, dim3(256, 2), dim3(256), 0, static_cast<hipStream_t>(stream), nets, (int)self_dim,
+                       static_cast<float *>(packed));
+    HNS_CHECK_HIP(hipGetLastError());
+    return HNS_OK;
+}
+
+int hns_policy_central_forward(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                               const hns_policy_io *io, const hns_policy_state *state, int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
+    const char *fn = "hns_policy_central_forward";
+    int rc = pol_check_shape(fn, packed, self_dim, num_envs, num_agents, num_cylinders, io);
+    if (rc != HNS_OK) return rc;
+    if (flags & ~(HNS_POLICY_DETERMINISTIC | HNS_POLICY_VALUE_ONLY)) return hns_fail(fn, "unknown flag");
+    const bool value_only = flags & HNS_POLICY_VALUE_ONLY, det = flags & HNS_POLICY_DETERMINISTIC;
+    if (!value_only) {                                            // the critic workgroups never read the observation
+        rc = pol_check_obs(fn, num_agents, io);
+        if (rc != HNS_OK) return rc;
+    }
+    if (!state || !state->state_drones || !state->cylinders || !hns_aligned(state->state_drones, 4) || !hns_aligned(state->cylinders, 4))
+        return hns_fail(fn, "state pointer missing or misaligned");
+    for (int k = 0; k < 2; ++k)
+        if (state->drones_stride[k] < 0 || state->cyl_stride[k] < 0) return hns_fail(fn, "negative stride");
+    rc = pol_check_outputs(fn, io, value_only, det, counter);
+    if (rc != HNS_OK) return rc;
+    hns::PolArgs a{}, c{};
+    a.img = static_cast<const float *>(packed);
+    a.net_floats = hns::pol_net_floats(self_dim);
+    a.rows = num_envs * num_agents; a.A = num_agents; a.K = num_cylinders; a.D = self_dim;
+    c = a;
+    c.img = a.img + a.net_floats;
+    c.xs = state->state_drones; c.sse = state->drones_stride[0]; c.ssa = state->drones_stride[1];
+    c.xc = state->cylinders; c.sce = state->cyl_stride[0]; c.sct = state->cyl_stride[1];
+    c.rows = num_envs; c.value = io->value;
+    unsigned actor_tiles = 0;
+    if (!value_only) {
+        a.xs = io->obs_self; a.xo = io->obs_others; a.xc = io->obs_cylinders;
+        a.sse = io->self_stride[0]; a.ssa = io->self_stride[1];
+        a.soe = io->others_stride[0]; a.soa = io->others_stride[1]; a.sot = io->others_stride[2];
+        a.sce = io->cyl_stride[0]; a.sca = io->cyl_stride[1]; a.sct = io->cyl_stride[2];
+        a.eps = io->eps; a.counter = reinterpret_cast<const unsigned long long *>(counter); a.seed = seed;
+        a.action = io->action; a.loc = io->loc; a.logp = io->log_prob; a.deterministic = det;
+        actor_tiles = (unsigned)((a.rows + hns::kEncRows - 1) / hns::kEncRows);
+    }
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_forward_central_kernel),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
+    HNS_CHECK_HIP(attr);
+    const unsigned critic_tiles = (unsigned)((num_envs + hns::kEncRows - 1) / hns::kEncRows);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(hns::hns_policy_forward_central_kernel, dim3(actor_tiles + critic_tiles), dim3(hns::kEncThreads), sizeof(hns::PolLds), st, a, c,
+                       actor_tiles);
+    HNS_CHECK_HIP(hipGetLastError());
+    if (!value_only && !det && !io->eps) {
+        hipLaunchKernelGGL(hns::hns_policy_bump_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<unsigned long long *>(counter));
+        HNS_CHECK_HIP(hipGetLastError());
+    }
+    return HNS_OK;
+}
 
 size_t hns_policy_packed_agents_bytes(int32_t self_dim, int32_t num_agents) {
     if (self_dim < 1 || self_dim > hns::kPolMaxSelf || num_agents < 1 || num_agents > HNS_MAX_AGENTS) return 0;

@@ -54,6 +54,11 @@
 //                                        op's [rows, 128] layout, row = position x A + agent.
 //   hns_critic_wgrad_kernel            : unchanged, on the padded agent-major tiles.
 //   hns_encoder_reduce_agents_kernel   : each agent's partials into its slice of the 20 stacked encoder tensors; no norm launch.
+// The centralised critic (critic_input: state; hns_critic_train_grad_central) is the critic's pipeline on tiles of 32 env-steps:
+//   hns_critic_central_kernel<BWD>   : the tile body under CT_CENTRAL — a row's tokens are the A state_drones rows through ONE embedding, then the
+//                                      cylinders; A values, loss terms and value gradients per row; d embed_self summed over all A drone tokens.
+//   hns_critic_reduce_central_kernel : the reduce kernel's body with the central partial row's destinations (head_w [A][128], head_b [A]).
+//   pack, loss, wgrad and norm kernels: the critic's, unchanged.
 // Determinism: every sum has a fixed order, no float atomics: the same inputs give the same bits.
 #include <hip/hip_runtime.h>
 
@@ -97,6 +102,11 @@ constexpr int kActLossSlots = 1 + 3 * HNS_MAX_AGENTS;   // a tile's fp64 partial
 // (heads = 0, the encoder op: the critic's layout, its O_HW and O_HB slots never written and never read)
 static __host__ __device__ constexpr int ct_partial_floats(int D, int heads = 1) { return O_EWS + D * kCtE + (heads > 1 ? (heads - 1) * kCtE + heads : 0); }
 static_assert((6 * kCtGemmOut + 31) / 32 + (ct_partial_floats(kCtMaxSelf, kActDim) + 31) / 32 <= kCtMaxBlocks, "the reduce kernel's grid outgrew its per-block sums");
+// the centralised critic's head (v_out = Linear(128, A), A <= 7): head_w row 0 at O_HW, rows 1 .. 6 behind the state_drones
+// embedding as the actor's, then head_b's up to seven values (+ 1 of padding); O_EBO, O_EWO and O_HB are never written and never read
+static __host__ __device__ constexpr int ct_central_hb(int D) { return O_EWS + D * kCtE + (HNS_MAX_AGENTS - 1) * kCtE; }
+static __host__ __device__ constexpr int ct_partial_central(int D) { return ct_central_hb(D) + 8; }
+static_assert((6 * kCtGemmOut + 31) / 32 + (ct_partial_central(kCtMaxSelf) + 31) / 32 <= kCtMaxBlocks, "the reduce kernel's grid outgrew its per-block sums");
 
 struct CtGrad {
     float *ew[3], *eb[3], *ln_w, *ln_b, *in_w, *in_b, *out_w, *out_b, *l1_w, *l1_b, *l2_w, *l2_b, *n1_w, *n1_b, *n2_w, *n2_b, *head_w, *head_b;
@@ -243,6 +253,71 @@ HNS_DEV float ct_token_j(const CtArgs &a, const CtRow &R, int j, int g, float (&
     x = R.xc ? R.xc + (j - a.A) * a.sc[3] : nullptr;
     n = 5;
     return ct_token(ewo + 3 * kCtE, a.net.eb[2], x, 5, a.net, g, xh, t);
+}
+
+// ---- the centralised critic (critic_input: state; include/hns.h: hns_critic_train_grad_central)
+// a row is an env-step: its query is drone 0's row of state_drones (a.xs, ss[2] apart), its cylinders the rows at agent index 0 of a.xc
+HNS_DEV CtRow ct_row_central(const CtArgs &a, long long row) {
+    CtRow R;
+    R.live = row < a.rows;
+    R.ag = 0;
+    R.e = R.live ? (a.index ? a.index[row] : row) : 0;
+    if (R.e < 0 || R.e >= a.steps) { R.live = false; R.e = 0; }
+    const long long n = R.e / a.T, t = R.e % a.T;
+    R.xs = R.live ? a.xs + n * a.ss[0] + t * a.ss[1] : nullptr;
+    R.xo = nullptr;
+    R.xc = R.live ? a.xc + n * a.sc[0] + t * a.sc[1] : nullptr;
+    return R;
+}
+
+// token j >= 1 of the row: drone j through token 0's embedding, then the cylinders
+HNS_DEV float ct_token_j_central(const CtArgs &a, const CtRow &R, int j, int g, float (&xh)[16], float (&t)[16], const float *&x, int &n) {
+    if (j < a.A) {
+        x = R.xs ? R.xs + j * a.ss[2] : nullptr;
+        n = a.D;
+        return ct_token(a.img + I_EW, a.net.eb[0], x, a.D, a.net, g, xh, t);
+    }
+    x = R.xc ? R.xc + (j - a.A) * a.sc[3] : nullptr;
+    n = 5;
+    return ct_token(a.img + I_EW + (a.D + 3) * kCtE, a.net.eb[2], x, 5, a.net, g, xh, t);
+}
+
+// One drone token's part of d embed_self_{b,w} in the tile's two partial rows (`ph`: the half's; thread = feature ef of half eh): the sums over
+// the half's 16 rows of de and of de (x) x, token 0's statements.  `add`: onto what an earlier token of the tile left there — the same thread
+// wrote it, so the order of the sum is the order of the tokens.
+HNS_DEV void ct_embed_self_sums(CtLds &L, const float (&de)[16], const float *x, int D, float *ph, int ef, int eh, int r, int g, bool add) {
+    crow_store(L.red, kCtRedLd, r, g, de);
+    for (int k = g; k < D; k += 8) L.sx[k * kCtRows + r] = x ? x[k] : 0.0f;
+    __syncthreads();
+    float sb = 0.0f;
+#pragma unroll
+    for (int rr = 0; rr < 16; ++rr) sb += L.red[(eh * 16 + rr) * kCtRedLd + ef];
+    ph[O_EBS + ef] = add ? ph[O_EBS + ef] + sb : sb;
+    for (int k = 0; k < D; ++k) {
+        float sw = 0.0f;
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) sw = __builtin_fmaf(L.red[(eh * 16 + rr) * kCtRedLd + ef], L.sx[k * kCtRows + eh * 16 + rr], sw);
+        ph[O_EWS + k * kCtE + ef] = add ? ph[O_EWS + k * kCtE + ef] + sw : sw;
+    }
+    __syncthreads();
+}
+
+// the critic's two tile kernels on tiles of 32 env-steps (a.rows = the minibatch's env-steps; b_values, b_returns and `values` [.., A])
+template <bool BWD, int HEAD = 1>
+__global__ __launch_bounds__(kCtThreads, BWD ? 1 : 2) void hns_critic_central_kernel(const CtArgs a) {
+#define CT_BODY_TILE
+#define CT_CENTRAL
+#define CT_TILE_BLOCK blockIdx.x
+#define CT_TILE_ROW ((long long)tile * kCtRows + r)
+#define CT_TILE_FIRST 0
+#define CT_TILE_STEP 1
+#include "hns_policy_train_bodies.inc"
+#undef CT_BODY_TILE
+#undef CT_CENTRAL
+#undef CT_TILE_BLOCK
+#undef CT_TILE_ROW
+#undef CT_TILE_FIRST
+#undef CT_TILE_STEP
 }
 
 template <bool BWD, int HEAD = 1>
@@ -511,9 +586,19 @@ HNS_DEV float *ct_dst_tile(const CtGrad &g, int D, int heads, int e) {
     return x < (heads - 1) * kCtE ? g.head_w + kCtE + x : g.log_std + (x - (heads - 1) * kCtE);
 }
 
+// the centralised critic's partial row (ct_central_hb): v_out's A rows and A biases, no state_others embedding
+HNS_DEV float *ct_dst_tile_central(const CtGrad &g, int D, int A, int e) {
+    if (e < O_EWO) return (e >> 7) == 8 ? nullptr : ct_dst_tile<true>(g, D, 1, e);
+    if (e < O_EWC || (e >= O_HB && e < O_EWS)) return nullptr;
+    if (e < O_EWS + D * kCtE) return ct_dst_tile<true>(g, D, 1, e);
+    const int x = e - (O_EWS + D * kCtE);
+    if (x < (HNS_MAX_AGENTS - 1) * kCtE) return x < (A - 1) * kCtE ? g.head_w + kCtE + x : nullptr;
+    return x - (HNS_MAX_AGENTS - 1) * kCtE < A ? g.head_b + (x - (HNS_MAX_AGENTS - 1) * kCtE) : nullptr;
+}
+
 // 32 gradient values per block, 8 threads each: slice s sums its range of the partials in fp64, the slices add up in order.  `ls_add` joins
 // every log_std value's sum once (the actor's -entropy_coef: the entropy term's gradient is the same constant whatever the rows)
-template <bool HEADS>
+template <bool HEADS, bool CENTRAL = false>                    // CENTRAL: `heads` is v_out's A rows, the tile partials' places ct_dst_tile_central's
 HNS_DEV void ct_reduce(const float *gpart, int splits, const float *tpart, int nt, int P, int gblocks, const CtGrad &g, int D, double *blockpart, int heads,
                        double ls_add) {
     __shared__ double sm[8][32];
@@ -526,7 +611,10 @@ HNS_DEV void ct_reduce(const float *gpart, int splits, const float *tpart, int n
     const float *src = gemm ? gpart : tpart;
     float *dst = nullptr;
     bool zero = false;
-    if (e < stride) dst = gemm ? ct_dst_gemm(g, e, zero) : ct_dst_tile<HEADS>(g, D, heads, e);
+    if (e < stride) {
+        if constexpr (CENTRAL) dst = gemm ? ct_dst_gemm(g, e, zero) : ct_dst_tile_central(g, D, heads, e);
+        else dst = gemm ? ct_dst_gemm(g, e, zero) : ct_dst_tile<HEADS>(g, D, heads, e);
+    }
     double acc = 0.0;
     if (dst && !zero) {
         const int lo = (int)((long long)n * sl / 8), hi = (int)((long long)n * (sl + 1) / 8);
@@ -538,7 +626,7 @@ HNS_DEV void ct_reduce(const float *gpart, int splits, const float *tpart, int n
         double tot = 0.0;
 #pragma unroll
         for (int q = 0; q < 8; ++q) tot += sm[q][el];
-        if (heads > 1 && !gemm && e >= P - heads && e < P) tot += ls_add;
+        if (!CENTRAL && heads > 1 && !gemm && e >= P - heads && e < P) tot += ls_add;
         const float s = (float)tot;
         if (dst) dst[0] = s;
         sq[el] = dst ? (double)s * (double)s : 0.0;
@@ -554,6 +642,11 @@ HNS_DEV void ct_reduce(const float *gpart, int splits, const float *tpart, int n
 __global__ __launch_bounds__(256) void hns_critic_reduce_kernel(const float *gpart, int splits, const float *tpart, int nt, int P, int gblocks, const CtGrad g,
                                                                 int D, double *blockpart, int heads, double ls_add) {
     ct_reduce<true>(gpart, splits, tpart, nt, P, gblocks, g, D, blockpart, heads, ls_add);
+}
+
+__global__ __launch_bounds__(256) void hns_critic_reduce_central_kernel(const float *gpart, int splits, const float *tpart, int nt, int P, int gblocks,
+                                                                        const CtGrad g, int D, double *blockpart, int A) {
+    ct_reduce<true, true>(gpart, splits, tpart, nt, P, gblocks, g, D, blockpart, A, 0.0);
 }
 
 // the encoder op's: the 20 encoder tensors alone (heads = 0); the per-block sums of squares are written and not used
@@ -607,13 +700,14 @@ struct CtPlan {
     size_t o_ctl, o_loss, o_block, o_img, o_tile, o_gemm, o_stage, total;
 };
 
-bool ct_plan(int64_t rows, int32_t D, int32_t A, int32_t K, CtPlan &p, int heads = 1) {
+// central: the centralised critic — `rows` env-steps in tiles of 32, ct_partial_central's partial rows
+bool ct_plan(int64_t rows, int32_t D, int32_t A, int32_t K, CtPlan &p, int heads = 1, bool central = false) {
     if (rows < 1 || rows > ((int64_t)1 << 31) - 64 || D < 1 || D > hns::kCtMaxSelf || A < 1 || A > HNS_MAX_AGENTS || K < 1 || K > HNS_MAX_CYLINDERS) return false;
     p.tiles = (rows + hns::kCtRows - 1) / hns::kCtRows;
     p.tps = (p.tiles + hns::kCtMaxSplits - 1) / hns::kCtMaxSplits;
     p.splits = (p.tiles + p.tps - 1) / p.tps;
     p.stage_rows = p.tiles * hns::kCtRows;
-    p.P = hns::ct_partial_floats(D, heads);
+    p.P = central ? hns::ct_partial_central(D) : hns::ct_partial_floats(D, heads);
     p.gblocks = (6 * hns::kCtGemmOut + 31) / 32;
     p.tblocks = (p.P + 31) / 32;
     size_t o = 0;
@@ -749,18 +843,21 @@ int ct_check_obs(const char *fn, const Batch &b, bool others) {
 // heads 0: the encoder op, whose plan is ct_plan_encoder's (`backward`: hns_encoder_backward's)
 template <typename Batch>
 int ct_plan_call(const char *fn, const Batch &b, std::initializer_list<const float *> outs, void *workspace, size_t workspace_bytes, int32_t self_dim,
-                 int32_t num_agents, int32_t num_cylinders, int heads, CtPlan &p, hns::CtArgs &a, bool backward = true, bool agents = false) {
+                 int32_t num_agents, int32_t num_cylinders, int heads, CtPlan &p, hns::CtArgs &a, bool backward = true, bool agents = false,
+                 bool central = false) {
     if (b.index && !hns_aligned(b.index, 8)) return hns_fail(fn, "misaligned index");
     bool ok = hns_aligned(workspace, 256);
     for (const float *o : outs) ok = ok && hns_aligned(o, 4);
     if (!ok) return hns_fail(fn, "misaligned output (scalars 4 bytes, workspace 256)");
-    const int64_t rows = b.batch * num_agents;
-    if (agents ? (heads == 0 ? !ct_plan_encoder_agents(rows, self_dim, num_agents, num_cylinders, backward, p)
+    const int64_t rows = central ? b.batch : b.batch * num_agents;   // the centralised critic's rows are env-steps
+    if (central ? !ct_plan(rows, self_dim, num_agents, num_cylinders, p, 1, true) :
+        agents ? (heads == 0 ? !ct_plan_encoder_agents(rows, self_dim, num_agents, num_cylinders, backward, p)
                              : !ct_plan_agents(rows, self_dim, num_agents, num_cylinders, p))
                : (heads == 0 ? !ct_plan_encoder(rows, self_dim, num_agents, num_cylinders, backward, p) : !ct_plan(rows, self_dim, num_agents, num_cylinders, p, heads)))
         return hns_fail(fn, "invalid shape");
     if (workspace_bytes < p.total)
-        return hns_fail(fn, agents       ? (heads == 0 ? "workspace too small (hns_encoder_agents_workspace_bytes)"
+        return hns_fail(fn, central      ? "workspace too small (hns_critic_train_central_workspace_bytes)"
+                            : agents     ? (heads == 0 ? "workspace too small (hns_encoder_agents_workspace_bytes)"
                                                         : "workspace too small (hns_actor_train_agents_workspace_bytes)")
                             : heads > 1  ? "workspace too small (hns_actor_train_workspace_bytes)"
                             : heads == 1 ? "workspace too small (hns_critic_train_workspace_bytes)"
@@ -768,13 +865,13 @@ int ct_plan_call(const char *fn, const Batch &b, std::initializer_list<const flo
 
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     a.img = reinterpret_cast<float *>(ws + p.o_img);
-    a.xs = b.obs_self; a.xo = num_agents > 1 ? b.obs_others : nullptr; a.xc = b.obs_cylinders;
+    a.xs = b.obs_self; a.xo = num_agents > 1 && !central ? b.obs_others : nullptr; a.xc = b.obs_cylinders;
     for (int k = 0; k < 3; ++k) a.ss[k] = b.self_stride[k];
     for (int k = 0; k < 4; ++k) { a.so[k] = b.others_stride[k]; a.sc[k] = b.cyl_stride[k]; }
     a.T = b.num_steps; a.steps = b.num_envs * b.num_steps;
     a.index = reinterpret_cast<const long long *>(b.index);
     a.rows = rows; a.A = num_agents; a.K = num_cylinders; a.D = self_dim; a.tiles = (int)p.tiles;
-    a.inv_n = (float)(1.0 / (double)rows);
+    a.inv_n = (float)(1.0 / (double)(central ? rows * num_agents : rows));   // the mean is over every value: batch A of them either way
     a.losspart = reinterpret_cast<double *>(ws + p.o_loss);
     a.tilepart = reinterpret_cast<float *>(ws + p.o_tile);
     a.P = p.P;
@@ -793,14 +890,18 @@ int ct_launch_pack(hipStream_t st, const hns::CtArgs &a, const CtPlan &p, void *
 
 // the launches behind them: weight gradients, the fixed-order sums into the PyTorch layouts (`ls_add`: hns_critic_reduce_kernel's; heads 0: the
 // encoder op's reduce), the total norm (grad_norm NULL: not launched)
-int ct_launch_tail(hipStream_t st, const hns::CtArgs &a, const CtPlan &p, const hns::CtGrad &g, void *workspace, int heads, double ls_add, float *grad_norm) {
+int ct_launch_tail(hipStream_t st, const hns::CtArgs &a, const CtPlan &p, const hns::CtGrad &g, void *workspace, int heads, double ls_add, float *grad_norm,
+                   bool central = false) {
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     float *gpart = reinterpret_cast<float *>(ws + p.o_gemm);
     hipLaunchKernelGGL(hns::hns_critic_wgrad_kernel, dim3((unsigned)p.splits, 6), dim3(256), 0, st, a.stage, a.stage_rows, (int)p.tiles, (int)p.tps, gpart);
     HNS_CHECK_HIP(hipGetLastError());
     double *blockpart = reinterpret_cast<double *>(ws + p.o_block);
     const int nb = p.gblocks + p.tblocks;
-    if (heads == 0)
+    if (central)
+        hipLaunchKernelGGL(hns::hns_critic_reduce_central_kernel, dim3(nb), dim3(256), 0, st, gpart, (int)p.splits, a.tilepart, (int)(2 * p.tiles), p.P, p.gblocks,
+                           g, a.D, blockpart, a.A);
+    else if (heads == 0)
         hipLaunchKernelGGL(hns::hns_encoder_reduce_kernel, dim3(nb), dim3(256), 0, st, gpart, (int)p.splits, a.tilepart, (int)(2 * p.tiles), p.P, p.gblocks, g, a.D,
                            blockpart);
     else
@@ -859,6 +960,47 @@ int ct_critic_call(const char *fn, CtMode mode, const hns_policy_net *critic, co
     hipLaunchKernelGGL(hns::hns_critic_kernel<true>, dim3((unsigned)p.tiles), dim3(hns::kCtThreads), sizeof(hns::CtLds), st, a);
     HNS_CHECK_HIP(hipGetLastError());
     return ct_launch_tail(st, a, p, g, workspace, 1, 0.0, grad_norm);
+}
+
+// hns_critic_train_grad_central: ct_critic_call's local mode on tiles of env-steps — the same refusals in the same order (the state has no
+// state_others: a pointer there is refused), the same launches with the central tile and reduce kernels, the loss over batch A values
+int ct_critic_central_call(const char *fn, const hns_policy_net *critic, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents,
+                           int32_t num_cylinders, float clip_param, int32_t loss_kind, float huber_delta, const hns_policy_grads *grads, float *value_loss,
+                           float *explained_var, float *grad_norm, float *values, void *workspace, size_t workspace_bytes, void *stream) {
+    if (int rc = ct_check_shape(fn, *batch, self_dim, num_agents, num_cylinders)) return rc;
+    if (loss_kind != HNS_CRITIC_LOSS_HUBER && loss_kind != HNS_CRITIC_LOSS_MSE) return hns_fail(fn, "loss_kind must be HNS_CRITIC_LOSS_HUBER or HNS_CRITIC_LOSS_MSE");
+    if (!(clip_param >= 0.0f) || (loss_kind == HNS_CRITIC_LOSS_HUBER && !(huber_delta > 0.0f))) return hns_fail(fn, "clip_param >= 0, huber_delta > 0");
+    if (critic->embed_others_w || critic->embed_others_b || batch->obs_others) return hns_fail(fn, "the centralised critic has no state_others (embedding and obs_others must be NULL)");
+    hns::CtArgs a{};
+    hns::CtGrad g{};
+    CtPlan p;
+    if (int rc = ct_bind_net(fn, *critic, grads, false, 1, a.net, g)) return rc;
+    if (int rc = ct_check_obs(fn, *batch, false)) return rc;
+    if (!batch->b_values || !batch->b_returns || !hns_aligned(batch->b_values, 4) || !hns_aligned(batch->b_returns, 4)) return hns_fail(fn, "b_values / b_returns missing or misaligned");
+    if (int rc = ct_plan_call(fn, *batch, {value_loss, explained_var, grad_norm, values}, workspace, workspace_bytes, self_dim, num_agents, num_cylinders, 1, p, a,
+                              true, false, true))
+        return rc;
+    float *ctl = reinterpret_cast<float *>(static_cast<unsigned char *>(workspace) + p.o_ctl);
+    a.bval = batch->b_values; a.bret = batch->b_returns;
+    a.clip = clip_param; a.delta = huber_delta; a.mse = loss_kind == HNS_CRITIC_LOSS_MSE;
+    a.values = values;
+    a.ctl = ctl;
+
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    static const hipError_t attr_f = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_central_kernel<false>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)hns::kCtLdsFwd);
+    static const hipError_t attr_b = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_critic_central_kernel<true>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::CtLds));
+    HNS_CHECK_HIP(attr_f);
+    HNS_CHECK_HIP(attr_b);
+    if (int rc = ct_launch_pack(st, a, p, workspace)) return rc;
+    hipLaunchKernelGGL(hns::hns_critic_central_kernel<false>, dim3((unsigned)p.tiles), dim3(hns::kCtThreads), hns::kCtLdsFwd, st, a);
+    HNS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hns::hns_critic_loss_kernel, dim3(1), dim3(256), 0, st, a.losspart, (int)p.tiles, (double)(a.rows * a.A), ctl, value_loss, explained_var);
+    HNS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(hns::hns_critic_central_kernel<true>, dim3((unsigned)p.tiles), dim3(hns::kCtThreads), sizeof(hns::CtLds), st, a);
+    HNS_CHECK_HIP(hipGetLastError());
+    return ct_launch_tail(st, a, p, g, workspace, 1, 0.0, grad_norm, true);
 }
 
 // The actor's two entries over one body.  global: the rows' backward weight and policy_loss are scaled by 1 / global_rows instead of 1 / rows (this
@@ -1027,6 +1169,20 @@ int hns_critic_train_grad_global(const hns_policy_net *critic, const hns_critic_
     if (!hns_aligned(sums, 8)) return hns_fail(fn, "misaligned sums (five fp64 values, 8-byte aligned)");
     return ct_critic_call(fn, kCtGlobal, critic, batch, self_dim, num_agents, num_cylinders, clip_param, loss_kind, huber_delta, grads, value_loss, explained_var,
                           grad_norm, values, const_cast<double *>(sums), global_rows, workspace, workspace_bytes, stream);
+}
+
+size_t hns_critic_train_central_workspace_bytes(int64_t batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders) {
+    CtPlan p;
+    return ct_plan(batch, self_dim, num_agents, num_cylinders, p, 1, true) ? p.total : 0;
+}
+
+int hns_critic_train_grad_central(const hns_policy_net *critic, const hns_critic_batch *batch, int32_t self_dim, int32_t num_agents, int32_t num_cylinders,
+                                  float clip_param, int32_t loss_kind, float huber_delta, const hns_policy_grads *grads, float *value_loss,
+                                  float *explained_var, float *grad_norm, float *values, void *workspace, size_t workspace_bytes, void *stream) {
+    const char *fn = "hns_critic_train_grad_central";
+    if (!critic || !batch || !grads || !value_loss || !explained_var || !grad_norm || !workspace) return hns_fail(fn, "null pointer");
+    return ct_critic_central_call(fn, critic, batch, self_dim, num_agents, num_cylinders, clip_param, loss_kind, huber_delta, grads, value_loss, explained_var,
+                                  grad_norm, values, workspace, workspace_bytes, stream);
 }
 
 size_t hns_actor_train_workspace_bytes(int64_t rows, int32_t self_dim, int32_t num_agents, int32_t num_cylinders) {

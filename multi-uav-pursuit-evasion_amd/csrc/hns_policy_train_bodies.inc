@@ -5,6 +5,9 @@
 // A tile kernel's body.  CT_TILE_BLOCK: the tile's number (its staging block, partial rows, loss partials); CT_TILE_ROW: the thread's row of the
 // minibatch, position x A + agent (from `tile` and `r`; >= a.rows: not live); CT_TILE_FIRST, CT_TILE_STEP: the tile's rows of agent `ag` for the
 // ratios' partials.  `a.img` and `a.net` are the network the tile runs.  The per-row arithmetic knows none of this.
+// CT_CENTRAL (the centralised critic, HEAD = 1; DESIGN.md §7.20) switches, by the preprocessor, so that every other kernel keeps its statements:
+// a row is an env-step (ct_row_central), tokens 1 .. A - 1 are state_drones rows through token 0's embedding (ct_token_j_central), the head has
+// A rows (the row's A values, A loss terms and A value gradients), and d embed_self is summed over all A drone tokens (ct_embed_self_sums).
     static_assert(HEAD == 0 || HEAD == 1 || (HEAD == kActDim && BWD), "the actor's head runs in the one-pass kernel");
     extern __shared__ __align__(16) unsigned char lds_raw[];
     CtLds &L = *reinterpret_cast<CtLds *>(lds_raw);
@@ -17,7 +20,13 @@
     {   // one tile per workgroup: its two partial rows are written, never accumulated
         const int tile = CT_TILE_BLOCK;
         const long long row = CT_TILE_ROW;
+#if defined(CT_CENTRAL)
+        const CtRow R = ct_row_central(a, row);
+#define CT_TOKEN_J ct_token_j_central
+#else
         const CtRow R = ct_row(a, row);
+#define CT_TOKEN_J ct_token_j
+#endif
         float *stg = BWD ? a.stage + (long long)tile * kCtRows * kCtE : nullptr;
         const long long SA = a.stage_rows * kCtE;               // floats per staging array
 
@@ -40,7 +49,7 @@
         for (int j = 1; j < ntok; ++j) {
             const float *x;
             int n;
-            ct_token_j(a, R, j, g, xh, t, x, n);
+            CT_TOKEN_J(a, R, j, g, xh, t, x, n);
             enc_softmax_step(kq, t, m, l, z);
         }
         const float il = 1.0f / l;
@@ -74,6 +83,73 @@
         const float rstd2 = enc_layernorm(u, N.n2_w, N.n2_b, g, xh2, y);                            // y = LN2(x0' + ff)
         float dv = 0.0f, dmu[HEAD ? HEAD : 1];
         float dy[16], dw[16], db[16], dx[16];
+#if defined(CT_CENTRAL)
+        // ---- v_out = Linear(128, A) on the row's ONE feature vector: A values against the env-step's A old values and returns.  Value o is
+        // the shared critic's statements on row o of the head; the first joins by assignment and the others by addition, so one agent
+        // leaves the shared critic's bits.
+        float dva[HNS_MAX_AGENTS];
+        {
+            float hw[16];
+            double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0, q4 = 0.0;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                dy[i] = 0.0f;
+                dw[i] = 0.0f;
+                db[i] = 0.0f;
+            }
+#pragma unroll
+            for (int o = 0; o < HNS_MAX_AGENTS; ++o) {
+                dva[o] = 0.0f;
+                if (o >= a.A) continue;
+                enc_vec_load(N.head_w + o * kCtE, g, hw);
+                s = 0.0f;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) s = __builtin_fmaf(hw[i], y[i], s);
+                const float v = row_sum8(s) + N.head_b[o];
+                float ret = 0.0f, bv = 0.0f;
+                if (R.live) {
+                    ret = a.bret[R.e * a.A + o];
+                    bv = a.bval[R.e * a.A + o];
+                }
+                const float d = v - bv;
+                const float dcl = fminf(fmaxf(d, -a.clip), a.clip);
+                const float clipped = bv + dcl;
+                if (!BWD) {
+                    if (g == 0 && R.live) {
+                        if (a.values) a.values[row * a.A + o] = v;
+                        const double e0 = (double)v - (double)ret, e1 = (double)clipped - (double)ret;
+                        const double l0 = ct_loss64(e0, (double)a.delta, a.mse), l1 = ct_loss64(e1, (double)a.delta, a.mse);
+                        q0 = o == 0 ? l0 : q0 + l0;
+                        q1 = o == 0 ? l1 : q1 + l1;
+                        q2 = o == 0 ? e0 * e0 : q2 + e0 * e0;
+                        q3 = o == 0 ? (double)ret : q3 + (double)ret;
+                        q4 = o == 0 ? (double)ret * (double)ret : q4 + (double)ret * (double)ret;
+                    }
+                } else {
+                    if (R.live) {
+                        const float g0 = ct_dloss(v - ret, a.delta, a.mse);
+                        const float g1 = (d >= -a.clip && d <= a.clip) ? ct_dloss(clipped - ret, a.delta, a.mse) : 0.0f;
+                        dva[o] = (a.ctl[0] * g0 + a.ctl[1] * g1) * a.inv_n;
+                    }
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) dy[i] = o == 0 ? dva[o] * hw[i] : __builtin_fmaf(dva[o], hw[i], dy[i]);
+                }
+            }
+            if (!BWD) {
+                if (g == 0) {
+                    L.dred[0 * kCtRows + r] = q0; L.dred[1 * kCtRows + r] = q1; L.dred[2 * kCtRows + r] = q2;
+                    L.dred[3 * kCtRows + r] = q3; L.dred[4 * kCtRows + r] = q4;
+                }
+                __syncthreads();
+                if (tid < 5) {
+                    double acc = 0.0;
+                    for (int rr = 0; rr < kCtRows; ++rr) acc += L.dred[tid * kCtRows + rr];
+                    a.losspart[(long long)tile * 5 + tid] = acc;
+                }
+                return;
+            }
+        }
+#else
         if constexpr (HEAD == 0) {
             // ---- the encoder op: the features leave, or d features arrive, as [rows, 128]; a row that is not live is neither written nor read
             if (!BWD) {
@@ -204,9 +280,27 @@
                 for (int q = 0; q < 16; ++q) dy[q] = __builtin_fmaf(dmu[i], hr[q], dy[q]);
             }
         }
+#endif
         ct_ln_bwd(dy, xh2, rstd2, N.n2_w, g, dx, dw, db);       // dx = d(x0' + ff)
         enc_lds_store(L.b, r, g, dx);
         crow_store(stg + 10 * SA, kCtE, r, g, dx);
+#if defined(CT_CENTRAL)
+#pragma unroll
+        for (int o = 0; o < HNS_MAX_AGENTS; ++o) {               // d v_out.weight[o] = sum_rows dv_o y; the rows' dv_o wait in sx for d v_out.bias
+            if (o >= a.A) continue;
+            if (g == 0) L.sx[o * kCtRows + r] = dva[o];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) u[i] = dva[o] * y[i];
+            ct_flush(L, u, part, a.P, o == 0 ? O_HW : O_EWS + a.D * kCtE + (o - 1) * kCtE, tid, r, g);
+        }
+        if (tid < 2 * a.A) {                                    // d v_out.bias: the two halves' sums of each dv_o
+            const int half = tid & 1, o = tid >> 1;
+            float sb = 0.0f;
+            for (int rr = 0; rr < 16; ++rr) sb += L.sx[o * kCtRows + half * 16 + rr];
+            float *dst = part + (long long)half * a.P + ct_central_hb(a.D) + o;
+            *dst = sb;
+        }
+#else
         if constexpr (HEAD == 1) {
             if (g == 0) L.sc[r] = dv;
             ct_flush(L, u, part, a.P, O_HW, tid, r, g);
@@ -244,8 +338,10 @@
                 a.losspart[(long long)tile * kActLossSlots] = acc;
             }
         }
+#endif
         ct_flush(L, dw, part, a.P, O_N2W, tid, r, g);
         ct_flush(L, db, part, a.P, O_N2B, tid, r, g);
+#if !defined(CT_CENTRAL)
         if constexpr (HEAD == 1) {
             if ((tid & 127) == 0) {                                 // d head_b: the two halves' sums of dv
                 const int half = tid >> 7;
@@ -255,6 +351,7 @@
                 *dst = sb;
             }
         }
+#endif
         enc_matvec<3>(img + 11 * kCtMat, nullptr, L.b, L.c, nullptr, nullptr, w, lane);      // dh = W_2^T dff
         __syncthreads();
         enc_lds_load(L.c, r, g, t);
@@ -318,7 +415,7 @@
         for (int j = 1; j < ntok; ++j) {
             const float *x;
             int n;
-            const float rs = ct_token_j(a, R, j, g, xh, t, x, n);
+            const float rs = CT_TOKEN_J(a, R, j, g, xh, t, x, n);
             float sa = 0.0f, sd = 0.0f;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
@@ -333,6 +430,12 @@
                 dkq[i] = __builtin_fmaf(ds, t[i], dkq[i]);
             }
             ct_ln_bwd(dt, xh, rs, N.ln_w, g, de, dw, db);
+#if defined(CT_CENTRAL)
+            if (j < a.A) {                                      // a drone token: the first of them writes the tile's d embed_self sums
+                ct_embed_self_sums(L, de, x, a.D, part + (long long)eh * a.P, ef, eh, r, g, j > 1);
+                continue;
+            }
+#endif
             crow_store(L.red, kCtRedLd, r, g, de);
             if (g < n) L.sx[g * kCtRows + r] = x ? x[g] : 0.0f;
             __syncthreads();
@@ -359,9 +462,11 @@
         }
         {
             float *ph = part + (long long)eh * a.P;
+#if !defined(CT_CENTRAL)
             ph[O_EBO + ef] = eo[0];
 #pragma unroll
             for (int k = 0; k < 3; ++k) ph[O_EWO + k * kCtE + ef] = eo[1 + k];
+#endif
             ph[O_EBC + ef] = ec[0];
 #pragma unroll
             for (int k = 0; k < 5; ++k) ph[O_EWC + k * kCtE + ef] = ec[1 + k];
@@ -383,6 +488,9 @@
             for (int i = 0; i < 16; ++i) dt0[i] = (dt0[i] + u[i]) + y[i];
             const float rs = ct_token(img + I_EW, N.eb[0], R.xs, a.D, N, g, xh, t);
             ct_ln_bwd(dt0, xh, rs, N.ln_w, g, de, dw, db);
+#if defined(CT_CENTRAL)
+            ct_embed_self_sums(L, de, R.xs, a.D, part + (long long)eh * a.P, ef, eh, r, g, a.A > 1);     // the query drone joins the others'
+#else
             crow_store(L.red, kCtRedLd, r, g, de);
             for (int k = g; k < a.D; k += 8) L.sx[k * kCtRows + r] = R.xs ? R.xs[k] : 0.0f;
             __syncthreads();
@@ -398,10 +506,12 @@
                 ph[O_EWS + k * kCtE + ef] = sw;
             }
             __syncthreads();
+#endif
         }
         ct_flush(L, dw, part, a.P, O_LNW, tid, r, g);
         ct_flush(L, db, part, a.P, O_LNB, tid, r, g);
     }
+#undef CT_TOKEN_J
 #elif defined(CT_BODY_LOSS)
 // The actor's scalars.  CT_LOSS_NLS: the log_std vectors ([CT_LOSS_NLS][4]); CT_LOSS_ENTROPY: the rows' mean entropy from their sum `ent`.
     __shared__ double sm[kActLossSlots][64];

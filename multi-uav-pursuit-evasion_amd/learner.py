@@ -27,6 +27,10 @@ actor_train.update_actor_per_agent over the stacked tensors, everything else Dev
 `PerAgentRecurrentDeviceLearner` is `RecurrentDeviceLearner` for share_actor: False with actor.rnn / critic.rnn (one actor and one actor GRU per
 agent): the actor step through rnn_train.update_actor_rnn_per_agent over the stacked tensors, everything else inherited.
 
+`CentralCriticDeviceLearner` is the same for critic_input: state (the centralised critic): the critic block through
+critic_train.update_critic_central on the stored state_drones, the bootstrap value from the last state, everything else DeviceLearner's.
+`DeviceLearner` keeps refusing that configuration.
+
 `DeviceLearner._ppo_loop` is the only PPO loop.  A variant overrides what differs and nothing else: the units a permutation draws from
 (`_units`), its update call for one index (`_actor_step`, `_critic_step`), its cached buffers (`_workspaces`), and its optimisers and tensors
 (`_make_actor_opt`, `_make_critic_opt`, `_network_tensors`: checkpoints, buckets and the broadcast are written once over them).
@@ -123,6 +127,9 @@ class DeviceLearner:
         if getattr(device_policy, "recurrent", False):
             raise P.PolicyConfigError("DeviceLearner updates the non-recurrent networks only: a recurrent policy (actor.rnn / critic.rnn) is trained "
                                       "in torch over encoder.encode -> rnn.gru -> head (examples/recurrent_policy.py)")
+        if getattr(device_policy, "central", False):
+            raise P.PolicyConfigError("DeviceLearner updates the critic on the observation: a centralised critic (critic_input: state) is "
+                                      "CentralCriticDeviceLearner's")
         self._configure(actor, critic, cfg, tp_net, value_normalizer, agent_name, generator)
         self._make_networks_state(device_policy, P.DevicePolicy)
         self._join(group)
@@ -480,6 +487,72 @@ class PerAgentDeviceLearner(DeviceLearner):
 
     def _actor_step(self, idx, obs, action, log_probs, adv, recurrent, bucket=None, **kw):        # (no group, so no bucket)
         return actor_train.update_actor_per_agent(self.actor, *obs, action, log_probs, adv, self.actor_opt, index=idx, cfg=self.cfg, **kw)
+
+
+class CentralCriticDeviceLearner(DeviceLearner):
+    """MAPPOPolicy's training half with critic_input: state (the centralised critic: ONE row per env over the state, v_out = Linear(128, A);
+    DESIGN.md §7.20): `DeviceLearner`'s train_op / train_rollout, info row, state_dict and checkpoint (the reference's, with the central
+    critic's names), with the critic block through critic_train.update_critic_central (one `hns_critic_train_grad_central` call and one
+    ClippedAdam step over the critic's 20 tensors per minibatch, a cached workspace, no host synchronisation in the PPO loop) and the
+    bootstrap value from the policy's value_only call on the last step's next state.  The actor block, the targets, the predictor and the
+    info row are DeviceLearner's, unchanged.
+
+    critic: the centralised critic's parameters (policy.CENTRAL_CRITIC_NAMES), live tensors updated in place; device_policy: a
+    CentralCriticDevicePolicy over the same tensors (built when None).  train_rollout takes two more tensors: state_drones [N, T, A, D] and
+    next_state_last [N, A, D] (RolloutStorage.learner_kwargs() of a collector over such a policy); the state's cylinders are agent 0's rows
+    of obs_cylinders, read in place.  Refused before anything is built: group= (NotImplementedError: there is no data-parallel form), a
+    recurrent or per-agent policy, a device_policy that is not a CentralCriticDevicePolicy, critic_input: obs, and whatever
+    CentralCriticDevicePolicy and the cfg checks of DeviceLearner refuse, with their exception types."""
+
+    def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, agent_name="drone", generator=None, device_policy=None, group=None):
+        if group is not None:
+            raise NotImplementedError("CentralCriticDeviceLearner takes no group=: the centralised critic has no data-parallel form")
+        if getattr(device_policy, "recurrent", False) or getattr(device_policy, "per_agent", False):
+            raise P.PolicyConfigError("CentralCriticDeviceLearner updates the shared non-recurrent actor and the centralised critic only")
+        if device_policy is not None and not getattr(device_policy, "central", False):
+            raise P.PolicyConfigError("CentralCriticDeviceLearner needs a CentralCriticDevicePolicy (a critic on the observation is DeviceLearner's)")
+        P.check_config_central(cfg)
+        rest = P.cfg_without(cfg, "critic_input")                # what the actor's functions (and policy.check_config behind them) take
+        actor_train.actor_cfg(rest)
+        critic_train.critic_cfg(rest, central=True)
+        self._configure(actor, critic, rest, tp_net, value_normalizer, agent_name, generator)
+        self._make_networks_state(device_policy, P.CentralCriticDevicePolicy)
+
+    def _network_tensors(self):
+        return list(actor_train.actor_parameters(self.actor).values()), list(critic_train.central_critic_parameters(self.critic).values())
+
+    def _rollout_kwargs(self, td):
+        """DeviceLearner's, and the state the critic reads: ("agents", "state", "state_drones") of every step and of the last step's next."""
+        kw = super()._rollout_kwargs(td)
+        kw["state_drones"] = td[("agents", "state")]["state_drones"]
+        kw["next_state_last"] = td["next"][("agents", "state")]["state_drones"][:, -1]
+        return kw
+
+    def train_rollout(self, *, obs_self, obs_others, obs_cylinders, action, log_probs, state_value, next_obs_last, reward, done, agent_done=None,
+                      tp=None, state_drones=None, next_state_last=None):
+        """DeviceLearner.train_rollout's arguments and the critic's: state_drones [N, T, A, D], next_state_last [N, A, D]."""
+        if state_drones is None or next_state_last is None:
+            raise ValueError("a centralised critic's rollout needs state_drones and next_state_last (RolloutStorage.learner_kwargs())")
+        if state_drones.dim() != 4 or tuple(state_drones.shape[:3]) != tuple(action.shape[:3]):
+            raise ValueError(f"state_drones must be [N, T, A, D] over the rollout's {tuple(action.shape[:3])}, not {tuple(state_drones.shape)}")
+        rk = dict(state_drones=state_drones, next_state_last=next_state_last)
+        return self._run(rk, obs_self, obs_others, obs_cylinders, action, log_probs, state_value, next_obs_last, reward, done, agent_done, tp)
+
+    def _bootstrap_value(self, next_obs_last, rk=None):
+        return self.policy.forward(*next_obs_last, rk["next_state_last"], value_only=True).value
+
+    def _workspaces(self, xs, xc):
+        N, T, A, D = xs.shape
+        dev, K, lib = xs.device, int(xc.shape[3]), abi.load_library()
+        batch = N * T // self.num_minibatches
+        na, nc = lib.hns_actor_train_workspace_bytes(batch * A, D, A, K), lib.hns_critic_train_central_workspace_bytes(batch, D, A, K)
+        if batch < 1 or na == 0 or nc == 0:
+            raise ValueError(f"shape outside the kernels' limits: {batch} env-steps per minibatch, self_dim {D}, {A} agents, {K} cylinders")
+        return self._workspace("actor", na, dev), self._workspace("critic", nc, dev)
+
+    def _critic_step(self, idx, obs, state_value, ret, rk, bucket=None, **kw):                      # (no group, so no bucket)
+        return critic_train.update_critic_central(self.critic, rk["state_drones"], obs[2], state_value, ret, self.critic_opt, index=idx,
+                                                  cfg=self.cfg, **kw)
 
 
 class RecurrentDeviceLearner(DeviceLearner):

@@ -30,6 +30,11 @@ over dim 0 of the stacked `actor_params`): one actor AND one actor GRU per agent
 `hns_policy_forward_rnn_agents` / `hns_policy_act_rnn_agents` in §7.16's tile, the state rows where they were ([E, A, 128]); row (e, a) is bit
 for bit `RecurrentDevicePolicy`'s with agent a's slices.  Collection and evaluation only: its update is an open item.
 
+`CentralCriticDevicePolicy` is the `critic_input: state` configuration (the centralised critic: ONE encoder row per env over the state spec
+— the A rows of state_drones through one embedding, then the cylinders — and v_out = Linear(128, A)) beside the shared non-recurrent actor on
+`hns_policy_central_forward`: actor tiles of 32 (env, agent) rows and critic tiles of 32 envs in one launch, the actor's outputs bit for bit
+`DevicePolicy`'s.  The four classes above keep refusing that configuration.
+
 Layout of this file, as the device side's (one tile body, three flags): the configuration checks and the parsers (`parse_parameters` and
 `split_rnn`, each with a `stacked` switch); ONE CPU restatement (`_restatement`: a GRU step or not, a stacked actor or not, the actor's half
 alone or not; `torch_forward` and `torch_forward_rnn` are its public forms); the random builders; `ENTRIES`, the eight C entries keyed
@@ -63,6 +68,11 @@ _ENCODER = {
 ACTOR_NAMES = {**{"encoder." + k: v for k, v in _ENCODER.items()},
                "act_dist.fc_mean.weight": "head_w", "act_dist.fc_mean.bias": "head_b", "act_dist.log_std": "log_std"}
 CRITIC_NAMES = {**{"base." + k: v for k, v in _ENCODER.items()}, "v_out.weight": "head_w", "v_out.bias": "head_b"}
+
+# the centralised critic (critic_input: state; make_critic(centralized=True), mappo.py:553-566): the encoder over the STATE spec — state_drones
+# (every drone's row through ONE embedding, here under hns_policy_net's embed_self_*) and cylinders, no state_others — and v_out = Linear(128, A)
+CENTRAL_CRITIC_NAMES = {**{"base." + k.replace("state_self", "state_drones"): v for k, v in _ENCODER.items() if "state_others" not in k},
+                        "v_out.weight": "head_w", "v_out.bias": "head_b"}
 
 PolicyOutput = collections.namedtuple("PolicyOutput", ["action", "log_prob", "value", "loc"])
 RecurrentPolicyOutput = collections.namedtuple("RecurrentPolicyOutput", ["action", "log_prob", "value", "loc", "actor_state", "critic_state"])
@@ -156,8 +166,10 @@ def _stacked_agents(tensors, what, kind, plural, show):
     return A
 
 
-def parse_parameters(params, names, what, stacked=False):
+def parse_parameters(params, names, what, stacked=False, central=False):
     """The hns_policy_net fields of one network from reference parameter names; raises PolicyConfigError on anything it does not implement.
+    central (the centralised critic, names = CENTRAL_CRITIC_NAMES): the head is Linear(128, A) with A in [1, 7] and a
+    state_others or state_self embedding is refused by name.
     stacked (share_actor: False, mappo.py:148-152): (the fields of the STACKED network, every tensor [A, ...]; A) — each
     agent's slice is held to the checks below; tensors that are not stacked, or whose leading sizes disagree, raise PolicyConfigError."""
     flat = {_strip(k): v for k, v in _flatten(params).items()}
@@ -176,6 +188,10 @@ def parse_parameters(params, names, what, stacked=False):
             out[names[k]] = v
         else:
             unknown.append(k)
+    if central and any(".state_others." in k or ".state_self." in k for k in unknown):
+        raise PolicyConfigError(f"{what}: the centralised critic embeds state_drones and cylinders, not "
+                                f"{sorted(k for k in unknown if '.state_others.' in k or '.state_self.' in k)[:4]} (a critic on the observation is "
+                                "DevicePolicy's)")
     if any(".rnn." in "." + k or k.startswith("rnn.") for k in unknown):
         raise PolicyConfigError(f"{what}: an rnn is not supported ({[k for k in unknown if 'rnn' in k][:3]})")
     if unknown:
@@ -193,9 +209,13 @@ def parse_parameters(params, names, what, stacked=False):
         raise PolicyConfigError(f"{what}: embed_dim and dim_feedforward must be 128 (in_proj_weight {tuple(w.shape)}, linear1 "
                                 f"{tuple(out['linear1_w'].shape)})")
     heads = ACTION_DIM if "log_std" in names.values() else 1
+    if central:
+        heads = int(out["head_w"].shape[0]) if out["head_w"].dim() == 2 else 0
+        if not 1 <= heads <= abi.HNS_MAX_AGENTS:
+            raise PolicyConfigError(f"{what}: v_out must be Linear(128, A) with A in [1, {abi.HNS_MAX_AGENTS}], not {tuple(out['head_w'].shape)}")
     if tuple(out["head_w"].shape) != (heads, E) or tuple(out["head_b"].shape) != (heads,):
         raise PolicyConfigError(f"{what}: the head must be Linear(128, {heads}), not {tuple(out['head_w'].shape)}")
-    if heads == ACTION_DIM and tuple(out["log_std"].shape) != (ACTION_DIM,):
+    if "log_std" in out and tuple(out["log_std"].shape) != (ACTION_DIM,):
         raise PolicyConfigError(f"{what}: log_std must have {ACTION_DIM} values")
     if tuple(out["embed_cyl_w"].shape) != (E, 5):
         raise PolicyConfigError(f"{what}: the cylinders embedding must be Linear(5, 128)")
@@ -203,7 +223,8 @@ def parse_parameters(params, names, what, stacked=False):
         raise PolicyConfigError(f"{what}: the state_others embedding must be Linear(3, 128)")
     sw = out["embed_self_w"]
     if sw.dim() != 2 or sw.shape[0] != E or not 1 <= sw.shape[1] <= abi.HNS_POLICY_MAX_SELF_DIM:
-        raise PolicyConfigError(f"{what}: the state_self embedding must be Linear(D, 128) with D in [1, {abi.HNS_POLICY_MAX_SELF_DIM}]")
+        raise PolicyConfigError(f"{what}: the {'state_drones' if central else 'state_self'} embedding must be Linear(D, 128) with D in "
+                                f"[1, {abi.HNS_POLICY_MAX_SELF_DIM}]")
     for k, v in out.items():
         if v.dtype != torch.float32:
             raise TypeError(f"{what}: parameter {k} must be float32, not {v.dtype}")
@@ -213,6 +234,12 @@ def parse_parameters(params, names, what, stacked=False):
 def parse_parameters_per_agent(params, what="actor"):
     """`parse_parameters` of the stacked actor: (its fields, every tensor [A, ...]; A)."""
     return parse_parameters(params, ACTOR_NAMES, what, stacked=True)
+
+
+def parse_parameters_central(critic, what="critic"):
+    """`parse_parameters` of the centralised critic's 20 tensors: (its fields — embed_self_* hold the state_drones embedding —, A = v_out's rows)."""
+    p = parse_parameters(critic, CENTRAL_CRITIC_NAMES, what, central=True)
+    return p, int(p["head_w"].shape[0])
 
 
 def agent_slice(actor_p, a):
@@ -268,6 +295,15 @@ def check_config_per_agent(cfg):
     if getter(cfg)("share_actor", False):
         raise PolicyConfigError("share_actor: True with one actor per agent; the shared actor is DevicePolicy's")
     check_config(cfg_without(cfg, "share_actor"))
+
+
+def check_config_central(cfg):
+    """`check_config` for the centralised critic: everything it refuses but critic_input: state; critic_input: obs is refused instead (a cfg
+    that does not say, like no cfg, is taken at the class's word — as check_config_per_agent takes share_actor)."""
+    if getter(cfg)("critic_input", "state") != "state":
+        raise PolicyConfigError(f"critic_input: {getter(cfg)('critic_input')} with the centralised critic; the critic on the observation is "
+                                "DevicePolicy's")
+    check_config(cfg_without(cfg, "critic_input"))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -367,6 +403,20 @@ def torch_forward_rnn(actor, critic, actor_rnn, critic_rnn, xs, xo, xc, actor_st
                                                deterministic, value_only, generator))
 
 
+def torch_forward_central(actor, critic, xs, xo, xc, state_drones, state_cylinders, eps=None, deterministic=False, value_only=False, generator=None):
+    """The CPU restatement of hns_policy_central_forward, any dtype: the shared actor as `torch_forward` runs it (xs [E, A, 1, D]) and the
+    centralised critic in the reference's statements (Critic.forward with centralized=True, mappo.py:644-660): the encoder over the state —
+    state_drones [E, A, D] and state_cylinders [E, K, 5] are SplitEmbedding's two keys, token 0 (drone 0) the query — and v_out, unflattened
+    to value [E, A, 1]."""
+    value = F.linear(_encoder(critic, state_drones, None, state_cylinders), critic["head_w"], critic["head_b"]).unsqueeze(-1)
+    if value_only:
+        return PolicyOutput(None, None, value, None)
+    if eps is None and not deterministic:
+        eps = torch.randn((*xs.shape[:-2], ACTION_DIM), dtype=xs.dtype, device=xs.device, generator=generator)
+    action, log_prob, loc = _heads(actor, _encoder(actor, xs, xo, xc), eps, deterministic)
+    return PolicyOutput(action, log_prob, value, loc)
+
+
 def _td_get(td, key):
     try:
         return td.get(key, None) if hasattr(td, "get") else td[key]
@@ -430,6 +480,18 @@ def random_parameters(self_dim, num_agents, seed=0):
     return actor, critic
 
 
+def random_parameters_central(self_dim, num_agents, seed=0):
+    """`random_parameters` for critic_input: state: (the shared actor, the centralised critic — the encoder over state_drones / cylinders and
+    v_out = Linear(128, num_agents), orthogonal with gain 0.01 —) in the reference's names, CPU fp32."""
+    actor, obs_critic = random_parameters(self_dim, num_agents, seed)
+    critic = {k.replace("state_self", "state_drones"): v for k, v in obs_critic.items() if "state_others" not in k and not k.startswith("v_out.")}
+    g = torch.Generator().manual_seed(seed + 7919)
+    q, _ = torch.linalg.qr(torch.randn(EMBED_DIM, num_agents, generator=g))
+    critic["v_out.weight"] = q.T.contiguous() * 0.01
+    critic["v_out.bias"] = (torch.rand(num_agents, generator=g) * 2 - 1) / math.sqrt(EMBED_DIM)
+    return actor, critic
+
+
 def random_parameters_per_agent(self_dim, num_agents, seed=0):
     """`random_parameters` for share_actor: False: (the stacked actor — `num_agents` independently initialised actors, every tensor
     [A, ...] — and the critic) in the reference's names, CPU fp32."""
@@ -465,7 +527,8 @@ class DevicePolicy:
     This class holds everything the four configurations share, switched by two class attributes: `per_agent` (a stacked actor, `num_agents`
     slices) and `recurrent` (`actor_rnn` / `critic_rnn`, a GRU behind each encoder).  The subclasses set them, parse their parameters and
     adapt the arguments of `forward`, `act` and `act_step` to `_pass`."""
-    per_agent = recurrent = False
+    per_agent = recurrent = central = False
+    needs_state = False                                          # the collector hands ("agents", "state") to `forward` (CentralCriticDevicePolicy)
     actor_rnn = critic_rnn = None
 
     def __init__(self, actor_params, critic, cfg=None, device=None, seed=0, agent_name="drone"):
@@ -483,7 +546,7 @@ class DevicePolicy:
         self.self_dim = int(self.actor_p["embed_self_w"].shape[-1])
         if int(self.critic_p["embed_self_w"].shape[1]) != self.self_dim:
             raise PolicyConfigError("actor and critic see state_self rows of different widths")
-        if ("embed_others_w" in self.actor_p) != ("embed_others_w" in self.critic_p):
+        if not self.central and ("embed_others_w" in self.actor_p) != ("embed_others_w" in self.critic_p):
             raise PolicyConfigError("actor and critic disagree on the state_others key")
         self.has_others = "embed_others_w" in self.actor_p
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -517,11 +580,13 @@ class DevicePolicy:
     def _packed_bytes(self):
         if self.per_agent:
             return self._lib.hns_policy_packed_agents_bytes(self.self_dim, self.num_agents)
+        if self.central:
+            return self._lib.hns_policy_packed_central_bytes(self.self_dim, self.num_agents)
         return self._lib.hns_policy_packed_bytes(self.self_dim)
 
     def _pack_agents(self):
         """The pack entry's num_agents.  Of hns_policy_pack's only > 1 matters (the networks have the state_others embedding)."""
-        return self.num_agents if self.per_agent else 2 if self.has_others else 1
+        return self.num_agents if self.per_agent or self.central else 2 if self.has_others else 1
 
     def _rnn_packed_bytes(self):
         return self._lib.hns_policy_rnn_packed_agents_bytes(self.num_agents) if self.per_agent else self._lib.hns_policy_rnn_packed_bytes()
@@ -557,7 +622,7 @@ class DevicePolicy:
         stamp = tuple((t.data_ptr(), t._version) for t in self._tensors())
         if not force and stamp == self._stamp:
             return
-        pack = "hns_policy_pack_agents" if self.per_agent else "hns_policy_pack"
+        pack = "hns_policy_pack_agents" if self.per_agent else "hns_policy_pack_central" if self.central else "hns_policy_pack"
         a, c = self._net(self.actor_p), self._net(self.critic_p)
         with torch.cuda.device(self.device):
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -638,15 +703,17 @@ class DevicePolicy:
         is_init = is_init.reshape(E).contiguous()                # (a time slice of a stored [N, T, 1] tensor is strided)
         return is_init.view(torch.uint8) if is_init.dtype == torch.bool else (is_init != 0).view(torch.uint8)
 
-    def _pass(self, obs, act=False, eps=None, deterministic=False, value_only=False, out=None, states=None, is_init=None):
+    def _pass(self, obs, act=False, eps=None, deterministic=False, value_only=False, out=None, states=None, is_init=None, state=None):
         """One call of ENTRIES[per_agent, recurrent, act] — on CPU tensors, of `_restatement` — as (action, log_prob, value, loc, actor_state,
         critic_state): what the pass does not compute is None.  obs: (state_self, state_others, cylinders).  act: the actor's half alone,
         the mode into `out` (or a fresh tensor), no noise, the call counter untouched.  states (recurrent): name -> tensor or None in the
         order (the actor's state, the critic's, the tensor the actor's new state is written into, the critic's), the names the caller's
-        own for the refusals; act takes the actor's two."""
+        own for the refusals; act takes the actor's two.  state (central): (state_drones, state_cylinders) as `forward` takes them."""
         xs, xo, xc = self._validate(*obs)
         E, A, _ = xs.shape
         dev = self.device
+        if self.central and not act:
+            sd, sc = self._validate_state(*state, xc)
         if eps is not None and (tuple(eps.shape) != (E, A, ACTION_DIM) or eps.dtype != torch.float32 or eps.device != dev):
             raise ValueError(f"eps must be float32 [{E}, {A}, {ACTION_DIM}] on {dev}")
         ha = hc = oa = oc = None
@@ -666,6 +733,10 @@ class DevicePolicy:
                 # from views of its storage must give the bits the collection gave.  The classes without a GRU never did this and still
                 # do not: their CPU bits on strided observations are the strided products'.
                 xs, xc, xo = xs.contiguous(), xc.contiguous(), (xo.contiguous() if xo is not None else None)
+            if self.central and not act:
+                with torch.no_grad():                            # (a contiguous state: a strided view of the env's cylinders rounds differently on the CPU)
+                    return (*torch_forward_central(self.actor_p, self.critic_p, xs.unsqueeze(2), xo, xc, sd.contiguous(), sc.contiguous(), eps,
+                                                   deterministic, value_only, self._generator), None, None)
             with torch.no_grad():
                 action, log_prob, value, loc, new_a, new_c = _restatement(
                     self.actor_p, self.critic_p, xs.unsqueeze(2), xo, xc, self.actor_rnn, self.critic_rnn, ha, hc, is_init, eps,
@@ -693,6 +764,13 @@ class DevicePolicy:
                 log_prob, loc = torch.empty(E, A, 1, device=dev), torch.empty(E, A, ACTION_DIM, device=dev)
                 io.log_prob, io.loc = log_prob.data_ptr(), loc.data_ptr()
         args = [self.packed.data_ptr(), self.self_dim, E, A, xc.shape[2], C.byref(io)]
+        if self.central and not act:
+            sd, sc = (t if t.stride(-1) == 1 else t.contiguous() for t in (sd, sc))
+            st = abi.HnsPolicyState()
+            st.state_drones, st.cylinders = sd.data_ptr(), sc.data_ptr()
+            st.drones_stride[:] = [sd.stride(0), sd.stride(1)]
+            st.cyl_stride[:] = [sc.stride(0), sc.stride(1)]
+            args.append(C.byref(st))
         if self.recurrent:
             rio = abi.HnsPolicyRnnIo()
             if actor:
@@ -709,7 +787,7 @@ class DevicePolicy:
         if not act:
             args += [(abi.HNS_POLICY_DETERMINISTIC if deterministic else 0) | (abi.HNS_POLICY_VALUE_ONLY if value_only else 0), self.seed,
                      self.counter.data_ptr()]
-        entry = ENTRIES[self.per_agent, self.recurrent, act]
+        entry = "hns_policy_central_forward" if self.central and not act else ENTRIES[self.per_agent, self.recurrent, act]
         with torch.cuda.device(dev):
             rc = getattr(self._lib, entry)(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         self._check(rc, entry)
@@ -845,3 +923,74 @@ class PerAgentRecurrentDevicePolicy(RecurrentDevicePolicy):
         if rnn_agents != self.num_agents:
             raise PolicyConfigError(f"actor: {self.num_agents} stacked actors with {rnn_agents} stacked GRUs")
         self._setup(actor_p, parse_parameters(critic_rest, CRITIC_NAMES, "critic"), device, seed, agent_name)
+
+
+class CentralCriticDevicePolicy(DevicePolicy):
+    """MAPPOPolicy with critic_input: state — the shared actor on the observation and ONE centralised critic row per env (make_critic with
+    centralized=True: the encoder over the state spec, the A rows of state_drones through one embedding, then the cylinders; v_out =
+    Linear(128, A)) — in one HIP launch per call (`hns_policy_central_forward`: actor tiles of 32 (env, agent) rows beside critic tiles of
+    32 envs).  DESIGN.md §7.20.
+
+    `CentralCriticDevicePolicy(actor_params, critic)`: actor_params as for DevicePolicy, critic the centralised critic's 20 tensors under
+    the reference's names (`base.split_embed.embed.state_drones.*`, `base.split_embed.embed.cylinders.*`, ..., `v_out.weight [A, 128]`).
+    action, log_prob and loc are bit for bit DevicePolicy's for the same actor and noise; `act` (evaluation) is DevicePolicy's.  The state's
+    cylinders: the reference's spec declares [E, K, 5] and its env returns [E, A, K, 5]; this class takes the declared shape and, from the
+    env's tensor, agent 0's rows (the query drone's K nearest), read in place — a documented reading, not reference parity.  Refused with
+    PolicyConfigError before anything is built: whatever DevicePolicy refuses except critic_input: state; critic_input: obs; stacked
+    actors; an rnn; a critic with a state_others or state_self embedding; v_out with one row beside an actor with a state_others key (or
+    several rows beside one without)."""
+    central = True
+    needs_state = True
+
+    def __init__(self, actor_params, critic, cfg=None, device=None, seed=0, agent_name="drone"):
+        check_config_central(cfg)
+        actor_p = parse_parameters(actor_params, ACTOR_NAMES, "actor")
+        critic_p, self.num_agents = parse_parameters_central(critic, "critic")
+        if ("embed_others_w" in actor_p) != (self.num_agents > 1):
+            raise PolicyConfigError(f"critic: v_out has {self.num_agents} row(s) but the actor has {'a' if 'embed_others_w' in actor_p else 'no'} "
+                                    "state_others embedding (v_out is Linear(128, A) for A agents)")
+        self._setup(actor_p, critic_p, device, seed, agent_name)
+
+    def _validate_state(self, sd, sc, xc):
+        """(state_drones [E, A, D], the state's cylinders [E, K, 5]) checked against the observation; sc None or [E, A, K, 5]: agent 0's rows."""
+        E, A, K = xc.shape[:3]
+        if A != self.num_agents:
+            raise ValueError(f"the observation has {A} agents, v_out {self.num_agents} rows")
+        if not torch.is_tensor(sd) or tuple(sd.shape) != (E, A, self.self_dim):
+            raise ValueError(f"state_drones must be [{E}, {A}, {self.self_dim}], not {tuple(sd.shape) if torch.is_tensor(sd) else type(sd).__name__}")
+        if sc is None:
+            sc = xc
+        if sc.dim() == 4 and tuple(sc.shape) == (E, A, K, 5):
+            sc = sc[:, 0]                                        # the query drone's K nearest: a view, no copy
+        if tuple(sc.shape) != (E, K, 5):
+            raise ValueError(f"the state's cylinders must be [{E}, {K}, 5] or [{E}, {A}, {K}, 5], not {tuple(sc.shape)}")
+        for name, t in (("state_drones", sd), ("the state's cylinders", sc)):
+            if t.dtype != torch.float32:
+                raise TypeError(f"{name} must be float32, not {t.dtype}")
+            if t.device != self.device:
+                raise ValueError(f"{name} is on {t.device}, the policy on {self.device}")
+        return sd, sc
+
+    def forward(self, obs_self, obs_others, obs_cylinders, state_drones, state_cylinders=None, eps=None, deterministic=False, value_only=False):
+        """PolicyOutput(action [E, A, 4], log_prob [E, A, 1], value [E, A, 1], loc [E, A, 4]); value_only: only value is set (the critic
+        workgroups alone).  state_drones [E, A, D]; state_cylinders [E, K, 5], the env's [E, A, K, 5] (agent 0's rows are read in place) or
+        None: agent 0's rows of obs_cylinders, in place."""
+        return PolicyOutput(*self._pass((obs_self, obs_others, obs_cylinders), eps=eps, deterministic=deterministic, value_only=value_only,
+                                        state=(state_drones, state_cylinders))[:4])
+
+    @staticmethod
+    def _state_of(td):
+        state = td[("agents", "state")]
+        return state["state_drones"], state["cylinders"]
+
+    def __call__(self, tensordict, deterministic=False):
+        """MAPPOPolicy.__call__ with critic_input: state: the critic reads ("agents", "state")."""
+        out = self.forward(*self._obs(tensordict), *self._state_of(tensordict), deterministic=deterministic)
+        tensordict[("agents", "action")] = out.action
+        tensordict[f"{self.agent_name}.action_logp"] = out.log_prob
+        tensordict["state_value"] = out.value
+        return tensordict
+
+    def value(self, tensordict):
+        """value_op: the critic's state_value [E, A, 1] from ("agents", "state")."""
+        return self.forward(*self._obs(tensordict), *self._state_of(tensordict), value_only=True).value
