@@ -332,15 +332,41 @@ def _validate_central(p, sd, sc, b_values, b_returns, index, check_index):
 
 def _torch_loss_and_grad_central(p, sd, sc, b_values, b_returns, index, clip_param, loss, huber_delta):
     """update_critic's statements (mappo.py:328-341) on the gathered minibatch of the centralised critic: values [B, A, 1] from ONE encoder
-    row per env-step (Critic.forward with centralized=True, mappo.py:644-660); autograd through policy_train's encoder."""
+    row per env-step (Critic.forward with centralized=True, mappo.py:644-660); autograd through policy_train's encoder.  An index entry
+    outside [0, N T) — reachable with check_index=False only — contributes nothing, as include/hns.h documents for hns_critic_batch.index and
+    as the kernel does (torch's own gather would read a negative entry from the end and raise on one past the end): its A values join no
+    sum, the means still divide by the whole minibatch's batch x A.  Its rows of `values` are zero HERE; on the device they are whatever the
+    freshly allocated tensor held (the kernel writes live rows only)."""
     N, T, A, D = sd.shape
     sd, sc = sd.reshape(N * T, A, D), sc.reshape(N * T, sc.shape[2], 5)
     bv, ret = b_values.reshape(N * T, A, 1), b_returns.reshape(N * T, A, 1)
+    live = None
     if index is not None:
+        live = (index >= 0) & (index < N * T)
+        if bool(live.all()):
+            live = None
+        else:
+            index = index[live]
         sd, sc, bv, ret = sd[index], sc[index], bv[index], ret[index]
     leaves = {k: v.detach().requires_grad_(True) for k, v in p.items()}
     values = F.linear(PT.encoder(leaves, sd, None, sc), leaves["head_w"], leaves["head_b"]).unsqueeze(-1)
     clipped = bv + (values - bv).clamp(-clip_param, clip_param)
+    if live is not None:
+        # sums over the live values divided by the whole minibatch's count, as the kernel's partials; the all-live statements below stay as
+        # they are for their bits (mean reductions round otherwise than sum / n)
+        n = float(live.numel() * A)
+        loss_fn = nn.HuberLoss(delta=huber_delta, reduction="sum") if loss == "huber" else nn.MSELoss(reduction="sum")
+        value_loss = torch.max(loss_fn(ret, values) / n, loss_fn(ret, clipped) / n)
+        grads = torch.autograd.grad(value_loss, list(leaves.values()))
+        for t, g in zip(p.values(), grads):
+            t.grad = g
+        with torch.no_grad():
+            grad_norm = nn.utils.clip_grad_norm_(list(p.values()), float("inf"))
+            v64, r64 = values.double(), ret.double()
+            explained_var = (1 - (((v64 - r64) ** 2).sum() / n) / (((r64 * r64).sum() - r64.sum() ** 2 / n) / (n - 1.0))).to(torch.float32)
+            out = values.new_zeros(live.numel(), A, 1)
+            out[live] = values.detach()
+        return CriticLoss(value_loss.detach(), explained_var, grad_norm, out)
     loss_fn = nn.HuberLoss(delta=huber_delta) if loss == "huber" else nn.MSELoss()
     l_clip = loss_fn(ret, clipped)
     l_orig = loss_fn(ret, values)
@@ -363,7 +389,10 @@ def value_loss_and_grad_central(critic, state_drones, state_cylinders, b_values,
 
     state_drones: the rollout's [N, T, A, D] (or a flat [R, A, D]), read in place; state_cylinders: [N, T, K, 5] — any strided view, so the
     stored obs_cylinders[:, :, 0] costs no copy — or the rollout's obs_cylinders [N, T, A, K, 5] itself, of which agent 0's rows are read;
-    b_values, b_returns, index, check_index, workspace (hns_critic_train_central_workspace_bytes bytes) and out: value_loss_and_grad's."""
+    b_values, b_returns, index, check_index, workspace (hns_critic_train_central_workspace_bytes bytes) and out: value_loss_and_grad's.
+    With check_index=False an index entry outside the rollout contributes nothing to value_loss, explained_var, grad_norm and the gradients,
+    on the device and on the CPU alike (include/hns.h); its rows of `values` are unspecified (the device leaves them unwritten, the CPU
+    path zeroes them)."""
     if loss not in LOSSES:
         raise ValueError(f"loss must be 'huber' or 'mse', not {loss!r}")
     if not clip_param >= 0 or (loss == "huber" and not huber_delta > 0):
