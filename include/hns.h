@@ -614,6 +614,36 @@ size_t hns_policy_packed_central_bytes(int32_t self_dim, int32_t num_agents);
 int hns_policy_pack_central(const hns_policy_net *actor, const hns_policy_net *critic, int32_t self_dim, int32_t num_agents, void *packed, void *stream);
 int hns_policy_central_forward(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
                                const hns_policy_io *io, const hns_policy_state *state, int32_t flags, uint64_t seed, uint64_t *counter, void *stream);
+/*
+ * One actor per agent beside the centralised critic (share_actor: false WITH critic_input: state — heterogeneous actors under one critic over
+ * the joint state; hns_amd.policy.PerAgentCentralCriticDevicePolicy).  The entries above are unchanged.
+ *
+ * hns_policy_packed_central_agents_bytes: bytes of the image [num_agents actors, the centralised critic]: num_agents times
+ * hns_policy_packed_bytes / 2, then the central critic's image as it lies behind hns_policy_pack_central's actor; 0 for self_dim outside
+ * [1, 96] or num_agents outside [1, 7].
+ * hns_policy_pack_central_agents: ONE launch builds that image (16-byte aligned); call it again after the parameters change.  `actors` is the
+ * stacked actor as hns_policy_pack_agents takes it (every tensor [A, ...], contiguous; the agents' slices are formed on the host the same
+ * way), `critic` the centralised critic as hns_policy_pack_central takes it (embed_others_* NULL, head_w [A, 128], head_b [A]).  The first
+ * num_agents actor images are byte for byte the first num_agents images hns_policy_pack_agents writes, so hns_policy_act_agents serves this
+ * image unchanged; the central image behind them is byte for byte the one hns_policy_pack_central writes behind its actor.  Refused before
+ * the launch, in this order: self_dim or num_agents out of range, a NULL or misaligned image, what hns_policy_pack_agents refuses of
+ * `actors` (a NULL or misaligned parameter pointer, a missing state_others embedding with num_agents > 1, no log_std), what
+ * hns_policy_pack_central refuses of `critic` (a NULL or misaligned parameter pointer, then a state_others embedding).
+ * hns_policy_central_forward_agents: hns_policy_central_forward's arguments, flags, outputs, output layouts, noise scheme, launch count (ONE
+ * launch, and the bump of the counter when the call samples without io->eps) and refusals (all before any launch, in its order) on that
+ * image.  The grid is ceil(E / 32) tiles of 32 envs times A + 1 ranges: range a < A is agent a's — the actor pass of
+ * hns_policy_forward_agents on agent a's image, row (e, a) keeping its number e A + a — and range A the critic's, the critic workgroups of
+ * hns_policy_central_forward.  For every row (e, a), action, log_prob and loc are bit for bit hns_policy_forward_agents' for the same stacked
+ * actor, eps or (seed, *counter, row); value is bit for bit hns_policy_central_forward's for the same critic and state.
+ * HNS_POLICY_VALUE_ONLY launches the critic's range alone: the observation pointers are not read (NULL is fine) and action / log_prob / loc
+ * are untouched.  Deterministic: fixed-order sums, no atomics.
+ */
+size_t hns_policy_packed_central_agents_bytes(int32_t self_dim, int32_t num_agents);
+int hns_policy_pack_central_agents(const hns_policy_net *actors, const hns_policy_net *critic, int32_t self_dim, int32_t num_agents, void *packed,
+                                   void *stream);
+int hns_policy_central_forward_agents(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                                      const hns_policy_io *io, const hns_policy_state *state, int32_t flags, uint64_t seed, uint64_t *counter,
+                                      void *stream);
 
 /*
  * The MAPPO critic's update (learning/mappo.py:326-352 on make_critic's network at the defaults: critic_input obs, no rnn): value

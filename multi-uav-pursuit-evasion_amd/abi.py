@@ -387,6 +387,13 @@ def load_library():
     lib.hns_policy_central_forward.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(HnsPolicyIo), C.POINTER(HnsPolicyState),
                                                C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.hns_policy_central_forward.restype = C.c_int
+    # one actor per agent beside the centralised critic (include/hns.h; hns_amd.policy.PerAgentCentralCriticDevicePolicy)
+    lib.hns_policy_packed_central_agents_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.hns_policy_packed_central_agents_bytes.restype = C.c_size_t
+    lib.hns_policy_pack_central_agents.argtypes = lib.hns_policy_pack.argtypes
+    lib.hns_policy_pack_central_agents.restype = C.c_int
+    lib.hns_policy_central_forward_agents.argtypes = lib.hns_policy_central_forward.argtypes
+    lib.hns_policy_central_forward_agents.restype = C.c_int
     lib.hns_critic_train_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32]
     lib.hns_critic_train_workspace_bytes.restype = C.c_size_t
     lib.hns_critic_train_grad.argtypes = [C.POINTER(HnsPolicyNet), C.POINTER(HnsCriticBatch), C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,
@@ -542,5 +549,5 @@ def check(rc, what):
 EXPORTED_SYMBOLS = [
     "hns_create", "hns_destroy", "hns_bind", "hns_step", "hns_reset", "hns_reset_tasks", "hns_raycast", "hns_set_v_prey",
     "hns_set_smoothness_coef", "hns_set_reset_epoch", "hns_get_reset_epoch", "hns_enable_timing",
-    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_gae", "hns_rollout_normalise", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_selected_kernels", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_tp_train_workspace_bytes", "hns_tp_train_grad", "hns_tp_adam", "hns_policy_packed_bytes", "hns_policy_pack", "hns_policy_forward", "hns_policy_act", "hns_critic_train_workspace_bytes", "hns_critic_train_grad", "hns_actor_train_workspace_bytes", "hns_actor_train_grad", "hns_critic_train_sums", "hns_critic_train_grad_global", "hns_actor_train_grad_global", "hns_grad_norm_workspace_bytes", "hns_grad_norm", "hns_adam_clipped", "hns_learner_info_workspace_bytes", "hns_learner_info", "hns_rollout_store", "hns_eval_means", "hns_encoder_workspace_bytes", "hns_encoder_forward", "hns_encoder_backward", "hns_gru_workspace_bytes", "hns_gru_forward", "hns_gru_backward", "hns_policy_rnn_packed_bytes", "hns_policy_rnn_pack", "hns_policy_forward_rnn", "hns_policy_act_rnn", "hns_rnn_actor_head_workspace_bytes", "hns_rnn_critic_head_workspace_bytes", "hns_rnn_actor_head_grad", "hns_rnn_critic_head_grad", "hns_rnn_critic_head_sums", "hns_rnn_critic_head_grad_global", "hns_rnn_actor_head_grad_global", "hns_policy_packed_agents_bytes", "hns_policy_pack_agents", "hns_policy_forward_agents", "hns_policy_act_agents", "hns_actor_train_agents_workspace_bytes", "hns_actor_train_grad_agents", "hns_policy_rnn_packed_agents_bytes", "hns_policy_rnn_pack_agents", "hns_policy_forward_rnn_agents", "hns_policy_act_rnn_agents", "hns_gru_agents_workspace_bytes", "hns_gru_forward_agents", "hns_gru_backward_agents", "hns_encoder_agents_workspace_bytes", "hns_encoder_forward_agents", "hns_encoder_backward_agents", "hns_rnn_actor_head_agents_workspace_bytes", "hns_rnn_actor_head_grad_agents", "hns_actor_train_grad_agents_global", "hns_rnn_actor_head_grad_agents_global", "hns_policy_packed_central_bytes", "hns_policy_pack_central", "hns_policy_central_forward", "hns_critic_train_central_workspace_bytes", "hns_critic_train_grad_central", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
+    "hns_step_kernel_ms", "hns_region_begin", "hns_region_end", "hns_region_ms", "hns_copy_f4", "hns_moments", "hns_rollout_moments", "hns_gae", "hns_rollout_normalise", "hns_clock_probe", "hns_set_phase_profile", "hns_step_mapping", "hns_selected_kernels", "hns_set_state", "hns_get_state", "hns_refresh_derived_state", "hns_fps", "hns_fps_scratch_bytes", "hns_perturb_tasks", "hns_tp_bind", "hns_tp_refresh", "hns_tp_packed_bytes", "hns_tp_observe", "hns_tp_train_workspace_bytes", "hns_tp_train_grad", "hns_tp_adam", "hns_policy_packed_bytes", "hns_policy_pack", "hns_policy_forward", "hns_policy_act", "hns_critic_train_workspace_bytes", "hns_critic_train_grad", "hns_actor_train_workspace_bytes", "hns_actor_train_grad", "hns_critic_train_sums", "hns_critic_train_grad_global", "hns_actor_train_grad_global", "hns_grad_norm_workspace_bytes", "hns_grad_norm", "hns_adam_clipped", "hns_learner_info_workspace_bytes", "hns_learner_info", "hns_rollout_store", "hns_eval_means", "hns_encoder_workspace_bytes", "hns_encoder_forward", "hns_encoder_backward", "hns_gru_workspace_bytes", "hns_gru_forward", "hns_gru_backward", "hns_policy_rnn_packed_bytes", "hns_policy_rnn_pack", "hns_policy_forward_rnn", "hns_policy_act_rnn", "hns_rnn_actor_head_workspace_bytes", "hns_rnn_critic_head_workspace_bytes", "hns_rnn_actor_head_grad", "hns_rnn_critic_head_grad", "hns_rnn_critic_head_sums", "hns_rnn_critic_head_grad_global", "hns_rnn_actor_head_grad_global", "hns_policy_packed_agents_bytes", "hns_policy_pack_agents", "hns_policy_forward_agents", "hns_policy_act_agents", "hns_actor_train_agents_workspace_bytes", "hns_actor_train_grad_agents", "hns_policy_rnn_packed_agents_bytes", "hns_policy_rnn_pack_agents", "hns_policy_forward_rnn_agents", "hns_policy_act_rnn_agents", "hns_gru_agents_workspace_bytes", "hns_gru_forward_agents", "hns_gru_backward_agents", "hns_encoder_agents_workspace_bytes", "hns_encoder_forward_agents", "hns_encoder_backward_agents", "hns_rnn_actor_head_agents_workspace_bytes", "hns_rnn_actor_head_grad_agents", "hns_actor_train_grad_agents_global", "hns_rnn_actor_head_grad_agents_global", "hns_policy_packed_central_bytes", "hns_policy_pack_central", "hns_policy_central_forward", "hns_critic_train_central_workspace_bytes", "hns_critic_train_grad_central", "hns_policy_packed_central_agents_bytes", "hns_policy_pack_central_agents", "hns_policy_central_forward_agents", "hns_hover_step", "hns_hover_reset", "hns_abi_version", "hns_cfg_size", "hns_last_error",
 ]

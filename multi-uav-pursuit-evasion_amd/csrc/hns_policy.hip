@@ -47,6 +47,10 @@
 //   hns_policy_forward_central_kernel : the centralised critic's configuration (critic_input: state): the grid is the shared
 //                                       actor's tiles — pol_tile's actor pass — followed by the critic's tiles of 32 ENVS on pol_encoder<true>
 //                                       (the state's tokens) and a head of A rows; hns_policy_pack_central_kernel builds its image.
+//   hns_policy_forward_central_agents_kernel : both at once (share_actor: false with critic_input: state): the grid is
+//                                       dim3(tiles of 32 envs, A + 1) — blockIdx.y < A is agent blockIdx.y's range, pol_tile<AGENTS>'s actor
+//                                       pass on that agent's image, and blockIdx.y == A the centralised critic's range, the kernel above's
+//                                       critic branch; hns_policy_pack_central_agents_kernel builds its image [A actors, the central critic].
 //   hns_policy_bump_kernel            : the device call counter += 1 after a sampling call (Philox counter; a captured graph draws fresh noise
 //                                       per replay).
 // Determinism: fixed reduction orders (butterflies over the eight lanes of a row), no atomics.
@@ -155,8 +159,18 @@ __global__ __launch_bounds__(256) void hns_policy_pack_central_kernel(const PolN
         dst[i] = critic ? pol_central_src(nets.n[1], D, i) : pol_src(nets.n[0], D, i);
 }
 
+// [the A actors' images as hns_policy_pack_agents_kernel writes them, the centralised critic's as hns_policy_pack_central_kernel does]:
+// nets.n[0 .. A - 1], nets.n[A]; image blockIdx.y, every one pol_net_floats behind the one before
+__global__ __launch_bounds__(256) void hns_policy_pack_central_agents_kernel(const PolNets nets, int D, int A, float *img) {
+    const bool critic = blockIdx.y == (unsigned)A;
+    const long long n = critic ? pol_central_floats(D) : pol_net_floats(D);
+    float *dst = img + blockIdx.y * pol_net_floats(D);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+        dst[i] = critic ? pol_central_src(nets.n[blockIdx.y], D, i) : pol_src(nets.n[blockIdx.y], D, i);
+}
+
 struct PolArgs {
-    const float *img;                        // the actor image(s), then the critic's, net_floats each
+    const float *img;                       // the actor image(s), then the critic's, net_floats each
     long long net_floats;
     const float *xs, *xo, *xc;               // obs_self [E, A, D], obs_others [E, A, A - 1, 3], obs_cylinders [E, A, K, 5]
     long long sse, ssa, soe, soa, sot, sce, sca, sct;
@@ -569,6 +583,35 @@ __global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_central_ker
     }
 }
 
+// One actor per agent beside the centralised critic (share_actor: false with critic_input: state; include/hns.h:
+// hns_policy_central_forward_agents).  The grid is dim3(tiles of 32 envs, ranges): range blockIdx.y < `agents` is agent
+// blockIdx.y's — pol_tile<AGENTS = true>'s actor pass, statement for statement, on `a`: 32 envs of one agent, pol_agent_row, that agent's
+// image, pol_head, pol_sample on row e A + a — and range blockIdx.y == `agents` the critic's — the kernel above's critic branch, statement
+// for statement, on `c`: 32 envs, pol_encoder<true>, pol_head_central A times — with exactly as many tiles as one agent's.  A value-only
+// call launches one range with agents = 0: the critic's alone, `a` never read.  The two passes never share a workgroup.
+__global__ __launch_bounds__(kEncThreads, 2) void hns_policy_forward_central_agents_kernel(const PolArgs a, const PolArgs c, const unsigned agents) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    PolLds &L = *reinterpret_cast<PolLds *>(lds_raw);
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = tid >> 3, g = tid & 7;
+    float y[16];
+    if (blockIdx.y < agents) {
+        const long long row = pol_agent_row(a, r), actor = blockIdx.y;
+        const float *net = a.img + actor * a.net_floats;          // the agent's actor, formed once per tile
+        pol_encoder(a, net, L, w, lane, r, g, row, y);
+        float loc[4];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) loc[o] = pol_head(net, o, y, g);
+        pol_sample(a, net, loc, row, row < a.rows, g);
+    } else {
+        const long long env = (long long)blockIdx.x * kEncRows + r;
+        pol_encoder<true>(c, c.img, L, w, lane, r, g, env, y);
+        for (int o = 0; o < c.A; ++o) {
+            const float v = pol_head_central(c.img, o, y, g);
+            if (env < c.rows && g == 0) c.value[env * c.A + o] = v;
+        }
+    }
+}
+
 __global__ void hns_policy_bump_kernel(unsigned long long *counter) { counter[0] += 1ull; }
 
 }  // namespace hns
@@ -747,6 +790,70 @@ int pol_call(const char *fn, bool agents, bool rnn, bool act, const void *packed
     return HNS_OK;
 }
 
+// hns_policy_central_forward and hns_policy_central_forward_agents: the same refusals in the same order, one set of arguments, one launch.
+// `agents` picks the per-agent image [A actors, the central critic], the agent-major actor tiles and the grid of A + 1 ranges.
+int pol_central_call(const char *fn, bool agents, const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                     const hns_policy_io *io, const hns_policy_state *state, int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
+    int rc = pol_check_shape(fn, packed, self_dim, num_envs, num_agents, num_cylinders, io);
+    if (rc != HNS_OK) return rc;
+    if (flags & ~(HNS_POLICY_DETERMINISTIC | HNS_POLICY_VALUE_ONLY)) return hns_fail(fn, "unknown flag");
+    const bool value_only = flags & HNS_POLICY_VALUE_ONLY, det = flags & HNS_POLICY_DETERMINISTIC;
+    if (!value_only) {                                            // the critic workgroups never read the observation
+        rc = pol_check_obs(fn, num_agents, io);
+        if (rc != HNS_OK) return rc;
+    }
+    if (!state || !state->state_drones || !state->cylinders || !hns_aligned(state->state_drones, 4) || !hns_aligned(state->cylinders, 4))
+        return hns_fail(fn, "state pointer missing or misaligned");
+    for (int k = 0; k < 2; ++k)
+        if (state->drones_stride[k] < 0 || state->cyl_stride[k] < 0) return hns_fail(fn, "negative stride");
+    rc = pol_check_outputs(fn, io, value_only, det, counter);
+    if (rc != HNS_OK) return rc;
+    hns::PolArgs a{}, c{};
+    a.img = static_cast<const float *>(packed);
+    a.net_floats = hns::pol_net_floats(self_dim);
+    a.rows = num_envs * num_agents; a.A = num_agents; a.K = num_cylinders; a.D = self_dim;
+    c = a;
+    c.img = a.img + (agents ? num_agents : 1) * a.net_floats;     // behind the actor's image(s)
+    c.xs = state->state_drones; c.sse = state->drones_stride[0]; c.ssa = state->drones_stride[1];
+    c.xc = state->cylinders; c.sce = state->cyl_stride[0]; c.sct = state->cyl_stride[1];
+    c.rows = num_envs; c.value = io->value;
+    if (!value_only) {
+        a.xs = io->obs_self; a.xo = io->obs_others; a.xc = io->obs_cylinders;
+        a.sse = io->self_stride[0]; a.ssa = io->self_stride[1];
+        a.soe = io->others_stride[0]; a.soa = io->others_stride[1]; a.sot = io->others_stride[2];
+        a.sce = io->cyl_stride[0]; a.sca = io->cyl_stride[1]; a.sct = io->cyl_stride[2];
+        a.eps = io->eps; a.counter = reinterpret_cast<const unsigned long long *>(counter); a.seed = seed;
+        a.action = io->action; a.loc = io->loc; a.logp = io->log_prob; a.deterministic = det;
+    }
+    static const hipError_t attr = [] {                           // 72 KB of dynamic LDS: above the default cap
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_forward_central_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_forward_central_agents_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
+        return e;
+    }();
+    HNS_CHECK_HIP(attr);
+    const unsigned critic_tiles = (unsigned)((num_envs + hns::kEncRows - 1) / hns::kEncRows);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (agents) {
+        // ranges of critic_tiles tiles of 32 envs: one per agent, then the critic's (value-only: the critic's alone)
+        const unsigned actor_ranges = value_only ? 0u : (unsigned)num_agents;
+        hipLaunchKernelGGL(hns::hns_policy_forward_central_agents_kernel, dim3(critic_tiles, actor_ranges + 1), dim3(hns::kEncThreads),
+                           sizeof(hns::PolLds), st, a, c, actor_ranges);
+    } else {
+        const unsigned actor_tiles = value_only ? 0u : (unsigned)((a.rows + hns::kEncRows - 1) / hns::kEncRows);
+        hipLaunchKernelGGL(hns::hns_policy_forward_central_kernel, dim3(actor_tiles + critic_tiles), dim3(hns::kEncThreads), sizeof(hns::PolLds), st, a, c,
+                           actor_tiles);
+    }
+    HNS_CHECK_HIP(hipGetLastError());
+    if (!value_only && !det && !io->eps) {
+        hipLaunchKernelGGL(hns::hns_policy_bump_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<unsigned long long *>(counter));
+        HNS_CHECK_HIP(hipGetLastError());
+    }
+    return HNS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -776,53 +883,40 @@ int hns_policy_pack_central(const hns_policy_net *actor, const hns_policy_net *c
 
 int hns_policy_central_forward(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
                                const hns_policy_io *io, const hns_policy_state *state, int32_t flags, uint64_t seed, uint64_t *counter, void *stream) {
-    const char *fn = "hns_policy_central_forward";
-    int rc = pol_check_shape(fn, packed, self_dim, num_envs, num_agents, num_cylinders, io);
+    return pol_central_call("hns_policy_central_forward", false, packed, self_dim, num_envs, num_agents, num_cylinders, io, state, flags, seed, counter, stream);
+}
+
+size_t hns_policy_packed_central_agents_bytes(int32_t self_dim, int32_t num_agents) {
+    if (self_dim < 1 || self_dim > hns::kPolMaxSelf || num_agents < 1 || num_agents > HNS_MAX_AGENTS) return 0;
+    return (size_t)(num_agents * hns::pol_net_floats(self_dim) + hns::pol_central_floats(self_dim)) * sizeof(float);
+}
+
+int hns_policy_pack_central_agents(const hns_policy_net *actors, const hns_policy_net *critic, int32_t self_dim, int32_t num_agents, void *packed,
+                                   void *stream) {
+    const char *fn = "hns_policy_pack_central_agents";
+    if (self_dim < 1 || self_dim > hns::kPolMaxSelf) return hns_fail(fn, "self_dim must be in [1, " + std::to_string(hns::kPolMaxSelf) + "]");
+    if (num_agents < 1 || num_agents > HNS_MAX_AGENTS) return hns_fail(fn, "num_agents must be in [1, 7]");
+    if (!packed || !hns_aligned(packed, 16)) return hns_fail(fn, "packed image must be a 16-byte aligned device array");
+    hns::EncNet sa{};
+    hns::PolNets nets{};
+    int rc = pol_net(fn, actors, num_agents > 1, true, sa);
     if (rc != HNS_OK) return rc;
-    if (flags & ~(HNS_POLICY_DETERMINISTIC | HNS_POLICY_VALUE_ONLY)) return hns_fail(fn, "unknown flag");
-    const bool value_only = flags & HNS_POLICY_VALUE_ONLY, det = flags & HNS_POLICY_DETERMINISTIC;
-    if (!value_only) {                                            // the critic workgroups never read the observation
-        rc = pol_check_obs(fn, num_agents, io);
-        if (rc != HNS_OK) return rc;
-    }
-    if (!state || !state->state_drones || !state->cylinders || !hns_aligned(state->state_drones, 4) || !hns_aligned(state->cylinders, 4))
-        return hns_fail(fn, "state pointer missing or misaligned");
-    for (int k = 0; k < 2; ++k)
-        if (state->drones_stride[k] < 0 || state->cyl_stride[k] < 0) return hns_fail(fn, "negative stride");
-    rc = pol_check_outputs(fn, io, value_only, det, counter);
+    rc = pol_net(fn, critic, false, false, nets.n[num_agents]);
     if (rc != HNS_OK) return rc;
-    hns::PolArgs a{}, c{};
-    a.img = static_cast<const float *>(packed);
-    a.net_floats = hns::pol_net_floats(self_dim);
-    a.rows = num_envs * num_agents; a.A = num_agents; a.K = num_cylinders; a.D = self_dim;
-    c = a;
-    c.img = a.img + a.net_floats;
-    c.xs = state->state_drones; c.sse = state->drones_stride[0]; c.ssa = state->drones_stride[1];
-    c.xc = state->cylinders; c.sce = state->cyl_stride[0]; c.sct = state->cyl_stride[1];
-    c.rows = num_envs; c.value = io->value;
-    unsigned actor_tiles = 0;
-    if (!value_only) {
-        a.xs = io->obs_self; a.xo = io->obs_others; a.xc = io->obs_cylinders;
-        a.sse = io->self_stride[0]; a.ssa = io->self_stride[1];
-        a.soe = io->others_stride[0]; a.soa = io->others_stride[1]; a.sot = io->others_stride[2];
-        a.sce = io->cyl_stride[0]; a.sca = io->cyl_stride[1]; a.sct = io->cyl_stride[2];
-        a.eps = io->eps; a.counter = reinterpret_cast<const unsigned long long *>(counter); a.seed = seed;
-        a.action = io->action; a.loc = io->loc; a.logp = io->log_prob; a.deterministic = det;
-        actor_tiles = (unsigned)((a.rows + hns::kEncRows - 1) / hns::kEncRows);
-    }
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&hns::hns_policy_forward_central_kernel),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(hns::PolLds));
-    HNS_CHECK_HIP(attr);
-    const unsigned critic_tiles = (unsigned)((num_envs + hns::kEncRows - 1) / hns::kEncRows);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(hns::hns_policy_forward_central_kernel, dim3(actor_tiles + critic_tiles), dim3(hns::kEncThreads), sizeof(hns::PolLds), st, a, c,
-                       actor_tiles);
+    if (critic->embed_others_w || critic->embed_others_b) return hns_fail(fn, "the centralised critic has no state_others embedding");
+    for (int ag = 0; ag < num_agents; ++ag) nets.n[ag] = hns::enc_agent_slice(sa, self_dim, 4, ag);      // as hns_policy_pack_agents forms them
+    nets.n[num_agents].head_n = num_agents;                      // v_out = Linear(128, A)
+    hipLaunchKernelGGL(hns::hns_policy_pack_central_agents_kernel, dim3(256, (unsigned)num_agents + 1), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       nets, (int)self_dim, (int)num_agents, static_cast<float *>(packed));
     HNS_CHECK_HIP(hipGetLastError());
-    if (!value_only && !det && !io->eps) {
-        hipLaunchKernelGGL(hns::hns_policy_bump_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<unsigned long long *>(counter));
-        HNS_CHECK_HIP(hipGetLastError());
-    }
     return HNS_OK;
+}
+
+int hns_policy_central_forward_agents(const void *packed, int32_t self_dim, int64_t num_envs, int32_t num_agents, int32_t num_cylinders,
+                                      const hns_policy_io *io, const hns_policy_state *state, int32_t flags, uint64_t seed, uint64_t *counter,
+                                      void *stream) {
+    return pol_central_call("hns_policy_central_forward_agents", true, packed, self_dim, num_envs, num_agents, num_cylinders, io, state, flags, seed, counter,
+                            stream);
 }
 
 size_t hns_policy_packed_agents_bytes(int32_t self_dim, int32_t num_agents) {

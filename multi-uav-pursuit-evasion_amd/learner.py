@@ -31,6 +31,10 @@ agent): the actor step through rnn_train.update_actor_rnn_per_
 critic_train.update_critic_central on the stored state_drones, the bootstrap value from the last state, everything else DeviceLearner's.
 `DeviceLearner` keeps refusing that configuration.
 
+`PerAgentCentralCriticDeviceLearner` joins the two (share_actor: False with critic_input: state): the actor block is
+PerAgentDeviceLearner's and the critic block, the rollout's state and the bootstrap value are CentralCriticDeviceLearner's — both classes are its
+bases, so their method bodies are the ones that run.
+
 `DeviceLearner._ppo_loop` is the only PPO loop.  A variant overrides what differs and nothing else: the units a permutation draws from
 (`_units`), its update call for one index (`_actor_step`, `_critic_step`), its cached buffers (`_workspaces`), and its optimisers and tensors
 (`_make_actor_opt`, `_make_critic_opt`, `_network_tensors`: checkpoints, buckets and the broadcast are written once over them).
@@ -553,6 +557,53 @@ class CentralCriticDeviceLearner(DeviceLearner):
     def _critic_step(self, idx, obs, state_value, ret, rk, bucket=None, **kw):                      # (no group, so no bucket)
         return critic_train.update_critic_central(self.critic, rk["state_drones"], obs[2], state_value, ret, self.critic_opt, index=idx,
                                                   cfg=self.cfg, **kw)
+
+
+class PerAgentCentralCriticDeviceLearner(PerAgentDeviceLearner, CentralCriticDeviceLearner):
+    """MAPPOPolicy's training half with share_actor: False AND critic_input: state (one actor per agent under ONE centralised critic over the
+    joint state): the join of its two bases, whose method bodies run unchanged.  PerAgentDeviceLearner's: the actor's
+    optimiser and the actor step (actor_train.update_actor_per_agent over the 23 stacked tensors).  CentralCriticDeviceLearner's:
+    `_rollout_kwargs`, `train_rollout(..., state_drones, next_state_last)`, the bootstrap value and the critic step
+    (critic_train.update_critic_central over the critic's 20 tensors).  DeviceLearner's: train_op, the targets, the predictor, the info row,
+    state_dict / load_state_dict and the checkpoint (the stacked "actor_params" beside the central critic's names).  Its own: the pairing of
+    the two halves in `_network_tensors` and `_workspaces` (hns_actor_train_agents_workspace_bytes,
+    hns_critic_train_central_workspace_bytes).
+
+    actor: the STACKED actor's parameters; critic: the centralised critic's — live tensors, updated in place; device_policy: a
+    PerAgentCentralCriticDevicePolicy over the same tensors (built when None).  Refused before anything is built: group=
+    (NotImplementedError: there is no data-parallel form), a recurrent policy, a device_policy that is not both per-agent and central,
+    share_actor: True, critic_input: obs, and whatever the two bases' cfg checks refuse, with their exception types."""
+
+    def __init__(self, actor, critic, cfg, tp_net=None, value_normalizer=None, agent_name="drone", generator=None, device_policy=None, group=None):
+        if group is not None:
+            raise NotImplementedError("PerAgentCentralCriticDeviceLearner takes no group=: per-agent actors beside the centralised critic have no "
+                                      "data-parallel form")
+        if getattr(device_policy, "recurrent", False):
+            raise P.PolicyConfigError("PerAgentCentralCriticDeviceLearner updates the non-recurrent networks only: the centralised critic with "
+                                      "actor.rnn / critic.rnn is not implemented")
+        if device_policy is not None and not (getattr(device_policy, "per_agent", False) and getattr(device_policy, "central", False)):
+            raise P.PolicyConfigError("PerAgentCentralCriticDeviceLearner needs a PerAgentCentralCriticDevicePolicy (a shared actor beside the "
+                                      "centralised critic is CentralCriticDeviceLearner's, per-agent actors beside the critic on the observation "
+                                      "PerAgentDeviceLearner's)")
+        P.check_config_per_agent_central(cfg)
+        rest = P.cfg_without(cfg, "share_actor", "critic_input")     # what both halves' functions (and policy.check_config behind them) take
+        actor_train.actor_cfg_per_agent(rest)
+        critic_train.critic_cfg(rest, central=True)
+        self._configure(actor, critic, rest, tp_net, value_normalizer, agent_name, generator)
+        self._make_networks_state(device_policy, P.PerAgentCentralCriticDevicePolicy)
+
+    def _network_tensors(self):
+        """The 23 stacked tensors in the actor optimiser's order, and the centralised critic's 20."""
+        return list(actor_train.actor_parameters_per_agent(self.actor).values()), list(critic_train.central_critic_parameters(self.critic).values())
+
+    def _workspaces(self, xs, xc):
+        N, T, A, D = xs.shape
+        dev, K, lib = xs.device, int(xc.shape[3]), abi.load_library()
+        batch = N * T // self.num_minibatches
+        na, nc = lib.hns_actor_train_agents_workspace_bytes(batch * A, D, A, K), lib.hns_critic_train_central_workspace_bytes(batch, D, A, K)
+        if batch < 1 or na == 0 or nc == 0:
+            raise ValueError(f"shape outside the kernels' limits: {batch} env-steps per minibatch, self_dim {D}, {A} agents, {K} cylinders")
+        return self._workspace("actor", na, dev), self._workspace("critic", nc, dev)
 
 
 class RecurrentDeviceLearner(DeviceLearner):

@@ -35,6 +35,11 @@ for bit `RecurrentDevicePolicy`'s with agent a's slices.  Col
 `hns_policy_central_forward`: actor tiles of 32 (env, agent) rows and critic tiles of 32 envs in one launch, the actor's outputs bit for bit
 `DevicePolicy`'s.  The four classes above keep refusing that configuration.
 
+`PerAgentCentralCriticDevicePolicy` is share_actor: False AND critic_input: state — heterogeneous actors under one critic over the joint state,
+the canonical centralised-training / decentralised-execution setup — on `hns_policy_central_forward_agents`: per agent a range of actor tiles
+of 32 envs, then one range of critic tiles of 32 envs, in one launch; action, log_prob and loc are bit for bit `PerAgentDevicePolicy`'s and
+value bit for bit `CentralCriticDevicePolicy`'s.  The five classes above keep their refusals.
+
 Layout of this file, as the device side's (one tile body, three flags): the configuration checks and the parsers (`parse_parameters` and
 `split_rnn`, each with a `stacked` switch); ONE CPU restatement (`_restatement`: a GRU step or not, a stacked actor or not, the actor's half
 alone or not; `torch_forward` and `torch_forward_rnn` are its public forms); the random builders; `ENTRIES`, the eight C entries keyed
@@ -306,6 +311,19 @@ def check_config_central(cfg):
     check_config(cfg_without(cfg, "critic_input"))
 
 
+def check_config_per_agent_central(cfg):
+    """`check_config` for one actor per agent beside the centralised critic: both switches are accepted (a cfg that does not say is taken at
+    the class's word), share_actor: True and critic_input: obs are refused as the two checks above refuse them, and so is everything else
+    `check_config` refuses."""
+    if getter(cfg)("share_actor", False):
+        raise PolicyConfigError("share_actor: True with one actor per agent; the shared actor beside the centralised critic is "
+                                "CentralCriticDevicePolicy's")
+    if getter(cfg)("critic_input", "state") != "state":
+        raise PolicyConfigError(f"critic_input: {getter(cfg)('critic_input')} with the centralised critic; per-agent actors beside the critic on "
+                                "the observation are PerAgentDevicePolicy's")
+    check_config(cfg_without(cfg, "share_actor", "critic_input"))
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # torch restatement (CPU path): the reference's statements, modules/networks.py:125-163, :250-313, distributions.py:66-82, mappo.py:591-660
 def _encoder(p, xs, xo, xc):
@@ -403,17 +421,24 @@ def torch_forward_rnn(actor, critic, actor_rnn, critic_rnn, xs, xo, xc, actor_st
                                                deterministic, value_only, generator))
 
 
-def torch_forward_central(actor, critic, xs, xo, xc, state_drones, state_cylinders, eps=None, deterministic=False, value_only=False, generator=None):
+def torch_forward_central(actor, critic, xs, xo, xc, state_drones, state_cylinders, eps=None, deterministic=False, value_only=False, generator=None,
+                          stacked=False):
     """The CPU restatement of hns_policy_central_forward, any dtype: the shared actor as `torch_forward` runs it (xs [E, A, 1, D]) and the
     centralised critic in the reference's statements (Critic.forward with centralized=True, mappo.py:644-660): the encoder over the state —
     state_drones [E, A, D] and state_cylinders [E, K, 5] are SplitEmbedding's two keys, token 0 (drone 0) the query — and v_out, unflattened
-    to value [E, A, 1]."""
+    to value [E, A, 1].  stacked (hns_policy_central_forward_agents): `actor` is the stacked actor and runs as
+    `_restatement(stacked=True)` runs it — each agent's slice on the whole observation, keeping its own agent's rows."""
     value = F.linear(_encoder(critic, state_drones, None, state_cylinders), critic["head_w"], critic["head_b"]).unsqueeze(-1)
     if value_only:
         return PolicyOutput(None, None, value, None)
     if eps is None and not deterministic:
         eps = torch.randn((*xs.shape[:-2], ACTION_DIM), dtype=xs.dtype, device=xs.device, generator=generator)
-    action, log_prob, loc = _heads(actor, _encoder(actor, xs, xo, xc), eps, deterministic)
+    if stacked:
+        slices = [agent_slice(actor, a) for a in range(xs.shape[1])]
+        rows = [[t[:, a:a + 1] for t in _heads(p, _encoder(p, xs, xo, xc), eps, deterministic)] for a, p in enumerate(slices)]
+        action, log_prob, loc = (torch.cat(t, dim=1) for t in zip(*rows))
+    else:
+        action, log_prob, loc = _heads(actor, _encoder(actor, xs, xo, xc), eps, deterministic)
     return PolicyOutput(action, log_prob, value, loc)
 
 
@@ -528,7 +553,7 @@ class DevicePolicy:
     slices) and `recurrent` (`actor_rnn` / `critic_rnn`, a GRU behind each encoder).  The subclasses set them, parse their parameters and
     adapt the arguments of `forward`, `act` and `act_step` to `_pass`."""
     per_agent = recurrent = central = False
-    needs_state = False                                          # the collector hands ("agents", "state") to `forward` (CentralCriticDevicePolicy)
+    needs_state = False                                          # the collector hands ("agents", "state") to `forward` (the two central classes)
     actor_rnn = critic_rnn = None
 
     def __init__(self, actor_params, critic, cfg=None, device=None, seed=0, agent_name="drone"):
@@ -578,6 +603,8 @@ class DevicePolicy:
 
     # ---- packed images
     def _packed_bytes(self):
+        if self.per_agent and self.central:
+            return self._lib.hns_policy_packed_central_agents_bytes(self.self_dim, self.num_agents)
         if self.per_agent:
             return self._lib.hns_policy_packed_agents_bytes(self.self_dim, self.num_agents)
         if self.central:
@@ -622,7 +649,8 @@ class DevicePolicy:
         stamp = tuple((t.data_ptr(), t._version) for t in self._tensors())
         if not force and stamp == self._stamp:
             return
-        pack = "hns_policy_pack_agents" if self.per_agent else "hns_policy_pack_central" if self.central else "hns_policy_pack"
+        pack = ("hns_policy_pack_central_agents" if self.per_agent and self.central else "hns_policy_pack_agents" if self.per_agent else
+                "hns_policy_pack_central" if self.central else "hns_policy_pack")
         a, c = self._net(self.actor_p), self._net(self.critic_p)
         with torch.cuda.device(self.device):
             st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -639,7 +667,8 @@ class DevicePolicy:
         self.refresh()
         img = self.packed.view(torch.float32)
         if self.per_agent:
-            return img.view(self.num_agents + 1, -1)[:self.num_agents, P_SCALE:P_SCALE + ACTION_DIM]
+            net = self._lib.hns_policy_packed_bytes(self.self_dim) // 8                 # one network's image, in floats: the actors' come first
+            return img[:self.num_agents * net].view(self.num_agents, net)[:, P_SCALE:P_SCALE + ACTION_DIM]
         return img[P_SCALE:P_SCALE + ACTION_DIM]
 
     def _check(self, rc, what):
@@ -736,7 +765,7 @@ class DevicePolicy:
             if self.central and not act:
                 with torch.no_grad():                            # (a contiguous state: a strided view of the env's cylinders rounds differently on the CPU)
                     return (*torch_forward_central(self.actor_p, self.critic_p, xs.unsqueeze(2), xo, xc, sd.contiguous(), sc.contiguous(), eps,
-                                                   deterministic, value_only, self._generator), None, None)
+                                                   deterministic, value_only, self._generator, stacked=self.per_agent), None, None)
             with torch.no_grad():
                 action, log_prob, value, loc, new_a, new_c = _restatement(
                     self.actor_p, self.critic_p, xs.unsqueeze(2), xo, xc, self.actor_rnn, self.critic_rnn, ha, hc, is_init, eps,
@@ -787,7 +816,8 @@ class DevicePolicy:
         if not act:
             args += [(abi.HNS_POLICY_DETERMINISTIC if deterministic else 0) | (abi.HNS_POLICY_VALUE_ONLY if value_only else 0), self.seed,
                      self.counter.data_ptr()]
-        entry = "hns_policy_central_forward" if self.central and not act else ENTRIES[self.per_agent, self.recurrent, act]
+        entry = (("hns_policy_central_forward_agents" if self.per_agent else "hns_policy_central_forward") if self.central and not act else
+                 ENTRIES[self.per_agent, self.recurrent, act])
         with torch.cuda.device(dev):
             rc = getattr(self._lib, entry)(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         self._check(rc, entry)
@@ -994,3 +1024,28 @@ class CentralCriticDevicePolicy(DevicePolicy):
     def value(self, tensordict):
         """value_op: the critic's state_value [E, A, 1] from ("agents", "state")."""
         return self.forward(*self._obs(tensordict), *self._state_of(tensordict), value_only=True).value
+
+
+class PerAgentCentralCriticDevicePolicy(CentralCriticDevicePolicy):
+    """MAPPOPolicy with share_actor: False AND critic_input: state — one actor per pursuer on its own observation and ONE centralised critic
+    row per env over the state: heterogeneous actors under one critic, centralised training with decentralised execution — in one HIP launch
+    per call (`hns_policy_central_forward_agents`: per agent a range of actor tiles of 32 envs reading that agent's image, then the critic's
+    range of tiles of 32 envs).  DESIGN.md §7.21.
+
+    `PerAgentCentralCriticDevicePolicy(actor_params, critic)`: actor_params the STACKED actor as for PerAgentDevicePolicy (every leaf
+    [A, ...]), critic the centralised critic's 20 tensors as for CentralCriticDevicePolicy; v_out's rows must equal the stacked leading size.
+    `forward(obs_self, obs_others, obs_cylinders, state_drones, state_cylinders=None, ...)`, `__call__` and `value` are
+    CentralCriticDevicePolicy's; `act` (`hns_policy_act_agents`, which this image serves unchanged) and `scale` [A, 4] are
+    PerAgentDevicePolicy's.  action, log_prob and loc are bit for bit PerAgentDevicePolicy's for the same stacked actor and noise, value bit for
+    bit CentralCriticDevicePolicy's for the same critic and state.  Refused with PolicyConfigError before anything is built: share_actor:
+    True; critic_input: obs; an rnn; a tanh actor; actor tensors that are not stacked or whose leading sizes disagree; whatever
+    CentralCriticDevicePolicy refuses of the critic; v_out with another number of rows than there are actors."""
+    per_agent = True
+
+    def __init__(self, actor_params, critic, cfg=None, device=None, seed=0, agent_name="drone"):
+        check_config_per_agent_central(cfg)
+        actor_p, self.num_agents = parse_parameters_per_agent(actor_params, "actor")
+        critic_p, rows = parse_parameters_central(critic, "critic")
+        if rows != self.num_agents:
+            raise PolicyConfigError(f"critic: v_out has {rows} row(s) beside {self.num_agents} stacked actors (v_out is Linear(128, A) for A agents)")
+        self._setup(actor_p, critic_p, device, seed, agent_name)
